@@ -12,9 +12,14 @@ every preconditioned call, every coin-triggered extra self-conditioning forward,
 N > 1 without a torchrun environment: this process becomes a LAUNCHER -- before any GPU call it starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
 as a child process (one rank per GPU over RCCL), relays rank 0's JSON line and exits with the child's status.  Launched
-by torchrun (RANK/LOCAL_RANK/WORLD_SIZE set) it is a rank.  The W warm-up samples run on a short schedule
-(`--warmup-num-steps`, default 20: graph capture, workspace allocation and clocks settle within the first forwards);
-the K timed steps are full T-step samples.  Prints ONE JSON line on rank 0 with `roofline` and `cpu_baseline` objects.
+by torchrun (RANK/LOCAL_RANK/WORLD_SIZE set) it is a rank.  The W untimed warm-up steps are the same full T-step samples
+as the K timed ones (graph capture, workspace allocation and clocks settle in them), so every one of the W + K steps takes
+about `ms_per_step`; `--warmup-num-steps` opts into shorter warm-up samples.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`value`, `ms_per_step`, ...).
+`--full` adds what takes runs of its own: the decode tail (`tail`), the GEMM roofline from eager profiled forwards (`roofline`)
+and the oracle timed on the host cores (`cpu_baseline`, unless --no-cpu-baseline); without it those keys are null.
+`--dump-outputs DIR` writes the raw samples of the last timed step as DIR/adj.npy and DIR/node.npy (float32), see dump_outputs().
 """
 import argparse
 import json
@@ -38,7 +43,8 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=64, help="graphs per GPU per step (configs[1]: 64; configs[3]: 256)")
     ap.add_argument("--num-steps", type=int, default=1000, help="sampler steps T (BASELINE metric: 1000)")
-    ap.add_argument("--warmup-num-steps", type=int, default=20, help="sampler steps of the untimed warm-up samples")
+    ap.add_argument("--warmup-num-steps", type=int, default=None,
+                    help="sampler steps of the untimed warm-up samples (default: --num-steps, i.e. a warm-up step is a timed step)")
     ap.add_argument("--config", default="vg", choices=["vg", "coco", "tiny"])
     ap.add_argument("--valid", type=int, default=None, help="valid nodes per graph (VG: 30)")
     ap.add_argument("--no-graph", action="store_true")
@@ -47,12 +53,17 @@ def parse_args(argv=None):
                          "partial products of hi/mid/lo operand splits; bf16: opt-in bf16-MFMA GEMMs with fp32 accumulate")
     ap.add_argument("--solver", default="heun", choices=["heun", "euler"], help="configs[2] variant 3b: --solver euler --s-churn 0")
     ap.add_argument("--s-churn", type=float, default=40.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the decode tail, the GEMM roofline (eager profiled forwards) and the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the raw samples of the last one as DIR/adj.npy and DIR/node.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-budget-s", type=float, default=40.0, help="wall-clock bound of the cpu_baseline leg")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--rehearse-collectives", action="store_true",
                     help="with --gpus 1: create the RCCL process group anyway (world size 1) so that the barrier, the float64 "
-                         "max-over-ranks all-reduce and both all-gathers (fp32 raw, int16-as-bytes decoded) run through RCCL on one GPU")
+                         "max-over-ranks all-reduce and the all-gathers (fp32 raw; with --full also int16-as-bytes decoded) run through "
+                         "RCCL on one GPU")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU rehearsal of the multi-rank plumbing (launcher, rank env, gloo process group, barrier, max-over-ranks "
                          "timing, packed all-gather) with a stand-in step; no GPU, no product kernels, the value is meaningless")
@@ -116,6 +127,28 @@ def cpu_baseline(cfg, sd, T, valid, budget_s):
                       f"{nfe} network forwards of {B} graphs in {elapsed:.1f} s, scaled to {nfe_total} forwards per graph"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, out, cfg):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the raw generated samples of every gathered
+    graph, adj [G, C_adj, N, N] and node [G, N, C_node] in float32.  Should they exceed 64 MB, a fixed subset of whole graphs is
+    written instead (seeded, in graph order), so that two builds run with the same arguments write the same graphs."""
+    import numpy as np
+    import torch
+    from diffusesg_amd import dist as dsg_dist
+    rows = out.shape[0]
+    keep = max(1, (DUMP_LIMIT_BYTES - 4096) // (out.shape[1] * out.element_size()))   # (4 KB for the two .npy headers)
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        out = out[torch.from_numpy(idx).to(out.device)]
+    n = cfg.max_node_num
+    adj, node = dsg_dist.unpack_results(out.float().cpu(), cfg.c_adj, n, cfg.c_node)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "adj.npy"), np.ascontiguousarray(adj.numpy()))
+    np.save(os.path.join(dirname, "node.npy"), np.ascontiguousarray(node.numpy()))
+
+
 def worker(args):
     import ctypes as C
 
@@ -166,6 +199,7 @@ def worker(args):
     n = cfg.max_node_num
     valid = args.valid if args.valid is not None else {"vg": 30, "coco": 20, "tiny": 8}[args.config]
     T, B = args.num_steps, args.batch
+    warm_T = T if args.warmup_num_steps is None else max(1, min(T, args.warmup_num_steps))
     seed = dsg_dist.rank_seed(args.seed, rank)     # arg_parser.py:293-294: seed += rank
     np.random.seed(seed)                           # the coin stream (np.random.rand, precond.py:90) is part of the workload
 
@@ -191,7 +225,7 @@ def worker(args):
                    clip_samples_min=-1.0, clip_samples_max=1.0, clip_samples_scope="x_0", self_condition=cfg.self_condition,
                    dev=dev, use_graph=not args.no_graph)
         smp = NodeAdjEDMSamplerHip(num_steps=T, **skw)
-        smp_warm = NodeAdjEDMSamplerHip(num_steps=max(1, min(T, args.warmup_num_steps)), **skw)
+        smp_warm = smp if warm_T == T else NodeAdjEDMSamplerHip(num_steps=warm_T, **skw)
         flags = torch.from_numpy(weights.synth_flags(B, n, valid)).to(dev)
 
         def one_step(k, sampler):
@@ -251,15 +285,18 @@ def worker(args):
         mine = out[rank * B:(rank + 1) * B]
         other = out[((rank + 1) % world) * B:((rank + 1) % world + 1) * B]
         assert not torch.equal(mine, other), "two ranks produced identical graphs: seeds are not offset by rank"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, cfg)
 
     line = None
+    tail = None
     if selftest:
         if rank == 0:
             line = {"metric": "launcher self-test (no GPU work)", "value": world * B * args.steps / max(elapsed, 1e-9),
                     "unit": "stand-in steps/s", "n_gpus": world, "world_size": world_seen, "steps": args.steps,
                     "warmup": args.warmup, "selftest": True, "backend": "gloo" if world > 1 else None,
                     "gathered_rows": int(out.shape[0]), "per_rank": per_rank, "cpu_baseline": None}
-    else:
+    elif args.full:
         # The tail the reference pays after sampling (sampler_node_adj.py:194-345): decode the 'bits' samples, gather the
         # decoded graphs and bring them to the host.  Reported beside `value`, never inside it.
         from diffusesg_amd import io as dsg_io
@@ -280,74 +317,75 @@ def worker(args):
         value = graphs / elapsed
         f_fwd = spec.flops_per_forward(cfg)
         mode = h.precision_mode()     # what the handle actually ran (options or DSG_* environment defaults), not the CLI flag
-        # roofline of the dominant kernel (the GEMM): HIP events around every launch of eager forwards on the state the timed
-        # run left in the workspace (random-data clocks, not zeros)
-        ms, cnt, fl = (C.c_double * 5)(), (C.c_int64 * 5)(), (C.c_double * 5)()
-        gemm_ms = C.c_double(0.0)
-        iters = 3
-        st_ptr = torch.cuda.current_stream(dev).cuda_stream
-        h.check(h.L.dsg_profile_forward(h.raw, B, iters, ms, cnt, fl, C.byref(gemm_ms), C.c_void_p(st_ptr)), "dsg_profile_forward")
-        # avg_launch_ms: HIP events recorded on the launch stream around every GEMM launch (eager forwards).
-        # avg_launch_ms_inkernel: first-block-start -> last-block-end stamps (100 MHz constant clock) of back-to-back
-        # launches; consecutive kernels overlap at their tails, so this one reads a few % high.
-        # the dominant kernel class: the GEMM, except on the bf16 block pipeline, where a Swin block is two kernels (QKV + attention;
-        # proj + MLP) and the second one carries most of the time and of the FLOPs
-        bx_pipe = mode == "bf16" and bool(h.get_option("bf16_pipe")) and bool(h.get_option("bf16_proj_mlp")) and cnt[4] > 0
-        dk = 4 if bx_pipe else 0
-        gemm_avg_ms = ms[dk] / cnt[dk]
-        gemm_avg_ms_inkernel = gemm_ms.value / cnt[0] if cnt[0] else None
-        achieved = (fl[dk] / cnt[dk]) / (gemm_avg_ms * 1e-3) / 1e12
-        clock_ghz = float(h.L.dsg_profile_clock_ghz(h.raw))   # shader clock held during those GEMM launches (in-kernel stamps)
-        kinds = ["gemm", "window_attn", "row", "elementwise", "fused_blocks"]
-        breakdown = {kinds[i]: {"ms_per_forward": ms[i] / iters, "launches_per_forward": cnt[i] // iters,
-                                "tflops": (fl[i] / (ms[i] * 1e-3) / 1e12) if fl[i] > 0 and ms[i] > 0 else None} for i in range(5)}
-        # HBM traffic of that kernel: PMC counters cannot be read from inside this process; the per-launch figure comes from
-        # the committed rocprofv3 --pmc passes over this same command (tools/pmc_traffic.sh -> profiles/*/pmc_traffic.json)
-        traffic, traffic_src = None, None
-        prof_root = os.path.join(ROOT, "profiles")
-        # (file, kernel family, condition): the committed PMC passes exist for the headline workload and for configs[4]'s per-GPU share
-        mlp384 = "mlp384d_bx_kernel" if (bx_pipe and h.get_option("bf16_mlp") in (1, 6)) else "mlp384_bx_kernel"
-        pmc_sets = [("pmc_traffic.json", "gemm4_f32_kernel", args.config == "vg" and B == 64 and mode == "f32"),
-                    ("pmc_traffic_vg_B256.json", "gemm4_f32_kernel", args.config == "vg" and B == 256 and mode == "f32"),
-                    ("pmc_traffic_coco_bf16.json", (mlp384, "mlp_bx_kernel") if bx_pipe else "gemm_bx_kernel",
-                     args.config == "coco" and B == 512 and mode == "bf16")]
-        for rnd in sorted(os.listdir(prof_root), reverse=True) if os.path.isdir(prof_root) else []:
-            for fname, fam, cond in pmc_sets:
-                pj = os.path.join(prof_root, rnd, fname)
-                if cond and traffic is None and os.path.exists(pj):
-                    tj = json.load(open(pj))
-                    fams = [f for f in ((fam,) if isinstance(fam, str) else fam) if f in tj.get("kernels", {})]
-                    if fams and len(fams) == (1 if isinstance(fam, str) else len(fam)):
-                        n_l = sum(tj["kernels"][f]["launches"] for f in fams)
-                        traffic = sum(tj["kernels"][f]["hbm_bytes_per_launch"] * tj["kernels"][f]["launches"] for f in fams) / n_l
-                        traffic_src = f"profiles/{rnd}/{fname} (committed rocprofv3 --pmc passes of this command from an earlier run of this build's kernels, not this process)"
-        # peak of the pipe the dominant kernel runs on, in ALGORITHMIC (2*M*N*K) FLOP/s: the split kernel issues six bf16
-        # MFMA products per algorithmic product, so its ceiling is the bf16 dense peak / 6
-        bf16_kern = ("mlp384d_bx_kernel + mlp_bx_kernel (proj + MLP half of a Swin block; the class's brackets also hold the PatchEmbed and "
-                     "read-out launches, 2 of 20 on COCO)" if bx_pipe else
-                     ("gemm_bx_kernel" if (mode == "bf16" and h.get_option("bf16_pipe")) else "gemm_bf16_kernel"))
-        kern, peak = {"f32": ("gemm4_f32_kernel", PEAK_F32_MFMA_TFLOPS), "bf16": (bf16_kern, PEAK_BF16_MFMA_TFLOPS),
-                      "f32-split": ("gemm_split2_kernel", PEAK_BF16_MFMA_TFLOPS / 6.0)}[mode]
-        if mode != "f32":
-            gemm_avg_ms_inkernel = None
-        roofline = {"bound": "mfma", "kernel": kern, "achieved": achieved, "peak": peak,
-                    "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
-                    "avg_launch_ms": gemm_avg_ms, "avg_launch_ms_inkernel": gemm_avg_ms_inkernel,
-                    "flops_per_launch": fl[dk] / cnt[dk], "launches_per_forward": cnt[dk] // iters,
-                    "held_clock_ghz": clock_ghz if mode == "f32" else None,
-                    "clock_limited_peak": (clock_ghz * 1024 * 64 / 1e3) if (mode == "f32" and clock_ghz > 0) else None,
-                    "forward_breakdown": breakdown}
-        # whole-path achieved rate: graphs/s/GPU x forwards per graph x FLOPs per forward
-        roofline["whole_path_tflops"] = nfe * B * f_fwd / elapsed / 1e12
-        # against the peak of the pipe the mode's GEMMs run on (bf16 mode: most of the path's FLOPs are bf16-MFMA products; the
-        # fp32 PatchEmbed / read-out / heads are priced against that peak too, which only understates the fraction)
-        roofline["whole_path_frac"] = roofline["whole_path_tflops"] / peak
-        # cpu_baseline on rank 0 at every world size: the timed region is over, the other ranks are idle at the final barrier (the
-        # leg is bounded by --cpu-budget-s, well inside the process group's timeout)
-        cpu = None
-        if not args.no_cpu_baseline:
-            progress(f"cpu_baseline: timing the oracle on the host cores for up to {args.cpu_budget_s:.0f} s")
-            cpu = cpu_baseline(cfg, sd, T, valid, args.cpu_budget_s)
+        roofline = cpu = None
+        if args.full:
+            # roofline of the dominant kernel (the GEMM): HIP events around every launch of eager forwards on the state the timed
+            # run left in the workspace (random-data clocks, not zeros)
+            ms, cnt, fl = (C.c_double * 5)(), (C.c_int64 * 5)(), (C.c_double * 5)()
+            gemm_ms = C.c_double(0.0)
+            iters = 3
+            st_ptr = torch.cuda.current_stream(dev).cuda_stream
+            h.check(h.L.dsg_profile_forward(h.raw, B, iters, ms, cnt, fl, C.byref(gemm_ms), C.c_void_p(st_ptr)), "dsg_profile_forward")
+            # avg_launch_ms: HIP events recorded on the launch stream around every GEMM launch (eager forwards).
+            # avg_launch_ms_inkernel: first-block-start -> last-block-end stamps (100 MHz constant clock) of back-to-back
+            # launches; consecutive kernels overlap at their tails, so this one reads a few % high.
+            # the dominant kernel class: the GEMM, except on the bf16 block pipeline, where a Swin block is two kernels (QKV + attention;
+            # proj + MLP) and the second one carries most of the time and of the FLOPs
+            bx_pipe = mode == "bf16" and bool(h.get_option("bf16_pipe")) and bool(h.get_option("bf16_proj_mlp")) and cnt[4] > 0
+            dk = 4 if bx_pipe else 0
+            gemm_avg_ms = ms[dk] / cnt[dk]
+            gemm_avg_ms_inkernel = gemm_ms.value / cnt[0] if cnt[0] else None
+            achieved = (fl[dk] / cnt[dk]) / (gemm_avg_ms * 1e-3) / 1e12
+            clock_ghz = float(h.L.dsg_profile_clock_ghz(h.raw))   # shader clock held during those GEMM launches (in-kernel stamps)
+            kinds = ["gemm", "window_attn", "row", "elementwise", "fused_blocks"]
+            breakdown = {kinds[i]: {"ms_per_forward": ms[i] / iters, "launches_per_forward": cnt[i] // iters,
+                                    "tflops": (fl[i] / (ms[i] * 1e-3) / 1e12) if fl[i] > 0 and ms[i] > 0 else None} for i in range(5)}
+            # HBM traffic of that kernel: PMC counters cannot be read from inside this process; the per-launch figure comes from
+            # the committed rocprofv3 --pmc passes over this same command (tools/pmc_traffic.sh -> profiles/*/pmc_traffic.json)
+            traffic, traffic_src = None, None
+            prof_root = os.path.join(ROOT, "profiles")
+            # (file, kernel family, condition): the committed PMC passes exist for the headline workload and for configs[4]'s per-GPU share
+            mlp384 = "mlp384d_bx_kernel" if (bx_pipe and h.get_option("bf16_mlp") in (1, 6)) else "mlp384_bx_kernel"
+            pmc_sets = [("pmc_traffic.json", "gemm4_f32_kernel", args.config == "vg" and B == 64 and mode == "f32"),
+                        ("pmc_traffic_vg_B256.json", "gemm4_f32_kernel", args.config == "vg" and B == 256 and mode == "f32"),
+                        ("pmc_traffic_coco_bf16.json", (mlp384, "mlp_bx_kernel") if bx_pipe else "gemm_bx_kernel",
+                         args.config == "coco" and B == 512 and mode == "bf16")]
+            for rnd in sorted(os.listdir(prof_root), reverse=True) if os.path.isdir(prof_root) else []:
+                for fname, fam, cond in pmc_sets:
+                    pj = os.path.join(prof_root, rnd, fname)
+                    if cond and traffic is None and os.path.exists(pj):
+                        tj = json.load(open(pj))
+                        fams = [f for f in ((fam,) if isinstance(fam, str) else fam) if f in tj.get("kernels", {})]
+                        if fams and len(fams) == (1 if isinstance(fam, str) else len(fam)):
+                            n_l = sum(tj["kernels"][f]["launches"] for f in fams)
+                            traffic = sum(tj["kernels"][f]["hbm_bytes_per_launch"] * tj["kernels"][f]["launches"] for f in fams) / n_l
+                            traffic_src = f"profiles/{rnd}/{fname} (committed rocprofv3 --pmc passes of this command from an earlier run of this build's kernels, not this process)"
+            # peak of the pipe the dominant kernel runs on, in ALGORITHMIC (2*M*N*K) FLOP/s: the split kernel issues six bf16
+            # MFMA products per algorithmic product, so its ceiling is the bf16 dense peak / 6
+            bf16_kern = ("mlp384d_bx_kernel + mlp_bx_kernel (proj + MLP half of a Swin block; the class's brackets also hold the PatchEmbed and "
+                         "read-out launches, 2 of 20 on COCO)" if bx_pipe else
+                         ("gemm_bx_kernel" if (mode == "bf16" and h.get_option("bf16_pipe")) else "gemm_bf16_kernel"))
+            kern, peak = {"f32": ("gemm4_f32_kernel", PEAK_F32_MFMA_TFLOPS), "bf16": (bf16_kern, PEAK_BF16_MFMA_TFLOPS),
+                          "f32-split": ("gemm_split2_kernel", PEAK_BF16_MFMA_TFLOPS / 6.0)}[mode]
+            if mode != "f32":
+                gemm_avg_ms_inkernel = None
+            roofline = {"bound": "mfma", "kernel": kern, "achieved": achieved, "peak": peak,
+                        "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
+                        "avg_launch_ms": gemm_avg_ms, "avg_launch_ms_inkernel": gemm_avg_ms_inkernel,
+                        "flops_per_launch": fl[dk] / cnt[dk], "launches_per_forward": cnt[dk] // iters,
+                        "held_clock_ghz": clock_ghz if mode == "f32" else None,
+                        "clock_limited_peak": (clock_ghz * 1024 * 64 / 1e3) if (mode == "f32" and clock_ghz > 0) else None,
+                        "forward_breakdown": breakdown}
+            # whole-path achieved rate: graphs/s/GPU x forwards per graph x FLOPs per forward
+            roofline["whole_path_tflops"] = nfe * B * f_fwd / elapsed / 1e12
+            # against the peak of the pipe the mode's GEMMs run on (bf16 mode: most of the path's FLOPs are bf16-MFMA products; the
+            # fp32 PatchEmbed / read-out / heads are priced against that peak too, which only understates the fraction)
+            roofline["whole_path_frac"] = roofline["whole_path_tflops"] / peak
+            # cpu_baseline on rank 0 at every world size: the timed region is over, the other ranks are idle at the final barrier (the
+            # leg is bounded by --cpu-budget-s, well inside the process group's timeout)
+            if not args.no_cpu_baseline:
+                progress(f"cpu_baseline: timing the oracle on the host cores for up to {args.cpu_budget_s:.0f} s")
+                cpu = cpu_baseline(cfg, sd, T, valid, args.cpu_budget_s)
         # BASELINE.json's metric string for the configuration it is quoted on (VG shape: 30 valid nodes, T=1000); any other
         # workload is labelled plainly and described in config.workload
         metric_name = "scene-graphs/sec"
@@ -366,13 +404,14 @@ def worker(args):
             "config": {"workload": f"{args.config}-bits N={n} valid={valid} C_adj={cfg.c_adj} C_node={cfg.c_node} "
                                    f"T={T} {args.solver} S_churn={args.s_churn:g} self_cond={int(cfg.self_condition)}",
                        "batch_per_gpu": B, "global_batch": world * B, "num_steps": T,
-                       "warmup_num_steps": max(1, min(T, args.warmup_num_steps)),
+                       "warmup_num_steps": warm_T,
                        "net_forwards_per_step": nfe / args.steps, "gflop_per_forward_per_graph": f_fwd / 1e9,
                        "hip_graph": not args.no_graph, "precision_mode": mode,
                        "parallelism": f"batch-sharded x{world}, one all-gather", "process_group": "nccl (RCCL)" if use_pg else None},
             "roofline": roofline, "cpu_baseline": cpu, "per_rank": per_rank,
-            "tail": {"what": "on-GPU decode of the bits samples + packed int16 all-gather + D2H of the decoded graphs (once per step)",
-                     "ms": 1e3 * tail, "value_with_tail": graphs / (elapsed + args.steps * tail)},
+            "tail": None if tail is None else {
+                "what": "on-GPU decode of the bits samples + packed int16 all-gather + D2H of the decoded graphs (once per step)",
+                "ms": 1e3 * tail, "value_with_tail": graphs / (elapsed + args.steps * tail)},
         }
     if line is not None:
         sys.stdout.write(json.dumps(line) + "\n")

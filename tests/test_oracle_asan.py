@@ -43,7 +43,9 @@ def test_oracle_runs_clean_under_address_sanitizer():
     if not os.path.isabs(libasan) or not os.path.exists(libasan):
         pytest.skip("no libasan in this toolchain")
     subprocess.check_call(["make", "-C", os.path.join(REPO, "oracle"), "libdsgref_asan.so"], stdout=subprocess.DEVNULL)
-    env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=23",
+    # the sanitizer runtime must come first; whatever the environment already preloads stays
+    preload = " ".join(p for p in (libasan, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=23",
                DSGREF_LIB=os.path.join(REPO, "oracle", "libdsgref_asan.so"), PYTHONPATH=REPO, OMP_NUM_THREADS="2")
     r = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-3000:]

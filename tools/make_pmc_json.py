@@ -21,7 +21,7 @@ for tag, key in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
         if key == "fetch":
             fam[f]["launches"] += v["launches"]
 out = {"source": f"tools/pmc_traffic.sh: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --no-graph --num-steps 3 "
-                 f"--warmup 0 --no-cpu-baseline`, MI355X, round {rnd[1:]}",
+                 f"--warmup 0 --full --no-cpu-baseline`, MI355X, round {rnd[1:]}",
        "units": "bytes; counter values are KiB; FETCH_SIZE doubled (gfx950 reports 1/2 of 16-B/lane coalesced reads, MI355X_MICROARCH.md §HBM); "
                 "WRITE_SIZE as read (calibrated 1.0000 for 4-B/lane and 16-B/lane stores: profiles/r2/write_size_cal.txt)",
        "kernels": {}, "instantiations": {}}

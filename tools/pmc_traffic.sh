@@ -5,8 +5,8 @@ R=$GRAFT_REPO_ROOT
 RAW=${PMC_RAW:-pmc_traffic_raw.json}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_f /tmp/pmc_w
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_f -- python3 $R/bench.py --no-graph --num-steps 3 --warmup 0 --no-cpu-baseline $PMC_BENCH_ARGS > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_w -- python3 $R/bench.py --no-graph --num-steps 3 --warmup 0 --no-cpu-baseline $PMC_BENCH_ARGS > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_f -- python3 $R/bench.py --no-graph --num-steps 3 --warmup 0 --full --no-cpu-baseline $PMC_BENCH_ARGS > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_w -- python3 $R/bench.py --no-graph --num-steps 3 --warmup 0 --full --no-cpu-baseline $PMC_BENCH_ARGS > /dev/null 2>&1
 python3 - <<PY
 import csv, glob, json, collections
 out={}
