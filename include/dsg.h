@@ -367,6 +367,47 @@ int dsg_adam_step(int32_t n_tensors, float *const *params, float *const *grads, 
                   float *out_total_norm, void *stream);
 int dsg_ema_update(int32_t n_tensors, float *const *ema, const float *const *params, const int64_t *numel, float decay, void *stream);
 
+/* ---- Sample evaluation (no handle): the reference's SceneGraphEvaluator (R/evaluation/bbox_metrics.py), which
+ * sg_go_sampling (R/runner/sampler/sampler_node_adj.py:446-600) and R/helper/eval_sg_samples.py run on the CPU after sampling.
+ * Kernels: csrc/eval_kernels.hip; Python: diffusesg_amd/evaluate.py (SceneGraphEvaluatorHip); pinned by tests/golden/eval_metrics.npz.
+ * Device pointers, caller's stream; all float64 sums run in a fixed order (repeated calls are bit-identical).
+ *
+ * Bounding-box F1 matrix (compute_bbox_f1 <-> measure_two_sets_of_bboxes, bbox_metrics.py:64-115):
+ *   boxes [S, N, 4] fp32 x1 y1 x2 y2, classes [S, N] int32, flags [S, N] uint8.  A box counts when its flag is set and
+ *   x1 >= 0, y1 >= 0, x2 > 0, y2 > 0 and 0 <= class < n_classes.  Generated and reference sets share N (pad with flag 0).
+ *   QUIRK kept from the reference: each box is its own "image" named after its NODE INDEX (imageName = str(i)), so the generated
+ *   box of node i can only match the reference box of node i, and only within one class; a pair of scenes is not matched up to a
+ *   permutation of its nodes.  IoU is Pascal VOC's with "+1" areas, float32 op by op.
+ *   weights: [W, n_classes] float64 class-weight table (W <= 8), or NULL for the unweighted mean (W must be 1 then); each pair
+ *   normalises them over the union of both scenes' classes (a zero sum there gives NaN, as in the reference).
+ * dsg_eval_bbox_prep: once per set, into `prep` (device, dsg_eval_bbox_prep_bytes(S, N, W) bytes); the same weights as the F1 call.
+ * dsg_eval_bbox_f1: out[x - x0][y - y0][w] (float64, contiguous [x1-x0, y1-y0, W]) for generated scenes [x0, x1) x reference
+ *   scenes [y0, y1); iou_thresholds: HOST array of n_iou (1..16) float64 thresholds (the reference's np.linspace(0.05, 0.5, 10)).
+ *   N <= 255, n_classes <= 192. */
+size_t dsg_eval_bbox_prep_bytes(int32_t S, int32_t N, int32_t W);
+int dsg_eval_bbox_prep(int32_t S, int32_t N, int32_t n_classes, const float *boxes, const int32_t *classes, const uint8_t *flags,
+                       int32_t W, const double *weights, void *prep, void *stream);
+int dsg_eval_bbox_f1(const void *gen_prep, int32_t X, const void *ref_prep, int32_t Y, int32_t N, int32_t n_classes, int32_t W,
+                     const double *weights, int32_t n_iou, const double *iou_thresholds, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                     double *out, void *stream);
+/* Histograms for the Gaussian MMDs, written feature-major: hist[k * ld + b] (ld >= B), normalised by their sums as compute_mmd
+ * does (mmd.py:152-153; a zero sum leaves the zeros), and sums[b] = the raw count.
+ * dsg_eval_type_hist, edges = 0: node types 0..K-1 of the flagged nodes, types [B, N] (_get_node_type_hist, bbox_metrics.py:181-195),
+ *   K rows.  edges = 1: edge types 1..K-1 over flagged x flagged entries (diagonal included), types [B, N, N]
+ *   (_get_edge_type_hist, :197-216), K-1 rows; the caller drops graphs whose sum is 0.  A type equal to K counts as K-1
+ *   (torch.histogram's closed last bin).  The float32 counts are normalised in float32, as the reference's are.  K <= 1024.
+ * dsg_eval_degree_hist: adj [B, N, N] fp32; edge where adj[i,j] != 0 or adj[j,i] != 0, i != j; isolated nodes dropped, a graph
+ *   without edges is one node of degree 0 (adjs_to_graphs + nx.degree_histogram, stats.py:23-60, 180-194); N rows (zero padding
+ *   beyond the largest degree changes no distance).  N <= 1024.
+ * dsg_eval_hist_mmd: Gaussian kernel exp(-|a-b|^2 / 2) in float64 (mmd.py:70-84): out[0] = disc(ref,ref) + disc(gen,gen)
+ *   - 2 disc(ref,gen), out[1..3] = the three discs (means of the kernel over all pairs); ref [L][ld_ref], gen [L][ld_gen]
+ *   (n_ref, n_gen >= 1, L <= 1024); ws: device scratch of 2 * n_ref + n_gen doubles. */
+int dsg_eval_type_hist(int32_t B, int32_t N, int32_t K, int32_t edges, const int32_t *types, const uint8_t *flags, double *hist,
+                       int32_t ld, double *sums, void *stream);
+int dsg_eval_degree_hist(int32_t B, int32_t N, const float *adj, double *hist, int32_t ld, double *sums, void *stream);
+int dsg_eval_hist_mmd(int32_t n_ref, const double *ref, int32_t ld_ref, int32_t n_gen, const double *gen, int32_t ld_gen, int32_t L,
+                      double *ws, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
