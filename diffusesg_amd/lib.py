@@ -17,6 +17,7 @@ EXPORTS = [
     "dsg_sigma_schedule", "dsg_debug_tap", "dsg_debug_clear_taps", "dsg_decode_bits", "dsg_decode", "dsg_profile_forward", "dsg_set_option",
     "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
+    "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
 ]
 
 
@@ -133,6 +134,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_eval_type_hist.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
     L.dsg_eval_degree_hist.argtypes = [i32, i32, vp, vp, i32, vp, vp]
     L.dsg_eval_hist_mmd.argtypes = [i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]
+    L.dsg_sgstat_triplet_counts.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.dsg_sgstat_layout.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp]
+    L.dsg_sgstat_f1_rowstats.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -408,6 +408,37 @@ int dsg_eval_degree_hist(int32_t B, int32_t N, const float *adj, double *hist, i
 int dsg_eval_hist_mmd(int32_t n_ref, const double *ref, int32_t ld_ref, int32_t n_gen, const double *gen, int32_t ld_gen, int32_t L,
                       double *ws, double *out, void *stream);
 
+/* ---- Scene-graph statistics (no handle): what is left of the evaluation block of sg_go_sampling
+ * (R/runner/sampler/sampler_node_adj.py:445-552) after the pairwise metrics above -- the triplet histogram of
+ * compute_triplet_tv_dist, the per-layout metrics of compute_bbox_ioa and the row statistics the F1 matrix is reduced to.
+ * Kernels: csrc/sgstat_kernels.hip; Python: diffusesg_amd/evaluate.py (SceneGraphEvaluatorHipFull, evaluate_samples); pinned by
+ * tests/golden/eval_full.npz.  Device pointers, caller's stream, DSG_ERR_INVALID for a bad argument instead of a launch.  Integer
+ * counts use integer atomics, float64 sums run in a fixed order: repeated calls are bit-identical.
+ *
+ * Triplet counts (_get_triplet_type_hist, bbox_metrics.py:215-268, summed over the graphs): edge_types [B, N, N] and node_types
+ *   [B, N] int32.  Every entry with edge_types[b,i,j] != 0 is the triplet (node_types[b,i], node_types[b,j], edge_types[b,i,j]).
+ *   QUIRKS kept from the reference: node flags are not consulted (it ignores its node_flags argument) and a diagonal entry counts.
+ *   sorted_keys: the n_keys allowed triplets packed as subject << 42 | object << 21 | predicate (21 bits each), ascending;
+ *   key_pos[k]: position of sorted key k in the caller's (dictionary) order.  counts [n_keys] int64 in that order and novel [1]
+ *   int64 (triplets not in the table) are zeroed on the stream and then filled.  A value outside [0, 2^21) never matches a key
+ *   (the Python wrapper refuses it beforehand).  n_keys may be 0 (everything is novel).
+ * Layout metrics (R/evaluation/blt_utils.py through compute_bbox_ioa, bbox_metrics.py:443-483): boxes [B, N, 4] fp32 x1 y1 x2 y2,
+ *   flags [B, N] uint8, canvas_size 1..64 (the reference passes 32), N <= 255.  values [4][B] float64 and valid [4][B] uint8
+ *   (0 where the reference returns None; the value is 0 then), metric order: 0 IoU (mean of the positive pair IoUs; the IoU is 0
+ *   where |union| <= 1e-8), 1 perceptual IoU (pixels covered more than once / pixels covered on the canvas, coordinates scaled
+ *   in float32 and rounded half to even), 2 overlap (sum of the positive intersection areas), 3 alignment (sum over the boxes of
+ *   the smallest left / centre / right distance to another box).  Pair terms are float32 op by op as in NumPy, summed in float64
+ *   (the reference sums IoU and overlap in float32).
+ * F1 row statistics: blk [rows, Y, W] float64 as the bbox F1 entry writes it; row_max, row_mean, row_median [rows, W] float64 and
+ *   row_argmax [rows, W] int32 over the Y axis: the exact median (np.median), the first index of the maximum (np.argmax); a row
+ *   holding a NaN gives NaN three times and the index of its first NaN.  Y <= 16384 (one row in LDS), W <= 8. */
+int dsg_sgstat_triplet_counts(int32_t B, int32_t N, const int32_t *edge_types, const int32_t *node_types, int32_t n_keys,
+                              const int64_t *sorted_keys, const int32_t *key_pos, int64_t *counts, int64_t *novel, void *stream);
+int dsg_sgstat_layout(int32_t B, int32_t N, const float *boxes, const uint8_t *flags, int32_t canvas_size, double *values,
+                      uint8_t *valid, void *stream);
+int dsg_sgstat_f1_rowstats(int32_t rows, int32_t Y, int32_t W, const double *blk, double *row_max, double *row_mean,
+                           double *row_median, int32_t *row_argmax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,11 +6,14 @@ Reports only, gates nothing.
     SceneGraphEvaluatorHip.compute_bbox_f1 call (prep, kernel, copy of the float64 matrix to the host), for the weighted call of
     sg_go_sampling (three class-weight vectors, 150 VG-like classes) and its "no node type" call (one class, no weights).
   * node-type, edge-type and node-degree MMD: the whole call each.
+  * the rest of sg_go_sampling's evaluation (SceneGraphEvaluatorHipFull): the whole calls of compute_bbox_ioa (one metric, and
+    the four from one launch), compute_triplet_tv_dist (--triplet-keys random keys over 150 node types x 50 predicates),
+    compute_bbox_f1_stats (weighted and "no node type"), and evaluate_samples (the whole block from device tensors).
 
 Inputs: VG-like scenes (N = 62) from a fixed seed: references random, generated ones perturbed copies of random references.
 --classes-used K draws the classes from K of the 150 (fewer: more same-class boxes at the same node, i.e. more IoUs per pair).
 
-Usage:  python tools/eval_bench.py [--x 4096] [--y 4096] [--reps 3] [--classes-used 150]
+Usage:  python tools/eval_bench.py [--x 4096] [--y 4096] [--reps 3] [--classes-used 150] [--triplet-keys 20000]
 """
 import argparse
 import ctypes as C
@@ -26,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffusesg_amd import lib                                                          # noqa: E402
 from diffusesg_amd import evaluate as E                                                # noqa: E402
 from diffusesg_amd.evaluate import SceneGraphEvaluatorHip as SGE, cxcywh_to_xyxy       # noqa: E402
+from diffusesg_amd.evaluate import SceneGraphEvaluatorHipFull as SGF, evaluate_samples  # noqa: E402
 
 
 def scenes(rng, X, Y, N, n_cls, dev, used):
@@ -58,6 +62,7 @@ def main():
     ap.add_argument("--y", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--classes-used", type=int, default=150, help="classes the scenes draw from (fewer: more same-class matches per pair)")
+    ap.add_argument("--triplet-keys", type=int, default=20000, help="keys of the triplet dictionary")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "eval_bench needs the GPU"
     dev = torch.device("cuda:0")
@@ -108,6 +113,25 @@ def main():
     res["mmd_node_type_s"], _ = timed(lambda: SGE.compute_node_type_mmd(a[1], a[4], a[2], a[5], n_cls, ["gaussian"]), reps)
     res["mmd_edge_type_s"], _ = timed(lambda: SGE.compute_edge_type_mmd(adj_g, adj_r, a[2], a[5], Ke, ["gaussian"]), reps)
     res["mmd_degree_s"], _ = timed(lambda: SGE.compute_node_degree_mmd(adj_g, adj_r, ["gaussian"]), reps)
+
+    # the rest of the evaluation block: whole calls
+    for metric in ("vanilla_iou", "perceptual_iou", "overlap", "alignment"):
+        res[f"ioa_{metric}_s"], _ = timed(lambda: SGF.compute_bbox_ioa(a[0], a[2], canvas_size=32, return_mean=True, **{"flag_" + metric: True}), reps)
+    res["ioa_four_metrics_s"], _ = timed(lambda: E.layout_metrics(a[0], a[2], 32, check_perceptual=True), reps)
+    n_pred = Ke - 1
+    ids = rng.choice(n_cls * n_cls * n_pred, args.triplet_keys, replace=False)
+    freq = rng.integers(1, 500, args.triplet_keys).astype(np.float64)
+    keys = zip((ids // (n_cls * n_pred)).tolist(), (ids // n_pred % n_cls).tolist(), (ids % n_pred + 1).tolist())
+    triplet_dict = dict(zip(keys, (freq / freq.sum()).tolist()))
+    to_count = list(triplet_dict.keys())[:1000]
+    res["triplet_keys"] = len(triplet_dict)
+    res["triplet_tv_s"], _ = timed(lambda: SGF.compute_triplet_tv_dist(adj_g, a[1], a[2], triplet_dict, to_count), reps)
+    res["triplet_novelty"] = float(SGF.compute_triplet_tv_dist(adj_g, a[1], a[2], triplet_dict, to_count)[3])
+    res["f1_stats_weighted_s"], _ = timed(lambda: SGF.compute_bbox_f1_stats(*a, w), reps)
+    res["f1_stats_no_node_type_s"], _ = timed(lambda: SGF.compute_bbox_f1_stats(a[0], ones_g, a[2], a[3], ones_r, a[5], None), reps)
+    to_cxcywh = lambda b: torch.cat([(b[..., :2] + b[..., 2:]) / 2, b[..., 2:] - b[..., :2]], -1)
+    res["evaluate_samples_s"], _ = timed(lambda: evaluate_samples(adj_g, a[1], to_cxcywh(a[0]), a[2], adj_r, a[4], to_cxcywh(a[3]), a[5], n_cls,
+                                                                  Ke, triplet_dict, triplet_dict, to_count, w[1], w[2]), reps)
     print(json.dumps(res))
 
 
