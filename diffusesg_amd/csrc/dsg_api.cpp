@@ -94,9 +94,27 @@ struct Workspace {
     RunCtl *ctl = nullptr;
     std::map<int, std::pair<hipGraphExec_t, int>> step_graphs;   // key -> (exec, network forwards inside)
     long plan_gen = -1;   // h->plan_gen this workspace's launch plan was last validated against (validate_plan)
+    // masked-token pruning: the need lists derived from `flags` whenever they are staged (stage_flags), at fixed addresses -- captured
+    // graphs read them -- and this batch size's list offsets; cnt [n_lists], cnt_ps [B][n_lists] scratch of the list kernel
+    int *need_lists = nullptr, *need_cnt = nullptr, *need_cnt_ps = nullptr;
+    size_t need_ints = 0;
+    NeedPlan need;
 };
 
 struct Tap { std::string name; float *dst; int64_t cap; };
+
+// Masked-token pruning (option "prune_masked"): which need list (kernels.h: NeedPlan) every up-path launch takes.  Built once per
+// handle from the up path's geometry (build_prune_plan); -1 = no list, the launch computes everything as before.
+struct PruneRole { int kind, res, shift, stage, block, list; };   // kind 0 run list / 1 window list; block >= 0: a Swin block of up stage
+                                                                  // `stage`; -1: its post_linear (fine rows); -2: its pre_linear / breakup_ln (coarse rows)
+struct PrunePlan {
+    bool built = false;
+    NeedPlan np;                                                     // list_off is filled per workspace (it depends on the batch size)
+    int items[NEED_MAX_LISTS] = {};                                  // entries of each list per sample when nothing is masked
+    std::vector<int> rows[DSG_MAX_LAYERS], wins[DSG_MAX_LAYERS];     // per up block: run list of its proj / MLP rows, window list of its attention
+    int fine[DSG_MAX_LAYERS], coarse[DSG_MAX_LAYERS];                // per up stage's PatchBreakup: post_linear rows, pre_linear / breakup_ln rows
+    std::vector<PruneRole> roles;                                    // the same assignment as a flat table (dsg_debug_need_lists)
+};
 
 }  // namespace
 
@@ -131,6 +149,10 @@ struct dsg_handle_s {
     // kernel-selection options (dsg_set_option); defaults may be overridden once by DSG_* environment variables
     bool opt_fused_attn = true, opt_fused_mlp = true, opt_fused_readout = true, opt_fused_pe = true;
     bool opt_fused_merge_small = false;   // also fuse PatchMerging below the size where it pays (tests force it on)
+    bool opt_prune_masked = true;     // up path: skip rows / windows that only feed masked (padded) tokens (prune_on below)
+    PrunePlan prune;
+    int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
+    std::vector<int> prof_list;
     bool opt_fused_merge = true;      // PatchMerging: gather + LayerNorm(4C) inside the reduction GEMM's A path (no merge_ln kernel)
     bool opt_loop_graph = true;       // capture whole step bodies of the reverse loop (0: only the network forward is a graph)
     bool opt_fused_qkv_attn = true;   // QKV projection + 64-token window attention in one kernel (q, k, v never reach HBM)
@@ -212,6 +234,8 @@ enum ProfKind { PK_GEMM = 0, PK_ATTN = 1, PK_ROW = 2, PK_ELEM = 3, PK_FUSED = 4,
 struct ProfScope {
     dsg_handle h; hipStream_t s;
     ProfScope(dsg_handle h_, hipStream_t s_, int kind, double flops, const char *tag = nullptr) : h(h_), s(s_) {
+        const int need_list = h->prof_next_list;
+        h->prof_next_list = -1;
         if (!h->prof_on) return;
         while (h->prof_events.size() < h->prof_used + 2) {
             hipEvent_t e;
@@ -219,6 +243,7 @@ struct ProfScope {
             h->prof_events.push_back(e);
         }
         h->prof_kind.push_back(kind);
+        h->prof_list.push_back(need_list);
         h->prof_flops.push_back(flops);
         h->prof_tag.push_back(tag ? tag : "");
         (void)hipEventRecord(h->prof_events[h->prof_used], s);
@@ -636,6 +661,7 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     h->opt_fused_qkv_attn = env_on("DSG_FUSED_QKV_ATTN", true);
     h->opt_loop_graph = env_on("DSG_LOOP_GRAPH", true);
     h->opt_fused_merge = env_on("DSG_FUSED_MERGE", true);
+    h->opt_prune_masked = env_on("DSG_PRUNE_MASKED", true);
     if (getenv("DSG_FUSED_MLP_MAXC")) h->opt_fused_mlp_maxc = atoi(getenv("DSG_FUSED_MLP_MAXC"));
     h->opt_gemm_bf16 = env_on("DSG_GEMM_BF16", false);
     h->opt_bf16_pipe = env_on("DSG_BF16_PIPE", true);
@@ -734,6 +760,7 @@ int dsg_finalize_weights(dsg_handle h) {
     for (int i = 0; i < L; i++)
         for (int j = 0; j < c.depths[L - 1 - i]; j++)
             h->up[i].push_back(mk("up_layers." + std::to_string(i) + ".blocks." + std::to_string(j), L - 1 - i, j));
+    h->prune.built = false;
     h->aff_n = off;
     void *p;
     if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * (size_t)off * NOISE_EMB)) return rc;
@@ -941,6 +968,7 @@ size_t per_sample_floats(dsg_handle h, std::vector<size_t> *parts = nullptr) {
 }
 
 int validate_plan(dsg_handle h, Workspace *w);
+const PrunePlan &prune_plan(dsg_handle h);
 int get_workspace(dsg_handle h, int B, Workspace **out) {
     auto it = h->ws.find(B);
     if (it != h->ws.end()) { *out = it->second.get(); return validate_plan(h, *out); }
@@ -978,6 +1006,23 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
     w->has_sc = (int *)q;
     if (int rc = dev_alloc(h, w->allocs, &q, sizeof(RunCtl))) return rc;
     w->ctl = (RunCtl *)q;
+    // masked-token pruning leaves the rows nobody reads untouched: they must never hold anything but finite numbers
+    HIP_TRY(h, hipMemset(w->x, 0, sizeof(float) * (size_t)B * T0 * E));
+    HIP_TRY(h, hipMemset(w->y, 0, sizeof(float) * (size_t)B * T0 * E));
+    HIP_TRY(h, hipMemset(w->att, 0, sizeof(float) * (size_t)B * T0 * E));
+    HIP_TRY(h, hipMemset(w->hid, 0, sizeof(float) * (size_t)B * h->cfg.mlp_ratio * T0 * E));
+    HIP_TRY(h, hipMemset(w->stats, 0, sizeof(float) * (size_t)B * 2 * T0));
+    w->need = prune_plan(h).np;
+    if (w->need.n_lists > 0) {
+        const int nl = w->need.n_lists;
+        size_t off = 0;
+        for (int k = 0; k < nl; k++) { w->need.list_off[k] = (int)off; off += (size_t)B * prune_plan(h).items[k] + 16; }
+        w->need_ints = off + nl + (size_t)B * nl;
+        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(int) * w->need_ints)) return rc;
+        HIP_TRY(h, hipMemset(q, 0, sizeof(int) * w->need_ints));   // counts of 0 until the first flags are staged
+        w->need_lists = (int *)q; w->need_cnt = w->need_lists + off; w->need_cnt_ps = w->need_cnt + nl;
+        w->bytes += sizeof(int) * w->need_ints;
+    }
     *out = w.get();
     h->ws[B] = std::move(w);
     return validate_plan(h, *out);
@@ -1009,6 +1054,73 @@ bool rowstats_on(dsg_handle h) { return h->opt_fused_rowstats && !h->opt_gemm_sp
 // does block `nb` take its input pre-modulated?  Generic blocks also read the LN1 partials the producer leaves; the C = 96 fused
 // attention kernel only skips its own modulate+SiLU (twice: prologue and shortcut) and keeps computing LN1 itself.
 bool wants_premod(dsg_handle h, const BlockPlan *nb) { return nb && rowstats_on(h); }
+
+// ---- masked-token pruning ------------------------------------------------------------------------------------------------
+// DiffuseSG.forward masks all it returns with node_flags (diffusesg.py:806-825), window attention does not (:108-139): the down
+// path and the coarsest level need every token, but on the way back up a token is needed only if it shares a window with a needed
+// token of the next stage.  The plan below walks the up path backwards from the read-out and gives every launch the list of 8-row
+// runs (or of windows) it has to compute; the walk stops at the first block whose need is structurally everything (one window, or
+// a shifted partition on a 2 x 2 window grid): it and all launches in front of it run as before.  Rows nobody reads are left
+// STALE in w->x / y / hid / att / stats, so every final mask must be a select (fused_readout96_kernel), never a product.
+void build_prune_plan(dsg_handle h) {
+    PrunePlan &P = h->prune;
+    P = PrunePlan();
+    P.built = true;
+    const int L = h->L, N = h->N;
+    for (int i = 0; i < DSG_MAX_LAYERS; i++) { P.fine[i] = P.coarse[i] = -1; }
+    for (int i = 0; i < L; i++) { P.rows[i].assign(h->up[i].size(), -1); P.wins[i].assign(h->up[i].size(), -1); }
+    if (N % 8 != 0 || N * N / 8 > NEED_MAX_RUNS) return;
+    for (int i = 0; i < L; i++)
+        for (auto &b : h->up[i]) if (b.ws != 8 || b.res % 8 != 0) return;   // 10 x 10 windows (COCO): not covered
+    NeedPlan np;
+    PrunePlan Q = P;
+    bool overflow = false, stop = false;
+    int cur = -1;   // list that holds the current set, -1: not emitted yet
+    auto new_list = [&](int items) { if (np.n_lists >= NEED_MAX_LISTS) { overflow = true; return -1; } Q.items[np.n_lists] = items; return np.n_lists++; };
+    auto push = [&](NeedOp op) { if (np.n_ops >= NEED_MAX_OPS) overflow = true; else np.op[np.n_ops++] = op; };
+    auto emit = [&](int res) { if (cur < 0) { cur = new_list(res * res / 8); push(NeedOp{NEED_EMIT, res, 0, cur}); } return cur; };
+    for (int i = L - 1; i >= 0 && !stop; i--) {
+        const int res = N >> (L - 1 - i);
+        for (int j = (int)h->up[i].size() - 1; j >= 0; j--) {
+            const BlockPlan &b = h->up[i][j];
+            Q.rows[i][j] = emit(res);
+            Q.roles.push_back(PruneRole{0, res, 0, i, j, Q.rows[i][j]});
+            const int nwr = res / 8;
+            if (nwr == 1 || (b.shift > 0 && nwr == 2)) { stop = true; break; }   // its attention needs everything
+            Q.wins[i][j] = new_list(nwr * nwr);
+            push(NeedOp{NEED_WINDOWS, res, b.shift, Q.wins[i][j]});
+            Q.roles.push_back(PruneRole{1, res, b.shift, i, j, Q.wins[i][j]});
+            cur = -1;
+        }
+        if (stop || i == 0 || res % 16 != 0) break;
+        Q.fine[i] = emit(res);
+        Q.roles.push_back(PruneRole{0, res, 0, i, -1, Q.fine[i]});
+        push(NeedOp{NEED_PARENT, res, 0, -1});
+        cur = -1;
+        Q.coarse[i] = emit(res / 2);
+        Q.roles.push_back(PruneRole{0, res / 2, 0, i, -2, Q.coarse[i]});
+    }
+    if (overflow) return;
+    P = Q;
+    P.np = np;
+}
+const PrunePlan &prune_plan(dsg_handle h) { if (!h->prune.built) build_prune_plan(h); return h->prune; }
+// Decided at plan time.  Off with debug taps (they return whole tensors: the same rule as rowstats_on), in the split / bf16 modes,
+// and whenever a launch of the up path is not one of the kernels that take a list.
+bool prune_opts_on(dsg_handle h) {
+    return h->opt_prune_masked && h->taps.empty() && !h->opt_gemm_split && !h->opt_gemm_bf16 && rowstats_on(h) && h->opt_fused_qkv_attn &&
+           h->opt_fused_readout && h->ro_fap && prune_plan(h).np.n_lists > 0;
+}
+bool prune_on(dsg_handle h, const Workspace *w) {
+    // (the row-mapped GEMM addresses whole tensors through one buffer descriptor: the widest one must stay below 2 GiB)
+    return w->need_lists && prune_opts_on(h) && (size_t)w->B * h->N * h->N * h->E * h->cfg.mlp_ratio * sizeof(float) < 0x7fffffffull;
+}
+struct NeedRef { const int *list = nullptr, *cnt = nullptr; int id = -1; };
+NeedRef need_ref(dsg_handle h, const Workspace *w, int id) {
+    if (id < 0 || !prune_on(h, w)) return NeedRef();
+    return NeedRef{w->need_lists + w->need.list_off[id], w->need_cnt + id, id};
+}
+struct BlockNeed { NeedRef rows, wins; };
 // attach "modulate for block nb + row statistics" to the GEMM that writes nb's input (M rows = B * T tokens of nb's level)
 void attach_premod(dsg_handle h, Workspace *w, GemmArgs &g, const BlockPlan *nb) {
     if (!wants_premod(h, nb)) return;
@@ -1022,7 +1134,8 @@ void attach_premod(dsg_handle h, Workspace *w, GemmArgs &g, const BlockPlan *nb)
 // reads them).  Returns what the producer left behind: .premod -- next's input is pre-modulated (+ its LN1 partials);
 // .stats_parts -- > 0: partials of the un-modulated output rows with that many pairs per row.
 struct BlockOut { bool premod; int stats_parts; };
-BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, const BlockPlan *next, bool want_stats, hipStream_t s) {
+BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, const BlockPlan *next, bool want_stats, hipStream_t s,
+                   const BlockNeed &need = BlockNeed()) {
     const int B = w->B, T = b.res * b.res, C = b.C, M = B * T, Hd = h->cfg.mlp_ratio * C;
     const std::string &p = b.prefix;
     const bool fuse = rowstats_on(h);
@@ -1036,9 +1149,10 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
     if (h->opt_fused_attn && b.wqp) {
         // modulate+SiLU, LN1, QKV, window attention, proj and the residual in one register-resident kernel
         WinGeom wg{b.res, b.ws, b.shift, b.heads, C};
+        h->prof_next_list = need.wins.id;
         P_KERN(PK_FUSED, 2.0 * (double)M * C * 4.0 * C + 4.0 * (double)M * (double)(b.ws * b.ws) * (double)C,
                launch_fused_attn96(w->x, w->aff, w->aff_ld, b.aff_off, WT(h, p + ".norm1.weight"), WT(h, p + ".norm1.bias"), b.wqp,
-                                   b.bqkv_s, b.biasT, b.wpp, WT(h, p + ".attn.proj.bias"), B, wg, premod, s));
+                                   b.bqkv_s, b.biasT, b.wpp, WT(h, p + ".attn.proj.bias"), B, wg, premod, s, need.wins.list, need.wins.cnt));
     } else {
         // x <- silu(shift + x*(1+scale)) (also the shortcut), LayerNorm-1 statistics
         if (!premod) P_KERN(PK_ROW, 0.0, launch_mod_stats(w->x, w->aff, w->aff_ld, b.aff_off, w->stats, B, T, C, s));
@@ -1051,14 +1165,17 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
         if (h->opt_fused_qkv_attn && (b.ws == 8 || b.ws == 10) && !h->opt_gemm_bf16 && !h->opt_gemm_split) {
             // LN1 -> QKV -> softmax(q k^T + bias) v in one kernel: q, k, v of (two windows, one head) stay in LDS
             g.attn_bias = b.biasT; g.wg = wg; g.attn_batch = B; g.C = w->att; g.ldc = C;
+            g.row_list = need.wins.list; g.row_cnt = need.wins.cnt;   // (a window list here)
+            h->prof_next_list = need.wins.id;
             char tg_[96];
             if (h->prof_stamps && h->prof_gemm && h->prof_gemm_used < h->prof_gemm_cap) g.prof = h->prof_gemm + 4 * (h->prof_gemm_used++);
             if (h->prof_on) snprintf(tg_, sizeof(tg_), "gemm+attn M=%d N=%d K=%d ln=%d heads=%d", g.M, g.N, g.K, g.ln_part ? 2 : 1, b.heads);
             ProfScope ps_(h, s, PK_GEMM, 2.0 * (double)M * 3.0 * C * C + 4.0 * (double)M * (double)(b.ws * b.ws) * (double)C, tg_);
             attn_done = launch_gemm_qkv_attn(g, s);
         }
+        if (!attn_done && need.wins.list) plan_fail(h, "%s: fused QKV + window attention with a window list not built", p.c_str());
         if (!attn_done) {
-            g.attn_bias = nullptr; g.prof = nullptr;
+            g.attn_bias = nullptr; g.prof = nullptr; g.row_list = nullptr; g.row_cnt = nullptr;
             g.C = w->qkv; g.ldc = 3 * C;
             att_bf16 = bf16_tensor_ok(WT(h, p + ".attn.proj.weight"), C);
             // level 2: q, k, v leave the QKV GEMM as bf16 too (the attention math stays fp32 on the widened values; this one
@@ -1076,14 +1193,16 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
         g.W = WT(h, p + ".attn.proj.weight"); g.bias = WT(h, p + ".attn.proj.bias");
         g.res = w->x; g.ldres = C; g.C = w->x; g.ldc = C;
         if (fuse && !mlp_fused) g.stats_out = w->stats;   // LN2 partials of x + proj(...)
+        g.row_list = need.rows.list; g.row_cnt = need.rows.cnt; h->prof_next_list = need.rows.id;
         P_GEMM_LP(g);
     }
     if (mlp_fused) {
         // LN2 + fc1 + GELU + fc2 + residual in one kernel, hidden activations never leave the register file
         const bool st = want_stats && fuse;
+        h->prof_next_list = need.rows.id;
         P_KERN(PK_FUSED, 4.0 * (double)M * (double)C * (double)Hd,
                launch_fused_mlp(w->x, WT(h, p + ".norm2.weight"), WT(h, p + ".norm2.bias"), b.w1p, WT(h, p + ".mlp.fc1.bias"), b.w2p,
-                                WT(h, p + ".mlp.fc2.bias"), M, C, st ? w->stats : nullptr, s));
+                                WT(h, p + ".mlp.fc2.bias"), M, C, st ? w->stats : nullptr, s, need.rows.list, need.rows.cnt));
         return BlockOut{false, st ? 1 : 0};   // the fused MLP has no modulate epilogue: the next block runs its own mod_stats
     }
     const bool ln2_part = fuse && !(h->opt_fused_attn && b.wqp);   // the proj GEMM above left the partials
@@ -1101,6 +1220,7 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
     if (hid_exp) g.ldc = 0;
     const bool hid_bf16 = bf16_tensor_ok(WT(h, p + ".mlp.fc2.weight"), Hd) && bf16_of(h, b.fc1_wf) != nullptr;
     g.c_bf16 = hid_bf16;
+    g.row_list = need.rows.list; g.row_cnt = need.rows.cnt; h->prof_next_list = need.rows.id;
     P_GEMM_LP(g);
     g = GemmArgs();
     g.A = w->hid; g.lda = hid_exp ? 0 : Hd; g.K1 = Hd; g.K = Hd; g.M = M; g.N = C;
@@ -1110,6 +1230,7 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
     attach_premod(h, w, g, next);
     const bool st = !g.stats_out && want_stats && fuse;
     if (st) g.stats_out = w->stats;   // plain row statistics of the output (EPI 1)
+    g.row_list = need.rows.list; g.row_cnt = need.rows.cnt; h->prof_next_list = need.rows.id;
     P_GEMM_LP(g);
     return BlockOut{g.mod_aff != nullptr, st ? (C + 95) / 96 : 0};
 }
@@ -1458,22 +1579,26 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
         tap(h, name, w->x, l < L - 1 ? (size_t)B * (T / 4) * 2 * C : (size_t)B * T * C, s);
         // the deepest level's skip is popped and discarded by the first up layer (diffusesg.py:754-755)
     }
-    // decoder (diffusesg.py:751-756)
+    // decoder (diffusesg.py:751-756); with masked-token pruning every launch behind the plan's cut takes its need list
+    const PrunePlan &pp = prune_plan(h);
     for (int i = 0; i < L; i++) {
         const int l = L - 1 - i, C = E << l, res = N >> l, T = res * res;
         if (i > 0) {
             const std::string p = "up_layers." + std::to_string(i) + ".upsample";
             const int D = 4 * C, Tc = T / 4;  // coarse tokens, concatenated width
+            const NeedRef coarse = need_ref(h, w, pp.coarse[i]), fine = need_ref(h, w, pp.fine[i]);
             g = GemmArgs();                   // pre_linear on cat([x, skip]) without materialising the concat
             g.A = w->x; g.lda = D / 2; g.K1 = D / 2; g.A2 = w->skips[l]; g.lda2 = D / 2; g.K = D; g.M = B * Tc; g.N = D;
             g.W = WT(h, p + ".pre_linear.weight"); g.C = w->hid; g.ldc = D;
+            g.row_list = coarse.list; g.row_cnt = coarse.cnt; h->prof_next_list = coarse.id;
             P_GEMM_LP(g);
             P_KERN(PK_ROW, 0.0, launch_breakup_ln(w->hid, WT(h, p + ".norm.weight"), WT(h, p + ".norm.bias"), WT(h, p + ".post_norm.weight"),
-                              WT(h, p + ".post_norm.bias"), w->y, B, res / 2, D, s));
+                              WT(h, p + ".post_norm.bias"), w->y, B, res / 2, D, s, false, coarse.list, coarse.cnt));
             g = GemmArgs();
             g.A = w->y; g.lda = C; g.K1 = C; g.K = C; g.M = B * T; g.N = C;
             g.W = WT(h, p + ".post_linear.weight"); g.C = w->x; g.ldc = C;
             attach_premod(h, w, g, h->up[i].empty() ? nullptr : &h->up[i][0]);
+            g.row_list = fine.list; g.row_cnt = fine.cnt; h->prof_next_list = fine.id;
             P_GEMM_LP(g);
             premod = g.mod_aff != nullptr;
             snprintf(name, sizeof(name), "up%d.upsample", i);
@@ -1481,7 +1606,8 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
         }
         for (size_t j = 0; j < h->up[i].size(); j++) {
             const BlockPlan *next = j + 1 < h->up[i].size() ? &h->up[i][j + 1] : nullptr;   // then PatchBreakup / the read-out
-            premod = run_block(h, w, h->up[i][j], premod, next, false, s).premod;
+            const BlockNeed bn{need_ref(h, w, pp.rows[i][j]), need_ref(h, w, pp.wins[i][j])};
+            premod = run_block(h, w, h->up[i][j], premod, next, false, s, bn).premod;
             snprintf(name, sizeof(name), "up%d.block%d", i, (int)j);
             tap(h, name, w->x, (size_t)B * T * C, s);
         }
@@ -1552,13 +1678,21 @@ int check_ready(dsg_handle h, int B) {
     return 0;
 }
 
+// node flags into the workspace + the need lists of the masked-token pruning that follow from them (two small launches).  Flags are
+// staged once per entry-point call -- never inside a captured step body; the captured graphs read lists and counts from fixed addresses
+int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s) {
+    HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)w->B * h->N, hipMemcpyDeviceToDevice, s));
+    if (w->need_lists) launch_need_lists(w->flags, w->B, h->N, w->need, w->need_cnt_ps, w->need_lists, w->need_cnt, s);
+    return 0;
+}
+
 // stage caller tensors into the fixed forward inputs
 int stage_inputs(dsg_handle h, Workspace *w, const float *adj, const float *node, const uint8_t *flags, const float *sc_adj,
                  const float *sc_node, hipStream_t s) {
     const size_t sa = sizeof(float) * (size_t)w->B * h->Ca * h->N * h->N, sn = sizeof(float) * (size_t)w->B * h->N * h->Cn;
     if (adj) HIP_TRY(h, hipMemcpyAsync(w->in_adj, adj, sa, hipMemcpyDeviceToDevice, s));
     if (node) HIP_TRY(h, hipMemcpyAsync(w->in_node, node, sn, hipMemcpyDeviceToDevice, s));
-    if (flags) HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)w->B * h->N, hipMemcpyDeviceToDevice, s));
+    if (flags) if (int rc = stage_flags(h, w, flags, s)) return rc;
     const int has = (sc_adj && sc_node && h->cfg.self_condition) ? 1 : 0;
     if (has) {
         if (sc_adj != w->sc_adj) HIP_TRY(h, hipMemcpyAsync(w->sc_adj, sc_adj, sa, hipMemcpyDeviceToDevice, s));
@@ -1697,7 +1831,10 @@ extern "C" {
 
 size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     if (!h || !h->finalized || B < 1) return 0;
-    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16;
+    size_t need = 0;   // the need lists of the masked-token pruning: every list + 16 pad entries, counts, per-sample counts
+    const PrunePlan &pp = prune_plan(h);
+    for (int k = 0; k < pp.np.n_lists; k++) need += sizeof(int) * ((size_t)B * pp.items[k] + 16 + 1 + (size_t)B);
+    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need;
 }
 
 int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
@@ -1707,9 +1844,9 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     auto opts = [h]() {
         return std::tie(h->opt_fused_attn, h->opt_fused_mlp, h->opt_fused_mlp_maxc, h->opt_fused_readout, h->opt_fused_pe, h->opt_fused_rowstats,
                         h->opt_fused_qkv_attn, h->opt_loop_graph, h->opt_bf16_act, h->opt_bf16_pipe, h->opt_bf16_mlp, h->opt_bf16_qkv_attn,
-                        h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split);
+                        h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked);
     };
-    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool> saved = opts();
+    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool> saved = opts();
     if (n == "fused_attn") h->opt_fused_attn = value != 0;
     else if (n == "fused_mlp") h->opt_fused_mlp = value != 0;
     else if (n == "fused_mlp_maxc") h->opt_fused_mlp_maxc = value;
@@ -1724,6 +1861,7 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     else if (n == "bf16_qkv_attn") h->opt_bf16_qkv_attn = value < 0 ? 0 : (value > 3 ? 3 : value);
     else if (n == "bf16_proj_mlp") h->opt_bf16_proj_mlp = value != 0;
     else if (n == "bf16_readout") h->opt_bf16_readout = value != 0;
+    else if (n == "prune_masked") h->opt_prune_masked = value != 0;
     else if (n == "fused_merge") { h->opt_fused_merge = value != 0; h->opt_fused_merge_small = value > 1; }   // 2: at every size
     else if (n == "gemm_bf16") {
         h->opt_gemm_bf16 = value != 0;
@@ -1765,6 +1903,7 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "bf16_qkv_attn") *value = bx_on(h) ? h->opt_bf16_qkv_attn : 0;
     else if (n == "bf16_proj_mlp") *value = (bx_on(h) && h->opt_bf16_mlp && h->opt_bf16_proj_mlp) ? 1 : 0;
     else if (n == "bf16_readout") *value = (bx_on(h) && h->opt_bf16_readout && h->opt_fused_readout) ? 1 : 0;
+    else if (n == "prune_masked") *value = prune_opts_on(h);   // what runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
     else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
     else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
     else if (n == "gemm_split") *value = h->opt_gemm_split;
@@ -1815,7 +1954,7 @@ int dsg_precond(dsg_handle h, int32_t B, const float *adj, const float *node, co
     hipStream_t s = (hipStream_t)stream;
     Workspace *w;
     if (int rc = get_workspace(h, B, &w)) return rc;
-    HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)B * h->N, hipMemcpyDeviceToDevice, s));
+    if (int rc = stage_flags(h, w, flags, s)) return rc;
     HIP_TRY(h, hipMemcpyAsync(w->sig, sigmas, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
     int64_t nfe = 0;
     if (int rc = precond_core(h, w, CStatePtrs{adj, node}, sc_adj, sc_node, coin != 0, StatePtrs{out_adj, out_node}, false, s, &nfe))
@@ -1888,7 +2027,7 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
         for (int i = 0; i < ncalls; i++) coin_buf[i] = (gen() >> 63) & 1;
     }
     h->last_stats = dsg_sample_stats{};
-    HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)B * h->N, hipMemcpyDeviceToDevice, s));
+    if (int rc = stage_flags(h, w, flags, s)) return rc;
     // x0 = init * sigma(t0) (edm.py:326, :346-347)
     launch_init(CStatePtrs{init_adj, init_node}, t_steps[0], seed, 0u, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     const bool use_graph = cfg->use_graph != 0 && !gt_adj && h->taps.empty();
@@ -2000,13 +2139,18 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
     h->prof_clock_ghz = clocks.empty() ? 0.0 : clocks[clocks.size() / 2];
     // pass B: HIP-event brackets around every launch (per-class breakdown; each bracket includes dispatch latency)
     for (int iter = 0; iter < n_iters; iter++) {
-        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear();
+        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear(); h->prof_list.clear();
         forward_fixed(h, w, s);
         const bool ok = h->prof_on;
         h->prof_on = false;
         HIP_TRY(h, hipStreamSynchronize(s));
         if (!ok) return fail(h, DSG_ERR_HIP, "hipEventCreate failed");
+        // a pruned launch ran only its need list's share of the rows: its FLOP figure is what was executed, not the full shape
+        std::vector<int> need_cnt(w->need.n_lists > 0 ? w->need.n_lists : 1, 0);
+        if (w->need_lists) HIP_TRY(h, hipMemcpy(need_cnt.data(), w->need_cnt, sizeof(int) * w->need.n_lists, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < h->prof_kind.size(); i++) {
+            const int nl = h->prof_list[i];
+            if (nl >= 0 && nl < w->need.n_lists) h->prof_flops[i] *= (double)need_cnt[nl] / ((double)B * (double)prune_plan(h).items[nl]);
             float ms = 0.f;
             HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_events[2 * i], h->prof_events[2 * i + 1]));
             if (iter == n_iters - 1 && getenv("DSG_PROFILE_VERBOSE"))
@@ -2017,6 +2161,37 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
         }
     }
     if (gemm_inkernel_ms_out) *gemm_inkernel_ms_out = gemm_inkernel_ms;
+    return DSG_OK;
+}
+
+int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_roles, int32_t *n_roles, int32_t *lists_out,
+                         int64_t lists_cap, void *stream) {
+    if (int rc = check_ready(h, B)) return rc;
+    if (!n_roles) return fail(h, DSG_ERR_INVALID, "null argument");
+    auto it = h->ws.find(B);
+    if (it == h->ws.end()) return fail(h, DSG_ERR_STATE, "no workspace for batch %d: run dsg_denoise/dsg_sample first", B);
+    Workspace *w = it->second.get();
+    const PrunePlan &pp = prune_plan(h);
+    *n_roles = w->need_lists ? (int32_t)pp.roles.size() : 0;
+    if (!w->need_lists || !roles) return DSG_OK;
+    if (max_roles < *n_roles) return fail(h, DSG_ERR_INVALID, "room for %d roles needed", *n_roles);
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    std::vector<int> all(w->need_ints);
+    HIP_TRY(h, hipMemcpy(all.data(), w->need_lists, sizeof(int) * w->need_ints, hipMemcpyDeviceToHost));
+    const int *cnt = all.data() + (w->need_cnt - w->need_lists);
+    int64_t off = 0;
+    for (size_t r = 0; r < pp.roles.size(); r++) {
+        const PruneRole &ro = pp.roles[r];
+        const int n = cnt[ro.list];
+        int32_t *row = roles + 8 * r;
+        row[0] = ro.kind; row[1] = ro.res; row[2] = ro.shift; row[3] = ro.stage; row[4] = ro.block; row[5] = n; row[6] = (int32_t)off;
+        row[7] = B * pp.items[ro.list];
+        if (lists_out) {
+            if (off + n > lists_cap) return fail(h, DSG_ERR_INVALID, "lists_out too small");
+            memcpy(lists_out + off, all.data() + w->need.list_off[ro.list], sizeof(int) * (size_t)n);
+        }
+        off += n;
+    }
     return DSG_OK;
 }
 

@@ -61,6 +61,11 @@ struct GemmArgs {
     int attn_batch = 0;
     int batch = 1;                               // > 1: that many independent products in one launch (fp32 kernel, AMODE 2: split-K slices)
     size_t batch_strideA = 0, batch_strideW = 0, batch_strideC = 0;   // floats between consecutive products' operands / outputs
+    // masked-token pruning (fp32 kernel, AMODE 3): the launch computes only the rows of the 8-row runs listed in row_list
+    // (run r = physical rows 8r .. 8r+7; -1 pads the list to a whole 128-row tile), *row_cnt of them (device-side: grids keep their
+    // full size, tiles beyond the count return at once).  One physical row indexes A, A2, res, C, ln_part / ln_stats, stats_out and the
+    // mod_aff sample alike.  launch_gemm_qkv_attn: row_list is a list of window indices instead (two per tile).
+    const int *row_list = nullptr, *row_cnt = nullptr;
     int a_bf16 = 0, c_bf16 = 0;                  // bf16 mode only: A / C are bf16 tensors (lda / ldc in elements); see kernels_lp.hip
     const float *gelu_tab = nullptr;             // filled in by launch_gemm (table-driven GELU of the split kernel)
     unsigned long long *prof = nullptr;          // measurement mode: {min block start, max block end} in 100 MHz ticks
@@ -136,7 +141,8 @@ const float *gelu_table();
 // x <- x + fc2(GELU(fc1(LN(x)))) with fragment-major packed weights (pack_mlp_weights in dsg_api.cpp); C in {96,192}
 // stats_out (optional): [M][1][2] (sum, sumsq) of the rows written back, in the GEMM epilogue's partial format
 void launch_fused_mlp(float *x, const float *gam, const float *bet, const float *W1p, const float *b1, const float *W2p,
-                      const float *b2, int M, int C, float *stats_out, hipStream_t s);
+                      const float *b2, int M, int C, float *stats_out, hipStream_t s,
+                      const int *run_list = nullptr, const int *run_cnt = nullptr);   // run list: only those 8-row runs (GemmArgs::row_list)
 
 // input assembly + 1x1 conv + LayerNorm + modulate+SiLU in one kernel (E = 96, in_chans <= 64); false if unsupported
 bool launch_fused_patch_embed96(const float *adj, const float *node, const float *sc_adj, const float *sc_node, const int *has_sc,
@@ -154,7 +160,8 @@ void launch_fused_readout96(const float *x, const float *gam, const float *bet, 
 // windows of at most 64 tokens; packed weights from pack_attn_weights in dsg_api.cpp
 void launch_fused_attn96(float *x, const float *aff, int aff_ld, int aff_off, const float *gam, const float *bet, const float *Wqp,
                          const float *bqkv, const float *biasT, const float *Wpp, const float *bproj, int B, const WinGeom &g,
-                         bool premod, hipStream_t s);   // premod: x is already modulated by the producing kernel
+                         bool premod, hipStream_t s,    // premod: x is already modulated by the producing kernel
+                         const int *win_list = nullptr, const int *win_cnt = nullptr);   // window list: only those windows (b * nW + w), *win_cnt of them
 // qkv [B*T, 3C] token order -> out [B*T, C] token order; biasT [nWt][heads][Wp][Wp] (key-major)
 bool launch_window_attn(const float *qkv, const float *biasT, float *out, int B, const WinGeom &g, hipStream_t s, bool out_bf16 = false, bool in_bf16 = false);   // false: not built (nothing launched)
 
@@ -169,7 +176,8 @@ void launch_ln_mod(const float *x, const float *g, const float *b, const float *
 void launch_merge_ln(const float *x, const float *g, const float *b, float *y, int B, int res, int C, hipStream_t s, bool out_bf16 = false);
 // PatchBreakup middle: LN(D) -> 4 chunks scattered 2x2 -> LN(D/4): y [B,res*res,D] -> z [B,(2res)^2,D/4]
 void launch_breakup_ln(const float *y, const float *g, const float *b, const float *pg, const float *pb, float *z,
-                       int B, int res, int D, hipStream_t s, bool out_bf16 = false);   // out_bf16: y / z are bf16 tensors
+                       int B, int res, int D, hipStream_t s, bool out_bf16 = false,   // out_bf16: y / z are bf16 tensors
+                       const int *run_list = nullptr, const int *run_cnt = nullptr);   // run list over the COARSE rows of y
 // positional embedding of the noise label: pe [B,E]
 void launch_noise_pe(const float *c_noise, float *pe, int B, int E, hipStream_t s);
 // input assembly: token-major [B*N*N, Kp] (zero padded), channel order of diffusesg.py:792-802
@@ -183,6 +191,20 @@ void launch_pool(const float *rep, const uint8_t *flags, float *pool, int B, int
 // node head tail: h [B*N, E] -> out [B,N,Cn] = mask(h @ W^T + b)
 void launch_head_node(const float *h, const float *W, const float *bias, const uint8_t *flags, float *out,
                       int B, int N, int E, int Cn, hipStream_t s);
+
+// ---- masked-token pruning: device-side need lists (kernels.hip: need_lists_kernel) ----
+// A plan is a short program on one sample's set of needed 8-token runs, starting from the last level's output need (runs that hold a
+// pair with flag_i && flag_j) and walking the up path backwards.  Lists are compacted over the whole batch: run lists hold
+// b * res * res / 8 + run, window lists b * nW + window; list L lives at lists + list_off[L] with room for every entry + 16.
+enum NeedKind { NEED_EMIT = 0,      // write the current set (side `res`) as run list `list`
+                NEED_WINDOWS = 1,   // windows of the partition (res, shift) holding a needed run -> window list `list` (-1: none);
+                                    // the set becomes every run those windows touch
+                NEED_PARENT = 2 };  // res = fine side: the set becomes the coarse runs holding a parent (i/2, j/2) of a needed token
+struct NeedOp { int kind, res, shift, list; };
+constexpr int NEED_MAX_OPS = 40, NEED_MAX_LISTS = 32, NEED_MAX_RUNS = 2048;   // runs of one sample at the finest level: N * N / 8
+struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_off[NEED_MAX_LISTS]; };
+// cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
+void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s);
 
 // ---- preconditioning / sampler elementwise kernels (adj and node parts handled in one launch) ----
 struct StatePtrs { float *adj; float *node; };

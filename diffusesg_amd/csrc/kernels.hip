@@ -5,6 +5,7 @@
 // elementwise work fused around them.  Reference semantics are cited per kernel
 // (R/ = DiffuseSG/ of the reference tree).
 #include "kernels_common.hip.h"
+#include <algorithm>
 
 namespace dsg {
 
@@ -117,6 +118,13 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
     const int xcd = bid & 7, seq = bid >> 3;
     const int tm = (seq / tiles_n) * 8 + xcd, tn = seq % tiles_n;
     if (tm >= tiles_m) return;
+    // AMODE 3 (masked-token pruning): the tile's rows are 16 runs of 8 consecutive rows taken from g.row_list (EPI == 4: its
+    // windows from the same list); tiles at or beyond the device-side count have nothing to do.  -1 pads the last tile.
+    int map_cnt = 0;
+    if (AMODE == 3) {
+        map_cnt = *g.row_cnt;
+        if (tm * (EPI == 4 ? GBM / 64 : GBM / 8) >= map_cnt) return;
+    }
     const int m0 = tm * GBM, n0 = tn * GBN;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c4 = tid & 7, r0 = tid >> 3;
@@ -129,9 +137,15 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
     constexpr int A_WT = WS * WS, A_WP = (A_WT + 31) / 32 * 32, A_KT = A_WP / 32, A_WPT = GBM / A_WP;   // 64/64/2/2 or 100/128/4/1
     const int a_res = g.wg.res, a_nwr = (EPI == 4) ? a_res / WS : 1, a_nW = a_nwr * a_nwr, a_T = a_res * a_res;
     const int a_nwin = g.attn_batch * a_nW;
+    int a_wmap[2] = {0, 0};   // AMODE 3: the tile's two windows through the window list
+    if (EPI == 4 && AMODE == 3) {
+#pragma unroll
+        for (int k = 0; k < 2; k++) a_wmap[k] = (2 * tm + k < map_cnt) ? g.row_list[2 * tm + k] : a_nwin;
+    }
+    auto tile_win = [&](int k) -> int { return (AMODE == 3) ? (k ? a_wmap[1] : a_wmap[0]) : A_WPT * tm + k; };
     auto win_row = [&](int r) -> int {   // global row of tile row r, or -1 if the window / the position does not exist
-        const int gw = A_WPT * tm + r / A_WP, pos = r % A_WP;
-        if (gw >= a_nwin || pos >= A_WT) return -1;
+        const int gw = tile_win(r / A_WP), pos = r % A_WP;
+        if (gw >= a_nwin || gw < 0 || pos >= A_WT) return -1;
         const int b = gw / a_nW, w = gw - b * a_nW, wi = w / a_nwr, wj = w - wi * a_nwr;
         int ti = wi * WS + pos / WS + g.wg.shift, tj = wj * WS + pos % WS + g.wg.shift;
         if (ti >= a_res) ti -= a_res;
@@ -140,10 +154,11 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
     };
     // block-uniform descriptors: base = first row of the tile, range = the valid rows (out-of-range reads give 0)
     const int a4_C = g.K >> 2;   // AMODE 1: channels of one source row
-    const rsrc_t rsA1 = (EPI == 4) ? make_rsrc(g.A, (unsigned)g.M * g.lda * 4u)
+    const rsrc_t rsA1 = (EPI == 4 || AMODE == 3) ? make_rsrc(g.A, (unsigned)g.M * g.lda * 4u)
                         : (AMODE == 1) ? make_rsrc(g.A, (unsigned)g.M * (unsigned)g.K * 4u)   // 4*M fine rows of K/4 floats
                                        : make_rsrc(gA + (size_t)m0 * g.lda, (unsigned)rows_m * g.lda * 4u);
-    const rsrc_t rsA2 = make_rsrc(g.A2 ? g.A2 + (size_t)m0 * g.lda2 : g.A, g.A2 ? (unsigned)rows_m * g.lda2 * 4u : 0u);
+    const rsrc_t rsA2 = (AMODE == 3) ? make_rsrc(g.A2 ? g.A2 : g.A, g.A2 ? (unsigned)g.M * g.lda2 * 4u : 0u)
+                                     : make_rsrc(g.A2 ? g.A2 + (size_t)m0 * g.lda2 : g.A, g.A2 ? (unsigned)rows_m * g.lda2 * 4u : 0u);
     const rsrc_t rsW = (EPI == 4) ? make_rsrc(g.W, (unsigned)(3 * g.wg.C) * g.K * 4u) : make_rsrc(gW + (size_t)n0 * g.K, (unsigned)rows_n * g.K * 4u);
     unsigned voffA1[4], voffA2[4], voffW[3];
     unsigned voffA4[4][4];   // AMODE 1: [part][staging row]
@@ -160,6 +175,12 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
         if (EPI == 4) {
             a_grow[p] = win_row(r);
             voffA1[p] = a_grow[p] >= 0 ? ((unsigned)a_grow[p] * g.lda + 4u * c4) * 4u : 0x7fffffffu;
+        }
+        if (EPI != 4 && AMODE == 3) {   // physical row of staging row r: run (r / 8) of the tile, position r % 8
+            const int run = g.row_list[tm * 16 + (r >> 3)];
+            a_grow[p] = run >= 0 ? run * 8 + (r & 7) : -1;
+            voffA1[p] = a_grow[p] >= 0 ? ((unsigned)a_grow[p] * g.lda + 4u * c4) * 4u : 0x7fffffffu;
+            voffA2[p] = a_grow[p] >= 0 ? ((unsigned)a_grow[p] * g.lda2 + 4u * c4) * 4u : 0x7fffffffu;
         }
         if (AMODE == 1) {
             // coarse row -> its four fine rows (order x00, x10, x01, x11: part q has di = q&1, dj = q>>1)
@@ -199,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
         } else if (LN) {
             int m[4];
 #pragma unroll
-            for (int p = 0; p < 4; p++) m[p] = (EPI == 4) ? max(a_grow[p], 0) : min(m0 + r0 + 32 * p, g.M - 1);
+            for (int p = 0; p < 4; p++) m[p] = (EPI == 4 || AMODE == 3) ? max(a_grow[p], 0) : min(m0 + r0 + 32 * p, g.M - 1);
             if (g.ln_part) {   // partial (sum, sumsq) per 96-column tile of the producer: [M][nparts][2], added in tile order
                 const float *pp[4];
                 float sm[4], sq[4];
@@ -375,8 +396,8 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
         if (tid < GBM) toks[tid] = my_tok;
         __syncthreads();
         const int wl = wave / A_KT, qh = wave % A_KT;   // window of the tile / 32-query block inside the window
-        const int gw = A_WPT * tm + wl;
-        if (gw < a_nwin && 32 * qh < A_WT) {   // wave-uniform: the last tile's second window may not exist
+        const int gw = tile_win(wl);
+        if (gw < a_nwin && gw >= 0 && 32 * qh < A_WT) {   // wave-uniform: the last tile's second window may not exist
             const int wbase = A_WP * wl;
             f32x4 qf[4];
 #pragma unroll
@@ -452,11 +473,27 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
     }
     // epilogue: buffer stores; lane-dependent part of the address in voffset, (register, tile) part in a scalar offset.
     // rows >= M fall outside the descriptor and are dropped; columns >= N get an out-of-range voffset.
-    const rsrc_t rsC = make_rsrc(gC + (size_t)m0 * g.ldc, (unsigned)rows_m * g.ldc * 4u);
-    const rsrc_t rsC2 = make_rsrc(g.C2 ? g.C2 + (size_t)m0 * g.ldc2 : g.C, g.C2 ? (unsigned)rows_m * g.ldc2 * 4u : 0u);
-    const rsrc_t rsR = make_rsrc(RES ? g.res + (size_t)m0 * g.ldres : g.C, RES ? (unsigned)rows_m * g.ldres * 4u : 0u);
-    const unsigned rowl = (unsigned)(wave * 32 + 4 * lhalf);
+    // AMODE 3: whole-tensor descriptors; the lane's 16 rows are 4 rows (r & 3) of each of the wave's 4 runs (r >> 2), whose first
+    // physical row is wave-uniform and goes into the scalar offset; a sentinel run gets an out-of-range lane offset
+    const size_t mbase = (AMODE == 3) ? 0 : (size_t)m0;
+    const unsigned mrows = (AMODE == 3) ? (unsigned)g.M : (unsigned)rows_m;
+    const rsrc_t rsC = make_rsrc(gC + mbase * g.ldc, mrows * g.ldc * 4u);
+    const rsrc_t rsC2 = make_rsrc(g.C2 ? g.C2 + mbase * g.ldc2 : g.C, g.C2 ? mrows * g.ldc2 * 4u : 0u);
+    const rsrc_t rsR = make_rsrc(RES ? g.res + mbase * g.ldres : g.C, RES ? mrows * g.ldres * 4u : 0u);
+    const unsigned rowl = (AMODE == 3) ? (unsigned)(4 * lhalf) : (unsigned)(wave * 32 + 4 * lhalf);
     const unsigned OOB = 0x7fffffffu;
+    unsigned e_row[4] = {0u, 8u, 16u, 24u};   // first row of the lane's row group q = r >> 2 (relative to the descriptor base; without rowl)
+    bool e_ok[4] = {true, true, true, true};
+    if (AMODE == 3) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int run = __builtin_amdgcn_readfirstlane(g.row_list[tm * 16 + wave * 4 + q]);
+            e_ok[q] = run >= 0;
+            e_row[q] = (unsigned)max(run, 0) * 8u;
+        }
+    }
+#define E_ROW(r) (e_row[(r) >> 2] + (unsigned)((r) & 3))
+#define E_OFF(v, r) ((AMODE == 3 && !e_ok[(r) >> 2]) ? OOB : (v))
     float st_s[16], st_q[16];   // EPI: this lane's share of (sum, sumsq) of its 16 rows
     int brow[16];               // EPI == 3: sample index of each of the lane's rows
     if (EPI >= 1) {
@@ -466,10 +503,14 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
     if (EPI == 3) {   // per-sample (scale,shift): row -> sample through a 128-entry LDS table (one division per thread)
         __syncthreads();   // every wave is done with the K loop's tiles
         int *bt = reinterpret_cast<int *>(lds) + 4 * 2304;   // behind the four per-wave reduction slabs used below
-        if (tid < GBM) bt[tid] = min(m0 + tid, g.M - 1) / g.mod_T;
+        if (tid < GBM) {
+            int prow = min(m0 + tid, g.M - 1);
+            if (AMODE == 3) prow = max(g.row_list[tm * 16 + (tid >> 3)], 0) * 8 + (tid & 7);
+            bt[tid] = prow / g.mod_T;
+        }
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < 16; r++) brow[r] = bt[rowl + (r & 3) + 8 * (r >> 2)];
+        for (int r = 0; r < 16; r++) brow[r] = bt[wave * 32 + 4 * lhalf + (r & 3) + 8 * (r >> 2)];
     }
 #pragma unroll
     for (int j = 0; j < 3; j++) {
@@ -484,7 +525,7 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
         float rres[16];
         if (RES) {
 #pragma unroll
-            for (int r = 0; r < 16; r++) rres[r] = buf_load1(rsR, vR, (unsigned)((r & 3) + 8 * (r >> 2)) * g.ldres * 4u);
+            for (int r = 0; r < 16; r++) rres[r] = buf_load1(rsR, E_OFF(vR, r), E_ROW(r) * g.ldres * 4u);
         }
         // phase by phase over the 16 rows of this 32-column slab, not row by row: the block-uniform `if (g.C2)` would otherwise
         // cut the loop into 16 basic blocks, each one serial dependency chain (bias -> activation -> store) that the
@@ -510,7 +551,7 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
         }
         if (g.C2) {
 #pragma unroll
-            for (int r = 0; r < 16; r++) buf_store1(v[r], rsC2, vC2, (unsigned)((r & 3) + 8 * (r >> 2)) * g.ldc2 * 4u);
+            for (int r = 0; r < 16; r++) buf_store1(v[r], rsC2, E_OFF(vC2, r), E_ROW(r) * g.ldc2 * 4u);
         }
         if (ACT == ACT_GELU_KEEP) {   // (training form) C2 just received the pre-activation
 #pragma unroll
@@ -539,8 +580,10 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
             }
         }
 #pragma unroll
-        for (int r = 0; r < 16; r++) buf_store1(v[r], rsC, vC, (unsigned)((r & 3) + 8 * (r >> 2)) * g.ldc * 4u);
+        for (int r = 0; r < 16; r++) buf_store1(v[r], rsC, E_OFF(vC, r), E_ROW(r) * g.ldc * 4u);
     }
+#undef E_ROW
+#undef E_OFF
     if (EPI >= 1) {
         // Row statistics of the stored tile.  A row's 96 values sit in the 32 lanes of a half-wave: transpose through a
         // per-wave LDS slab (the K loop's tiles are dead) so that lane (row, q) adds the 32 lane-partials of quantity q
@@ -561,8 +604,13 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
             const f32x4 q4 = *reinterpret_cast<const f32x4 *>(src + 4 * i);
             tot += (q4[0] + q4[1]) + (q4[2] + q4[3]);
         }
-        const rsrc_t rsP = make_rsrc(g.stats_out + (size_t)m0 * tiles_n * 2, (unsigned)(rows_m * tiles_n) * 8u);   // [M][tiles_n][2]
-        buf_store1(tot, rsP, (unsigned)(((wave * 32 + lrow) * tiles_n + tn) * 2 + lhalf) * 4u, 0u);
+        const rsrc_t rsP = make_rsrc(g.stats_out + mbase * tiles_n * 2, (mrows * tiles_n) * 8u);   // [M][tiles_n][2]
+        unsigned voffP = (unsigned)(((wave * 32 + lrow) * tiles_n + tn) * 2 + lhalf) * 4u;
+        if (AMODE == 3) {
+            const int run = g.row_list[tm * 16 + wave * 4 + (lrow >> 3)];
+            voffP = run >= 0 ? (unsigned)(((run * 8 + (lrow & 7)) * tiles_n + tn) * 2 + lhalf) * 4u : OOB;
+        }
+        buf_store1(tot, rsP, voffP, 0u);
     }
 #ifdef DSG_PHASE_DIAG
     if (tid == 0 && g.prof) {   // g.prof doubles as a [4 x blocks] stamp buffer in this build
@@ -619,6 +667,22 @@ bool launch_gemm(const GemmArgs &g, hipStream_t s) {
     }
 #define GEMM_CASE(L, A, R) DSG_LAUNCH((gemm4_f32_kernel<L, A, R, 0>), grid, block, 0, s, g, tiles_m, tiles_n)
 #define GEMM_EPI(R, E) DSG_LAUNCH((gemm4_f32_kernel<false, ACT_NONE, R, E>), grid, block, 0, s, g, tiles_m, tiles_n)
+    if (g.row_list) {   // row-mapped forms (masked-token pruning): the up path's pre_linear / post_linear / proj / fc1 / fc2 shapes only
+        const size_t widest = (size_t)std::max(std::max(g.lda, g.lda2), std::max(std::max(g.ldc, g.ldc2), std::max(g.ldres, 2 * tiles_n)));
+        if (!g.row_cnt || g.a4_res > 0 || g.M % 8 != 0 || (size_t)g.M * widest * 4u >= 0x7fffffffull) return false;
+#define GEMM_MAP(L, A, R, E) DSG_LAUNCH((gemm4_f32_kernel<L, A, R, E, 8, 3>), grid, block, 0, s, g, tiles_m, tiles_n)
+        const int epi = !g.stats_out ? 0 : (!g.mod_aff ? 1 : (g.mod_ld == 0 ? 2 : 3));
+        if (ln) {
+            if (g.act != ACT_GELU || res || epi != 0 || g.C2 || g.A2) return false;
+            GEMM_MAP(true, ACT_GELU, false, 0);
+        } else {
+            if (g.act != ACT_NONE || g.C2 || (g.mod_aff && !g.stats_out)) return false;
+            if (res) { if (epi == 0) GEMM_MAP(false, ACT_NONE, true, 0); else if (epi == 1) GEMM_MAP(false, ACT_NONE, true, 1); else if (epi == 2) GEMM_MAP(false, ACT_NONE, true, 2); else GEMM_MAP(false, ACT_NONE, true, 3); }
+            else { if (epi == 0) GEMM_MAP(false, ACT_NONE, false, 0); else if (epi == 1) GEMM_MAP(false, ACT_NONE, false, 1); else if (epi == 2) GEMM_MAP(false, ACT_NONE, false, 2); else GEMM_MAP(false, ACT_NONE, false, 3); }
+        }
+#undef GEMM_MAP
+        return true;
+    }
     if (g.a4_res > 0) {   // PatchMerging gather + LayerNorm(4C) from partials; epilogue: plain, or premod + stats (dual store allowed)
         if (!g.ln_part || g.A2 || g.act != ACT_NONE || res || (g.K >> 2) % GBK != 0 || (g.stats_out && !g.mod_aff)) return false;
 #define GEMM_MERGE(E) DSG_LAUNCH((gemm4_f32_kernel<true, ACT_NONE, false, E, 8, 1>), grid, block, 0, s, g, tiles_m, tiles_n)
@@ -663,6 +727,11 @@ bool launch_gemm_qkv_attn(const GemmArgs &g, hipStream_t s) {
     const int wpt = wg.ws == 8 ? 2 : 1;   // windows per 128-row tile: two of 64 tokens, or one of 100 padded to 128
     const int tiles_m = (n_windows + wpt - 1) / wpt, tiles_n = wg.heads;
     const dim3 grid(((tiles_m + 7) / 8) * 8 * tiles_n), block(256);
+    if (g.row_list) {   // windows through a window list (masked-token pruning)
+        if (wg.ws != 8 || !g.row_cnt) return false;
+        DSG_LAUNCH((gemm4_f32_kernel<true, ACT_NONE, false, 4, 8, 3>), grid, block, 0, s, g, tiles_m, tiles_n);
+        return true;
+    }
     if (wg.ws == 8) DSG_LAUNCH((gemm4_f32_kernel<true, ACT_NONE, false, 4, 8>), grid, block, 0, s, g, tiles_m, tiles_n);
     else DSG_LAUNCH((gemm4_f32_kernel<true, ACT_NONE, false, 4, 10>), grid, block, 0, s, g, tiles_m, tiles_n);
     return true;
@@ -684,13 +753,21 @@ template <int C>
 __global__ __launch_bounds__(256, (C <= 96 ? 2 : 1)) void fused_mlp_kernel(float *__restrict__ x, const float *__restrict__ gam,
                                                            const float *__restrict__ bet, const float *__restrict__ W1p,
                                                            const float *__restrict__ b1, const float *__restrict__ W2p,
-                                                           const float *__restrict__ b2, int M, float *__restrict__ stats_out) {
+                                                           const float *__restrict__ b2, int M, float *__restrict__ stats_out,
+                                                           const int *__restrict__ run_list, const int *__restrict__ run_cnt) {
     constexpr int S = C / 8, CT = C / 32, NT = 4 * C / 32;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lrow = lane & 31, lhalf = lane >> 5;
-    const int m = (blockIdx.x * 4 + wave) * 32 + lrow;
-    const bool ok = m < M;
-    float *xr = x + (size_t)(ok ? m : M - 1) * C + 4 * lhalf;
+    int m = (blockIdx.x * 4 + wave) * 32 + lrow;
+    bool ok = m < M;
+    if (run_list) {   // masked-token pruning: the wave's 32 rows are 4 runs of the list (-1 pads); nothing at or beyond the count
+        const int r4 = (blockIdx.x * 4 + wave) * 4;
+        if (r4 >= *run_cnt) return;   // no block-level synchronisation below
+        const int run = run_list[r4 + (lrow >> 3)];
+        ok = run >= 0;
+        m = run * 8 + (lrow & 7);
+    }
+    float *xr = x + (size_t)(ok ? m : (run_list ? 0 : M - 1)) * C + 4 * lhalf;
 
     f32x4 xn[S];
     float sum = 0.f;
@@ -780,10 +857,10 @@ __global__ __launch_bounds__(256, (C <= 96 ? 2 : 1)) void fused_mlp_kernel(float
 }
 
 void launch_fused_mlp(float *x, const float *gam, const float *bet, const float *W1p, const float *b1, const float *W2p,
-                      const float *b2, int M, int C, float *stats_out, hipStream_t s) {
+                      const float *b2, int M, int C, float *stats_out, hipStream_t s, const int *run_list, const int *run_cnt) {
     const dim3 grid((M + 127) / 128), block(256);
-    if (C == 96) DSG_LAUNCH(fused_mlp_kernel<96>, grid, block, 0, s, x, gam, bet, W1p, b1, W2p, b2, M, stats_out);
-    else if (C == 192) DSG_LAUNCH(fused_mlp_kernel<192>, grid, block, 0, s, x, gam, bet, W1p, b1, W2p, b2, M, stats_out);
+    if (C == 96) DSG_LAUNCH(fused_mlp_kernel<96>, grid, block, 0, s, x, gam, bet, W1p, b1, W2p, b2, M, stats_out, run_list, run_cnt);
+    else if (C == 192) DSG_LAUNCH(fused_mlp_kernel<192>, grid, block, 0, s, x, gam, bet, W1p, b1, W2p, b2, M, stats_out, run_list, run_cnt);
 }
 
 // =================================================================================================
@@ -803,12 +880,18 @@ __global__ __launch_bounds__(256, 1) void fused_attn96_kernel(float *__restrict_
                                                              const float *__restrict__ bet, const float *__restrict__ Wqp,
                                                              const float *__restrict__ bqkv, const float *__restrict__ biasT,
                                                              const float *__restrict__ Wpp, const float *__restrict__ bproj,
-                                                             WinGeom g, int n_windows) {
+                                                             WinGeom g, int n_windows, const int *__restrict__ win_list,
+                                                             const int *__restrict__ win_cnt) {
     constexpr int C = 96, S = 12, CT = 3, HEADS = 3, Wp = 32 * MB;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lrow = lane & 31, lhalf = lane >> 5;
-    const int win = blockIdx.x * 4 + wave;
+    int win = blockIdx.x * 4 + wave;
     if (win >= n_windows) return;  // no block-level synchronisation below
+    if (win_list) {   // masked-token pruning: the wave's window comes from the list; nothing at or beyond the count
+        if (win >= *win_cnt) return;
+        win = __builtin_amdgcn_readfirstlane(win_list[win]);
+        if (win < 0) return;
+    }
     const int res = g.res, ws = g.ws, nwr = res / ws, nW = nwr * nwr, Wt = ws * ws, T = res * res;
     const int w = win % nW, b = win / nW;
     const int wi = w / nwr, wj = w % nwr;
@@ -995,11 +1078,11 @@ __global__ __launch_bounds__(256, 1) void fused_attn96_kernel(float *__restrict_
 
 void launch_fused_attn96(float *x, const float *aff, int aff_ld, int aff_off, const float *gam, const float *bet, const float *Wqp,
                          const float *bqkv, const float *biasT, const float *Wpp, const float *bproj, int B, const WinGeom &g,
-                         bool premod, hipStream_t s) {
+                         bool premod, hipStream_t s, const int *win_list, const int *win_cnt) {
     const int nW = (g.res / g.ws) * (g.res / g.ws), n_windows = B * nW;
     const int MB = (g.ws * g.ws + 31) / 32;
     const dim3 grid((n_windows + 3) / 4), block(256);
-#define FA(MB_, PM_) DSG_LAUNCH((fused_attn96_kernel<MB_, PM_>), grid, block, 0, s, x, aff, aff_ld, aff_off, gam, bet, Wqp, bqkv, biasT, Wpp, bproj, g, n_windows)
+#define FA(MB_, PM_) DSG_LAUNCH((fused_attn96_kernel<MB_, PM_>), grid, block, 0, s, x, aff, aff_ld, aff_off, gam, bet, Wqp, bqkv, biasT, Wpp, bproj, g, n_windows, win_list, win_cnt)
     if (MB == 1) { if (premod) FA(1, true); else FA(1, false); }
     else { if (premod) FA(2, true); else FA(2, false); }
 #undef FA
@@ -1070,6 +1153,29 @@ __global__ __launch_bounds__(256, 2) void fused_readout96_kernel(const float *__
     const bool ok = m < M;
     const int mc = ok ? m : M - 1;
     const int b = mc / T, i = (mc / N) % N, j = mc % N;
+    if (!BF && __ballot(ok && flags[(size_t)b * N + i] != 0 && flags[(size_t)b * N + j] != 0) == 0) {
+        // no valid pair among the wave's 32 tokens: the adjacency output and the pooling partials are exact zeros whatever x holds
+        // (with masked-token pruning these rows of x are not computed at all), so the LayerNorm and both products are skipped.
+        // Same slots as below: pool_finish_kernel's summation order does not change.
+        const int tile = blockIdx.x * 4 + wave;
+        const int rowid = ok ? b * N + i : -1;
+        const int r_first = __shfl(rowid, 0, 64);
+        int r_last = __shfl(rowid, 31, 64);
+        if (r_last < 0) r_last = (M - 1) / N;
+        if (r_first < 0) r_last = -2;
+        for (int r = r_first; r <= r_last; r++) {
+            float *dst = pool_part + ((size_t)r * nseg + (tile - (r * N) / 32)) * C;
+            if (lrow < S) *reinterpret_cast<f32x4 *>(dst + 8 * lrow + 4 * lhalf) = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        if (ok) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int c = (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                if (c < Ca) out_adj[(((size_t)b * Ca + c) * N + i) * N + j] = 0.f;
+            }
+        }
+        return;
+    }
     const float *xr = x + (size_t)mc * C + 4 * lhalf;
     f32x4 xn[S];
     float sum = 0.f;
@@ -1095,6 +1201,11 @@ __global__ __launch_bounds__(256, 2) void fused_readout96_kernel(const float *__
     }
     const bool fi = flags[(size_t)b * N + i] != 0, fj = flags[(size_t)b * N + j] != 0;
     const bool valid = ok && fi && fj;
+    // a masked token contributes nothing below (weight 0, output select); with masked-token pruning its row of x may be stale, so its
+    // LayerNorm is replaced by zeros -- a select, so that no stale non-finite value can travel through the products with 0
+#pragma unroll
+    for (int s = 0; s < S; s++)
+        if (!valid) xn[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // pooled LN(x): segmented sum over the tokens of this wave that share a row (b,i).  No atomics: the wave stores its
     // partial for row r into slot (tile - first tile of r) of pool_part[r]; pool_finish_kernel adds a row's slots in slot
@@ -1696,10 +1807,17 @@ void launch_merge_ln(const float *x, const float *g, const float *b, float *y, i
 // PatchBreakup middle (diffusesg.py:386-400): LN_D(row) -> chunk q -> token (2i+(q&1), 2j+(q>>1)) -> LN_{D/4}
 template <bool OBF>   // OBF: z is a bf16 tensor (the bf16 block pipeline's post_linear GEMM reads bf16)
 __global__ __launch_bounds__(256) void breakup_ln_kernel(const float *y, const float *g, const float *bta, const float *pg,
-                                                         const float *pb, float *z, int res, int D, int M) {
+                                                         const float *pb, float *z, int res, int D, int M,
+                                                         const int *__restrict__ run_list, const int *__restrict__ run_cnt) {
     const int lane = threadIdx.x & 63;
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    int m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
+    if (run_list) {   // masked-token pruning: coarse rows through the run list (8 rows per run)
+        if ((m >> 3) >= *run_cnt) return;
+        const int run = __builtin_amdgcn_readfirstlane(run_list[m >> 3]);
+        if (run < 0) return;
+        m = run * 8 + (m & 7);
+    }
     const int T = res * res, b = m / T, t = m % T, i = t / res, j = t % res;
     const int Co = D / 4, R = 2 * res, D4 = D >> 2, Co4 = Co >> 2;
     const f32x4 *yr = reinterpret_cast<const f32x4 *>(y + (size_t)m * D);
@@ -1772,10 +1890,10 @@ __global__ __launch_bounds__(256) void breakup_ln_kernel(const float *y, const f
     }
 }
 void launch_breakup_ln(const float *y, const float *g, const float *b, const float *pg, const float *pb, float *z, int B,
-                       int res, int D, hipStream_t s, bool out_bf16) {
+                       int res, int D, hipStream_t s, bool out_bf16, const int *run_list, const int *run_cnt) {
     const int M = B * res * res;
-    if (out_bf16) DSG_LAUNCH(breakup_ln_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, s, y, g, b, pg, pb, z, res, D, M);
-    else DSG_LAUNCH(breakup_ln_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, s, y, g, b, pg, pb, z, res, D, M);
+    if (out_bf16) DSG_LAUNCH(breakup_ln_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, s, y, g, b, pg, pb, z, res, D, M, run_list, run_cnt);
+    else DSG_LAUNCH(breakup_ln_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, s, y, g, b, pg, pb, z, res, D, M, run_list, run_cnt);
 }
 
 // PositionalEmbedding (diffusesg.py:507-513): freqs = (1/10000)^(k/(E/2)); [cos(x f), sin(x f)]
@@ -2414,6 +2532,120 @@ void launch_decode(const float *adj, const float *node, const uint8_t *flags, in
     const size_t n = (size_t)d.B * d.N * d.N + (size_t)d.B * d.N;
     DSG_LAUNCH(decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, adj, node, flags, enc_adj, enc_node, n_adj_type,
                n_node_type, node_chans, out_adj, out_node, out_bbox, d);
+}
+
+// =================================================================================================
+// Need lists of the masked-token pruning (NeedPlan in kernels.h).  DiffuseSG.forward masks everything it returns with
+// node_flags (diffusesg.py:806-825), so only the last-level tokens (i, j) with flag_i && flag_j matter; walking the up path
+// backwards, a token is needed iff it lies in a window that a needed token of the next stage lies in (window attention itself is
+// unmasked, diffusesg.py:108-139).  One block per sample runs the plan's ops on a byte map of 8-token runs in LDS.  Phase 0 leaves
+// the per-sample entry counts, phase 1 writes every list compacted in (sample, run) order -- deterministic -- plus the totals and
+// the -1 padding of the last tile.
+// =================================================================================================
+template <int PHASE>
+__global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restrict__ flags, int B, int N, NeedPlan plan,
+                                                         int *__restrict__ cnt_ps, int *__restrict__ lists, int *__restrict__ cnt) {
+    __shared__ uint8_t map_a[NEED_MAX_RUNS], map_b[NEED_MAX_RUNS], win[NEED_MAX_RUNS / 8];
+    __shared__ int scan[257];
+    __shared__ int base_part[8][NEED_MAX_LISTS];
+    __shared__ int base[NEED_MAX_LISTS];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    uint8_t *cur = map_a, *nxt = map_b;
+    if (PHASE == 1) {   // entries of the samples in front of this one, per list
+        const int l = tid & (NEED_MAX_LISTS - 1), sl = tid / NEED_MAX_LISTS;
+        int acc = 0;
+        if (l < plan.n_lists)
+            for (int bb = sl; bb < b; bb += 8) acc += cnt_ps[bb * plan.n_lists + l];
+        base_part[sl][l] = acc;
+        __syncthreads();
+        if (tid < NEED_MAX_LISTS) {
+            int t = 0;
+            for (int k = 0; k < 8; k++) t += base_part[k][tid];
+            base[tid] = t;
+        }
+        __syncthreads();
+    }
+    // compact the set bits of bits[0, n) into list L as id0 + index, in index order
+    auto emit = [&](const uint8_t *bits, int n, int L, int id0) {
+        const int per = (n + 255) / 256, lo = min(tid * per, n), hi = min(lo + per, n);
+        int c = 0;
+        for (int k = lo; k < hi; k++) c += bits[k] ? 1 : 0;
+        scan[tid + 1] = c;
+        __syncthreads();
+        if (tid == 0) { scan[0] = 0; for (int k = 1; k <= 256; k++) scan[k] += scan[k - 1]; }
+        __syncthreads();
+        const int total = scan[256];
+        if (PHASE == 0) {
+            if (tid == 0) cnt_ps[b * plan.n_lists + L] = total;
+        } else {
+            int *dst = lists + plan.list_off[L] + base[L];
+            int o = scan[tid];
+            for (int k = lo; k < hi; k++) if (bits[k]) dst[o++] = id0 + k;
+            if (b == B - 1) {
+                const int all = base[L] + total, padded = (all + 15) / 16 * 16;
+                for (int k = all + tid; k < padded; k += 256) lists[plan.list_off[L] + k] = -1;
+                if (tid == 0) cnt[L] = all;
+            }
+        }
+        __syncthreads();
+    };
+    {   // last-level output need: runs (i, 8 consecutive j) that hold a valid pair
+        const int rpr = N / 8;
+        for (int idx = tid; idx < N * rpr; idx += 256) {
+            const int i = idx / rpr, jr = idx - i * rpr;
+            bool any = false;
+            for (int k = 0; k < 8; k++) any = any || flags[(size_t)b * N + jr * 8 + k] != 0;
+            cur[idx] = (flags[(size_t)b * N + i] != 0 && any) ? 1 : 0;
+        }
+        __syncthreads();
+    }
+    for (int o = 0; o < plan.n_ops; o++) {
+        const NeedOp op = plan.op[o];
+        const int res = op.res, rpr = res / 8;
+        if (op.kind == NEED_EMIT) {
+            emit(cur, res * rpr, op.list, b * res * rpr);
+        } else if (op.kind == NEED_WINDOWS) {
+            // windows of the (cyclically shifted) partition that hold a needed run; then every run those windows touch
+            const int nwr = res / 8, nW = nwr * nwr, sh = op.shift;
+            for (int w = tid; w < nW; w += 256) {
+                const int wi = w / nwr, wj = w - wi * nwr;
+                const int j0 = ((wj * 8 + sh) % res) / 8, j1 = ((wj * 8 + sh + 7) % res) / 8;
+                bool any = false;
+                for (int pi = 0; pi < 8; pi++) {
+                    const int ti = (wi * 8 + pi + sh) % res;
+                    any = any || cur[ti * rpr + j0] || cur[ti * rpr + j1];
+                }
+                win[w] = any ? 1 : 0;
+            }
+            __syncthreads();
+            if (op.list >= 0) emit(win, nW, op.list, b * nW);
+            for (int idx = tid; idx < res * rpr; idx += 256) {
+                const int ti = idx / rpr, jr = idx - ti * rpr;
+                const int wi = ((ti - sh + res) % res) / 8;
+                const int w0 = ((jr * 8 - sh + res) % res) / 8, w1 = ((jr * 8 + 7 - sh + res) % res) / 8;
+                nxt[idx] = (win[wi * nwr + w0] || win[wi * nwr + w1]) ? 1 : 0;
+            }
+            __syncthreads();
+            uint8_t *t = cur; cur = nxt; nxt = t;
+        } else {   // NEED_PARENT: res is the fine side; coarse runs that hold the parent (i/2, j/2) of a needed token
+            const int rc = res / 2, rprc = rc / 8;
+            for (int idx = tid; idx < rc * rprc; idx += 256) {
+                const int ci = idx / rprc, cjr = idx - ci * rprc;
+                bool any = false;
+                for (int d = 0; d < 2; d++)
+                    for (int e = 0; e < 2; e++) any = any || cur[(2 * ci + d) * rpr + 2 * cjr + e];
+                nxt[idx] = any ? 1 : 0;
+            }
+            __syncthreads();
+            uint8_t *t = cur; cur = nxt; nxt = t;
+        }
+    }
+}
+
+void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s) {
+    if (plan.n_lists < 1) return;
+    DSG_LAUNCH(need_lists_kernel<0>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt);
+    DSG_LAUNCH(need_lists_kernel<1>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt);
 }
 
 }  // namespace dsg

@@ -15,7 +15,7 @@ EXPORTS = [
     "dsg_create", "dsg_destroy", "dsg_last_error", "dsg_version", "dsg_abi_version", "dsg_set_weight", "dsg_finalize_weights",
     "dsg_num_weight_keys", "dsg_weight_key", "dsg_workspace_bytes", "dsg_denoise", "dsg_precond", "dsg_sample",
     "dsg_sigma_schedule", "dsg_debug_tap", "dsg_debug_clear_taps", "dsg_decode_bits", "dsg_decode", "dsg_profile_forward", "dsg_set_option",
-    "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz",
+    "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
 ]
@@ -100,6 +100,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_debug_tap.argtypes = [vp, C.c_char_p, vp, i64]
     L.dsg_debug_clear_taps.argtypes = [vp]
     L.dsg_debug_clear_taps.restype = None
+    L.dsg_debug_need_lists.argtypes = [vp, i32, vp, i32, C.POINTER(i32), vp, i64, vp]
     L.dsg_set_option.argtypes = [vp, C.c_char_p, i32]
     L.dsg_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
     L.dsg_gen_noise.argtypes = [vp, i32, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
@@ -222,6 +223,24 @@ class Handle:
         v = C.c_int32(0)
         self.check(self.L.dsg_get_option(self._h, name.encode(), C.byref(v)), f"dsg_get_option({name})")
         return int(v.value)
+
+    def need_lists(self, B: int, stream=None):
+        """Need lists of the masked-token pruning as the flags last staged for batch B left them (dsg_debug_need_lists): a list of
+        dicts {kind ('runs' | 'windows'), res, shift, stage, block, full, entries (int32 array)}; [] when the configuration is not
+        covered.  A run is 8 consecutive token rows (entry = first row / 8), a window entry is b * nW + window."""
+        import numpy as np
+        n = C.c_int32(0)
+        self.check(self.L.dsg_debug_need_lists(self._h, B, None, 0, C.byref(n), None, 0, stream), "dsg_debug_need_lists")
+        if n.value == 0:
+            return []
+        roles = np.zeros((n.value, 8), np.int32)
+        self.check(self.L.dsg_debug_need_lists(self._h, B, roles.ctypes.data, n.value, C.byref(n), None, 0, stream), "dsg_debug_need_lists")
+        total = int(roles[:, 5].sum())
+        ents = np.zeros(max(total, 1), np.int32)
+        self.check(self.L.dsg_debug_need_lists(self._h, B, roles.ctypes.data, n.value, C.byref(n), ents.ctypes.data, total, stream),
+                   "dsg_debug_need_lists")
+        return [dict(kind="windows" if r[0] else "runs", res=int(r[1]), shift=int(r[2]), stage=int(r[3]), block=int(r[4]),
+                     full=int(r[7]), entries=ents[int(r[6]):int(r[6]) + int(r[5])].copy()) for r in roles]
 
     def precision_mode(self) -> str:
         """'f32' | 'f32-split' | 'bf16': the GEMM arithmetic the handle will actually run (options or DSG_* env defaults)."""

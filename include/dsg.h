@@ -155,6 +155,8 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *   "fused_attn" (C=96 attention block), "fused_mlp", "fused_mlp_maxc" (96|192), "fused_readout", "fused_patch_embed",
  *   "fused_rowstats" (modulate+SiLU and LayerNorm statistics in the producing GEMM's epilogue instead of row kernels),
  *   "fused_qkv_attn" (8x8 / 10x10 windows: QKV projection + window attention in one kernel, q/k/v never reach HBM),
+ *   "prune_masked" (default 1): the up path computes only rows / windows that can reach an unmasked output (see
+ *       dsg_debug_need_lists below); 0: every row.  Bit-identical results either way.
  *   "fused_merge" (PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path; 1: where it pays (>= 8192 merged
  *   rows), 2: at every size, 0: merge_ln kernel).
  * Reverse loop: "loop_graph" = 1 (default): dsg_sample replays one captured hipGraph per step (a handful of distinct step bodies:
@@ -198,6 +200,18 @@ double dsg_profile_clock_ghz(dsg_handle h);
 
 /* Debug: copy the named stage's activation (e.g. "down0.block0") of the next dsg_denoise call to
  * `dst` (device, capacity in floats).  Token-major [B, T, C]. */
+/* Masked-token pruning (option "prune_masked", default 1).  Everything a forward returns is masked with the node flags, so on the
+ * up path only tokens that share a window with a needed token of the following stage are computed; the lists of needed 8-token runs /
+ * windows are derived on the device whenever flags are staged (dsg_denoise, dsg_precond, dsg_sample).  Results are unchanged bit for
+ * bit.  Rows nobody reads are left STALE in the workspace activations, so workspace intermediates are only meaningful through
+ * dsg_debug_tap -- which, like the split / bf16 modes and 10 x 10 windows, switches the pruning off (dsg_get_option reports what runs).
+ * dsg_debug_need_lists copies the lists that the flags last staged for batch B produced to HOST buffers: *n_roles rows of
+ * roles [max_roles][8] = {kind (0: list of runs = 8 consecutive token rows, entry b * res * res / 8 + run; 1: list of windows, entry
+ * b * nW + window), res, shift, up stage, block (>= 0: a Swin block's proj / MLP rows resp. attention windows; -1: the stage's post_linear
+ * rows; -2: its pre_linear / breakup rows, on the coarser grid), count, offset of the entries in lists_out, entries when nothing is
+ * masked}.  roles == NULL only returns *n_roles (0 when the configuration is not covered). */
+int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_roles, int32_t *n_roles, int32_t *lists_out,
+                         int64_t lists_cap, void *stream);
 int dsg_debug_tap(dsg_handle h, const char *stage, float *dst, int64_t capacity);
 void dsg_debug_clear_taps(dsg_handle h);
 
