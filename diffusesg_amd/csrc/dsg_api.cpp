@@ -83,6 +83,11 @@ struct Workspace {
     // sampler state
     float *x_adj, *x_node, *xh_adj, *xh_node, *sig;
     float *d_adj[3], *d_node[3];
+    // conditional sampling (dsg_sample_known): the library's own copy of the caller's known tensors and element masks, state layouts;
+    // allocated by the first conditioned call at this batch size.  Captured step bodies bake these addresses, never the caller's
+    float *kn_adj = nullptr, *kn_node = nullptr;
+    uint8_t *km_adj = nullptr, *km_node = nullptr;
+    size_t known_bytes = 0;
     // batch-uniform noise level (the sampler): every sample shares one (scale,shift) row, taken from a table that
     // dsg_sample computes once for all steps; aff_ld == 0 broadcasts row 0 of `aff`
     bool uniform = false;
@@ -1735,13 +1740,24 @@ struct StepPlan {
     int s1, s2;           // d_* buffers receiving the stage-1 / stage-2 denoised outputs
     bool euler;           // Euler update (solver 'euler', or the last step: edm.py:394-396), else Heun
     bool coin1, coin2;    // outcome of the self-conditioning coin of each preconditioned call (precond.py:90)
-    int key() const { return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8); }
+    bool known = false;   // conditional sampling: every D goes through the known-entry select (w->kn_* / w->km_*)
+    int key() const {
+        return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8) | ((int)known << 9);
+    }
 };
+
+// D = mask(c_skip x + c_out F) at sigma[step]; known: with the select of the conditioned loop in front of the store
+void precond_out_step(dsg_handle h, Workspace *w, CStatePtrs x, StatePtrs dst, bool known, const Dims &d, hipStream_t s) {
+    const CStatePtrs F{w->f_adj, w->f_node};
+    if (known) launch_precond_out_tab_known(x, F, h->tab_step, w->ctl, w->flags, CStatePtrs{w->kn_adj, w->kn_node}, CMaskPtrs{w->km_adj, w->km_node}, dst, d, s);
+    else launch_precond_out_tab(x, F, h->tab_step, w->ctl, w->flags, dst, d, s);
+}
 
 // NodeAdjPrecond.forward at sigma[step] on workspace state x -> dst; forwards run inline on `s` (capturable)
 // fwd_graph: replay the captured network forward (round-1 scheme: only the forward is a graph, the loop is host-enqueued)
+// known: conditional sampling -- both D writes (the extra self-conditioning pass's too) take the known entries from the workspace
 int precond_tab(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, const float *sc_node, bool coin, StatePtrs dst,
-                hipStream_t s, int *nfe, bool fwd_graph) {
+                hipStream_t s, int *nfe, bool fwd_graph, bool known) {
     const Dims d = dims_of(h, w->B);
     w->uniform = true;
     launch_precond_in_tab(x, h->tab_step, w->ctl, StatePtrs{w->in_adj, w->in_node}, d, s);
@@ -1754,13 +1770,13 @@ int precond_tab(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, c
     if (h->cfg.self_condition && coin) {  // precond.py:90-98: the D of the extra pass becomes the self-cond input
         if (int rc = run_forward(h, w, fwd_graph, s)) return rc;
         (*nfe)++;
-        launch_precond_out_tab(x, CStatePtrs{w->f_adj, w->f_node}, h->tab_step, w->ctl, w->flags, StatePtrs{w->sc_adj, w->sc_node}, d, s);
+        precond_out_step(h, w, x, StatePtrs{w->sc_adj, w->sc_node}, known, d, s);
         if (fwd_graph) HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)w->has_sc, 1, 1, s));
         else { w->cur_sc_adj = w->sc_adj; w->cur_sc_node = w->sc_node; }
     }
     if (int rc = run_forward(h, w, fwd_graph, s)) return rc;
     (*nfe)++;
-    launch_precond_out_tab(x, CStatePtrs{w->f_adj, w->f_node}, h->tab_step, w->ctl, w->flags, dst, d, s);
+    precond_out_step(h, w, x, dst, known, d, s);
     return 0;
 }
 
@@ -1773,7 +1789,7 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
     if (!gt_adj) {
         launch_step_row(h->tab_aff, h->aff_n, w->ctl, w->aff, s);   // this step's (scale,shift) row for every block
         if (int rc = precond_tab(h, w, xh, p.sc_slot >= 0 ? w->d_adj[p.sc_slot] : nullptr, p.sc_slot >= 0 ? w->d_node[p.sc_slot] : nullptr,
-                                 p.coin1, StatePtrs{w->d_adj[p.s1], w->d_node[p.s1]}, s, nfe, fwd_graph)) return rc;
+                                 p.coin1, StatePtrs{w->d_adj[p.s1], w->d_node[p.s1]}, s, nfe, fwd_graph, p.known)) return rc;
         D1 = CStatePtrs{w->d_adj[p.s1], w->d_node[p.s1]};
     }
     if (p.euler) {
@@ -1783,7 +1799,7 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
         if (!gt_adj) {   // stage 2 re-evaluates at (x_hat, sigma(t_hat)) with self-cond = D1 (edm.py:400-405)
             const bool sc = h->cfg.self_condition;
             if (int rc = precond_tab(h, w, xh, sc ? w->d_adj[p.s1] : nullptr, sc ? w->d_node[p.s1] : nullptr, p.coin2,
-                                     StatePtrs{w->d_adj[p.s2], w->d_node[p.s2]}, s, nfe, fwd_graph)) return rc;
+                                     StatePtrs{w->d_adj[p.s2], w->d_node[p.s2]}, s, nfe, fwd_graph, p.known)) return rc;
             D2 = CStatePtrs{w->d_adj[p.s2], w->d_node[p.s2]};
         }
         launch_heun_tab(xh, D1, D2, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
@@ -1810,8 +1826,8 @@ int ensure_step_graph(dsg_handle h, Workspace *w, const StepPlan &p) {
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(h, DSG_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
     w->step_graphs.emplace(p.key(), std::make_pair(exec, n));
-    if (getenv("DSG_GRAPH_VERBOSE")) fprintf(stderr, "[dsg-graph] captured step body key=%d (sc %d s1 %d s2 %d euler %d coins %d%d): %d forwards\n",
-                                             p.key(), p.sc_slot, p.s1, p.s2, (int)p.euler, (int)p.coin1, (int)p.coin2, n);
+    if (getenv("DSG_GRAPH_VERBOSE")) fprintf(stderr, "[dsg-graph] captured step body key=%d (sc %d s1 %d s2 %d euler %d coins %d%d known %d): %d forwards\n",
+                                             p.key(), p.sc_slot, p.s1, p.s2, (int)p.euler, (int)p.coin1, (int)p.coin2, (int)p.known, n);
     return 0;
 }
 
@@ -1834,7 +1850,9 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     size_t need = 0;   // the need lists of the masked-token pruning: every list + 16 pad entries, counts, per-sample counts
     const PrunePlan &pp = prune_plan(h);
     for (int k = 0; k < pp.np.n_lists; k++) need += sizeof(int) * ((size_t)B * pp.items[k] + 16 + 1 + (size_t)B);
-    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need;
+    auto it = h->ws.find(B);   // + the known tensors and masks of dsg_sample_known, once a conditioned call has allocated them
+    const size_t known = it != h->ws.end() ? it->second->known_bytes : 0;
+    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need + known;
 }
 
 int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
@@ -1995,10 +2013,18 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *c, double *sigma_steps, float *t_h
     return DSG_OK;
 }
 
-int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags, const float *init_adj,
-               const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
-               const float *gt_adj, const float *gt_node, const int32_t *snap_steps, int32_t n_snap, float *snap_adj,
-               float *snap_node, float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// the caller's known tensors and element masks of a conditioned run
+struct KnownArgs { const float *adj, *node; const uint8_t *mask_adj, *mask_node; };
+
+// dsg_sample (known == nullptr) and dsg_sample_known: one reverse loop
+int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags, const float *init_adj,
+                const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
+                const float *gt_adj, const float *gt_node, const KnownArgs *known, const int32_t *snap_steps, int32_t n_snap,
+                float *snap_adj, float *snap_node, float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
     if (int rc = check_ready(h, B)) return rc;
     if (!cfg || !flags || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null argument");
     if ((init_adj == nullptr) != (init_node == nullptr)) return fail(h, DSG_ERR_INVALID, "init_adj/init_node must both be given");
@@ -2060,6 +2086,27 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
         launch_cnoise(h->tab_sig, h->tab_cn, T, s);
         embed_rows(h, h->tab_cn, T, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff, s);
     }
+    if (known) {
+        // the known tensors and masks move into workspace-owned buffers: conditioned step bodies bake these addresses and must not
+        // reference caller memory.  Staged on the caller's stream ahead of the synchronise below, i.e. before any body is captured
+        if (!w->kn_adj) {
+            void *q;
+            if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sa)) return rc;
+            w->kn_adj = (float *)q;
+            if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sn)) return rc;
+            w->kn_node = (float *)q;
+            if (int rc = dev_alloc(h, w->allocs, &q, sa)) return rc;
+            w->km_adj = (uint8_t *)q;
+            if (int rc = dev_alloc(h, w->allocs, &q, sn)) return rc;
+            w->km_node = (uint8_t *)q;
+            w->known_bytes = (sizeof(float) + 1) * (sa + sn);
+            w->bytes += w->known_bytes;
+        }
+        HIP_TRY(h, hipMemcpyAsync(w->kn_adj, known->adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(w->kn_node, known->node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(w->km_adj, known->mask_adj, sa, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(w->km_node, known->mask_node, sn, hipMemcpyDeviceToDevice, s));
+    }
     HIP_TRY(h, hipStreamSynchronize(s));  // the host vectors above must outlive their async copies; once per sample() call
     // the static plan of every step (edm.py:350-427): buffer rotation, Euler/Heun update, the pre-drawn coins
     std::vector<StepPlan> plans(T);
@@ -2073,6 +2120,7 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
             p.s1 = free_slot(sc_slot, -1);
             p.s2 = free_slot(p.s1, -1);
             p.euler = !cfg->heun || i == T - 1;   // edm.py:394-396
+            p.known = known != nullptr;
             p.coin1 = !gt_adj && coin_buf[call] != 0;
             p.coin2 = !gt_adj && !p.euler && coin_buf[call + 1] != 0;
             if (!gt_adj) call += p.euler ? 1 : 2;
@@ -2099,6 +2147,32 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
     h->last_stats.net_forwards = nfe;
     if (stats) *stats = h->last_stats;
     return DSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags, const float *init_adj,
+               const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
+               const float *gt_adj, const float *gt_node, const int32_t *snap_steps, int32_t n_snap, float *snap_adj,
+               float *snap_node, float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
+    return sample_impl(h, cfg, B, flags, init_adj, init_node, noise_adj, noise_node, coins, seed, gt_adj, gt_node, nullptr, snap_steps,
+                       n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+}
+
+int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags, const float *init_adj,
+                     const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
+                     const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                     const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
+                     dsg_sample_stats *stats, void *stream) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!known_adj || !known_node || !mask_adj || !mask_node)
+        return fail(h, DSG_ERR_INVALID, "dsg_sample_known needs known_adj, known_node, mask_adj and mask_node (%s is NULL)",
+                    !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
+    const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
+    return sample_impl(h, cfg, B, flags, init_adj, init_node, noise_adj, noise_node, coins, seed, nullptr, nullptr, &known, snap_steps,
+                       n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
 }
 
 int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_kind, int64_t *launches_by_kind,
@@ -3061,6 +3135,29 @@ int dsg_decode(dsg_handle h, int32_t B, const float *adj, const float *node, con
         (node_encoding == DSG_ENC_BITS && (node_chans > 30 || (1 << node_chans) < n_node_type)))
         return fail(h, DSG_ERR_INVALID, "node encoding %d with %d types does not fit %d attribute channels", node_encoding, n_node_type, node_chans);
     launch_decode(adj, node, flags, edge_encoding, node_encoding, n_adj_type, n_node_type, node_chans, out_adj, out_node, out_bbox,
+                  dims_of(h, B), (hipStream_t)stream);
+    HIP_TRY(h, hipGetLastError());
+    return DSG_OK;
+}
+
+int dsg_encode(dsg_handle h, int32_t B, const int32_t *q_adj, const int32_t *q_node, const float *bbox, const uint8_t *flags,
+               int32_t edge_encoding, int32_t node_encoding, int32_t n_adj_type, int32_t n_node_type, int32_t node_chans, float *out_adj,
+               float *out_node, void *stream) {
+    if (!h || B < 1) return fail(h, DSG_ERR_INVALID, "batch must be >= 1");
+    if (!q_adj || !q_node || !flags || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null tensor");
+    if (edge_encoding < DSG_ENC_BITS || edge_encoding > DSG_ENC_DDPM || node_encoding < DSG_ENC_BITS || node_encoding > DSG_ENC_DDPM)
+        return fail(h, DSG_ERR_INVALID, "encoding must be DSG_ENC_BITS, DSG_ENC_ONE_HOT or DSG_ENC_DDPM");
+    if (n_adj_type < 2 || n_node_type < 2) return fail(h, DSG_ERR_INVALID, "fewer than two types");
+    if (node_chans < 1 || node_chans > h->Cn || (bbox && h->Cn < node_chans + 4))
+        return fail(h, DSG_ERR_INVALID, "node_chans %d does not fit C_node %d%s", node_chans, h->Cn, bbox ? " with four bbox channels" : "");
+    // the channel counts an encoding implies, as dsg_decode checks them
+    if ((edge_encoding == DSG_ENC_ONE_HOT && h->Ca != n_adj_type) || (edge_encoding == DSG_ENC_DDPM && h->Ca != 1) ||
+        (edge_encoding == DSG_ENC_BITS && (h->Ca > 30 || (1 << h->Ca) < n_adj_type)))
+        return fail(h, DSG_ERR_INVALID, "edge encoding %d with %d types does not fit %d adjacency channels", edge_encoding, n_adj_type, h->Ca);
+    if ((node_encoding == DSG_ENC_ONE_HOT && node_chans != n_node_type) || (node_encoding == DSG_ENC_DDPM && node_chans != 1) ||
+        (node_encoding == DSG_ENC_BITS && (node_chans > 30 || (1 << node_chans) < n_node_type)))
+        return fail(h, DSG_ERR_INVALID, "node encoding %d with %d types does not fit %d attribute channels", node_encoding, n_node_type, node_chans);
+    launch_encode(q_adj, q_node, bbox, flags, edge_encoding, node_encoding, n_adj_type, n_node_type, node_chans, out_adj, out_node,
                   dims_of(h, B), (hipStream_t)stream);
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;

@@ -234,6 +234,11 @@ void launch_precond_in_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, 
 // D = mask(c_skip*x + c_out*F) at sigma[step]
 void launch_precond_out_tab(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs D, Dims d,
                             hipStream_t s);
+// conditional sampling: the same D with a per-element select in front of the store -- mask ? known : c_skip*x + c_out*F (0 at padded
+// entries); mask_adj / mask_node uint8 in the state layouts, nonzero = known.  A select, not a blend: known arrives bit-exact in D
+struct CMaskPtrs { const uint8_t *adj; const uint8_t *node; };
+void launch_precond_out_tab_known(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, CStatePtrs known,
+                                  CMaskPtrs mask, StatePtrs D, Dims d, hipStream_t s);
 void launch_euler_tab(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d,
                       hipStream_t s);
 void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
@@ -308,5 +313,9 @@ void launch_rainbow_loss_backward(CStatePtrs pred, CStatePtrs tgt, const uint8_t
 // post-decode of the samples; enc_*: 0 'bits', 1 'one_hot', 2 'ddpm' (DSG_ENC_* of dsg.h); node_chans = attribute channels of a node row
 void launch_decode(const float *adj, const float *node, const uint8_t *flags, int enc_adj, int enc_node, int n_adj_type, int n_node_type,
                    int node_chans, int32_t *out_adj, int32_t *out_node, float *out_bbox, Dims d, hipStream_t s);
+// the inverse: integer graphs (q_adj [B,N,N], q_node [B,N], bbox [B,N,4] in [0,1] or null) -> the network's value space, out_adj
+// [B,Ca,N,N], out_node [B,N,Cn] (attribute in the first node_chans channels, bbox in the last four, channels in between 0)
+void launch_encode(const int32_t *q_adj, const int32_t *q_node, const float *bbox, const uint8_t *flags, int enc_adj, int enc_node,
+                   int n_adj_type, int n_node_type, int node_chans, float *out_adj, float *out_node, Dims d, hipStream_t s);
 
 }  // namespace dsg

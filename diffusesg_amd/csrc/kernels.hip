@@ -2169,6 +2169,32 @@ void launch_precond_out_tab(CStatePtrs x, CStatePtrs F, const StepRow *tab, cons
     const size_t n = total_elems(d);
     DSG_LAUNCH(precond_out_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, F, tab, ctl, flags, D, d);
 }
+// conditional sampling (dsg_sample_known): the same D, with a select in front of the store.  Where the element mask is set the
+// denoised estimate IS the known value -- copied, not blended, so it arrives bit-exact -- and known entries of the state then
+// follow known + t * eps like the sanity-check mode's (edm.py:372-377) do everywhere.  A separate kernel: the unconditioned
+// path keeps launching the one above.
+__global__ void precond_out_tab_known_kernel(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
+                                             CStatePtrs known, CMaskPtrs mask, StatePtrs D, Dims d) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total_elems(d)) return;
+    const ElemIdx e = elem_index(idx, d, flags);
+    const float s = tab[ctl->step].sigma;
+    const float s2 = FADD(FMUL(s, s), 0.25f);
+    const float c_skip = __fdiv_rn(0.25f, s2);                                       // objectives/edm.py:123
+    const float c_out = __fdiv_rn(FMUL(s, 0.5f), __fsqrt_rn(s2));                    // objectives/edm.py:124
+    const float xv = e.is_adj ? x.adj[e.off] : x.node[e.off];
+    const float fv = e.is_adj ? F.adj[e.off] : F.node[e.off];
+    const bool is_known = (e.is_adj ? mask.adj[e.off] : mask.node[e.off]) != 0;
+    const float kv = e.is_adj ? known.adj[e.off] : known.node[e.off];
+    const float net = FADD(FMUL(c_skip, xv), FMUL(c_out, fv));                       // precond.py:102-105
+    const float v = e.valid ? (is_known ? kv : net) : 0.f;
+    if (e.is_adj) D.adj[e.off] = v; else D.node[e.off] = v;
+}
+void launch_precond_out_tab_known(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, CStatePtrs known,
+                                  CMaskPtrs mask, StatePtrs D, Dims d, hipStream_t s) {
+    const size_t n = total_elems(d);
+    DSG_LAUNCH(precond_out_tab_known_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, F, tab, ctl, flags, known, mask, D, d);
+}
 __global__ void euler_tab_kernel(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs x,
                                  Dims d) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2532,6 +2558,45 @@ void launch_decode(const float *adj, const float *node, const uint8_t *flags, in
     const size_t n = (size_t)d.B * d.N * d.N + (size_t)d.B * d.N;
     DSG_LAUNCH(decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, adj, node, flags, enc_adj, enc_node, n_adj_type,
                n_node_type, node_chans, out_adj, out_node, out_bbox, d);
+}
+
+// The inverse of decode_kernel: integer graphs -> the network's value space, the on-device attribute_converter(in_encoding='int',
+// out_encoding=...) (R/utils/attribute_code.py:240-304) plus the data loader's bbox shift (dataloader.py:168):
+//   bits    dec2bin MSB-first (:307-316) -> 2 b - 1          one_hot  2 onehot - 1 (:295-300)
+//   ddpm    2 i / (k - 1) - 1 (:251), float32 op by op: the int64 tensor is promoted to float32 before the division
+// Rows / columns of padded nodes are 0 (mask_adjs / mask_nodes); the diagonal is encoded like any other entry, as the reference
+// does.  Node rows: attribute in the first node_chans channels, (b - 0.5) * 2 in the last four when bbox is given, 0 elsewhere.
+__device__ __forceinline__ float encode_value(int q, int c, int chans, int enc, int n_type) {
+    if (enc == 0) return ((q >> (chans - 1 - c)) & 1) ? 1.0f : -1.0f;
+    if (enc == 1) return c == q ? 1.0f : -1.0f;
+    return FSUB(__fdiv_rn((float)(2 * q), (float)(n_type - 1)), 1.0f);
+}
+__global__ void encode_kernel(const int32_t *q_adj, const int32_t *q_node, const float *bbox, const uint8_t *flags, int enc_adj,
+                              int enc_node, int n_adj_type, int n_node_type, int node_chans, float *out_adj, float *out_node, Dims d) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total_elems(d)) return;
+    const ElemIdx e = elem_index(idx, d, flags);
+    if (e.is_adj) {
+        const size_t cs = (size_t)d.N * d.N;
+        const int c = (int)((e.off / cs) % d.Ca);
+        const size_t ij = e.off % cs;
+        out_adj[e.off] = e.valid ? encode_value(q_adj[(size_t)e.b * cs + ij], c, d.Ca, enc_adj, n_adj_type) : 0.f;
+    } else {
+        const int c = (int)(e.off % d.Cn);
+        const size_t m = e.off / d.Cn;   // b * N + i
+        float v = 0.f;
+        if (e.valid) {
+            if (c < node_chans) v = encode_value(q_node[m], c, node_chans, enc_node, n_node_type);
+            else if (bbox && c >= d.Cn - 4) v = FMUL(FSUB(bbox[m * 4 + (c - (d.Cn - 4))], 0.5f), 2.0f);
+        }
+        out_node[e.off] = v;
+    }
+}
+void launch_encode(const int32_t *q_adj, const int32_t *q_node, const float *bbox, const uint8_t *flags, int enc_adj, int enc_node,
+                   int n_adj_type, int n_node_type, int node_chans, float *out_adj, float *out_node, Dims d, hipStream_t s) {
+    const size_t n = total_elems(d);
+    DSG_LAUNCH(encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q_adj, q_node, bbox, flags, enc_adj, enc_node, n_adj_type,
+               n_node_type, node_chans, out_adj, out_node, d);
 }
 
 // =================================================================================================

@@ -5,6 +5,7 @@
     optionally with DDP's 'module.' prefix.  Loaded with weights_only=True (nothing from the file is executed).
   * weight selection   R/eval.py:15-40 (get_ema_weight_keywords), R/utils/sampling_utils.py:34-60 (load_model).
   * post-decode        R/runner/sampler/sampler_node_adj.py:194-311 -> dsg_decode_bits on the device.
+  * encode              R/utils/attribute_code.py:240-304 ('int' -> encoding) -> dsg_encode on the device (known values of a completion).
   * sample archive     R/runner/sampler/sampler_node_adj.py:395-407 (final_samples_array_before_eval.npz keys), which
     R/helper/eval_sg_samples.py and the reference's CPU metrics consume as-is.
 """
@@ -151,6 +152,37 @@ def decode(net, adj: torch.Tensor, node: torch.Tensor, node_flags: torch.Tensor,
                            int(n_adj_type), int(n_node_type), node_chans, qa.data_ptr(), qn.data_ptr(),
                            None if bb is None else bb.data_ptr(), C.c_void_p(st)), "dsg_decode")
     return qa, qn, bb
+
+
+def encode(net, q_adj: torch.Tensor, q_node: torch.Tensor, bbox: Optional[torch.Tensor], node_flags: torch.Tensor, n_adj_type: int,
+           n_node_type: int, edge_encoding: str = "bits", node_encoding: str = "bits"):
+    """The inverse of `decode`, on the device (dsg_encode <-> attribute_converter(in_encoding='int', ...), R/utils/attribute_code.py:
+    240-304, and the data loader's bbox shift, R/utils/dataloader.py:168): integer graphs q_adj [B,N,N], q_node [B,N] and bbox [B,N,4]
+    in [0,1] (None: the network has no bbox channels) -> (adj [B,C_adj,N,N], node [B,N,C_node]) float32 in the network's value
+    space -- what `NodeAdjEDMSamplerHip.sample_known` takes as known values.  `net`: a DiffuseSGHip, the precond wrapper or a bare
+    `lib.Handle`, as for `decode`."""
+    from .lib import ENCODINGS, Handle
+    for e in (edge_encoding, node_encoding):
+        if e not in ENCODINGS:
+            raise ValueError("encoding should be 'int', 'ddpm', 'bits' or 'one_hot'")   # attribute_code.py:57
+    if isinstance(net, Handle):
+        h, cfg, dev = net, net.cfg, torch.device("cuda", torch.cuda.current_device())
+    else:
+        m = getattr(net, "model", net)
+        h, cfg, dev = m._ensure_handle(), m.config, m._dev
+    B, n = node_flags.shape[0], cfg.max_node_num
+    qa = q_adj.to(device=dev).to(torch.int32).reshape(B, n, n).contiguous()
+    qn = q_node.to(device=dev).to(torch.int32).reshape(B, n).contiguous()
+    bb = None if bbox is None else bbox.to(device=dev, dtype=torch.float32).reshape(B, n, 4).contiguous()
+    fl = node_flags.to(device=dev).to(torch.uint8).contiguous()
+    node_chans = cfg.c_node - 4 if bbox is not None else cfg.c_node
+    a = torch.empty((B, cfg.c_adj, n, n), dtype=torch.float32, device=dev)
+    x = torch.empty((B, n, cfg.c_node), dtype=torch.float32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    h.check(h.L.dsg_encode(h.raw, B, qa.data_ptr(), qn.data_ptr(), None if bb is None else bb.data_ptr(), fl.data_ptr(),
+                           ENCODINGS[edge_encoding], ENCODINGS[node_encoding], int(n_adj_type), int(n_node_type), node_chans,
+                           a.data_ptr(), x.data_ptr(), C.c_void_p(st)), "dsg_encode")
+    return a, x
 
 
 def pack_decoded(q_adj: torch.Tensor, q_node: torch.Tensor, bbox: Optional[torch.Tensor], node_flags: torch.Tensor) -> torch.Tensor:

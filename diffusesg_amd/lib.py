@@ -18,7 +18,10 @@ EXPORTS = [
     "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
+    "dsg_sample_known", "dsg_encode",
 ]
+
+DSG_ERR_INVALID = -1   # dsg_status of include/dsg.h: bad argument / unsupported configuration
 
 
 class DsgError(RuntimeError):
@@ -96,6 +99,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_precond.argtypes = [vp, i32] + [vp] * 6 + [i32] + [vp] * 3
     L.dsg_sample.argtypes = [vp, C.POINTER(DsgSamplerCfg), i32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp,
                              vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
+    L.dsg_sample_known.argtypes = [vp, C.POINTER(DsgSamplerCfg), i32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp,
+                                   vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
     L.dsg_sigma_schedule.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, vp, vp]
     L.dsg_debug_tap.argtypes = [vp, C.c_char_p, vp, i64]
     L.dsg_debug_clear_taps.argtypes = [vp]
@@ -128,6 +133,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_profile_forward.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.dsg_decode_bits.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.dsg_decode.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.dsg_encode.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.dsg_eval_bbox_prep_bytes.argtypes = [i32, i32, i32]
     L.dsg_eval_bbox_prep_bytes.restype = C.c_size_t
     L.dsg_eval_bbox_prep.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]

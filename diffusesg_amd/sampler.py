@@ -165,6 +165,32 @@ class NodeAdjEDMSamplerHip(object):
                                    "only the sanity-check form, which bypasses the network, runs in float64)")
             return self._sample_sanity_double(model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes,
                                               flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, churn_noise, seed)
+        return self._sample_hip(model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, None,
+                                flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
+                                churn_noise, coins, seed, return_device)
+
+    @torch.no_grad()
+    def sample_known(self, model, node_flags, known_adjs, known_nodes, known_adj_mask, known_node_mask, *,
+                     init_adjs=None, init_nodes=None, flag_interim_adjs=False, max_num_interim_adjs=None,
+                     flag_node_multi_channel=False, flag_adj_multi_channel=False,
+                     num_node_chan=150, num_edge_chan=51, churn_noise=None, coins=None, seed=None, return_device=False):
+        """Conditional sampling (`dsg_sample_known`; not in the reference): `sample()` with the entries selected by the masks held at
+        the known values -- scene-graph completion, or layout generation when every label and relation is known and the boxes are not.
+        known_adjs / known_adj_mask: [B,C_adj,N,N], known_nodes / known_node_mask: [B,N,C_node] (or squeezed, [B,N,N] / [B,N], for
+        single-channel networks); masks are bool or integer, nonzero = known; the known values are in the network's value space
+        (`diffusesg_amd.io.encode`).  Everything else, and the return convention, as `sample()`: no entry known gives `sample()`'s
+        result bit for bit, every entry known its sanity-check mode's."""
+        if isinstance(model, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)):
+            model = model.module
+        return self._sample_hip(model, node_flags, init_adjs, init_nodes, None, None,
+                                (known_adjs, known_nodes, known_adj_mask, known_node_mask),
+                                flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
+                                churn_noise, coins, seed, return_device)
+
+    def _sample_hip(self, model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, known,
+                    flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
+                    churn_noise, coins, seed, return_device):
+        """The loop inside libdsg.so: `dsg_sample`, or `dsg_sample_known` when `known` = (adjs, nodes, adj mask, node mask)."""
         if not isinstance(model, NodeAdjPrecondHip):
             raise TypeError("NodeAdjEDMSamplerHip needs the NodeAdjPrecondHip network returned by build_network()")
         net = model.model
@@ -182,6 +208,23 @@ class NodeAdjEDMSamplerHip(object):
             init_adjs = init_nodes = None  # both are redrawn together (edm.py:325-329)
         ia, inn = prep(init_adjs, sa), prep(init_nodes, sn)
         ga, gn = prep(sanity_check_gt_adjs, sa), prep(sanity_check_gt_nodes, sn)
+        if known is not None:
+            # shapes are checked here, before anything is launched: the library only sees pointers
+            def prep_known(x, shape, what, dtype):
+                if x is None:
+                    return None   # the library refuses a missing tensor (DSG_ERR_INVALID)
+                full = tuple(shape)
+                squeezed = tuple(d for k, d in enumerate(shape) if not (d == 1 and k in (1, len(shape) - 1)))
+                if tuple(x.shape) not in (full, squeezed):
+                    raise ValueError(f"sample_known: {what} has shape {tuple(x.shape)}, expected {full}"
+                                     + (f" or {squeezed}" if squeezed != full else ""))
+                if dtype is torch.uint8:
+                    x = x != 0
+                return x.to(device=dev).to(dtype).reshape(shape).contiguous()
+            ka = prep_known(known[0], sa, "known_adjs", torch.float32)
+            kn = prep_known(known[1], sn, "known_nodes", torch.float32)
+            ma = prep_known(known[2], sa, "known_adj_mask", torch.uint8)
+            mn = prep_known(known[3], sn, "known_node_mask", torch.uint8)
         na = nn_ = None
         if churn_noise is not None:
             na, nn_ = prep(churn_noise[0], (T,) + sa), prep(churn_noise[1], (T,) + sn)
@@ -217,12 +260,18 @@ class NodeAdjEDMSamplerHip(object):
             ia = torch.empty(sa, dtype=torch.float32, device=dev)
             inn = torch.empty(sn, dtype=torch.float32, device=dev)
             h.check(h.L.dsg_gen_noise(h.raw, B, p(fl), C.c_uint64(seed_v), 0, p(ia), p(inn), C.c_void_p(st)), "dsg_gen_noise")
-        h.check(h.L.dsg_sample(h.raw, C.byref(scfg), B, p(fl), p(ia), p(inn), p(na), p(nn_),
-                               C.c_void_p(coins.ctypes.data), C.c_uint64(seed_v),
-                               p(ga), p(gn),
-                               C.c_void_p(0 if snap_steps is None else snap_steps.ctypes.data),
-                               0 if snap_steps is None else len(snap_steps), p(snap_a), p(snap_n),
-                               p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample")
+        snap_args = (C.c_void_p(0 if snap_steps is None else snap_steps.ctypes.data),
+                     0 if snap_steps is None else len(snap_steps), p(snap_a), p(snap_n))
+        if known is None:
+            h.check(h.L.dsg_sample(h.raw, C.byref(scfg), B, p(fl), p(ia), p(inn), p(na), p(nn_),
+                                   C.c_void_p(coins.ctypes.data), C.c_uint64(seed_v),
+                                   p(ga), p(gn), *snap_args,
+                                   p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample")
+        else:
+            h.check(h.L.dsg_sample_known(h.raw, C.byref(scfg), B, p(fl), p(ia), p(inn), p(na), p(nn_),
+                                         C.c_void_p(coins.ctypes.data), C.c_uint64(seed_v),
+                                         p(ka), p(kn), p(ma), p(mn), *snap_args,
+                                         p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample_known")
         self.last_stats = {"precond_calls": stats.precond_calls, "net_forwards": stats.net_forwards,
                            "graph_replays": stats.graph_replays}
         logging.info("Done with EDM-NodeAdj MCMC (HIP).")

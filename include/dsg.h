@@ -80,7 +80,7 @@ typedef struct dsg_sampler_cfg {
     int32_t reserved;
 } dsg_sampler_cfg;
 
-/* Counters of the last dsg_sample call. */
+/* Counters of the last dsg_sample / dsg_sample_known call. */
 typedef struct dsg_sample_stats {
     int64_t precond_calls;             /* 2T-1 (heun) or T (euler) */
     int64_t net_forwards;              /* precond_calls + number of coins that fired */
@@ -106,7 +106,8 @@ int dsg_finalize_weights(dsg_handle h);
 int dsg_num_weight_keys(dsg_handle h);
 const char *dsg_weight_key(dsg_handle h, int32_t i);
 
-/* Device bytes the library holds for batch size B (activations + sampler state). */
+/* Device bytes the library holds for batch size B (activations + sampler state; + the known tensors and masks of dsg_sample_known
+ * once a conditioned call has run at that batch size). */
 size_t dsg_workspace_bytes(dsg_handle h, int32_t B);
 
 /* DiffuseSG.forward: noise_labels[B] = c_noise; sc_adj / sc_node may be NULL (zeros). */
@@ -135,6 +136,32 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
                const float *gt_adj, const float *gt_node,
                const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
                float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream);
+
+/* Conditional sampling: dsg_sample with some entries of the result given (scene-graph completion; with all labels and relations
+ * given and the boxes free, layout generation).  Not in the reference; it is its sanity-check mode (edm.py:372-377, gt_adj / gt_node
+ * above: the denoiser's output replaced EVERYWHERE, the state converges to it) applied per entry.  Wherever mask_* is nonzero the
+ * denoised estimate D is known_* -- selected, not blended, so the value arrives bit-exact -- and the network's elsewhere.  Known entries
+ * of the state then follow known + t * eps, a draw of the forward marginal at every noise level: the network sees them as noisy
+ * context, and the last step (Euler to t = 0) lands them on the known values.  The select sits in the kernel that writes D, for the
+ * stage-1 D, the stage-2 D and the D of the extra self-conditioning pass of a fired coin alike, so the self-conditioning input of the
+ * next forward carries the known values too; no extra pass over the state, no extra launch.
+ *   known_adj [B,C_adj,N,N], known_node [B,N,C_node] fp32, mask_adj / mask_node uint8 of the same shapes (nonzero = known): device
+ *         pointers, all four required (DSG_ERR_INVALID otherwise).  known_* at padded nodes or where the mask is 0 is ignored.
+ *   everything else -- init, churn noise, coins, seed, snapshots, stats, use_graph / "loop_graph" -- as dsg_sample, which this call
+ *         equals bit for bit when no entry is known; with every entry known it equals dsg_sample(gt_* = known_*).
+ * The four tensors are copied (on `stream`) into buffers of the batch-B workspace, allocated by the first conditioned call for that
+ * batch size and freed with the handle: captured step bodies never reference caller memory, and the caller may reuse its buffers as
+ * soon as the call returns.  Conditioned and unconditioned step bodies are captured separately; nothing is remembered between
+ * calls -- the next dsg_sample is unconditioned.  dsg_workspace_bytes(h, B) includes these 5 * (C_adj N N + N C_node) * B bytes
+ * from that first conditioned call on (before it, and for batch sizes never sampled conditionally, it does not). */
+int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags,
+                     const float *init_adj, const float *init_node,
+                     const float *noise_adj, const float *noise_node,
+                     const uint8_t *coins, uint64_t seed,
+                     const float *known_adj, const float *known_node,
+                     const uint8_t *mask_adj, const uint8_t *mask_node,
+                     const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                     float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream);
 
 /* The library's device noise streams (Philox4x32-10 keyed by `seed`, Box-Muller): what dsg_sample draws when it is handed
  * NULL init / NULL churn noise.  noise_stream 0 = the initial sample of gen_init_sample (edm.py:257-289: randn, rows and
@@ -233,6 +260,20 @@ int dsg_decode_bits(dsg_handle h, int32_t B, const float *adj, const float *node
                     int32_t n_adj_type, int32_t n_node_type, int32_t node_bits,
                     int32_t *out_adj /*[B,N,N]*/, int32_t *out_node /*[B,N]*/, float *out_bbox /*[B,N,4] or NULL*/,
                     void *stream);
+
+/* The inverse of dsg_decode: integer graphs -> the network's value space, the on-device attribute_converter(in_encoding = 'int',
+ * out_encoding = ...) (R/utils/attribute_code.py:240-304) -- what dsg_sample_known takes as known_adj / known_node:
+ *   DSG_ENC_BITS     MSB-first binary digits (dec2bin, :307) -> 2 b - 1
+ *   DSG_ENC_ONE_HOT  2 onehot - 1 over the n_type channels
+ *   DSG_ENC_DDPM     2 i / (n_type - 1) - 1, float32 op by op like the reference's tensor arithmetic
+ * q_adj [B,N,N], q_node [B,N] int32 in [0, n_type - 1]; bbox [B,N,4] fp32 in [0,1] or NULL.  out_adj [B,C_adj,N,N]; out_node [B,N,C_node]:
+ * the attribute in the first node_chans channels, (bbox - 0.5) * 2 (R/utils/dataloader.py:168) in the last four when bbox != NULL, 0 in
+ * any channel in between.  Rows / columns of padded nodes are 0; the adjacency diagonal is encoded like every other entry (the
+ * reference masks with the node flags only).  Channel counts are checked like dsg_decode's.  Needs the handle only for N / C_adj /
+ * C_node (no weights). */
+int dsg_encode(dsg_handle h, int32_t B, const int32_t *q_adj, const int32_t *q_node, const float *bbox /*[B,N,4] or NULL*/,
+               const uint8_t *flags, int32_t edge_encoding, int32_t node_encoding, int32_t n_adj_type, int32_t n_node_type,
+               int32_t node_chans, float *out_adj /*[B,C_adj,N,N]*/, float *out_node /*[B,N,C_node]*/, void *stream);
 
 /* Debug / verification: one GEMM of the library, C[M,N] = act(LN?(A)[M,K] . W[N,K]^T + bias) (+ res), in a chosen arithmetic
  * (mode 0: fp32 MFMA; 1: bf16 operands, fp32 accumulate -- "gemm_bf16"; 2: three-way split bf16 -- "gemm_split"); act 0 none,
