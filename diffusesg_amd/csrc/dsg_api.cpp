@@ -180,6 +180,7 @@ struct dsg_handle_s {
     int opt_fused_mlp_maxc = 96;   // at C = 192 the plain GEMM pair is faster than the one-wave-per-SIMD fused kernel
     // per-step (scale,shift) table of the sampler (batch-uniform sigma): [cap][aff_n] and its staging buffers
     int tab_cap = 0;
+    int tab_step_cap = 0;          // rows of tab_step: one per EXECUTED step (a resampling walk has more of them than schedule indices)
     float *tab_sig = nullptr, *tab_cn = nullptr, *tab_pe = nullptr, *tab_e0 = nullptr, *tab_e1 = nullptr, *tab_aff = nullptr;
     StepRow *tab_step = nullptr;   // per-step scalars of the loop, read by the table-driven sampler kernels
     std::vector<Tap> taps;
@@ -1787,7 +1788,7 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
     launch_churn_tab(CStatePtrs{w->x_adj, w->x_node}, h->tab_step, w->ctl, w->flags, StatePtrs{w->xh_adj, w->xh_node}, d, s);   // edm.py:355-366
     CStatePtrs D1{gt_adj, gt_node};   // sanity-check mode (edm.py:372-377): the denoiser is bypassed
     if (!gt_adj) {
-        launch_step_row(h->tab_aff, h->aff_n, w->ctl, w->aff, s);   // this step's (scale,shift) row for every block
+        launch_step_row(h->tab_aff, h->aff_n, h->tab_step, w->ctl, w->aff, s);   // this step's (scale,shift) row for every block
         if (int rc = precond_tab(h, w, xh, p.sc_slot >= 0 ? w->d_adj[p.sc_slot] : nullptr, p.sc_slot >= 0 ? w->d_node[p.sc_slot] : nullptr,
                                  p.coin1, StatePtrs{w->d_adj[p.s1], w->d_node[p.s1]}, s, nfe, fwd_graph, p.known)) return rc;
         D1 = CStatePtrs{w->d_adj[p.s1], w->d_node[p.s1]};
@@ -2013,6 +2014,40 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *c, double *sigma_steps, float *t_h
     return DSG_OK;
 }
 
+// Host-side walk over the schedule (include/dsg.h): which schedule index every executed step runs at, and its churn coefficient.
+// A repeated pass of a block [b, e) begins with the state at t_e; the jump back to t_b (variance t_b^2 - t_e^2) and the step's own
+// churn (variance nz_b^2) are independent Gaussians, i.e. one: a single coefficient, evaluated in double and rounded once.
+int32_t dsg_walk_steps(const dsg_sampler_cfg *c, const dsg_walk_cfg *wk, int32_t *sched_idx, float *noise_coef, int32_t cap) {
+    if (!c || !wk || c->num_steps < 1) return DSG_ERR_INVALID;
+    const int T = c->num_steps;
+    const int s = wk->start_step, j = wk->jump_len, r = wk->n_resample, lo = wk->resample_lo;
+    const int hi = wk->resample_hi <= 0 ? T : wk->resample_hi;
+    if (s < 0 || s >= T || j < 1 || r < 1 || lo < s || hi < lo || hi > T) return DSG_ERR_INVALID;
+    const int64_t L = (int64_t)T - s + (int64_t)(r - 1) * (hi - lo);
+    if (L > DSG_WALK_MAX_STEPS) return DSG_ERR_INVALID;
+    if (!sched_idx && !noise_coef) return (int32_t)L;
+    if (cap < L) return DSG_ERR_INVALID;
+    std::vector<double> sg(T);
+    std::vector<float> nz(T);
+    dsg_sigma_schedule(c, sg.data(), nullptr, nz.data(), nullptr);
+    int k = 0;
+    auto emit = [&](int i, float coef) {
+        if (sched_idx) sched_idx[k] = i;
+        if (noise_coef) noise_coef[k] = coef;
+        k++;
+    };
+    for (int i = s; i < lo; i++) emit(i, nz[i]);
+    for (int b = lo; b < hi; b += j) {
+        const int e = b + j < hi ? b + j : hi;
+        const double tb = (double)(float)sg[b], te = e == T ? 0.0 : (double)(float)sg[e], nb = (double)nz[b];
+        const float jump = (float)std::sqrt(tb * tb - te * te + nb * nb);
+        for (int pass = 0; pass < r; pass++)
+            for (int i = b; i < e; i++) emit(i, (pass > 0 && i == b) ? jump : nz[i]);
+    }
+    for (int i = hi; i < T; i++) emit(i, nz[i]);
+    return (int32_t)L;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2020,18 +2055,35 @@ namespace {
 // the caller's known tensors and element masks of a conditioned run
 struct KnownArgs { const float *adj, *node; const uint8_t *mask_adj, *mask_node; };
 
-// dsg_sample (known == nullptr) and dsg_sample_known: one reverse loop
-int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags, const float *init_adj,
-                const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
-                const float *gt_adj, const float *gt_node, const KnownArgs *known, const int32_t *snap_steps, int32_t n_snap,
-                float *snap_adj, float *snap_node, float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
+// dsg_sample (known == nullptr), dsg_sample_known and dsg_sample_walk: one reverse loop.  walk == nullptr is the trivial walk (every
+// schedule index once, from pure noise); base_* (a walk's partial-noise start) only reaches the init kernel.
+int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags, const float *init_adj,
+                const float *init_node, const float *base_adj, const float *base_node, const float *noise_adj, const float *noise_node,
+                const uint8_t *coins, uint64_t seed, const float *gt_adj, const float *gt_node, const KnownArgs *known,
+                const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
+                dsg_sample_stats *stats, void *stream) {
     if (int rc = check_ready(h, B)) return rc;
     if (!cfg || !flags || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null argument");
     if ((init_adj == nullptr) != (init_node == nullptr)) return fail(h, DSG_ERR_INVALID, "init_adj/init_node must both be given");
     if ((noise_adj == nullptr) != (noise_node == nullptr)) return fail(h, DSG_ERR_INVALID, "noise_adj/noise_node must both be given");
     if ((gt_adj == nullptr) != (gt_node == nullptr)) return fail(h, DSG_ERR_INVALID, "gt_adj/gt_node must both be given");
+    if ((base_adj == nullptr) != (base_node == nullptr)) return fail(h, DSG_ERR_INVALID, "base_adj/base_node must both be given");
     const int T = cfg->num_steps;
     if (T < 1) return fail(h, DSG_ERR_INVALID, "num_steps < 1");
+    // the walk: schedule index and churn coefficient of every executed step (the trivial walk: 0..T-1 with the schedule's own)
+    const dsg_walk_cfg trivial{0, 1, 1, 0, 0, {0, 0, 0}};
+    if (!walk) walk = &trivial;
+    const int32_t L = dsg_walk_steps(cfg, walk, nullptr, nullptr, 0);
+    if (L < 0)
+        return fail(h, DSG_ERR_INVALID, "bad walk: start_step %d, jump_len %d, n_resample %d, resample range [%d, %d) with num_steps %d "
+                    "(need 0 <= start_step < T, jump_len >= 1, n_resample >= 1, start_step <= lo <= hi <= T, at most %d executed steps)",
+                    walk->start_step, walk->jump_len, walk->n_resample, walk->resample_lo, walk->resample_hi <= 0 ? T : walk->resample_hi, T,
+                    DSG_WALK_MAX_STEPS);
+    if (walk->start_step > 0 && !base_adj)
+        return fail(h, DSG_ERR_INVALID, "start_step %d > 0 needs base_adj / base_node (the graph the run starts from)", walk->start_step);
+    std::vector<int32_t> sched(L);
+    std::vector<float> coef(L);
+    dsg_walk_steps(cfg, walk, sched.data(), coef.data(), L);
     hipStream_t s = (hipStream_t)stream;
     Workspace *w;
     if (int rc = get_workspace(h, B, &w)) return rc;
@@ -2045,7 +2097,8 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8
         dsg_sigma_schedule(cfg, sg.data(), nullptr, nullptr, nullptr);
         for (int i = 0; i < T; i++) t_steps[i] = (float)sg[i];
     }
-    const int ncalls = cfg->heun ? 2 * T - 1 : T;
+    int ncalls = 0;   // preconditioned calls of the walk: two per Heun step, one where the step is the Euler step to 0 (index T - 1)
+    for (int k = 0; k < L; k++) ncalls += (cfg->heun && sched[k] != T - 1) ? 2 : 1;
     std::vector<uint8_t> coin_buf(ncalls, 0);
     if (coins) memcpy(coin_buf.data(), coins, ncalls);
     else if (h->cfg.self_condition) {
@@ -2055,14 +2108,16 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8
     h->last_stats = dsg_sample_stats{};
     if (int rc = stage_flags(h, w, flags, s)) return rc;
     // x0 = init * sigma(t0) (edm.py:326, :346-347)
-    launch_init(CStatePtrs{init_adj, init_node}, t_steps[0], seed, 0u, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
+    if (base_adj)   // partial-noise start: x = base + t_s * eps
+        launch_init_base(CStatePtrs{init_adj, init_node}, CStatePtrs{base_adj, base_node}, t_steps[walk->start_step], seed, 0u, w->flags,
+                         StatePtrs{w->x_adj, w->x_node}, d, s);
+    else launch_init(CStatePtrs{init_adj, init_node}, t_steps[0], seed, 0u, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     const bool use_graph = cfg->use_graph != 0 && !gt_adj && h->taps.empty();
     // per-step tables on the device: the loop's scalars (StepRow) and, since sigma is batch-uniform (edm.py:371), one noise
     // embedding + (scale,shift) row per step for all blocks, computed once for all steps in three GEMMs with M = T
     if (h->tab_cap < T) {
         drop_graphs(h);   // the captured step bodies bake the table addresses
         for (float **q : {&h->tab_sig, &h->tab_cn, &h->tab_pe, &h->tab_e0, &h->tab_e1, &h->tab_aff}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-        if (h->tab_step) { (void)hipFree(h->tab_step); h->tab_step = nullptr; }
         h->tab_cap = 0;
         HIP_TRY(h, hipMalloc((void **)&h->tab_sig, sizeof(float) * T));
         HIP_TRY(h, hipMalloc((void **)&h->tab_cn, sizeof(float) * T));
@@ -2070,16 +2125,23 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8
         HIP_TRY(h, hipMalloc((void **)&h->tab_e0, sizeof(float) * (size_t)T * NOISE_EMB));
         HIP_TRY(h, hipMalloc((void **)&h->tab_e1, sizeof(float) * (size_t)T * NOISE_EMB));
         HIP_TRY(h, hipMalloc((void **)&h->tab_aff, sizeof(float) * (size_t)T * h->aff_n));
-        HIP_TRY(h, hipMalloc((void **)&h->tab_step, sizeof(StepRow) * (size_t)T));
         h->tab_cap = T;
     }
-    std::vector<StepRow> rows(T);
-    for (int i = 0; i < T; i++) {
+    if (h->tab_step_cap < L) {   // one row per executed step: its own capacity, the tables above stay at one row per schedule index
+        drop_graphs(h);
+        if (h->tab_step) { (void)hipFree(h->tab_step); h->tab_step = nullptr; }
+        h->tab_step_cap = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->tab_step, sizeof(StepRow) * (size_t)L));
+        h->tab_step_cap = L;
+    }
+    std::vector<StepRow> rows(L);
+    for (int k = 0; k < L; k++) {
+        const int i = sched[k];
         volatile float t_prime = t_hat[i] + hs[i];  // alpha = 1 (edm.py:391)
-        rows[i] = StepRow{nz[i], t_hat[i], 1.0f / t_hat[i], 1.0f / t_prime, hs[i], {0, 0, 0}};
+        rows[k] = StepRow{coef[k], t_hat[i], 1.0f / t_hat[i], 1.0f / t_prime, hs[i], i, {0, 0}};
     }
     RunCtl ctl_host{0, 0, (unsigned long long)seed, noise_adj, noise_node};
-    HIP_TRY(h, hipMemcpyAsync(h->tab_step, rows.data(), sizeof(StepRow) * T, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->tab_step, rows.data(), sizeof(StepRow) * L, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(w->ctl, &ctl_host, sizeof(RunCtl), hipMemcpyHostToDevice, s));
     if (!gt_adj) {
         HIP_TRY(h, hipMemcpyAsync(h->tab_sig, t_hat.data(), sizeof(float) * T, hipMemcpyHostToDevice, s));
@@ -2108,18 +2170,19 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8
         HIP_TRY(h, hipMemcpyAsync(w->km_node, known->mask_node, sn, hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(h, hipStreamSynchronize(s));  // the host vectors above must outlive their async copies; once per sample() call
-    // the static plan of every step (edm.py:350-427): buffer rotation, Euler/Heun update, the pre-drawn coins
-    std::vector<StepPlan> plans(T);
+    // the static plan of every executed step (edm.py:350-427): buffer rotation (it simply continues across a jump: the
+    // self-conditioning input is the last denoised estimate, whichever level it came from), Euler/Heun update, the pre-drawn coins
+    std::vector<StepPlan> plans(L);
     int call = 0, snap_k = 0, nfe = 0;
     {
         int sc_slot = -1;  // which d_* buffer holds the current self-cond, -1 = None
         auto free_slot = [&](int a, int b2) { for (int k = 0; k < 3; k++) if (k != a && k != b2) return k; return 0; };
-        for (int i = 0; i < T; i++) {
+        for (int i = 0; i < L; i++) {
             StepPlan &p = plans[i];
             p.sc_slot = sc_slot;
             p.s1 = free_slot(sc_slot, -1);
             p.s2 = free_slot(p.s1, -1);
-            p.euler = !cfg->heun || i == T - 1;   // edm.py:394-396
+            p.euler = !cfg->heun || sched[i] == T - 1;   // edm.py:394-396
             p.known = known != nullptr;
             p.coin1 = !gt_adj && coin_buf[call] != 0;
             p.coin2 = !gt_adj && !p.euler && coin_buf[call + 1] != 0;
@@ -2129,8 +2192,8 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8
     }
     const bool step_graphs = use_graph && h->opt_loop_graph;
     if (step_graphs)
-        for (int i = 0; i < T; i++) if (int rc = ensure_step_graph(h, w, plans[i])) return rc;   // at most ten distinct bodies
-    for (int i = 0; i < T; i++) {
+        for (int i = 0; i < L; i++) if (int rc = ensure_step_graph(h, w, plans[i])) return rc;   // at most ten distinct bodies
+    for (int i = 0; i < L; i++) {
         if (step_graphs) { if (int rc = replay_step(h, w, plans[i], s, &nfe)) return rc; }
         else if (int rc = enqueue_step(h, w, plans[i], gt_adj, gt_node, s, &nfe, use_graph)) return rc;
         // interim snapshots (edm.py:429-432)
@@ -2157,8 +2220,8 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
                const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
                const float *gt_adj, const float *gt_node, const int32_t *snap_steps, int32_t n_snap, float *snap_adj,
                float *snap_node, float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
-    return sample_impl(h, cfg, B, flags, init_adj, init_node, noise_adj, noise_node, coins, seed, gt_adj, gt_node, nullptr, snap_steps,
-                       n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, gt_adj, gt_node,
+                       nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
 }
 
 int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags, const float *init_adj,
@@ -2171,8 +2234,25 @@ int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const 
         return fail(h, DSG_ERR_INVALID, "dsg_sample_known needs known_adj, known_node, mask_adj and mask_node (%s is NULL)",
                     !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
     const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
-    return sample_impl(h, cfg, B, flags, init_adj, init_node, noise_adj, noise_node, coins, seed, nullptr, nullptr, &known, snap_steps,
-                       n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, nullptr, nullptr,
+                       &known, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+}
+
+int dsg_sample_walk(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
+                    const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                    const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
+                    const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                    const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
+                    dsg_sample_stats *stats, void *stream) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!walk) return fail(h, DSG_ERR_INVALID, "dsg_sample_walk needs a walk (walk is NULL)");
+    const int n_known = (known_adj != nullptr) + (known_node != nullptr) + (mask_adj != nullptr) + (mask_node != nullptr);
+    if (n_known != 0 && n_known != 4)
+        return fail(h, DSG_ERR_INVALID, "dsg_sample_walk needs known_adj, known_node, mask_adj and mask_node all given or all NULL (%s is NULL)",
+                    !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
+    const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
+    return sample_impl(h, cfg, walk, B, flags, init_adj, init_node, base_adj, base_node, noise_adj, noise_node, coins, seed, nullptr, nullptr,
+                       n_known ? &known : nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
 }
 
 int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_kind, int64_t *launches_by_kind,

@@ -221,10 +221,15 @@ void launch_precond_out(CStatePtrs x, CStatePtrs F, const float *sigmas, const u
 // x0 = mask(eps) * scale (gen_init_sample + initial scaling); eps from `init` or Philox(seed, stream): stream 0 is the
 // initial sample, stream i+1 the churn noise of step i (launch_churn)
 void launch_init(CStatePtrs init, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
+// partial-noise start (dsg_sample_walk with base_*): x = mask(base + scale * eps), eps as launch_init's; base in the state layouts
+void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d,
+                      hipStream_t s);
 
 // ---- reverse-loop kernels driven by a DEVICE step counter, so that one captured step body can be replayed for every step ----
-// Per-step scalars, computed on the host up front exactly as before (dsg_sigma_schedule) and uploaded once per sample() call.
-struct StepRow { float noise_coef, sigma, inv_t, inv_tp, h; int pad[3]; };
+// Per-step scalars, computed on the host up front exactly as before (dsg_sigma_schedule) and uploaded once per sample() call: one row
+// per EXECUTED step.  sched = the schedule index the step runs at -- the row of the per-schedule-index tables (launch_step_row); it
+// equals the step counter in the plain loop and repeats in a resampling walk (dsg_sample_walk).
+struct StepRow { float noise_coef, sigma, inv_t, inv_tp, h; int sched; int pad[2]; };
 // Per-run control block at a fixed device address: the step counter the kernels index StepRow[] / the noise streams with.
 struct RunCtl { int step; int pad; unsigned long long seed; const float *noise_adj; const float *noise_node; };
 // x_hat = mask(x + coef[step]*eps), eps = recorded noise[step] (ctl->noise_*) or Philox(seed, step+1)
@@ -243,8 +248,8 @@ void launch_euler_tab(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const R
                       hipStream_t s);
 void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
                      StatePtrs x, Dims d, hipStream_t s);
-// dst[0..n) = table[step][0..n)  (the step's (scale,shift) row), and ctl->step += 1
-void launch_step_row(const float *table, int n, const RunCtl *ctl, float *dst, hipStream_t s);
+// dst[0..n) = table[tab[step].sched][0..n)  (the (scale,shift) row of the step's schedule index), and ctl->step += 1
+void launch_step_row(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst, hipStream_t s);
 void launch_step_advance(RunCtl *ctl, hipStream_t s);
 // ---- training-time objective and loss, forward only ----
 // sigma_b = exp(rnd_b*1.2 - 1.2), weight_b = (sigma^2 + .25)/(sigma*.5)^2, noisy = clean + mask(eps*sigma) (adjacency: the sum

@@ -2117,6 +2117,26 @@ void launch_init(CStatePtrs init, float scale, uint64_t seed, uint32_t stream, c
     DSG_LAUNCH(init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, scale, seed, stream, flags, x, d);
 }
 
+// partial-noise start of a walk (SDEdit-style): the state begins at a noised copy of `base`, x = mask(base + scale * eps).  A separate
+// kernel: every run that starts from pure noise keeps launching the one above.
+__global__ void init_base_kernel(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags,
+                                 StatePtrs x, Dims d) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total_elems(d)) return;
+    const ElemIdx e = elem_index(idx, d, flags);
+    float v;
+    if (init.adj) v = e.is_adj ? init.adj[e.off] : init.node[e.off];
+    else v = philox_normal(seed, stream, idx);
+    const float bv = e.is_adj ? base.adj[e.off] : base.node[e.off];
+    v = e.valid ? FADD(bv, FMUL(v, scale)) : 0.f;
+    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
+}
+void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d,
+                      hipStream_t s) {
+    const size_t n = total_elems(d);
+    DSG_LAUNCH(init_base_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, base, scale, seed, stream, flags, x, d);
+}
+
 // ---- reverse-loop kernels: scalars from StepRow[ctl->step] (one captured step body serves every step; edm.py:355-427) ----
 __global__ void churn_tab_kernel(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs xhat, Dims d) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2233,12 +2253,13 @@ void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRo
     const size_t n = total_elems(d);
     DSG_LAUNCH(heun_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xhat, D1, D2, tab, ctl, flags, x, d);
 }
-__global__ void step_row_kernel(const float *table, int n, const RunCtl *ctl, float *dst) {
+// the table has one row per SCHEDULE index; the executed step's row names it (a resampling walk visits an index more than once)
+__global__ void step_row_kernel(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = table[(size_t)ctl->step * n + i];
+    if (i < n) dst[i] = table[(size_t)tab[ctl->step].sched * n + i];
 }
-void launch_step_row(const float *table, int n, const RunCtl *ctl, float *dst, hipStream_t s) {
-    DSG_LAUNCH(step_row_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, n, ctl, dst);
+void launch_step_row(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst, hipStream_t s) {
+    DSG_LAUNCH(step_row_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, n, tab, ctl, dst);
 }
 __global__ void step_advance_kernel(RunCtl *ctl) { ctl->step += 1; }
 void launch_step_advance(RunCtl *ctl, hipStream_t s) { DSG_LAUNCH(step_advance_kernel, dim3(1), dim3(1), 0, s, ctl); }

@@ -18,7 +18,7 @@ EXPORTS = [
     "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
-    "dsg_sample_known", "dsg_encode",
+    "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps",
 ]
 
 DSG_ERR_INVALID = -1   # dsg_status of include/dsg.h: bad argument / unsupported configuration
@@ -43,6 +43,14 @@ class DsgSamplerCfg(C.Structure):
 
 class DsgSampleStats(C.Structure):
     _fields_ = [("precond_calls", C.c_int64), ("net_forwards", C.c_int64), ("graph_replays", C.c_int64)]
+
+
+class DsgWalkCfg(C.Structure):
+    _fields_ = [("start_step", C.c_int32), ("jump_len", C.c_int32), ("n_resample", C.c_int32),
+                ("resample_lo", C.c_int32), ("resample_hi", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+WALK_MAX_STEPS = 1 << 20   # DSG_WALK_MAX_STEPS
 
 
 _lib = None
@@ -101,6 +109,10 @@ def load(path: Optional[str] = None) -> C.CDLL:
                              vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
     L.dsg_sample_known.argtypes = [vp, C.POINTER(DsgSamplerCfg), i32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp,
                                    vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
+    L.dsg_sample_walk.argtypes = [vp, C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64,
+                                  vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
+    L.dsg_walk_steps.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, vp, i32]
+    L.dsg_walk_steps.restype = i32
     L.dsg_sigma_schedule.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, vp, vp]
     L.dsg_debug_tap.argtypes = [vp, C.c_char_p, vp, i64]
     L.dsg_debug_clear_taps.argtypes = [vp]
@@ -265,3 +277,29 @@ def sigma_schedule(scfg: DsgSamplerCfg):
     if rc != 0:
         raise DsgError(f"dsg_sigma_schedule: status {rc}")
     return sg, th, nz, hs
+
+
+def make_walk_cfg(start_step: int = 0, resample=None, resample_range=None) -> DsgWalkCfg:
+    """dsg_walk_cfg from the sampler's keywords: resample = (jump_len, n_resample) or None (no resampling); resample_range = (lo, hi)
+    or None = from start_step to the end of the schedule (hi <= 0 also means the end)."""
+    j, r = (1, 1) if resample is None else (int(resample[0]), int(resample[1]))
+    lo, hi = (int(start_step), 0) if resample_range is None else (int(resample_range[0]), int(resample_range[1]))
+    return DsgWalkCfg(int(start_step), j, r, lo, hi, (C.c_int32 * 3)(0, 0, 0))
+
+
+def walk_steps(scfg: DsgSamplerCfg, walk: DsgWalkCfg):
+    """(sched_idx int32 [L], noise_coef float32 [L]) of the walk as the loop executes it (dsg_walk_steps) -- host-only, no GPU
+    needed.  DsgError naming the walk when the library refuses it."""
+    import numpy as np
+    L = load()
+    n = int(L.dsg_walk_steps(C.byref(scfg), C.byref(walk), None, None, 0))
+    if n < 0:
+        raise DsgError(f"dsg_walk_steps: status {n}: bad walk (start_step {walk.start_step}, jump_len {walk.jump_len}, n_resample "
+                       f"{walk.n_resample}, resample range ({walk.resample_lo}, {walk.resample_hi})) for num_steps {scfg.num_steps}: need "
+                       f"0 <= start_step < T, jump_len >= 1, n_resample >= 1, start_step <= lo <= hi <= T and at most {WALK_MAX_STEPS} "
+                       f"executed steps")
+    idx, coef = np.empty(n, np.int32), np.empty(n, np.float32)
+    rc = int(L.dsg_walk_steps(C.byref(scfg), C.byref(walk), idx.ctypes.data, coef.ctypes.data, n))
+    if rc != n:
+        raise DsgError(f"dsg_walk_steps: status {rc}")
+    return idx, coef

@@ -173,24 +173,41 @@ class NodeAdjEDMSamplerHip(object):
     def sample_known(self, model, node_flags, known_adjs, known_nodes, known_adj_mask, known_node_mask, *,
                      init_adjs=None, init_nodes=None, flag_interim_adjs=False, max_num_interim_adjs=None,
                      flag_node_multi_channel=False, flag_adj_multi_channel=False,
-                     num_node_chan=150, num_edge_chan=51, churn_noise=None, coins=None, seed=None, return_device=False):
+                     num_node_chan=150, num_edge_chan=51, churn_noise=None, coins=None, seed=None, return_device=False,
+                     resample=None, resample_range=None, start_step=0, base_adjs=None, base_nodes=None):
         """Conditional sampling (`dsg_sample_known`; not in the reference): `sample()` with the entries selected by the masks held at
         the known values -- scene-graph completion, or layout generation when every label and relation is known and the boxes are not.
         known_adjs / known_adj_mask: [B,C_adj,N,N], known_nodes / known_node_mask: [B,N,C_node] (or squeezed, [B,N,N] / [B,N], for
         single-channel networks); masks are bool or integer, nonzero = known; the known values are in the network's value space
         (`diffusesg_amd.io.encode`).  Everything else, and the return convention, as `sample()`: no entry known gives `sample()`'s
-        result bit for bit, every entry known its sanity-check mode's."""
+        result bit for bit, every entry known its sanity-check mode's.
+
+        A walk over the noise levels (`dsg_sample_walk`, `dsg_walk_cfg` in include/dsg.h); with every one of these at its default the
+        call is the one above, on the same path as ever:
+          resample=(jump_len, n_resample)  RePaint-style resampling: the schedule is cut into blocks of jump_len indices and each
+                block is run n_resample times in a row, the state diffused back up to the block's first level in between;
+          resample_range=(lo, hi)  the schedule indices the blocks partition (default: from start_step to the end; hi <= 0 = the end);
+          start_step, base_adjs, base_nodes  partial-noise start: the run begins at schedule index start_step from
+                base + sigma_steps[start_step] * eps (eps = init_* or the library's stream 0); base_* in the network's value space,
+                shapes of known_*.  start_step > 0 needs a base.  Making the base agree with the known values at known entries is
+                the caller's business.
+        The walk executes L = T - start_step + (n_resample - 1)(hi - lo) steps (`lib.walk_steps`): recorded churn_noise has leading
+        dimension L, coins one entry per preconditioned call of the walk, snapshots count executed steps."""
         if isinstance(model, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)):
             model = model.module
+        walk = None
+        if resample is not None or resample_range is not None or start_step != 0 or base_adjs is not None or base_nodes is not None:
+            walk = dict(resample=resample, resample_range=resample_range, start_step=start_step, base_adjs=base_adjs, base_nodes=base_nodes)
         return self._sample_hip(model, node_flags, init_adjs, init_nodes, None, None,
                                 (known_adjs, known_nodes, known_adj_mask, known_node_mask),
                                 flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
-                                churn_noise, coins, seed, return_device)
+                                churn_noise, coins, seed, return_device, walk)
 
     def _sample_hip(self, model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, known,
                     flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
-                    churn_noise, coins, seed, return_device):
-        """The loop inside libdsg.so: `dsg_sample`, or `dsg_sample_known` when `known` = (adjs, nodes, adj mask, node mask)."""
+                    churn_noise, coins, seed, return_device, walk=None):
+        """The loop inside libdsg.so: `dsg_sample`, or `dsg_sample_known` when `known` = (adjs, nodes, adj mask, node mask); with
+        `walk` (the walk keywords of `sample_known`) `dsg_sample_walk`."""
         if not isinstance(model, NodeAdjPrecondHip):
             raise TypeError("NodeAdjEDMSamplerHip needs the NodeAdjPrecondHip network returned by build_network()")
         net = model.model
@@ -208,27 +225,47 @@ class NodeAdjEDMSamplerHip(object):
             init_adjs = init_nodes = None  # both are redrawn together (edm.py:325-329)
         ia, inn = prep(init_adjs, sa), prep(init_nodes, sn)
         ga, gn = prep(sanity_check_gt_adjs, sa), prep(sanity_check_gt_nodes, sn)
+
+        # shapes are checked here, before anything is launched: the library only sees pointers
+        def prep_known(x, shape, what, dtype):
+            if x is None:
+                return None   # the library refuses a missing tensor (DSG_ERR_INVALID)
+            full = tuple(shape)
+            squeezed = tuple(d for k, d in enumerate(shape) if not (d == 1 and k in (1, len(shape) - 1)))
+            if tuple(x.shape) not in (full, squeezed):
+                raise ValueError(f"sample_known: {what} has shape {tuple(x.shape)}, expected {full}"
+                                 + (f" or {squeezed}" if squeezed != full else ""))
+            if dtype is torch.uint8:
+                x = x != 0
+            return x.to(device=dev).to(dtype).reshape(shape).contiguous()
         if known is not None:
-            # shapes are checked here, before anything is launched: the library only sees pointers
-            def prep_known(x, shape, what, dtype):
-                if x is None:
-                    return None   # the library refuses a missing tensor (DSG_ERR_INVALID)
-                full = tuple(shape)
-                squeezed = tuple(d for k, d in enumerate(shape) if not (d == 1 and k in (1, len(shape) - 1)))
-                if tuple(x.shape) not in (full, squeezed):
-                    raise ValueError(f"sample_known: {what} has shape {tuple(x.shape)}, expected {full}"
-                                     + (f" or {squeezed}" if squeezed != full else ""))
-                if dtype is torch.uint8:
-                    x = x != 0
-                return x.to(device=dev).to(dtype).reshape(shape).contiguous()
             ka = prep_known(known[0], sa, "known_adjs", torch.float32)
             kn = prep_known(known[1], sn, "known_nodes", torch.float32)
             ma = prep_known(known[2], sa, "known_adj_mask", torch.uint8)
             mn = prep_known(known[3], sn, "known_node_mask", torch.uint8)
         na = nn_ = None
-        if churn_noise is not None:
-            na, nn_ = prep(churn_noise[0], (T,) + sa), prep(churn_noise[1], (T,) + sn)
+        L = T   # executed steps
         n_calls = T if self.solver == "euler" else 2 * T - 1
+        wcfg = ba = bn = None
+        if walk is not None:
+            # the walk, the base and the sizes of the recorded randomness: all refused here, before anything is launched
+            wcfg = _lib.make_walk_cfg(walk["start_step"], walk["resample"], walk["resample_range"])
+            sched, _ = _lib.walk_steps(self._cfg(), wcfg)
+            L = len(sched)
+            n_calls = L if self.solver == "euler" else int(2 * L - np.count_nonzero(sched == T - 1))
+            if (walk["base_adjs"] is None) != (walk["base_nodes"] is None):
+                raise ValueError("sample_known: base_adjs and base_nodes must both be given")
+            if wcfg.start_step > 0 and walk["base_adjs"] is None:
+                raise ValueError(f"sample_known: start_step = {wcfg.start_step} > 0 needs base_adjs / base_nodes (the graph the run starts from)")
+            ba = prep_known(walk["base_adjs"], sa, "base_adjs", torch.float32)
+            bn = prep_known(walk["base_nodes"], sn, "base_nodes", torch.float32)
+            if churn_noise is not None and (churn_noise[0].shape[0] != L or churn_noise[1].shape[0] != L):
+                raise ValueError(f"sample_known: churn_noise has leading dimensions {churn_noise[0].shape[0]} / {churn_noise[1].shape[0]}, "
+                                 f"expected L = {L}: one slice per executed step of the walk")
+            if coins is not None and np.size(coins) < n_calls:
+                raise ValueError(f"sample_known: coins has {np.size(coins)} entries, the walk makes {n_calls} preconditioned calls")
+        if churn_noise is not None:
+            na, nn_ = prep(churn_noise[0], (L,) + sa), prep(churn_noise[1], (L,) + sn)
         if coins is None:
             coins = self.draw_coins(n_calls) if ga is None else np.zeros(n_calls, np.uint8)
         coins = np.ascontiguousarray(coins, dtype=np.uint8)
@@ -238,9 +275,9 @@ class NodeAdjEDMSamplerHip(object):
         snap_a = snap_n = None
         if flag_interim_adjs:
             if max_num_interim_adjs is None:
-                ts = np.arange(T)
+                ts = np.arange(L)
             else:
-                ts = np.linspace(0, T, max_num_interim_adjs).astype(int).clip(max=T - 1)
+                ts = np.linspace(0, L, max_num_interim_adjs).astype(int).clip(max=L - 1)
             snap_steps = np.ascontiguousarray(np.unique(ts), dtype=np.int32)
             snap_n = torch.empty((len(snap_steps),) + sn, dtype=torch.float32, device=dev)
             if not flag_adj_multi_channel:
@@ -262,7 +299,13 @@ class NodeAdjEDMSamplerHip(object):
             h.check(h.L.dsg_gen_noise(h.raw, B, p(fl), C.c_uint64(seed_v), 0, p(ia), p(inn), C.c_void_p(st)), "dsg_gen_noise")
         snap_args = (C.c_void_p(0 if snap_steps is None else snap_steps.ctypes.data),
                      0 if snap_steps is None else len(snap_steps), p(snap_a), p(snap_n))
-        if known is None:
+        if walk is not None:
+            ka, kn, ma, mn = (ka, kn, ma, mn) if known is not None else (None,) * 4
+            h.check(h.L.dsg_sample_walk(h.raw, C.byref(scfg), C.byref(wcfg), B, p(fl), p(ia), p(inn), p(ba), p(bn), p(na), p(nn_),
+                                        C.c_void_p(coins.ctypes.data), C.c_uint64(seed_v),
+                                        p(ka), p(kn), p(ma), p(mn), *snap_args,
+                                        p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample_walk")
+        elif known is None:
             h.check(h.L.dsg_sample(h.raw, C.byref(scfg), B, p(fl), p(ia), p(inn), p(na), p(nn_),
                                    C.c_void_p(coins.ctypes.data), C.c_uint64(seed_v),
                                    p(ga), p(gn), *snap_args,

@@ -80,9 +80,9 @@ typedef struct dsg_sampler_cfg {
     int32_t reserved;
 } dsg_sampler_cfg;
 
-/* Counters of the last dsg_sample / dsg_sample_known call. */
+/* Counters of the last dsg_sample / dsg_sample_known / dsg_sample_walk call. */
 typedef struct dsg_sample_stats {
-    int64_t precond_calls;             /* 2T-1 (heun) or T (euler) */
+    int64_t precond_calls;             /* 2T-1 (heun) or T (euler); of a walk: 2 per executed Heun step whose index is not T-1, else 1 */
     int64_t net_forwards;              /* precond_calls + number of coins that fired */
     int64_t graph_replays;             /* network forwards that ran from replayed graphs (== net_forwards with use_graph) */
 } dsg_sample_stats;
@@ -162,6 +162,55 @@ int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const 
                      const uint8_t *mask_adj, const uint8_t *mask_node,
                      const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
                      float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream);
+
+/* A walk over the noise levels: which schedule indices a run executes, in which order.  The schedule of dsg_sigma_schedule has
+ * indices 0..T-1 with levels t_0 > ... > t_{T-1}, and t_T = 0.  Indices in [start_step, lo) and [hi, T) are executed once, in order;
+ * [lo, hi) is cut into blocks [b, e) of jump_len indices (the last one may be shorter) and each block is executed n_resample times in a
+ * row (RePaint-style resampling: go down a few levels, diffuse back up, go down again -- the generated and the known part get time
+ * to agree).  Between two passes the state, which is at t_e, is diffused forward to t_b by ONE Gaussian of variance t_b^2 - t_e^2 (the
+ * composition of the forward steps in between, not jump_len single steps).  L = T - start_step + (n_resample - 1)(hi - lo) steps are
+ * executed; the walk is batch-uniform, as sigma is.  {0, 1, 1, 0, 0} is the trivial walk: dsg_sample's. */
+#define DSG_WALK_MAX_STEPS (1 << 20)   /* cap on L */
+typedef struct dsg_walk_cfg {
+    int32_t start_step;                /* s: first schedule index executed, 0 <= s < T */
+    int32_t jump_len;                  /* j >= 1: length of a resampled block */
+    int32_t n_resample;                /* r >= 1: times each block is executed; 1 = no resampling */
+    int32_t resample_lo;               /* blocks partition [lo, hi), starting at lo; s <= lo <= hi <= T */
+    int32_t resample_hi;               /* <= 0 means T */
+    int32_t reserved[3];
+} dsg_walk_cfg;
+
+/* The walk as the loop executes it -- host-only, as dsg_sigma_schedule exposes the schedule.  Returns L, or a negative dsg_status
+ * (DSG_ERR_INVALID: a violated range above, L > DSG_WALK_MAX_STEPS, or cap < L with an output array given).  sched_idx [L]: the schedule
+ * index of executed step k.  noise_coef [L]: the coefficient of its churn draw -- the schedule's noise_coef[sched_idx[k]], the very
+ * float, except at the first step of a repeated pass of a block [b, e): there the jump-back noise is merged into the churn draw (two
+ * independent Gaussians are one), coef = (float)sqrt((double)t_b^2 - (double)t_e^2 + (double)noise_coef[b]^2) on the widened fp32
+ * schedule values, t_e = 0 where the block ends the schedule.  The step is still evaluated at t_hat_b.  Either array may be NULL. */
+int32_t dsg_walk_steps(const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t *sched_idx, float *noise_coef, int32_t cap);
+
+/* dsg_sample_known along a walk, optionally from a partial-noise start.  dsg_sample and dsg_sample_known are the trivial walk of the
+ * same loop; a walk changes which rows the loop's tables hold, not the step: the captured step bodies, the launches per executed step
+ * and their cost are the plain loop's (the jump-back noise rides in the step's churn draw: no extra pass over the state, no extra
+ * launch).  Randomness is indexed by EXECUTED step k = 0..L-1: Philox stream k + 1 (stream 0 stays the initial sample), recorded
+ * churn noise noise_adj [L,B,C_adj,N,N] / noise_node [L,B,N,C_node], coins one per preconditioned call in executed order (a Heun
+ * step at schedule index T-1 is the Euler step to 0 on every pass); snap_steps counts executed steps.  Self-conditioning carries over
+ * a jump unchanged: its input is the last denoised estimate, whichever level it came from.
+ *   known_* / mask_*: all four given -- everything said about dsg_sample_known holds (workspace copies, nothing sticky, separate
+ *         conditioned step bodies) -- or all four NULL: an unconditioned walk.  Anything in between is DSG_ERR_INVALID.
+ *   base_adj [B,C_adj,N,N], base_node [B,N,C_node] (both or neither): the partial-noise start (SDEdit-style variation / editing).  The
+ *         run begins at index start_step with x = mask(base + t_s * eps), eps = init_* or stream 0 as ever; base_* holds value-space
+ *         tensors (what dsg_encode writes), is read once before the loop and never by a step body.  NULL is allowed only with
+ *         start_step = 0 and is dsg_sample's pure-noise start, bit for bit; start_step > 0 without a base is DSG_ERR_INVALID.  With
+ *         a mask as well, making the base agree with known_* at known entries is the caller's business: the loop pulls known entries
+ *         to known_* whatever the base says, but the first steps then see a context that is not a draw of its forward marginal.
+ * The step table has L rows, the per-level tables (noise embedding, the blocks' (scale, shift) rows) stay at T rows and are reached
+ * through each row's schedule index.  A call whose L outgrows the step table reallocates it and drops the captured step bodies. */
+int dsg_sample_walk(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
+                    const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                    const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
+                    const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                    const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                    float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream);
 
 /* The library's device noise streams (Philox4x32-10 keyed by `seed`, Box-Muller): what dsg_sample draws when it is handed
  * NULL init / NULL churn noise.  noise_stream 0 = the initial sample of gen_init_sample (edm.py:257-289: randn, rows and
