@@ -95,7 +95,8 @@ struct Workspace {
     hipGraphExec_t graph = nullptr, graph_uniform = nullptr;
     hipStream_t cap_stream = nullptr;
     // reverse loop: control block (device step counter, seed, recorded-noise pointers) and the captured step bodies, one
-    // per (self-cond slot, output slots, Euler/Heun update, coin of stage 1, coin of stage 2) combination that occurs
+    // per (self-cond slot, output slots, Euler/Heun update, coin of stage 1, coin of stage 2, known, multistep D_prev slot) combination
+    // that occurs
     RunCtl *ctl = nullptr;
     std::map<int, std::pair<hipGraphExec_t, int>> step_graphs;   // key -> (exec, network forwards inside)
     long plan_gen = -1;   // h->plan_gen this workspace's launch plan was last validated against (validate_plan)
@@ -1742,8 +1743,11 @@ struct StepPlan {
     bool euler;           // Euler update (solver 'euler', or the last step: edm.py:394-396), else Heun
     bool coin1, coin2;    // outcome of the self-conditioning coin of each preconditioned call (precond.py:90)
     bool known = false;   // conditional sampling: every D goes through the known-entry select (w->kn_* / w->km_*)
-    int key() const {
-        return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8) | ((int)known << 9);
+    int prev = -1;        // second-order multistep step (DSG_SOLVER_DPMPP_2M, row coefficient != 0): d_* buffer holding the previous
+                          // step's D, never s1 nor a buffer the step writes; -1 = none, the plain Euler / Heun step
+    int key() const {   // prev sits above every older bit: plans without it keep their keys
+        return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8) | ((int)known << 9) |
+               ((prev + 1) << 10);
     }
 };
 
@@ -1793,7 +1797,10 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
                                  p.coin1, StatePtrs{w->d_adj[p.s1], w->d_node[p.s1]}, s, nfe, fwd_graph, p.known)) return rc;
         D1 = CStatePtrs{w->d_adj[p.s1], w->d_node[p.s1]};
     }
-    if (p.euler) {
+    if (p.euler && p.prev >= 0) {   // sanity-check mode: D_prev = D = gt
+        const CStatePtrs Dp = gt_adj ? D1 : CStatePtrs{w->d_adj[p.prev], w->d_node[p.prev]};
+        launch_multistep_tab(xh, D1, Dp, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
+    } else if (p.euler) {
         launch_euler_tab(xh, D1, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     } else {
         CStatePtrs D2 = D1;
@@ -1827,8 +1834,8 @@ int ensure_step_graph(dsg_handle h, Workspace *w, const StepPlan &p) {
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(h, DSG_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
     w->step_graphs.emplace(p.key(), std::make_pair(exec, n));
-    if (getenv("DSG_GRAPH_VERBOSE")) fprintf(stderr, "[dsg-graph] captured step body key=%d (sc %d s1 %d s2 %d euler %d coins %d%d known %d): %d forwards\n",
-                                             p.key(), p.sc_slot, p.s1, p.s2, (int)p.euler, (int)p.coin1, (int)p.coin2, (int)p.known, n);
+    if (getenv("DSG_GRAPH_VERBOSE")) fprintf(stderr, "[dsg-graph] captured step body key=%d (sc %d s1 %d s2 %d euler %d coins %d%d known %d prev %d): %d forwards\n",
+                                             p.key(), p.sc_slot, p.s1, p.s2, (int)p.euler, (int)p.coin1, (int)p.coin2, (int)p.known, p.prev, n);
     return 0;
 }
 
@@ -1841,6 +1848,10 @@ int replay_step(dsg_handle h, Workspace *w, const StepPlan &p, hipStream_t s, in
     h->last_stats.graph_replays += it->second.second;
     return 0;
 }
+
+// dsg_sampler_cfg.heun names the solver: 0 Euler, 2 DPM-Solver++ 2M, every other value Heun (it was a truth value once)
+bool solver_heun(const dsg_sampler_cfg *c) { return c->heun != DSG_SOLVER_EULER && c->heun != DSG_SOLVER_DPMPP_2M; }
+bool solver_2m(const dsg_sampler_cfg *c) { return c->heun == DSG_SOLVER_DPMPP_2M; }
 
 }  // namespace
 
@@ -2048,6 +2059,34 @@ int32_t dsg_walk_steps(const dsg_sampler_cfg *c, const dsg_walk_cfg *wk, int32_t
     return (int32_t)L;
 }
 
+// Host-side coefficients of the second-order multistep update (include/dsg.h): c_k of every executed step of the walk, 0 where the
+// step is the Euler step.  In double on the widened fp32 levels, rounded once.
+int32_t dsg_multistep_coef(const dsg_sampler_cfg *c, const dsg_walk_cfg *wk, float *coef, int32_t cap) {
+    const dsg_walk_cfg trivial{0, 1, 1, 0, 0, {0, 0, 0}};
+    if (!wk) wk = &trivial;
+    const int32_t L = dsg_walk_steps(c, wk, nullptr, nullptr, 0);
+    if (L < 0) return L;
+    const int T = c->num_steps;
+    std::vector<double> sg(T);
+    std::vector<float> nz(T);
+    dsg_sigma_schedule(c, sg.data(), nullptr, nz.data(), nullptr);
+    if (solver_2m(c))   // the update extrapolates D along the probability-flow ODE: a level that draws churn noise breaks the history
+        for (int i = 0; i < T; i++) if (nz[i] != 0.f) return DSG_ERR_INVALID;
+    if (!coef) return L;
+    if (cap < L) return DSG_ERR_INVALID;
+    std::vector<int32_t> sched(L);
+    std::vector<float> jump(L);
+    dsg_walk_steps(c, wk, sched.data(), jump.data(), L);
+    for (int k = 0; k < L; k++) {
+        const int i = sched[k];
+        coef[k] = 0.f;
+        if (!solver_2m(c) || k == 0 || i == T - 1 || sched[k - 1] != i - 1 || jump[k] != 0.f) continue;
+        const double tp = (double)(float)sg[i - 1], tc = (double)(float)sg[i], tn = (double)(float)sg[i + 1];
+        coef[k] = (float)(std::log(tc / tn) / (2.0 * std::log(tp / tc)));
+    }
+    return L;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2082,8 +2121,11 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
     if (walk->start_step > 0 && !base_adj)
         return fail(h, DSG_ERR_INVALID, "start_step %d > 0 needs base_adj / base_node (the graph the run starts from)", walk->start_step);
     std::vector<int32_t> sched(L);
-    std::vector<float> coef(L);
+    std::vector<float> coef(L), ms_coef(L);
     dsg_walk_steps(cfg, walk, sched.data(), coef.data(), L);
+    if (dsg_multistep_coef(cfg, walk, ms_coef.data(), L) != L)   // the walk is good: what is left is a level with churn noise
+        return fail(h, DSG_ERR_INVALID, "solver dpmpp_2m (heun = %d) needs a schedule that draws no churn noise at any level: set S_churn = 0 "
+                    "(S_churn is %g)", DSG_SOLVER_DPMPP_2M, (double)cfg->S_churn);
     hipStream_t s = (hipStream_t)stream;
     Workspace *w;
     if (int rc = get_workspace(h, B, &w)) return rc;
@@ -2097,8 +2139,9 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
         dsg_sigma_schedule(cfg, sg.data(), nullptr, nullptr, nullptr);
         for (int i = 0; i < T; i++) t_steps[i] = (float)sg[i];
     }
-    int ncalls = 0;   // preconditioned calls of the walk: two per Heun step, one where the step is the Euler step to 0 (index T - 1)
-    for (int k = 0; k < L; k++) ncalls += (cfg->heun && sched[k] != T - 1) ? 2 : 1;
+    // preconditioned calls of the walk: two per Heun step, one where the step is the Euler step to 0 (index T - 1); Euler and multistep: one
+    int ncalls = 0;
+    for (int k = 0; k < L; k++) ncalls += (solver_heun(cfg) && sched[k] != T - 1) ? 2 : 1;
     std::vector<uint8_t> coin_buf(ncalls, 0);
     if (coins) memcpy(coin_buf.data(), coins, ncalls);
     else if (h->cfg.self_condition) {
@@ -2138,7 +2181,7 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
     for (int k = 0; k < L; k++) {
         const int i = sched[k];
         volatile float t_prime = t_hat[i] + hs[i];  // alpha = 1 (edm.py:391)
-        rows[k] = StepRow{coef[k], t_hat[i], 1.0f / t_hat[i], 1.0f / t_prime, hs[i], i, {0, 0}};
+        rows[k] = StepRow{coef[k], t_hat[i], 1.0f / t_hat[i], 1.0f / t_prime, hs[i], i, ms_coef[k], 0};
     }
     RunCtl ctl_host{0, 0, (unsigned long long)seed, noise_adj, noise_node};
     HIP_TRY(h, hipMemcpyAsync(h->tab_step, rows.data(), sizeof(StepRow) * L, hipMemcpyHostToDevice, s));
@@ -2171,23 +2214,29 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
     }
     HIP_TRY(h, hipStreamSynchronize(s));  // the host vectors above must outlive their async copies; once per sample() call
     // the static plan of every executed step (edm.py:350-427): buffer rotation (it simply continues across a jump: the
-    // self-conditioning input is the last denoised estimate, whichever level it came from), Euler/Heun update, the pre-drawn coins
+    // self-conditioning input is the last denoised estimate, whichever level it came from), Euler/Heun/multistep update, the pre-drawn coins
     std::vector<StepPlan> plans(L);
     int call = 0, snap_k = 0, nfe = 0;
     {
         int sc_slot = -1;  // which d_* buffer holds the current self-cond, -1 = None
+        int last_s1 = -1;  // which d_* buffer the previous step's D went to (a network without self-conditioning keeps no sc_slot)
         auto free_slot = [&](int a, int b2) { for (int k = 0; k < 3; k++) if (k != a && k != b2) return k; return 0; };
         for (int i = 0; i < L; i++) {
             StepPlan &p = plans[i];
             p.sc_slot = sc_slot;
-            p.s1 = free_slot(sc_slot, -1);
+            // a multistep step (coefficient != 0, so never the first) reads the previous step's D: the self-conditioning input where the
+            // network has one (the D of a fired coin's extra pass goes to w->sc_*, not there), else the previous s1; s1 avoids both.
+            // Every other step is planned as ever (prev = -1).  Sanity-check mode: no slot is read, D_prev = D = gt
+            if (ms_coef[i] != 0.f) p.prev = gt_adj ? 0 : (h->cfg.self_condition ? sc_slot : last_s1);
+            p.s1 = free_slot(sc_slot, p.prev);
             p.s2 = free_slot(p.s1, -1);
-            p.euler = !cfg->heun || sched[i] == T - 1;   // edm.py:394-396
+            p.euler = !solver_heun(cfg) || sched[i] == T - 1;   // edm.py:394-396
             p.known = known != nullptr;
             p.coin1 = !gt_adj && coin_buf[call] != 0;
             p.coin2 = !gt_adj && !p.euler && coin_buf[call + 1] != 0;
             if (!gt_adj) call += p.euler ? 1 : 2;
             if (!gt_adj && h->cfg.self_condition) sc_slot = p.euler ? p.s1 : p.s2;   // edm.py:423-424: sc <- last denoised
+            if (!gt_adj) last_s1 = p.s1;
         }
     }
     const bool step_graphs = use_graph && h->opt_loop_graph;

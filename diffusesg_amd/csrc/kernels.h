@@ -229,7 +229,9 @@ void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t se
 // Per-step scalars, computed on the host up front exactly as before (dsg_sigma_schedule) and uploaded once per sample() call: one row
 // per EXECUTED step.  sched = the schedule index the step runs at -- the row of the per-schedule-index tables (launch_step_row); it
 // equals the step counter in the plain loop and repeats in a resampling walk (dsg_sample_walk).
-struct StepRow { float noise_coef, sigma, inv_t, inv_tp, h; int sched; int pad[2]; };
+// ms_coef = c_k of the second-order multistep update (launch_multistep_tab); 0 in every row of every other step, where no kernel reads it.
+struct StepRow { float noise_coef, sigma, inv_t, inv_tp, h; int sched; float ms_coef; int pad; };
+static_assert(sizeof(StepRow) == 32, "StepRow is 32 bytes");
 // Per-run control block at a fixed device address: the step counter the kernels index StepRow[] / the noise streams with.
 struct RunCtl { int step; int pad; unsigned long long seed; const float *noise_adj; const float *noise_node; };
 // x_hat = mask(x + coef[step]*eps), eps = recorded noise[step] (ctl->noise_*) or Philox(seed, step+1)
@@ -248,6 +250,9 @@ void launch_euler_tab(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const R
                       hipStream_t s);
 void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
                      StatePtrs x, Dims d, hipStream_t s);
+// DPM-Solver++ 2M in EDM variables: the Euler update with D replaced by D + ms_coef[step] * (D - Dprev), Dprev = the previous step's D
+void launch_multistep_tab(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
+                          StatePtrs x, Dims d, hipStream_t s);
 // dst[0..n) = table[tab[step].sched][0..n)  (the (scale,shift) row of the step's schedule index), and ctl->step += 1
 void launch_step_row(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst, hipStream_t s);
 void launch_step_advance(RunCtl *ctl, hipStream_t s);

@@ -2253,6 +2253,28 @@ void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRo
     const size_t n = total_elems(d);
     DSG_LAUNCH(heun_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xhat, D1, D2, tab, ctl, flags, x, d);
 }
+// second-order multistep update (DPM-Solver++ 2M in EDM variables, sigma(t) = t): the Euler update above on the extrapolated estimate
+// D~ = D + c (D - Dprev), c = the row's ms_coef.  Where D == Dprev (a known entry of a conditioned run, the sanity-check mode) D~ is D
+// exactly.  A separate kernel: steps with c = 0 keep launching the Euler kernel.
+__global__ void multistep_tab_kernel(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const StepRow *tab, const RunCtl *ctl,
+                                     const uint8_t *flags, StatePtrs x, Dims d) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total_elems(d)) return;
+    const StepRow r = tab[ctl->step];
+    const ElemIdx e = elem_index(idx, d, flags);
+    const float xh = e.is_adj ? xhat.adj[e.off] : xhat.node[e.off];
+    const float dn = e.is_adj ? D.adj[e.off] : D.node[e.off];
+    const float dp = e.is_adj ? Dprev.adj[e.off] : Dprev.node[e.off];
+    const float dt = FADD(dn, FMUL(r.ms_coef, FSUB(dn, dp)));
+    const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, dt));
+    const float v = e.valid ? FADD(xh, FMUL(r.h, dc)) : 0.f;
+    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
+}
+void launch_multistep_tab(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
+                          StatePtrs x, Dims d, hipStream_t s) {
+    const size_t n = total_elems(d);
+    DSG_LAUNCH(multistep_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xhat, D, Dprev, tab, ctl, flags, x, d);
+}
 // the table has one row per SCHEDULE index; the executed step's row names it (a resampling walk visits an index more than once)
 __global__ void step_row_kernel(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -18,7 +18,7 @@ EXPORTS = [
     "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
-    "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps",
+    "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
 ]
 
 DSG_ERR_INVALID = -1   # dsg_status of include/dsg.h: bad argument / unsupported configuration
@@ -113,6 +113,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
                                   vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
     L.dsg_walk_steps.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, vp, i32]
     L.dsg_walk_steps.restype = i32
+    L.dsg_multistep_coef.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, i32]
+    L.dsg_multistep_coef.restype = i32
     L.dsg_sigma_schedule.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, vp, vp]
     L.dsg_debug_tap.argtypes = [vp, C.c_char_p, vp, i64]
     L.dsg_debug_clear_taps.argtypes = [vp]
@@ -185,12 +187,16 @@ def make_config(cfg) -> DsgConfig:
     return c
 
 
+# solver= of the sampler -> DSG_SOLVER_* (dsg_sampler_cfg.heun, include/dsg.h)
+SOLVERS = {"euler": 0, "heun": 1, "dpmpp_2m": 2}
+
+
 def make_sampler_cfg(num_steps: int, solver: str = "heun", S_churn: float = 40.0, S_min: float = 0.05,
                      S_max: float = 50.0, S_noise: float = 1.003, sigma_min: float = 0.002, sigma_max: float = 80.0,
                      rho: float = 7.0, use_graph: bool = True) -> DsgSamplerCfg:
-    if solver not in ("heun", "euler"):
+    if solver not in SOLVERS:
         raise ValueError(solver)
-    return DsgSamplerCfg(int(num_steps), 1 if solver == "heun" else 0, S_churn, S_min, S_max, S_noise,
+    return DsgSamplerCfg(int(num_steps), SOLVERS[solver], S_churn, S_min, S_max, S_noise,
                          sigma_min, sigma_max, rho, int(bool(use_graph)), 0)
 
 
@@ -303,3 +309,21 @@ def walk_steps(scfg: DsgSamplerCfg, walk: DsgWalkCfg):
     if rc != n:
         raise DsgError(f"dsg_walk_steps: status {rc}")
     return idx, coef
+
+
+def multistep_coef(scfg: DsgSamplerCfg, walk: Optional[DsgWalkCfg] = None):
+    """c_k float32 [L] of the second-order multistep update (dsg_multistep_coef) for every executed step of the walk (None = the
+    trivial walk), as the loop runs them: 0 where the step is the Euler step, all 0 unless the solver is 'dpmpp_2m' -- host-only, no
+    GPU needed.  DsgError when the library refuses the walk, or the multistep solver on a schedule with churn noise."""
+    import numpy as np
+    L = load()
+    w = None if walk is None else C.byref(walk)
+    n = int(L.dsg_multistep_coef(C.byref(scfg), w, None, 0))
+    if n < 0:
+        raise DsgError(f"dsg_multistep_coef: status {n}: a bad walk, or solver 'dpmpp_2m' on a schedule that draws churn noise "
+                       f"(S_churn = {scfg.S_churn:g}; it needs S_churn = 0)")
+    coef = np.empty(n, np.float32)
+    rc = int(L.dsg_multistep_coef(C.byref(scfg), w, coef.ctypes.data, n))
+    if rc != n:
+        raise DsgError(f"dsg_multistep_coef: status {rc}")
+    return coef

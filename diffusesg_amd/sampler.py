@@ -6,6 +6,10 @@ multi-channel adjacency are requested, edm.py:439-443).  The T-step loop itself 
 (`dsg_sample`): per-step scalars are computed on the host up front, no device->host sync happens inside the
 loop (the reference's per-step `.item()` logging, edm.py:433-434, is dropped), and the network forward is
 replayed from a captured hipGraph.
+
+Beyond the reference's solvers 'euler' and 'heun': solver='dpmpp_2m', a second-order multistep step (DPM-Solver++ 2M in EDM
+variables) at one network forward per step -- the Euler step on the denoised estimate extrapolated from the previous step's.  It
+needs S_churn = 0 (ValueError otherwise); include/dsg.h (dsg_multistep_coef), DESIGN.md §9.
 """
 from __future__ import annotations
 
@@ -27,13 +31,17 @@ class NodeAdjEDMSamplerHip(object):
                  clip_samples=False, clip_samples_min=None, clip_samples_max=None, clip_samples_scope="x_0",
                  self_condition=True, dev="cuda", objective="edm", symmetric_noise=False, use_graph=True):
         assert clip_samples_scope == "x_0"
-        assert solver in ["euler", "heun"]
+        assert solver in ["euler", "heun", "dpmpp_2m"]
         assert objective in ["diffusion", "score", "edm"]
         if discretization != "edm" or schedule != "linear" or scaling != "none" or alpha != 1:
             raise NotImplementedError("only discretization='edm', schedule='linear', scaling='none', alpha=1 "
                                       "(what get_mc_sampler builds, sampling_utils.py:15-23)")
         if symmetric_noise:
             raise NotImplementedError("symmetric_noise=True is not used for scene graphs (sampling_utils.py:23)")
+        if solver == "dpmpp_2m" and S_churn != 0:
+            # the second-order multistep solver follows the probability-flow ODE: churn noise between two steps breaks its history
+            raise ValueError(f"solver='dpmpp_2m' needs S_churn = 0 (got S_churn = {S_churn}): it reuses the previous step's denoised "
+                             f"estimate, which churn noise invalidates; use solver='heun' or 'euler' with churn")
         self.solver, self.num_steps = solver, int(num_steps)
         self.S_churn, self.S_min, self.S_max, self.S_noise = S_churn, S_min, S_max, S_noise
         self.sigma_min = 0.002 if sigma_min is None else sigma_min   # edm_params.sigma_min_sampling
@@ -121,7 +129,7 @@ class NodeAdjEDMSamplerHip(object):
             xha, xhn = (xa + coef * ea) * fa, (xn + coef * en) * fn                            # edm.py:356-366
             h = t_next - t_hat
             da, dn = ((xha - ga) / t_hat) * fa, ((xhn - gn) / t_hat) * fn                     # edm.py:384-387
-            if self.solver == "euler" or i == T - 1:
+            if self.solver != "heun" or i == T - 1:   # 'dpmpp_2m': D = D_prev = gt, the multistep step is the Euler step
                 xa, xn = xha + h * da, xhn + h * dn                                           # edm.py:394-396
             else:
                 t_prime = t_hat + h
@@ -245,14 +253,14 @@ class NodeAdjEDMSamplerHip(object):
             mn = prep_known(known[3], sn, "known_node_mask", torch.uint8)
         na = nn_ = None
         L = T   # executed steps
-        n_calls = T if self.solver == "euler" else 2 * T - 1
+        n_calls = T if self.solver != "heun" else 2 * T - 1
         wcfg = ba = bn = None
         if walk is not None:
             # the walk, the base and the sizes of the recorded randomness: all refused here, before anything is launched
             wcfg = _lib.make_walk_cfg(walk["start_step"], walk["resample"], walk["resample_range"])
             sched, _ = _lib.walk_steps(self._cfg(), wcfg)
             L = len(sched)
-            n_calls = L if self.solver == "euler" else int(2 * L - np.count_nonzero(sched == T - 1))
+            n_calls = L if self.solver != "heun" else int(2 * L - np.count_nonzero(sched == T - 1))
             if (walk["base_adjs"] is None) != (walk["base_nodes"] is None):
                 raise ValueError("sample_known: base_adjs and base_nodes must both be given")
             if wcfg.start_step > 0 and walk["base_adjs"] is None:

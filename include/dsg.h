@@ -68,13 +68,16 @@ typedef struct dsg_config {
 
 /* Mirrors NodeAdjEDMSampler.__init__ (edm.py:236-255) for discretization='edm', schedule='linear',
  * scaling='none' (the only combination get_mc_sampler builds, sampling_utils.py:15-23). */
+#define DSG_SOLVER_EULER 0
+#define DSG_SOLVER_HEUN 1
+#define DSG_SOLVER_DPMPP_2M 2          /* second-order multistep (DPM-Solver++ 2M): one forward per step, see dsg_multistep_coef */
 typedef struct dsg_sampler_cfg {
     int32_t num_steps;
-    int32_t heun;                      /* 1: solver='heun', 0: 'euler' */
+    int32_t heun;                      /* the solver, DSG_SOLVER_*: 0 'euler', 1 'heun', 2 'dpmpp_2m'; any other nonzero value is 'heun' */
     float S_churn, S_min, S_max, S_noise;
     double sigma_min, sigma_max, rho;  /* 0.002, 80, 7 */
     int32_t use_graph;                 /* 1: replay captured hipGraphs: whole step bodies of the loop (churn, preconditioning, the
-                                          network forwards, the Euler/Heun update; per-step scalars come from a device table
+                                          network forwards, the Euler/Heun/multistep update; per-step scalars come from a device table
                                           indexed by a device step counter), or with option "loop_graph" = 0 only the network
                                           forward; 0: every kernel is launched eagerly */
     int32_t reserved;
@@ -82,7 +85,8 @@ typedef struct dsg_sampler_cfg {
 
 /* Counters of the last dsg_sample / dsg_sample_known / dsg_sample_walk call. */
 typedef struct dsg_sample_stats {
-    int64_t precond_calls;             /* 2T-1 (heun) or T (euler); of a walk: 2 per executed Heun step whose index is not T-1, else 1 */
+    int64_t precond_calls;             /* 2T-1 (heun) or T (euler, dpmpp_2m); of a walk: 2 per executed Heun step whose index is not T-1,
+                                          else 1 */
     int64_t net_forwards;              /* precond_calls + number of coins that fired */
     int64_t graph_replays;             /* network forwards that ran from replayed graphs (== net_forwards with use_graph) */
 } dsg_sample_stats;
@@ -187,6 +191,25 @@ typedef struct dsg_walk_cfg {
  * independent Gaussians are one), coef = (float)sqrt((double)t_b^2 - (double)t_e^2 + (double)noise_coef[b]^2) on the widened fp32
  * schedule values, t_e = 0 where the block ends the schedule.  The step is still evaluated at t_hat_b.  Either array may be NULL. */
 int32_t dsg_walk_steps(const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t *sched_idx, float *noise_coef, int32_t cap);
+
+/* The second-order multistep solver, heun = DSG_SOLVER_DPMPP_2M: DPM-Solver++ 2M (Lu et al. 2022) in EDM variables, sigma(t) = t,
+ * lambda = -ln t.  An executed step k at schedule index i, with no noise drawn in front of it, is the Euler step on an estimate
+ * extrapolated from the previous step's:
+ *     x_next = mask(x_hat + h (x_hat - D~) / t_hat),   D~ = D + c_k (D - D_prev),   c_k = ln(t_i / t_{i+1}) / (2 ln(t_{i-1} / t_i)).
+ * One preconditioned call per executed step: coins, precond_calls and cost are the Euler solver's.  c_k = 0 -- the Euler step itself,
+ * the same kernel and the same captured step body as under DSG_SOLVER_EULER, bit for bit -- where there is no usable history:
+ *   - k = 0 (a partial-noise start included);
+ *   - schedule index T-1, the step to t = 0 (the usual lower-order final step; ln is undefined there);
+ *   - the previous executed step was not schedule index i-1;
+ *   - the step's noise_coef (dsg_walk_steps) is nonzero: the first step of a repeated pass of a resampling walk.
+ * The solver follows the probability-flow ODE, so a schedule that draws churn noise at any level (dsg_sigma_schedule's noise_coef) is
+ * refused with DSG_ERR_INVALID, by this function and by the dsg_sample* calls before anything is launched: use S_churn = 0.  Walks
+ * (resampling, partial-noise start) and known entries are allowed; at a known entry D = D_prev = known, so D~ = known exactly and
+ * the last step still lands on it.  In the sanity-check mode D_prev = D = gt.
+ * This helper is host-only: returns L, as dsg_walk_steps does, or a negative status: DSG_ERR_INVALID for a bad walk, cap < L with coef
+ * given, or churn noise with the multistep solver.  walk == NULL is the trivial walk.  coef [L]: c_k, evaluated in double on the widened fp32 levels
+ * (float)sigma_steps[.] and rounded once to float -- the values the loop puts into its step table; all 0 for the other solvers. */
+int32_t dsg_multistep_coef(const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, float *coef, int32_t cap);
 
 /* dsg_sample_known along a walk, optionally from a partial-noise start.  dsg_sample and dsg_sample_known are the trivial walk of the
  * same loop; a walk changes which rows the loop's tables hold, not the step: the captured step bodies, the launches per executed step
