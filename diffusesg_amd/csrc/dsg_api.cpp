@@ -2440,6 +2440,78 @@ int dsg_debug_gemm(int32_t M, int32_t N, int32_t K, const float *A, const float 
     return (e == hipSuccess && hipGetLastError() == hipSuccess) ? DSG_OK : DSG_ERR_HIP;
 }
 
+// ---- the default fp32 path's kernels on their own (test hooks): each fills the launcher's arguments from its parameters, launches once
+// and synchronises the stream; DSG_ERR_INVALID when the launcher does not build the form ----
+static int debug_finish(bool built, hipStream_t s) {
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!built) return DSG_ERR_INVALID;
+    return (e == hipSuccess && hipGetLastError() == hipSuccess) ? DSG_OK : DSG_ERR_HIP;
+}
+
+int dsg_debug_gemm_f32(const dsg_gemm_f32_args *a, void *stream) {
+    if (!a || !a->A || !a->W || !a->C || a->act < ACT_NONE || a->act > ACT_DGELU) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    GemmArgs g;
+    g.A = a->A; g.lda = a->lda; g.A2 = a->A2; g.lda2 = a->lda2; g.K1 = a->A2 ? a->K1 : a->K;
+    g.W = a->W; g.bias = a->bias;
+    g.ln_stats = a->ln_stats; g.ln_part = a->ln_part; g.ln_nparts = a->ln_nparts;
+    g.res = a->res; g.ldres = a->ldres; g.C = a->C; g.ldc = a->ldc; g.C2 = a->C2; g.ldc2 = a->ldc2;
+    g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act;
+    g.mod_aff = a->mod_aff; g.mod_ld = a->mod_ld; g.mod_off = a->mod_off; g.mod_T = a->mod_T > 0 ? a->mod_T : 1;
+    g.stats_out = a->stats_out;
+    g.a4_res = a->a4_res;
+    g.row_list = a->row_list; g.row_cnt = a->row_cnt;
+    return debug_finish(launch_gemm(g, s), s);
+}
+
+int dsg_debug_qkv_attn_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, int32_t K, const float *x, const float *W,
+                           const float *bias, const float *ln_stats, const float *ln_part, int32_t ln_nparts, const float *attn_bias,
+                           const int32_t *win_list, const int32_t *win_cnt, float *out, void *stream) {
+    if (B < 1 || res < 1 || ws < 1 || heads < 1 || K < 1 || shift < 0 || shift >= ws || !x || !W || !out) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int C = 32 * heads;
+    GemmArgs g;
+    g.A = x; g.lda = K; g.K1 = K; g.K = K; g.M = B * res * res; g.N = 3 * C;
+    g.W = W; g.bias = bias; g.ln_stats = ln_stats; g.ln_part = ln_part; g.ln_nparts = ln_nparts;
+    g.attn_bias = attn_bias; g.wg = WinGeom{res, ws, shift, heads, C}; g.attn_batch = B;
+    g.C = out; g.ldc = C;
+    g.row_list = win_list; g.row_cnt = win_cnt;
+    return debug_finish(launch_gemm_qkv_attn(g, s), s);
+}
+
+int dsg_debug_window_attn_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const float *qkv, const float *biasT,
+                              float *out, void *stream) {
+    if (B < 1 || res < 1 || ws < 1 || heads < 1 || shift < 0 || shift >= ws || !qkv || !biasT || !out) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish(launch_window_attn(qkv, biasT, out, B, WinGeom{res, ws, shift, heads, 32 * heads}, s), s);
+}
+
+int dsg_debug_fused_mlp_f32(int32_t M, int32_t C, float *x, const float *gam, const float *bet, const float *W1p, const float *b1,
+                            const float *W2p, const float *b2, float *stats_out, const int32_t *run_list, const int32_t *run_cnt,
+                            void *stream) {
+    // launch_fused_mlp builds C = 96 and C = 192 only and launches nothing otherwise; a run list addresses whole 8-row runs
+    if (M < 1 || (C != 96 && C != 192) || !x || !gam || !bet || !W1p || !b1 || !W2p || !b2 || (run_list && (!run_cnt || M % 8 != 0)))
+        return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    launch_fused_mlp(x, gam, bet, W1p, b1, W2p, b2, M, C, stats_out, s, run_list, run_cnt);
+    return debug_finish(true, s);
+}
+
+int dsg_debug_fused_attn96_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, float *x, const float *aff, int32_t aff_ld,
+                               int32_t aff_off, const float *gam, const float *bet, const float *Wqp, const float *bqkv, const float *biasT,
+                               const float *Wpp, const float *bproj, int32_t premod, const int32_t *win_list, const int32_t *win_cnt,
+                               void *stream) {
+    // launch_fused_attn96 covers windows of at most 64 tokens (pack_attn_weights packs for nothing else)
+    // (aff is required with premod too: the kernel forms the pointers to the sample's rows either way)
+    if (B < 1 || res < 1 || ws < 1 || ws * ws > 64 || res % ws != 0 || shift < 0 || shift >= ws || !x || !aff || !gam || !bet || !Wqp ||
+        !bqkv || !biasT || !Wpp || !bproj || (win_list && !win_cnt))
+        return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    launch_fused_attn96(x, aff, aff_ld, aff_off, gam, bet, Wqp, bqkv, biasT, Wpp, bproj, B, WinGeom{res, ws, shift, 3, 96}, premod != 0, s,
+                        win_list, win_cnt);
+    return debug_finish(true, s);
+}
+
 static float time_launches(hipStream_t s, int iters, const std::function<void()> &launch) {
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.f;

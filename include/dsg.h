@@ -354,6 +354,53 @@ int dsg_encode(dsg_handle h, int32_t B, const int32_t *q_adj, const int32_t *q_n
 int dsg_debug_gemm(int32_t M, int32_t N, int32_t K, const float *A, const float *W, const float *bias, const float *ln_stats,
                    const float *res, int32_t act, int32_t mode, float *C, void *stream);
 
+/* The default fp32 path's kernels on their own (test hooks, csrc/kernels.hip; device pointers, synchronise `stream`; DSG_ERR_INVALID
+ * when the launcher does not build the form, never an abort).  tests/test_f32_kernels.py compares every output element with float64.
+ * dsg_debug_gemm_f32: one launch of the fp32 GEMM in any form its launcher admits.  The struct mirrors the fp32 fields of the
+ *   launcher's argument block: C[M,N] = act(LN?(A | A2)[M,K] . W[N,K]^T + bias) (+ res), leading dimensions in floats.
+ *     A2 / lda2 / K1   second source for k >= K1 (concat along K); NULL: K1 is ignored
+ *     ln_stats [M,2] (mean, rstd) or ln_part [M][ln_nparts][2] (sum, sumsq per 96 columns): LayerNorm without affine on the way in
+ *     act              0 none, 1 GELU, 2 SiLU, 3 GELU with the pre-activation kept in C2, 4 product * GELU'(res)
+ *     C2 / ldc2        second store (with mod_aff: the value before the modulation)
+ *     stats_out        [M][ceil(N/96)][2] (sum, sumsq) of what was stored to C, per column tile
+ *     mod_aff          silu(shift + v (1 + scale)) on the value stored to C, (scale, shift) = mod_aff[b mod_ld + mod_off + {n, N + n}],
+ *                      b = row / mod_T (mod_ld == 0: one row for the whole batch); needs stats_out
+ *     a4_res > 0       PatchMerging gather: A is the fine activation [B a4_res^2, K/4], M = B (a4_res/2)^2, ln_part per fine row
+ *     row_list/row_cnt only the 8-row runs listed (device int32, -1 pads to a multiple of 16), *row_cnt of them (device) */
+typedef struct dsg_gemm_f32_args {
+    const float *A, *A2, *W, *bias, *ln_stats, *ln_part, *res;
+    float *C, *C2;
+    const float *mod_aff;
+    float *stats_out;
+    const int32_t *row_list, *row_cnt;
+    int32_t lda, lda2, K1, ln_nparts, ldres, ldc, ldc2, M, N, K, act, mod_ld, mod_off, mod_T, a4_res, reserved;
+} dsg_gemm_f32_args;
+int dsg_debug_gemm_f32(const dsg_gemm_f32_args *args, void *stream);
+/* LayerNorm-1 -> QKV -> window attention in the GEMM's epilogue (8 x 8 and 10 x 10 windows): x [B res^2, K], W [3C, K] (C = 32 heads,
+ * q rows pre-scaled by d^-1/2 log2 e), bias [3C], one of ln_stats / ln_part, attn_bias the key-major log2(e)-scaled table
+ * [nW | 1][heads][Wp][Wp] (-1e30 in padded key slots); win_list / win_cnt (device, 8 x 8 only): only those windows (b nW + w, -1: none)
+ * -> out [B res^2, C]. */
+int dsg_debug_qkv_attn_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, int32_t K, const float *x, const float *W,
+                           const float *bias, const float *ln_stats, const float *ln_part, int32_t ln_nparts, const float *attn_bias,
+                           const int32_t *win_list, const int32_t *win_cnt, float *out, void *stream);
+/* window attention, fp32 in and out: qkv [B res^2, 3C] (q pre-scaled), biasT as attn_bias above -> out [B res^2, C] */
+int dsg_debug_window_attn_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const float *qkv, const float *biasT,
+                              float *out, void *stream);
+/* x [M,C] <- x + fc2(GELU(fc1(LN(x)))) in place, C in {96, 192}; W1p / W2p ALREADY in the kernel's fragment order (the index formulas
+ * above pack_mlp_weights in csrc/dsg_api.cpp); stats_out [M][2] (sum, sumsq) of the rows written, or NULL; run_list / run_cnt as
+ * dsg_gemm_f32_args::row_list (-1 pads to a multiple of 4 at least). */
+int dsg_debug_fused_mlp_f32(int32_t M, int32_t C, float *x, const float *gam, const float *bet, const float *W1p, const float *b1,
+                            const float *W2p, const float *b2, float *stats_out, const int32_t *run_list, const int32_t *run_cnt,
+                            void *stream);
+/* the attention half of a C = 96 block in place: x [B res^2, 96] <- x' + proj(window_attention(LN(x'))), x' = premod ? x :
+ * silu(shift + x (1 + scale)), (scale | shift) = aff[b aff_ld + aff_off + ...] (aff must be a valid table with premod too; aff_ld and
+ * aff_off multiples of 4); windows of at most 64 tokens; Wqp / Wpp ALREADY in
+ * fragment order and bqkv with its q part scaled (pack_attn_weights); biasT [nW | 1][3][Wp][Wp]; win_list / win_cnt: only those windows. */
+int dsg_debug_fused_attn96_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, float *x, const float *aff, int32_t aff_ld,
+                               int32_t aff_off, const float *gam, const float *bet, const float *Wqp, const float *bqkv, const float *biasT,
+                               const float *Wpp, const float *bproj, int32_t premod, const int32_t *win_list, const int32_t *win_cnt,
+                               void *stream);
+
 /* The bf16 block pipeline's kernels on their own (test hooks, csrc/kernels_bx.hip; device pointers, synchronise `stream`).
  * dsg_debug_gemm_bx: A [M,K], W [N,K] given as fp32 and rounded to bf16 inside; epilogue pieces as in the forward: bias [N], fp32
  *   residual res [M,N], act (0 | 1 GELU), mod = (scale [N] | shift [N]) of a batch-uniform modulate+SiLU, ln_out (LayerNorm of the

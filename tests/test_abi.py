@@ -43,6 +43,8 @@ def test_structs_match_header_layout():
     assert C.sizeof(lib.DsgConfig) == 4 * (5 + 8 + 8 + 3)
     assert C.sizeof(lib.DsgSamplerCfg) == 56
     assert C.sizeof(lib.DsgSampleStats) == 24
+    assert C.sizeof(lib.DsgGemmF32Args) == 13 * 8 + 16 * 4      # dsg_gemm_f32_args: thirteen pointers, sixteen int32
+    assert lib.DsgGemmF32Args.lda.offset == 13 * 8 and lib.DsgGemmF32Args.reserved.offset == 13 * 8 + 15 * 4
 
 
 def test_param_counts_and_flops():

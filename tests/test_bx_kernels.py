@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from util import window_tokens as _window_tokens
+
 pytestmark = pytest.mark.gpu
 
 
@@ -70,19 +72,6 @@ def test_gemm_bx_whole_matrix(M, N, K, act, res, mod, ln):
         assert worst <= 3e-4, f"{what}: {worst:.2e} beyond bf16 rounding"
     check_bf16(out_Cb, ref_b, "bf16 store" + (" (LayerNorm)" if ln else ""))
     check_bf16(out_C2, pre, "bf16 pre-modulation copy")
-
-
-def _window_tokens(res, ws, shift):
-    """[nW, ws*ws] token index of every window position (partition after the cyclic shift; diffusesg.py:28-57, :246-256)"""
-    nwr = res // ws
-    idx = np.zeros((nwr * nwr, ws * ws), np.int64)
-    for wi in range(nwr):
-        for wj in range(nwr):
-            for p in range(ws * ws):
-                ti = (wi * ws + p // ws + shift) % res
-                tj = (wj * ws + p % ws + shift) % res
-                idx[wi * nwr + wj, p] = ti * res + tj
-    return idx
 
 
 @pytest.mark.parametrize("B,res,ws,shift,heads", [(3, 10, 10, 0, 12), (5, 20, 10, 5, 6), (2, 40, 10, 0, 3), (4, 16, 8, 4, 12), (3, 8, 8, 0, 24),

@@ -23,3 +23,16 @@ def assert_close(a, ref, tol, what=""):
     e = rel_err(a, ref)
     assert e <= tol, f"{what}: rel err {e:.3e} > {tol:.1e}"
     return e
+
+
+def window_tokens(res, ws, shift):
+    """[nW, ws*ws] token index of every window position (partition after the cyclic shift; diffusesg.py:28-57, :246-256)"""
+    nwr = res // ws
+    idx = np.zeros((nwr * nwr, ws * ws), np.int64)
+    for wi in range(nwr):
+        for wj in range(nwr):
+            for p in range(ws * ws):
+                ti = (wi * ws + p // ws + shift) % res
+                tj = (wj * ws + p % ws + shift) % res
+                idx[wi * nwr + wj, p] = ti * res + tj
+    return idx
