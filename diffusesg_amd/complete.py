@@ -53,19 +53,22 @@ def completion_masks(cfg, node_flags, known_nodes, *, labels=True, boxes=True, e
 
 
 def complete_scene_graphs(net, sampler, q_adj, q_node, bbox, node_flags, known_nodes, n_adj_type, n_node_type, *,
-                          encoding="bits", labels=True, boxes=True, edges="among_known", seed=None, resample=None, resample_range=None):
+                          encoding="bits", labels=True, boxes=True, edges="among_known", seed=None, resample=None, resample_range=None,
+                          graph_seeds=None, coin_seed=None):
     """Scene-graph completion: the labels / boxes of the nodes `known_nodes` marks and the relations `edges` selects are held at the
     values in q_adj [B,N,N], q_node [B,N] (integer types) and bbox [B,N,4] (in [0,1]); everything else is generated.  Values at
     unknown entries are ignored.  Returns the decoded batch (q_adj int32 [B,N,N], q_node int32 [B,N], bbox float32 [B,N,4]) on the
     device.  `net`: the NodeAdjPrecondHip network with bbox channels, `sampler`: a NodeAdjEDMSamplerHip; `encoding` is the
-    network's edge and node encoding; `resample` / `resample_range`: the resampling walk (default: none)."""
+    network's edge and node encoding; `resample` / `resample_range`: the resampling walk (default: none); `graph_seeds` / `coin_seed`:
+    per-graph noise streams, as `NodeAdjEDMSamplerHip.sample` takes them."""
     cfg = getattr(net, "module", net).model.config
     known_adj, known_node = _io.encode(net, q_adj, q_node, bbox, node_flags, n_adj_type, n_node_type, encoding, encoding)
     mask_adj, mask_node = completion_masks(cfg, node_flags.to(known_adj.device), known_nodes.to(known_adj.device),
                                            labels=labels, boxes=boxes, edges=edges)
     adj, node = sampler.sample_known(net, node_flags, known_adj, known_node, mask_adj, mask_node, seed=seed, return_device=True,
                                      flag_node_multi_channel=True, flag_adj_multi_channel=True,
-                                     num_node_chan=cfg.c_node, num_edge_chan=cfg.c_adj, **_walk_kw(resample, resample_range))
+                                     num_node_chan=cfg.c_node, num_edge_chan=cfg.c_adj, **_walk_kw(resample, resample_range),
+                                     **_seed_kw(graph_seeds, coin_seed))
     return _io.decode(net, adj, node, node_flags, n_adj_type, n_node_type, encoding, encoding, bbox=True)
 
 
@@ -79,15 +82,25 @@ def _walk_kw(resample, resample_range, **more):
     return kw
 
 
+def _seed_kw(graph_seeds, coin_seed):
+    """the per-graph seed keywords of sample_known that are given (a call without any is the one it was before they existed)"""
+    kw = {}
+    if graph_seeds is not None:
+        kw["graph_seeds"] = graph_seeds
+    if coin_seed is not None:
+        kw["coin_seed"] = coin_seed
+    return kw
+
+
 def layout_from_graph(net, sampler, q_adj, q_node, node_flags, n_adj_type, n_node_type, *, encoding="bits", seed=None, resample=None,
-                      resample_range=None):
+                      resample_range=None, graph_seeds=None, coin_seed=None):
     """Layout generation from a graph: every label and every relation is known, the bounding boxes are generated.  Returns the
     decoded batch like `complete_scene_graphs`; its q_adj / q_node equal the inputs at valid nodes (off the diagonal)."""
     B, n = node_flags.shape[0], q_node.shape[-1]
     free_boxes = torch.full((B, n, 4), 0.5, dtype=torch.float32)   # placeholder: the box channels are unknown
     return complete_scene_graphs(net, sampler, q_adj, q_node, free_boxes, node_flags, node_flags.bool(), n_adj_type, n_node_type,
                                  encoding=encoding, labels=True, boxes=False, edges="all", seed=seed, resample=resample,
-                                 resample_range=resample_range)
+                                 resample_range=resample_range, graph_seeds=graph_seeds, coin_seed=coin_seed)
 
 
 def start_step_for_sigma(sampler, sigma):
@@ -100,7 +113,8 @@ def start_step_for_sigma(sampler, sigma):
 
 
 def vary_scene_graphs(net, sampler, q_adj, q_node, bbox, node_flags, n_adj_type, n_node_type, *, start_step, known_nodes=None,
-                      encoding="bits", labels=True, boxes=True, edges="among_known", resample=None, seed=None):
+                      encoding="bits", labels=True, boxes=True, edges="among_known", resample=None, seed=None,
+                      graph_seeds=None, coin_seed=None):
     """A variation of given scene graphs (SDEdit-style): the encoded graph is noised to the level of schedule index `start_step`
     (`start_step_for_sigma`) and denoised from there, so the result keeps as much of the input's structure as that noise level leaves.
     q_adj [B,N,N], q_node [B,N], bbox [B,N,4] as `complete_scene_graphs`; returns the decoded batch like it.  Nothing is held when
@@ -114,5 +128,6 @@ def vary_scene_graphs(net, sampler, q_adj, q_node, bbox, node_flags, n_adj_type,
     adj, node = sampler.sample_known(net, node_flags, base_adj, base_node, mask_adj, mask_node, seed=seed, return_device=True,
                                      flag_node_multi_channel=True, flag_adj_multi_channel=True,
                                      num_node_chan=cfg.c_node, num_edge_chan=cfg.c_adj,
-                                     **_walk_kw(resample, None, start_step=int(start_step), base_adjs=base_adj, base_nodes=base_node))
+                                     **_walk_kw(resample, None, start_step=int(start_step), base_adjs=base_adj, base_nodes=base_node),
+                                     **_seed_kw(graph_seeds, coin_seed))
     return _io.decode(net, adj, node, node_flags, n_adj_type, n_node_type, encoding, encoding, bbox=True)

@@ -88,6 +88,10 @@ struct Workspace {
     float *kn_adj = nullptr, *kn_node = nullptr;
     uint8_t *km_adj = nullptr, *km_node = nullptr;
     size_t known_bytes = 0;
+    // per-graph noise streams (dsg_sample_seeded / dsg_gen_noise_seeded): the library's copy of the caller's graph seeds, [B];
+    // allocated by the first seeded call at this batch size.  RunCtl points at it for the length of a seeded run
+    unsigned long long *gseeds = nullptr;
+    size_t seeds_bytes = 0;
     // batch-uniform noise level (the sampler): every sample shares one (scale,shift) row, taken from a table that
     // dsg_sample computes once for all steps; aff_ld == 0 broadcasts row 0 of `aff`
     bool uniform = false;
@@ -160,6 +164,7 @@ struct dsg_handle_s {
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
     std::vector<int> prof_list;
     bool opt_fused_merge = true;      // PatchMerging: gather + LayerNorm(4C) inside the reduction GEMM's A path (no merge_ln kernel)
+    bool opt_batch_invariant = false; // every choice of the plan is a function of the geometry and the other options, never of B
     bool opt_loop_graph = true;       // capture whole step bodies of the reverse loop (0: only the network forward is a graph)
     bool opt_fused_qkv_attn = true;   // QKV projection + 64-token window attention in one kernel (q, k, v never reach HBM)
     bool opt_fused_rowstats = true;   // modulate+SiLU and LayerNorm statistics in the producing GEMM's epilogue (fp32 kernel)
@@ -1051,7 +1056,8 @@ void tap(dsg_handle h, const char *name, const float *src, size_t numel, hipStre
 #define P_GEMM_(g) do { char tg_[96]; if (h->prof_stamps && h->prof_gemm && h->prof_gemm_used < h->prof_gemm_cap) (g).prof = h->prof_gemm + 4 * (h->prof_gemm_used++); else (g).prof = nullptr; \
     if (h->prof_on) snprintf(tg_, sizeof(tg_), "gemm M=%d N=%d K=%d ln=%d act=%d res=%d", (g).M, (g).N, (g).K, ((g).ln_stats != nullptr) + 2 * ((g).ln_part != nullptr) + 4 * ((g).stats_out != nullptr) + 8 * ((g).mod_aff != nullptr), (g).act, (g).res != nullptr); \
     ProfScope ps_(h, s, PK_GEMM, 2.0 * (double)(g).M * (double)(g).N * (double)(g).K, tg_); \
-    if (!launch_gemm((g), s)) plan_fail(h, "gemm: argument combination not built (M=%d N=%d K=%d ln=%d act=%d res=%d bf16 A/C=%d/%d)", (g).M, (g).N, (g).K, ((g).ln_stats != nullptr) + 2 * ((g).ln_part != nullptr), (g).act, (g).res != nullptr, (g).a_bf16, (g).c_bf16); } while (0)
+    g_fixed_tiles = h->opt_batch_invariant; const bool built_ = launch_gemm((g), s); g_fixed_tiles = false; \
+    if (!built_) plan_fail(h, "gemm: argument combination not built (M=%d N=%d K=%d ln=%d act=%d res=%d bf16 A/C=%d/%d)", (g).M, (g).N, (g).K, ((g).ln_stats != nullptr) + 2 * ((g).ln_part != nullptr), (g).act, (g).res != nullptr, (g).a_bf16, (g).c_bf16); } while (0)
 #define P_KERN(kind, flops, call) do { ProfScope ps_(h, s, (kind), (flops), #call); call; } while (0)
 
 // Row-kernel fusion (fp32 GEMM kernel only; off while debug taps want the un-modulated block outputs): the GEMM that produces
@@ -1300,6 +1306,11 @@ void readout_stage(dsg_handle h, Workspace *w, hipStream_t s) {
     GemmArgs g;
     const int M0 = B * T0;
     if (h->opt_fused_readout && h->ro_fap && h->taps.empty()) {
+        // the pooling partials of node row r go to slot (32-token tile) - (r N) / 32: where a graph's rows sit relative to the tiles, and with
+        // it the order its partials are added in, is the same for every b only if a graph is a whole number of tiles
+        if (h->opt_batch_invariant && T0 % 32 != 0)
+            plan_fail(h, "batch_invariant: the fused read-out's pooling slots depend on a graph's position in the batch unless N * N is a multiple "
+                         "of 32 (N = %d); set \"fused_readout\" = 0 or leave the option off", N);
         // one pass over x: LN, folded read_out+fc1, GELU, fc2, masked adjacency store; pooled LN(x) for the node head
         // (the bf16 block pipeline runs the two products of the read-out on the bf16 matrix pipe as well: option bf16_readout)
         const float *fap_b = (bx_on(h) && h->opt_bf16_readout && h->ro_fapb) ? (const float *)bf16_of(h, h->ro_fapb) : nullptr;
@@ -1554,7 +1565,7 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             // (below ~8k merged rows the reduction GEMM is a single partial wave of tiles and the gather + LayerNorm FMA in its
             // long K loop costs more than the small merge_ln launch it replaces: measured 103 vs 81 + 13 us at M = 4096, K = 1536)
             const bool for_merge = !next && l < L - 1 && h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16 && C % 32 == 0 &&
-                                   (B * T / 4 >= 8192 || h->opt_fused_merge_small);
+                                   (B * T / 4 >= 8192 || h->opt_fused_merge_small || h->opt_batch_invariant);   // "batch_invariant": the size plays no part
             const BlockOut bo = run_block(h, w, h->down[l][j], premod, next, for_merge, s);
             premod = bo.premod; merge_parts = bo.stats_parts;
             snprintf(name, sizeof(name), "down%d.block%d", l, (int)j);
@@ -1690,6 +1701,20 @@ int check_ready(dsg_handle h, int B) {
 int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s) {
     HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)w->B * h->N, hipMemcpyDeviceToDevice, s));
     if (w->need_lists) launch_need_lists(w->flags, w->B, h->N, w->need, w->need_cnt_ps, w->need_lists, w->need_cnt, s);
+    return 0;
+}
+
+// the caller's graph seeds (host, [B]) into the workspace-owned device buffer, allocated by the first seeded call at this batch size.
+// Enqueued on the caller's stream; the callers synchronise before they return, so the host array is read while it is still theirs
+int stage_seeds(dsg_handle h, Workspace *w, const uint64_t *graph_seeds, hipStream_t s) {
+    if (!w->gseeds) {
+        void *q;
+        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(unsigned long long) * (size_t)w->B)) return rc;
+        w->gseeds = (unsigned long long *)q;
+        w->seeds_bytes = sizeof(unsigned long long) * (size_t)w->B;
+        w->bytes += w->seeds_bytes;
+    }
+    HIP_TRY(h, hipMemcpyAsync(w->gseeds, graph_seeds, sizeof(unsigned long long) * (size_t)w->B, hipMemcpyHostToDevice, s));
     return 0;
 }
 
@@ -1864,7 +1889,8 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     for (int k = 0; k < pp.np.n_lists; k++) need += sizeof(int) * ((size_t)B * pp.items[k] + 16 + 1 + (size_t)B);
     auto it = h->ws.find(B);   // + the known tensors and masks of dsg_sample_known, once a conditioned call has allocated them
     const size_t known = it != h->ws.end() ? it->second->known_bytes : 0;
-    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need + known;
+    const size_t seeds = it != h->ws.end() ? it->second->seeds_bytes : 0;   // + the graph seeds, once a seeded call has allocated them
+    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need + known + seeds;
 }
 
 int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
@@ -1874,9 +1900,10 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     auto opts = [h]() {
         return std::tie(h->opt_fused_attn, h->opt_fused_mlp, h->opt_fused_mlp_maxc, h->opt_fused_readout, h->opt_fused_pe, h->opt_fused_rowstats,
                         h->opt_fused_qkv_attn, h->opt_loop_graph, h->opt_bf16_act, h->opt_bf16_pipe, h->opt_bf16_mlp, h->opt_bf16_qkv_attn,
-                        h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked);
+                        h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked,
+                        h->opt_batch_invariant);
     };
-    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool> saved = opts();
+    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool> saved = opts();
     if (n == "fused_attn") h->opt_fused_attn = value != 0;
     else if (n == "fused_mlp") h->opt_fused_mlp = value != 0;
     else if (n == "fused_mlp_maxc") h->opt_fused_mlp_maxc = value;
@@ -1892,6 +1919,7 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     else if (n == "bf16_proj_mlp") h->opt_bf16_proj_mlp = value != 0;
     else if (n == "bf16_readout") h->opt_bf16_readout = value != 0;
     else if (n == "prune_masked") h->opt_prune_masked = value != 0;
+    else if (n == "batch_invariant") h->opt_batch_invariant = value != 0;
     else if (n == "fused_merge") { h->opt_fused_merge = value != 0; h->opt_fused_merge_small = value > 1; }   // 2: at every size
     else if (n == "gemm_bf16") {
         h->opt_gemm_bf16 = value != 0;
@@ -1934,6 +1962,7 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "bf16_proj_mlp") *value = (bx_on(h) && h->opt_bf16_mlp && h->opt_bf16_proj_mlp) ? 1 : 0;
     else if (n == "bf16_readout") *value = (bx_on(h) && h->opt_bf16_readout && h->opt_fused_readout) ? 1 : 0;
     else if (n == "prune_masked") *value = prune_opts_on(h);   // what runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
+    else if (n == "batch_invariant") *value = h->opt_batch_invariant;
     else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
     else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
     else if (n == "gemm_split") *value = h->opt_gemm_split;
@@ -1948,6 +1977,21 @@ int dsg_gen_noise(dsg_handle h, int32_t B, const uint8_t *flags, uint64_t seed, 
     launch_init(CStatePtrs{nullptr, nullptr}, 1.0f, seed, noise_stream, flags, StatePtrs{out_adj, out_node}, dims_of(h, B),
                 (hipStream_t)stream);
     HIP_TRY(h, hipGetLastError());
+    return DSG_OK;
+}
+
+int dsg_gen_noise_seeded(dsg_handle h, int32_t B, const uint8_t *flags, const uint64_t *graph_seeds, uint32_t noise_stream, float *out_adj,
+                         float *out_node, void *stream) {
+    if (int rc = check_ready(h, B)) return rc;
+    if (!flags || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null tensor");
+    if (!graph_seeds) return fail(h, DSG_ERR_INVALID, "dsg_gen_noise_seeded needs graph_seeds (host, one per graph); graph_seeds is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    Workspace *w;
+    if (int rc = get_workspace(h, B, &w)) return rc;
+    if (int rc = stage_seeds(h, w, graph_seeds, s)) return rc;
+    launch_init_seeded(CStatePtrs{nullptr, nullptr}, 1.0f, w->gseeds, noise_stream, flags, StatePtrs{out_adj, out_node}, dims_of(h, B), s);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(s));   // the seeds are the caller's host memory
     return DSG_OK;
 }
 
@@ -2094,12 +2138,13 @@ namespace {
 // the caller's known tensors and element masks of a conditioned run
 struct KnownArgs { const float *adj, *node; const uint8_t *mask_adj, *mask_node; };
 
-// dsg_sample (known == nullptr), dsg_sample_known and dsg_sample_walk: one reverse loop.  walk == nullptr is the trivial walk (every
+// dsg_sample (known == nullptr), dsg_sample_known, dsg_sample_walk and dsg_sample_seeded (graph_seeds != nullptr: per-graph noise
+// streams; `seed` then only draws the coins): one reverse loop.  walk == nullptr is the trivial walk (every
 // schedule index once, from pure noise); base_* (a walk's partial-noise start) only reaches the init kernel.
 int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags, const float *init_adj,
                 const float *init_node, const float *base_adj, const float *base_node, const float *noise_adj, const float *noise_node,
-                const uint8_t *coins, uint64_t seed, const float *gt_adj, const float *gt_node, const KnownArgs *known,
-                const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
+                const uint8_t *coins, uint64_t seed, const uint64_t *graph_seeds, const float *gt_adj, const float *gt_node,
+                const KnownArgs *known, const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
                 dsg_sample_stats *stats, void *stream) {
     if (int rc = check_ready(h, B)) return rc;
     if (!cfg || !flags || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null argument");
@@ -2150,8 +2195,13 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
     }
     h->last_stats = dsg_sample_stats{};
     if (int rc = stage_flags(h, w, flags, s)) return rc;
+    if (graph_seeds) if (int rc = stage_seeds(h, w, graph_seeds, s)) return rc;
     // x0 = init * sigma(t0) (edm.py:326, :346-347)
-    if (base_adj)   // partial-noise start: x = base + t_s * eps
+    if (graph_seeds && base_adj)
+        launch_init_base_seeded(CStatePtrs{init_adj, init_node}, CStatePtrs{base_adj, base_node}, t_steps[walk->start_step], w->gseeds, 0u, w->flags,
+                                StatePtrs{w->x_adj, w->x_node}, d, s);
+    else if (graph_seeds) launch_init_seeded(CStatePtrs{init_adj, init_node}, t_steps[0], w->gseeds, 0u, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
+    else if (base_adj)   // partial-noise start: x = base + t_s * eps
         launch_init_base(CStatePtrs{init_adj, init_node}, CStatePtrs{base_adj, base_node}, t_steps[walk->start_step], seed, 0u, w->flags,
                          StatePtrs{w->x_adj, w->x_node}, d, s);
     else launch_init(CStatePtrs{init_adj, init_node}, t_steps[0], seed, 0u, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
@@ -2183,7 +2233,7 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
         volatile float t_prime = t_hat[i] + hs[i];  // alpha = 1 (edm.py:391)
         rows[k] = StepRow{coef[k], t_hat[i], 1.0f / t_hat[i], 1.0f / t_prime, hs[i], i, ms_coef[k], 0};
     }
-    RunCtl ctl_host{0, 0, (unsigned long long)seed, noise_adj, noise_node};
+    RunCtl ctl_host{0, 0, (unsigned long long)seed, noise_adj, noise_node, graph_seeds ? w->gseeds : nullptr};   // nothing sticky: rewritten by every run
     HIP_TRY(h, hipMemcpyAsync(h->tab_step, rows.data(), sizeof(StepRow) * L, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(w->ctl, &ctl_host, sizeof(RunCtl), hipMemcpyHostToDevice, s));
     if (!gt_adj) {
@@ -2269,7 +2319,7 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
                const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
                const float *gt_adj, const float *gt_node, const int32_t *snap_steps, int32_t n_snap, float *snap_adj,
                float *snap_node, float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
-    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, gt_adj, gt_node,
+    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, nullptr, gt_adj, gt_node,
                        nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
 }
 
@@ -2283,7 +2333,7 @@ int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const 
         return fail(h, DSG_ERR_INVALID, "dsg_sample_known needs known_adj, known_node, mask_adj and mask_node (%s is NULL)",
                     !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
     const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
-    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, nullptr, nullptr,
+    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, nullptr, nullptr, nullptr,
                        &known, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
 }
 
@@ -2300,8 +2350,26 @@ int dsg_sample_walk(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg
         return fail(h, DSG_ERR_INVALID, "dsg_sample_walk needs known_adj, known_node, mask_adj and mask_node all given or all NULL (%s is NULL)",
                     !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
     const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
-    return sample_impl(h, cfg, walk, B, flags, init_adj, init_node, base_adj, base_node, noise_adj, noise_node, coins, seed, nullptr, nullptr,
+    return sample_impl(h, cfg, walk, B, flags, init_adj, init_node, base_adj, base_node, noise_adj, noise_node, coins, seed, nullptr, nullptr, nullptr,
                        n_known ? &known : nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+}
+
+int dsg_sample_seeded(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
+                      const uint64_t *graph_seeds, uint64_t coin_seed,
+                      const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                      const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                      const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                      const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
+                      dsg_sample_stats *stats, void *stream) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!graph_seeds) return fail(h, DSG_ERR_INVALID, "dsg_sample_seeded needs graph_seeds (host, one per graph); graph_seeds is NULL");
+    const int n_known = (known_adj != nullptr) + (known_node != nullptr) + (mask_adj != nullptr) + (mask_node != nullptr);
+    if (n_known != 0 && n_known != 4)
+        return fail(h, DSG_ERR_INVALID, "dsg_sample_seeded needs known_adj, known_node, mask_adj and mask_node all given or all NULL (%s is NULL)",
+                    !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
+    const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
+    return sample_impl(h, cfg, walk, B, flags, init_adj, init_node, base_adj, base_node, noise_adj, noise_node, coins, coin_seed, graph_seeds,
+                       nullptr, nullptr, n_known ? &known : nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
 }
 
 int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_kind, int64_t *launches_by_kind,

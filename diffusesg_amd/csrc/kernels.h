@@ -9,6 +9,10 @@ namespace dsg {
 // its arguments and picks its kernel as usual but launches nothing.  A launcher that does not cover a shape returns false -- it never
 // terminates the process; the host turns that into DSG_ERR_INVALID at plan time (first use of a batch size / dsg_set_option).
 extern thread_local bool g_dry_run;
+// Option "batch_invariant" (dsg_api.cpp sets it in front of every GEMM launch): a launcher that would pick its tile from the number of
+// rows keeps ONE tile at every size, so that which kernel computes a row never depends on the batch size.  Today that is the bf16
+// GEMM's 256x96 / 128x96 choice (kernels_lp.hip: launch_gemm_lp).
+extern thread_local bool g_fixed_tiles;
 
 enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2,
            // training-form products of the fp32 GEMM only (launch_gemm): GELU whose pre-activation is kept in C2 (the backward needs it);
@@ -224,6 +228,13 @@ void launch_init(CStatePtrs init, float scale, uint64_t seed, uint32_t stream, c
 // partial-noise start (dsg_sample_walk with base_*): x = mask(base + scale * eps), eps as launch_init's; base in the state layouts
 void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d,
                       hipStream_t s);
+// Per-graph noise streams (dsg_sample_seeded / dsg_gen_noise_seeded): the draw of graph b is Philox(graph_seeds[b], stream, j), the
+// same generator, with j the element's index INSIDE its graph -- adjacency (c, i, k): (c N + i) N + k; node (i, c): Ca N^2 + i Cn + c,
+// i.e. the global index of the kernels above at B = 1.  graph_seeds: device [B].  Otherwise as launch_init / launch_init_base.
+void launch_init_seeded(CStatePtrs init, float scale, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags, StatePtrs x,
+                        Dims d, hipStream_t s);
+void launch_init_base_seeded(CStatePtrs init, CStatePtrs base, float scale, const unsigned long long *graph_seeds, uint32_t stream,
+                             const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
 
 // ---- reverse-loop kernels driven by a DEVICE step counter, so that one captured step body can be replayed for every step ----
 // Per-step scalars, computed on the host up front exactly as before (dsg_sigma_schedule) and uploaded once per sample() call: one row
@@ -233,8 +244,9 @@ void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t se
 struct StepRow { float noise_coef, sigma, inv_t, inv_tp, h; int sched; float ms_coef; int pad; };
 static_assert(sizeof(StepRow) == 32, "StepRow is 32 bytes");
 // Per-run control block at a fixed device address: the step counter the kernels index StepRow[] / the noise streams with.
-struct RunCtl { int step; int pad; unsigned long long seed; const float *noise_adj; const float *noise_node; };
-// x_hat = mask(x + coef[step]*eps), eps = recorded noise[step] (ctl->noise_*) or Philox(seed, step+1)
+// graph_seeds: null -- one key (`seed`) and the global element index; device [B] (a seeded run) -- per-graph keys and local indices
+struct RunCtl { int step; int pad; unsigned long long seed; const float *noise_adj; const float *noise_node; const unsigned long long *graph_seeds; };
+// x_hat = mask(x + coef[step]*eps), eps = recorded noise[step] (ctl->noise_*) or Philox(seed, step+1) / Philox(graph_seeds[b], step+1)
 void launch_churn_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs xhat, Dims d, hipStream_t s);
 // in = c_in(sigma[step]) * x
 void launch_precond_in_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, StatePtrs in, Dims d, hipStream_t s);

@@ -649,6 +649,7 @@ const float *gelu_table() {
 }
 
 thread_local bool g_dry_run = false;
+thread_local bool g_fixed_tiles = false;
 
 // false = this argument combination is not built; nothing has been launched and the caller reports DSG_ERR_INVALID (the host
 // validates a whole forward's launches in a dry run at plan time, so a forward never meets this half-way)
@@ -2034,6 +2035,11 @@ __device__ __forceinline__ ElemIdx elem_index(size_t idx, const Dims &d, const u
     }
     return e;
 }
+// the element's index inside its own graph: the global index it has at B = 1 (per-graph noise streams)
+__device__ __forceinline__ size_t local_index(const ElemIdx &e, const Dims &d) {
+    const size_t ga = (size_t)d.Ca * d.N * d.N, gn = (size_t)d.N * d.Cn;
+    return e.is_adj ? e.off - (size_t)e.b * ga : ga + (e.off - (size_t)e.b * gn);
+}
 __host__ __device__ inline size_t total_elems(const Dims &d) { return (size_t)d.B * ((size_t)d.Ca * d.N * d.N + (size_t)d.N * d.Cn); }
 
 #define FMUL(a, b) __fmul_rn((a), (b))
@@ -2137,6 +2143,42 @@ void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t se
     DSG_LAUNCH(init_base_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, base, scale, seed, stream, flags, x, d);
 }
 
+// per-graph noise streams: the two kernels above keyed by graph_seeds[b] and the element's index inside its graph.  Separate kernels:
+// unseeded runs keep launching the ones above.
+__global__ void init_seeded_kernel(CStatePtrs init, float scale, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags,
+                                   StatePtrs x, Dims d) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total_elems(d)) return;
+    const ElemIdx e = elem_index(idx, d, flags);
+    float v;
+    if (init.adj) v = e.is_adj ? init.adj[e.off] : init.node[e.off];
+    else v = philox_normal(graph_seeds[e.b], stream, local_index(e, d));
+    v = e.valid ? FMUL(v, scale) : 0.f;
+    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
+}
+void launch_init_seeded(CStatePtrs init, float scale, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags, StatePtrs x,
+                        Dims d, hipStream_t s) {
+    const size_t n = total_elems(d);
+    DSG_LAUNCH(init_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, scale, graph_seeds, stream, flags, x, d);
+}
+__global__ void init_base_seeded_kernel(CStatePtrs init, CStatePtrs base, float scale, const unsigned long long *graph_seeds, uint32_t stream,
+                                        const uint8_t *flags, StatePtrs x, Dims d) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total_elems(d)) return;
+    const ElemIdx e = elem_index(idx, d, flags);
+    float v;
+    if (init.adj) v = e.is_adj ? init.adj[e.off] : init.node[e.off];
+    else v = philox_normal(graph_seeds[e.b], stream, local_index(e, d));
+    const float bv = e.is_adj ? base.adj[e.off] : base.node[e.off];
+    v = e.valid ? FADD(bv, FMUL(v, scale)) : 0.f;
+    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
+}
+void launch_init_base_seeded(CStatePtrs init, CStatePtrs base, float scale, const unsigned long long *graph_seeds, uint32_t stream,
+                             const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
+    const size_t n = total_elems(d);
+    DSG_LAUNCH(init_base_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, base, scale, graph_seeds, stream, flags, x, d);
+}
+
 // ---- reverse-loop kernels: scalars from StepRow[ctl->step] (one captured step body serves every step; edm.py:355-427) ----
 __global__ void churn_tab_kernel(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs xhat, Dims d) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2149,7 +2191,11 @@ __global__ void churn_tab_kernel(CStatePtrs x, const StepRow *tab, const RunCtl 
     if (ctl->noise_adj) {
         const size_t sa = (size_t)d.B * d.Ca * d.N * d.N, sn = (size_t)d.B * d.N * d.Cn;
         eps = e.is_adj ? ctl->noise_adj[(size_t)step * sa + e.off] : ctl->noise_node[(size_t)step * sn + e.off];
-    } else eps = (coef != 0.f && e.valid) ? philox_normal(ctl->seed, (uint32_t)step + 1u, idx) : 0.f;
+    } else if (coef != 0.f && e.valid) {
+        // a seeded run (ctl->graph_seeds, uniform over the launch): the graph's own key and the element's index inside the graph
+        const unsigned long long *gs = ctl->graph_seeds;
+        eps = philox_normal(gs ? gs[e.b] : ctl->seed, (uint32_t)step + 1u, gs ? local_index(e, d) : idx);
+    } else eps = 0.f;
     const float v = e.valid ? FADD(xv, FMUL(coef, eps)) : 0.f;  // edm.py:361-366
     if (e.is_adj) xhat.adj[e.off] = v; else xhat.node[e.off] = v;
 }

@@ -527,7 +527,8 @@ bool launch_gemm_lp(const GemmArgs &g_in, hipStream_t s) {
     // bf16 kernel: the 256x96 tile (RB = 2, a wave owns 64 rows) wherever there are enough rows to fill the chip with it
     static const bool narrow_only = getenv("DSG_BF16_NARROW") != nullptr;   // dev knob: A/B against the 128x96 tile
     static const bool force_wide = getenv("DSG_BF16_WIDE") != nullptr;      // tests: the wide tile at every size
-    const bool wide = !split && !narrow_only && (force_wide ? g.M >= 256 : (size_t)((g.M + 255) / 256) * tiles_n >= 512);
+    // (g_fixed_tiles, option "batch_invariant": the choice below depends on M, i.e. on the batch size -- the 128x96 tile at every size)
+    const bool wide = !split && !narrow_only && !g_fixed_tiles && (force_wide ? g.M >= 256 : (size_t)((g.M + 255) / 256) * tiles_n >= 512);
     const int tile_m = split ? 256 : (wide ? 2 * GBM : GBM);
     const int tiles_m = (g.M + tile_m - 1) / tile_m;
     const dim3 grid(round_up8(tiles_m) * tiles_n), block(256);

@@ -12,6 +12,7 @@ from __future__ import annotations
 import os
 from typing import Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -20,8 +21,37 @@ def rank_seed(base_seed: int, rank: int) -> int:
     return int(base_seed) + int(rank)
 
 
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x: int) -> int:
+    """One output of SplitMix64 (Steele, Lea, Flood 2014) for state x, in uint64 arithmetic."""
+    z = (x + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def graph_seed(base_seed: int, k: int) -> int:
+    """The seed of graph k of the run `base_seed`: splitmix64(splitmix64(base) + k) in uint64 arithmetic.  A graph keeps its seed
+    whichever batch or rank generates it (`diffusesg_amd.generate`); hashing the base first keeps runs with nearby base seeds from
+    sharing graphs, which base + k would make them do."""
+    return _splitmix64((_splitmix64(int(base_seed) & _M64) + int(k)) & _M64)
+
+
+def graph_seeds(base_seed: int, start: int, count: int) -> np.ndarray:
+    """graph_seed(base_seed, start + i) for i in range(count), as a uint64 array."""
+    with np.errstate(over="ignore"):
+        z = np.uint64(_splitmix64(int(base_seed) & _M64)) + (np.arange(count, dtype=np.uint64) + np.uint64(int(start) & _M64))
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
 def shard_batch(total_batch: int, world_size: int) -> int:
-    """Per-rank batch, like the reference: batch_size // world_size (remainder samples are not generated)."""
+    """Per-rank batch, like the reference: batch_size // world_size (remainder samples are not generated).  The unseeded path;
+    `diffusesg_amd.generate` generates every graph of a request, with per-graph seeds."""
     if world_size < 1 or total_batch < world_size:
         raise ValueError("batch smaller than world size")
     return total_batch // world_size

@@ -19,6 +19,7 @@ EXPORTS = [
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
     "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
+    "dsg_sample_seeded", "dsg_gen_noise_seeded",
 ]
 
 DSG_ERR_INVALID = -1   # dsg_status of include/dsg.h: bad argument / unsupported configuration
@@ -119,6 +120,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
                                    vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
     L.dsg_sample_walk.argtypes = [vp, C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64,
                                   vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
+    L.dsg_sample_seeded.argtypes = [vp, C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), i32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
+    L.dsg_gen_noise_seeded.argtypes = [vp, i32, vp, vp, C.c_uint32, vp, vp, vp]
     L.dsg_walk_steps.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, vp, i32]
     L.dsg_walk_steps.restype = i32
     L.dsg_multistep_coef.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, i32]

@@ -10,6 +10,9 @@ replayed from a captured hipGraph.
 Beyond the reference's solvers 'euler' and 'heun': solver='dpmpp_2m', a second-order multistep step (DPM-Solver++ 2M in EDM
 variables) at one network forward per step -- the Euler step on the denoised estimate extrapolated from the previous step's.  It
 needs S_churn = 0 (ValueError otherwise); include/dsg.h (dsg_multistep_coef), DESIGN.md §9.
+
+Per-graph seeds (`graph_seeds=`, `coin_seed=` of `sample`, `sample_known`, `device_noise`; `dsg_sample_seeded`): every graph draws its
+noise from its own stream, so its result does not depend on the batch it is generated in (`diffusesg_amd.generate`).
 """
 from __future__ import annotations
 
@@ -22,6 +25,32 @@ import torch
 
 from . import lib as _lib
 from .model import NodeAdjPrecondHip
+
+
+def check_graph_seeds(graph_seeds, B: int) -> np.ndarray:
+    """`graph_seeds` (list, ndarray or tensor of B integers in [0, 2**64)) as a contiguous uint64 array; ValueError / TypeError before
+    anything is launched.  Values go through Python integers: no silent wrap of a negative or a too large seed."""
+    if isinstance(graph_seeds, torch.Tensor):
+        if graph_seeds.is_floating_point() or graph_seeds.is_complex() or graph_seeds.dtype == torch.bool:
+            raise TypeError(f"graph_seeds must hold integers, got a {graph_seeds.dtype} tensor")
+        graph_seeds = graph_seeds.detach().cpu().numpy()
+    if isinstance(graph_seeds, np.ndarray):
+        if graph_seeds.dtype.kind not in "iuO":
+            raise TypeError(f"graph_seeds must hold integers, got dtype {graph_seeds.dtype}")
+        vals = graph_seeds.reshape(-1).tolist() if graph_seeds.ndim == 1 else None
+    else:
+        vals = list(graph_seeds)
+    if vals is None or len(vals) != B:
+        raise ValueError(f"graph_seeds must be one seed per graph: expected {B} of them in one dimension, got "
+                         f"{'shape ' + str(tuple(graph_seeds.shape)) if vals is None else len(vals)}")
+    out = np.empty(B, dtype=np.uint64)
+    for k, v in enumerate(vals):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"graph_seeds[{k}] = {v!r} is not an integer")
+        if not 0 <= int(v) < 2 ** 64:
+            raise ValueError(f"graph_seeds[{k}] = {int(v)} is outside [0, 2**64)")
+        out[k] = int(v)
+    return out
 
 
 class NodeAdjEDMSamplerHip(object):
@@ -79,17 +108,35 @@ class NodeAdjEDMSamplerHip(object):
             return np.zeros(n_calls, dtype=np.uint8)
         return np.array([np.random.rand() < 0.5 for _ in range(n_calls)], dtype=np.uint8)
 
+    def draw_coins_seeded(self, n_calls: int, coin_seed: int) -> np.ndarray:
+        """The coins of a seeded run (`graph_seeds=` without `coins=`): Bernoulli(0.5) from a generator of their own, seeded with
+        `coin_seed` -- the NumPy global generator is not touched, the call stays a pure function of its arguments."""
+        if not self.self_condition:
+            return np.zeros(n_calls, dtype=np.uint8)
+        return (np.random.default_rng(int(coin_seed)).random(n_calls) < 0.5).astype(np.uint8)
+
     @torch.no_grad()
-    def device_noise(self, model, node_flags, stream: int = 0, seed=None):
+    def device_noise(self, model, node_flags, stream: int = 0, seed=None, graph_seeds=None):
         """The library's Philox stream `stream` for this batch, on the device: stream 0 is what `sample()` uses as
-        gen_init_sample (edm.py:257-289: masked, unscaled), stream i+1 its churn noise of step i (edm.py:361-364)."""
+        gen_init_sample (edm.py:257-289: masked, unscaled), stream i+1 its churn noise of step i (edm.py:361-364).
+        `graph_seeds` (B integers in [0, 2**64)): the per-graph streams instead -- row b is what `seed=graph_seeds[b]` gives for that
+        graph alone (`dsg_gen_noise_seeded`)."""
         net = getattr(model, "module", model).model
+        B = node_flags.shape[0]
+        if graph_seeds is not None:
+            if seed is not None:
+                raise ValueError("device_noise: give seed= (one stream over the batch) or graph_seeds= (one per graph), not both")
+            gs = check_graph_seeds(graph_seeds, B)
         h, cfg, dev = net._ensure_handle(), net.config, net._dev
-        B, n = node_flags.shape[0], cfg.max_node_num
+        n = cfg.max_node_num
         fl = node_flags.to(device=dev).to(torch.uint8).contiguous()
         a = torch.empty((B, cfg.c_adj, n, n), dtype=torch.float32, device=dev)
         x = torch.empty((B, n, cfg.c_node), dtype=torch.float32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
+        if graph_seeds is not None:
+            h.check(h.L.dsg_gen_noise_seeded(h.raw, B, C.c_void_p(fl.data_ptr()), C.c_void_p(gs.ctypes.data), int(stream),
+                                             C.c_void_p(a.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(st)), "dsg_gen_noise_seeded")
+            return a, x
         h.check(h.L.dsg_gen_noise(h.raw, B, C.c_void_p(fl.data_ptr()), C.c_uint64(self.seed if seed is None else int(seed)),
                                   int(stream), C.c_void_p(a.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(st)), "dsg_gen_noise")
         return a, x
@@ -154,13 +201,20 @@ class NodeAdjEDMSamplerHip(object):
                sanity_check_gt_adjs=None, sanity_check_gt_nodes=None,
                flag_interim_adjs=False, max_num_interim_adjs=None, flag_use_double=False,
                flag_node_multi_channel=False, flag_adj_multi_channel=False,
-               num_node_chan=150, num_edge_chan=51, churn_noise=None, coins=None, seed=None, return_device=False):
+               num_node_chan=150, num_edge_chan=51, churn_noise=None, coins=None, seed=None, return_device=False,
+               graph_seeds=None, coin_seed=None):
         """See NodeAdjEDMSampler.sample (edm.py:291).  Extra keyword-only knobs (not in the reference):
         `churn_noise=(adj [T,B,..], node [T,B,..])` and `coins` replay recorded randomness (parity tests);
         `seed` seeds the on-device Philox streams (default self.seed; the reference seeds torch per rank,
-        arg_parser.py:293-294 -- set `sampler.seed = base_seed + rank`); `return_device=True` skips the final `.cpu()`."""
+        arg_parser.py:293-294 -- set `sampler.seed = base_seed + rank`); `return_device=True` skips the final `.cpu()`.
+        `graph_seeds` (B integers in [0, 2**64); list, ndarray or tensor): per-graph noise streams (`dsg_sample_seeded`) -- graph b
+        draws what `seed=graph_seeds[b]` gives it at B = 1, wherever it sits in whichever batch; not together with `seed`.  The
+        self-conditioning coins, one sequence per run, then come from `coins` or from `np.random.default_rng(coin_seed)`
+        (`coin_seed` defaults to self.seed); the NumPy global generator is not touched."""
         if isinstance(model, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)):
             model = model.module
+        if graph_seeds is not None and (flag_use_double or sanity_check_gt_adjs is not None or sanity_check_gt_nodes is not None):
+            raise ValueError("graph_seeds= is not available in the sanity-check mode (sanity_check_gt_* / flag_use_double)")
         if flag_use_double:
             # What the reference does with this kwarg (edm.py:320-323, :342-344, :378-380): the loop's state and time steps become float64
             # and the denoiser's output is cast up.  With a real (fp32) network the reference FAILS in its first preconditioned call --
@@ -175,14 +229,15 @@ class NodeAdjEDMSamplerHip(object):
                                               flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, churn_noise, seed)
         return self._sample_hip(model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, None,
                                 flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
-                                churn_noise, coins, seed, return_device)
+                                churn_noise, coins, seed, return_device, None, graph_seeds, coin_seed)
 
     @torch.no_grad()
     def sample_known(self, model, node_flags, known_adjs, known_nodes, known_adj_mask, known_node_mask, *,
                      init_adjs=None, init_nodes=None, flag_interim_adjs=False, max_num_interim_adjs=None,
                      flag_node_multi_channel=False, flag_adj_multi_channel=False,
                      num_node_chan=150, num_edge_chan=51, churn_noise=None, coins=None, seed=None, return_device=False,
-                     resample=None, resample_range=None, start_step=0, base_adjs=None, base_nodes=None):
+                     resample=None, resample_range=None, start_step=0, base_adjs=None, base_nodes=None,
+                     graph_seeds=None, coin_seed=None):
         """Conditional sampling (`dsg_sample_known`; not in the reference): `sample()` with the entries selected by the masks held at
         the known values -- scene-graph completion, or layout generation when every label and relation is known and the boxes are not.
         known_adjs / known_adj_mask: [B,C_adj,N,N], known_nodes / known_node_mask: [B,N,C_node] (or squeezed, [B,N,N] / [B,N], for
@@ -200,7 +255,8 @@ class NodeAdjEDMSamplerHip(object):
                 shapes of known_*.  start_step > 0 needs a base.  Making the base agree with the known values at known entries is
                 the caller's business.
         The walk executes L = T - start_step + (n_resample - 1)(hi - lo) steps (`lib.walk_steps`): recorded churn_noise has leading
-        dimension L, coins one entry per preconditioned call of the walk, snapshots count executed steps."""
+        dimension L, coins one entry per preconditioned call of the walk, snapshots count executed steps.
+        `graph_seeds`, `coin_seed`: per-graph noise streams, as in `sample()`."""
         if isinstance(model, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)):
             model = model.module
         walk = None
@@ -209,15 +265,22 @@ class NodeAdjEDMSamplerHip(object):
         return self._sample_hip(model, node_flags, init_adjs, init_nodes, None, None,
                                 (known_adjs, known_nodes, known_adj_mask, known_node_mask),
                                 flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
-                                churn_noise, coins, seed, return_device, walk)
+                                churn_noise, coins, seed, return_device, walk, graph_seeds, coin_seed)
 
     def _sample_hip(self, model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, known,
                     flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
-                    churn_noise, coins, seed, return_device, walk=None):
+                    churn_noise, coins, seed, return_device, walk=None, graph_seeds=None, coin_seed=None):
         """The loop inside libdsg.so: `dsg_sample`, or `dsg_sample_known` when `known` = (adjs, nodes, adj mask, node mask); with
-        `walk` (the walk keywords of `sample_known`) `dsg_sample_walk`."""
+        `walk` (the walk keywords of `sample_known`) `dsg_sample_walk`; with `graph_seeds` `dsg_sample_seeded`, whatever else is given."""
         if not isinstance(model, NodeAdjPrecondHip):
             raise TypeError("NodeAdjEDMSamplerHip needs the NodeAdjPrecondHip network returned by build_network()")
+        gs = None
+        if graph_seeds is not None:   # refused here, before the handle is touched and anything is launched
+            if seed is not None:
+                raise ValueError("give seed= (one noise stream over the whole batch) or graph_seeds= (one per graph), not both")
+            gs = check_graph_seeds(graph_seeds, node_flags.shape[0])
+        elif coin_seed is not None:
+            raise ValueError("coin_seed= belongs to graph_seeds=; an unseeded call draws its coins from the NumPy global generator")
         net = model.model
         h = net._ensure_handle()
         cfg = net.config
@@ -274,6 +337,8 @@ class NodeAdjEDMSamplerHip(object):
                 raise ValueError(f"sample_known: coins has {np.size(coins)} entries, the walk makes {n_calls} preconditioned calls")
         if churn_noise is not None:
             na, nn_ = prep(churn_noise[0], (L,) + sa), prep(churn_noise[1], (L,) + sn)
+        if coins is None and gs is not None:
+            coins = self.draw_coins_seeded(n_calls, self.seed if coin_seed is None else coin_seed)
         if coins is None:
             coins = self.draw_coins(n_calls) if ga is None else np.zeros(n_calls, np.uint8)
         coins = np.ascontiguousarray(coins, dtype=np.uint8)
@@ -304,10 +369,22 @@ class NodeAdjEDMSamplerHip(object):
             # to letting dsg_sample draw them itself.
             ia = torch.empty(sa, dtype=torch.float32, device=dev)
             inn = torch.empty(sn, dtype=torch.float32, device=dev)
-            h.check(h.L.dsg_gen_noise(h.raw, B, p(fl), C.c_uint64(seed_v), 0, p(ia), p(inn), C.c_void_p(st)), "dsg_gen_noise")
+            if gs is not None:
+                h.check(h.L.dsg_gen_noise_seeded(h.raw, B, p(fl), C.c_void_p(gs.ctypes.data), 0, p(ia), p(inn), C.c_void_p(st)),
+                        "dsg_gen_noise_seeded")
+            else:
+                h.check(h.L.dsg_gen_noise(h.raw, B, p(fl), C.c_uint64(seed_v), 0, p(ia), p(inn), C.c_void_p(st)), "dsg_gen_noise")
         snap_args = (C.c_void_p(0 if snap_steps is None else snap_steps.ctypes.data),
                      0 if snap_steps is None else len(snap_steps), p(snap_a), p(snap_n))
-        if walk is not None:
+        if gs is not None:
+            ka, kn, ma, mn = (ka, kn, ma, mn) if known is not None else (None,) * 4
+            coin_seed_v = self.seed if coin_seed is None else int(coin_seed)   # (the coins are always handed over: not read by the library)
+            h.check(h.L.dsg_sample_seeded(h.raw, C.byref(scfg), C.byref(wcfg) if wcfg is not None else None, B, p(fl),
+                                          C.c_void_p(gs.ctypes.data), C.c_uint64(coin_seed_v & (2 ** 64 - 1)),
+                                          p(ia), p(inn), p(ba), p(bn), p(na), p(nn_), C.c_void_p(coins.ctypes.data),
+                                          p(ka), p(kn), p(ma), p(mn), *snap_args,
+                                          p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample_seeded")
+        elif walk is not None:
             ka, kn, ma, mn = (ka, kn, ma, mn) if known is not None else (None,) * 4
             h.check(h.L.dsg_sample_walk(h.raw, C.byref(scfg), C.byref(wcfg), B, p(fl), p(ia), p(inn), p(ba), p(bn), p(na), p(nn_),
                                         C.c_void_p(coins.ctypes.data), C.c_uint64(seed_v),

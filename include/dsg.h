@@ -39,7 +39,8 @@ extern "C" {
 /* Generation of this header's argument lists; dsg_abi_version() returns the one the library was built with.  A binding compares the two
  * at load time (diffusesg_amd/lib.py does): round 3 inserted `iou_loss_type` into three entries, and a caller built against the older
  * header would otherwise pass shifted arguments without any error.  History: 1-3 = rounds 1-3 (unversioned), 4 = round 4
- * (dsg_decode with an encoding argument, dsg_abi_version, dsg_last_error(NULL)). */
+ * (dsg_decode with an encoding argument, dsg_abi_version, dsg_last_error(NULL)).  dsg_sample_seeded, dsg_gen_noise_seeded and the option
+ * "batch_invariant" were added without touching an existing argument list: still 4. */
 #define DSG_ABI_VERSION 4
 
 typedef enum {
@@ -111,7 +112,7 @@ int dsg_num_weight_keys(dsg_handle h);
 const char *dsg_weight_key(dsg_handle h, int32_t i);
 
 /* Device bytes the library holds for batch size B (activations + sampler state; + the known tensors and masks of dsg_sample_known
- * once a conditioned call has run at that batch size). */
+ * once a conditioned call has run at that batch size; + the 8 B bytes of graph seeds once a seeded call has). */
 size_t dsg_workspace_bytes(dsg_handle h, int32_t B);
 
 /* DiffuseSG.forward: noise_labels[B] = c_noise; sc_adj / sc_node may be NULL (zeros). */
@@ -244,6 +245,39 @@ int dsg_sample_walk(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg
 int dsg_gen_noise(dsg_handle h, int32_t B, const uint8_t *flags, uint64_t seed, uint32_t noise_stream,
                   float *out_adj, float *out_node, void *stream);
 
+/* Per-graph noise streams: every graph of the batch has its own 64-bit key, and the draw for graph b, stream r, element j is the
+ * generator above, unchanged, as Philox(graph_seeds[b], r, j) with j the element's index INSIDE its graph:
+ *     adjacency entry (c, i, k): j = (c N + i) N + k        node entry (i, c): j = C_adj N^2 + i C_node + c
+ * -- the global index of the unseeded stream at B = 1, so dsg_gen_noise_seeded(B = 1, {s}) is dsg_gen_noise(B = 1, s) bit for bit, and
+ * row b of a seeded batch is the B = 1 draw of graph_seeds[b] whatever B is and wherever the graph sits.  Streams as above (0: initial
+ * sample, k + 1: churn draw of executed step k, a walk's merged jump-back noise included); padded entries draw nothing and are 0.
+ * graph_seeds: HOST pointer, [B], required (NULL is DSG_ERR_INVALID).  It is copied, on `stream`, into a device buffer of the batch-B
+ * workspace, allocated by the first seeded call at that batch size (dsg_workspace_bytes counts its 8 B bytes from then on); the call
+ * synchronises `stream` before it returns.  Needs finalized weights (it uses the workspace). */
+int dsg_gen_noise_seeded(dsg_handle h, int32_t B, const uint8_t *flags, const uint64_t *graph_seeds /* host */,
+                         uint32_t noise_stream, float *out_adj, float *out_node, void *stream);
+
+/* dsg_sample_walk drawing from the per-graph streams: the same loop, and everything said above about walks, known entries, the
+ * multistep solver, snapshots, stats and captured step bodies holds (a seeded run replays the same bodies, one graph launch per step).
+ * Two differences:
+ *   - noise: init (stream 0, also of a partial-noise start) and churn draws come from Philox(graph_seeds[b], stream, local index), see
+ *         dsg_gen_noise_seeded.  Precedence is unchanged: given init_* win over stream 0, recorded noise_* over the churn streams.
+ *   - coins: coins == NULL draws them from `coin_seed`, by the generator and formula dsg_sample uses for `seed`.  The coin is one draw
+ *         per preconditioned call shared by the whole batch (precond.py:90): part of a run's identity, not of a graph's.
+ * Hence dsg_sample_seeded(B = 1, graph_seeds = {s}, coin_seed = s) equals dsg_sample(B = 1, seed = s) bit for bit.  With the option
+ * "batch_invariant" = 1 a graph's result depends on the weights, its flags row, its seed, the coin sequence, cfg / walk, its own known
+ * row and the handle's options -- not on B, its position, the other graphs.
+ *   walk == NULL: the trivial walk.  graph_seeds: host, [B], required; copied to the workspace on `stream` ahead of the synchronise
+ *   the loop's set-up already has.  Nothing is sticky: the next dsg_sample is unseeded. */
+int dsg_sample_seeded(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk /* NULL: trivial walk */,
+                      int32_t B, const uint8_t *flags,
+                      const uint64_t *graph_seeds /* host, [B], required */, uint64_t coin_seed,
+                      const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                      const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                      const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                      const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                      float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream);
+
 /* sigma_steps (fp64, edm.py:84-88) and the fp32 per-step scalars the loop uses; out arrays of
  * length num_steps.  Host-only helper, exposed so bindings/tests can inspect the schedule. */
 int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t_hat, float *noise_coef,
@@ -258,6 +292,12 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *       dsg_debug_need_lists below); 0: every row.  Bit-identical results either way.
  *   "fused_merge" (PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path; 1: where it pays (>= 8192 merged
  *   rows), 2: at every size, 0: merge_ln kernel).
+ * "batch_invariant" (default 0): 1 -- every choice the plan makes (which kernel, which tile, fused or not, any summation order) is a
+ *   function of the network geometry and the other options only, never of the batch size: PatchMerging is fused wherever "fused_merge"
+ *   is on, at every size, and the bf16 GEMM of the "gemm_bf16" / bf16_pipe = 0 path keeps its 128 x 96 tile.  A sample's result then
+ *   does not depend on B or on its position.  A geometry whose fused read-out would place a graph's pooling partials by
+ *   its position (N * N not a multiple of 32) is refused with DSG_ERR_INVALID.  Holds on the default fp32 path and under "gemm_bf16";
+ *   not under "gemm_split", whose kernel orders a row's partial products by the row's index mod 64.  0: the previous behaviour, bit for bit.
  * Reverse loop: "loop_graph" = 1 (default): dsg_sample replays one captured hipGraph per step (a handful of distinct step bodies:
  *   first / steady / last step x the two self-conditioning coins); 0: the round-1 scheme, only the network forward is a graph.
  * Precision modes (default: exact fp32 MFMA everywhere):
