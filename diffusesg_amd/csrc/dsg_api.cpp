@@ -107,6 +107,9 @@ struct Workspace {
     // masked-token pruning: the need lists derived from `flags` whenever they are staged (stage_flags), at fixed addresses -- captured
     // graphs read them -- and this batch size's list offsets; cnt [n_lists], cnt_ps [B][n_lists] scratch of the list kernel
     int *need_lists = nullptr, *need_cnt = nullptr, *need_cnt_ps = nullptr;
+    int *dd_rep = nullptr;   // pure-window deduplication: every graph's representative pure window (kernels.h), [B] behind cnt_ps
+    int dd_fwd = -1;         // what this workspace's last forward did: -1 no deduplication, 0 the copy moved rows of x only, 1 also their
+                             // (sum, sumsq) pairs in `stats` (the block left them for the fused PatchMerging); dsg_debug_dedup_lists
     size_t need_ints = 0;
     NeedPlan need;
 };
@@ -160,6 +163,7 @@ struct dsg_handle_s {
     bool opt_fused_attn = true, opt_fused_mlp = true, opt_fused_readout = true, opt_fused_pe = true;
     bool opt_fused_merge_small = false;   // also fuse PatchMerging below the size where it pays (tests force it on)
     bool opt_prune_masked = true;     // up path: skip rows / windows that only feed masked (padded) tokens (prune_on below)
+    bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_on below)
     PrunePlan prune;
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
     std::vector<int> prof_list;
@@ -674,6 +678,7 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     h->opt_loop_graph = env_on("DSG_LOOP_GRAPH", true);
     h->opt_fused_merge = env_on("DSG_FUSED_MERGE", true);
     h->opt_prune_masked = env_on("DSG_PRUNE_MASKED", true);
+    h->opt_dedup_masked = env_on("DSG_DEDUP_MASKED", true);
     if (getenv("DSG_FUSED_MLP_MAXC")) h->opt_fused_mlp_maxc = atoi(getenv("DSG_FUSED_MLP_MAXC"));
     h->opt_gemm_bf16 = env_on("DSG_GEMM_BF16", false);
     h->opt_bf16_pipe = env_on("DSG_BF16_PIPE", true);
@@ -1029,10 +1034,12 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
         const int nl = w->need.n_lists;
         size_t off = 0;
         for (int k = 0; k < nl; k++) { w->need.list_off[k] = (int)off; off += (size_t)B * prune_plan(h).items[k] + 16; }
-        w->need_ints = off + nl + (size_t)B * nl;
+        const bool dd = w->need.dd_wins >= 0;
+        w->need_ints = off + nl + (size_t)B * nl + (dd ? (size_t)B : 0);
         if (int rc = dev_alloc(h, w->allocs, &q, sizeof(int) * w->need_ints)) return rc;
         HIP_TRY(h, hipMemset(q, 0, sizeof(int) * w->need_ints));   // counts of 0 until the first flags are staged
         w->need_lists = (int *)q; w->need_cnt = w->need_lists + off; w->need_cnt_ps = w->need_cnt + nl;
+        if (dd) w->dd_rep = w->need_cnt_ps + (size_t)B * nl;
         w->bytes += sizeof(int) * w->need_ints;
     }
     *out = w.get();
@@ -1114,6 +1121,15 @@ void build_prune_plan(dsg_handle h) {
         Q.roles.push_back(PruneRole{0, res / 2, 0, i, -2, Q.coarse[i]});
     }
     if (overflow) return;
+    // pure-window deduplication: PatchEmbed and the finest level's first block, where that block is unshifted on 8 x 8 windows
+    // (three lists behind the pruning's; without room for them the pruning stands alone)
+    if (!h->down[0].empty() && h->down[0][0].shift == 0 && h->down[0][0].ws == 8 && h->down[0][0].res == N && h->down[0][0].C == 96 &&
+        np.n_lists + 3 <= NEED_MAX_LISTS) {
+        const int nW = (N / 8) * (N / 8);
+        np.dd_wins = new_list(nW);
+        np.dd_runs = new_list(N * N / 8);
+        np.dd_copy = new_list(nW);
+    }
     P = Q;
     P.np = np;
 }
@@ -1128,6 +1144,24 @@ bool prune_on(dsg_handle h, const Workspace *w) {
     // (the row-mapped GEMM addresses whole tensors through one buffer descriptor: the widest one must stay below 2 GiB)
     return w->need_lists && prune_opts_on(h) && (size_t)w->B * h->N * h->N * h->E * h->cfg.mlp_ratio * sizeof(float) < 0x7fffffffull;
 }
+// Pure-window deduplication (option "dedup_masked"; rule and list formats: kernels.h).  At a token (i, j) with a padded endpoint
+// fused_patch_embed96_kernel zeroes the node channels itself, and the adjacency channels it reads there are zero whenever the state came
+// from the sampler's own kernels (each stores `valid ? ... : 0.f`).  The PatchEmbed accumulator of such a token is then the bias, its
+// row depends on nothing but the graph's (scale, shift), and an unshifted block maps every all-padding ("pure") window of a graph to the
+// same 64 rows -- bit for bit, the kernels being deterministic and position-blind apart from the position inside the window.  So
+// PatchEmbed and the finest level's first block run over the non-pure windows plus ONE pure window per graph, and
+// window_broadcast96_kernel copies that window's rows (and their LayerNorm partials) to the graph's other pure windows before anything
+// else reads them: behind the copy w->x / w->stats hold exactly what the full launches would have written.
+// Decided at plan time: on only where the pruning is (same kernels, same list machinery) and where PatchEmbed, attention and MLP of
+// that block are the fused C = 96 kernels.  Decided per call on the device: an entry point that cannot vouch for the zeros (caller
+// tensors: dsg_denoise, dsg_precond) stages lists that name every window as unique and copy nothing (stage_flags).
+bool dedup_opts_on(dsg_handle h) {
+    if (!h->opt_dedup_masked || !prune_opts_on(h) || prune_plan(h).np.dd_wins < 0) return false;
+    const BlockPlan &b0 = h->down[0][0];
+    return h->opt_fused_pe && h->pe_wp && (h->Kp == 32 || h->Kp == 64) && h->opt_fused_attn && b0.wqp && h->opt_fused_mlp && b0.w1p &&
+           b0.C <= h->opt_fused_mlp_maxc;
+}
+bool dedup_on(dsg_handle h, const Workspace *w) { return w->dd_rep && dedup_opts_on(h) && prune_on(h, w); }
 struct NeedRef { const int *list = nullptr, *cnt = nullptr; int id = -1; };
 NeedRef need_ref(dsg_handle h, const Workspace *w, int id) {
     if (id < 0 || !prune_on(h, w)) return NeedRef();
@@ -1268,12 +1302,13 @@ void embed_rows(dsg_handle h, const float *c_noise, int rows, float *pe, float *
 // input assembly + PatchEmbed (diffusesg.py:784-802, 562-577) -> w->x.  Returns true when the first block's modulate+SiLU rode
 // along (fused kernel only).  fp32 path: only when that block is the fused C = 96 attention kernel (which then skips it);
 // any_first_block: whatever the first block is (the bf16 block pipeline normalises the modulated tensor in its own row pass).
-bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s, bool *xn_done = nullptr) {
+bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s, bool *xn_done = nullptr, const NeedRef &pe_runs = NeedRef()) {
     const dsg_config &c = h->cfg;
     const int B = w->B, N = h->N, E = h->E, T0 = N * N;
     GemmArgs g;
     bool pe_done = false, pe_premod = false;
     if (h->opt_fused_pe && h->pe_wp) {
+        h->prof_next_list = pe_runs.id;
         ProfScope ps_(h, s, PK_FUSED, 2.0 * (double)B * T0 * E * h->Cin, "launch_fused_patch_embed96");
         // the first block's modulate+SiLU rides along when that block is the fused C = 96 attention kernel (which then skips it)
         const BlockPlan *b0 = h->down[0].empty() ? nullptr : &h->down[0][0];
@@ -1281,7 +1316,9 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
         pe_done = launch_fused_patch_embed96(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
                                              WT(h, "patch_embed.proj.bias"), WT(h, "patch_embed.norm.weight"),
                                              WT(h, "patch_embed.norm.bias"), w->aff, w->aff_ld, h->pe_aff_off, pe_premod ? b0->aff_off : -1,
-                                             w->x, B, N, h->Ca, h->Cn, c.self_condition, h->Kp, s, (xn_done && pe_premod) ? w->xn : nullptr);
+                                             w->x, B, N, h->Ca, h->Cn, c.self_condition, h->Kp, s, (xn_done && pe_premod) ? w->xn : nullptr,
+                                             pe_runs.list, pe_runs.cnt);
+        if (pe_runs.list && !pe_done) plan_fail(h, "patch_embed: fused kernel with a run list not built (Kp=%d)", h->Kp);
         pe_premod = pe_premod && pe_done;
         if (xn_done) *xn_done = pe_premod;
     }
@@ -1550,7 +1587,11 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
         // noise embedding (diffusesg.py:768-771) and every block's (scale,shift) in one GEMM
         embed_rows(h, w->c_noise, B, w->pe, w->emb0, w->emb, w->aff, s);
     }
-    const bool pe_premod = patch_embed_stage(h, w, true, s);
+    // pure-window deduplication: PatchEmbed and level 0's first block take the unique lists, then the copy fills the other pure windows
+    const bool dedup = dedup_on(h, w);
+    const NeedRef dd_runs = dedup ? need_ref(h, w, w->need.dd_runs) : NeedRef(), dd_wins = dedup ? need_ref(h, w, w->need.dd_wins) : NeedRef(),
+                  dd_copy = dedup ? need_ref(h, w, w->need.dd_copy) : NeedRef();
+    const bool pe_premod = patch_embed_stage(h, w, true, s, nullptr, dd_runs);
     tap(h, "patch_embed", w->x, (size_t)B * T0 * E, s);
     // encoder (diffusesg.py:745-748)
     bool premod = pe_premod;   // is w->x already modulated for the next block (generic blocks: with LN1 partials in w->stats)?
@@ -1566,8 +1607,14 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             // long K loop costs more than the small merge_ln launch it replaces: measured 103 vs 81 + 13 us at M = 4096, K = 1536)
             const bool for_merge = !next && l < L - 1 && h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16 && C % 32 == 0 &&
                                    (B * T / 4 >= 8192 || h->opt_fused_merge_small || h->opt_batch_invariant);   // "batch_invariant": the size plays no part
-            const BlockOut bo = run_block(h, w, h->down[l][j], premod, next, for_merge, s);
+            const bool dd = dedup && l == 0 && j == 0;
+            const BlockOut bo = run_block(h, w, h->down[l][j], premod, next, for_merge, s, dd ? BlockNeed{dd_runs, dd_wins} : BlockNeed());
             premod = bo.premod; merge_parts = bo.stats_parts;
+            if (l == 0 && j == 0 && !g_dry_run) w->dd_fwd = dd ? (bo.stats_parts == 1 ? 1 : 0) : -1;
+            if (dd) {
+                // (dedup_opts_on admits the fused C = 96 attention + MLP pair only: it leaves un-modulated rows and at most one pair of partials per row)
+                P_KERN(PK_ELEM, 0.0, launch_window_broadcast96(w->x, bo.stats_parts == 1 ? w->stats : nullptr, B, N, dd_copy.list, dd_copy.cnt, w->dd_rep, s));
+            }
             snprintf(name, sizeof(name), "down%d.block%d", l, (int)j);
             tap(h, name, w->x, (size_t)B * T * C, s);
         }
@@ -1698,9 +1745,11 @@ int check_ready(dsg_handle h, int B) {
 
 // node flags into the workspace + the need lists of the masked-token pruning that follow from them (two small launches).  Flags are
 // staged once per entry-point call -- never inside a captured step body; the captured graphs read lists and counts from fixed addresses
-int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s) {
+// zero_padded: the caller vouches that every adjacency / self-conditioning value the forwards of this call read at a pair with a padded
+// endpoint is zero (the sampler: its state only ever comes from its own masking kernels) -- the pure-window deduplication's condition
+int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s, bool zero_padded = false) {
     HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)w->B * h->N, hipMemcpyDeviceToDevice, s));
-    if (w->need_lists) launch_need_lists(w->flags, w->B, h->N, w->need, w->need_cnt_ps, w->need_lists, w->need_cnt, s);
+    if (w->need_lists) launch_need_lists(w->flags, w->B, h->N, w->need, w->need_cnt_ps, w->need_lists, w->need_cnt, s, zero_padded, w->dd_rep);
     return 0;
 }
 
@@ -1887,6 +1936,7 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     size_t need = 0;   // the need lists of the masked-token pruning: every list + 16 pad entries, counts, per-sample counts
     const PrunePlan &pp = prune_plan(h);
     for (int k = 0; k < pp.np.n_lists; k++) need += sizeof(int) * ((size_t)B * pp.items[k] + 16 + 1 + (size_t)B);
+    if (pp.np.dd_wins >= 0) need += sizeof(int) * (size_t)B;   // the representative windows of the pure-window deduplication
     auto it = h->ws.find(B);   // + the known tensors and masks of dsg_sample_known, once a conditioned call has allocated them
     const size_t known = it != h->ws.end() ? it->second->known_bytes : 0;
     const size_t seeds = it != h->ws.end() ? it->second->seeds_bytes : 0;   // + the graph seeds, once a seeded call has allocated them
@@ -1901,9 +1951,9 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         return std::tie(h->opt_fused_attn, h->opt_fused_mlp, h->opt_fused_mlp_maxc, h->opt_fused_readout, h->opt_fused_pe, h->opt_fused_rowstats,
                         h->opt_fused_qkv_attn, h->opt_loop_graph, h->opt_bf16_act, h->opt_bf16_pipe, h->opt_bf16_mlp, h->opt_bf16_qkv_attn,
                         h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked,
-                        h->opt_batch_invariant);
+                        h->opt_batch_invariant, h->opt_dedup_masked);
     };
-    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool> saved = opts();
+    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool> saved = opts();
     if (n == "fused_attn") h->opt_fused_attn = value != 0;
     else if (n == "fused_mlp") h->opt_fused_mlp = value != 0;
     else if (n == "fused_mlp_maxc") h->opt_fused_mlp_maxc = value;
@@ -1919,6 +1969,7 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     else if (n == "bf16_proj_mlp") h->opt_bf16_proj_mlp = value != 0;
     else if (n == "bf16_readout") h->opt_bf16_readout = value != 0;
     else if (n == "prune_masked") h->opt_prune_masked = value != 0;
+    else if (n == "dedup_masked") h->opt_dedup_masked = value != 0;
     else if (n == "batch_invariant") h->opt_batch_invariant = value != 0;
     else if (n == "fused_merge") { h->opt_fused_merge = value != 0; h->opt_fused_merge_small = value > 1; }   // 2: at every size
     else if (n == "gemm_bf16") {
@@ -1962,6 +2013,7 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "bf16_proj_mlp") *value = (bx_on(h) && h->opt_bf16_mlp && h->opt_bf16_proj_mlp) ? 1 : 0;
     else if (n == "bf16_readout") *value = (bx_on(h) && h->opt_bf16_readout && h->opt_fused_readout) ? 1 : 0;
     else if (n == "prune_masked") *value = prune_opts_on(h);   // what runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
+    else if (n == "dedup_masked") *value = dedup_opts_on(h);   // what runs (in the sampler): 0 wherever the pruning is off, or the fused C = 96 kernels are
     else if (n == "batch_invariant") *value = h->opt_batch_invariant;
     else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
     else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
@@ -2194,7 +2246,9 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
         for (int i = 0; i < ncalls; i++) coin_buf[i] = (gen() >> 63) & 1;
     }
     h->last_stats = dsg_sample_stats{};
-    if (int rc = stage_flags(h, w, flags, s)) return rc;
+    // every state the loop's forwards read (x_hat, the denoised estimates, the known-entry select) is stored as `valid ? ... : 0.f` by
+    // init_*_kernel, churn_tab_kernel, precond_out_tab*_kernel and the update kernels: zero at padded pairs whatever the caller passed
+    if (int rc = stage_flags(h, w, flags, s, /*zero_padded=*/true)) return rc;
     if (graph_seeds) if (int rc = stage_seeds(h, w, graph_seeds, s)) return rc;
     // x0 = init * sigma(t0) (edm.py:326, :346-347)
     if (graph_seeds && base_adj)
@@ -2463,6 +2517,29 @@ int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_ro
         }
         off += n;
     }
+    return DSG_OK;
+}
+
+int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream) {
+    if (int rc = check_ready(h, B)) return rc;
+    if (!counts) return fail(h, DSG_ERR_INVALID, "null argument");
+    auto it = h->ws.find(B);
+    if (it == h->ws.end()) return fail(h, DSG_ERR_STATE, "no workspace for batch %d: run dsg_denoise/dsg_sample first", B);
+    Workspace *w = it->second.get();
+    counts[0] = counts[1] = counts[2] = -1;
+    counts[3] = w->dd_fwd;
+    if (!w->dd_rep) return DSG_OK;
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    std::vector<int> all(w->need_ints);
+    HIP_TRY(h, hipMemcpy(all.data(), w->need_lists, sizeof(int) * w->need_ints, hipMemcpyDeviceToHost));
+    const int *cnt = all.data() + (w->need_cnt - w->need_lists);
+    const int ids[3] = {w->need.dd_wins, w->need.dd_runs, w->need.dd_copy};
+    int32_t *dst[3] = {wins, runs, copy};
+    for (int k = 0; k < 3; k++) {
+        counts[k] = cnt[ids[k]];
+        if (dst[k]) memcpy(dst[k], all.data() + w->need.list_off[ids[k]], sizeof(int) * (size_t)counts[k]);
+    }
+    if (rep) memcpy(rep, all.data() + (w->dd_rep - w->need_lists), sizeof(int) * (size_t)B);
     return DSG_OK;
 }
 

@@ -152,8 +152,9 @@ void launch_fused_mlp(float *x, const float *gam, const float *bet, const float 
 bool launch_fused_patch_embed96(const float *adj, const float *node, const float *sc_adj, const float *sc_node, const int *has_sc,
                                 const uint8_t *flags, const float *Wp, const float *bias, const float *gam, const float *bet,
                                 const float *aff, int aff_ld, int aff_off, int aff_off2, float *x, int B, int N, int Ca, int Cn,
-                                int self_cond, int Kp, hipStream_t s, void *xn = nullptr);   // aff_off2 >= 0: also apply that block's
+                                int self_cond, int Kp, hipStream_t s, void *xn = nullptr,   // aff_off2 >= 0: also apply that block's
                                 // modulate+SiLU; xn (bf16 [B*N*N, 96]): also the LayerNorm (no affine) of the stored row (bf16 pipeline)
+                                const int *run_list = nullptr, const int *run_cnt = nullptr);   // run list: only those 8-token runs (no xn then)
 // final LN + folded read_out/adj-head chain + masked adjacency output, and the LN(x) pooling for the node head (E = 96)
 // pool_part [B*N][readout_pool_segments(N)][96]: per-tile partial sums, reduced in fixed order into pool_ext [B*N,128]
 int readout_pool_segments(int N);
@@ -206,9 +207,24 @@ enum NeedKind { NEED_EMIT = 0,      // write the current set (side `res`) as run
                 NEED_PARENT = 2 };  // res = fine side: the set becomes the coarse runs holding a parent (i/2, j/2) of a needed token
 struct NeedOp { int kind, res, shift, list; };
 constexpr int NEED_MAX_OPS = 40, NEED_MAX_LISTS = 32, NEED_MAX_RUNS = 2048;   // runs of one sample at the finest level: N * N / 8
-struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_off[NEED_MAX_LISTS]; };
+struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_off[NEED_MAX_LISTS];
+                  // pure-window deduplication (below): the unique 8-token runs / unique windows of the finest level and the pure windows
+                  // that are filled by copy; -1 = no such lists
+                  int dd_runs = -1, dd_wins = -1, dd_copy = -1; };
 // cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
-void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s);
+// dedup / dd_rep: see below (dd_rep may be null when the plan has no dd_* lists)
+void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s,
+                       bool dedup = false, int *dd_rep = nullptr);
+
+// ---- pure-window deduplication (option "dedup_masked") ----
+// An 8 x 8 window of the finest level is PURE when every token (i, j) of it has a padded endpoint (!(flag_i && flag_j)).  Where the
+// forward's inputs are zero at such tokens, PatchEmbed gives all of them one row and an unshifted Swin block gives every pure window of
+// a graph the same 64 rows, so one representative per graph (its first pure window, dd_rep[b] = b * nW + w, -1: the graph has none) is
+// computed and the others are filled by copy.  need_lists_kernel writes, in the formats above: dd_wins / dd_runs -- every non-pure
+// window plus the representative, as windows and as their 8-token runs; dd_copy -- the pure windows other than the representative.
+// dedup == false (the caller does not vouch for the zeros): every window is listed as unique, nothing is copied.
+// The copy: rows of x [B * N * N, 96] and, when stats is non-null, their (sum, sumsq) pairs stats [B * N * N][2]
+void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *copy_list, const int *copy_cnt, const int *dd_rep, hipStream_t s);
 
 // ---- preconditioning / sampler elementwise kernels (adj and node parts handled in one launch) ----
 struct StatePtrs { float *adj; float *node; };

@@ -1342,7 +1342,9 @@ void launch_fused_readout96(const float *x, const float *gam, const float *bet, 
 // coalesced), Y^T = Wpe . in^T on the matrix cores, LayerNorm over the 96 outputs (split over registers and the two
 // half-waves), modulate, SiLU, 16-B stores.  KP = in_chans rounded up to 32.
 // =================================================================================================
-template <int KP, int CA = 0, int CN = 0>   // CA, CN > 0: compile-time channel counts (the index divisions become multiplies)
+// LIST (pure-window deduplication): the wave's 32 tokens are 4 runs of 8 consecutive tokens taken from run_list (-1 pads; nothing at or
+// beyond *run_cnt), as in fused_mlp_kernel; the tile goes back run by run.  Every token is computed exactly as without a list.
+template <int KP, int CA = 0, int CN = 0, bool LIST = false>   // CA, CN > 0: compile-time channel counts (the index divisions become multiplies)
 __global__ __launch_bounds__(256, 2) void fused_patch_embed96_kernel(const float *__restrict__ adj, const float *__restrict__ node,
                                                                     const float *__restrict__ sc_adj, const float *__restrict__ sc_node,
                                                                     const int *__restrict__ has_sc, const uint8_t *__restrict__ flags,
@@ -1350,14 +1352,26 @@ __global__ __launch_bounds__(256, 2) void fused_patch_embed96_kernel(const float
                                                                     const float *__restrict__ gam, const float *__restrict__ bet,
                                                                     const float *__restrict__ aff, int aff_ld, int aff_off, int aff_off2,
                                                                     float *__restrict__ x, int B, int N, int Ca_rt, int Cn_rt, int self_cond,
-                                                                    void *__restrict__ xn) {
+                                                                    void *__restrict__ xn, const int *__restrict__ run_list,
+                                                                    const int *__restrict__ run_cnt) {
     constexpr int C = 96, S = KP / 8;
     const int Ca = CA > 0 ? CA : Ca_rt, Cn = CN > 0 ? CN : Cn_rt;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lrow = lane & 31, lhalf = lane >> 5;
     const int T = N * N, M = B * T;
-    const int m = (blockIdx.x * 4 + wave) * 32 + lrow;
-    const bool ok = m < M;
+    int m = (blockIdx.x * 4 + wave) * 32 + lrow;
+    bool ok = m < M;
+    int run4[4] = {-1, -1, -1, -1};   // LIST: the wave's four runs (wave-uniform)
+    if (LIST) {
+        const int r4 = (blockIdx.x * 4 + wave) * 4;
+        if (r4 >= *run_cnt) return;   // no block-level synchronisation below
+#pragma unroll
+        for (int q = 0; q < 4; q++) run4[q] = __builtin_amdgcn_readfirstlane(run_list[r4 + q]);
+        const int q = lrow >> 3;
+        const int run = q == 0 ? run4[0] : (q == 1 ? run4[1] : (q == 2 ? run4[2] : run4[3]));
+        ok = run >= 0 && run < M / 8;
+        m = run * 8 + (lrow & 7);
+    }
     const int mc = ok ? m : M - 1;
     const int b = mc / T, i = (mc / N) % N, j = mc % N;
     const bool sc_on = self_cond && sc_adj != nullptr && (has_sc == nullptr || *has_sc != 0);
@@ -1446,6 +1460,18 @@ __global__ __launch_bounds__(256, 2) void fused_patch_embed96_kernel(const float
                 for (int t = 0; t < 4; t++) { acc[nt][4 * g + t] = o[t]; s1 += o[t]; s2 = fmaf(o[t], o[t], s2); }
             }
         }
+    if (LIST) {
+#pragma unroll
+        for (int q = 0; q < 4; q++)   // tile rows 8 q .. 8 q + 7 -> the run's 8 consecutive rows (8 x 24 float4 pieces, three per lane)
+            if (run4[q] >= 0 && run4[q] < M / 8) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const int p = 64 * k + lane, r = p / 24, c = p - 24 * r;
+                    *reinterpret_cast<f32x4 *>(x + ((size_t)run4[q] * 8 + r) * C + 4 * c) = *reinterpret_cast<const f32x4 *>(tile + (8 * q + r) * T96_LD + 4 * c);
+                }
+            }
+        return;   // (no xn with a list: the bf16 pipeline does not deduplicate)
+    }
     if (rows_w > 0) t96_store_rows(tile, x + (size_t)m_w * C, rows_w, lane);
     if (xn) {   // bf16 block pipeline: LayerNorm-1 (no affine) of the stored row as the bf16 tensor the first QKV GEMM reads
         s1 += __shfl_xor(s1, 32, 64);
@@ -1467,10 +1493,19 @@ __global__ __launch_bounds__(256, 2) void fused_patch_embed96_kernel(const float
 bool launch_fused_patch_embed96(const float *adj, const float *node, const float *sc_adj, const float *sc_node, const int *has_sc,
                                 const uint8_t *flags, const float *Wp, const float *bias, const float *gam, const float *bet,
                                 const float *aff, int aff_ld, int aff_off, int aff_off2, float *x, int B, int N, int Ca, int Cn,
-                                int self_cond, int Kp, hipStream_t s, void *xn) {
+                                int self_cond, int Kp, hipStream_t s, void *xn, const int *run_list, const int *run_cnt) {
     const int M = B * N * N;
     const dim3 grid((M + 127) / 128), block(256);
-#define PE_ARGS adj, node, sc_adj, sc_node, has_sc, flags, Wp, bias, gam, bet, aff, aff_ld, aff_off, aff_off2, x, B, N, Ca, Cn, self_cond, xn
+#define PE_ARGS adj, node, sc_adj, sc_node, has_sc, flags, Wp, bias, gam, bet, aff, aff_ld, aff_off, aff_off2, x, B, N, Ca, Cn, self_cond, xn, run_list, run_cnt
+    if (run_list) {   // (runs are 8 consecutive tokens of one row of the grid: N % 8 == 0)
+        if (xn || !run_cnt || N % 8 != 0) return false;
+        if (Kp == 64 && Ca == 6 && Cn == 12) DSG_LAUNCH((fused_patch_embed96_kernel<64, 6, 12, true>), grid, block, 0, s, PE_ARGS);
+        else if (Kp == 64 && Ca == 3 && Cn == 12) DSG_LAUNCH((fused_patch_embed96_kernel<64, 3, 12, true>), grid, block, 0, s, PE_ARGS);
+        else if (Kp == 32) DSG_LAUNCH((fused_patch_embed96_kernel<32, 0, 0, true>), grid, block, 0, s, PE_ARGS);
+        else if (Kp == 64) DSG_LAUNCH((fused_patch_embed96_kernel<64, 0, 0, true>), grid, block, 0, s, PE_ARGS);
+        else return false;
+        return true;
+    }
     if (Kp == 64 && Ca == 6 && Cn == 12) DSG_LAUNCH((fused_patch_embed96_kernel<64, 6, 12>), grid, block, 0, s, PE_ARGS);       // VG bits
     else if (Kp == 64 && Ca == 3 && Cn == 12) DSG_LAUNCH((fused_patch_embed96_kernel<64, 3, 12>), grid, block, 0, s, PE_ARGS);  // COCO bits
     else if (Kp == 32) DSG_LAUNCH((fused_patch_embed96_kernel<32>), grid, block, 0, s, PE_ARGS);
@@ -2698,8 +2733,11 @@ void launch_encode(const int32_t *q_adj, const int32_t *q_node, const float *bbo
 // =================================================================================================
 template <int PHASE>
 __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restrict__ flags, int B, int N, NeedPlan plan,
-                                                         int *__restrict__ cnt_ps, int *__restrict__ lists, int *__restrict__ cnt) {
+                                                         int *__restrict__ cnt_ps, int *__restrict__ lists, int *__restrict__ cnt,
+                                                         int dedup, int *__restrict__ dd_rep) {
     __shared__ uint8_t map_a[NEED_MAX_RUNS], map_b[NEED_MAX_RUNS], win[NEED_MAX_RUNS / 8];
+    __shared__ uint8_t blk_any[NEED_MAX_RUNS / 8];
+    __shared__ int rep_s;
     __shared__ int scan[257];
     __shared__ int base_part[8][NEED_MAX_LISTS];
     __shared__ int base[NEED_MAX_LISTS];
@@ -2794,12 +2832,79 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             uint8_t *t = cur; cur = nxt; nxt = t;
         }
     }
+    // Pure-window deduplication (kernels.h): the finest level's 8 x 8 windows.  Window (wi, wj) is pure iff no node of row block wi or
+    // none of column block wj is valid -- then !(flag_i && flag_j) for each of its 64 tokens.  (N <= 128: at most 16 x 16 windows.)
+    if (plan.dd_wins >= 0) {
+        const int nwr = N / 8, nW = nwr * nwr;
+        uint8_t *pure = map_a, *runs = map_b;   // the walk above is over: its maps are free
+        __syncthreads();
+        if (tid < nwr) {
+            bool any = false;
+            for (int k = 0; k < 8; k++) any = any || flags[(size_t)b * N + tid * 8 + k] != 0;
+            blk_any[tid] = any ? 1 : 0;
+        }
+        __syncthreads();
+        for (int w = tid; w < nW; w += 256) pure[w] = (dedup && !(blk_any[w / nwr] && blk_any[w % nwr])) ? 1 : 0;
+        __syncthreads();
+        if (tid == 0) {   // the representative: the graph's first pure window
+            int r = -1;
+            for (int w = 0; w < nW && r < 0; w++) if (pure[w]) r = w;
+            rep_s = r;
+        }
+        __syncthreads();
+        const int rep = rep_s;
+        for (int w = tid; w < nW; w += 256) win[w] = (!pure[w] || w == rep) ? 1 : 0;
+        __syncthreads();
+        emit(win, nW, plan.dd_wins, b * nW);
+        for (int idx = tid; idx < N * nwr; idx += 256) {   // run (i, jr) lies in window (i / 8, jr)
+            const int i = idx / nwr, jr = idx - i * nwr;
+            runs[idx] = win[(i >> 3) * nwr + jr];
+        }
+        __syncthreads();
+        emit(runs, N * nwr, plan.dd_runs, b * N * nwr);
+        for (int w = tid; w < nW; w += 256) win[w] = (pure[w] && w != rep) ? 1 : 0;
+        __syncthreads();
+        emit(win, nW, plan.dd_copy, b * nW);
+        if (PHASE == 1 && tid == 0) dd_rep[b] = rep < 0 ? -1 : b * nW + rep;
+    }
 }
 
-void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s) {
+void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s,
+                       bool dedup, int *dd_rep) {
     if (plan.n_lists < 1) return;
-    DSG_LAUNCH(need_lists_kernel<0>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt);
-    DSG_LAUNCH(need_lists_kernel<1>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt);
+    DSG_LAUNCH(need_lists_kernel<0>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt, dedup ? 1 : 0, dd_rep);
+    DSG_LAUNCH(need_lists_kernel<1>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt, dedup ? 1 : 0, dd_rep);
+}
+
+// The copy of the pure-window deduplication: block k fills window copy_list[k] (b * nW + w) of x [B * N * N, 96] from its graph's
+// representative window dd_rep[b] -- 64 rows of 24 float4 -- and, with stats, the rows' (sum, sumsq) pairs.  Fixed grid of B * nW
+// blocks; blocks at or beyond *copy_cnt return.  Source and destination windows are disjoint, so one launch needs no ordering inside.
+__global__ __launch_bounds__(256) void window_broadcast96_kernel(float *__restrict__ x, float *__restrict__ stats, int B, int N,
+                                                                 const int *__restrict__ copy_list, const int *__restrict__ copy_cnt,
+                                                                 const int *__restrict__ dd_rep) {
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (k >= *copy_cnt) return;
+    const int nwr = N / 8, nW = nwr * nwr;
+    const int dst = copy_list[k];
+    if (dst < 0 || dst >= B * nW) return;
+    const int b = dst / nW, src = dd_rep[b];
+    if (src < b * nW || src >= (b + 1) * nW || src == dst) return;
+    const int dw = dst - b * nW, sw = src - b * nW;
+    const size_t d0 = (size_t)b * N * N + (size_t)(dw / nwr) * 8 * N + (dw % nwr) * 8;   // first token of the window
+    const size_t s0 = (size_t)b * N * N + (size_t)(sw / nwr) * 8 * N + (sw % nwr) * 8;
+    for (int p = tid; p < 64 * 24; p += 256) {
+        const int t = p / 24, c = p - 24 * t;
+        const size_t off = (size_t)(t >> 3) * N + (t & 7);   // token t = (row t / 8, column t % 8) of the window
+        *reinterpret_cast<f32x4 *>(x + (d0 + off) * 96 + 4 * c) = *reinterpret_cast<const f32x4 *>(x + (s0 + off) * 96 + 4 * c);
+    }
+    if (stats && tid < 64) {
+        const size_t off = (size_t)(tid >> 3) * N + (tid & 7);
+        *reinterpret_cast<float2 *>(stats + 2 * (d0 + off)) = *reinterpret_cast<const float2 *>(stats + 2 * (s0 + off));
+    }
+}
+
+void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *copy_list, const int *copy_cnt, const int *dd_rep, hipStream_t s) {
+    DSG_LAUNCH(window_broadcast96_kernel, dim3(B * (N / 8) * (N / 8)), dim3(256), 0, s, x, stats, B, N, copy_list, copy_cnt, dd_rep);
 }
 
 }  // namespace dsg

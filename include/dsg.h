@@ -290,6 +290,9 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *   "fused_qkv_attn" (8x8 / 10x10 windows: QKV projection + window attention in one kernel, q/k/v never reach HBM),
  *   "prune_masked" (default 1): the up path computes only rows / windows that can reach an unmasked output (see
  *       dsg_debug_need_lists below); 0: every row.  Bit-identical results either way.
+ *   "dedup_masked" (default 1; acts in the sampler entry points only, and only where "prune_masked" does): a graph's level-0
+ *       windows that hold nothing but padded pairs are computed once through PatchEmbed and the first Swin block and copied (see
+ *       dsg_debug_dedup_lists below); 0: every window is computed.  Bit-identical results either way.
  *   "fused_merge" (PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path; 1: where it pays (>= 8192 merged
  *   rows), 2: at every size, 0: merge_ln kernel).
  * "batch_invariant" (default 0): 1 -- every choice the plan makes (which kernel, which tile, fused or not, any summation order) is a
@@ -351,6 +354,18 @@ double dsg_profile_clock_ghz(dsg_handle h);
  * masked}.  roles == NULL only returns *n_roles (0 when the configuration is not covered). */
 int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_roles, int32_t *n_roles, int32_t *lists_out,
                          int64_t lists_cap, void *stream);
+/* Pure-window deduplication (option "dedup_masked", default 1).  An 8 x 8 window of the finest level is pure when each of its tokens
+ * (i, j) has a padded endpoint.  In the sampler every input of the network is zero at such tokens (the loop's own kernels store the
+ * zeros), so all pure windows of a graph leave PatchEmbed and the first, unshifted Swin block with the same 64 rows: one representative
+ * per graph is computed, the others are filled by a copy before PatchMerging reads them.  dsg_denoise / dsg_precond take caller
+ * tensors and compute every window.  Off wherever "prune_masked" is, and unless PatchEmbed and that block run the fused C = 96 kernels.
+ * dsg_debug_dedup_lists copies what the flags last staged for batch B produced to HOST buffers (any but counts may be NULL): counts [4] =
+ * entries of wins / runs / copy (-1 each: the configuration has no such lists) and what the batch size's last forward did (-1: it did not
+ * deduplicate; 0: the copy moved activation rows; 1: also their LayerNorm partials, which the fused PatchMerging reads); wins (capacity B * nW): unique windows b * nW + w -- every
+ * non-pure window and the representative; runs (B * N * N / 8): the same set as 8-token runs; copy (B * nW): the pure windows filled
+ * by copy; rep [B]: each graph's representative window b * nW + w, -1 where the graph has no pure window (or the call deduplicates
+ * nothing). */
+int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream);
 int dsg_debug_tap(dsg_handle h, const char *stage, float *dst, int64_t capacity);
 void dsg_debug_clear_taps(dsg_handle h);
 
