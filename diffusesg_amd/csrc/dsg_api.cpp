@@ -107,9 +107,10 @@ struct Workspace {
     // masked-token pruning: the need lists derived from `flags` whenever they are staged (stage_flags), at fixed addresses -- captured
     // graphs read them -- and this batch size's list offsets; cnt [n_lists], cnt_ps [B][n_lists] scratch of the list kernel
     int *need_lists = nullptr, *need_cnt = nullptr, *need_cnt_ps = nullptr;
-    int *dd_rep = nullptr;   // pure-window deduplication: every graph's representative pure window (kernels.h), [B] behind cnt_ps
-    int dd_fwd = -1;         // what this workspace's last forward did: -1 no deduplication, 0 the copy moved rows of x only, 1 also their
-                             // (sum, sumsq) pairs in `stats` (the block left them for the fused PatchMerging); dsg_debug_dedup_lists
+    int *dd_rep = nullptr;   // pure-window deduplication: every graph's representative pure window (kernels.h), [1 + dd_up][B] behind cnt_ps
+    // what this workspace's last forward did at level k: -1 no deduplication, 0 the copy moved rows of x (levels >= 1: and of the skip) only,
+    // 1 also their (sum, sumsq) pairs in `stats` (the block left them for its consumer); dsg_debug_dedup_lists / dsg_debug_dedup_level_lists
+    int dd_fwd[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1};
     size_t need_ints = 0;
     NeedPlan need;
 };
@@ -164,6 +165,7 @@ struct dsg_handle_s {
     bool opt_fused_merge_small = false;   // also fuse PatchMerging below the size where it pays (tests force it on)
     bool opt_prune_masked = true;     // up path: skip rows / windows that only feed masked (padded) tokens (prune_on below)
     bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_on below)
+    int opt_dedup_levels = 0;         // how many levels may do so: 0 every qualifying one, 1 the finest only, ... (dedup_levels below)
     PrunePlan prune;
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
     std::vector<int> prof_list;
@@ -679,6 +681,7 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     h->opt_fused_merge = env_on("DSG_FUSED_MERGE", true);
     h->opt_prune_masked = env_on("DSG_PRUNE_MASKED", true);
     h->opt_dedup_masked = env_on("DSG_DEDUP_MASKED", true);
+    if (getenv("DSG_DEDUP_LEVELS")) h->opt_dedup_levels = std::max(0, atoi(getenv("DSG_DEDUP_LEVELS")));
     if (getenv("DSG_FUSED_MLP_MAXC")) h->opt_fused_mlp_maxc = atoi(getenv("DSG_FUSED_MLP_MAXC"));
     h->opt_gemm_bf16 = env_on("DSG_GEMM_BF16", false);
     h->opt_bf16_pipe = env_on("DSG_BF16_PIPE", true);
@@ -1035,7 +1038,7 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
         size_t off = 0;
         for (int k = 0; k < nl; k++) { w->need.list_off[k] = (int)off; off += (size_t)B * prune_plan(h).items[k] + 16; }
         const bool dd = w->need.dd_wins >= 0;
-        w->need_ints = off + nl + (size_t)B * nl + (dd ? (size_t)B : 0);
+        w->need_ints = off + nl + (size_t)B * nl + (dd ? (size_t)B * (1 + w->need.dd_up) : 0);
         if (int rc = dev_alloc(h, w->allocs, &q, sizeof(int) * w->need_ints)) return rc;
         HIP_TRY(h, hipMemset(q, 0, sizeof(int) * w->need_ints));   // counts of 0 until the first flags are staged
         w->need_lists = (int *)q; w->need_cnt = w->need_lists + off; w->need_cnt_ps = w->need_cnt + nl;
@@ -1129,6 +1132,20 @@ void build_prune_plan(dsg_handle h) {
         np.dd_wins = new_list(nW);
         np.dd_runs = new_list(N * N / 8);
         np.dd_copy = new_list(nW);
+        // ... and the coarser levels, as far as the chain goes (kernels.h): the level below is deduplicated and that block is its only
+        // one (a second, shifted block mixes neighbouring windows: behind it pure windows no longer share their rows); level k's first
+        // block unshifted on 8 x 8 windows, at least 2 x 2 of them (a level of one window has nothing to share: its only window is its
+        // own representative); room for its lists
+        for (int k = 1; k < L && k <= NEED_MAX_DD_UP; k++) {
+            const int res = N >> k;
+            if (h->down[k - 1].size() != 1 || h->down[k].empty() || h->down[k][0].shift != 0 || h->down[k][0].ws != 8 || h->down[k][0].res != res || res % 16 != 0 ||
+                np.n_lists + 3 > NEED_MAX_LISTS)
+                break;
+            np.ddu_wins[k - 1] = new_list((res / 8) * (res / 8));
+            np.ddu_runs[k - 1] = new_list(res * res / 8);
+            np.ddu_copy[k - 1] = new_list((res / 8) * (res / 8));
+            np.dd_up = k;
+        }
     }
     P = Q;
     P.np = np;
@@ -1162,6 +1179,19 @@ bool dedup_opts_on(dsg_handle h) {
            b0.C <= h->opt_fused_mlp_maxc;
 }
 bool dedup_on(dsg_handle h, const Workspace *w) { return w->dd_rep && dedup_opts_on(h) && prune_on(h, w); }
+// How many levels may deduplicate (option "dedup_levels": 0 = every qualifying one), the finest included; 0 when none does.  Level k >= 1
+// qualifies by the plan (build_prune_plan) and where the merge into it is the partial-statistics form of PatchMerging (the "fused_merge"
+// path): forward_fixed then runs that merge over the level's run list (launch_merge_norm_runs + the row-mapped reduction GEMM: the
+// values of the gather GEMM, bit for bit) and the level's first block over its lists.  Whether a given batch size takes that merge is
+// the forward's own rule (8192 merged rows, or "fused_merge" 2 / "batch_invariant"); a level whose merge is the merge_ln kernel ends
+// the chain.  Every block kernel of those levels takes a list wherever the pruning is on (prune_opts_on).
+int dedup_levels(dsg_handle h) {
+    if (!dedup_opts_on(h)) return 0;
+    int n = 1;
+    if (h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16)
+        for (int k = 1; k <= prune_plan(h).np.dd_up && (h->E << (k - 1)) % 32 == 0; k++) n = k + 1;
+    return h->opt_dedup_levels > 0 ? std::min(n, h->opt_dedup_levels) : n;
+}
 struct NeedRef { const int *list = nullptr, *cnt = nullptr; int id = -1; };
 NeedRef need_ref(dsg_handle h, const Workspace *w, int id) {
     if (id < 0 || !prune_on(h, w)) return NeedRef();
@@ -1591,6 +1621,8 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
     const bool dedup = dedup_on(h, w);
     const NeedRef dd_runs = dedup ? need_ref(h, w, w->need.dd_runs) : NeedRef(), dd_wins = dedup ? need_ref(h, w, w->need.dd_wins) : NeedRef(),
                   dd_copy = dedup ? need_ref(h, w, w->need.dd_copy) : NeedRef();
+    const int dd_levels = dedup ? dedup_levels(h) : 0;
+    int dd_chain = 0;   // levels 0 .. dd_chain - 1 have been deduplicated by this forward
     const bool pe_premod = patch_embed_stage(h, w, true, s, nullptr, dd_runs);
     tap(h, "patch_embed", w->x, (size_t)B * T0 * E, s);
     // encoder (diffusesg.py:745-748)
@@ -1608,12 +1640,26 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             const bool for_merge = !next && l < L - 1 && h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16 && C % 32 == 0 &&
                                    (B * T / 4 >= 8192 || h->opt_fused_merge_small || h->opt_batch_invariant);   // "batch_invariant": the size plays no part
             const bool dd = dedup && l == 0 && j == 0;
-            const BlockOut bo = run_block(h, w, h->down[l][j], premod, next, for_merge, s, dd ? BlockNeed{dd_runs, dd_wins} : BlockNeed());
+            const bool ddk = l > 0 && j == 0 && dd_chain == l + 1;   // the merge above came over this level's run list
+            const BlockNeed bn = dd ? BlockNeed{dd_runs, dd_wins}
+                                    : (ddk ? BlockNeed{need_ref(h, w, w->need.ddu_runs[l - 1]), need_ref(h, w, w->need.ddu_wins[l - 1])} : BlockNeed());
+            const BlockOut bo = run_block(h, w, h->down[l][j], premod, next, for_merge, s, bn);
             premod = bo.premod; merge_parts = bo.stats_parts;
-            if (l == 0 && j == 0 && !g_dry_run) w->dd_fwd = dd ? (bo.stats_parts == 1 ? 1 : 0) : -1;
+            if (l == 0 && j == 0 && !g_dry_run) w->dd_fwd[0] = dd ? (bo.stats_parts == 1 ? 1 : 0) : -1;
             if (dd) {
                 // (dedup_opts_on admits the fused C = 96 attention + MLP pair only: it leaves un-modulated rows and at most one pair of partials per row)
                 P_KERN(PK_ELEM, 0.0, launch_window_broadcast96(w->x, bo.stats_parts == 1 ? w->stats : nullptr, B, N, dd_copy.list, dd_copy.cnt, w->dd_rep, s));
+                dd_chain = 1;
+            }
+            if (l > 0 && l <= NEED_MAX_DD_UP && j == 0 && !g_dry_run) w->dd_fwd[l] = -1;
+            if (ddk) {
+                // behind this copy x, the skip and the partials the next launch reads (a following block's LN1 partials of the
+                // pre-modulated rows, or the output rows' partials for the next merge) hold what the full launches would have written
+                const int parts = bo.premod ? (C + 95) / 96 : bo.stats_parts;
+                const NeedRef cp = need_ref(h, w, w->need.ddu_copy[l - 1]);
+                P_KERN(PK_ELEM, 0.0, launch_window_broadcast(w->x, w->skips[l - 1], parts > 0 ? w->stats : nullptr, parts, B, res, C, cp.list, cp.cnt,
+                                                             w->dd_rep + (size_t)l * B, s));
+                if (!g_dry_run) w->dd_fwd[l] = parts > 0 ? 1 : 0;
             }
             snprintf(name, sizeof(name), "down%d.block%d", l, (int)j);
             tap(h, name, w->x, (size_t)B * T * C, s);
@@ -1622,7 +1668,19 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             const std::string p = "down_layers." + std::to_string(l) + ".downsample";
             g = GemmArgs();
             g.K1 = 4 * C; g.K = 4 * C; g.M = B * T / 4; g.N = 2 * C;
-            if (merge_parts > 0) {
+            // pure-window deduplication of level l + 1: only the merged rows of its unique windows (dedup_levels above)
+            const bool ddm = merge_parts > 0 && dd_chain == l + 1 && l + 1 < dd_levels && !h->down[l + 1].empty();
+            if (ddm) {
+                // the gather + LayerNorm(4C) of the listed merged rows into y -- the values the gather form below puts into its A
+                // tile -- then the reduction over the same list, in place of the fine level (all of x has been read by then)
+                const NeedRef mr = need_ref(h, w, w->need.ddu_runs[l]);
+                P_KERN(PK_ROW, 0.0, launch_merge_norm_runs(w->x, w->stats, merge_parts, w->y, B, res, C, mr.list, mr.cnt, s));
+                g.A = w->y; g.lda = 4 * C;
+                g.W = h->merge_wf[l]; g.bias = h->merge_bf[l];
+                g.C = w->x; g.ldc = 2 * C;
+                g.row_list = mr.list; g.row_cnt = mr.cnt; h->prof_next_list = mr.id;
+                dd_chain = l + 2;
+            } else if (merge_parts > 0) {
                 // 2x2 gather, LayerNorm(4C) (statistics from the four source rows' partials, gamma/beta folded into the weight)
                 // and the reduction in one GEMM: the merged [B*T/4, 4C] tensor is never written
                 g.A = w->x; g.lda = C; g.a4_res = res; g.ln_part = w->stats; g.ln_nparts = merge_parts;
@@ -1637,7 +1695,8 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             attach_premod(h, w, g, h->down[l + 1].empty() ? nullptr : &h->down[l + 1][0]);   // the skip copy (C2) stays un-modulated
             P_GEMM_LP(g);
             premod = g.mod_aff != nullptr;
-            if (merge_parts > 0) std::swap(w->x, w->y);   // the new level's activation lives in the other buffer from here on
+            if (ddm && !premod) plan_fail(h, "down%d: the list form of PatchMerging needs the pre-modulating epilogue", l + 1);   // (mod_stats takes no list)
+            if (merge_parts > 0 && !ddm) std::swap(w->x, w->y);   // the new level's activation lives in the other buffer from here on
             merge_parts = 0;
         }
         snprintf(name, sizeof(name), "down%d", l);
@@ -1936,7 +1995,7 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     size_t need = 0;   // the need lists of the masked-token pruning: every list + 16 pad entries, counts, per-sample counts
     const PrunePlan &pp = prune_plan(h);
     for (int k = 0; k < pp.np.n_lists; k++) need += sizeof(int) * ((size_t)B * pp.items[k] + 16 + 1 + (size_t)B);
-    if (pp.np.dd_wins >= 0) need += sizeof(int) * (size_t)B;   // the representative windows of the pure-window deduplication
+    if (pp.np.dd_wins >= 0) need += sizeof(int) * (size_t)B * (1 + pp.np.dd_up);   // the representative windows of the pure-window deduplication
     auto it = h->ws.find(B);   // + the known tensors and masks of dsg_sample_known, once a conditioned call has allocated them
     const size_t known = it != h->ws.end() ? it->second->known_bytes : 0;
     const size_t seeds = it != h->ws.end() ? it->second->seeds_bytes : 0;   // + the graph seeds, once a seeded call has allocated them
@@ -1951,9 +2010,9 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         return std::tie(h->opt_fused_attn, h->opt_fused_mlp, h->opt_fused_mlp_maxc, h->opt_fused_readout, h->opt_fused_pe, h->opt_fused_rowstats,
                         h->opt_fused_qkv_attn, h->opt_loop_graph, h->opt_bf16_act, h->opt_bf16_pipe, h->opt_bf16_mlp, h->opt_bf16_qkv_attn,
                         h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked,
-                        h->opt_batch_invariant, h->opt_dedup_masked);
+                        h->opt_batch_invariant, h->opt_dedup_masked, h->opt_dedup_levels);
     };
-    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool> saved = opts();
+    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool, int> saved = opts();
     if (n == "fused_attn") h->opt_fused_attn = value != 0;
     else if (n == "fused_mlp") h->opt_fused_mlp = value != 0;
     else if (n == "fused_mlp_maxc") h->opt_fused_mlp_maxc = value;
@@ -1970,6 +2029,7 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     else if (n == "bf16_readout") h->opt_bf16_readout = value != 0;
     else if (n == "prune_masked") h->opt_prune_masked = value != 0;
     else if (n == "dedup_masked") h->opt_dedup_masked = value != 0;
+    else if (n == "dedup_levels") h->opt_dedup_levels = value > 0 ? value : 0;
     else if (n == "batch_invariant") h->opt_batch_invariant = value != 0;
     else if (n == "fused_merge") { h->opt_fused_merge = value != 0; h->opt_fused_merge_small = value > 1; }   // 2: at every size
     else if (n == "gemm_bf16") {
@@ -2014,6 +2074,7 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "bf16_readout") *value = (bx_on(h) && h->opt_bf16_readout && h->opt_fused_readout) ? 1 : 0;
     else if (n == "prune_masked") *value = prune_opts_on(h);   // what runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
     else if (n == "dedup_masked") *value = dedup_opts_on(h);   // what runs (in the sampler): 0 wherever the pruning is off, or the fused C = 96 kernels are
+    else if (n == "dedup_levels") *value = dedup_levels(h);   // what runs (in the sampler, where PatchMerging takes its partial-statistics form)
     else if (n == "batch_invariant") *value = h->opt_batch_invariant;
     else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
     else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
@@ -2520,27 +2581,33 @@ int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_ro
     return DSG_OK;
 }
 
-int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream) {
+int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
+                                int32_t *rep, void *stream) {
     if (int rc = check_ready(h, B)) return rc;
-    if (!counts) return fail(h, DSG_ERR_INVALID, "null argument");
+    if (!counts || level < 0) return fail(h, DSG_ERR_INVALID, "null argument or negative level");
     auto it = h->ws.find(B);
     if (it == h->ws.end()) return fail(h, DSG_ERR_STATE, "no workspace for batch %d: run dsg_denoise/dsg_sample first", B);
     Workspace *w = it->second.get();
     counts[0] = counts[1] = counts[2] = -1;
-    counts[3] = w->dd_fwd;
-    if (!w->dd_rep) return DSG_OK;
+    counts[3] = level <= NEED_MAX_DD_UP ? w->dd_fwd[level] : -1;
+    if (!w->dd_rep || level > w->need.dd_up) return DSG_OK;
     HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
     std::vector<int> all(w->need_ints);
     HIP_TRY(h, hipMemcpy(all.data(), w->need_lists, sizeof(int) * w->need_ints, hipMemcpyDeviceToHost));
     const int *cnt = all.data() + (w->need_cnt - w->need_lists);
-    const int ids[3] = {w->need.dd_wins, w->need.dd_runs, w->need.dd_copy};
+    const int ids[3] = {level ? w->need.ddu_wins[level - 1] : w->need.dd_wins, level ? w->need.ddu_runs[level - 1] : w->need.dd_runs,
+                        level ? w->need.ddu_copy[level - 1] : w->need.dd_copy};
     int32_t *dst[3] = {wins, runs, copy};
     for (int k = 0; k < 3; k++) {
         counts[k] = cnt[ids[k]];
         if (dst[k]) memcpy(dst[k], all.data() + w->need.list_off[ids[k]], sizeof(int) * (size_t)counts[k]);
     }
-    if (rep) memcpy(rep, all.data() + (w->dd_rep - w->need_lists), sizeof(int) * (size_t)B);
+    if (rep) memcpy(rep, all.data() + (w->dd_rep - w->need_lists) + (size_t)level * B, sizeof(int) * (size_t)B);
     return DSG_OK;
+}
+
+int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream) {
+    return dsg_debug_dedup_level_lists(h, B, 0, counts, wins, runs, copy, rep, stream);
 }
 
 int32_t dsg_affine_width(dsg_handle h) { return (h && h->finalized) ? h->aff_n : 0; }

@@ -207,12 +207,15 @@ enum NeedKind { NEED_EMIT = 0,      // write the current set (side `res`) as run
                 NEED_PARENT = 2 };  // res = fine side: the set becomes the coarse runs holding a parent (i/2, j/2) of a needed token
 struct NeedOp { int kind, res, shift, list; };
 constexpr int NEED_MAX_OPS = 40, NEED_MAX_LISTS = 32, NEED_MAX_RUNS = 2048;   // runs of one sample at the finest level: N * N / 8
+constexpr int NEED_MAX_DD_UP = 3;   // coarser levels the pure-window deduplication may reach (N <= 128: 16, 8, 4, 2 windows per side)
 struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_off[NEED_MAX_LISTS];
                   // pure-window deduplication (below): the unique 8-token runs / unique windows of the finest level and the pure windows
                   // that are filled by copy; -1 = no such lists
-                  int dd_runs = -1, dd_wins = -1, dd_copy = -1; };
+                  int dd_runs = -1, dd_wins = -1, dd_copy = -1;
+                  // the same three lists for the coarser levels 1 .. dd_up (index k - 1; "Coarser levels" below)
+                  int dd_up = 0, ddu_runs[NEED_MAX_DD_UP], ddu_wins[NEED_MAX_DD_UP], ddu_copy[NEED_MAX_DD_UP]; };
 // cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
-// dedup / dd_rep: see below (dd_rep may be null when the plan has no dd_* lists)
+// dedup / dd_rep: see below (dd_rep [1 + plan.dd_up][B]; may be null when the plan has no dd_* lists)
 void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s,
                        bool dedup = false, int *dd_rep = nullptr);
 
@@ -225,6 +228,22 @@ void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan,
 // dedup == false (the caller does not vouch for the zeros): every window is listed as unique, nothing is copied.
 // The copy: rows of x [B * N * N, 96] and, when stats is non-null, their (sum, sumsq) pairs stats [B * N * N][2]
 void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *copy_list, const int *copy_cnt, const int *dd_rep, hipStream_t s);
+// Coarser levels.  A window of level k (res = N >> k tokens per side, 8 << k nodes per window side) is pure when no valid pair lies under
+// it: no valid node in its row block of 8 << k nodes, or none in its column block.  It then lies over 2 x 2 pure windows of level k - 1,
+// whose rows are equal window by window behind that level's copy (provided that level has no further, shifted block); PatchMerging is a row-wise function of the 2 x 2 fine rows and the
+// unshifted first block of level k sees positions only inside a window, so every pure window of level k gets the same 64 rows again.
+// need_lists_kernel writes ddu_wins / ddu_runs / ddu_copy [k - 1] by the same rule and in the same formats as level 0 (ids b * nW_k + w,
+// runs b * res * res / 8 + run) and the representatives dd_rep [k * B + b].
+// The merge into such a level, over its run list: merged row m = (b, i, j) of y [B * (res / 2)^2, 4 C] = the LayerNorm(4 C) (no affine:
+// gamma / beta are folded into the reduction weight) of cat[x(2i,2j), x(2i+1,2j), x(2i,2j+1), x(2i+1,2j+1)], statistics from the four
+// fine rows' (sum, sumsq) partials ln_part [B * res^2][nparts][2] -- element for element the value the gather form of the GEMM
+// (GemmArgs::a4_res) puts into its A tile, so the row-mapped GEMM on y gives that launch's rows bit for bit.  C % 4 == 0, (res / 2) % 8 == 0.
+void launch_merge_norm_runs(const float *x, const float *ln_part, int nparts, float *y, int B, int res, int C, const int *run_list,
+                            const int *run_cnt, hipStream_t s);
+// The copy at width C: rows of x [B * res * res, C], of skip (same shape; null: none) and nparts (sum, sumsq) pairs per row of stats
+// (null: none); rep [B] = that level's representatives
+void launch_window_broadcast(float *x, float *skip, float *stats, int nparts, int B, int res, int C, const int *copy_list,
+                             const int *copy_cnt, const int *rep, hipStream_t s);
 
 // ---- preconditioning / sampler elementwise kernels (adj and node parts handled in one launch) ----
 struct StatePtrs { float *adj; float *node; };

@@ -677,7 +677,7 @@ bool launch_gemm(const GemmArgs &g, hipStream_t s) {
             if (g.act != ACT_GELU || res || epi != 0 || g.C2 || g.A2) return false;
             GEMM_MAP(true, ACT_GELU, false, 0);
         } else {
-            if (g.act != ACT_NONE || g.C2 || (g.mod_aff && !g.stats_out)) return false;
+            if (g.act != ACT_NONE || (g.C2 && res) || (g.mod_aff && !g.stats_out)) return false;   // (dual store: the list form of PatchMerging's reduction)
             if (res) { if (epi == 0) GEMM_MAP(false, ACT_NONE, true, 0); else if (epi == 1) GEMM_MAP(false, ACT_NONE, true, 1); else if (epi == 2) GEMM_MAP(false, ACT_NONE, true, 2); else GEMM_MAP(false, ACT_NONE, true, 3); }
             else { if (epi == 0) GEMM_MAP(false, ACT_NONE, false, 0); else if (epi == 1) GEMM_MAP(false, ACT_NONE, false, 1); else if (epi == 2) GEMM_MAP(false, ACT_NONE, false, 2); else GEMM_MAP(false, ACT_NONE, false, 3); }
         }
@@ -2832,40 +2832,45 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             uint8_t *t = cur; cur = nxt; nxt = t;
         }
     }
-    // Pure-window deduplication (kernels.h): the finest level's 8 x 8 windows.  Window (wi, wj) is pure iff no node of row block wi or
-    // none of column block wj is valid -- then !(flag_i && flag_j) for each of its 64 tokens.  (N <= 128: at most 16 x 16 windows.)
+    // Pure-window deduplication (kernels.h): the 8 x 8 windows of level k = 0 (the finest) .. plan.dd_up.  A level-k window covers
+    // 8 << k nodes per side; window (wi, wj) is pure iff no node of row block wi or none of column block wj is valid -- then
+    // !(flag_i && flag_j) for every pair under it.  (N <= 128: at most 16 x 16 windows.)
     if (plan.dd_wins >= 0) {
-        const int nwr = N / 8, nW = nwr * nwr;
         uint8_t *pure = map_a, *runs = map_b;   // the walk above is over: its maps are free
-        __syncthreads();
-        if (tid < nwr) {
-            bool any = false;
-            for (int k = 0; k < 8; k++) any = any || flags[(size_t)b * N + tid * 8 + k] != 0;
-            blk_any[tid] = any ? 1 : 0;
+        for (int k = 0; k <= plan.dd_up; k++) {
+            const int side = 8 << k, res = N >> k, nwr = res / 8, nW = nwr * nwr;
+            const int l_wins = k ? plan.ddu_wins[k - 1] : plan.dd_wins, l_runs = k ? plan.ddu_runs[k - 1] : plan.dd_runs,
+                      l_copy = k ? plan.ddu_copy[k - 1] : plan.dd_copy;
+            __syncthreads();
+            if (tid < nwr) {
+                bool any = false;
+                for (int q = 0; q < side; q++) any = any || flags[(size_t)b * N + tid * side + q] != 0;
+                blk_any[tid] = any ? 1 : 0;
+            }
+            __syncthreads();
+            for (int w = tid; w < nW; w += 256) pure[w] = (dedup && !(blk_any[w / nwr] && blk_any[w % nwr])) ? 1 : 0;
+            __syncthreads();
+            if (tid == 0) {   // the representative: the graph's first pure window
+                int r = -1;
+                for (int w = 0; w < nW && r < 0; w++) if (pure[w]) r = w;
+                rep_s = r;
+            }
+            __syncthreads();
+            const int rep = rep_s;
+            for (int w = tid; w < nW; w += 256) win[w] = (!pure[w] || w == rep) ? 1 : 0;
+            __syncthreads();
+            emit(win, nW, l_wins, b * nW);
+            for (int idx = tid; idx < res * nwr; idx += 256) {   // run (i, jr) lies in window (i / 8, jr)
+                const int i = idx / nwr, jr = idx - i * nwr;
+                runs[idx] = win[(i >> 3) * nwr + jr];
+            }
+            __syncthreads();
+            emit(runs, res * nwr, l_runs, b * res * nwr);
+            for (int w = tid; w < nW; w += 256) win[w] = (pure[w] && w != rep) ? 1 : 0;
+            __syncthreads();
+            emit(win, nW, l_copy, b * nW);
+            if (PHASE == 1 && tid == 0) dd_rep[(size_t)k * B + b] = rep < 0 ? -1 : b * nW + rep;
         }
-        __syncthreads();
-        for (int w = tid; w < nW; w += 256) pure[w] = (dedup && !(blk_any[w / nwr] && blk_any[w % nwr])) ? 1 : 0;
-        __syncthreads();
-        if (tid == 0) {   // the representative: the graph's first pure window
-            int r = -1;
-            for (int w = 0; w < nW && r < 0; w++) if (pure[w]) r = w;
-            rep_s = r;
-        }
-        __syncthreads();
-        const int rep = rep_s;
-        for (int w = tid; w < nW; w += 256) win[w] = (!pure[w] || w == rep) ? 1 : 0;
-        __syncthreads();
-        emit(win, nW, plan.dd_wins, b * nW);
-        for (int idx = tid; idx < N * nwr; idx += 256) {   // run (i, jr) lies in window (i / 8, jr)
-            const int i = idx / nwr, jr = idx - i * nwr;
-            runs[idx] = win[(i >> 3) * nwr + jr];
-        }
-        __syncthreads();
-        emit(runs, N * nwr, plan.dd_runs, b * N * nwr);
-        for (int w = tid; w < nW; w += 256) win[w] = (pure[w] && w != rep) ? 1 : 0;
-        __syncthreads();
-        emit(win, nW, plan.dd_copy, b * nW);
-        if (PHASE == 1 && tid == 0) dd_rep[b] = rep < 0 ? -1 : b * nW + rep;
     }
 }
 
@@ -2905,6 +2910,87 @@ __global__ __launch_bounds__(256) void window_broadcast96_kernel(float *__restri
 
 void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *copy_list, const int *copy_cnt, const int *dd_rep, hipStream_t s) {
     DSG_LAUNCH(window_broadcast96_kernel, dim3(B * (N / 8) * (N / 8)), dim3(256), 0, s, x, stats, B, N, copy_list, copy_cnt, dd_rep);
+}
+
+// The copy at width C (levels >= 1; kernels.h): block k fills window copy_list[k] (b * nW + w) of x [B * res * res, C] -- and of skip
+// and stats where given -- from its graph's representative rep[b].  Fixed grid of B * nW blocks; blocks at or beyond *copy_cnt return.
+__global__ __launch_bounds__(256) void window_broadcast_kernel(float *__restrict__ x, float *__restrict__ skip, float *__restrict__ stats,
+                                                               int nparts, int B, int res, int C, const int *__restrict__ copy_list,
+                                                               const int *__restrict__ copy_cnt, const int *__restrict__ rep) {
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (k >= *copy_cnt) return;
+    const int nwr = res / 8, nW = nwr * nwr;
+    const int dst = copy_list[k];
+    if (dst < 0 || dst >= B * nW) return;
+    const int b = dst / nW, src = rep[b];
+    if (src < b * nW || src >= (b + 1) * nW || src == dst) return;
+    const int dw = dst - b * nW, sw = src - b * nW;
+    const size_t d0 = (size_t)b * res * res + (size_t)(dw / nwr) * 8 * res + (dw % nwr) * 8;   // first token of the window
+    const size_t s0 = (size_t)b * res * res + (size_t)(sw / nwr) * 8 * res + (sw % nwr) * 8;
+    const int c4n = C / 4;
+    for (int p = tid; p < 64 * c4n; p += 256) {
+        const int t = p / c4n, c = p - c4n * t;
+        const size_t off = (size_t)(t >> 3) * res + (t & 7);   // token t = (row t / 8, column t % 8) of the window
+        *reinterpret_cast<f32x4 *>(x + (d0 + off) * C + 4 * c) = *reinterpret_cast<const f32x4 *>(x + (s0 + off) * C + 4 * c);
+        if (skip) *reinterpret_cast<f32x4 *>(skip + (d0 + off) * C + 4 * c) = *reinterpret_cast<const f32x4 *>(skip + (s0 + off) * C + 4 * c);
+    }
+    if (stats)
+        for (int p = tid; p < 64 * nparts; p += 256) {
+            const int t = p / nparts, c = p - nparts * t;
+            const size_t off = (size_t)(t >> 3) * res + (t & 7);
+            *reinterpret_cast<float2 *>(stats + 2 * ((d0 + off) * nparts + c)) = *reinterpret_cast<const float2 *>(stats + 2 * ((s0 + off) * nparts + c));
+        }
+}
+
+void launch_window_broadcast(float *x, float *skip, float *stats, int nparts, int B, int res, int C, const int *copy_list,
+                             const int *copy_cnt, const int *rep, hipStream_t s) {
+    DSG_LAUNCH(window_broadcast_kernel, dim3(B * (res / 8) * (res / 8)), dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep);
+}
+
+// PatchMerging's gather + LayerNorm(4C) over a run list of MERGED rows (kernels.h).  Block k takes run run_list[k]: 8 consecutive merged
+// rows (b, i, 8 jr .. 8 jr + 7).  Threads 0..7 form the rows' statistics exactly as gemm4_f32_kernel's AMODE 1 prologue does -- the four
+// fine rows' partial pairs through row_partials_n, added (p0 + p1) + (p2 + p3), the same `finish` arithmetic -- and every element is
+// fmaf(x, rstd, -mean * rstd), the one operation that kernel applies on the way into its A tile.  Fixed grid of B * (res / 2)^2 / 8
+// blocks; blocks at or beyond *run_cnt, and -1 pads, return.
+__global__ __launch_bounds__(256) void merge_norm_runs_kernel(const float *__restrict__ x, const float *__restrict__ ln_part, int nparts,
+                                                              float *__restrict__ y, int B, int res, int C,
+                                                              const int *__restrict__ run_list, const int *__restrict__ run_cnt) {
+    __shared__ float s_rstd[8], s_nmr[8];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= *run_cnt) return;
+    const int r2 = res >> 1, T2 = r2 * r2, M2 = B * T2;
+    const int run = run_list[blockIdx.x];
+    if (run < 0 || run >= M2 / 8) return;
+    const int m0 = run * 8;   // first merged row: (b, i, j0 .. j0 + 7), one row of the merged grid (r2 % 8 == 0)
+    const int b = m0 / T2, t = m0 - b * T2, i = t / r2, j0 = t - i * r2;
+    const size_t f0 = (size_t)b * res * res + (size_t)2 * i * res + 2 * j0;   // fine row of part 0 of merged row m0
+    if (tid < 8) {
+        const float *pp[4];
+        float sm[4], sq[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) pp[q] = ln_part + (f0 + 2 * tid + (size_t)(q & 1) * res + (q >> 1)) * nparts * 2;
+        row_partials_n<4>(pp, nparts, sm, sq);
+        const float invk = 1.0f / (float)(4 * C);
+        const float tsm = (sm[0] + sm[1]) + (sm[2] + sm[3]), tsq = (sq[0] + sq[1]) + (sq[2] + sq[3]);
+        const float mean = tsm * invk, rstd = fast_rsqrt(fmaxf(fmaf(-mean, mean, tsq * invk), 0.f) + LN_EPS);
+        s_rstd[tid] = rstd;
+        s_nmr[tid] = -mean * rstd;
+    }
+    __syncthreads();
+    const int c4n = C / 4, per_row = 4 * c4n;   // float4 pieces of one merged row: parts x00, x10, x01, x11
+    for (int p = tid; p < 8 * per_row; p += 256) {
+        const int r = p / per_row, e = p - r * per_row, q = e / c4n, c = e - q * c4n;
+        const float rstd = s_rstd[r], nmr = s_nmr[r];
+        f32x4 v = *reinterpret_cast<const f32x4 *>(x + (f0 + 2 * r + (size_t)(q & 1) * res + (q >> 1)) * C + 4 * c);
+#pragma unroll
+        for (int u = 0; u < 4; u++) v[u] = fmaf(v[u], rstd, nmr);
+        *reinterpret_cast<f32x4 *>(y + ((size_t)m0 + r) * 4 * C + (size_t)q * C + 4 * c) = v;
+    }
+}
+
+void launch_merge_norm_runs(const float *x, const float *ln_part, int nparts, float *y, int B, int res, int C, const int *run_list,
+                            const int *run_cnt, hipStream_t s) {
+    DSG_LAUNCH(merge_norm_runs_kernel, dim3(B * (res / 2) * (res / 2) / 8), dim3(256), 0, s, x, ln_part, nparts, y, B, res, C, run_list, run_cnt);
 }
 
 }  // namespace dsg

@@ -293,6 +293,13 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *   "dedup_masked" (default 1; acts in the sampler entry points only, and only where "prune_masked" does): a graph's level-0
  *       windows that hold nothing but padded pairs are computed once through PatchEmbed and the first Swin block and copied (see
  *       dsg_debug_dedup_lists below); 0: every window is computed.  Bit-identical results either way.
+ *   "dedup_levels" (default 0 = every qualifying level; env DSG_DEDUP_LEVELS): how many levels "dedup_masked" may reach, the finest
+ *       included; 1: PatchEmbed and level 0's first block only.  Level k >= 1 qualifies when level k - 1 does and has no second
+ *       (shifted) block, its own first block is unshifted on at least 2 x 2 windows of 8 x 8, and the PatchMerging into it is the partial-statistics form ("fused_merge" where
+ *       it applies: 8192 merged rows, or value 2, or "batch_invariant"): that merge then computes only the merged rows of the level's
+ *       unique windows, the first block runs over the same lists, and a copy fills the other pure windows of the activation, of the
+ *       skip tensor and of the row statistics (dsg_debug_dedup_level_lists below).  dsg_get_option reports the number of levels that
+ *       deduplicate under the present options (0: none).  Bit-identical results whatever the value.
  *   "fused_merge" (PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path; 1: where it pays (>= 8192 merged
  *   rows), 2: at every size, 0: merge_ln kernel).
  * "batch_invariant" (default 0): 1 -- every choice the plan makes (which kernel, which tile, fused or not, any summation order) is a
@@ -366,6 +373,15 @@ int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_ro
  * by copy; rep [B]: each graph's representative window b * nW + w, -1 where the graph has no pure window (or the call deduplicates
  * nothing). */
 int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream);
+/* The same for level `level` of the down path (0: exactly dsg_debug_dedup_lists).  A window of level k has 8 x 8 tokens of the grid of
+ * res = N >> k tokens per side and covers 8 << k nodes per side; it is pure when no valid pair lies under it (no valid node in its row
+ * block, or none in its column block).  wins (capacity B * nW, nW = (res / 8)^2): unique windows b * nW + w; runs (B * res * res / 8): the
+ * same set as 8-token runs b * res * res / 8 + i * res / 8 + jr -- the rows PatchMerging into the level and the level's first block
+ * compute; copy (B * nW): the pure windows filled by copy; rep [B]: the representatives.  counts [3]: what the batch size's last forward
+ * did at that level (-1: no deduplication there; 0: the copy moved rows of the activation and of the skip tensor; 1: also the rows'
+ * (sum, sumsq) partials, which the next block or the next PatchMerging reads).  counts [0..2] = -1: the plan has no lists for the level. */
+int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
+                                int32_t *rep, void *stream);
 int dsg_debug_tap(dsg_handle h, const char *stage, float *dst, int64_t capacity);
 void dsg_debug_clear_taps(dsg_handle h);
 
