@@ -111,6 +111,9 @@ struct Workspace {
     // what this workspace's last forward did at level k: -1 no deduplication, 0 the copy moved rows of x (levels >= 1: and of the skip) only,
     // 1 also their (sum, sumsq) pairs in `stats` (the block left them for its consumer); dsg_debug_dedup_lists / dsg_debug_dedup_level_lists
     int dd_fwd[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1};
+    // what stage_flags last wrote (dedup_stage_mode below): the DedupMode of the lists, the levels whose fill is trimmed (bit k) and the
+    // chain depth the trimming was worked out for -- forward_fixed checks that it reaches exactly that depth
+    int dd_mode = DD_OFF, dd_trim = 0, dd_depth = 0;
     size_t need_ints = 0;
     NeedPlan need;
 };
@@ -165,6 +168,7 @@ struct dsg_handle_s {
     bool opt_fused_merge_small = false;   // also fuse PatchMerging below the size where it pays (tests force it on)
     bool opt_prune_masked = true;     // up path: skip rows / windows that only feed masked (padded) tokens (prune_on below)
     bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_on below)
+    int opt_dedup_batch = 1;          // ... and once for the whole batch in the sampler: 0 never, 1 from DEDUP_BATCH_MIN graphs, 2 always (dedup_stage_mode below)
     int opt_dedup_levels = 0;         // how many levels may do so: 0 every qualifying one, 1 the finest only, ... (dedup_levels below)
     PrunePlan prune;
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
@@ -681,6 +685,7 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     h->opt_fused_merge = env_on("DSG_FUSED_MERGE", true);
     h->opt_prune_masked = env_on("DSG_PRUNE_MASKED", true);
     h->opt_dedup_masked = env_on("DSG_DEDUP_MASKED", true);
+    if (getenv("DSG_DEDUP_BATCH")) h->opt_dedup_batch = std::min(2, std::max(0, atoi(getenv("DSG_DEDUP_BATCH"))));
     if (getenv("DSG_DEDUP_LEVELS")) h->opt_dedup_levels = std::max(0, atoi(getenv("DSG_DEDUP_LEVELS")));
     if (getenv("DSG_FUSED_MLP_MAXC")) h->opt_fused_mlp_maxc = atoi(getenv("DSG_FUSED_MLP_MAXC"));
     h->opt_gemm_bf16 = env_on("DSG_GEMM_BF16", false);
@@ -1192,6 +1197,45 @@ int dedup_levels(dsg_handle h) {
         for (int k = 1; k <= prune_plan(h).np.dd_up && (h->E << (k - 1)) % 32 == 0; k++) n = k + 1;
     return h->opt_dedup_levels > 0 ? std::min(n, h->opt_dedup_levels) : n;
 }
+// Does the last block of level l leave row statistics for the partial-statistics form of PatchMerging at this batch size?
+// (below ~8k merged rows the reduction GEMM is a single partial wave of tiles and the gather + LayerNorm FMA in its
+// long K loop costs more than the small merge_ln launch it replaces: measured 103 vs 81 + 13 us at M = 4096, K = 1536)
+bool merge_fused_at(dsg_handle h, int B, int l) {
+    const int C = h->E << l, res = h->N >> l;
+    return l < h->L - 1 && h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16 && C % 32 == 0 &&
+           (B * res * res / 4 >= 8192 || h->opt_fused_merge_small || h->opt_batch_invariant);   // "batch_invariant": the size plays no part
+}
+// How far the chain of deduplicated levels reaches in a forward of this workspace: levels 0 .. depth - 1.  The one predicate of
+// forward_fixed (which walks the chain launch by launch and checks that it ends here) and of stage_flags (which must know the top
+// level before the lists are written: only the levels under it may trim their fills).
+int dedup_chain_depth(dsg_handle h, const Workspace *w) {
+    if (!dedup_on(h, w)) return 0;
+    const int n = dedup_levels(h);
+    int depth = 1;
+    while (depth < n && h->down[depth - 1].size() == 1 && merge_fused_at(h, w->B, depth - 1) && !h->down[depth].empty()) depth++;
+    return depth;
+}
+// One representative for the batch (option "dedup_batch"; rule: kernels.h).  The per-graph argument above never uses the graph index,
+// so it holds across graphs wherever every graph reads the same (scale, shift) row: `uniform_row` is the caller's word that every
+// forward between this staging and the next is batch-uniform (sample_impl: all of them go through precond_tab, which sets
+// w->uniform).  From DEDUP_BATCH_MIN graphs by default: below 16 graphs no down-path list launch of the N = 64 network exceeds half a
+// round of 512 resident GEMM tiles, so fewer rows buy no time there -- and the per-graph lists stay what small batches always had.
+// Results are bit-identical either way.
+// Trimming (bit k of *trim): level k's fill may leave out what nobody reads only when every later reader of its activation,
+// statistics and skip goes through a list -- level k + 1 is deduplicated by the same forward (its merge takes the run list) and, from
+// level 1 on, the up stage reads the skip through a coarse list (levels 0 .. k then have single unshifted blocks, down and up alike,
+// so that list stays inside non-pure windows).  Without a coarse list the skip is read whole and the level is filled completely.
+constexpr int DEDUP_BATCH_MIN = 16;
+int dedup_stage_mode(dsg_handle h, const Workspace *w, bool zero_padded, bool uniform_row, int *trim, int *depth) {
+    *trim = 0; *depth = 0;
+    if (!zero_padded) return DD_OFF;
+    if (!uniform_row || !dedup_on(h, w) || h->opt_dedup_batch == 0 || (h->opt_dedup_batch == 1 && w->B < DEDUP_BATCH_MIN)) return DD_GRAPH;
+    *depth = dedup_chain_depth(h, w);
+    const PrunePlan &pp = prune_plan(h);
+    for (int k = 0; k + 1 < *depth; k++)
+        if (k == 0 || pp.coarse[h->L - k] >= 0) *trim |= 1 << k;
+    return DD_BATCH;
+}
 struct NeedRef { const int *list = nullptr, *cnt = nullptr; int id = -1; };
 NeedRef need_ref(dsg_handle h, const Workspace *w, int id) {
     if (id < 0 || !prune_on(h, w)) return NeedRef();
@@ -1635,10 +1679,7 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             // block (no upsample there); otherwise PatchMerging, which takes the un-modulated tensor
             const BlockPlan *next = j + 1 < h->down[l].size() ? &h->down[l][j + 1] : (l == L - 1 && !h->up[0].empty() ? &h->up[0][0] : nullptr);
             // the level's last block leaves row statistics for the fused PatchMerging
-            // (below ~8k merged rows the reduction GEMM is a single partial wave of tiles and the gather + LayerNorm FMA in its
-            // long K loop costs more than the small merge_ln launch it replaces: measured 103 vs 81 + 13 us at M = 4096, K = 1536)
-            const bool for_merge = !next && l < L - 1 && h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16 && C % 32 == 0 &&
-                                   (B * T / 4 >= 8192 || h->opt_fused_merge_small || h->opt_batch_invariant);   // "batch_invariant": the size plays no part
+            const bool for_merge = !next && merge_fused_at(h, B, l);
             const bool dd = dedup && l == 0 && j == 0;
             const bool ddk = l > 0 && j == 0 && dd_chain == l + 1;   // the merge above came over this level's run list
             const BlockNeed bn = dd ? BlockNeed{dd_runs, dd_wins}
@@ -1702,6 +1743,11 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
         snprintf(name, sizeof(name), "down%d", l);
         tap(h, name, w->x, l < L - 1 ? (size_t)B * (T / 4) * 2 * C : (size_t)B * T * C, s);
         // the deepest level's skip is popped and discarded by the first up layer (diffusesg.py:754-755)
+    }
+    // lists with one representative for the batch were trimmed for one chain depth and hold for batch-uniform forwards only
+    if (dedup && w->dd_mode == DD_BATCH && !g_dry_run) {
+        if (dd_chain != w->dd_depth) plan_fail(h, "dedup_batch: the forward deduplicated %d levels, the lists were staged for %d", dd_chain, w->dd_depth);
+        if (!w->uniform) plan_fail(h, "dedup_batch: a forward with per-sample noise labels under lists shared across the batch");
     }
     // decoder (diffusesg.py:751-756); with masked-token pruning every launch behind the plan's cut takes its need list
     const PrunePlan &pp = prune_plan(h);
@@ -1806,9 +1852,13 @@ int check_ready(dsg_handle h, int B) {
 // staged once per entry-point call -- never inside a captured step body; the captured graphs read lists and counts from fixed addresses
 // zero_padded: the caller vouches that every adjacency / self-conditioning value the forwards of this call read at a pair with a padded
 // endpoint is zero (the sampler: its state only ever comes from its own masking kernels) -- the pure-window deduplication's condition
-int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s, bool zero_padded = false) {
+// uniform_row: ... and that every one of those forwards reads the batch-uniform (scale, shift) row: one representative may then serve
+// the whole batch (dedup_stage_mode)
+int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s, bool zero_padded = false, bool uniform_row = false) {
     HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)w->B * h->N, hipMemcpyDeviceToDevice, s));
-    if (w->need_lists) launch_need_lists(w->flags, w->B, h->N, w->need, w->need_cnt_ps, w->need_lists, w->need_cnt, s, zero_padded, w->dd_rep);
+    w->dd_mode = dedup_stage_mode(h, w, zero_padded, uniform_row, &w->dd_trim, &w->dd_depth);
+    if (w->need_lists)
+        launch_need_lists(w->flags, w->B, h->N, w->need, w->need_cnt_ps, w->need_lists, w->need_cnt, s, w->dd_mode, w->dd_rep, w->dd_trim);
     return 0;
 }
 
@@ -2010,9 +2060,9 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         return std::tie(h->opt_fused_attn, h->opt_fused_mlp, h->opt_fused_mlp_maxc, h->opt_fused_readout, h->opt_fused_pe, h->opt_fused_rowstats,
                         h->opt_fused_qkv_attn, h->opt_loop_graph, h->opt_bf16_act, h->opt_bf16_pipe, h->opt_bf16_mlp, h->opt_bf16_qkv_attn,
                         h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked,
-                        h->opt_batch_invariant, h->opt_dedup_masked, h->opt_dedup_levels);
+                        h->opt_batch_invariant, h->opt_dedup_masked, h->opt_dedup_levels, h->opt_dedup_batch);
     };
-    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool, int> saved = opts();
+    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool, int, int> saved = opts();
     if (n == "fused_attn") h->opt_fused_attn = value != 0;
     else if (n == "fused_mlp") h->opt_fused_mlp = value != 0;
     else if (n == "fused_mlp_maxc") h->opt_fused_mlp_maxc = value;
@@ -2030,6 +2080,12 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     else if (n == "prune_masked") h->opt_prune_masked = value != 0;
     else if (n == "dedup_masked") h->opt_dedup_masked = value != 0;
     else if (n == "dedup_levels") h->opt_dedup_levels = value > 0 ? value : 0;
+    else if (n == "dedup_batch") {
+        // acts where the lists are written (stage_flags) and nowhere else: the launches, their grids and the list addresses are the
+        // same for every value, so the captured graphs stay -- one captured under either kind of list replays under the other
+        h->opt_dedup_batch = value < 0 ? 0 : (value > 2 ? 2 : value);
+        return DSG_OK;
+    }
     else if (n == "batch_invariant") h->opt_batch_invariant = value != 0;
     else if (n == "fused_merge") { h->opt_fused_merge = value != 0; h->opt_fused_merge_small = value > 1; }   // 2: at every size
     else if (n == "gemm_bf16") {
@@ -2075,6 +2131,7 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "prune_masked") *value = prune_opts_on(h);   // what runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
     else if (n == "dedup_masked") *value = dedup_opts_on(h);   // what runs (in the sampler): 0 wherever the pruning is off, or the fused C = 96 kernels are
     else if (n == "dedup_levels") *value = dedup_levels(h);   // what runs (in the sampler, where PatchMerging takes its partial-statistics form)
+    else if (n == "dedup_batch") *value = dedup_opts_on(h) ? h->opt_dedup_batch : 0;   // what runs (in the sampler; 1: from 16 graphs)
     else if (n == "batch_invariant") *value = h->opt_batch_invariant;
     else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
     else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
@@ -2309,7 +2366,8 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
     h->last_stats = dsg_sample_stats{};
     // every state the loop's forwards read (x_hat, the denoised estimates, the known-entry select) is stored as `valid ? ... : 0.f` by
     // init_*_kernel, churn_tab_kernel, precond_out_tab*_kernel and the update kernels: zero at padded pairs whatever the caller passed
-    if (int rc = stage_flags(h, w, flags, s, /*zero_padded=*/true)) return rc;
+    // ... and every forward of the loop goes through precond_tab: one sigma, one (scale, shift) row for the whole batch
+    if (int rc = stage_flags(h, w, flags, s, /*zero_padded=*/true, /*uniform_row=*/true)) return rc;
     if (graph_seeds) if (int rc = stage_seeds(h, w, graph_seeds, s)) return rc;
     // x0 = init * sigma(t0) (edm.py:326, :346-347)
     if (graph_seeds && base_adj)
@@ -2512,6 +2570,7 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
         forward_fixed(h, w, s);
         h->prof_stamps = false;
         HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = plan_status(h, w)) return rc;   // (lists staged under other options: run the entry point again first)
         HIP_TRY(h, hipMemcpy(stamps.data(), h->prof_gemm, sizeof(unsigned long long) * stamps.size(), hipMemcpyDeviceToHost));
         for (int i = 0; i < h->prof_gemm_used; i++) {
             if (stamps[4 * i + 1] > stamps[4 * i]) gemm_inkernel_ms += (double)(stamps[4 * i + 1] - stamps[4 * i]) * 1e-5;  // 100 MHz ticks

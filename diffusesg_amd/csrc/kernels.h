@@ -215,9 +215,12 @@ struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_
                   // the same three lists for the coarser levels 1 .. dd_up (index k - 1; "Coarser levels" below)
                   int dd_up = 0, ddu_runs[NEED_MAX_DD_UP], ddu_wins[NEED_MAX_DD_UP], ddu_copy[NEED_MAX_DD_UP]; };
 // cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
-// dedup / dd_rep: see below (dd_rep [1 + plan.dd_up][B]; may be null when the plan has no dd_* lists)
+// dedup (a DedupMode) / dd_rep / trim_mask: see below (dd_rep [1 + plan.dd_up][B]; may be null when the plan has no dd_* lists)
+enum DedupMode { DD_OFF = 0,      // every window is listed as unique, nothing is copied
+                 DD_GRAPH = 1,    // one representative pure window per graph
+                 DD_BATCH = 2 };  // one for the whole batch ("One representative for the batch" below)
 void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s,
-                       bool dedup = false, int *dd_rep = nullptr);
+                       int dedup = DD_OFF, int *dd_rep = nullptr, int trim_mask = 0);
 
 // ---- pure-window deduplication (option "dedup_masked") ----
 // An 8 x 8 window of the finest level is PURE when every token (i, j) of it has a padded endpoint (!(flag_i && flag_j)).  Where the
@@ -225,7 +228,7 @@ void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan,
 // a graph the same 64 rows, so one representative per graph (its first pure window, dd_rep[b] = b * nW + w, -1: the graph has none) is
 // computed and the others are filled by copy.  need_lists_kernel writes, in the formats above: dd_wins / dd_runs -- every non-pure
 // window plus the representative, as windows and as their 8-token runs; dd_copy -- the pure windows other than the representative.
-// dedup == false (the caller does not vouch for the zeros): every window is listed as unique, nothing is copied.
+// DD_OFF (the caller does not vouch for the zeros): every window is listed as unique, nothing is copied.
 // The copy: rows of x [B * N * N, 96] and, when stats is non-null, their (sum, sumsq) pairs stats [B * N * N][2]
 void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *copy_list, const int *copy_cnt, const int *dd_rep, hipStream_t s);
 // Coarser levels.  A window of level k (res = N >> k tokens per side, 8 << k nodes per window side) is pure when no valid pair lies under
@@ -234,6 +237,16 @@ void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *
 // unshifted first block of level k sees positions only inside a window, so every pure window of level k gets the same 64 rows again.
 // need_lists_kernel writes ddu_wins / ddu_runs / ddu_copy [k - 1] by the same rule and in the same formats as level 0 (ids b * nW_k + w,
 // runs b * res * res / 8 + run) and the representatives dd_rep [k * B + b].
+// One representative for the batch (DD_BATCH).  Nothing in the argument above uses the graph index: where every graph also reads the
+// same (scale, shift) row (the sampler's batch-uniform sigma, aff_ld = 0), a pure window of graph a and one of graph b get the same 64
+// rows at every level.  Level k's representative is then the first pure window of the BATCH in (graph, window) order; dd_rep[k * B + b]
+// holds that one global id for every b (-1: no graph has a pure window at level k), the unique lists hold every non-pure window plus
+// that one, and the copies read it across graphs.  The representatives of two levels may lie in different graphs.
+// trim_mask, bit k: level k's fill lists only the pure windows that lie under a unique window of level k + 1 (a non-pure one or that
+// level's representative) -- the only ones anything reads when the merge into level k + 1 runs over that level's run list and the
+// up path reads level k's skip through a coarse list (which stays inside non-pure windows below a chain of unshifted single blocks).
+// A level without the bit (the top of the chain, whose next reader takes everything) fills every other pure window.  Chain premise:
+// every fine window under a unique coarse window is unique or filled, whichever graphs the representatives lie in.
 // The merge into such a level, over its run list: merged row m = (b, i, j) of y [B * (res / 2)^2, 4 C] = the LayerNorm(4 C) (no affine:
 // gamma / beta are folded into the reduction weight) of cat[x(2i,2j), x(2i+1,2j), x(2i,2j+1), x(2i+1,2j+1)], statistics from the four
 // fine rows' (sum, sumsq) partials ln_part [B * res^2][nparts][2] -- element for element the value the gather form of the GEMM
@@ -241,7 +254,7 @@ void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *
 void launch_merge_norm_runs(const float *x, const float *ln_part, int nparts, float *y, int B, int res, int C, const int *run_list,
                             const int *run_cnt, hipStream_t s);
 // The copy at width C: rows of x [B * res * res, C], of skip (same shape; null: none) and nparts (sum, sumsq) pairs per row of stats
-// (null: none); rep [B] = that level's representatives
+// (null: none); rep [B] = that level's representatives (global window ids, of any graph)
 void launch_window_broadcast(float *x, float *skip, float *stats, int nparts, int B, int res, int C, const int *copy_list,
                              const int *copy_cnt, const int *rep, hipStream_t s);
 

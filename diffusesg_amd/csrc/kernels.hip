@@ -2734,10 +2734,11 @@ void launch_encode(const int32_t *q_adj, const int32_t *q_node, const float *bbo
 template <int PHASE>
 __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restrict__ flags, int B, int N, NeedPlan plan,
                                                          int *__restrict__ cnt_ps, int *__restrict__ lists, int *__restrict__ cnt,
-                                                         int dedup, int *__restrict__ dd_rep) {
+                                                         int dedup, int trim_mask, int *__restrict__ dd_rep) {
     __shared__ uint8_t map_a[NEED_MAX_RUNS], map_b[NEED_MAX_RUNS], win[NEED_MAX_RUNS / 8];
     __shared__ uint8_t blk_any[NEED_MAX_RUNS / 8];
     __shared__ int rep_s;
+    __shared__ int rep_all[NEED_MAX_DD_UP + 1];
     __shared__ int scan[257];
     __shared__ int base_part[8][NEED_MAX_LISTS];
     __shared__ int base[NEED_MAX_LISTS];
@@ -2835,8 +2836,36 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
     // Pure-window deduplication (kernels.h): the 8 x 8 windows of level k = 0 (the finest) .. plan.dd_up.  A level-k window covers
     // 8 << k nodes per side; window (wi, wj) is pure iff no node of row block wi or none of column block wj is valid -- then
     // !(flag_i && flag_j) for every pair under it.  (N <= 128: at most 16 x 16 windows.)
+    // DD_BATCH (kernels.h, "One representative for the batch"): level k's representative is the first pure window of the whole batch in
+    // (graph, window) order, found by every block for itself from the flags of all graphs -- B * N bytes, the same answer in every
+    // block and in both phases -- and the fill of a level whose bit is set in trim_mask lists only the pure windows under a unique
+    // window of level k + 1.
     if (plan.dd_wins >= 0) {
         uint8_t *pure = map_a, *runs = map_b;   // the walk above is over: its maps are free
+        if (dedup == DD_BATCH) {
+            __syncthreads();
+            if (tid <= plan.dd_up) rep_all[tid] = 0x7fffffff;
+            __syncthreads();
+            for (int g = tid; g < B; g += 256) {
+                unsigned any = 0;   // bit q: a valid node among nodes 8 q .. 8 q + 7 of graph g; then, level by level, among (8 << k) q ..
+                for (int q = 0; q < N / 8; q++)
+                    for (int e = 0; e < 8; e++) any |= flags[(size_t)g * N + q * 8 + e] != 0 ? 1u << q : 0u;
+                for (int k = 0; k <= plan.dd_up; k++) {
+                    const int nwr = (N >> k) / 8;
+                    if (k > 0) {
+                        unsigned up = 0;
+                        for (int q = 0; q < nwr; q++) up |= ((any >> (2 * q)) & 3u) ? 1u << q : 0u;
+                        any = up;
+                    }
+                    // the graph's first pure window: window 0 when row block 0 is empty, else (0, q) for the first empty column block q
+                    int first = -1;
+                    if (!(any & 1u)) first = 0;
+                    else for (int q = 1; q < nwr && first < 0; q++) if (!((any >> q) & 1u)) first = q;
+                    if (first >= 0) atomicMin(&rep_all[k], g * nwr * nwr + first);
+                }
+            }
+            __syncthreads();
+        }
         for (int k = 0; k <= plan.dd_up; k++) {
             const int side = 8 << k, res = N >> k, nwr = res / 8, nW = nwr * nwr;
             const int l_wins = k ? plan.ddu_wins[k - 1] : plan.dd_wins, l_runs = k ? plan.ddu_runs[k - 1] : plan.dd_runs,
@@ -2850,9 +2879,10 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             __syncthreads();
             for (int w = tid; w < nW; w += 256) pure[w] = (dedup && !(blk_any[w / nwr] && blk_any[w % nwr])) ? 1 : 0;
             __syncthreads();
-            if (tid == 0) {   // the representative: the graph's first pure window
+            if (tid == 0) {   // the representative: the graph's first pure window; DD_BATCH: the batch's, where it lies in this graph
                 int r = -1;
-                for (int w = 0; w < nW && r < 0; w++) if (pure[w]) r = w;
+                if (dedup == DD_BATCH) { if (rep_all[k] >= b * nW && rep_all[k] < (b + 1) * nW) r = rep_all[k] - b * nW; }
+                else for (int w = 0; w < nW && r < 0; w++) if (pure[w]) r = w;
                 rep_s = r;
             }
             __syncthreads();
@@ -2866,24 +2896,37 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             }
             __syncthreads();
             emit(runs, res * nwr, l_runs, b * res * nwr);
-            for (int w = tid; w < nW; w += 256) win[w] = (pure[w] && w != rep) ? 1 : 0;
+            const bool trim = dedup == DD_BATCH && ((trim_mask >> k) & 1) && k < plan.dd_up;
+            for (int w = tid; w < nW; w += 256) {
+                bool fill = pure[w] && w != rep;
+                if (fill && trim) {   // only under a unique window of level k + 1: a non-pure one, or that level's representative
+                    const int pi = (w / nwr) >> 1, pj = (w % nwr) >> 1, nwr1 = nwr / 2;
+                    const bool up_valid = (blk_any[2 * pi] || blk_any[2 * pi + 1]) && (blk_any[2 * pj] || blk_any[2 * pj + 1]);
+                    fill = up_valid || b * nwr1 * nwr1 + pi * nwr1 + pj == rep_all[k + 1];
+                }
+                win[w] = fill ? 1 : 0;
+            }
             __syncthreads();
             emit(win, nW, l_copy, b * nW);
-            if (PHASE == 1 && tid == 0) dd_rep[(size_t)k * B + b] = rep < 0 ? -1 : b * nW + rep;
+            if (PHASE == 1 && tid == 0) {
+                if (dedup == DD_BATCH) dd_rep[(size_t)k * B + b] = rep_all[k] == 0x7fffffff ? -1 : rep_all[k];
+                else dd_rep[(size_t)k * B + b] = rep < 0 ? -1 : b * nW + rep;
+            }
         }
     }
 }
 
 void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s,
-                       bool dedup, int *dd_rep) {
+                       int dedup, int *dd_rep, int trim_mask) {
     if (plan.n_lists < 1) return;
-    DSG_LAUNCH(need_lists_kernel<0>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt, dedup ? 1 : 0, dd_rep);
-    DSG_LAUNCH(need_lists_kernel<1>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt, dedup ? 1 : 0, dd_rep);
+    DSG_LAUNCH(need_lists_kernel<0>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt, dedup, trim_mask, dd_rep);
+    DSG_LAUNCH(need_lists_kernel<1>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt, dedup, trim_mask, dd_rep);
 }
 
-// The copy of the pure-window deduplication: block k fills window copy_list[k] (b * nW + w) of x [B * N * N, 96] from its graph's
-// representative window dd_rep[b] -- 64 rows of 24 float4 -- and, with stats, the rows' (sum, sumsq) pairs.  Fixed grid of B * nW
-// blocks; blocks at or beyond *copy_cnt return.  Source and destination windows are disjoint, so one launch needs no ordering inside.
+// The copy of the pure-window deduplication: block k fills window copy_list[k] (b * nW + w) of x [B * N * N, 96] from the
+// representative window dd_rep[b] of its graph b (a window of b, or of any graph when the batch shares one) -- 64 rows of 24 float4 --
+// and, with stats, the rows' (sum, sumsq) pairs.  Fixed grid of B * nW blocks; blocks at or beyond *copy_cnt, and entries or sources
+// outside [0, B * nW), return.  Sources are unique windows and never listed for a fill, so one launch needs no ordering inside.
 __global__ __launch_bounds__(256) void window_broadcast96_kernel(float *__restrict__ x, float *__restrict__ stats, int B, int N,
                                                                  const int *__restrict__ copy_list, const int *__restrict__ copy_cnt,
                                                                  const int *__restrict__ dd_rep) {
@@ -2893,10 +2936,11 @@ __global__ __launch_bounds__(256) void window_broadcast96_kernel(float *__restri
     const int dst = copy_list[k];
     if (dst < 0 || dst >= B * nW) return;
     const int b = dst / nW, src = dd_rep[b];
-    if (src < b * nW || src >= (b + 1) * nW || src == dst) return;
-    const int dw = dst - b * nW, sw = src - b * nW;
+    if (src < 0 || src >= B * nW || src == dst) return;
+    const int sb = src / nW;   // the source's graph: b, or with one representative for the batch any graph
+    const int dw = dst - b * nW, sw = src - sb * nW;
     const size_t d0 = (size_t)b * N * N + (size_t)(dw / nwr) * 8 * N + (dw % nwr) * 8;   // first token of the window
-    const size_t s0 = (size_t)b * N * N + (size_t)(sw / nwr) * 8 * N + (sw % nwr) * 8;
+    const size_t s0 = (size_t)sb * N * N + (size_t)(sw / nwr) * 8 * N + (sw % nwr) * 8;
     for (int p = tid; p < 64 * 24; p += 256) {
         const int t = p / 24, c = p - 24 * t;
         const size_t off = (size_t)(t >> 3) * N + (t & 7);   // token t = (row t / 8, column t % 8) of the window
@@ -2923,10 +2967,11 @@ __global__ __launch_bounds__(256) void window_broadcast_kernel(float *__restrict
     const int dst = copy_list[k];
     if (dst < 0 || dst >= B * nW) return;
     const int b = dst / nW, src = rep[b];
-    if (src < b * nW || src >= (b + 1) * nW || src == dst) return;
-    const int dw = dst - b * nW, sw = src - b * nW;
+    if (src < 0 || src >= B * nW || src == dst) return;
+    const int sb = src / nW;   // the source's graph: b, or with one representative for the batch any graph
+    const int dw = dst - b * nW, sw = src - sb * nW;
     const size_t d0 = (size_t)b * res * res + (size_t)(dw / nwr) * 8 * res + (dw % nwr) * 8;   // first token of the window
-    const size_t s0 = (size_t)b * res * res + (size_t)(sw / nwr) * 8 * res + (sw % nwr) * 8;
+    const size_t s0 = (size_t)sb * res * res + (size_t)(sw / nwr) * 8 * res + (sw % nwr) * 8;
     const int c4n = C / 4;
     for (int p = tid; p < 64 * c4n; p += 256) {
         const int t = p / c4n, c = p - c4n * t;

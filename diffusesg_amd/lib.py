@@ -288,7 +288,8 @@ class Handle:
     def dedup_lists(self, B: int, stream=None):
         """Lists of the pure-window deduplication as the flags last staged for batch B left them (dsg_debug_dedup_lists): dict of
         int32 arrays wins (unique windows b * nW + w), runs (the same set as 8-token runs), copy (pure windows filled by copy) and
-        rep [B] (each graph's representative window, -1: none), and fwd: what the batch size's last forward did (-1 no deduplication,
+        rep [B] (each graph's representative window, -1: none; in a sampler call under "dedup_batch" one global id, of whichever graph,
+        for every graph), and fwd: what the batch size's last forward did (-1 no deduplication,
         0 the copy moved activation rows, 1 also their LayerNorm partials); None when the configuration has no such lists."""
         import numpy as np
         n = self.cfg.max_node_num

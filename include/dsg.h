@@ -300,6 +300,14 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *       unique windows, the first block runs over the same lists, and a copy fills the other pure windows of the activation, of the
  *       skip tensor and of the row statistics (dsg_debug_dedup_level_lists below).  dsg_get_option reports the number of levels that
  *       deduplicate under the present options (0: none).  Bit-identical results whatever the value.
+ *   "dedup_batch" (default 1; env DSG_DEDUP_BATCH; acts in the sampler entry points only, where sigma -- and with it every block's
+ *       (scale, shift) row -- is the same for the whole batch): the pure windows of ALL graphs of a batch share one computed
+ *       representative per level, the batch's first pure window, and a level below the top of the chain fills only the pure windows
+ *       that a unique window of the next level lies over (nothing reads the others).  0: one representative per graph.  1: across the
+ *       batch from 16 graphs on, per graph below -- below 16 graphs no list launch of the N = 64 network's down path exceeds half a
+ *       round of resident GEMM tiles, so fewer rows buy no time there.  2: across the batch at every size.  dsg_denoise / dsg_precond
+ *       (per-sample noise labels, caller tensors) list every window as unique whatever the value.  dsg_get_option reports the value in
+ *       force (0 wherever "dedup_masked" is off).  Bit-identical results whatever the value.
  *   "fused_merge" (PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path; 1: where it pays (>= 8192 merged
  *   rows), 2: at every size, 0: merge_ln kernel).
  * "batch_invariant" (default 0): 1 -- every choice the plan makes (which kernel, which tile, fused or not, any summation order) is a
@@ -371,7 +379,10 @@ int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_ro
  * deduplicate; 0: the copy moved activation rows; 1: also their LayerNorm partials, which the fused PatchMerging reads); wins (capacity B * nW): unique windows b * nW + w -- every
  * non-pure window and the representative; runs (B * N * N / 8): the same set as 8-token runs; copy (B * nW): the pure windows filled
  * by copy; rep [B]: each graph's representative window b * nW + w, -1 where the graph has no pure window (or the call deduplicates
- * nothing). */
+ * nothing).  What is reported is what was staged, i.e. the lists the launches iterate: under "dedup_batch" (a sampler call with one
+ * representative for the batch) rep holds the same global id b' * nW + w for every graph -- a window of whichever graph b' comes first
+ * with a pure window -- wins / runs hold every non-pure window plus that one, and copy holds the pure windows that are filled: all
+ * others at the top level of the chain, below it only those under a unique window of the next level. */
 int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream);
 /* The same for level `level` of the down path (0: exactly dsg_debug_dedup_lists).  A window of level k has 8 x 8 tokens of the grid of
  * res = N >> k tokens per side and covers 8 << k nodes per side; it is pure when no valid pair lies under it (no valid node in its row
