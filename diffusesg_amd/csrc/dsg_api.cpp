@@ -2783,6 +2783,85 @@ int dsg_debug_fused_attn96_f32(int32_t B, int32_t res, int32_t ws, int32_t shift
     return debug_finish(true, s);
 }
 
+// ---- the training kernels on their own (test hooks, csrc/train_kernels.hip): no handle, device pointers, one call of the launcher,
+// then the stream is synchronised; a form the launcher refuses (it marks the stream's scratch) is DSG_ERR_INVALID, a HIP error
+// DSG_ERR_HIP ----
+static int debug_t_finish(bool built, hipStream_t s) {
+    const hipError_t e = hipStreamSynchronize(s), le = hipGetLastError();
+    const bool refused = t_scratch_failed(s, true);
+    if (e != hipSuccess || le != hipSuccess) return DSG_ERR_HIP;
+    return (built && !refused) ? DSG_OK : DSG_ERR_INVALID;
+}
+
+int dsg_debug_t_gemm(int32_t ta, int32_t tb, const float *A, int32_t lda, const float *B, int32_t ldb, const float *bias, float *C, int32_t ldc,
+                     int32_t M, int32_t N, int32_t K, int32_t accumulate, float *a_colsum, const float *res, int32_t act, float *c2,
+                     int32_t force_plain, int32_t *route_out, void *stream) {
+    if (!A || !B || !C || M < 1 || N < 1 || K < 1 || lda < 1 || ldb < 1 || ldc < N) return DSG_ERR_INVALID;
+    if (act != ACT_NONE && act != ACT_GELU_KEEP && act != ACT_DGELU) return DSG_ERR_INVALID;
+    if ((act == ACT_GELU_KEEP && !c2) || (act == ACT_DGELU && !res) || (a_colsum && !(ta && !tb))) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    int route[2] = {0, 0};
+    t_gemm(ta != 0, tb != 0, A, lda, B, ldb, bias, C, ldc, M, N, K, accumulate != 0, s, a_colsum, res, act, c2, route, force_plain != 0 ? 1 : 0);
+    if (route_out) { route_out[0] = route[0]; route_out[1] = route[1]; }
+    return debug_t_finish(true, s);
+}
+
+int dsg_debug_t_attn(int32_t bwd, int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const float *qkv, const float *table,
+                     float *out, const float *d_out, float *d_qkv, float *d_table, int32_t force_plain, void *stream) {
+    if (B < 1 || ws < 1 || res < ws || res % ws != 0 || ws * ws > 128 || shift < 0 || shift >= ws || heads < 1 || !qkv || !table)
+        return DSG_ERR_INVALID;
+    if (bwd ? (!d_out || !d_qkv || !d_table) : !out) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_t_finish(t_attn_debug(bwd != 0, qkv, table, out, d_out, d_qkv, d_table, B, res, ws, shift, heads, force_plain != 0, s), s);
+}
+
+int dsg_debug_t_ln(int32_t bwd, int32_t M, int32_t C, int32_t T, const float *x, const float *aff, float *y_mod, const float *gamma,
+                   const float *beta, float *y, float *stats, const float *dy, const float *dx_in, float *dx_out, float *d_gamma,
+                   float *d_beta, void *stream) {
+    if (M < 1 || C < 1 || !x || !gamma || !stats) return DSG_ERR_INVALID;
+    if (bwd ? (!dy || !dx_out) : (!beta || !y || (aff && (!y_mod || T < 1)))) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (bwd) t_ln_bwd(x, gamma, stats, dy, dx_in, dx_out, d_gamma, d_beta, M, C, s);
+    else t_ln_fwd_mod(x, aff, y_mod, gamma, beta, y, stats, M, C, aff ? T : 1, s);
+    return debug_t_finish(true, s);
+}
+
+int dsg_debug_t_modulate(int32_t bwd, int32_t B, int32_t T, int32_t C, const float *x, const float *aff, const float *dy, float *out,
+                         float *d_aff, void *stream) {
+    if (B < 1 || T < 1 || C < 1 || !x || !aff || !out || (bwd && (!dy || !d_aff))) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    t_modulate(x, aff, dy, out, d_aff, B, T, C, bwd != 0, s);
+    return debug_t_finish(true, s);
+}
+
+int dsg_debug_t_colsum(const float *X, int32_t ld, float *out, int32_t M, int32_t N, void *stream) {
+    if (!X || !out || M < 1 || N < 1 || ld < N) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    t_colsum(X, ld, out, M, N, s);
+    return debug_t_finish(true, s);
+}
+
+int dsg_debug_t_grouped(int32_t kind, int32_t n, const dsg_t_prob *probs, float *out, int32_t n_out, void *stream) {
+    if (n < 1 || n > T_GROUP_MAX || !probs || kind < DSG_TGROUP_NT || kind > DSG_TGROUP_TT) return DSG_ERR_INVALID;
+    TGemmGroup g;
+    g.n = n;
+    for (int z = 0; z < n; z++) {
+        const dsg_t_prob &p = probs[z];
+        if (p.M < 1 || p.N < 1 || !p.C) return DSG_ERR_INVALID;
+        if (kind != DSG_TGROUP_SUM && !p.A) return DSG_ERR_INVALID;
+        if (kind != DSG_TGROUP_SUM && kind != DSG_TGROUP_COLSUM && (!p.B || p.K < 1)) return DSG_ERR_INVALID;
+        if (kind == DSG_TGROUP_NN_SUM && (p.M != probs[0].M || p.N != probs[0].N)) return DSG_ERR_INVALID;
+        g.p[z] = TGemmProb{p.A, p.B, p.bias, p.C, p.lda, p.ldb, p.ldc, p.M, p.N, p.K};
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (kind == DSG_TGROUP_SUM) {
+        if (!out || n_out < 1) return DSG_ERR_INVALID;
+        t_sum_grouped(g, out, n_out, s);
+    } else if (kind == DSG_TGROUP_COLSUM) t_colsum_grouped(g, s);
+    else t_gemm_grouped(kind == DSG_TGROUP_TN || kind == DSG_TGROUP_TT, kind == DSG_TGROUP_NT || kind == DSG_TGROUP_TT, kind == DSG_TGROUP_NN_SUM, g, s);
+    return debug_t_finish(true, s);
+}
+
 static float time_launches(hipStream_t s, int iters, const std::function<void()> &launch) {
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1.f;

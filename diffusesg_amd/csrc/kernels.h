@@ -354,8 +354,11 @@ bool train_block_backward(const TrainBlockArgs &a, hipStream_t s);   // backward
 // building blocks of the whole-network training step (same file): C (+)= op(A) op(B) (+ bias), column sums, elementwise / row ops
 // a_colsum (weight-gradient products, ta && !tb): also out[m] = sum_k A[k][m], the bias gradient that goes with dW = dy^T x
 void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K,
-            bool accumulate, hipStream_t s, float *a_colsum = nullptr, const float *res = nullptr, int act = ACT_NONE, float *c2 = nullptr);
+            bool accumulate, hipStream_t s, float *a_colsum = nullptr, const float *res = nullptr, int act = ACT_NONE, float *c2 = nullptr,
+            int *route = nullptr, int force_plain = -1);
 // res: C = res + product (same pitch as C); act = ACT_GELU_KEEP: c2 = product + bias, C = GELU(c2); act = ACT_DGELU: C = product * GELU'(res)
+// route (test hook, host): route[0] = the path taken -- 1 the sampling GEMM (launch_gemm), 2 gemm_tn_f32_kernel + reduce, 3 the plain
+// kernel, 4 the plain kernel with split-K, 0 refused --, route[1] = its slice count S; force_plain >= 0 replaces DSG_TRAIN_PLAIN_GEMM
 // scratch of the training kernels is kept per stream (train_kernels.hip); a failed allocation is reported here, once
 bool t_scratch_failed(hipStream_t s, bool clear);
 void t_scratch_release();
@@ -368,6 +371,11 @@ void t_ln_fwd(const float *x, const float *gam, const float *bet, float *y, floa
 void t_ln_bwd(const float *x, const float *gam, const float *stats, const float *dy, const float *dx_in, float *dx_out, float *d_gamma, float *d_beta,
               int M, int C, hipStream_t s);
 void t_modulate(const float *x, const float *aff, const float *dy, float *out, float *d_aff, int B, int T, int C, bool bwd, hipStream_t s);
+// test hooks (dsg_debug_t_attn / dsg_debug_t_ln): the file-local launchers; force_plain replaces DSG_TRAIN_PLAIN_ATTN
+bool t_attn_debug(bool bwd, const float *qkv, const float *table, float *out, const float *d_out, float *d_qkv, float *d_table, int B, int res,
+                  int ws, int shift, int heads, bool force_plain, hipStream_t s);
+void t_ln_fwd_mod(const float *x, const float *aff, float *y_mod, const float *gam, const float *bet, float *y, float *stats, int M, int C, int T,
+                  hipStream_t s);
 void t_regroup(const float *src, float *dst, int B, int res, int C, bool gather, hipStream_t s);
 void t_concat(const float *x, const float *skip, float *cat, size_t M, int C, hipStream_t s);
 void t_split(const float *dcat, float *dx, float *dskip_acc, size_t M, int C, hipStream_t s);

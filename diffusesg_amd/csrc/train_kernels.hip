@@ -322,7 +322,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f32_kernel(const float *__rest
 }
 
 void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K,
-            bool accumulate, hipStream_t s, float *a_colsum, const float *res, int act, float *c2) {
+            bool accumulate, hipStream_t s, float *a_colsum, const float *res, int act, float *c2, int *route, int force_plain) {
+    if (route) { route[0] = 0; route[1] = 0; }
     // res (activation-side products only): C = res + product, res a tensor of C's shape and pitch -- the MFMA kernel reads it in its
     // epilogue; the fallbacks copy it into C first and accumulate
     if (act == ACT_NONE && res && res == C) { res = nullptr; accumulate = true; }
@@ -341,7 +342,8 @@ void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, 
     // The activation-side products y = x W^T and dx = dy W have the sampling path's GEMM form (A [M,K] row-major, second operand
     // [N,K]): large ones go to gemm4_f32_kernel (dx after transposing the weight into a scratch tile).  The weight-gradient
     // products (ta: K = tokens) and everything small or oddly shaped stay on the plain kernel below.
-    static const bool use_mfma = getenv("DSG_TRAIN_PLAIN_GEMM") == nullptr;
+    static const bool env_mfma = getenv("DSG_TRAIN_PLAIN_GEMM") == nullptr;
+    const bool use_mfma = force_plain < 0 ? env_mfma : force_plain == 0;
     // (K not a multiple of the 32-deep chunk -- PatchEmbed's 60 input channels: the weight goes into the scratch tile zero-padded to Kp
     // columns; the activation rows keep their pitch, the chunk's overhang reads the next row's first values (finite) against those zeros,
     // and past the last row the buffer descriptor returns zeros)
@@ -374,6 +376,7 @@ void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, 
             if (act == ACT_GELU_KEEP) { g.C2 = c2; g.ldc2 = ldc; }
             if (!launch_gemm(g, s)) ts.failed = true;   // reported by the entry point as DSG_ERR_HIP / INVALID (t_scratch_failed)
             act_after.done = true;
+            if (route) { route[0] = 1; route[1] = 1; }
             return;
         }
     }
@@ -402,6 +405,7 @@ void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, 
             else hipLaunchKernelGGL((gemm_tn_f32_kernel<false>), grid, dim3(256), 0, s, A, lda, B, ldb, buf, M, N, K, kslice, tiles_m, tiles_n, nullptr);
             t_splitk_reduce(buf, C, ldc, M, N, S, accumulate, buf + nC, a_colsum, s);
             if (a_colsum) colsum_done = true;
+            if (route) { route[0] = 2; route[1] = S; }
             return;
         }
     }
@@ -426,6 +430,7 @@ void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, 
     else if (ta && !tb) hipLaunchKernelGGL((t_gemm_kernel<true, false>), grid, block, 0, s, A, lda, B, ldb, bias, Cout, ldo, M, N, K, acc1, kslice);
     else hipLaunchKernelGGL((t_gemm_kernel<true, true>), grid, block, 0, s, A, lda, B, ldb, bias, Cout, ldo, M, N, K, acc1, kslice);
     if (S > 1) t_splitk_reduce(ts.sk, C, ldc, M, N, S, accumulate, nullptr, nullptr, s);
+    if (route) { route[0] = S > 1 ? 4 : 3; route[1] = S; }
 }
 
 void t_gemm_grouped(bool ta, bool tb, bool sum, const TGemmGroup &g, hipStream_t s) {
@@ -1031,10 +1036,11 @@ static bool t_attn_mfma_launch(bool bwd, const float *qkv, const float *table, f
 }
 
 static bool t_attn_launch(bool bwd, const float *qkv, const float *table, float *out, const float *d_out, float *d_qkv, float *d_table,
-                          int B, TAttnGeom g, hipStream_t s) {
+                          int B, TAttnGeom g, hipStream_t s, int force_plain = -1) {
     const int Wt = g.ws * g.ws, HD = g.C / g.heads, LD = HD + 1;
     if (Wt > 128 || HD % 4 != 0) return false;
-    static const bool plain = getenv("DSG_TRAIN_PLAIN_ATTN") != nullptr;   // dev knob: the scalar kernel below
+    static const bool env_plain = getenv("DSG_TRAIN_PLAIN_ATTN") != nullptr;   // dev knob: the scalar kernel below
+    const bool plain = force_plain < 0 ? env_plain : force_plain != 0;
     if (!plain && HD == 32 && g.C % 4 == 0) {
         if (Wt <= 32) return t_attn_mfma_launch<1>(bwd, qkv, table, out, d_out, d_qkv, d_table, B, g, s);
         if (Wt <= 64) return t_attn_mfma_launch<2>(bwd, qkv, table, out, d_out, d_qkv, d_table, B, g, s);
@@ -1051,6 +1057,11 @@ static bool t_attn_launch(bool bwd, const float *qkv, const float *table, float 
         hipLaunchKernelGGL((t_attn_kernel<false>), grid, block, lds, s, qkv, table, out, d_out, d_qkv, d_table, g);
     }
     return true;
+}
+
+bool t_attn_debug(bool bwd, const float *qkv, const float *table, float *out, const float *d_out, float *d_qkv, float *d_table, int B, int res,
+                  int ws, int shift, int heads, bool force_plain, hipStream_t s) {
+    return t_attn_launch(bwd, qkv, table, out, d_out, d_qkv, d_table, B, TAttnGeom{res, ws, shift, heads, 32 * heads}, s, force_plain ? 1 : 0);
 }
 
 // ---- small kernels of the rest of the network (training form) ----
@@ -1183,6 +1194,10 @@ void t_gelu(const float *x, const float *dy, float *out, size_t n, bool bwd, hip
 void t_add(float *a, const float *b, size_t n, hipStream_t s) { hipLaunchKernelGGL(t_add_kernel, dim3(t_blocks(n)), dim3(256), 0, s, a, b, n); }
 void t_ln_fwd(const float *x, const float *gam, const float *bet, float *y, float *stats, int M, int C, hipStream_t s) {
     t_ln_fwd_launch(x, nullptr, nullptr, gam, bet, y, stats, M, C, 1, s);
+}
+void t_ln_fwd_mod(const float *x, const float *aff, float *y_mod, const float *gam, const float *bet, float *y, float *stats, int M, int C, int T,
+                  hipStream_t s) {
+    t_ln_fwd_launch(x, aff, y_mod, gam, bet, y, stats, M, C, T, s);
 }
 void t_ln_bwd(const float *x, const float *gam, const float *stats, const float *dy, const float *dx_in, float *dx_out, float *d_gamma, float *d_beta,
               int M, int C, hipStream_t s) {

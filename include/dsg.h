@@ -483,6 +483,45 @@ int dsg_debug_fused_attn96_f32(int32_t B, int32_t res, int32_t ws, int32_t shift
                                const float *Wpp, const float *bproj, int32_t premod, const int32_t *win_list, const int32_t *win_cnt,
                                void *stream);
 
+/* The training kernels on their own (test hooks, csrc/train_kernels.hip; no handle, device pointers, synchronise `stream`;
+ * DSG_ERR_INVALID where the launcher refuses the form, DSG_ERR_HIP on a HIP error, never an abort).  tests/test_train_kernels.py
+ * compares every output element with float64.
+ * dsg_debug_t_gemm: the training step's product launcher, C[M,N] (+)= op(A) op(B) (+ bias[n]); op(A)(m,k) = ta ? A[k lda + m] :
+ *   A[m lda + k], op(B)(k,n) = tb ? B[n ldb + k] : B[k ldb + n].  a_colsum [M] (ta && !tb only): also sum_k A[k][m].  res: C = res +
+ *   product (res has C's pitch).  act 0 none, 3 c2 = product + bias and C = GELU(c2), 4 C = product * GELU'(res).  force_plain != 0:
+ *   the plain kernel only (what DSG_TRAIN_PLAIN_GEMM selects).  route_out (HOST, two values or NULL): [0] the path taken -- 1 the
+ *   sampling path's MFMA GEMM, 2 the split-K weight-gradient MFMA kernel + reduction, 3 the plain kernel, 4 the plain kernel with
+ *   split-K, 0 refused; [1] the number of K slices. */
+int dsg_debug_t_gemm(int32_t ta, int32_t tb, const float *A, int32_t lda, const float *B, int32_t ldb, const float *bias, float *C, int32_t ldc,
+                     int32_t M, int32_t N, int32_t K, int32_t accumulate, float *a_colsum, const float *res, int32_t act, float *c2,
+                     int32_t force_plain, int32_t *route_out, void *stream);
+/* window attention of the training block, forward (bwd == 0: qkv [B res^2, 3C], C = 32 heads, table [(2 ws - 1)^2, heads] -> out
+ * [B res^2, C]) or backward (d_out [B res^2, C] -> d_qkv [B res^2, 3C] written, d_table ADDED to: the caller zeroes it).
+ * S = q k^T / sqrt(32) + table[index][h] (- 100 where the shifted window's regions differ).  force_plain != 0: the scalar kernel. */
+int dsg_debug_t_attn(int32_t bwd, int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const float *qkv, const float *table,
+                     float *out, const float *d_out, float *d_qkv, float *d_table, int32_t force_plain, void *stream);
+/* LayerNorm with affine on x [M, C].  Forward (bwd == 0): y, stats [M][2] = (mean, rstd); with aff [ceil(M/T), 2C] = (scale | shift)
+ * the row is modulated first, x' = silu(shift + x (1 + scale)), and written to y_mod.  Backward: stats is read; dx_out = (dx_in ? dx_in
+ * : 0) + the LayerNorm backward of dy (dx_in may alias dx_out); d_gamma / d_beta [C] may be NULL.  C % 4 == 0, C <= 1536. */
+int dsg_debug_t_ln(int32_t bwd, int32_t M, int32_t C, int32_t T, const float *x, const float *aff, float *y_mod, const float *gamma,
+                   const float *beta, float *y, float *stats, const float *dy, const float *dx_in, float *dx_out, float *d_gamma,
+                   float *d_beta, void *stream);
+/* out = silu(shift_b + x (1 + scale_b)) on x [B T, C], aff [B, 2C] = (scale | shift); backward: out = dx from dy, d_aff [B, 2C] */
+int dsg_debug_t_modulate(int32_t bwd, int32_t B, int32_t T, int32_t C, const float *x, const float *aff, const float *dy, float *out,
+                         float *d_aff, void *stream);
+/* out[n] = sum_m X[m ld + n] */
+int dsg_debug_t_colsum(const float *X, int32_t ld, float *out, int32_t M, int32_t N, void *stream);
+/* up to 32 small problems in one launch.  kind: DSG_TGROUP_NT / TN / NN: C_z = op(A_z) op(B_z) (+ bias_z); NN_SUM: ONE C = sum_z A_z B_z
+ * (shared M, N, C; bias of problem 0); SUM: out[i] = sum_z C_z[i], i < n_out; COLSUM: C_z[n] = sum_m A_z[m lda + n]; TT is not built
+ * and is refused. */
+typedef struct dsg_t_prob {
+    const float *A, *B, *bias;
+    float *C;
+    int32_t lda, ldb, ldc, M, N, K;
+} dsg_t_prob;
+enum { DSG_TGROUP_NT = 0, DSG_TGROUP_TN = 1, DSG_TGROUP_NN = 2, DSG_TGROUP_NN_SUM = 3, DSG_TGROUP_SUM = 4, DSG_TGROUP_COLSUM = 5, DSG_TGROUP_TT = 6 };
+int dsg_debug_t_grouped(int32_t kind, int32_t n, const dsg_t_prob *probs, float *out, int32_t n_out, void *stream);
+
 /* The bf16 block pipeline's kernels on their own (test hooks, csrc/kernels_bx.hip; device pointers, synchronise `stream`).
  * dsg_debug_gemm_bx: A [M,K], W [N,K] given as fp32 and rounded to bf16 inside; epilogue pieces as in the forward: bias [N], fp32
  *   residual res [M,N], act (0 | 1 GELU), mod = (scale [N] | shift [N]) of a batch-uniform modulate+SiLU, ln_out (LayerNorm of the
