@@ -4,4 +4,15 @@ The product is libdsg.so (diffusesg_amd/csrc, include/dsg.h); this package is th
 side mirroring the reference's `model/` and `runner/mcmc_sampler/` callables."""
 from .spec import ModelConfig, tiny_config, vg_config, coco_config  # noqa: F401
 
-__all__ = ["ModelConfig", "tiny_config", "vg_config", "coco_config"]
+__all__ = ["ModelConfig", "tiny_config", "vg_config", "coco_config",
+           "guided_sample", "box_region_loss", "box_overlap_loss", "box_alignment_loss"]
+
+_GUIDE = ("guided_sample", "box_region_loss", "box_overlap_loss", "box_alignment_loss")
+
+
+def __getattr__(name):
+    # loss-guided sampling (diffusesg_amd.guide) pulls in torch: resolved on first use, so that `import diffusesg_amd` stays light
+    if name in _GUIDE:
+        from . import guide
+        return getattr(guide, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

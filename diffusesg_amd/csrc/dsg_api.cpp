@@ -202,8 +202,8 @@ struct dsg_handle_s {
     std::vector<Tap> taps;
     // training form (dsg_train_*): saved-activation arena and backward scratch, owned by the handle and kept between calls
     // (hipMalloc / hipFree of ~10 GB per iteration cost more than a tenth of it); they only grow
-    float *train_arena = nullptr, *train_scr = nullptr, *train_io = nullptr, *train_mid = nullptr;
-    size_t train_arena_cap = 0, train_scr_cap = 0, train_io_cap = 0, train_mid_cap = 0;
+    float *train_arena = nullptr, *train_scr = nullptr, *train_io = nullptr, *train_mid = nullptr, *train_vjp = nullptr;
+    size_t train_arena_cap = 0, train_scr_cap = 0, train_io_cap = 0, train_mid_cap = 0, train_vjp_cap = 0;
     int *train_const = nullptr;                                   // device {0, 1}: the "self-conditioning present" switch of launch_assemble
     // dsg_train_bind_params: parameters the training form reads in place (the optimiser's own device tensors) instead of the handle's copies
     std::unordered_map<std::string, const float *> train_params;
@@ -717,6 +717,7 @@ void dsg_destroy(dsg_handle h) {
     if (h->train_scr) (void)hipFree(h->train_scr);
     if (h->train_io) (void)hipFree(h->train_io);
     if (h->train_mid) (void)hipFree(h->train_mid);
+    if (h->train_vjp) (void)hipFree(h->train_vjp);
     if (h->train_const) (void)hipFree(h->train_const);
     for (auto &kv : h->ws) {
         if (kv.second->cap_stream) (void)hipStreamDestroy(kv.second->cap_stream);
@@ -2841,6 +2842,14 @@ int dsg_debug_t_colsum(const float *X, int32_t ld, float *out, int32_t M, int32_
     return debug_t_finish(true, s);
 }
 
+int dsg_debug_t_assemble_bwd(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, int32_t self_cond, const float *d_tok, int32_t ld,
+                             const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj, const float *g_node,
+                             float *out_adj, float *out_node, void *stream) {
+    if (!d_tok || !flags || !c_skip || !c_in || !g_adj || !g_node || !out_adj || !out_node) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_t_finish(t_assemble_bwd(d_tok, ld, flags, c_skip, c_in, g_adj, g_node, out_adj, out_node, B, N, c_adj, c_node, self_cond != 0, s), s);
+}
+
 int dsg_debug_t_grouped(int32_t kind, int32_t n, const dsg_t_prob *probs, float *out, int32_t n_out, void *stream) {
     if (n < 1 || n > T_GROUP_MAX || !probs || kind < DSG_TGROUP_NT || kind > DSG_TGROUP_TT) return DSG_ERR_INVALID;
     TGemmGroup g;
@@ -3249,27 +3258,32 @@ static float *train_buf(dsg_handle h, float *&buf, size_t &cap, size_t need, hip
 
 // `mid` (optional) runs between forward and backward on the same stream and fills dL/dF from the forward's outputs
 typedef std::function<int(const float *F_adj, const float *F_node, float *dF_adj, float *dF_node)> TrainMid;
+// input-gradient mode (dsg_precond_vjp): the backward carries dL/d(activation) only -- no dW / db product, no affine or noise-embedding
+// backward, no parameter gradient buffer -- and ends in d_tok [B N N, ld] = d_pe_lin W_img, the gradient of the live columns of the
+// assembled input (img [E][ld]: scratch for the weight image of t_live_cols)
+struct TrainInputGrad { float *d_tok, *img; int ld; };
 static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const float *in_node, const uint8_t *flags, const float *c_noise,
                             const float *sc_adj, const float *sc_node, const float *grad_F_adj, const float *grad_F_node, const TrainMid *mid,
                             float *out_F_adj, float *out_F_node, int32_t n_params, const char *const *names, float *const *grad_params,
-                            void *stream) {
+                            void *stream, const TrainInputGrad *ig = nullptr) {
     // the training form reads the raw weights only, so weights re-uploaded after an optimiser step need no re-packing here
     // (dsg_finalize_weights must have run once: block plans); the sampling-path entries still insist on `finalized`
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
     if (B < 1 || !in_adj || !in_node || !flags || !c_noise || !out_F_adj || !out_F_node) return fail(h, DSG_ERR_INVALID, "null argument");
     const bool bwd = grad_F_adj != nullptr || mid != nullptr;
-    if (bwd && ((!mid && !grad_F_node) || !names || !grad_params)) return fail(h, DSG_ERR_INVALID, "backward needs both output gradients and the parameter gradient buffers");
+    const bool wg = ig == nullptr;   // weight gradients wanted
+    if (bwd && ((!mid && !grad_F_node) || (wg && (!names || !grad_params)))) return fail(h, DSG_ERR_INVALID, "backward needs both output gradients and the parameter gradient buffers");
     if (h->cfg.self_condition && ((sc_adj == nullptr) != (sc_node == nullptr))) return fail(h, DSG_ERR_INVALID, "self-conditioning needs both tensors or none");
     hipStream_t s = (hipStream_t)stream;
     const int N = h->N, E = h->E, L = h->L, Ca = h->Ca, Cn = h->Cn, Cin = h->Cin, T0 = N * N;
     const size_t M0 = (size_t)B * T0;
     std::unordered_map<std::string, float *> gmap;
-    if (bwd) for (int k = 0; k < n_params; k++) if (names[k] && grad_params[k]) gmap[names[k]] = grad_params[k];
+    if (bwd && wg) for (int k = 0; k < n_params; k++) if (names[k] && grad_params[k]) gmap[names[k]] = grad_params[k];
     std::string missing;
     auto Wt = [&](const std::string &k) -> float * {
         if (!h->train_params.empty()) { auto bt = h->train_params.find(k); if (bt != h->train_params.end()) return const_cast<float *>(bt->second); }
         auto it = h->w.find(k); if (it == h->w.end()) { if (missing.empty()) missing = k; return nullptr; } return it->second.p; };
-    auto Gd = [&](const std::string &k) -> float * { if (!bwd) return nullptr; auto it = gmap.find(k); if (it == gmap.end()) { if (missing.empty()) missing = "grad:" + k; return nullptr; } return it->second; };
+    auto Gd = [&](const std::string &k) -> float * { if (!bwd || !wg) return nullptr; auto it = gmap.find(k); if (it == gmap.end()) { if (missing.empty()) missing = "grad:" + k; return nullptr; } return it->second; };
     // collect the blocks in execution order
     struct Stage { const BlockPlan *bp; TrainBlockArgs a; float *x_in, *x_out, *d_emb; };
     std::vector<Stage> enc[8], dec[8];
@@ -3372,7 +3386,7 @@ static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const 
         t_gemm(false, true, x, in, Wm, in, bias, y, out, (int)M, out, in, false, s);
     };
     auto lin_bwd = [&](const float *x, const float *Wm, const float *dy, float *dx, float *dW, float *db, size_t M, int in, int out) {
-        t_gemm(true, false, dy, out, x, in, nullptr, dW, in, out, in, (int)M, false, s, db);       // dW [out,in] = dy^T x, db = colsum(dy)
+        if (wg) t_gemm(true, false, dy, out, x, in, nullptr, dW, in, out, in, (int)M, false, s, db);   // dW [out,in] = dy^T x, db = colsum(dy)
         if (dx) t_gemm(false, false, dy, out, Wm, in, nullptr, dx, in, (int)M, in, out, false, s);   // dx = dy W
     };
     bool ok = true;
@@ -3461,7 +3475,7 @@ static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const 
         else { ok = (*mid)(out_F_adj, out_F_node, mid_buf, mid_buf + na) == DSG_OK; grad_F_adj = mid_buf; grad_F_node = mid_buf + na; }
     }
     if (bwd && ok) {
-        hipError_t e0 = grouped ? hipSuccess : hipMemsetAsync(Bf.d_emb, 0, sizeof(float) * (size_t)B * NOISE_EMB, s);
+        hipError_t e0 = (grouped || !wg) ? hipSuccess : hipMemsetAsync(Bf.d_emb, 0, sizeof(float) * (size_t)B * NOISE_EMB, s);
         for (int l = 0; l < L && e0 == hipSuccess; l++) e0 = hipMemsetAsync(Bf.d_skip[l], 0, sizeof(float) * (size_t)B * skip_res[l] * skip_res[l] * skip_C[l], s);
         ok = ok && e0 == hipSuccess;
         // heads
@@ -3480,8 +3494,10 @@ static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const 
         float *d_z2 = t_mh, *d_z1 = t_m3c, *d_fy = t_w;
         lin_bwd(Bf.z2, Wt("read_out.2.weight"), d_rep, d_z2, Gd("read_out.2.weight"), Gd("read_out.2.bias"), M0, E, E);
         lin_bwd(Bf.z1, Wt("read_out.1.weight"), d_z2, d_z1, Gd("read_out.1.weight"), Gd("read_out.1.bias"), M0, E, E);
-        t_gemm(true, false, Bf.fy, E, d_z1, E, nullptr, Gd("read_out.0.weight"), E, E, E, (int)M0, false, s);        // dW [in,out] = y^T dz
-        t_colsum(d_z1, E, Gd("read_out.0.bias"), (int)M0, E, s);
+        if (wg) {
+            t_gemm(true, false, Bf.fy, E, d_z1, E, nullptr, Gd("read_out.0.weight"), E, E, E, (int)M0, false, s);    // dW [in,out] = y^T dz
+            t_colsum(d_z1, E, Gd("read_out.0.bias"), (int)M0, E, s);
+        }
         t_gemm(false, true, d_z1, E, Wt("read_out.0.weight"), E, nullptr, d_fy, E, (int)M0, E, E, false, s);        // dy = dz W^T
         float *dx = d_x;   // running gradient wrt the current activation x (size up to M0*E*2)
         t_ln_bwd(xL, Wt("norm.weight"), Bf.fstats, d_fy, nullptr, dx, Gd("norm.weight"), Gd("norm.bias"), (int)M0, E, s);
@@ -3494,9 +3510,10 @@ static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const 
                 const size_t M = (size_t)B * a.res * a.res, Cc = a.C, H = a.hidden;
                 a.grad_out = dcur; a.grad_in = dnext; a.grad_emb = st.d_emb;
                 a.d_x1 = t_w; a.t_mc = t_mc; a.t_mc2 = t_mc2; a.t_m3c = t_m3c; a.t_mh = t_mh;
+                a.no_wgrad = !wg;
                 (void)M; (void)Cc; (void)H;
                 ok = ok && train_block_backward(a, s);
-                if (!a.aff_grouped) t_add(Bf.d_emb, st.d_emb, (size_t)B * NOISE_EMB, s);
+                if (!a.aff_grouped && wg) t_add(Bf.d_emb, st.d_emb, (size_t)B * NOISE_EMB, s);
                 std::swap(dcur, dnext);
             }
         };
@@ -3535,10 +3552,12 @@ static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const 
             }
             run_blocks_bwd(enc[l]);
         }
-        // PatchEmbed: modulate <- LN <- 1x1 conv (the inputs are leaves)
+        // PatchEmbed: modulate <- LN <- 1x1 conv (the inputs are leaves of the training entries; dsg_precond_vjp goes on to them)
         float *d_pe_ln = dnext, *d_pe_lin = t_mh;
         t_modulate(Bf.pe_ln, Bf.pe_aff, dcur, d_pe_ln, Bf.pe_daff, B, T0, E, true, s);
-        if (grouped) {
+        if (!wg) {
+            // (sigma is not differentiated: the affine linears' own backward feeds parameter gradients and d_emb only)
+        } else if (grouped) {
             // the affine linears' own backward, all at once: dWa_z = d_aff_z^T emb, d_ba_z = colsum(d_aff_z), d_emb = sum_z d_aff_z Wa_z
             TGemmGroup gw, gb, ge;
             // (d_emb: every product into its own [B, 512] buffer -- 16 x 2 tiles per product fill the chip, one shared output would
@@ -3561,13 +3580,20 @@ static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const 
         }
         t_ln_bwd(Bf.pe_lin, Wt("patch_embed.norm.weight"), Bf.pe_stats, d_pe_ln, nullptr, d_pe_lin, Gd("patch_embed.norm.weight"), Gd("patch_embed.norm.bias"),
                  (int)M0, E, s);
-        lin_bwd(Bf.tok, Wt("patch_embed.proj.weight"), d_pe_lin, nullptr, Gd("patch_embed.proj.weight"), Gd("patch_embed.proj.bias"), M0, Cin, E);
-        // noise embedding: emb = silu(map1(silu(map0(pe))))
-        float *d_m1 = t_mc, *d_s0 = t_mc2;
-        t_silu(Bf.m1, Bf.d_emb, d_m1, (size_t)B * NOISE_EMB, true, s);
-        lin_bwd(Bf.s0, Wt("map_layer1.weight"), d_m1, d_s0, Gd("map_layer1.weight"), Gd("map_layer1.bias"), B, NOISE_EMB, NOISE_EMB);
-        t_silu(Bf.m0, d_s0, d_s0, (size_t)B * NOISE_EMB, true, s);
-        lin_bwd(Bf.pe, Wt("map_layer0.weight"), d_s0, nullptr, Gd("map_layer0.weight"), Gd("map_layer0.bias"), B, E, NOISE_EMB);
+        if (!wg) {
+            // d_tok = d_pe_lin W_img: only the columns of the current adjacency / node values, the weight image zero-padded to x32 columns
+            // (sigma is not differentiated: no noise-embedding backward)
+            t_live_cols(Wt("patch_embed.proj.weight"), Cin, ig->img, E, Ca, Cn, h->cfg.self_condition != 0, s);
+            t_gemm(false, false, d_pe_lin, E, ig->img, ig->ld, nullptr, ig->d_tok, ig->ld, (int)M0, ig->ld, E, false, s);
+        } else {
+            lin_bwd(Bf.tok, Wt("patch_embed.proj.weight"), d_pe_lin, nullptr, Gd("patch_embed.proj.weight"), Gd("patch_embed.proj.bias"), M0, Cin, E);
+            // noise embedding: emb = silu(map1(silu(map0(pe))))
+            float *d_m1 = t_mc, *d_s0 = t_mc2;
+            t_silu(Bf.m1, Bf.d_emb, d_m1, (size_t)B * NOISE_EMB, true, s);
+            lin_bwd(Bf.s0, Wt("map_layer1.weight"), d_m1, d_s0, Gd("map_layer1.weight"), Gd("map_layer1.bias"), B, NOISE_EMB, NOISE_EMB);
+            t_silu(Bf.m0, d_s0, d_s0, (size_t)B * NOISE_EMB, true, s);
+            lin_bwd(Bf.pe, Wt("map_layer0.weight"), d_s0, nullptr, Gd("map_layer0.weight"), Gd("map_layer0.bias"), B, E, NOISE_EMB);
+        }
     }
     // everything is queued on the caller's stream and every buffer involved outlives the call (caller's or the handle's): no
     // synchronisation here -- the host runs ahead into the optimiser step's launches
@@ -3635,6 +3661,51 @@ int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const f
     if (rc != DSG_OK) return rc;
     launch_precond_out(CStatePtrs{noisy_adj, noisy_node}, CStatePtrs{F_a, F_n}, sigmas, flags, StatePtrs{out_sc_adj, out_sc_node},
                        StatePtrs{nullptr, nullptr}, d, s);
+    HIP_TRY(h, hipGetLastError());
+    return DSG_OK;
+}
+
+int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node, const uint8_t *flags, const float *sigmas,
+                    const float *sc_adj, const float *sc_node, const float *grad_D_adj, const float *grad_D_node, dsg_grad_fn fn, void *user,
+                    float *out_D_adj, float *out_D_node, float *out_grad_adj, float *out_grad_node, void *stream) {
+    if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (B < 1 || !adj || !node || !flags || !sigmas || !out_D_adj || !out_D_node || !out_grad_adj || !out_grad_node)
+        return fail(h, DSG_ERR_INVALID, "null argument");
+    if ((grad_D_adj == nullptr) != (grad_D_node == nullptr)) return fail(h, DSG_ERR_INVALID, "grad_D_adj and grad_D_node go together");
+    if ((fn != nullptr) == (grad_D_adj != nullptr)) return fail(h, DSG_ERR_INVALID, "give either the callback or grad_D_adj / grad_D_node, not %s", fn ? "both" : "neither");
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d = dims_of(h, B);
+    const int N = h->N, Ca = h->Ca, Cn = h->Cn, E = h->E;
+    const size_t na = (size_t)B * Ca * N * N, nn = (size_t)B * N * Cn, M0 = (size_t)B * N * N;
+    // refused before anything is enqueued: what the last kernel (t_assemble_bwd) cannot take
+    if (!t_assemble_bwd_ok(Cn) || (size_t)B * N > 0x7fffffffu)
+        return fail(h, DSG_ERR_INVALID, "input gradients are not built for C_node %d (partial sums beyond LDS) or B * N = %zu", Cn, (size_t)B * N);
+    const int Np = t_live_cols_width(Ca, Cn);
+    // in_adj | in_node | c_noise | F_adj | F_node: the training entries' handle-owned buffer (same layout); d_tok | W_img | coef: its own
+    float *buf = train_buf(h, h->train_io, h->train_io_cap, 3 * na + 3 * nn + (size_t)B + 64, s);
+    float *vb = train_buf(h, h->train_vjp, h->train_vjp_cap, M0 * Np + (size_t)E * Np + 2 * (size_t)B + 64, s);
+    if (!buf || !vb) return fail(h, DSG_ERR_HIP, "out of memory");
+    float *in_a = buf, *in_n = in_a + na, *cn = in_n + nn, *F_a = cn + ((B + 63) / 64) * 64, *F_n = F_a + na;
+    TrainInputGrad ig{vb, vb + M0 * Np, Np};
+    float *coef = ig.img + (size_t)E * Np;
+    launch_precond_in(CStatePtrs{adj, node}, sigmas, StatePtrs{in_a, in_n}, cn, d, s);
+    int cb_rc = 0;
+    const float *g_a = grad_D_adj, *g_n = grad_D_node;
+    const TrainMid mid = [&](const float *Fa, const float *Fn, float *dFa, float *dFn) -> int {
+        launch_precond_out(CStatePtrs{adj, node}, CStatePtrs{Fa, Fn}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, StatePtrs{nullptr, nullptr}, d, s);
+        if (fn) {   // the callee enqueues g = dL/dD into the gradient outputs, which the last kernel below turns into the result in place
+            cb_rc = fn(user, out_D_adj, out_D_node, out_grad_adj, out_grad_node);
+            if (cb_rc != 0) return DSG_ERR_INVALID;
+            g_a = out_grad_adj; g_n = out_grad_node;
+        }
+        t_precond_bwd(g_a, g_n, sigmas, flags, dFa, dFn, coef, B, N, Ca, Cn, s);
+        return hipGetLastError() == hipSuccess ? DSG_OK : DSG_ERR_HIP;
+    };
+    const int rc = train_grads_core(h, B, in_a, in_n, flags, cn, sc_adj, sc_node, nullptr, nullptr, &mid, F_a, F_n, 0, nullptr, nullptr, stream, &ig);
+    if (cb_rc != 0) return fail(h, DSG_ERR_INVALID, "the gradient callback returned %d: no backward kernel was launched", cb_rc);
+    if (rc != DSG_OK) return rc;
+    if (!t_assemble_bwd(ig.d_tok, Np, flags, coef, coef + B, g_a, g_n, out_grad_adj, out_grad_node, B, N, Ca, Cn, false, s))
+        return fail(h, DSG_ERR_INVALID, "the assemble backward refused B %d, N %d, C_adj %d, C_node %d, pitch %d", B, N, Ca, Cn, Np);
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
 }

@@ -341,6 +341,9 @@ struct TrainBlockArgs {
     // whole-network step: a.aff is already filled (one grouped launch for all blocks) and the affine linear's own backward
     // (dW, db, d_emb from a.d_aff) is left to grouped launches at the end
     bool aff_grouped = false;
+    // backward without the weight-gradient products (dW, db, d_gamma, d_beta, d_table, and the affine linear's own backward): only
+    // grad_in is produced, G is not touched (input gradients, dsg_precond_vjp)
+    bool no_wgrad = false;
 };
 // a group of small products in one launch (t_gemm_grouped / t_colsum_grouped): C = op(A) op(B) (+ bias)
 struct TGemmProb { const float *A, *B, *bias; float *C; int lda, ldb, ldc, M, N, K; };
@@ -382,6 +385,18 @@ void t_split(const float *dcat, float *dx, float *dskip_acc, size_t M, int C, hi
 void t_adj_out(const float *oa, const uint8_t *flags, float *F, const float *dF, float *d_oa, int B, int N, int Ca, bool bwd, hipStream_t s);
 void t_pool_bwd(const float *d_pool, const uint8_t *flags, float *d_rep_acc, int B, int N, int E, hipStream_t s);
 void t_rowmask(const float *x, const uint8_t *flags, float *y, size_t M, int C, hipStream_t s);
+// input gradients of the preconditioned denoiser (dsg_precond_vjp; train_kernels.hip)
+// dF = c_out_b mask(g) (the way in); coef [2B] = (c_skip | c_in), formulas as launch_precond_out / launch_precond_in
+void t_precond_bwd(const float *g_adj, const float *g_node, const float *sigmas, const uint8_t *flags, float *dF_adj, float *dF_node,
+                   float *coef, int B, int N, int Ca, int Cn, hipStream_t s);
+// img [E][t_live_cols_width] = the columns of PatchEmbed's W [E, Cin] that see the current adjacency / node values, zero-padded to x32
+int t_live_cols_width(int Ca, int Cn);
+void t_live_cols(const float *W, int Cin, float *img, int E, int Ca, int Cn, bool self_cond, hipStream_t s);
+// backward of launch_assemble fused with the preconditioning chain (formulas at the kernel); false: shape refused (B, N, Ca < 1, a pitch
+// below the channel count, or a C_node whose partial sums do not fit LDS: t_assemble_bwd_ok)
+bool t_assemble_bwd_ok(int Cn);
+bool t_assemble_bwd(const float *d_tok, int ld, const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj,
+                    const float *g_node, float *out_adj, float *out_node, int B, int N, int Ca, int Cn, bool self_cond, hipStream_t s);
 bool t_adam_step(int n, float *const *params, float *const *grads, float *const *m, float *const *v, const int64_t *numel, int step, float lr,
                  float b1, float b2, float eps, float wd, float max_norm, float *host_total_norm, hipStream_t s);
 bool t_ema_update(int n, float *const *ema, const float *const *params, const int64_t *numel, float decay, hipStream_t s);

@@ -814,7 +814,8 @@ __global__ void t_attn_kernel(const float *qkv, const float *table, float *out, 
             atomicAdd(&dtab[idx], ds);   // LDS atomics; one global atomic per table entry and block below (4096 -> 225 per 8x8 window)
         }
     __syncthreads();
-    for (int t = threadIdx.x; t < ntab; t += blockDim.x) atomicAdd(d_table + (size_t)t * g.heads + h, dtab[t]);
+    if (d_table)   // (null: the input-gradient mode, which needs no parameter gradient)
+        for (int t = threadIdx.x; t < ntab; t += blockDim.x) atomicAdd(d_table + (size_t)t * g.heads + h, dtab[t]);
     // ---- dQ[i] = scale sum_j dS[i][j] k[j];  dK[i] = scale sum_q dS[q][i] q[q] ----
     if (act)
         for (int d = d0; d < d0 + DG; d++) {
@@ -979,7 +980,8 @@ __global__ __launch_bounds__(64 * KT) void t_attn_mfma_kernel(const float *__res
         if (pi_ok) store_T(dQ, scale, d_qkv + ((size_t)b * T + toks[pi]) * 3 * C + h * 32);
     }
     __syncthreads();   // (m, 1/l, t) of every query are in LDS; dtab is complete
-    for (int t = tid; t < ntab; t += NT) atomicAdd(d_table + (size_t)t * g.heads + h, dtab[t]);
+    if (d_table)
+        for (int t = tid; t < ntab; t += NT) atomicAdd(d_table + (size_t)t * g.heads + h, dtab[t]);
     // ---------------- phase 2: lane = key pi ----------------
     f32x16 dV, dK;
 #pragma unroll
@@ -1158,28 +1160,155 @@ bool train_block_backward(const TrainBlockArgs &a, hipStream_t s) {
     const int B = a.B, T = a.res * a.res, C = a.C, M = B * T, H = a.hidden;
     TAttnGeom g{a.res, a.ws, a.shift, a.heads, C};
     const float *dY = a.grad_out;
+    const bool wg = !a.no_wgrad;   // false: only the activation-side chain (input gradients); a.G is not touched
     // MLP: x_out = x1 + hid W2^T + b2
-    t_gemm(true, false, dY, C, a.hid, H, nullptr, a.G.fc2_w, H, C, H, M, false, s, a.G.fc2_b);  // dW2 [C,H] = dY^T hid, db2 = colsum(dY)
+    if (wg) t_gemm(true, false, dY, C, a.hid, H, nullptr, a.G.fc2_w, H, C, H, M, false, s, a.G.fc2_b);  // dW2 [C,H] = dY^T hid, db2 = colsum(dY)
     t_gemm(false, false, dY, C, a.W.fc2_w, H, nullptr, a.t_mh, H, M, H, C, false, s, nullptr, a.pre, ACT_DGELU);   // d_pre = (dY W2) GELU'(pre)
-    t_gemm(true, false, a.t_mh, H, a.xn2, C, nullptr, a.G.fc1_w, C, H, C, M, false, s, a.G.fc1_b);   // dW1 [H,C] = d_pre^T xn2, db1
+    if (wg) t_gemm(true, false, a.t_mh, H, a.xn2, C, nullptr, a.G.fc1_w, C, H, C, M, false, s, a.G.fc1_b);   // dW1 [H,C] = d_pre^T xn2, db1
     t_gemm(false, false, a.t_mh, H, a.W.fc1_w, C, nullptr, a.t_mc, C, M, C, H, false, s);       // d_xn2 = d_pre W1
-    t_ln_bwd(a.x1, a.W.n2_w, a.stats2, a.t_mc, dY, a.d_x1, a.G.n2_w, a.G.n2_b, M, C, s);       // d_x1 = dY (residual branch) + LN2 backward; d_gamma2, d_beta2
+    t_ln_bwd(a.x1, a.W.n2_w, a.stats2, a.t_mc, dY, a.d_x1, wg ? a.G.n2_w : nullptr, wg ? a.G.n2_b : nullptr, M, C, s);   // d_x1 = dY (residual branch) + LN2 backward; d_gamma2, d_beta2
     // attention half: x1 = x_mod + att Wp^T + bp
-    t_gemm(true, false, a.d_x1, C, a.att, C, nullptr, a.G.proj_w, C, C, C, M, false, s, a.G.proj_b);
+    if (wg) t_gemm(true, false, a.d_x1, C, a.att, C, nullptr, a.G.proj_w, C, C, C, M, false, s, a.G.proj_b);
     t_gemm(false, false, a.d_x1, C, a.W.proj_w, C, nullptr, a.t_mc, C, M, C, C, false, s);      // d_att
-    if (hipMemsetAsync(a.G.rpb, 0, sizeof(float) * (size_t)(2 * a.ws - 1) * (2 * a.ws - 1) * a.heads, s) != hipSuccess) return false;
-    if (!t_attn_launch(true, a.qkv, a.W.rpb, nullptr, a.t_mc, a.t_m3c, a.G.rpb, B, g, s)) return false;   // d_qkv, d_table
-    t_gemm(true, false, a.t_m3c, 3 * C, a.xn1, C, nullptr, a.G.qkv_w, C, 3 * C, C, M, false, s, a.G.qkv_b);
+    if (wg && hipMemsetAsync(a.G.rpb, 0, sizeof(float) * (size_t)(2 * a.ws - 1) * (2 * a.ws - 1) * a.heads, s) != hipSuccess) return false;
+    if (!t_attn_launch(true, a.qkv, a.W.rpb, nullptr, a.t_mc, a.t_m3c, wg ? a.G.rpb : nullptr, B, g, s)) return false;   // d_qkv, d_table
+    if (wg) t_gemm(true, false, a.t_m3c, 3 * C, a.xn1, C, nullptr, a.G.qkv_w, C, 3 * C, C, M, false, s, a.G.qkv_b);
     t_gemm(false, false, a.t_m3c, 3 * C, a.W.qkv_w, C, nullptr, a.t_mc, C, M, C, 3 * C, false, s);   // d_xn1
     // d_xmod = d_x1 (shortcut) + LN1 backward
-    t_ln_bwd(a.x_mod, a.W.n1_w, a.stats1, a.t_mc, a.d_x1, a.d_x1, a.G.n1_w, a.G.n1_b, M, C, s);
+    t_ln_bwd(a.x_mod, a.W.n1_w, a.stats1, a.t_mc, a.d_x1, a.d_x1, wg ? a.G.n1_w : nullptr, wg ? a.G.n1_b : nullptr, M, C, s);
     // modulate: x_mod = silu(shift + x (1 + scale)); params = emb Wa^T + ba
     t_modulate(a.x_in, a.aff, a.d_x1, a.grad_in, a.d_aff, B, T, C, true, s);
-    if (a.aff_grouped) return hipGetLastError() == hipSuccess;   // dWa, d_ba and d_emb of all blocks: grouped launches of the whole-network step
+    if (a.aff_grouped || !wg) return hipGetLastError() == hipSuccess;   // dWa, d_ba and d_emb of all blocks: grouped launches of the whole-network step
     t_gemm(true, false, a.d_aff, 2 * C, a.emb, NOISE_EMB, nullptr, a.G.aff_w, NOISE_EMB, 2 * C, NOISE_EMB, B, false, s);   // dWa = d_aff^T emb
     t_colsum(a.d_aff, 2 * C, a.G.aff_b, B, 2 * C, s);
     t_gemm(false, false, a.d_aff, 2 * C, a.W.aff_w, NOISE_EMB, nullptr, a.grad_emb, NOISE_EMB, B, NOISE_EMB, 2 * C, false, s);   // d_emb
     return hipGetLastError() == hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Input gradients of the preconditioned denoiser (dsg_precond_vjp): the way in, the PatchEmbed weight image, the way out.
+// ---------------------------------------------------------------------------------------------------------------------
+// dF = c_out_b mask(g) for D = mask(c_skip x + c_out F) (precond.py:102-105), coefficient formulas as precond_out_kernel /
+// precond_in_kernel op by op; coef [2B] = (c_skip | c_in) for t_assemble_bwd
+__global__ void t_precond_bwd_kernel(const float *g_adj, const float *g_node, const float *sigmas, const uint8_t *flags, float *dF_adj,
+                                     float *dF_node, float *coef, int B, int N, int Ca, int Cn) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n_adj = (size_t)B * Ca * N * N, n_node = (size_t)B * N * Cn;
+    if (idx < (size_t)B) {
+        const float sg = sigmas[idx], s2 = __fadd_rn(__fmul_rn(sg, sg), 0.25f);
+        coef[idx] = __fdiv_rn(0.25f, s2);                                                       // c_skip, objectives/edm.py:123
+        coef[B + idx] = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(0.25f, __fmul_rn(sg, sg))));       // c_in, objectives/edm.py:125
+    }
+    if (idx >= n_adj + n_node) return;
+    int b; bool valid;
+    if (idx < n_adj) {
+        const int j = idx % N, i = (idx / N) % N;
+        b = (int)(idx / ((size_t)Ca * N * N));
+        valid = flags[(size_t)b * N + i] && flags[(size_t)b * N + j];
+    } else {
+        const size_t o = idx - n_adj;
+        b = (int)(o / ((size_t)N * Cn));
+        valid = flags[(size_t)b * N + (o / Cn) % N];
+    }
+    const float sg = sigmas[b], s2 = __fadd_rn(__fmul_rn(sg, sg), 0.25f);
+    const float c_out = __fdiv_rn(__fmul_rn(sg, 0.5f), __fsqrt_rn(s2));                          // objectives/edm.py:124
+    if (idx < n_adj) dF_adj[idx] = valid ? __fmul_rn(c_out, g_adj[idx]) : 0.f;
+    else dF_node[idx - n_adj] = valid ? __fmul_rn(c_out, g_node[idx - n_adj]) : 0.f;
+}
+void t_precond_bwd(const float *g_adj, const float *g_node, const float *sigmas, const uint8_t *flags, float *dF_adj, float *dF_node,
+                   float *coef, int B, int N, int Ca, int Cn, hipStream_t s) {
+    const size_t n = (size_t)B * Ca * N * N + (size_t)B * N * Cn;
+    hipLaunchKernelGGL(t_precond_bwd_kernel, dim3(t_blocks(n)), dim3(256), 0, s, g_adj, g_node, sigmas, flags, dF_adj, dF_node, coef, B, N, Ca, Cn);
+}
+
+// PatchEmbed's dx product needs the columns of W_proj [E, Cin] that multiply the CURRENT adjacency and node values only (the
+// self-conditioning inputs are constants): img [E][Np] = (adj | node of the row | node of the column | zeros), Np a multiple of 32, so
+// that d_tok = d_pe_lin img is a shape t_gemm's MFMA route takes (the weight is padded, never the activation)
+__global__ void t_live_cols_kernel(const float *__restrict__ W, int Cin, float *__restrict__ img, int E, int Np, int Ca, int Cn, int self_cond) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)E * Np) return;
+    const int e = (int)(i / Np), c = (int)(i % Np), nsc = self_cond ? 2 : 1, sc = self_cond ? 1 : 0;
+    int src = -1;
+    if (c < Ca) src = sc * Ca + c;
+    else if (c < Ca + Cn) src = nsc * Ca + sc * Cn + (c - Ca);
+    else if (c < Ca + 2 * Cn) src = nsc * Ca + nsc * Cn + sc * Cn + (c - Ca - Cn);
+    img[i] = src >= 0 ? W[(size_t)e * Cin + src] : 0.f;
+}
+int t_live_cols_width(int Ca, int Cn) { return (Ca + 2 * Cn + 31) / 32 * 32; }
+void t_live_cols(const float *W, int Cin, float *img, int E, int Ca, int Cn, bool self_cond, hipStream_t s) {
+    const int Np = t_live_cols_width(Ca, Cn);
+    hipLaunchKernelGGL(t_live_cols_kernel, dim3(t_blocks((size_t)E * Np)), dim3(256), 0, s, W, Cin, img, E, Np, Ca, Cn, (int)self_cond);
+}
+
+// The backward of assemble_kernel (kernels.hip) fused with the preconditioning chain.  d_tok [B N N, ld] token-major in assemble's
+// channel order (self_cond: the slots of the current values sit behind their self-conditioning copies); with m the flags and g = dL/dD
+//   out_adj[b,c,i,j] = c_skip_b m_i m_j g_adj[b,c,i,j] + c_in_b d_tok[(b,i,j)][adj slot c]             (the adjacency input is not masked)
+//   out_node[b,i,c]  = c_skip_b m_i g_node[b,i,c] + c_in_b m_i (sum_j m_j d_tok[(b,i,j)][row slot c] + sum_j m_j d_tok[(b,j,i)][col slot c])
+// One block per (b, i).  Adjacency: the N tokens of the row are contiguous in d_tok; 32 channels x 64 columns go through an LDS tile,
+// read channel-fastest (128 B per token) and written column-fastest (256 B per channel row).  Node: work item (q, r), q one of the 2 Cn
+// row / column slots, r one of SUM_G interleaved groups of j; a thread adds its j ascending, the SUM_G partials are added in order, the
+// row sum before the column sum: no atomics, one fixed order.  out_* may alias g_* (same index read, then written, by one thread).
+constexpr int ASM_TC = 32, ASM_TJ = 64, SUM_G = 8;
+__global__ __launch_bounds__(256) void t_assemble_bwd_kernel(const float *__restrict__ d_tok, int ld, const uint8_t *__restrict__ flags,
+                                                             const float *__restrict__ c_skip, const float *__restrict__ c_in,
+                                                             const float *g_adj, const float *g_node, float *out_adj, float *out_node,
+                                                             int N, int Ca, int Cn, int self_cond) {
+    extern __shared__ __attribute__((aligned(16))) float asm_lds[];
+    float *tile = asm_lds;                         // [ASM_TC][ASM_TJ + 1]
+    float *part = asm_lds + ASM_TC * (ASM_TJ + 1); // [SUM_G][2 Cn]
+    const int b = blockIdx.x / N, i = blockIdx.x % N, tid = threadIdx.x;
+    const int nsc = self_cond ? 2 : 1, sc = self_cond ? 1 : 0;
+    const int adj_off = sc * Ca, row_off = nsc * Ca + sc * Cn, col_off = nsc * Ca + nsc * Cn + sc * Cn;
+    const uint8_t *fl = flags + (size_t)b * N;
+    const bool mi = fl[i] != 0;
+    const float cs = c_skip[b], ci = c_in[b];
+    const float *row = d_tok + ((size_t)b * N + i) * N * ld;   // tokens (b, i, 0 .. N-1)
+    // ---- node sums: partials ----
+    const int nq = 2 * Cn;
+    for (int w = tid; w < nq * SUM_G; w += 256) {
+        const int q = w % nq, r = w / nq;
+        float acc = 0.f;
+        if (mi) {
+            if (q < Cn) { for (int j = r; j < N; j += SUM_G) if (fl[j]) acc += row[(size_t)j * ld + row_off + q]; }
+            else { for (int j = r; j < N; j += SUM_G) if (fl[j]) acc += d_tok[(((size_t)b * N + j) * N + i) * ld + col_off + (q - Cn)]; }
+        }
+        part[w] = acc;
+    }
+    // ---- adjacency: transpose through LDS ----
+    for (int c0 = 0; c0 < Ca; c0 += ASM_TC)
+        for (int j0 = 0; j0 < N; j0 += ASM_TJ) {
+            __syncthreads();   // the previous tile has been read (and, the first time, nothing is pending)
+            for (int k = tid; k < ASM_TC * ASM_TJ; k += 256) {
+                const int c = k % ASM_TC, j = k / ASM_TC;
+                if (c0 + c < Ca && j0 + j < N) tile[c * (ASM_TJ + 1) + j] = row[(size_t)(j0 + j) * ld + adj_off + c0 + c];
+            }
+            __syncthreads();
+            for (int k = tid; k < ASM_TC * ASM_TJ; k += 256) {
+                const int j = k % ASM_TJ, c = k / ASM_TJ;
+                if (c0 + c < Ca && j0 + j < N) {
+                    const size_t o = (((size_t)b * Ca + c0 + c) * N + i) * N + j0 + j;
+                    const float skip = (mi && fl[j0 + j]) ? cs * g_adj[o] : 0.f;
+                    out_adj[o] = skip + ci * tile[c * (ASM_TJ + 1) + j];
+                }
+            }
+        }
+    __syncthreads();   // part[] is complete
+    for (int c = tid; c < Cn; c += 256) {
+        const size_t o = ((size_t)b * N + i) * Cn + c;
+        float srow = 0.f, scol = 0.f;
+#pragma unroll
+        for (int r = 0; r < SUM_G; r++) { srow += part[r * nq + c]; scol += part[r * nq + Cn + c]; }
+        out_node[o] = mi ? cs * g_node[o] + ci * (srow + scol) : 0.f;
+    }
+}
+bool t_assemble_bwd_ok(int Cn) { return Cn >= 1 && sizeof(float) * ((size_t)ASM_TC * (ASM_TJ + 1) + (size_t)SUM_G * 2 * Cn) <= 64 * 1024; }
+bool t_assemble_bwd(const float *d_tok, int ld, const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj,
+                    const float *g_node, float *out_adj, float *out_node, int B, int N, int Ca, int Cn, bool self_cond, hipStream_t s) {
+    const size_t lds = sizeof(float) * ((size_t)ASM_TC * (ASM_TJ + 1) + (size_t)SUM_G * 2 * Cn);
+    if (B < 1 || N < 1 || Ca < 1 || !t_assemble_bwd_ok(Cn) || ld < (self_cond ? 2 : 1) * (Ca + 2 * Cn) || (size_t)B * N > 0x7fffffffu) return false;
+    hipLaunchKernelGGL(t_assemble_bwd_kernel, dim3((unsigned)(B * N)), dim3(256), lds, s, d_tok, ld, flags, c_skip, c_in, g_adj, g_node, out_adj,
+                       out_node, N, Ca, Cn, (int)self_cond);
+    return true;
 }
 
 // ---- launch wrappers used by the whole-network training step (dsg_api.cpp) ----
@@ -1212,7 +1341,7 @@ void t_ln_bwd(const float *x, const float *gam, const float *stats, const float 
     if (C % 4 != 0 || C > 1536) { ts.failed = true; return; }   // (4 x 384 is the widest LayerNorm of the networks)
     if (C <= 128) T_LNB(32, 1); else if (C <= 256) T_LNB(64, 1); else if (C <= 512) T_LNB(64, 2); else if (C <= 768) T_LNB(64, 3); else T_LNB(64, 6);
 #undef T_LNB
-    hipLaunchKernelGGL(t_ln_bwd_final_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, s, part, d_gamma, d_beta, C, blocks);
+    if (d_gamma || d_beta) hipLaunchKernelGGL(t_ln_bwd_final_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, s, part, d_gamma, d_beta, C, blocks);
 }
 void t_modulate(const float *x, const float *aff, const float *dy, float *out, float *d_aff, int B, int T, int C, bool bwd, hipStream_t s) {
     if (bwd) {

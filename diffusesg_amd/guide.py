@@ -1,0 +1,283 @@
+"""Loss-guided sampling on top of `NodeAdjPrecondHip.value_and_input_grad` (`dsg_precond_vjp`), and three ready-made box losses.
+
+`guided_sample` is an eager reverse loop for the solvers 'euler', 'heun' and 'dpmpp_2m' built from the library's own pieces: the
+schedule of `dsg_sigma_schedule`, the Philox noise streams of `device_noise`, the coin draws of the sampler and the multistep
+coefficients of `dsg_multistep_coef`.  The state algebra is torch float32 elementwise arithmetic on the device, written operation by
+operation like the loop kernels of the library, so that with scale = 0 the loop is `sampler.sample` up to the difference between the
+training-form and the sampling-form forward.
+
+Per preconditioned call the denoised estimate is shifted against the gradient of the loss,
+
+    D~ = D - w_i * t_hat^2 * mask(grad_{x_hat} L(D(x_hat, t_hat)))
+
+which is the score identity  grad log p_t(x) = (D - x) / t^2  with  -grad L  added to the score.  No trained weights ship with the
+project: what guidance does to sample quality is not validated here.
+
+The losses read boxes the way `io.decode` does: the last four node channels, * 0.5 + 0.5, (cx, cy, w, h).  They are plain torch and
+run on any device.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import lib as _lib
+from .model import NodeAdjPrecondHip
+from .sampler import check_graph_seeds
+
+SOLVERS = ("euler", "heun", "dpmpp_2m")
+
+
+# ---- losses ---------------------------------------------------------------------------------------------------------
+def _boxes(D_node):
+    """[B, N, 4] (cx, cy, w, h) in [0, 1] from the node estimate [B, N, C_node] (io.decode: last four channels * 0.5 + 0.5)"""
+    if D_node.dim() != 3 or D_node.shape[-1] < 4:
+        raise ValueError(f"box losses need a node tensor [B, N, C_node >= 4], got {tuple(D_node.shape)}")
+    return D_node[..., -4:] * 0.5 + 0.5
+
+
+def _corners(b):
+    return b[..., 0] - 0.5 * b[..., 2], b[..., 1] - 0.5 * b[..., 3], b[..., 0] + 0.5 * b[..., 2], b[..., 1] + 0.5 * b[..., 3]
+
+
+def box_region_loss(node_idx, region, node_flags=None):
+    """Squared hinge that pulls the box of node `node_idx` (an index, or a list of them) inside the rectangle region = (x0, y0, x1, y1)
+    in [0, 1] coordinates: the sum over graphs and the four sides of relu(overshoot)^2.  `node_flags` [B, N] (optional): graphs in
+    which the node is padding contribute nothing."""
+    x0, y0, x1, y1 = (float(v) for v in region)
+    if not (x0 < x1 and y0 < y1):
+        raise ValueError(f"box_region_loss: empty region {region}")
+    idx = [int(node_idx)] if isinstance(node_idx, (int, np.integer)) else [int(k) for k in node_idx]
+    if not idx or min(idx) < 0:
+        raise ValueError(f"box_region_loss: bad node index {node_idx}")
+
+    def loss(D_adj, D_node):
+        b = _boxes(D_node)
+        if max(idx) >= b.shape[1]:
+            raise ValueError(f"box_region_loss: node index {max(idx)} is outside the {b.shape[1]} nodes")
+        b = b[:, idx]
+        l, t, r, bt = _corners(b)
+        over = torch.relu(x0 - l) ** 2 + torch.relu(y0 - t) ** 2 + torch.relu(r - x1) ** 2 + torch.relu(bt - y1) ** 2
+        if node_flags is not None:
+            over = over * node_flags.to(device=over.device)[:, idx].to(over.dtype)
+        return over.sum()
+    return loss
+
+
+def box_overlap_loss(node_flags=None):
+    """Sum over graphs and unordered pairs of valid nodes of the intersection area of their boxes (negative extents clamped to 0):
+    the differentiable form of the evaluator's overlap metric.  `node_flags` [B, N] (optional): padded nodes take no part; without it
+    every node does (the denoised estimate of a padded node is all zeros, a box of extent 0.5 at the centre)."""
+    def loss(D_adj, D_node):
+        b = _boxes(D_node)
+        l, t, r, bt = _corners(b)
+        iw = torch.relu(torch.minimum(r[:, :, None], r[:, None, :]) - torch.maximum(l[:, :, None], l[:, None, :]))
+        ih = torch.relu(torch.minimum(bt[:, :, None], bt[:, None, :]) - torch.maximum(t[:, :, None], t[:, None, :]))
+        area = iw * ih
+        n = b.shape[1]
+        pair = torch.triu(torch.ones(n, n, dtype=torch.bool, device=b.device), diagonal=1)
+        if node_flags is not None:
+            f = node_flags.to(device=b.device).bool()
+            pair = pair[None] & f[:, :, None] & f[:, None, :]
+        return (area * pair.to(area.dtype)).sum()
+    return loss
+
+
+def box_alignment_loss(node_flags=None, tau=0.05):
+    """Alignment of a layout: for every valid node and each of the six lines (left, centre x, right, top, centre y, bottom), a soft
+    minimum over the other nodes of the squared distance between the same lines, summed.  The soft minimum is
+    -tau log sum_j exp(-d_ij^2 / tau) + tau log(n - 1): 0 for a node whose line coincides with every other node's, and close to the
+    squared distance to the nearest one when tau is small against it."""
+    tau = float(tau)
+    if tau <= 0:
+        raise ValueError("box_alignment_loss: tau must be positive")
+
+    def loss(D_adj, D_node):
+        b = _boxes(D_node)
+        l, t, r, bt = _corners(b)
+        lines = torch.stack([l, b[..., 0], r, t, b[..., 1], bt], dim=1)          # [B, 6, N]
+        d2 = (lines[..., :, None] - lines[..., None, :]) ** 2                    # [B, 6, N, N]
+        n = b.shape[1]
+        other = ~torch.eye(n, dtype=torch.bool, device=b.device)
+        valid = torch.ones(b.shape[:2], dtype=torch.bool, device=b.device) if node_flags is None else node_flags.to(device=b.device).bool()
+        pair = (other[None] & valid[:, :, None] & valid[:, None, :])[:, None]    # [B, 1, N, N]
+        cnt = pair.sum(-1).clamp(min=1).to(d2.dtype)                             # [B, 1, N]
+        z = torch.where(pair, -d2 / tau, torch.full_like(d2, -float("inf")))
+        has = pair.any(-1)
+        z = torch.where(has[..., None], z, torch.zeros_like(z))                  # rows without a partner: finite, dropped below
+        soft = -tau * torch.logsumexp(z, dim=-1) + tau * torch.log(cnt)
+        return (soft * has.to(soft.dtype)).sum()
+    return loss
+
+
+# ---- host arithmetic of the guided loop (no GPU needed) -------------------------------------------------------------
+def guidance_weights(scale, T: int) -> np.ndarray:
+    """w_i float32 [T] from `scale`: a number (the same weight at every level) or T of them (list, ndarray, tensor)."""
+    if isinstance(scale, torch.Tensor):
+        scale = scale.detach().cpu().numpy()
+    w = np.asarray(scale, dtype=np.float64)
+    if w.ndim == 0:
+        w = np.full(T, float(w))
+    if w.shape != (T,):
+        raise ValueError(f"scale must be a number or {T} weights (one per schedule index), got shape {w.shape}")
+    if not np.all(np.isfinite(w)):
+        raise ValueError("scale must be finite")
+    return w.astype(np.float32)
+
+
+def clip_factor(shift_norm, ref_norm, clip_ratio):
+    """Per-graph factor in (0, 1] that rescales a shift of 2-norm `shift_norm` so that it never exceeds clip_ratio * ref_norm
+    (ref_norm = ||x_hat_b - D_b||); 1 where the shift is already inside, or where clip_ratio is None.  Tensors [B] in, [B] out."""
+    if clip_ratio is None:
+        return torch.ones_like(shift_norm)
+    r = float(clip_ratio)
+    if not r >= 0:
+        raise ValueError(f"clip_ratio must be >= 0 or None, got {clip_ratio}")
+    bound = r * ref_norm
+    return torch.where(shift_norm > bound, bound / shift_norm.clamp(min=torch.finfo(shift_norm.dtype).tiny), torch.ones_like(shift_norm))
+
+
+def _graph_norm(a, x):
+    return torch.sqrt((a * a).flatten(1).sum(1) + (x * x).flatten(1).sum(1))
+
+
+# ---- the loop -------------------------------------------------------------------------------------------------------
+def guided_sample(net, sampler, node_flags, loss_fn, scale, *, clip_ratio=1.0, known=None, seed=None, graph_seeds=None,
+                  coin_seed=None, return_trace=False):
+    """Sample with the denoised estimate of every preconditioned call shifted against grad_x L(D(x, sigma)) (module docstring).
+
+    net: the NodeAdjPrecondHip of build_network(); sampler: a NodeAdjEDMSamplerHip (schedule, solver, churn, seed, self-conditioning).
+    loss_fn(D_adj, D_node) -> scalar, as in `value_and_input_grad`.  scale: w, or one w_i per schedule index.  clip_ratio = r: per
+    graph the shift is rescaled so that its 2-norm never exceeds r * ||x_hat_b - D_b||; None: unclipped.
+    known = (known_adj, known_node, mask_adj, mask_node): the exact select of `sample_known`, applied after the shift (known entries
+    win).  The self-conditioning input of the next call is the estimate after the select and before the shift.
+    seed / graph_seeds / coin_seed: as in `sampler.sample`.  Heun's stage 2 is evaluated at (x_hat, t_hat) like the reference's and
+    guided the same way; 'dpmpp_2m' extrapolates the guided estimate.
+    Returns (adjs, nodes) on the device (single channels squeezed); with return_trace also a list with one dict per preconditioned call:
+    step, stage, t_hat, w, x_hat, D (after the select), grad, shift (as applied), D_guided, and x (the state after the call's update, in
+    the entry of a step's last call) -- (adj, node) pairs of device tensors."""
+    if not isinstance(net, NodeAdjPrecondHip):
+        raise TypeError("guided_sample needs the NodeAdjPrecondHip network returned by build_network()")
+    if sampler.solver not in SOLVERS:
+        raise ValueError(sampler.solver)
+    if not callable(loss_fn):
+        raise TypeError("loss_fn must be callable: loss_fn(D_adj, D_node) -> scalar tensor")
+    T = sampler.num_steps
+    w_all = guidance_weights(scale, T)
+    if clip_ratio is not None and not float(clip_ratio) >= 0:
+        raise ValueError(f"clip_ratio must be >= 0 or None, got {clip_ratio}")
+    m = net.model
+    cfg, dev = m.config, m._dev
+    B, n = node_flags.shape[0], cfg.max_node_num
+    gs = None
+    if graph_seeds is not None:
+        if seed is not None:
+            raise ValueError("give seed= (one noise stream over the whole batch) or graph_seeds= (one per graph), not both")
+        gs = check_graph_seeds(graph_seeds, B)
+    elif coin_seed is not None:
+        raise ValueError("coin_seed= belongs to graph_seeds=; an unseeded call draws its coins from the NumPy global generator")
+    sa, sn = (B, cfg.c_adj, n, n), (B, n, cfg.c_node)
+    if known is not None:
+        if len(known) != 4 or any(k is None for k in known):
+            raise ValueError("known = (known_adj, known_node, mask_adj, mask_node)")
+        ka = known[0].to(device=dev, dtype=torch.float32).reshape(sa)
+        kn = known[1].to(device=dev, dtype=torch.float32).reshape(sn)
+        ma = (known[2].to(device=dev) != 0).reshape(sa)
+        mn = (known[3].to(device=dev) != 0).reshape(sn)
+    scfg = sampler._cfg()
+    sigma_steps, t_hat, noise_coef, h_step = _lib.sigma_schedule(scfg)
+    ms_coef = _lib.multistep_coef(scfg)
+    heun = sampler.solver == "heun"
+    n_calls = 2 * T - 1 if heun else T
+    if gs is not None:
+        coins = sampler.draw_coins_seeded(n_calls, sampler.seed if coin_seed is None else coin_seed)
+    else:
+        coins = sampler.draw_coins(n_calls)
+    f = node_flags.to(device=dev).bool()
+    fa, fn = (f[:, None, :, None] & f[:, None, None, :]), f[:, :, None]
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    mask = lambda a, x: (torch.where(fa, a, zero), torch.where(fn, x, zero))
+    noise = lambda stream: sampler.device_noise(net, node_flags, stream=stream, seed=seed, graph_seeds=gs)
+    fl8 = f.to(torch.uint8).contiguous()
+    f32 = np.float32
+    # per-step scalars: float32 values held as Python floats (exact), so that torch applies them as float32 scalars, tensor on the left
+
+    def denoise(xa, xn, t, w, sc, coin):
+        """one guided preconditioned call at (x_hat, t): (D after the select, D~, trace entry)"""
+        sca, scn = sc
+        if net.self_condition and coin:   # precond.py:90-98: the estimate of a no-grad extra pass becomes the self-conditioning input
+            with torch.no_grad():
+                sig = torch.full((B,), float(t), dtype=torch.float32, device=dev)
+                p = lambda v: None if v is None else v.data_ptr()
+                hd = m._ensure_handle()
+                ca, cx = torch.empty(sa, dtype=torch.float32, device=dev), torch.empty(sn, dtype=torch.float32, device=dev)
+                hd.check(hd.L.dsg_precond(hd.raw, B, p(xa), p(xn), p(fl8), p(sig), p(sca), p(scn), 0, p(ca), p(cx),
+                                          torch.cuda.current_stream(dev).cuda_stream), "dsg_precond")
+                if known is not None:
+                    ca, cx = mask(torch.where(ma, ka, ca), torch.where(mn, kn, cx))
+                sca, scn = ca, cx
+        Da, Dn, _, ga, gn = net.value_and_input_grad(xa, xn, node_flags, float(t), loss_fn=loss_fn, self_cond_adjs=sca,
+                                                     self_cond_nodes=scn, coin=False)
+        with torch.no_grad():
+            Da, Dn, ga, gn = Da.reshape(sa), Dn.reshape(sn), ga.reshape(sa), gn.reshape(sn)
+            if known is not None:
+                Da, Dn = mask(torch.where(ma, ka, Da), torch.where(mn, kn, Dn))
+            wt2 = float(f32(w) * f32(t) * f32(t))
+            sha, shn = mask(ga * wt2, gn * wt2)
+            fac = clip_factor(_graph_norm(sha, shn), _graph_norm(xa - Da, xn - Dn), clip_ratio)
+            sha, shn = sha * fac[:, None, None, None], shn * fac[:, None, None]
+            Ga, Gn = Da - sha, Dn - shn
+            if known is not None:
+                Ga, Gn = mask(torch.where(ma, ka, Ga), torch.where(mn, kn, Gn))
+        entry = dict(t_hat=float(t), w=float(w), x_hat=(xa, xn), D=(Da, Dn), grad=(ga, gn), shift=(sha, shn), D_guided=(Ga, Gn)) if return_trace else None
+        return (Da, Dn), (Ga, Gn), entry
+
+    trace = []
+    with torch.no_grad():
+        ia, inn = noise(0)
+        xa, xn = mask(ia * float(f32(sigma_steps[0])), inn * float(f32(sigma_steps[0])))   # x0 = init * sigma(t0) (edm.py:326, :346-347)
+    sc = (None, None)
+    prev = None   # the previous step's guided estimate (dpmpp_2m)
+    call = 0
+    for i in range(T):
+        t, hs, inv_t, nc, mc = float(t_hat[i]), float(h_step[i]), float(f32(1.0) / f32(t_hat[i])), float(noise_coef[i]), float(ms_coef[i])
+        with torch.no_grad():
+            if nc != 0:
+                ea, en = noise(i + 1)
+                xha, xhn = mask(xa + ea * nc, xn + en * nc)   # edm.py:361-366
+            else:
+                xha, xhn = mask(xa, xn)
+        D1, G1, e1 = denoise(xha, xhn, t, float(w_all[i]), sc, bool(coins[call]))
+        call += 1
+        euler = not heun or i == T - 1
+        with torch.no_grad():
+            if euler:
+                Ta, Tn = G1
+                if mc != 0 and prev is not None:   # D~ + c (D~ - D~prev): DPM-Solver++ 2M on the guided estimate
+                    Ta, Tn = Ta + (Ta - prev[0]) * mc, Tn + (Tn - prev[1]) * mc
+                xa, xn = mask(xha + (xha * inv_t - Ta * inv_t) * hs, xhn + (xhn * inv_t - Tn * inv_t) * hs)   # edm.py:384-385, :395-396
+                sc_next, last = D1, e1
+        if not euler:
+            # stage 2 re-evaluates at (x_hat, t_hat) with self-cond = the stage-1 estimate (edm.py:400-405)
+            D2, G2, e2 = denoise(xha, xhn, t, float(w_all[i]), D1 if net.self_condition else (None, None), bool(coins[call]))
+            call += 1
+            with torch.no_grad():
+                inv_tp = float(f32(1.0) / (f32(t) + f32(hs)))
+                upd = []
+                for xh, g1, g2 in ((xha, G1[0], G2[0]), (xhn, G1[1], G2[1])):
+                    dc = xh * inv_t - g1 * inv_t
+                    xp = xh + dc * hs
+                    dp = xp * inv_tp - g2 * inv_tp
+                    upd.append(xh + (dc * 0.5 + dp * 0.5) * hs)                                       # edm.py:414-422
+                xa, xn = mask(*upd)
+            sc_next, last = D2, e2
+            if return_trace:
+                e1.update(step=i, stage=1)
+                trace.append(e1)
+        if return_trace:
+            last.update(step=i, stage=1 if euler else 2, x=(xa, xn))
+            trace.append(last)
+        prev = G1
+        sc = sc_next if net.self_condition else (None, None)
+    out = m._shape_out(xa, xn)
+    return (out[0], out[1], trace) if return_trace else out

@@ -20,7 +20,11 @@ EXPORTS = [
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
     "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
     "dsg_sample_seeded", "dsg_gen_noise_seeded",
+    "dsg_precond_vjp", "dsg_debug_t_assemble_bwd",
 ]
+
+# dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
+GRAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
 DSG_ERR_INVALID = -1   # dsg_status of include/dsg.h: bad argument / unsupported configuration
 
@@ -170,6 +174,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_train_grads.argtypes = [vp, i32] + [vp] * 10 + [i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), vp]
     L.dsg_train_step_grads.argtypes = [vp, i32] + [vp] * 9 + [C.c_float] * 3 + [i32] + [vp] * 4 + [i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), vp]
     L.dsg_train_self_cond.argtypes = [vp, i32] + [vp] * 7
+    L.dsg_precond_vjp.argtypes = [vp, i32] + [vp] * 8 + [GRAD_FN, vp] + [vp] * 5
+    L.dsg_debug_t_assemble_bwd.argtypes = [i32] * 5 + [vp, i32] + [vp] * 8
     L.dsg_train_bind_params.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
     L.dsg_adam_step.argtypes = [i32] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int64), i32] + [C.c_float] * 6 + [C.POINTER(C.c_float), vp]
     L.dsg_ema_update.argtypes = [i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, vp]

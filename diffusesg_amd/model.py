@@ -206,6 +206,77 @@ class NodeAdjPrecondHip(nn.Module):
                 "dsg_precond")
         return m._shape_out(oa, on)
 
+    def value_and_input_grad(self, adjs, nodes, node_flags, sigmas, loss_fn=None, grad_outputs=None, self_cond_adjs=None,
+                             self_cond_nodes=None, coin=None):
+        """D = forward(adjs, nodes, ...) with the network in training form (fp32) and the gradient of a scalar of D with respect to the
+        noisy input (`dsg_precond_vjp`): returns (D_adj, D_node, loss, grad_adj, grad_node), device tensors in the shapes of the inputs.
+
+        Exactly one of `loss_fn` and `grad_outputs`:
+          loss_fn(D_adj, D_node) -> scalar tensor: an ordinary torch callable.  It runs between the library's forward and backward, on
+              torch's current stream (the one the library is given), on leaf tensors that wrap the library's D; `loss.backward()` fills
+              the cotangent.  An exception it raises is re-raised here after the library call has returned (no backward is launched).
+          grad_outputs = (g_adj, g_node): a cotangent dL/dD that does not depend on D; `loss` is then None.
+        sigmas: a scalar or [B].  The self-conditioning inputs are constants (not differentiated), sigma is not differentiated.
+        coin: None draws `np.random.rand() < 0.5` as forward() does (self-conditioning networks only); a fired coin computes the
+        self-conditioning input by the no-grad pass forward() runs (precond.py:90-98, on the sampling path) and passes it on as a constant.
+        The adjacency gradient at padded pairs is not zero: the network reads the unmasked adjacency input (diffusesg.py:784-802)."""
+        if (loss_fn is None) == (grad_outputs is None):
+            raise ValueError("value_and_input_grad: give exactly one of loss_fn and grad_outputs")
+        m = self.model
+        h = m._ensure_handle()
+        B, a, x, fl, sa, sx = m._canon(adjs, nodes, node_flags, self_cond_adjs, self_cond_nodes)
+        if (sa is None) != (sx is None):
+            raise ValueError("value_and_input_grad: self_cond_adjs and self_cond_nodes go together")
+        sg = torch.as_tensor(sigmas).to(device=m._dev, dtype=torch.float32).reshape(-1).expand(B).contiguous()
+        if coin is None:
+            coin = bool(self.self_condition and np.random.rand() < 0.5)
+        st = torch.cuda.current_stream(m._dev).cuda_stream
+        p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        if self.self_condition and coin:
+            with torch.no_grad():
+                ca, cx = torch.empty_like(a), torch.empty_like(x)
+                h.check(h.L.dsg_precond(h.raw, B, p(a), p(x), p(fl), p(sg), p(sa), p(sx), 0, p(ca), p(cx), C.c_void_p(st)), "dsg_precond")
+            sa, sx = ca, cx
+        if not self.self_condition:
+            sa = sx = None
+        oa, on = torch.empty_like(a), torch.empty_like(x)
+        ga, gn = torch.empty_like(a), torch.empty_like(x)
+        box = {"loss": None, "exc": None}
+
+        def callback(user, D_adj, D_node, g_adj, g_node):
+            try:
+                if D_adj != oa.data_ptr() or D_node != on.data_ptr() or g_adj != ga.data_ptr() or g_node != gn.data_ptr():
+                    raise _lib.DsgError("dsg_precond_vjp handed the callback buffers other than the call's outputs")
+                la, ln = oa.detach().requires_grad_(True), on.detach().requires_grad_(True)   # leaves on the library's D
+                with torch.enable_grad():
+                    loss = loss_fn(*m._shape_out(la, ln))
+                    if not isinstance(loss, torch.Tensor) or loss.numel() != 1:
+                        raise TypeError("loss_fn must return a scalar tensor")
+                    loss.backward()
+                for dst, leaf in ((ga, la), (gn, ln)):
+                    if leaf.grad is None:
+                        dst.zero_()
+                    else:
+                        dst.copy_(leaf.grad)
+                box["loss"] = loss.detach()
+                return 0
+            except BaseException as e:   # must not propagate through the C frames
+                box["exc"] = e
+                return 1
+        if loss_fn is not None:
+            fn = _lib.GRAD_FN(callback)
+            rc = h.L.dsg_precond_vjp(h.raw, B, p(a), p(x), p(fl), p(sg), p(sa), p(sx), None, None, fn, None,
+                                     p(oa), p(on), p(ga), p(gn), C.c_void_p(st))
+            if box["exc"] is not None:
+                raise box["exc"]
+        else:
+            da = grad_outputs[0].to(device=m._dev, dtype=torch.float32).reshape(a.shape).contiguous()
+            dn = grad_outputs[1].to(device=m._dev, dtype=torch.float32).reshape(x.shape).contiguous()
+            rc = h.L.dsg_precond_vjp(h.raw, B, p(a), p(x), p(fl), p(sg), p(sa), p(sx), p(da), p(dn), _lib.GRAD_FN(), None,
+                                     p(oa), p(on), p(ga), p(gn), C.c_void_p(st))
+        h.check(rc, "dsg_precond_vjp")
+        return (*m._shape_out(oa, on), box["loss"], *m._shape_out(ga, gn))
+
     @staticmethod
     def round_sigma(sigma):
         return torch.as_tensor(sigma)

@@ -303,3 +303,37 @@ def block_case(cfg, prefix: str, B: int, seed: int = 11):
     emb = (0.3 * W.normal(seed, f"blk/{prefix}/emb", (B, 512))).astype(np.float32)
     dy = W.normal(seed, f"blk/{prefix}/dy", (B, res * res, C))
     return x, emb, dy
+
+
+# ---- input-gradient fixture (tests/golden/input_grad.npz; tools/gen_input_grad_golden.py): NodeAdjPrecond under the reference's autograd
+# with the noisy inputs requiring grad.  tag -> (config, valid nodes per sample, per-sample sigmas, self-conditioning given, cotangent:
+# 'gen' = portable-generator draws g (L = <g, D>), 'overlap' = box_overlap_loss on D, stride of the stored D's last two adjacency dims)
+INPUT_GRAD_CASES = {
+    "tiny_sc": ("tiny", [8, 5, 3], [80.0, 1.5, 0.002], True, "gen", 1),
+    "tiny_none": ("tiny", [8, 5, 3], [80.0, 1.5, 0.002], False, "gen", 1),
+    "tiny_overlap": ("tiny", [8, 5, 3], [1.5, 0.6, 0.2], True, "overlap", 1),
+    "small": ("small", [16, 9], [1.5, 0.3], True, "gen", 1),          # shifted, masked windows
+    "nosc": ("nosc", [8, 3], [80.0, 0.5], False, "gen", 1),           # one channel each: squeezed shapes, no self-conditioning
+    "vg": ("vg", [30], [1.5], True, "gen", 4),
+    "coco": ("coco", [20], [0.7], True, "gen", 4),                    # 100-token windows
+}
+
+
+def input_grad_case(tag: str, seed: int = 29):
+    """cfg, flags, noisy adj / node (sample b scaled to its sigma's marginal, masked), sigmas [B], sc_adj / sc_node (None when the case
+    passes no self-conditioning), g_adj / g_node (None for the 'overlap' cotangent), D stride"""
+    name, valid, sigmas, with_sc, cot, stride = INPUT_GRAD_CASES[tag]
+    cfg = CONFIGS[name]()
+    B, n = len(valid), cfg.max_node_num
+    sig = np.asarray(sigmas, np.float32)
+    flags, adj, node, sc_adj, sc_node = case_inputs(cfg, B, valid, seed, f"igrad/{tag}")
+    scale = np.sqrt(sig.astype(np.float64) ** 2 + 0.25).astype(np.float32)
+    adj = (adj * scale[:, None, None, None]).astype(np.float32)
+    node = (node * scale[:, None, None]).astype(np.float32)
+    if not with_sc:
+        sc_adj = sc_node = None
+    g_adj = g_node = None
+    if cot == "gen":
+        g_adj = W.normal(seed, f"igrad/{tag}/g_adj", (B, cfg.c_adj, n, n))
+        g_node = W.normal(seed, f"igrad/{tag}/g_node", (B, n, cfg.c_node))
+    return cfg, flags, adj, node, sig, sc_adj, sc_node, g_adj, g_node, stride

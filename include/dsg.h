@@ -502,7 +502,8 @@ int dsg_debug_t_attn(int32_t bwd, int32_t B, int32_t res, int32_t ws, int32_t sh
                      float *out, const float *d_out, float *d_qkv, float *d_table, int32_t force_plain, void *stream);
 /* LayerNorm with affine on x [M, C].  Forward (bwd == 0): y, stats [M][2] = (mean, rstd); with aff [ceil(M/T), 2C] = (scale | shift)
  * the row is modulated first, x' = silu(shift + x (1 + scale)), and written to y_mod.  Backward: stats is read; dx_out = (dx_in ? dx_in
- * : 0) + the LayerNorm backward of dy (dx_in may alias dx_out); d_gamma / d_beta [C] may be NULL.  C % 4 == 0, C <= 1536. */
+ * : 0) + the LayerNorm backward of dy (dx_in may alias dx_out); d_gamma / d_beta [C] may be NULL (both NULL: the final reduction of their
+ * partials is not launched at all).  C % 4 == 0, C <= 1536. */
 int dsg_debug_t_ln(int32_t bwd, int32_t M, int32_t C, int32_t T, const float *x, const float *aff, float *y_mod, const float *gamma,
                    const float *beta, float *y, float *stats, const float *dy, const float *dx_in, float *dx_out, float *d_gamma,
                    float *d_beta, void *stream);
@@ -511,6 +512,16 @@ int dsg_debug_t_modulate(int32_t bwd, int32_t B, int32_t T, int32_t C, const flo
                          float *d_aff, void *stream);
 /* out[n] = sum_m X[m ld + n] */
 int dsg_debug_t_colsum(const float *X, int32_t ld, float *out, int32_t M, int32_t N, void *stream);
+/* the backward of the input assembly fused with the preconditioning chain (dsg_precond_vjp's last kernel) on its own.  d_tok [B N N, ld]
+ * token-major in the assembly's channel order -- self_cond == 0: [adj | node of the row | node of the column]; != 0: [sc_adj | adj |
+ * sc_node(row) | node(row) | sc_node(col) | node(col)], of which only the current-value slots are read --, flags [B, N], c_skip / c_in
+ * [B] (device), g = dL/dD in D's layouts.  With m the flags:
+ *   out_adj[b,c,i,j] = c_skip_b m_i m_j g_adj[b,c,i,j] + c_in_b d_tok[(b,i,j)][adj slot c]
+ *   out_node[b,i,c]  = c_skip_b m_i g_node[b,i,c] + c_in_b m_i (sum_j m_j d_tok[(b,i,j)][row slot c] + sum_j m_j d_tok[(b,j,i)][col slot c])
+ * No atomics, one summation order: repeated calls give the same bits.  out_* may alias g_*.  Any N; ld >= the channel count. */
+int dsg_debug_t_assemble_bwd(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, int32_t self_cond, const float *d_tok, int32_t ld,
+                             const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj, const float *g_node,
+                             float *out_adj, float *out_node, void *stream);
 /* up to 32 small problems in one launch.  kind: DSG_TGROUP_NT / TN / NN: C_z = op(A_z) op(B_z) (+ bias_z); NN_SUM: ONE C = sum_z A_z B_z
  * (shared M, N, C; bias of problem 0); SUM: out[i] = sum_z C_z[i], i < n_out; COLSUM: C_z[n] = sum_m A_z[m lda + n]; TT is not built
  * and is refused. */
@@ -642,6 +653,22 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
  * masked D tensors the caller then passes to dsg_train_step_grads as sc_adj / sc_node. */
 int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const float *noisy_node, const uint8_t *flags, const float *sigmas,
                         float *out_sc_adj, float *out_sc_node, void *stream);
+
+/* Vector-Jacobian product of the preconditioned denoiser with respect to its noisy input: D = NodeAdjPrecond.forward(adj, node, sigmas)
+ * with the network in training form (fp32 whatever the precision options; the bits dsg_train_self_cond gives when sc is NULL), then
+ * out_grad_adj = dL/d adj [B,C_adj,N,N] and out_grad_node = dL/d node [B,N,C_node] for the cotangent g = dL/dD.  sc_adj / sc_node: the
+ * self-conditioning inputs, constants (not differentiated; both or NULL); sigma is not differentiated either.  The backward runs
+ * without any weight-gradient product.  The adjacency gradient at padded pairs is NOT zero (the network reads the unmasked adjacency
+ * input); the node gradient of padded nodes is.
+ * g is either given (grad_D_adj / grad_D_node, device, D's layouts: a cotangent that does not depend on D) or produced by `fn`, which
+ * is called once between the forward and the backward: D_* are out_D_* (already enqueued on `stream`), and the callee ENQUEUES work on
+ * the same stream that fills g_* (device, D's layouts; they are out_grad_*, used as staging and overwritten with the result).  A nonzero
+ * return aborts the call before any backward launch: DSG_ERR_INVALID.  Exactly one of fn and grad_D_* must be given (DSG_ERR_INVALID
+ * otherwise).  DSG_ERR_STATE before dsg_finalize_weights.  The work is only enqueued; arena and scratch are the training entries'. */
+typedef int (*dsg_grad_fn)(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node);
+int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node, const uint8_t *flags, const float *sigmas /*[B]*/,
+                    const float *sc_adj, const float *sc_node, const float *grad_D_adj, const float *grad_D_node, dsg_grad_fn fn, void *user,
+                    float *out_D_adj, float *out_D_node, float *out_grad_adj, float *out_grad_node, void *stream);
 
 /* Let the training-form entries (dsg_train_grads, dsg_train_step_grads, dsg_train_self_cond) read these parameters IN PLACE: names[i]
  * (state-dict key) -> params[i] (device tensor of the parameter's shape, e.g. the tensor the optimiser updates), instead of the
