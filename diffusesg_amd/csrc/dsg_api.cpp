@@ -107,7 +107,7 @@ struct Workspace {
     // masked-token pruning: the need lists derived from `flags` whenever they are staged (stage_flags), at fixed addresses -- captured
     // graphs read them -- and this batch size's list offsets; cnt [n_lists], cnt_ps [B][n_lists] scratch of the list kernel
     int *need_lists = nullptr, *need_cnt = nullptr, *need_cnt_ps = nullptr;
-    int *dd_rep = nullptr;   // pure-window deduplication: every graph's representative pure window (kernels.h), [1 + dd_up][B] behind cnt_ps
+    int *dd_rep = nullptr;   // pure-window deduplication: every graph's representative pure window (kernels.h), [dd_n][B] behind cnt_ps
     // what this workspace's last forward did at level k: -1 no deduplication, 0 the copy moved rows of x (levels >= 1: and of the skip) only,
     // 1 also their (sum, sumsq) pairs in `stats` (the block left them for its consumer); dsg_debug_dedup_lists / dsg_debug_dedup_level_lists
     int dd_fwd[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1};
@@ -167,7 +167,7 @@ struct dsg_handle_s {
     bool opt_fused_attn = true, opt_fused_mlp = true, opt_fused_readout = true, opt_fused_pe = true;
     bool opt_fused_merge_small = false;   // also fuse PatchMerging below the size where it pays (tests force it on)
     bool opt_prune_masked = true;     // up path: skip rows / windows that only feed masked (padded) tokens (prune_on below)
-    bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_on below)
+    bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_opts_on below)
     int opt_dedup_batch = 1;          // ... and once for the whole batch in the sampler: 0 never, 1 from DEDUP_BATCH_MIN graphs, 2 always (dedup_stage_mode below)
     int opt_dedup_levels = 0;         // how many levels may do so: 0 every qualifying one, 1 the finest only, ... (dedup_levels below)
     PrunePlan prune;
@@ -1043,8 +1043,8 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
         const int nl = w->need.n_lists;
         size_t off = 0;
         for (int k = 0; k < nl; k++) { w->need.list_off[k] = (int)off; off += (size_t)B * prune_plan(h).items[k] + 16; }
-        const bool dd = w->need.dd_wins >= 0;
-        w->need_ints = off + nl + (size_t)B * nl + (dd ? (size_t)B * (1 + w->need.dd_up) : 0);
+        const bool dd = w->need.dd_n > 0;
+        w->need_ints = off + nl + (size_t)B * nl + (size_t)B * w->need.dd_n;
         if (int rc = dev_alloc(h, w->allocs, &q, sizeof(int) * w->need_ints)) return rc;
         HIP_TRY(h, hipMemset(q, 0, sizeof(int) * w->need_ints));   // counts of 0 until the first flags are staged
         w->need_lists = (int *)q; w->need_cnt = w->need_lists + off; w->need_cnt_ps = w->need_cnt + nl;
@@ -1130,28 +1130,22 @@ void build_prune_plan(dsg_handle h) {
         Q.roles.push_back(PruneRole{0, res / 2, 0, i, -2, Q.coarse[i]});
     }
     if (overflow) return;
-    // pure-window deduplication: PatchEmbed and the finest level's first block, where that block is unshifted on 8 x 8 windows
-    // (three lists behind the pruning's; without room for them the pruning stands alone)
-    if (!h->down[0].empty() && h->down[0][0].shift == 0 && h->down[0][0].ws == 8 && h->down[0][0].res == N && h->down[0][0].C == 96 &&
-        np.n_lists + 3 <= NEED_MAX_LISTS) {
-        const int nW = (N / 8) * (N / 8);
-        np.dd_wins = new_list(nW);
-        np.dd_runs = new_list(N * N / 8);
-        np.dd_copy = new_list(nW);
-        // ... and the coarser levels, as far as the chain goes (kernels.h): the level below is deduplicated and that block is its only
-        // one (a second, shifted block mixes neighbouring windows: behind it pure windows no longer share their rows); level k's first
-        // block unshifted on 8 x 8 windows, at least 2 x 2 of them (a level of one window has nothing to share: its only window is its
-        // own representative); room for its lists
-        for (int k = 1; k < L && k <= NEED_MAX_DD_UP; k++) {
-            const int res = N >> k;
-            if (h->down[k - 1].size() != 1 || h->down[k].empty() || h->down[k][0].shift != 0 || h->down[k][0].ws != 8 || h->down[k][0].res != res || res % 16 != 0 ||
-                np.n_lists + 3 > NEED_MAX_LISTS)
-                break;
-            np.ddu_wins[k - 1] = new_list((res / 8) * (res / 8));
-            np.ddu_runs[k - 1] = new_list(res * res / 8);
-            np.ddu_copy[k - 1] = new_list((res / 8) * (res / 8));
-            np.dd_up = k;
-        }
+    // pure-window deduplication (kernels.h): level k = 0, 1, ... of the down path as far as the chain goes, three lists each behind the
+    // pruning's (without room for them the chain ends; without level 0 the pruning stands alone).  A level qualifies where its first
+    // block is unshifted on 8 x 8 windows of the level's own grid.  Level 0 also is PatchEmbed's: the C = 96 kernels.  Level k >= 1
+    // needs the level below deduplicated with that block its only one (a second, shifted block mixes neighbouring windows: behind it
+    // pure windows no longer share their rows) and at least 2 x 2 windows (a level of one window has nothing to share: its only
+    // window is its own representative).
+    for (int k = 0; k < L && k <= NEED_MAX_DD_UP; k++) {
+        const int res = N >> k;
+        if (h->down[k].empty() || np.n_lists + 3 > NEED_MAX_LISTS) break;
+        const BlockPlan &b = h->down[k][0];
+        const bool qualifies = b.shift == 0 && b.ws == 8 && b.res == res && (k == 0 ? b.C == 96 : h->down[k - 1].size() == 1 && res % 16 == 0);
+        if (!qualifies) break;
+        np.dd_wins[k] = new_list((res / 8) * (res / 8));
+        np.dd_runs[k] = new_list(res * res / 8);
+        np.dd_copy[k] = new_list((res / 8) * (res / 8));
+        np.dd_n = k + 1;
     }
     P = Q;
     P.np = np;
@@ -1167,37 +1161,6 @@ bool prune_on(dsg_handle h, const Workspace *w) {
     // (the row-mapped GEMM addresses whole tensors through one buffer descriptor: the widest one must stay below 2 GiB)
     return w->need_lists && prune_opts_on(h) && (size_t)w->B * h->N * h->N * h->E * h->cfg.mlp_ratio * sizeof(float) < 0x7fffffffull;
 }
-// Pure-window deduplication (option "dedup_masked"; rule and list formats: kernels.h).  At a token (i, j) with a padded endpoint
-// fused_patch_embed96_kernel zeroes the node channels itself, and the adjacency channels it reads there are zero whenever the state came
-// from the sampler's own kernels (each stores `valid ? ... : 0.f`).  The PatchEmbed accumulator of such a token is then the bias, its
-// row depends on nothing but the graph's (scale, shift), and an unshifted block maps every all-padding ("pure") window of a graph to the
-// same 64 rows -- bit for bit, the kernels being deterministic and position-blind apart from the position inside the window.  So
-// PatchEmbed and the finest level's first block run over the non-pure windows plus ONE pure window per graph, and
-// window_broadcast96_kernel copies that window's rows (and their LayerNorm partials) to the graph's other pure windows before anything
-// else reads them: behind the copy w->x / w->stats hold exactly what the full launches would have written.
-// Decided at plan time: on only where the pruning is (same kernels, same list machinery) and where PatchEmbed, attention and MLP of
-// that block are the fused C = 96 kernels.  Decided per call on the device: an entry point that cannot vouch for the zeros (caller
-// tensors: dsg_denoise, dsg_precond) stages lists that name every window as unique and copy nothing (stage_flags).
-bool dedup_opts_on(dsg_handle h) {
-    if (!h->opt_dedup_masked || !prune_opts_on(h) || prune_plan(h).np.dd_wins < 0) return false;
-    const BlockPlan &b0 = h->down[0][0];
-    return h->opt_fused_pe && h->pe_wp && (h->Kp == 32 || h->Kp == 64) && h->opt_fused_attn && b0.wqp && h->opt_fused_mlp && b0.w1p &&
-           b0.C <= h->opt_fused_mlp_maxc;
-}
-bool dedup_on(dsg_handle h, const Workspace *w) { return w->dd_rep && dedup_opts_on(h) && prune_on(h, w); }
-// How many levels may deduplicate (option "dedup_levels": 0 = every qualifying one), the finest included; 0 when none does.  Level k >= 1
-// qualifies by the plan (build_prune_plan) and where the merge into it is the partial-statistics form of PatchMerging (the "fused_merge"
-// path): forward_fixed then runs that merge over the level's run list (launch_merge_norm_runs + the row-mapped reduction GEMM: the
-// values of the gather GEMM, bit for bit) and the level's first block over its lists.  Whether a given batch size takes that merge is
-// the forward's own rule (8192 merged rows, or "fused_merge" 2 / "batch_invariant"); a level whose merge is the merge_ln kernel ends
-// the chain.  Every block kernel of those levels takes a list wherever the pruning is on (prune_opts_on).
-int dedup_levels(dsg_handle h) {
-    if (!dedup_opts_on(h)) return 0;
-    int n = 1;
-    if (h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16)
-        for (int k = 1; k <= prune_plan(h).np.dd_up && (h->E << (k - 1)) % 32 == 0; k++) n = k + 1;
-    return h->opt_dedup_levels > 0 ? std::min(n, h->opt_dedup_levels) : n;
-}
 // Does the last block of level l leave row statistics for the partial-statistics form of PatchMerging at this batch size?
 // (below ~8k merged rows the reduction GEMM is a single partial wave of tiles and the gather + LayerNorm FMA in its
 // long K loop costs more than the small merge_ln launch it replaces: measured 103 vs 81 + 13 us at M = 4096, K = 1536)
@@ -1206,34 +1169,72 @@ bool merge_fused_at(dsg_handle h, int B, int l) {
     return l < h->L - 1 && h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16 && C % 32 == 0 &&
            (B * res * res / 4 >= 8192 || h->opt_fused_merge_small || h->opt_batch_invariant);   // "batch_invariant": the size plays no part
 }
-// How far the chain of deduplicated levels reaches in a forward of this workspace: levels 0 .. depth - 1.  The one predicate of
-// forward_fixed (which walks the chain launch by launch and checks that it ends here) and of stage_flags (which must know the top
-// level before the lists are written: only the levels under it may trim their fills).
+// Pure-window deduplication of the down path (options "dedup_masked", "dedup_levels", "dedup_batch"; rule and list formats: kernels.h).
+// At a token (i, j) with a padded endpoint fused_patch_embed96_kernel zeroes the node channels itself, and the adjacency channels it
+// reads there are zero whenever the state came from the sampler's own kernels (each stores `valid ? ... : 0.f`).  The PatchEmbed
+// accumulator of such a token is then the bias, its row depends on nothing but the graph's (scale, shift), and the unshifted first
+// block of a level maps every all-padding ("pure") window of a graph to the same 64 rows -- bit for bit, the kernels being
+// deterministic and position-blind apart from the position inside the window.  So at level k of the chain the producer (PatchEmbed,
+// or the merge into the level) and that block run over the non-pure windows plus ONE pure window per graph, and
+// window_broadcast_kernel copies that window's rows (with the skip and the row statistics the next launch reads) to the other pure
+// windows before anything else reads them: behind the copy the buffers hold exactly what the full launches would have written.
+//
+// Who decides what, and when:
+// * Plan time (build_prune_plan): which levels CAN deduplicate -- np.dd_n, from the block geometry alone -- and their lists.
+// * Options (dedup_opts_on, dedup_levels; what dsg_get_option reports): on only where the pruning is (same kernels, same list
+//   machinery) and where PatchEmbed, attention and MLP of level 0's block are the fused C = 96 kernels.  Level k >= 1 also needs the
+//   merge into it to be the partial-statistics form of PatchMerging (the "fused_merge" path), which runs over the level's run list
+//   (launch_merge_norm_runs + the row-mapped reduction GEMM: the values of the gather GEMM, bit for bit); "dedup_levels" caps the count.
+//   Every block kernel of those levels takes a list wherever the pruning is on (prune_opts_on).
+// * Per workspace (dedup_chain_depth): how many of those levels a forward at this batch size deduplicates, 0 .. depth - 1.  Whether a
+//   batch size takes the partial-statistics merge is merge_fused_at's rule (8192 merged rows, or "fused_merge" 2 / "batch_invariant");
+//   a level whose merge is the merge_ln kernel ends the chain.  This is the one predicate of forward_fixed, which asks it once and
+//   only checks, launch by launch, that the kernels left what it promised, and of stage_flags, which must know the top level before
+//   the lists are written: only the levels under it may trim their fills.
+// * Staging time (stage_flags -> dedup_stage_mode), per entry-point call, on the device: an entry point that cannot vouch for the
+//   zeros (caller tensors: dsg_denoise, dsg_precond) stages lists that name every window as unique and copy nothing (DD_OFF); the
+//   sampler stages one representative per graph (DD_GRAPH) or one for the batch (DD_BATCH, option "dedup_batch"; rule: kernels.h).
+//   The per-graph argument never uses the graph index, so it holds across graphs wherever every graph reads the same (scale, shift)
+//   row: `uniform_row` is the caller's word that every forward between this staging and the next is batch-uniform (sample_impl: all
+//   of them go through precond_tab, which sets w->uniform).  From DEDUP_BATCH_MIN graphs by default: below 16 graphs no down-path
+//   list launch of the N = 64 network exceeds half a round of 512 resident GEMM tiles, so fewer rows buy no time there -- and the
+//   per-graph lists stay what small batches always had.  Results are bit-identical either way.
+//   Trimming (bit k of *trim): level k's fill may leave out what nobody reads only when every later reader of its activation,
+//   statistics and skip goes through a list -- level k + 1 is deduplicated by the same forward (its merge takes the run list) and,
+//   from level 1 on, the up stage reads the skip through a coarse list (levels 0 .. k then have single unshifted blocks, down and up
+//   alike, so that list stays inside non-pure windows).  Without a coarse list the skip is read whole and the level is filled completely.
+// * Forward time (forward_fixed): nothing is decided.  The lists are whatever the last staging wrote; under DD_BATCH the forward
+//   checks that it runs at the depth they were trimmed for and reads the batch-uniform row.
+bool dedup_opts_on(dsg_handle h) {
+    if (!h->opt_dedup_masked || !prune_opts_on(h) || prune_plan(h).np.dd_n == 0) return false;
+    const BlockPlan &b0 = h->down[0][0];
+    return h->opt_fused_pe && h->pe_wp && (h->Kp == 32 || h->Kp == 64) && h->opt_fused_attn && b0.wqp && h->opt_fused_mlp && b0.w1p &&
+           b0.C <= h->opt_fused_mlp_maxc;
+}
+// how many levels may deduplicate (option "dedup_levels": 0 = every qualifying one), the finest included; 0 when none does
+int dedup_levels(dsg_handle h) {
+    if (!dedup_opts_on(h)) return 0;
+    int n = 1;
+    if (h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16)
+        while (n < prune_plan(h).np.dd_n && (h->E << (n - 1)) % 32 == 0) n++;
+    return h->opt_dedup_levels > 0 ? std::min(n, h->opt_dedup_levels) : n;
+}
 int dedup_chain_depth(dsg_handle h, const Workspace *w) {
-    if (!dedup_on(h, w)) return 0;
+    if (!w->dd_rep || !prune_on(h, w)) return 0;
     const int n = dedup_levels(h);
-    int depth = 1;
-    while (depth < n && h->down[depth - 1].size() == 1 && merge_fused_at(h, w->B, depth - 1) && !h->down[depth].empty()) depth++;
+    int depth = std::min(n, 1);
+    while (depth < n && merge_fused_at(h, w->B, depth - 1)) depth++;   // (the plan has made sure of the blocks: build_prune_plan)
     return depth;
 }
-// One representative for the batch (option "dedup_batch"; rule: kernels.h).  The per-graph argument above never uses the graph index,
-// so it holds across graphs wherever every graph reads the same (scale, shift) row: `uniform_row` is the caller's word that every
-// forward between this staging and the next is batch-uniform (sample_impl: all of them go through precond_tab, which sets
-// w->uniform).  From DEDUP_BATCH_MIN graphs by default: below 16 graphs no down-path list launch of the N = 64 network exceeds half a
-// round of 512 resident GEMM tiles, so fewer rows buy no time there -- and the per-graph lists stay what small batches always had.
-// Results are bit-identical either way.
-// Trimming (bit k of *trim): level k's fill may leave out what nobody reads only when every later reader of its activation,
-// statistics and skip goes through a list -- level k + 1 is deduplicated by the same forward (its merge takes the run list) and, from
-// level 1 on, the up stage reads the skip through a coarse list (levels 0 .. k then have single unshifted blocks, down and up alike,
-// so that list stays inside non-pure windows).  Without a coarse list the skip is read whole and the level is filled completely.
 constexpr int DEDUP_BATCH_MIN = 16;
 int dedup_stage_mode(dsg_handle h, const Workspace *w, bool zero_padded, bool uniform_row, int *trim, int *depth) {
     *trim = 0; *depth = 0;
     if (!zero_padded) return DD_OFF;
-    if (!uniform_row || !dedup_on(h, w) || h->opt_dedup_batch == 0 || (h->opt_dedup_batch == 1 && w->B < DEDUP_BATCH_MIN)) return DD_GRAPH;
-    *depth = dedup_chain_depth(h, w);
+    const int d = dedup_chain_depth(h, w);
+    if (!uniform_row || d == 0 || h->opt_dedup_batch == 0 || (h->opt_dedup_batch == 1 && w->B < DEDUP_BATCH_MIN)) return DD_GRAPH;
+    *depth = d;
     const PrunePlan &pp = prune_plan(h);
-    for (int k = 0; k + 1 < *depth; k++)
+    for (int k = 0; k + 1 < d; k++)
         if (k == 0 || pp.coarse[h->L - k] >= 0) *trim |= 1 << k;
     return DD_BATCH;
 }
@@ -1662,13 +1663,15 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
         // noise embedding (diffusesg.py:768-771) and every block's (scale,shift) in one GEMM
         embed_rows(h, w->c_noise, B, w->pe, w->emb0, w->emb, w->aff, s);
     }
-    // pure-window deduplication: PatchEmbed and level 0's first block take the unique lists, then the copy fills the other pure windows
-    const bool dedup = dedup_on(h, w);
-    const NeedRef dd_runs = dedup ? need_ref(h, w, w->need.dd_runs) : NeedRef(), dd_wins = dedup ? need_ref(h, w, w->need.dd_wins) : NeedRef(),
-                  dd_copy = dedup ? need_ref(h, w, w->need.dd_copy) : NeedRef();
-    const int dd_levels = dedup ? dedup_levels(h) : 0;
-    int dd_chain = 0;   // levels 0 .. dd_chain - 1 have been deduplicated by this forward
-    const bool pe_premod = patch_embed_stage(h, w, true, s, nullptr, dd_runs);
+    // pure-window deduplication of levels 0 .. depth - 1: the producer of level l's input (PatchEmbed, or the merge into the level) and
+    // the level's first block take its unique lists, then the copy fills the other pure windows
+    const int depth = dedup_chain_depth(h, w);
+    // lists with one representative for the batch were trimmed for one chain depth and hold for batch-uniform forwards only
+    if (depth > 0 && w->dd_mode == DD_BATCH && !g_dry_run) {
+        if (depth != w->dd_depth) plan_fail(h, "dedup_batch: the forward deduplicates %d levels, the lists were staged for %d", depth, w->dd_depth);
+        if (!w->uniform) plan_fail(h, "dedup_batch: a forward with per-sample noise labels under lists shared across the batch");
+    }
+    const bool pe_premod = patch_embed_stage(h, w, true, s, nullptr, depth > 0 ? need_ref(h, w, w->need.dd_runs[0]) : NeedRef());
     tap(h, "patch_embed", w->x, (size_t)B * T0 * E, s);
     // encoder (diffusesg.py:745-748)
     bool premod = pe_premod;   // is w->x already modulated for the next block (generic blocks: with LN1 partials in w->stats)?
@@ -1681,28 +1684,19 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             const BlockPlan *next = j + 1 < h->down[l].size() ? &h->down[l][j + 1] : (l == L - 1 && !h->up[0].empty() ? &h->up[0][0] : nullptr);
             // the level's last block leaves row statistics for the fused PatchMerging
             const bool for_merge = !next && merge_fused_at(h, B, l);
-            const bool dd = dedup && l == 0 && j == 0;
-            const bool ddk = l > 0 && j == 0 && dd_chain == l + 1;   // the merge above came over this level's run list
-            const BlockNeed bn = dd ? BlockNeed{dd_runs, dd_wins}
-                                    : (ddk ? BlockNeed{need_ref(h, w, w->need.ddu_runs[l - 1]), need_ref(h, w, w->need.ddu_wins[l - 1])} : BlockNeed());
+            const bool dd = j == 0 && l < depth;   // the level's input came over its run list
+            const BlockNeed bn = dd ? BlockNeed{need_ref(h, w, w->need.dd_runs[l]), need_ref(h, w, w->need.dd_wins[l])} : BlockNeed();
             const BlockOut bo = run_block(h, w, h->down[l][j], premod, next, for_merge, s, bn);
             premod = bo.premod; merge_parts = bo.stats_parts;
-            if (l == 0 && j == 0 && !g_dry_run) w->dd_fwd[0] = dd ? (bo.stats_parts == 1 ? 1 : 0) : -1;
+            // behind the copy x, the skip (level 0 has none yet) and the partials the next launch reads (a following block's LN1 partials
+            // of the pre-modulated rows, or the output rows' partials for the next merge) hold what the full launches would have written
+            const int parts = bo.premod ? (C + 95) / 96 : bo.stats_parts;
             if (dd) {
-                // (dedup_opts_on admits the fused C = 96 attention + MLP pair only: it leaves un-modulated rows and at most one pair of partials per row)
-                P_KERN(PK_ELEM, 0.0, launch_window_broadcast96(w->x, bo.stats_parts == 1 ? w->stats : nullptr, B, N, dd_copy.list, dd_copy.cnt, w->dd_rep, s));
-                dd_chain = 1;
+                const NeedRef cp = need_ref(h, w, w->need.dd_copy[l]);
+                P_KERN(PK_ELEM, 0.0, launch_window_broadcast(w->x, l ? w->skips[l - 1] : nullptr, parts > 0 ? w->stats : nullptr, parts, B, res, C,
+                                                             cp.list, cp.cnt, w->dd_rep + (size_t)l * B, s));
             }
-            if (l > 0 && l <= NEED_MAX_DD_UP && j == 0 && !g_dry_run) w->dd_fwd[l] = -1;
-            if (ddk) {
-                // behind this copy x, the skip and the partials the next launch reads (a following block's LN1 partials of the
-                // pre-modulated rows, or the output rows' partials for the next merge) hold what the full launches would have written
-                const int parts = bo.premod ? (C + 95) / 96 : bo.stats_parts;
-                const NeedRef cp = need_ref(h, w, w->need.ddu_copy[l - 1]);
-                P_KERN(PK_ELEM, 0.0, launch_window_broadcast(w->x, w->skips[l - 1], parts > 0 ? w->stats : nullptr, parts, B, res, C, cp.list, cp.cnt,
-                                                             w->dd_rep + (size_t)l * B, s));
-                if (!g_dry_run) w->dd_fwd[l] = parts > 0 ? 1 : 0;
-            }
+            if (j == 0 && l <= NEED_MAX_DD_UP && !g_dry_run) w->dd_fwd[l] = dd ? (parts > 0 ? 1 : 0) : -1;
             snprintf(name, sizeof(name), "down%d.block%d", l, (int)j);
             tap(h, name, w->x, (size_t)B * T * C, s);
         }
@@ -1710,18 +1704,21 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             const std::string p = "down_layers." + std::to_string(l) + ".downsample";
             g = GemmArgs();
             g.K1 = 4 * C; g.K = 4 * C; g.M = B * T / 4; g.N = 2 * C;
-            // pure-window deduplication of level l + 1: only the merged rows of its unique windows (dedup_levels above)
-            const bool ddm = merge_parts > 0 && dd_chain == l + 1 && l + 1 < dd_levels && !h->down[l + 1].empty();
-            if (ddm) {
+            // pure-window deduplication of level l + 1: only the merged rows of its unique windows
+            const bool dd_next = l + 1 < depth;
+            if (dd_next && merge_parts == 0) {   // (dedup_chain_depth promised the partial-statistics merge)
+                plan_fail(h, "down%d: deduplicated by the chain depth, but level %d's last block left no merge partials", l + 1, l);
+                return;
+            }
+            if (dd_next) {
                 // the gather + LayerNorm(4C) of the listed merged rows into y -- the values the gather form below puts into its A
                 // tile -- then the reduction over the same list, in place of the fine level (all of x has been read by then)
-                const NeedRef mr = need_ref(h, w, w->need.ddu_runs[l]);
+                const NeedRef mr = need_ref(h, w, w->need.dd_runs[l + 1]);
                 P_KERN(PK_ROW, 0.0, launch_merge_norm_runs(w->x, w->stats, merge_parts, w->y, B, res, C, mr.list, mr.cnt, s));
                 g.A = w->y; g.lda = 4 * C;
                 g.W = h->merge_wf[l]; g.bias = h->merge_bf[l];
                 g.C = w->x; g.ldc = 2 * C;
                 g.row_list = mr.list; g.row_cnt = mr.cnt; h->prof_next_list = mr.id;
-                dd_chain = l + 2;
             } else if (merge_parts > 0) {
                 // 2x2 gather, LayerNorm(4C) (statistics from the four source rows' partials, gamma/beta folded into the weight)
                 // and the reduction in one GEMM: the merged [B*T/4, 4C] tensor is never written
@@ -1737,18 +1734,13 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             attach_premod(h, w, g, h->down[l + 1].empty() ? nullptr : &h->down[l + 1][0]);   // the skip copy (C2) stays un-modulated
             P_GEMM_LP(g);
             premod = g.mod_aff != nullptr;
-            if (ddm && !premod) plan_fail(h, "down%d: the list form of PatchMerging needs the pre-modulating epilogue", l + 1);   // (mod_stats takes no list)
-            if (merge_parts > 0 && !ddm) std::swap(w->x, w->y);   // the new level's activation lives in the other buffer from here on
+            if (dd_next && !premod) plan_fail(h, "down%d: the list form of PatchMerging needs the pre-modulating epilogue", l + 1);   // (mod_stats takes no list)
+            if (merge_parts > 0 && !dd_next) std::swap(w->x, w->y);   // the new level's activation lives in the other buffer from here on
             merge_parts = 0;
         }
         snprintf(name, sizeof(name), "down%d", l);
         tap(h, name, w->x, l < L - 1 ? (size_t)B * (T / 4) * 2 * C : (size_t)B * T * C, s);
         // the deepest level's skip is popped and discarded by the first up layer (diffusesg.py:754-755)
-    }
-    // lists with one representative for the batch were trimmed for one chain depth and hold for batch-uniform forwards only
-    if (dedup && w->dd_mode == DD_BATCH && !g_dry_run) {
-        if (dd_chain != w->dd_depth) plan_fail(h, "dedup_batch: the forward deduplicated %d levels, the lists were staged for %d", dd_chain, w->dd_depth);
-        if (!w->uniform) plan_fail(h, "dedup_batch: a forward with per-sample noise labels under lists shared across the batch");
     }
     // decoder (diffusesg.py:751-756); with masked-token pruning every launch behind the plan's cut takes its need list
     const PrunePlan &pp = prune_plan(h);
@@ -2046,7 +2038,7 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     size_t need = 0;   // the need lists of the masked-token pruning: every list + 16 pad entries, counts, per-sample counts
     const PrunePlan &pp = prune_plan(h);
     for (int k = 0; k < pp.np.n_lists; k++) need += sizeof(int) * ((size_t)B * pp.items[k] + 16 + 1 + (size_t)B);
-    if (pp.np.dd_wins >= 0) need += sizeof(int) * (size_t)B * (1 + pp.np.dd_up);   // the representative windows of the pure-window deduplication
+    need += sizeof(int) * (size_t)B * pp.np.dd_n;   // the representative windows of the pure-window deduplication
     auto it = h->ws.find(B);   // + the known tensors and masks of dsg_sample_known, once a conditioned call has allocated them
     const size_t known = it != h->ws.end() ? it->second->known_bytes : 0;
     const size_t seeds = it != h->ws.end() ? it->second->seeds_bytes : 0;   // + the graph seeds, once a seeded call has allocated them
@@ -2650,13 +2642,12 @@ int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t 
     Workspace *w = it->second.get();
     counts[0] = counts[1] = counts[2] = -1;
     counts[3] = level <= NEED_MAX_DD_UP ? w->dd_fwd[level] : -1;
-    if (!w->dd_rep || level > w->need.dd_up) return DSG_OK;
+    if (!w->dd_rep || level >= w->need.dd_n) return DSG_OK;
     HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
     std::vector<int> all(w->need_ints);
     HIP_TRY(h, hipMemcpy(all.data(), w->need_lists, sizeof(int) * w->need_ints, hipMemcpyDeviceToHost));
     const int *cnt = all.data() + (w->need_cnt - w->need_lists);
-    const int ids[3] = {level ? w->need.ddu_wins[level - 1] : w->need.dd_wins, level ? w->need.ddu_runs[level - 1] : w->need.dd_runs,
-                        level ? w->need.ddu_copy[level - 1] : w->need.dd_copy};
+    const int ids[3] = {w->need.dd_wins[level], w->need.dd_runs[level], w->need.dd_copy[level]};
     int32_t *dst[3] = {wins, runs, copy};
     for (int k = 0; k < 3; k++) {
         counts[k] = cnt[ids[k]];

@@ -209,13 +209,13 @@ struct NeedOp { int kind, res, shift, list; };
 constexpr int NEED_MAX_OPS = 40, NEED_MAX_LISTS = 32, NEED_MAX_RUNS = 2048;   // runs of one sample at the finest level: N * N / 8
 constexpr int NEED_MAX_DD_UP = 3;   // coarser levels the pure-window deduplication may reach (N <= 128: 16, 8, 4, 2 windows per side)
 struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_off[NEED_MAX_LISTS];
-                  // pure-window deduplication (below): the unique 8-token runs / unique windows of the finest level and the pure windows
-                  // that are filled by copy; -1 = no such lists
-                  int dd_runs = -1, dd_wins = -1, dd_copy = -1;
-                  // the same three lists for the coarser levels 1 .. dd_up (index k - 1; "Coarser levels" below)
-                  int dd_up = 0, ddu_runs[NEED_MAX_DD_UP], ddu_wins[NEED_MAX_DD_UP], ddu_copy[NEED_MAX_DD_UP]; };
+                  // pure-window deduplication (below), levels 0 .. dd_n - 1 of the down path (0: none): level k's unique 8-token runs,
+                  // its unique windows and the pure windows that are filled by copy; -1 = the level has no such lists
+                  int dd_n = 0, dd_runs[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}, dd_wins[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1},
+                      dd_copy[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}; };
+static_assert(sizeof(NeedPlan) == sizeof(int) * (2 + 4 * NEED_MAX_OPS + NEED_MAX_LISTS + 1 + 3 * (1 + NEED_MAX_DD_UP)), "NeedPlan is a kernel argument: keep it packed");
 // cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
-// dedup (a DedupMode) / dd_rep / trim_mask: see below (dd_rep [1 + plan.dd_up][B]; may be null when the plan has no dd_* lists)
+// dedup (a DedupMode) / dd_rep / trim_mask: see below (dd_rep [plan.dd_n][B]; may be null when the plan has no dd_* lists)
 enum DedupMode { DD_OFF = 0,      // every window is listed as unique, nothing is copied
                  DD_GRAPH = 1,    // one representative pure window per graph
                  DD_BATCH = 2 };  // one for the whole batch ("One representative for the batch" below)
@@ -223,20 +223,18 @@ void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan,
                        int dedup = DD_OFF, int *dd_rep = nullptr, int trim_mask = 0);
 
 // ---- pure-window deduplication (option "dedup_masked") ----
-// An 8 x 8 window of the finest level is PURE when every token (i, j) of it has a padded endpoint (!(flag_i && flag_j)).  Where the
-// forward's inputs are zero at such tokens, PatchEmbed gives all of them one row and an unshifted Swin block gives every pure window of
-// a graph the same 64 rows, so one representative per graph (its first pure window, dd_rep[b] = b * nW + w, -1: the graph has none) is
-// computed and the others are filled by copy.  need_lists_kernel writes, in the formats above: dd_wins / dd_runs -- every non-pure
-// window plus the representative, as windows and as their 8-token runs; dd_copy -- the pure windows other than the representative.
+// Level k of the down path (k = 0 the finest; res = N >> k tokens per side, width C = E << k) has 8 x 8 windows that cover 8 << k nodes
+// per side.  Such a window is PURE when no valid pair lies under it: no valid node in its row block of 8 << k nodes, or none in its
+// column block -- at level 0, every token (i, j) of it has a padded endpoint (!(flag_i && flag_j)).  Every pure window of a graph gets
+// the same 64 rows from the level's unshifted first block:
+//   level 0 -- where the forward's inputs are zero at such tokens, PatchEmbed gives all of them one row;
+//   level k >= 1 -- a pure window lies over 2 x 2 pure windows of level k - 1, whose rows are equal window by window behind that level's
+//   copy (provided that level has no further, shifted block), and PatchMerging is a row-wise function of the 2 x 2 fine rows;
+// and the block sees positions only inside a window.  So one representative per graph (its first pure window, dd_rep[k * B + b] =
+// b * nW_k + w, -1: the graph has none) is computed and the others are filled by copy.  need_lists_kernel writes, for every planned
+// level and in the formats above (ids b * nW_k + w, runs b * res * res / 8 + run): dd_wins[k] / dd_runs[k] -- every non-pure window
+// plus the representative, as windows and as their 8-token runs; dd_copy[k] -- the pure windows other than the representative.
 // DD_OFF (the caller does not vouch for the zeros): every window is listed as unique, nothing is copied.
-// The copy: rows of x [B * N * N, 96] and, when stats is non-null, their (sum, sumsq) pairs stats [B * N * N][2]
-void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *copy_list, const int *copy_cnt, const int *dd_rep, hipStream_t s);
-// Coarser levels.  A window of level k (res = N >> k tokens per side, 8 << k nodes per window side) is pure when no valid pair lies under
-// it: no valid node in its row block of 8 << k nodes, or none in its column block.  It then lies over 2 x 2 pure windows of level k - 1,
-// whose rows are equal window by window behind that level's copy (provided that level has no further, shifted block); PatchMerging is a row-wise function of the 2 x 2 fine rows and the
-// unshifted first block of level k sees positions only inside a window, so every pure window of level k gets the same 64 rows again.
-// need_lists_kernel writes ddu_wins / ddu_runs / ddu_copy [k - 1] by the same rule and in the same formats as level 0 (ids b * nW_k + w,
-// runs b * res * res / 8 + run) and the representatives dd_rep [k * B + b].
 // One representative for the batch (DD_BATCH).  Nothing in the argument above uses the graph index: where every graph also reads the
 // same (scale, shift) row (the sampler's batch-uniform sigma, aff_ld = 0), a pure window of graph a and one of graph b get the same 64
 // rows at every level.  Level k's representative is then the first pure window of the BATCH in (graph, window) order; dd_rep[k * B + b]
@@ -253,8 +251,8 @@ void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *
 // (GemmArgs::a4_res) puts into its A tile, so the row-mapped GEMM on y gives that launch's rows bit for bit.  C % 4 == 0, (res / 2) % 8 == 0.
 void launch_merge_norm_runs(const float *x, const float *ln_part, int nparts, float *y, int B, int res, int C, const int *run_list,
                             const int *run_cnt, hipStream_t s);
-// The copy at width C: rows of x [B * res * res, C], of skip (same shape; null: none) and nparts (sum, sumsq) pairs per row of stats
-// (null: none); rep [B] = that level's representatives (global window ids, of any graph)
+// The copy of level k: rows of x [B * res * res, C], of skip (same shape; null: none -- level 0 has no skip yet) and nparts (sum, sumsq)
+// pairs per row of stats (null: none); rep [B] = that level's representatives (global window ids, of any graph).  C % 4 == 0
 void launch_window_broadcast(float *x, float *skip, float *stats, int nparts, int B, int res, int C, const int *copy_list,
                              const int *copy_cnt, const int *rep, hipStream_t s);
 

@@ -2833,24 +2833,24 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             uint8_t *t = cur; cur = nxt; nxt = t;
         }
     }
-    // Pure-window deduplication (kernels.h): the 8 x 8 windows of level k = 0 (the finest) .. plan.dd_up.  A level-k window covers
+    // Pure-window deduplication (kernels.h): the 8 x 8 windows of level k = 0 (the finest) .. plan.dd_n - 1.  A level-k window covers
     // 8 << k nodes per side; window (wi, wj) is pure iff no node of row block wi or none of column block wj is valid -- then
     // !(flag_i && flag_j) for every pair under it.  (N <= 128: at most 16 x 16 windows.)
     // DD_BATCH (kernels.h, "One representative for the batch"): level k's representative is the first pure window of the whole batch in
     // (graph, window) order, found by every block for itself from the flags of all graphs -- B * N bytes, the same answer in every
     // block and in both phases -- and the fill of a level whose bit is set in trim_mask lists only the pure windows under a unique
     // window of level k + 1.
-    if (plan.dd_wins >= 0) {
+    if (plan.dd_n > 0) {
         uint8_t *pure = map_a, *runs = map_b;   // the walk above is over: its maps are free
         if (dedup == DD_BATCH) {
             __syncthreads();
-            if (tid <= plan.dd_up) rep_all[tid] = 0x7fffffff;
+            if (tid < plan.dd_n) rep_all[tid] = 0x7fffffff;
             __syncthreads();
             for (int g = tid; g < B; g += 256) {
                 unsigned any = 0;   // bit q: a valid node among nodes 8 q .. 8 q + 7 of graph g; then, level by level, among (8 << k) q ..
                 for (int q = 0; q < N / 8; q++)
                     for (int e = 0; e < 8; e++) any |= flags[(size_t)g * N + q * 8 + e] != 0 ? 1u << q : 0u;
-                for (int k = 0; k <= plan.dd_up; k++) {
+                for (int k = 0; k < plan.dd_n; k++) {
                     const int nwr = (N >> k) / 8;
                     if (k > 0) {
                         unsigned up = 0;
@@ -2866,10 +2866,9 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             }
             __syncthreads();
         }
-        for (int k = 0; k <= plan.dd_up; k++) {
+        for (int k = 0; k < plan.dd_n; k++) {
             const int side = 8 << k, res = N >> k, nwr = res / 8, nW = nwr * nwr;
-            const int l_wins = k ? plan.ddu_wins[k - 1] : plan.dd_wins, l_runs = k ? plan.ddu_runs[k - 1] : plan.dd_runs,
-                      l_copy = k ? plan.ddu_copy[k - 1] : plan.dd_copy;
+            const int l_wins = plan.dd_wins[k], l_runs = plan.dd_runs[k], l_copy = plan.dd_copy[k];
             __syncthreads();
             if (tid < nwr) {
                 bool any = false;
@@ -2896,7 +2895,7 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             }
             __syncthreads();
             emit(runs, res * nwr, l_runs, b * res * nwr);
-            const bool trim = dedup == DD_BATCH && ((trim_mask >> k) & 1) && k < plan.dd_up;
+            const bool trim = dedup == DD_BATCH && ((trim_mask >> k) & 1) && k + 1 < plan.dd_n;
             for (int w = tid; w < nW; w += 256) {
                 bool fill = pure[w] && w != rep;
                 if (fill && trim) {   // only under a unique window of level k + 1: a non-pure one, or that level's representative
@@ -2923,41 +2922,13 @@ void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan,
     DSG_LAUNCH(need_lists_kernel<1>, dim3(B), dim3(256), 0, s, flags, B, N, plan, cnt_ps, lists, cnt, dedup, trim_mask, dd_rep);
 }
 
-// The copy of the pure-window deduplication: block k fills window copy_list[k] (b * nW + w) of x [B * N * N, 96] from the
-// representative window dd_rep[b] of its graph b (a window of b, or of any graph when the batch shares one) -- 64 rows of 24 float4 --
-// and, with stats, the rows' (sum, sumsq) pairs.  Fixed grid of B * nW blocks; blocks at or beyond *copy_cnt, and entries or sources
-// outside [0, B * nW), return.  Sources are unique windows and never listed for a fill, so one launch needs no ordering inside.
-__global__ __launch_bounds__(256) void window_broadcast96_kernel(float *__restrict__ x, float *__restrict__ stats, int B, int N,
-                                                                 const int *__restrict__ copy_list, const int *__restrict__ copy_cnt,
-                                                                 const int *__restrict__ dd_rep) {
-    const int k = blockIdx.x, tid = threadIdx.x;
-    if (k >= *copy_cnt) return;
-    const int nwr = N / 8, nW = nwr * nwr;
-    const int dst = copy_list[k];
-    if (dst < 0 || dst >= B * nW) return;
-    const int b = dst / nW, src = dd_rep[b];
-    if (src < 0 || src >= B * nW || src == dst) return;
-    const int sb = src / nW;   // the source's graph: b, or with one representative for the batch any graph
-    const int dw = dst - b * nW, sw = src - sb * nW;
-    const size_t d0 = (size_t)b * N * N + (size_t)(dw / nwr) * 8 * N + (dw % nwr) * 8;   // first token of the window
-    const size_t s0 = (size_t)sb * N * N + (size_t)(sw / nwr) * 8 * N + (sw % nwr) * 8;
-    for (int p = tid; p < 64 * 24; p += 256) {
-        const int t = p / 24, c = p - 24 * t;
-        const size_t off = (size_t)(t >> 3) * N + (t & 7);   // token t = (row t / 8, column t % 8) of the window
-        *reinterpret_cast<f32x4 *>(x + (d0 + off) * 96 + 4 * c) = *reinterpret_cast<const f32x4 *>(x + (s0 + off) * 96 + 4 * c);
-    }
-    if (stats && tid < 64) {
-        const size_t off = (size_t)(tid >> 3) * N + (tid & 7);
-        *reinterpret_cast<float2 *>(stats + 2 * (d0 + off)) = *reinterpret_cast<const float2 *>(stats + 2 * (s0 + off));
-    }
-}
-
-void launch_window_broadcast96(float *x, float *stats, int B, int N, const int *copy_list, const int *copy_cnt, const int *dd_rep, hipStream_t s) {
-    DSG_LAUNCH(window_broadcast96_kernel, dim3(B * (N / 8) * (N / 8)), dim3(256), 0, s, x, stats, B, N, copy_list, copy_cnt, dd_rep);
-}
-
-// The copy at width C (levels >= 1; kernels.h): block k fills window copy_list[k] (b * nW + w) of x [B * res * res, C] -- and of skip
-// and stats where given -- from its graph's representative rep[b].  Fixed grid of B * nW blocks; blocks at or beyond *copy_cnt return.
+// The copy of the pure-window deduplication at level k (kernels.h): block i fills window copy_list[i] (b * nW + w) of x [B * res * res, C]
+// -- and of skip and stats where given -- from the representative window rep[b] of its graph b (a window of b, or of any graph when the
+// batch shares one): 64 rows of C / 4 float4 and, with stats, the rows' nparts (sum, sumsq) pairs.  Fixed grid of B * nW blocks; blocks
+// at or beyond *copy_cnt, and entries or sources outside [0, B * nW), return.  Sources are unique windows and never listed for a fill,
+// so one launch needs no ordering inside.  C4 > 0: C / 4 at compile time (level 0's C = 96: the division by a constant measured 0.4 -
+// 0.5 us of that 7 us launch); 0: the run-time value.
+template <int C4>
 __global__ __launch_bounds__(256) void window_broadcast_kernel(float *__restrict__ x, float *__restrict__ skip, float *__restrict__ stats,
                                                                int nparts, int B, int res, int C, const int *__restrict__ copy_list,
                                                                const int *__restrict__ copy_cnt, const int *__restrict__ rep) {
@@ -2972,7 +2943,7 @@ __global__ __launch_bounds__(256) void window_broadcast_kernel(float *__restrict
     const int dw = dst - b * nW, sw = src - sb * nW;
     const size_t d0 = (size_t)b * res * res + (size_t)(dw / nwr) * 8 * res + (dw % nwr) * 8;   // first token of the window
     const size_t s0 = (size_t)sb * res * res + (size_t)(sw / nwr) * 8 * res + (sw % nwr) * 8;
-    const int c4n = C / 4;
+    const int c4n = C4 > 0 ? C4 : C / 4;
     for (int p = tid; p < 64 * c4n; p += 256) {
         const int t = p / c4n, c = p - c4n * t;
         const size_t off = (size_t)(t >> 3) * res + (t & 7);   // token t = (row t / 8, column t % 8) of the window
@@ -2989,7 +2960,9 @@ __global__ __launch_bounds__(256) void window_broadcast_kernel(float *__restrict
 
 void launch_window_broadcast(float *x, float *skip, float *stats, int nparts, int B, int res, int C, const int *copy_list,
                              const int *copy_cnt, const int *rep, hipStream_t s) {
-    DSG_LAUNCH(window_broadcast_kernel, dim3(B * (res / 8) * (res / 8)), dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep);
+    const dim3 grid(B * (res / 8) * (res / 8));
+    if (C == 96) DSG_LAUNCH(window_broadcast_kernel<24>, grid, dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep);
+    else DSG_LAUNCH(window_broadcast_kernel<0>, grid, dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep);
 }
 
 // PatchMerging's gather + LayerNorm(4C) over a run list of MERGED rows (kernels.h).  Block k takes run run_list[k]: 8 consecutive merged

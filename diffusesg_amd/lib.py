@@ -311,17 +311,7 @@ class Handle:
         rep [B] (each graph's representative window, -1: none; in a sampler call under "dedup_batch" one global id, of whichever graph,
         for every graph), and fwd: what the batch size's last forward did (-1 no deduplication,
         0 the copy moved activation rows, 1 also their LayerNorm partials); None when the configuration has no such lists."""
-        import numpy as np
-        n = self.cfg.max_node_num
-        nw = (n // 8) ** 2
-        counts = np.zeros(4, np.int32)
-        wins, runs, copy = np.zeros(B * nw, np.int32), np.zeros(B * n * n // 8, np.int32), np.zeros(B * nw, np.int32)
-        rep = np.zeros(B, np.int32)
-        self.check(self.L.dsg_debug_dedup_lists(self._h, B, counts.ctypes.data, wins.ctypes.data, runs.ctypes.data, copy.ctypes.data,
-                                                rep.ctypes.data, stream), "dsg_debug_dedup_lists")
-        if counts[0] < 0:
-            return None
-        return dict(wins=wins[:counts[0]].copy(), runs=runs[:counts[1]].copy(), copy=copy[:counts[2]].copy(), rep=rep, fwd=int(counts[3]))
+        return self.dedup_level_lists(B, 0, stream)
 
     def dedup_level_lists(self, B: int, level: int, stream=None):
         """dedup_lists for level `level` of the down path (dsg_debug_dedup_level_lists; level 0 is dedup_lists itself): window ids
