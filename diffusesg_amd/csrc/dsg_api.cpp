@@ -119,6 +119,7 @@ struct Workspace {
 };
 
 struct Tap { std::string name; float *dst; int64_t cap; };
+struct DevBuf { float *p = nullptr; size_t cap = 0; };   // a handle-owned device buffer that only grows (train_buf); cap in floats
 
 // Masked-token pruning (option "prune_masked"): which need list (kernels.h: NeedPlan) every up-path launch takes.  Built once per
 // handle from the up path's geometry (build_prune_plan); -1 = no list, the launch computes everything as before.
@@ -201,9 +202,9 @@ struct dsg_handle_s {
     StepRow *tab_step = nullptr;   // per-step scalars of the loop, read by the table-driven sampler kernels
     std::vector<Tap> taps;
     // training form (dsg_train_*): saved-activation arena and backward scratch, owned by the handle and kept between calls
-    // (hipMalloc / hipFree of ~10 GB per iteration cost more than a tenth of it); they only grow
-    float *train_arena = nullptr, *train_scr = nullptr, *train_io = nullptr, *train_mid = nullptr, *train_vjp = nullptr;
-    size_t train_arena_cap = 0, train_scr_cap = 0, train_io_cap = 0, train_mid_cap = 0, train_vjp_cap = 0;
+    // (hipMalloc / hipFree of ~10 GB per iteration cost more than a tenth of it); they only grow (train_buf).  train_io: the entries'
+    // preconditioned inputs, F and dL/dF; train_vjp: d_tok | W_img | coef of dsg_precond_vjp
+    DevBuf train_arena, train_scr, train_io, train_vjp;
     int *train_const = nullptr;                                   // device {0, 1}: the "self-conditioning present" switch of launch_assemble
     // dsg_train_bind_params: parameters the training form reads in place (the optimiser's own device tensors) instead of the handle's copies
     std::unordered_map<std::string, const float *> train_params;
@@ -713,11 +714,7 @@ void dsg_destroy(dsg_handle h) {
     for (float *q : {h->tab_sig, h->tab_cn, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff}) if (q) (void)hipFree(q);
     drop_graphs(h);
     if (h->tab_step) (void)hipFree(h->tab_step);
-    if (h->train_arena) (void)hipFree(h->train_arena);
-    if (h->train_scr) (void)hipFree(h->train_scr);
-    if (h->train_io) (void)hipFree(h->train_io);
-    if (h->train_mid) (void)hipFree(h->train_mid);
-    if (h->train_vjp) (void)hipFree(h->train_vjp);
+    for (DevBuf *b : {&h->train_arena, &h->train_scr, &h->train_io, &h->train_vjp}) if (b->p) (void)hipFree(b->p);
     if (h->train_const) (void)hipFree(h->train_const);
     for (auto &kv : h->ws) {
         if (kv.second->cap_stream) (void)hipStreamDestroy(kv.second->cap_stream);
@@ -3174,7 +3171,62 @@ int dsg_rainbow_loss_backward(int32_t B, int32_t N, int32_t c_adj, int32_t c_nod
     return hipGetLastError() == hipSuccess ? DSG_OK : DSG_ERR_HIP;
 }
 
-int dsg_block_train(dsg_handle h, const char *block, int32_t B, const float *x_in, const float *emb, const float *grad_out, float *x_out,
+}  // extern "C"
+
+// ---- training form: what one block and the whole network share ----
+namespace {
+struct TArena {   // bump allocator over one device buffer; without a base it only sizes (every get returns null)
+    float *base = nullptr; size_t off = 0;
+    float *get(size_t n) { n = (n + 63) / 64 * 64; float *p = base ? base + off : nullptr; off += n; return p; }
+};
+}  // namespace
+
+// a handle-owned device buffer of at least `need` floats (grown after draining the stream that may still read the old one)
+static float *train_buf(DevBuf &b, size_t need, hipStream_t s) {
+    if (need > b.cap) {
+        if (b.p) { (void)hipStreamSynchronize(s); (void)hipFree(b.p); }
+        b = DevBuf{};
+        if (hipMalloc((void **)&b.p, sizeof(float) * need) != hipSuccess) { b.p = nullptr; return nullptr; }
+        b.cap = need;
+    }
+    return b.p;
+}
+
+// `carve` hands out a buffer's regions; it runs twice, over no memory to get the size and then over the grown buffer, so that the size
+// and the layout cannot disagree.  false: out of memory
+template <class Carve> static bool train_carve(DevBuf &b, hipStream_t s, Carve carve) {
+    TArena A;
+    carve(A);
+    if (!train_buf(b, A.off, s)) return false;
+    A = TArena{b.p, 0};
+    carve(A);
+    return true;
+}
+
+// the 15 parameter tensors of a SwinTransformerBlock: state-dict names below the block's prefix and their slots in a.W / a.G
+static const char *const kBlockParamNames[15] = {"affine.weight", "affine.bias", "norm1.weight", "norm1.bias", "attn.relative_position_bias_table",
+                                                 "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
+                                                 "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"};
+static float *TrainBlockParams::*const kBlockParamSlots[15] = {
+    &TrainBlockParams::aff_w, &TrainBlockParams::aff_b, &TrainBlockParams::n1_w, &TrainBlockParams::n1_b, &TrainBlockParams::rpb,
+    &TrainBlockParams::qkv_w, &TrainBlockParams::qkv_b, &TrainBlockParams::proj_w, &TrainBlockParams::proj_b, &TrainBlockParams::n2_w,
+    &TrainBlockParams::n2_b, &TrainBlockParams::fc1_w, &TrainBlockParams::fc1_b, &TrainBlockParams::fc2_w, &TrainBlockParams::fc2_b};
+
+// geometry of block `b` at batch B, and its parameters / gradient buffers as weight(name) / grad(name) resolve them
+template <class FW, class FG> static void bind_block(TrainBlockArgs &a, const BlockPlan &b, int B, int mlp_ratio, FW weight, FG grad) {
+    a.B = B; a.res = b.res; a.ws = b.ws; a.shift = b.shift; a.heads = b.heads; a.C = b.C; a.hidden = mlp_ratio * b.C;
+    for (int i = 0; i < 15; i++) { a.W.*kBlockParamSlots[i] = weight(kBlockParamNames[i]); a.G.*kBlockParamSlots[i] = grad(kBlockParamNames[i]); }
+}
+
+// the tensors a block's forward saves for its backward
+static void carve_block_saved(TArena &A, TrainBlockArgs &a) {
+    const size_t M = (size_t)a.B * a.res * a.res, C = a.C, H = a.hidden;
+    a.aff = A.get((size_t)a.B * 2 * C); a.d_aff = A.get((size_t)a.B * 2 * C);
+    a.x_mod = A.get(M * C); a.xn1 = A.get(M * C); a.att = A.get(M * C); a.x1 = A.get(M * C); a.xn2 = A.get(M * C);
+    a.stats1 = A.get(M * 2); a.stats2 = A.get(M * 2); a.qkv = A.get(M * 3 * C); a.pre = A.get(M * H); a.hid = A.get(M * H);
+}
+
+extern "C" int dsg_block_train(dsg_handle h, const char *block, int32_t B, const float *x_in, const float *emb, const float *grad_out, float *x_out,
                     float *grad_in, float *grad_emb, int32_t n_params, const char *const *names, float *const *grad_params, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
     if (!block || B < 1 || !x_in || !emb || !x_out) return fail(h, DSG_ERR_INVALID, "null argument");
@@ -3183,44 +3235,32 @@ int dsg_block_train(dsg_handle h, const char *block, int32_t B, const float *x_i
         for (auto *vec : {&h->down[l], &h->up[l]})
             for (auto &b : *vec) if (b.prefix == block) bp = &b;
     if (!bp) return fail(h, DSG_ERR_INVALID, "no block '%s'", block);
-    static const char *kNames[15] = {"affine.weight", "affine.bias", "norm1.weight", "norm1.bias", "attn.relative_position_bias_table",
-                                     "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
-                                     "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"};
+    const bool bwd_args = grad_in && grad_emb && names && grad_params;
+    const char *no_weight = nullptr, *no_grad = nullptr;
     TrainBlockArgs a{};
-    float **Wp[15] = {&a.W.aff_w, &a.W.aff_b, &a.W.n1_w, &a.W.n1_b, &a.W.rpb, &a.W.qkv_w, &a.W.qkv_b, &a.W.proj_w, &a.W.proj_b,
-                      &a.W.n2_w, &a.W.n2_b, &a.W.fc1_w, &a.W.fc1_b, &a.W.fc2_w, &a.W.fc2_b};
-    float **Gp[15] = {&a.G.aff_w, &a.G.aff_b, &a.G.n1_w, &a.G.n1_b, &a.G.rpb, &a.G.qkv_w, &a.G.qkv_b, &a.G.proj_w, &a.G.proj_b,
-                      &a.G.n2_w, &a.G.n2_b, &a.G.fc1_w, &a.G.fc1_b, &a.G.fc2_w, &a.G.fc2_b};
-    for (int i = 0; i < 15; i++) {
-        auto it = h->w.find(bp->prefix + "." + kNames[i]);
-        if (it == h->w.end()) return fail(h, DSG_ERR_STATE, "weight '%s.%s' is not loaded", block, kNames[i]);
-        *Wp[i] = it->second.p;
-    }
-    if (grad_out) {
-        if (!grad_in || !grad_emb || !names || !grad_params) return fail(h, DSG_ERR_INVALID, "backward needs grad_in, grad_emb and the parameter gradient buffers");
-        for (int i = 0; i < 15; i++) {
-            float *dst = nullptr;
-            for (int k = 0; k < n_params; k++) if (names[k] && !strcmp(names[k], kNames[i])) dst = grad_params[k];
-            if (!dst) return fail(h, DSG_ERR_INVALID, "no gradient buffer for '%s'", kNames[i]);
-            *Gp[i] = dst;
-        }
-    }
-    a.B = B; a.res = bp->res; a.ws = bp->ws; a.shift = bp->shift; a.heads = bp->heads; a.C = bp->C; a.hidden = h->cfg.mlp_ratio * bp->C;
+    auto weight = [&](const char *name) -> float * {
+        auto it = h->w.find(bp->prefix + "." + name); if (it == h->w.end()) { if (!no_weight) no_weight = name; return nullptr; } return it->second.p; };
+    auto grad = [&](const char *name) -> float * {
+        float *dst = nullptr;
+        if (grad_out && bwd_args) for (int k = 0; k < n_params; k++) if (names[k] && !strcmp(names[k], name)) dst = grad_params[k];
+        if (!dst && !no_grad) no_grad = name;
+        return dst;
+    };
+    bind_block(a, *bp, B, h->cfg.mlp_ratio, weight, grad);
+    if (no_weight) return fail(h, DSG_ERR_STATE, "weight '%s.%s' is not loaded", block, no_weight);
+    if (grad_out && !bwd_args) return fail(h, DSG_ERR_INVALID, "backward needs grad_in, grad_emb and the parameter gradient buffers");
+    if (grad_out && no_grad) return fail(h, DSG_ERR_INVALID, "no gradient buffer for '%s'", no_grad);
     a.x_in = x_in; a.emb = emb; a.grad_out = grad_out; a.x_out = x_out; a.grad_in = grad_in; a.grad_emb = grad_emb;
-    const size_t M = (size_t)B * a.res * a.res, C = a.C, H = a.hidden;
-    const size_t sizes[17] = {(size_t)B * 2 * C, (size_t)B * 2 * C, M * C, M * C, M * C, M * C, M * C, M * C, M * C, M * C, M * 2, M * 2,
-                              M * 3 * C, M * 3 * C, M * H, M * H, M * H};
-    float **slots[17] = {&a.aff, &a.d_aff, &a.x_mod, &a.xn1, &a.att, &a.x1, &a.xn2, &a.d_x1, &a.t_mc, &a.t_mc2, &a.stats1, &a.stats2,
-                         &a.qkv, &a.t_m3c, &a.pre, &a.hid, &a.t_mh};
-    size_t total = 0;
-    for (size_t v : sizes) total += (v + 63) / 64 * 64;
-    float *scratch = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&scratch, sizeof(float) * total));
-    size_t off = 0;
-    for (int i = 0; i < 17; i++) { *slots[i] = scratch + off; off += (sizes[i] + 63) / 64 * 64; }
+    DevBuf scratch;   // this call's own: the saved tensors and the backward's scratch, freed below
+    const bool fits = train_carve(scratch, (hipStream_t)stream, [&](TArena &A) {
+        const size_t M = (size_t)B * a.res * a.res, C = a.C, H = a.hidden;
+        carve_block_saved(A, a);
+        a.d_x1 = A.get(M * C); a.t_mc = A.get(M * C); a.t_mc2 = A.get(M * C); a.t_m3c = A.get(M * 3 * C); a.t_mh = A.get(M * H);
+    });
+    if (!fits) return fail(h, DSG_ERR_HIP, "out of memory");
     const bool ok = train_block(a, (hipStream_t)stream);
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(scratch);
+    (void)hipFree(scratch.p);
     HIP_TRY(h, e);
     if (t_scratch_failed((hipStream_t)stream, true)) return fail(h, DSG_ERR_HIP, "out of memory (training scratch of this stream)");
     if (!ok) return fail(h, DSG_ERR_HIP, "train_block failed (window larger than 128 tokens or a launch error)");
@@ -3228,377 +3268,391 @@ int dsg_block_train(dsg_handle h, const char *block, int32_t B, const float *x_i
 }
 
 // ---- whole-network training step: forward in training form + backward to every parameter (correctness-first kernels) ----
+// The entries below build a TrainNet (parameters bound, buffers carved: nothing enqueued), then run train_forward, their own launches
+// on its outputs, and train_backward, all on the caller's stream.
 namespace {
-struct TArena {   // bump allocator over one hipMalloc
-    float *base = nullptr; size_t cap = 0, off = 0; bool dry = true;
-    float *get(size_t n) { n = (n + 63) / 64 * 64; float *p = dry ? nullptr : base + off; off += n; return p; }
+struct TrainLin { float *w, *b, *dw, *db; };   // a module's weight and bias and, when weight gradients are asked for, their gradient buffers
+struct TrainBufs {   // saved activations outside the blocks
+    float *pe, *m0, *s0, *m1, *emb, *d_emb, *pe_demb, *tok, *pe_lin, *pe_ln, *pe_stats, *pe_aff, *pe_daff, *x0;
+    float *mcat[8], *mnrm[8], *mstats[8], *mout[8];                                          // PatchMerging per level
+    float *ucat[8], *uy[8], *un[8], *ustats[8], *usc[8], *upn[8], *upstats[8], *uout[8];   // PatchBreakup per up layer
+    float *fy, *fstats, *z1, *z2, *rep, *ha_pre, *ha, *oa, *pool, *hn_pre, *hn, *on;
+    float *d_skip[8];
 };
-struct TLin { const float *x; float *y; };   // nothing else: linears keep their input pointer in the stage structs below
-}  // namespace
-
-// a handle-owned device buffer of at least `need` floats (grown after draining the stream that may still read the old one)
-static float *train_buf(dsg_handle h, float *&buf, size_t &cap, size_t need, hipStream_t s) {
-    if (need > cap) {
-        if (buf) { (void)hipStreamSynchronize(s); (void)hipFree(buf); }
-        buf = nullptr; cap = 0;
-        if (hipMalloc((void **)&buf, sizeof(float) * need) != hipSuccess) { buf = nullptr; return nullptr; }
-        cap = need;
-    }
-    return buf;
-}
-
-// `mid` (optional) runs between forward and backward on the same stream and fills dL/dF from the forward's outputs
-typedef std::function<int(const float *F_adj, const float *F_node, float *dF_adj, float *dF_node)> TrainMid;
+struct TrainStage { TrainBlockArgs a; float *x_out, *d_emb; };
+struct TrainNet {
+    int B, N, E, L, Ca, Cn, Cin, self_condition;
+    size_t M0;                        // B N N: tokens of level 0
+    std::vector<TrainStage> stages;   // the blocks in execution order: encoder level l is [first[l], first[l + 1]), up layer i starts at first[L + i]
+    int first[2 * DSG_MAX_LAYERS + 1];
+    bool grouped;                     // every `affine` linear of the network in one grouped launch (at most T_GROUP_MAX - 1 blocks)
+    // the modules outside the blocks; mrg_*: PatchMerging after encoder level l, up_*: PatchBreakup before up layer i (no biases but the norms')
+    TrainLin map0, map1, pe, pe_norm, pe_aff, norm, ro0, ro1, ro2, adj1, adj2, node1, node2;
+    TrainLin mrg_norm[8], mrg_red[8], up_pre[8], up_norm[8], up_pn[8], up_post[8];
+    TrainBufs Bf;
+    int skip_res[8], skip_C[8];       // the tensor at the end of encoder level l (after its merging, if any): the decoder's skip input
+    const int *has_sc;                // device 0 / 1: the "self-conditioning present" switch of launch_assemble
+    const float *xL;                  // the last block's output, left by train_forward for train_backward
+    float *t_mh, *t_m3c, *t_w, *t_mc, *t_mc2, *d_x, *d_y;   // backward scratch
+};
+struct TrainInputs { const float *adj, *node; const uint8_t *flags; const float *c_noise, *sc_adj, *sc_node; };
 // input-gradient mode (dsg_precond_vjp): the backward carries dL/d(activation) only -- no dW / db product, no affine or noise-embedding
 // backward, no parameter gradient buffer -- and ends in d_tok [B N N, ld] = d_pe_lin W_img, the gradient of the live columns of the
 // assembled input (img [E][ld]: scratch for the weight image of t_live_cols)
 struct TrainInputGrad { float *d_tok, *img; int ld; };
-static int train_grads_core(dsg_handle h, int32_t B, const float *in_adj, const float *in_node, const uint8_t *flags, const float *c_noise,
-                            const float *sc_adj, const float *sc_node, const float *grad_F_adj, const float *grad_F_node, const TrainMid *mid,
-                            float *out_F_adj, float *out_F_node, int32_t n_params, const char *const *names, float *const *grad_params,
-                            void *stream, const TrainInputGrad *ig = nullptr) {
-    // the training form reads the raw weights only, so weights re-uploaded after an optimiser step need no re-packing here
-    // (dsg_finalize_weights must have run once: block plans); the sampling-path entries still insist on `finalized`
-    if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
-    if (B < 1 || !in_adj || !in_node || !flags || !c_noise || !out_F_adj || !out_F_node) return fail(h, DSG_ERR_INVALID, "null argument");
-    const bool bwd = grad_F_adj != nullptr || mid != nullptr;
-    const bool wg = ig == nullptr;   // weight gradients wanted
-    if (bwd && ((!mid && !grad_F_node) || (wg && (!names || !grad_params)))) return fail(h, DSG_ERR_INVALID, "backward needs both output gradients and the parameter gradient buffers");
+enum TrainBackward { TRAIN_WEIGHT_GRADS, TRAIN_INPUT_GRADS };
+}  // namespace
+
+// saved activations of the whole network (pointers only: no lookup, nothing rebuilt)
+static void train_net_carve(TrainNet &net, TArena &A) {
+    TrainBufs &Bf = net.Bf;
+    const int B = net.B, N = net.N, E = net.E, L = net.L;
+    const size_t M0 = net.M0;
+    auto carve_stages = [&](int g) {
+        for (int k = net.first[g]; k < net.first[g + 1]; k++) {
+            TrainStage &st = net.stages[k];
+            carve_block_saved(A, st.a);
+            st.x_out = A.get((size_t)B * st.a.res * st.a.res * st.a.C); st.d_emb = A.get((size_t)B * NOISE_EMB);
+        }
+    };
+    Bf.pe = A.get((size_t)B * E); Bf.m0 = A.get((size_t)B * NOISE_EMB); Bf.s0 = A.get((size_t)B * NOISE_EMB);
+    Bf.m1 = A.get((size_t)B * NOISE_EMB); Bf.emb = A.get((size_t)B * NOISE_EMB); Bf.d_emb = A.get((size_t)B * NOISE_EMB);
+    Bf.pe_demb = A.get((size_t)B * NOISE_EMB);
+    Bf.tok = A.get(M0 * net.Cin); Bf.pe_lin = A.get(M0 * E); Bf.pe_ln = A.get(M0 * E); Bf.pe_stats = A.get(M0 * 2);
+    Bf.pe_aff = A.get((size_t)B * 2 * E); Bf.pe_daff = A.get((size_t)B * 2 * E); Bf.x0 = A.get(M0 * E);
+    int res = N, C = E;
+    for (int l = 0; l < L; l++) {
+        carve_stages(l);
+        if (l < L - 1) {
+            const size_t M2 = (size_t)B * (res / 2) * (res / 2);
+            Bf.mcat[l] = A.get(M2 * 4 * C); Bf.mnrm[l] = A.get(M2 * 4 * C); Bf.mstats[l] = A.get(M2 * 2); Bf.mout[l] = A.get(M2 * 2 * C);
+            res /= 2; C *= 2;
+        }
+        net.skip_res[l] = res; net.skip_C[l] = C;
+        Bf.d_skip[l] = A.get((size_t)B * res * res * C);
+    }
+    for (int i = 0; i < L; i++) {
+        if (i > 0) {
+            const size_t Mi = (size_t)B * res * res; const int D = 2 * C, Co = D / 4;
+            Bf.ucat[i] = A.get(Mi * D); Bf.uy[i] = A.get(Mi * D); Bf.un[i] = A.get(Mi * D); Bf.ustats[i] = A.get(Mi * 2);
+            Bf.usc[i] = A.get(Mi * 4 * Co); Bf.upn[i] = A.get(Mi * 4 * Co); Bf.upstats[i] = A.get(Mi * 4 * 2); Bf.uout[i] = A.get(Mi * 4 * Co);
+            res *= 2; C /= 2;
+        }
+        carve_stages(L + i);
+    }
+    Bf.fy = A.get(M0 * E); Bf.fstats = A.get(M0 * 2); Bf.z1 = A.get(M0 * E); Bf.z2 = A.get(M0 * E); Bf.rep = A.get(M0 * E);
+    Bf.ha_pre = A.get(M0 * E); Bf.ha = A.get(M0 * E); Bf.oa = A.get(M0 * net.Ca);
+    Bf.pool = A.get((size_t)B * N * E); Bf.hn_pre = A.get((size_t)B * N * E); Bf.hn = A.get((size_t)B * N * E); Bf.on = A.get((size_t)B * N * net.Cn);
+}
+
+// Validates, binds every parameter (and, with `weight_grads`, every gradient buffer of names / grad_params) once, and carves the
+// handle's arena and backward scratch for batch B.  Nothing is enqueued; a buffer that has to grow is freed after `s` has drained.
+static int train_net_build(dsg_handle h, TrainNet &net, int32_t B, const float *sc_adj, const float *sc_node, bool weight_grads,
+                           int32_t n_params, const char *const *names, float *const *grad_params, hipStream_t s) {
     if (h->cfg.self_condition && ((sc_adj == nullptr) != (sc_node == nullptr))) return fail(h, DSG_ERR_INVALID, "self-conditioning needs both tensors or none");
-    hipStream_t s = (hipStream_t)stream;
-    const int N = h->N, E = h->E, L = h->L, Ca = h->Ca, Cn = h->Cn, Cin = h->Cin, T0 = N * N;
-    const size_t M0 = (size_t)B * T0;
-    std::unordered_map<std::string, float *> gmap;
-    if (bwd && wg) for (int k = 0; k < n_params; k++) if (names[k] && grad_params[k]) gmap[names[k]] = grad_params[k];
-    std::string missing;
-    auto Wt = [&](const std::string &k) -> float * {
-        if (!h->train_params.empty()) { auto bt = h->train_params.find(k); if (bt != h->train_params.end()) return const_cast<float *>(bt->second); }
-        auto it = h->w.find(k); if (it == h->w.end()) { if (missing.empty()) missing = k; return nullptr; } return it->second.p; };
-    auto Gd = [&](const std::string &k) -> float * { if (!bwd || !wg) return nullptr; auto it = gmap.find(k); if (it == gmap.end()) { if (missing.empty()) missing = "grad:" + k; return nullptr; } return it->second; };
-    // collect the blocks in execution order
-    struct Stage { const BlockPlan *bp; TrainBlockArgs a; float *x_in, *x_out, *d_emb; };
-    std::vector<Stage> enc[8], dec[8];
-    TArena A;
-    const int has_sc_host = (h->cfg.self_condition && sc_adj) ? 1 : 0;
+    const int L = h->L;
+    net.B = B; net.N = h->N; net.E = h->E; net.L = L; net.Ca = h->Ca; net.Cn = h->Cn; net.Cin = h->Cin;
+    net.self_condition = h->cfg.self_condition; net.M0 = (size_t)B * h->N * h->N;
     if (!h->train_const) {
         const int zo[2] = {0, 1};
         HIP_TRY(h, hipMalloc((void **)&h->train_const, sizeof(zo)));
         HIP_TRY(h, hipMemcpy(h->train_const, zo, sizeof(zo), hipMemcpyHostToDevice));
     }
-    const int *has_sc_dev = h->train_const + has_sc_host;
-    // everything below runs twice: a dry pass that only sizes the arena, then the real pass
-    struct Bufs {
-        float *pe, *m0, *s0, *m1, *emb, *d_emb, *pe_demb, *tok, *pe_lin, *pe_ln, *pe_stats, *pe_aff, *pe_daff, *x0;
-        float *mcat[8], *mnrm[8], *mstats[8], *mout[8];                       // PatchMerging per level
-        float *ucat[8], *uy[8], *un[8], *ustats[8], *usc[8], *upn[8], *upstats[8], *uout[8];   // PatchBreakup per up layer
-        float *fy, *fstats, *z1, *z2, *rep, *ha_pre, *ha, *oa, *pool, *hn_pre, *hn, *on;
-        float *d_skip[8];
-    } Bf{};
-    const float *skip_ptr[8] = {};
-    int skip_res[8] = {}, skip_C[8] = {};
-    auto fill_block = [&](const BlockPlan &b, Stage &st) -> bool {
-        static const char *kNames[15] = {"affine.weight", "affine.bias", "norm1.weight", "norm1.bias", "attn.relative_position_bias_table",
-                                         "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
-                                         "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"};
-        TrainBlockArgs &a = st.a;
-        float **Wp[15] = {&a.W.aff_w, &a.W.aff_b, &a.W.n1_w, &a.W.n1_b, &a.W.rpb, &a.W.qkv_w, &a.W.qkv_b, &a.W.proj_w, &a.W.proj_b,
-                          &a.W.n2_w, &a.W.n2_b, &a.W.fc1_w, &a.W.fc1_b, &a.W.fc2_w, &a.W.fc2_b};
-        float **Gp[15] = {&a.G.aff_w, &a.G.aff_b, &a.G.n1_w, &a.G.n1_b, &a.G.rpb, &a.G.qkv_w, &a.G.qkv_b, &a.G.proj_w, &a.G.proj_b,
-                          &a.G.n2_w, &a.G.n2_b, &a.G.fc1_w, &a.G.fc1_b, &a.G.fc2_w, &a.G.fc2_b};
-        for (int i = 0; i < 15; i++) { *Wp[i] = Wt(b.prefix + "." + kNames[i]); *Gp[i] = Gd(b.prefix + "." + kNames[i]); }
-        a.B = B; a.res = b.res; a.ws = b.ws; a.shift = b.shift; a.heads = b.heads; a.C = b.C; a.hidden = h->cfg.mlp_ratio * b.C;
-        const size_t M = (size_t)B * b.res * b.res, C = b.C, H = a.hidden;
-        a.aff = A.get((size_t)B * 2 * C); a.d_aff = A.get((size_t)B * 2 * C);
-        a.x_mod = A.get(M * C); a.xn1 = A.get(M * C); a.att = A.get(M * C); a.x1 = A.get(M * C); a.xn2 = A.get(M * C);
-        a.stats1 = A.get(M * 2); a.stats2 = A.get(M * 2); a.qkv = A.get(M * 3 * C); a.pre = A.get(M * H); a.hid = A.get(M * H);
-        st.x_out = A.get(M * C); st.d_emb = A.get((size_t)B * NOISE_EMB);
-        return true;
-    };
-    for (int pass = 0; pass < 2; pass++) {
-        A.off = 0; A.dry = pass == 0;
-        for (int l = 0; l < 8; l++) { enc[l].clear(); dec[l].clear(); }
-        Bf.pe = A.get((size_t)B * E); Bf.m0 = A.get((size_t)B * NOISE_EMB); Bf.s0 = A.get((size_t)B * NOISE_EMB);
-        Bf.m1 = A.get((size_t)B * NOISE_EMB); Bf.emb = A.get((size_t)B * NOISE_EMB); Bf.d_emb = A.get((size_t)B * NOISE_EMB);
-        Bf.pe_demb = A.get((size_t)B * NOISE_EMB);
-        Bf.tok = A.get(M0 * Cin); Bf.pe_lin = A.get(M0 * E); Bf.pe_ln = A.get(M0 * E); Bf.pe_stats = A.get(M0 * 2);
-        Bf.pe_aff = A.get((size_t)B * 2 * E); Bf.pe_daff = A.get((size_t)B * 2 * E); Bf.x0 = A.get(M0 * E);
-        int res = N, C = E;
-        for (int l = 0; l < L; l++) {
-            for (auto &b : h->down[l]) { Stage st{}; st.bp = &b; fill_block(b, st); enc[l].push_back(st); }
-            if (l < L - 1) {
-                const size_t M2 = (size_t)B * (res / 2) * (res / 2);
-                Bf.mcat[l] = A.get(M2 * 4 * C); Bf.mnrm[l] = A.get(M2 * 4 * C); Bf.mstats[l] = A.get(M2 * 2); Bf.mout[l] = A.get(M2 * 2 * C);
-                res /= 2; C *= 2;
-            }
-            skip_res[l] = res; skip_C[l] = C;
-            Bf.d_skip[l] = A.get((size_t)B * res * res * C);
-        }
-        for (int i = 0; i < L; i++) {
-            const int lvl = L - 1 - i;
-            if (i > 0) {
-                const size_t Mi = (size_t)B * res * res; const int D = 2 * C, Co = D / 4;
-                Bf.ucat[i] = A.get(Mi * D); Bf.uy[i] = A.get(Mi * D); Bf.un[i] = A.get(Mi * D); Bf.ustats[i] = A.get(Mi * 2);
-                Bf.usc[i] = A.get(Mi * 4 * Co); Bf.upn[i] = A.get(Mi * 4 * Co); Bf.upstats[i] = A.get(Mi * 4 * 2); Bf.uout[i] = A.get(Mi * 4 * Co);
-                res *= 2; C /= 2;
-            }
-            for (auto &b : h->up[i]) { Stage st{}; st.bp = &b; fill_block(b, st); dec[i].push_back(st); }
-            (void)lvl;
-        }
-        Bf.fy = A.get(M0 * E); Bf.fstats = A.get(M0 * 2); Bf.z1 = A.get(M0 * E); Bf.z2 = A.get(M0 * E); Bf.rep = A.get(M0 * E);
-        Bf.ha_pre = A.get(M0 * E); Bf.ha = A.get(M0 * E); Bf.oa = A.get(M0 * Ca);
-        Bf.pool = A.get((size_t)B * N * E); Bf.hn_pre = A.get((size_t)B * N * E); Bf.hn = A.get((size_t)B * N * E); Bf.on = A.get((size_t)B * N * Cn);
-        if (pass == 0) {
-            if (!missing.empty()) return fail(h, DSG_ERR_INVALID, "missing tensor '%s'", missing.c_str());
-            // scratch for the backward: the widest [M, 4C] tensors of any stage, three of them, + block scratch
-            A.cap = A.off;
-            // the saved-activation arena and the backward scratch belong to the handle and are kept between calls
-            if (A.cap + 16 > h->train_arena_cap) {
-                if (h->train_arena) { (void)hipStreamSynchronize(s); (void)hipFree(h->train_arena); }
-                h->train_arena = nullptr; h->train_arena_cap = 0;
-                HIP_TRY(h, hipMalloc((void **)&h->train_arena, sizeof(float) * (A.cap + 16)));
-                h->train_arena_cap = A.cap + 16;
-            }
-            A.base = h->train_arena;
+    net.has_sc = h->train_const + ((h->cfg.self_condition && sc_adj) ? 1 : 0);
+    std::unordered_map<std::string, float *> gmap;
+    if (weight_grads) for (int k = 0; k < n_params; k++) if (names[k] && grad_params[k]) gmap[names[k]] = grad_params[k];
+    std::string missing;
+    auto Wt = [&](const std::string &k) -> float * {
+        if (!h->train_params.empty()) { auto bt = h->train_params.find(k); if (bt != h->train_params.end()) return const_cast<float *>(bt->second); }
+        auto it = h->w.find(k); if (it == h->w.end()) { if (missing.empty()) missing = k; return nullptr; } return it->second.p; };
+    auto Gd = [&](const std::string &k) -> float * { if (!weight_grads) return nullptr; auto it = gmap.find(k); if (it == gmap.end()) { if (missing.empty()) missing = "grad:" + k; return nullptr; } return it->second; };
+    for (int g = 0; g < 2 * L; g++) {
+        net.first[g] = (int)net.stages.size();
+        for (const BlockPlan &b : g < L ? h->down[g] : h->up[g - L]) {
+            net.stages.emplace_back();
+            bind_block(net.stages.back().a, b, B, h->cfg.mlp_ratio, [&](const char *name) { return Wt(b.prefix + "." + name); },
+                       [&](const char *name) { return Gd(b.prefix + "." + name); });
         }
     }
-    // widest scratch tensors (backward): sized for level 0's [M0, 4E]; every level has M C constant up to the 2x of merging
-    size_t wide = M0 * (size_t)(4 * E);
-    const size_t scr_need = wide * 3 + M0 * (size_t)E * 8 + 4096;
-    if (scr_need > h->train_scr_cap) {
-        if (h->train_scr) { (void)hipStreamSynchronize(s); (void)hipFree(h->train_scr); }
-        h->train_scr = nullptr; h->train_scr_cap = 0;
-        if (hipMalloc((void **)&h->train_scr, sizeof(float) * scr_need) != hipSuccess) return fail(h, DSG_ERR_HIP, "out of memory");
-        h->train_scr_cap = scr_need;
+    net.first[2 * L] = (int)net.stages.size();
+    net.grouped = (int)net.stages.size() + 1 <= T_GROUP_MAX;
+    for (TrainStage &st : net.stages) st.a.aff_grouped = net.grouped;
+    auto lin = [&](const std::string &p, bool bias = true) {
+        return TrainLin{Wt(p + ".weight"), bias ? Wt(p + ".bias") : nullptr, Gd(p + ".weight"), bias ? Gd(p + ".bias") : nullptr}; };
+    net.map0 = lin("map_layer0"); net.map1 = lin("map_layer1"); net.pe = lin("patch_embed.proj"); net.pe_norm = lin("patch_embed.norm");
+    net.pe_aff = lin("patch_embed.affine"); net.norm = lin("norm"); net.ro0 = lin("read_out.0"); net.ro1 = lin("read_out.1");
+    net.ro2 = lin("read_out.2"); net.adj1 = lin("readout_adj_mlp.fc1"); net.adj2 = lin("readout_adj_mlp.fc2");
+    net.node1 = lin("readout_node_mlp.fc1"); net.node2 = lin("readout_node_mlp.fc2");
+    for (int l = 0; l < L - 1; l++) {
+        const std::string p = "down_layers." + std::to_string(l) + ".downsample.";
+        net.mrg_norm[l] = lin(p + "norm"); net.mrg_red[l] = lin(p + "reduction", false);
     }
-    float *scr = h->train_scr;
-    float *t_mh = scr, *t_m3c = scr + wide, *t_w = scr + 2 * wide, *t_mc = scr + 3 * wide, *t_mc2 = t_mc + M0 * E * 2, *d_x = t_mc2 + M0 * E * 2,
-          *d_y = d_x + M0 * E * 2;
-    auto lin_fwd = [&](const float *x, const float *Wm, const float *bias, float *y, size_t M, int in, int out) {
-        t_gemm(false, true, x, in, Wm, in, bias, y, out, (int)M, out, in, false, s);
-    };
-    auto lin_bwd = [&](const float *x, const float *Wm, const float *dy, float *dx, float *dW, float *db, size_t M, int in, int out) {
-        if (wg) t_gemm(true, false, dy, out, x, in, nullptr, dW, in, out, in, (int)M, false, s, db);   // dW [out,in] = dy^T x, db = colsum(dy)
-        if (dx) t_gemm(false, false, dy, out, Wm, in, nullptr, dx, in, (int)M, in, out, false, s);   // dx = dy W
-    };
+    for (int i = 1; i < L; i++) {
+        const std::string p = "up_layers." + std::to_string(i) + ".upsample.";
+        net.up_pre[i] = lin(p + "pre_linear", false); net.up_norm[i] = lin(p + "norm"); net.up_pn[i] = lin(p + "post_norm");
+        net.up_post[i] = lin(p + "post_linear", false);
+    }
+    if (!missing.empty()) return fail(h, DSG_ERR_INVALID, "missing tensor '%s'", missing.c_str());
+    // the saved-activation arena and the backward scratch belong to the handle and are kept between calls.  Scratch: three of the
+    // widest tensors, level 0's [M0, 4E] (every level has M C constant up to the 2x of merging), and four of [M0, 2E]
+    const size_t wide = net.M0 * (size_t)(4 * net.E), two = net.M0 * (size_t)net.E * 2;
+    if (!train_carve(h->train_arena, s, [&](TArena &A) { train_net_carve(net, A); A.get(16); }) ||
+        !train_carve(h->train_scr, s, [&](TArena &A) {
+            net.t_mh = A.get(wide); net.t_m3c = A.get(wide); net.t_w = A.get(wide); net.t_mc = A.get(two); net.t_mc2 = A.get(two);
+            net.d_x = A.get(two); net.d_y = A.get(two + 4096);
+        }))
+        return fail(h, DSG_ERR_HIP, "out of memory");
+    return DSG_OK;
+}
+
+// y [M, out] = x [M, in] W^T + bias (W [out, in]); its backward: dW = dy^T x and db = colsum(dy) when `wg`, dx = dy W when dx is given
+static void lin_fwd(const float *x, const float *W, const float *bias, float *y, size_t M, int in, int out, hipStream_t s) {
+    t_gemm(false, true, x, in, W, in, bias, y, out, (int)M, out, in, false, s);
+}
+static void lin_bwd(bool wg, const float *x, const float *W, const float *dy, float *dx, float *dW, float *db, size_t M, int in, int out,
+                    hipStream_t s) {
+    if (wg) t_gemm(true, false, dy, out, x, in, nullptr, dW, in, out, in, (int)M, false, s, db);
+    if (dx) t_gemm(false, false, dy, out, W, in, nullptr, dx, in, (int)M, in, out, false, s);
+}
+
+// F = network(in) in training form, every activation the backward needs left in the arena; false: a block refused to launch
+static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F, hipStream_t s) {
+    const TrainBufs &Bf = net.Bf;
+    const int B = net.B, N = net.N, E = net.E, L = net.L, Ca = net.Ca, Cn = net.Cn, Cin = net.Cin, T0 = N * N;
+    const size_t M0 = net.M0;
     bool ok = true;
-    // ================================ forward ================================
-    launch_noise_pe(c_noise, Bf.pe, B, E, s);
-    lin_fwd(Bf.pe, Wt("map_layer0.weight"), Wt("map_layer0.bias"), Bf.m0, B, E, NOISE_EMB);
+    launch_noise_pe(in.c_noise, Bf.pe, B, E, s);
+    lin_fwd(Bf.pe, net.map0.w, net.map0.b, Bf.m0, B, E, NOISE_EMB, s);
     t_silu(Bf.m0, nullptr, Bf.s0, (size_t)B * NOISE_EMB, false, s);
-    lin_fwd(Bf.s0, Wt("map_layer1.weight"), Wt("map_layer1.bias"), Bf.m1, B, NOISE_EMB, NOISE_EMB);
+    lin_fwd(Bf.s0, net.map1.w, net.map1.b, Bf.m1, B, NOISE_EMB, NOISE_EMB, s);
     t_silu(Bf.m1, nullptr, Bf.emb, (size_t)B * NOISE_EMB, false, s);
-    launch_assemble(in_adj, in_node, sc_adj, sc_node, has_sc_dev, flags, Bf.tok, B, N, Ca, Cn, h->cfg.self_condition, Cin, s);
-    lin_fwd(Bf.tok, Wt("patch_embed.proj.weight"), Wt("patch_embed.proj.bias"), Bf.pe_lin, M0, Cin, E);
-    t_ln_fwd(Bf.pe_lin, Wt("patch_embed.norm.weight"), Wt("patch_embed.norm.bias"), Bf.pe_ln, Bf.pe_stats, (int)M0, E, s);
-    // every `affine` linear of the network (PatchEmbed + all blocks) hangs off emb: one grouped launch
-    std::vector<Stage *> all_stages;
-    for (int l = 0; l < L; l++) for (auto &st : enc[l]) all_stages.push_back(&st);
-    for (int i = 0; i < L; i++) for (auto &st : dec[i]) all_stages.push_back(&st);
-    const bool grouped = (int)all_stages.size() + 1 <= T_GROUP_MAX;
-    if (grouped) {
+    launch_assemble(in.adj, in.node, in.sc_adj, in.sc_node, net.has_sc, in.flags, Bf.tok, B, N, Ca, Cn, net.self_condition, Cin, s);
+    lin_fwd(Bf.tok, net.pe.w, net.pe.b, Bf.pe_lin, M0, Cin, E, s);
+    t_ln_fwd(Bf.pe_lin, net.pe_norm.w, net.pe_norm.b, Bf.pe_ln, Bf.pe_stats, (int)M0, E, s);
+    if (net.grouped) {
+        // every `affine` linear of the network (PatchEmbed + all blocks) hangs off emb: one grouped launch
         TGemmGroup gf;
-        gf.p[gf.n++] = TGemmProb{Bf.emb, Wt("patch_embed.affine.weight"), Wt("patch_embed.affine.bias"), Bf.pe_aff, NOISE_EMB, NOISE_EMB, 2 * E, B, 2 * E, NOISE_EMB};
-        for (Stage *st : all_stages) {
-            st->a.aff_grouped = true;
-            gf.p[gf.n++] = TGemmProb{Bf.emb, st->a.W.aff_w, st->a.W.aff_b, st->a.aff, NOISE_EMB, NOISE_EMB, 2 * st->a.C, B, 2 * st->a.C, NOISE_EMB};
-        }
+        gf.p[gf.n++] = TGemmProb{Bf.emb, net.pe_aff.w, net.pe_aff.b, Bf.pe_aff, NOISE_EMB, NOISE_EMB, 2 * E, B, 2 * E, NOISE_EMB};
+        for (const TrainStage &st : net.stages)
+            gf.p[gf.n++] = TGemmProb{Bf.emb, st.a.W.aff_w, st.a.W.aff_b, st.a.aff, NOISE_EMB, NOISE_EMB, 2 * st.a.C, B, 2 * st.a.C, NOISE_EMB};
         t_gemm_grouped(false, true, false, gf, s);
-    } else {
-        lin_fwd(Bf.emb, Wt("patch_embed.affine.weight"), Wt("patch_embed.affine.bias"), Bf.pe_aff, B, NOISE_EMB, 2 * E);
+    } else {   // more blocks than one group holds: PatchEmbed's here, each block's own in train_block
+        lin_fwd(Bf.emb, net.pe_aff.w, net.pe_aff.b, Bf.pe_aff, B, NOISE_EMB, 2 * E, s);
     }
     t_modulate(Bf.pe_ln, Bf.pe_aff, nullptr, Bf.x0, nullptr, B, T0, E, false, s);
-    const float *x = Bf.x0;
+    const float *x = Bf.x0, *skip[8] = {};
     int res = N, C = E;
-    auto run_blocks_fwd = [&](std::vector<Stage> &v) {
-        for (auto &st : v) {
-            st.x_in = const_cast<float *>(x);
+    auto run_blocks = [&](int g) {
+        for (int k = net.first[g]; k < net.first[g + 1]; k++) {
+            TrainStage &st = net.stages[k];
             st.a.x_in = x; st.a.emb = Bf.emb; st.a.x_out = st.x_out; st.a.grad_out = nullptr;
             ok = ok && train_block(st.a, s);
             x = st.x_out;
         }
     };
     for (int l = 0; l < L; l++) {
-        run_blocks_fwd(enc[l]);
+        run_blocks(l);
         if (l < L - 1) {
-            const std::string p = "down_layers." + std::to_string(l) + ".downsample";
             const size_t M2 = (size_t)B * (res / 2) * (res / 2);
             t_regroup(x, Bf.mcat[l], B, res, C, true, s);
-            t_ln_fwd(Bf.mcat[l], Wt(p + ".norm.weight"), Wt(p + ".norm.bias"), Bf.mnrm[l], Bf.mstats[l], (int)M2, 4 * C, s);
-            lin_fwd(Bf.mnrm[l], Wt(p + ".reduction.weight"), nullptr, Bf.mout[l], M2, 4 * C, 2 * C);
+            t_ln_fwd(Bf.mcat[l], net.mrg_norm[l].w, net.mrg_norm[l].b, Bf.mnrm[l], Bf.mstats[l], (int)M2, 4 * C, s);
+            lin_fwd(Bf.mnrm[l], net.mrg_red[l].w, nullptr, Bf.mout[l], M2, 4 * C, 2 * C, s);
             x = Bf.mout[l]; res /= 2; C *= 2;
         }
-        skip_ptr[l] = x;
+        skip[l] = x;
     }
     for (int i = 0; i < L; i++) {
-        const int lvl = L - 1 - i;
         if (i > 0) {
-            const std::string p = "up_layers." + std::to_string(i) + ".upsample";
             const size_t Mi = (size_t)B * res * res; const int D = 2 * C, Co = D / 4;
-            t_concat(x, skip_ptr[lvl], Bf.ucat[i], Mi, C, s);
-            lin_fwd(Bf.ucat[i], Wt(p + ".pre_linear.weight"), nullptr, Bf.uy[i], Mi, D, D);
-            t_ln_fwd(Bf.uy[i], Wt(p + ".norm.weight"), Wt(p + ".norm.bias"), Bf.un[i], Bf.ustats[i], (int)Mi, D, s);
+            t_concat(x, skip[L - 1 - i], Bf.ucat[i], Mi, C, s);
+            lin_fwd(Bf.ucat[i], net.up_pre[i].w, nullptr, Bf.uy[i], Mi, D, D, s);
+            t_ln_fwd(Bf.uy[i], net.up_norm[i].w, net.up_norm[i].b, Bf.un[i], Bf.ustats[i], (int)Mi, D, s);
             t_regroup(Bf.un[i], Bf.usc[i], B, 2 * res, Co, false, s);   // scatter: fine [4 Mi, Co] <- coarse [Mi, 4 Co]
-            t_ln_fwd(Bf.usc[i], Wt(p + ".post_norm.weight"), Wt(p + ".post_norm.bias"), Bf.upn[i], Bf.upstats[i], (int)(4 * Mi), Co, s);
-            lin_fwd(Bf.upn[i], Wt(p + ".post_linear.weight"), nullptr, Bf.uout[i], 4 * Mi, Co, Co);
+            t_ln_fwd(Bf.usc[i], net.up_pn[i].w, net.up_pn[i].b, Bf.upn[i], Bf.upstats[i], (int)(4 * Mi), Co, s);
+            lin_fwd(Bf.upn[i], net.up_post[i].w, nullptr, Bf.uout[i], 4 * Mi, Co, Co, s);
             x = Bf.uout[i]; res *= 2; C /= 2;
         }
-        run_blocks_fwd(dec[i]);
+        run_blocks(L + i);
     }
-    const float *xL = x;
-    t_ln_fwd(xL, Wt("norm.weight"), Wt("norm.bias"), Bf.fy, Bf.fstats, (int)M0, E, s);
-    t_gemm(false, false, Bf.fy, E, Wt("read_out.0.weight"), E, Wt("read_out.0.bias"), Bf.z1, E, (int)M0, E, E, false, s);   // ConvTranspose2d: [in, out]
-    lin_fwd(Bf.z1, Wt("read_out.1.weight"), Wt("read_out.1.bias"), Bf.z2, M0, E, E);
-    lin_fwd(Bf.z2, Wt("read_out.2.weight"), Wt("read_out.2.bias"), Bf.rep, M0, E, E);
-    lin_fwd(Bf.rep, Wt("readout_adj_mlp.fc1.weight"), Wt("readout_adj_mlp.fc1.bias"), Bf.ha_pre, M0, E, E);
+    net.xL = x;
+    t_ln_fwd(x, net.norm.w, net.norm.b, Bf.fy, Bf.fstats, (int)M0, E, s);
+    t_gemm(false, false, Bf.fy, E, net.ro0.w, E, net.ro0.b, Bf.z1, E, (int)M0, E, E, false, s);   // ConvTranspose2d: [in, out]
+    lin_fwd(Bf.z1, net.ro1.w, net.ro1.b, Bf.z2, M0, E, E, s);
+    lin_fwd(Bf.z2, net.ro2.w, net.ro2.b, Bf.rep, M0, E, E, s);
+    lin_fwd(Bf.rep, net.adj1.w, net.adj1.b, Bf.ha_pre, M0, E, E, s);
     t_gelu(Bf.ha_pre, nullptr, Bf.ha, M0 * E, false, s);
-    lin_fwd(Bf.ha, Wt("readout_adj_mlp.fc2.weight"), Wt("readout_adj_mlp.fc2.bias"), Bf.oa, M0, E, Ca);
-    t_adj_out(Bf.oa, flags, out_F_adj, nullptr, nullptr, B, N, Ca, false, s);
-    launch_pool(Bf.rep, flags, Bf.pool, B, N, E, s);
-    lin_fwd(Bf.pool, Wt("readout_node_mlp.fc1.weight"), Wt("readout_node_mlp.fc1.bias"), Bf.hn_pre, (size_t)B * N, E, E);
+    lin_fwd(Bf.ha, net.adj2.w, net.adj2.b, Bf.oa, M0, E, Ca, s);
+    t_adj_out(Bf.oa, in.flags, out_F.adj, nullptr, nullptr, B, N, Ca, false, s);
+    launch_pool(Bf.rep, in.flags, Bf.pool, B, N, E, s);
+    lin_fwd(Bf.pool, net.node1.w, net.node1.b, Bf.hn_pre, (size_t)B * N, E, E, s);
     t_gelu(Bf.hn_pre, nullptr, Bf.hn, (size_t)B * N * E, false, s);
-    lin_fwd(Bf.hn, Wt("readout_node_mlp.fc2.weight"), Wt("readout_node_mlp.fc2.bias"), Bf.on, (size_t)B * N, E, Cn);
-    t_rowmask(Bf.on, flags, out_F_node, (size_t)B * N, Cn, s);
-    // ================================ backward ================================
-    if (bwd && ok && mid) {
-        const size_t na = (size_t)B * Ca * N * N, nn = (size_t)B * N * Cn;
-        float *mid_buf = train_buf(h, h->train_mid, h->train_mid_cap, na + nn, s);
-        if (!mid_buf) ok = false;
-        else { ok = (*mid)(out_F_adj, out_F_node, mid_buf, mid_buf + na) == DSG_OK; grad_F_adj = mid_buf; grad_F_node = mid_buf + na; }
+    lin_fwd(Bf.hn, net.node2.w, net.node2.b, Bf.on, (size_t)B * N, E, Cn, s);
+    t_rowmask(Bf.on, in.flags, out_F.node, (size_t)B * N, Cn, s);
+    return ok;
+}
+
+// from dF = dL/dF of the forward just run on `net`: TRAIN_WEIGHT_GRADS fills every gradient buffer bound in net.G; TRAIN_INPUT_GRADS
+// (with `ig`) carries activation gradients only and ends in ig->d_tok.  false: a launch was refused
+static bool train_backward(TrainNet &net, TrainBackward mode, const uint8_t *flags, CStatePtrs dF, const TrainInputGrad *ig, hipStream_t s) {
+    const bool wg = mode == TRAIN_WEIGHT_GRADS;
+    const TrainBufs &Bf = net.Bf;
+    const int B = net.B, N = net.N, E = net.E, L = net.L, Ca = net.Ca, Cn = net.Cn, Cin = net.Cin, T0 = N * N;
+    const size_t M0 = net.M0;
+    float *const t_mh = net.t_mh, *const t_m3c = net.t_m3c, *const t_w = net.t_w, *const t_mc = net.t_mc, *const t_mc2 = net.t_mc2;
+    auto skip_size = [&](int l) { return (size_t)B * net.skip_res[l] * net.skip_res[l] * net.skip_C[l]; };
+    hipError_t e0 = (net.grouped || !wg) ? hipSuccess : hipMemsetAsync(Bf.d_emb, 0, sizeof(float) * (size_t)B * NOISE_EMB, s);
+    for (int l = 0; l < L && e0 == hipSuccess; l++) e0 = hipMemsetAsync(Bf.d_skip[l], 0, sizeof(float) * skip_size(l), s);
+    bool ok = e0 == hipSuccess;
+    // heads
+    float *d_on = t_mc, *d_hn = t_mc2, *d_pool = net.d_x, *d_rep = net.d_y;
+    t_rowmask(dF.node, flags, d_on, (size_t)B * N, Cn, s);
+    lin_bwd(wg, Bf.hn, net.node2.w, d_on, d_hn, net.node2.dw, net.node2.db, (size_t)B * N, E, Cn, s);
+    t_gelu(Bf.hn_pre, d_hn, d_hn, (size_t)B * N * E, true, s);
+    lin_bwd(wg, Bf.pool, net.node1.w, d_hn, d_pool, net.node1.dw, net.node1.db, (size_t)B * N, E, E, s);
+    float *d_oa = t_m3c, *d_ha = t_mh;
+    t_adj_out(nullptr, flags, nullptr, dF.adj, d_oa, B, N, Ca, true, s);
+    lin_bwd(wg, Bf.ha, net.adj2.w, d_oa, d_ha, net.adj2.dw, net.adj2.db, M0, E, Ca, s);
+    t_gelu(Bf.ha_pre, d_ha, d_ha, M0 * E, true, s);
+    lin_bwd(wg, Bf.rep, net.adj1.w, d_ha, d_rep, net.adj1.dw, net.adj1.db, M0, E, E, s);
+    t_pool_bwd(d_pool, flags, d_rep, B, N, E, s);
+    // read_out.2, .1 (Conv2d [out,in]) and .0 (ConvTranspose2d [in,out]), final norm
+    float *d_z2 = t_mh, *d_z1 = t_m3c, *d_fy = t_w;
+    lin_bwd(wg, Bf.z2, net.ro2.w, d_rep, d_z2, net.ro2.dw, net.ro2.db, M0, E, E, s);
+    lin_bwd(wg, Bf.z1, net.ro1.w, d_z2, d_z1, net.ro1.dw, net.ro1.db, M0, E, E, s);
+    if (wg) {
+        t_gemm(true, false, Bf.fy, E, d_z1, E, nullptr, net.ro0.dw, E, E, E, (int)M0, false, s);    // dW [in,out] = y^T dz
+        t_colsum(d_z1, E, net.ro0.db, (int)M0, E, s);
     }
-    if (bwd && ok) {
-        hipError_t e0 = (grouped || !wg) ? hipSuccess : hipMemsetAsync(Bf.d_emb, 0, sizeof(float) * (size_t)B * NOISE_EMB, s);
-        for (int l = 0; l < L && e0 == hipSuccess; l++) e0 = hipMemsetAsync(Bf.d_skip[l], 0, sizeof(float) * (size_t)B * skip_res[l] * skip_res[l] * skip_C[l], s);
-        ok = ok && e0 == hipSuccess;
-        // heads
-        float *d_on = t_mc, *d_hn = t_mc2, *d_pool = d_x, *d_rep = d_y;
-        t_rowmask(grad_F_node, flags, d_on, (size_t)B * N, Cn, s);
-        lin_bwd(Bf.hn, Wt("readout_node_mlp.fc2.weight"), d_on, d_hn, Gd("readout_node_mlp.fc2.weight"), Gd("readout_node_mlp.fc2.bias"), (size_t)B * N, E, Cn);
-        t_gelu(Bf.hn_pre, d_hn, d_hn, (size_t)B * N * E, true, s);
-        lin_bwd(Bf.pool, Wt("readout_node_mlp.fc1.weight"), d_hn, d_pool, Gd("readout_node_mlp.fc1.weight"), Gd("readout_node_mlp.fc1.bias"), (size_t)B * N, E, E);
-        float *d_oa = t_m3c, *d_ha = t_mh;
-        t_adj_out(nullptr, flags, nullptr, grad_F_adj, d_oa, B, N, Ca, true, s);
-        lin_bwd(Bf.ha, Wt("readout_adj_mlp.fc2.weight"), d_oa, d_ha, Gd("readout_adj_mlp.fc2.weight"), Gd("readout_adj_mlp.fc2.bias"), M0, E, Ca);
-        t_gelu(Bf.ha_pre, d_ha, d_ha, M0 * E, true, s);
-        lin_bwd(Bf.rep, Wt("readout_adj_mlp.fc1.weight"), d_ha, d_rep, Gd("readout_adj_mlp.fc1.weight"), Gd("readout_adj_mlp.fc1.bias"), M0, E, E);
-        t_pool_bwd(d_pool, flags, d_rep, B, N, E, s);
-        // read_out.2, .1 (Conv2d [out,in]) and .0 (ConvTranspose2d [in,out]), final norm
-        float *d_z2 = t_mh, *d_z1 = t_m3c, *d_fy = t_w;
-        lin_bwd(Bf.z2, Wt("read_out.2.weight"), d_rep, d_z2, Gd("read_out.2.weight"), Gd("read_out.2.bias"), M0, E, E);
-        lin_bwd(Bf.z1, Wt("read_out.1.weight"), d_z2, d_z1, Gd("read_out.1.weight"), Gd("read_out.1.bias"), M0, E, E);
-        if (wg) {
-            t_gemm(true, false, Bf.fy, E, d_z1, E, nullptr, Gd("read_out.0.weight"), E, E, E, (int)M0, false, s);    // dW [in,out] = y^T dz
-            t_colsum(d_z1, E, Gd("read_out.0.bias"), (int)M0, E, s);
+    t_gemm(false, true, d_z1, E, net.ro0.w, E, nullptr, d_fy, E, (int)M0, E, E, false, s);        // dy = dz W^T
+    // blocks / up / down in reverse; dcur: the running gradient wrt the current activation (size up to M0*E*2), ping-pong with dnext
+    float *dcur = net.d_x, *dnext = net.d_y;
+    t_ln_bwd(net.xL, net.norm.w, Bf.fstats, d_fy, nullptr, dcur, net.norm.dw, net.norm.db, (int)M0, E, s);
+    auto run_blocks = [&](int g) {
+        for (int k = net.first[g + 1] - 1; k >= net.first[g]; k--) {
+            TrainStage &st = net.stages[k];
+            TrainBlockArgs &a = st.a;
+            a.grad_out = dcur; a.grad_in = dnext; a.grad_emb = st.d_emb;
+            a.d_x1 = t_w; a.t_mc = t_mc; a.t_mc2 = t_mc2; a.t_m3c = t_m3c; a.t_mh = t_mh;
+            a.no_wgrad = !wg;
+            ok = ok && train_block_backward(a, s);
+            if (!net.grouped && wg) t_add(Bf.d_emb, st.d_emb, (size_t)B * NOISE_EMB, s);
+            std::swap(dcur, dnext);
         }
-        t_gemm(false, true, d_z1, E, Wt("read_out.0.weight"), E, nullptr, d_fy, E, (int)M0, E, E, false, s);        // dy = dz W^T
-        float *dx = d_x;   // running gradient wrt the current activation x (size up to M0*E*2)
-        t_ln_bwd(xL, Wt("norm.weight"), Bf.fstats, d_fy, nullptr, dx, Gd("norm.weight"), Gd("norm.bias"), (int)M0, E, s);
-        // blocks / up / down in reverse
-        float *dcur = dx, *dnext = d_y;   // ping-pong
-        auto run_blocks_bwd = [&](std::vector<Stage> &v) {
-            for (int k = (int)v.size() - 1; k >= 0; k--) {
-                Stage &st = v[k];
-                TrainBlockArgs &a = st.a;
-                const size_t M = (size_t)B * a.res * a.res, Cc = a.C, H = a.hidden;
-                a.grad_out = dcur; a.grad_in = dnext; a.grad_emb = st.d_emb;
-                a.d_x1 = t_w; a.t_mc = t_mc; a.t_mc2 = t_mc2; a.t_m3c = t_m3c; a.t_mh = t_mh;
-                a.no_wgrad = !wg;
-                (void)M; (void)Cc; (void)H;
-                ok = ok && train_block_backward(a, s);
-                if (!a.aff_grouped && wg) t_add(Bf.d_emb, st.d_emb, (size_t)B * NOISE_EMB, s);
-                std::swap(dcur, dnext);
-            }
+    };
+    int res = N, C = E;
+    for (int i = L - 1; i >= 0; i--) {
+        run_blocks(L + i);
+        if (i > 0) {
+            // here res, C are the FINE values (after the breakup); the coarse input had res/2, 2C per source
+            const int rc = res / 2, Cc = 2 * C; const size_t Mi = (size_t)B * rc * rc; const int D = 2 * Cc, Co = D / 4;
+            float *d_upn = t_mh, *d_usc = t_m3c, *d_un = t_w, *d_uy = t_mh, *d_cat = t_m3c;
+            lin_bwd(wg, Bf.upn[i], net.up_post[i].w, dcur, d_upn, net.up_post[i].dw, nullptr, 4 * Mi, Co, Co, s);
+            t_ln_bwd(Bf.usc[i], net.up_pn[i].w, Bf.upstats[i], d_upn, nullptr, d_usc, net.up_pn[i].dw, net.up_pn[i].db, (int)(4 * Mi), Co, s);
+            t_regroup(d_usc, d_un, B, res, Co, true, s);   // transpose of the scatter = gather
+            t_ln_bwd(Bf.uy[i], net.up_norm[i].w, Bf.ustats[i], d_un, nullptr, d_uy, net.up_norm[i].dw, net.up_norm[i].db, (int)Mi, D, s);
+            lin_bwd(wg, Bf.ucat[i], net.up_pre[i].w, d_uy, d_cat, net.up_pre[i].dw, nullptr, Mi, D, D, s);
+            t_split(d_cat, dnext, Bf.d_skip[L - 1 - i], Mi, Cc, s);
+            std::swap(dcur, dnext);
+            res = rc; C = Cc;
+        }
+    }
+    for (int l = L - 1; l >= 0; l--) {
+        // the tensor at the end of encoder level l (after its merging, if any) also fed the decoder as skip[l]
+        t_add(dcur, Bf.d_skip[l], skip_size(l), s);
+        if (l < L - 1) {
+            const int rf = res * 2, Cf = C / 2; const size_t M2 = (size_t)B * res * res;
+            float *d_nrm = t_mh, *d_cat = t_m3c;
+            lin_bwd(wg, Bf.mnrm[l], net.mrg_red[l].w, dcur, d_nrm, net.mrg_red[l].dw, nullptr, M2, 4 * Cf, 2 * Cf, s);
+            t_ln_bwd(Bf.mcat[l], net.mrg_norm[l].w, Bf.mstats[l], d_nrm, nullptr, d_cat, net.mrg_norm[l].dw, net.mrg_norm[l].db, (int)M2, 4 * Cf, s);
+            t_regroup(d_cat, dnext, B, rf, Cf, false, s);   // transpose of the gather = scatter back to the fine grid
+            std::swap(dcur, dnext);
+            res = rf; C = Cf;
+        }
+        run_blocks(l);
+    }
+    // PatchEmbed: modulate <- LN <- 1x1 conv (the inputs are leaves of the training entries; dsg_precond_vjp goes on to them)
+    float *d_pe_ln = dnext, *d_pe_lin = t_mh;
+    t_modulate(Bf.pe_ln, Bf.pe_aff, dcur, d_pe_ln, Bf.pe_daff, B, T0, E, true, s);
+    if (!wg) {
+        // (sigma is not differentiated: the affine linears' own backward feeds parameter gradients and d_emb only)
+    } else if (net.grouped) {
+        // the affine linears' own backward, all at once: dWa_z = d_aff_z^T emb, d_ba_z = colsum(d_aff_z), d_emb = sum_z d_aff_z Wa_z
+        TGemmGroup gw, gb, ge;
+        // (d_emb: every product into its own [B, 512] buffer -- 16 x 2 tiles per product fill the chip, one shared output would
+        // leave it to 32 blocks -- then one ordered sum)
+        auto add = [&](const float *d_aff, const float *Wa, float *dWa, float *dba, float *d_emb_z, int C2) {
+            gw.p[gw.n++] = TGemmProb{d_aff, Bf.emb, nullptr, dWa, C2, NOISE_EMB, NOISE_EMB, C2, NOISE_EMB, B};
+            gb.p[gb.n++] = TGemmProb{d_aff, nullptr, nullptr, dba, C2, 0, 0, B, C2, 0};
+            ge.p[ge.n++] = TGemmProb{d_aff, Wa, nullptr, d_emb_z, C2, NOISE_EMB, NOISE_EMB, B, NOISE_EMB, C2};
         };
-        res = N; C = E;
-        for (int i = L - 1; i >= 0; i--) {
-            const int lvl = L - 1 - i;
-            run_blocks_bwd(dec[i]);
-            if (i > 0) {
-                // here res, C are the FINE values (after the breakup); the coarse input had res/2, 2C per source
-                const std::string p = "up_layers." + std::to_string(i) + ".upsample";
-                const int rc = res / 2, Cc = 2 * C; const size_t Mi = (size_t)B * rc * rc; const int D = 2 * Cc, Co = D / 4;
-                float *d_upn = t_mh, *d_usc = t_m3c, *d_un = t_w, *d_uy = t_mh, *d_cat = t_m3c;
-                lin_bwd(Bf.upn[i], Wt(p + ".post_linear.weight"), dcur, d_upn, Gd(p + ".post_linear.weight"), nullptr, 4 * Mi, Co, Co);
-                t_ln_bwd(Bf.usc[i], Wt(p + ".post_norm.weight"), Bf.upstats[i], d_upn, nullptr, d_usc, Gd(p + ".post_norm.weight"), Gd(p + ".post_norm.bias"),
-                         (int)(4 * Mi), Co, s);
-                t_regroup(d_usc, d_un, B, res, Co, true, s);   // transpose of the scatter = gather
-                t_ln_bwd(Bf.uy[i], Wt(p + ".norm.weight"), Bf.ustats[i], d_un, nullptr, d_uy, Gd(p + ".norm.weight"), Gd(p + ".norm.bias"), (int)Mi, D, s);
-                lin_bwd(Bf.ucat[i], Wt(p + ".pre_linear.weight"), d_uy, d_cat, Gd(p + ".pre_linear.weight"), nullptr, Mi, D, D);
-                t_split(d_cat, dnext, Bf.d_skip[lvl], Mi, Cc, s);
-                std::swap(dcur, dnext);
-                res = rc; C = Cc;
-            }
-        }
-        for (int l = L - 1; l >= 0; l--) {
-            // the tensor at the end of encoder level l (after its merging, if any) also fed the decoder as skip[l]
-            if (l < L - 1 || true) t_add(dcur, Bf.d_skip[l], (size_t)B * skip_res[l] * skip_res[l] * skip_C[l], s);
-            if (l < L - 1) {
-                const std::string p = "down_layers." + std::to_string(l) + ".downsample";
-                const int rf = res * 2, Cf = C / 2; const size_t M2 = (size_t)B * res * res;
-                float *d_nrm = t_mh, *d_cat = t_m3c;
-                lin_bwd(Bf.mnrm[l], Wt(p + ".reduction.weight"), dcur, d_nrm, Gd(p + ".reduction.weight"), nullptr, M2, 4 * Cf, 2 * Cf);
-                t_ln_bwd(Bf.mcat[l], Wt(p + ".norm.weight"), Bf.mstats[l], d_nrm, nullptr, d_cat, Gd(p + ".norm.weight"), Gd(p + ".norm.bias"), (int)M2, 4 * Cf, s);
-                t_regroup(d_cat, dnext, B, rf, Cf, false, s);   // transpose of the gather = scatter back to the fine grid
-                std::swap(dcur, dnext);
-                res = rf; C = Cf;
-            }
-            run_blocks_bwd(enc[l]);
-        }
-        // PatchEmbed: modulate <- LN <- 1x1 conv (the inputs are leaves of the training entries; dsg_precond_vjp goes on to them)
-        float *d_pe_ln = dnext, *d_pe_lin = t_mh;
-        t_modulate(Bf.pe_ln, Bf.pe_aff, dcur, d_pe_ln, Bf.pe_daff, B, T0, E, true, s);
-        if (!wg) {
-            // (sigma is not differentiated: the affine linears' own backward feeds parameter gradients and d_emb only)
-        } else if (grouped) {
-            // the affine linears' own backward, all at once: dWa_z = d_aff_z^T emb, d_ba_z = colsum(d_aff_z), d_emb = sum_z d_aff_z Wa_z
-            TGemmGroup gw, gb, ge;
-            // (d_emb: every product into its own [B, 512] buffer -- 16 x 2 tiles per product fill the chip, one shared output would
-            // leave it to 32 blocks -- then one ordered sum)
-            auto add = [&](const float *d_aff, const float *Wa, float *dWa, float *dba, float *d_emb_z, int C2) {
-                gw.p[gw.n++] = TGemmProb{d_aff, Bf.emb, nullptr, dWa, C2, NOISE_EMB, NOISE_EMB, C2, NOISE_EMB, B};
-                gb.p[gb.n++] = TGemmProb{d_aff, nullptr, nullptr, dba, C2, 0, 0, B, C2, 0};
-                ge.p[ge.n++] = TGemmProb{d_aff, Wa, nullptr, d_emb_z, C2, NOISE_EMB, NOISE_EMB, B, NOISE_EMB, C2};
-            };
-            add(Bf.pe_daff, Wt("patch_embed.affine.weight"), Gd("patch_embed.affine.weight"), Gd("patch_embed.affine.bias"), Bf.pe_demb, 2 * E);
-            for (Stage *st : all_stages) add(st->a.d_aff, st->a.W.aff_w, st->a.G.aff_w, st->a.G.aff_b, st->d_emb, 2 * st->a.C);
-            t_gemm_grouped(true, false, false, gw, s);
-            t_colsum_grouped(gb, s);
-            t_gemm_grouped(false, false, false, ge, s);
-            t_sum_grouped(ge, Bf.d_emb, B * NOISE_EMB, s);
-        } else {
-            t_gemm(true, false, Bf.pe_daff, 2 * E, Bf.emb, NOISE_EMB, nullptr, Gd("patch_embed.affine.weight"), NOISE_EMB, 2 * E, NOISE_EMB, B, false, s);
-            t_colsum(Bf.pe_daff, 2 * E, Gd("patch_embed.affine.bias"), B, 2 * E, s);
-            t_gemm(false, false, Bf.pe_daff, 2 * E, Wt("patch_embed.affine.weight"), NOISE_EMB, nullptr, Bf.d_emb, NOISE_EMB, B, NOISE_EMB, 2 * E, true, s);
-        }
-        t_ln_bwd(Bf.pe_lin, Wt("patch_embed.norm.weight"), Bf.pe_stats, d_pe_ln, nullptr, d_pe_lin, Gd("patch_embed.norm.weight"), Gd("patch_embed.norm.bias"),
-                 (int)M0, E, s);
-        if (!wg) {
-            // d_tok = d_pe_lin W_img: only the columns of the current adjacency / node values, the weight image zero-padded to x32 columns
-            // (sigma is not differentiated: no noise-embedding backward)
-            t_live_cols(Wt("patch_embed.proj.weight"), Cin, ig->img, E, Ca, Cn, h->cfg.self_condition != 0, s);
-            t_gemm(false, false, d_pe_lin, E, ig->img, ig->ld, nullptr, ig->d_tok, ig->ld, (int)M0, ig->ld, E, false, s);
-        } else {
-            lin_bwd(Bf.tok, Wt("patch_embed.proj.weight"), d_pe_lin, nullptr, Gd("patch_embed.proj.weight"), Gd("patch_embed.proj.bias"), M0, Cin, E);
-            // noise embedding: emb = silu(map1(silu(map0(pe))))
-            float *d_m1 = t_mc, *d_s0 = t_mc2;
-            t_silu(Bf.m1, Bf.d_emb, d_m1, (size_t)B * NOISE_EMB, true, s);
-            lin_bwd(Bf.s0, Wt("map_layer1.weight"), d_m1, d_s0, Gd("map_layer1.weight"), Gd("map_layer1.bias"), B, NOISE_EMB, NOISE_EMB);
-            t_silu(Bf.m0, d_s0, d_s0, (size_t)B * NOISE_EMB, true, s);
-            lin_bwd(Bf.pe, Wt("map_layer0.weight"), d_s0, nullptr, Gd("map_layer0.weight"), Gd("map_layer0.bias"), B, E, NOISE_EMB);
-        }
+        add(Bf.pe_daff, net.pe_aff.w, net.pe_aff.dw, net.pe_aff.db, Bf.pe_demb, 2 * E);
+        for (const TrainStage &st : net.stages) add(st.a.d_aff, st.a.W.aff_w, st.a.G.aff_w, st.a.G.aff_b, st.d_emb, 2 * st.a.C);
+        t_gemm_grouped(true, false, false, gw, s);
+        t_colsum_grouped(gb, s);
+        t_gemm_grouped(false, false, false, ge, s);
+        t_sum_grouped(ge, Bf.d_emb, B * NOISE_EMB, s);
+    } else {   // each block has added its own d_emb above; PatchEmbed's affine accumulates into the same sum
+        t_gemm(true, false, Bf.pe_daff, 2 * E, Bf.emb, NOISE_EMB, nullptr, net.pe_aff.dw, NOISE_EMB, 2 * E, NOISE_EMB, B, false, s);
+        t_colsum(Bf.pe_daff, 2 * E, net.pe_aff.db, B, 2 * E, s);
+        t_gemm(false, false, Bf.pe_daff, 2 * E, net.pe_aff.w, NOISE_EMB, nullptr, Bf.d_emb, NOISE_EMB, B, NOISE_EMB, 2 * E, true, s);
     }
-    // everything is queued on the caller's stream and every buffer involved outlives the call (caller's or the handle's): no
-    // synchronisation here -- the host runs ahead into the optimiser step's launches
+    t_ln_bwd(Bf.pe_lin, net.pe_norm.w, Bf.pe_stats, d_pe_ln, nullptr, d_pe_lin, net.pe_norm.dw, net.pe_norm.db, (int)M0, E, s);
+    if (!wg) {
+        // d_tok = d_pe_lin W_img: only the columns of the current adjacency / node values, the weight image zero-padded to x32 columns
+        // (sigma is not differentiated: no noise-embedding backward)
+        t_live_cols(net.pe.w, Cin, ig->img, E, Ca, Cn, net.self_condition != 0, s);
+        t_gemm(false, false, d_pe_lin, E, ig->img, ig->ld, nullptr, ig->d_tok, ig->ld, (int)M0, ig->ld, E, false, s);
+    } else {
+        lin_bwd(wg, Bf.tok, net.pe.w, d_pe_lin, nullptr, net.pe.dw, net.pe.db, M0, Cin, E, s);
+        // noise embedding: emb = silu(map1(silu(map0(pe))))
+        float *d_m1 = t_mc, *d_s0 = t_mc2;
+        t_silu(Bf.m1, Bf.d_emb, d_m1, (size_t)B * NOISE_EMB, true, s);
+        lin_bwd(wg, Bf.s0, net.map1.w, d_m1, d_s0, net.map1.dw, net.map1.db, B, NOISE_EMB, NOISE_EMB, s);
+        t_silu(Bf.m0, d_s0, d_s0, (size_t)B * NOISE_EMB, true, s);
+        lin_bwd(wg, Bf.pe, net.map0.w, d_s0, nullptr, net.map0.dw, net.map0.db, B, E, NOISE_EMB, s);
+    }
+    return ok;
+}
+
+// the end of every entry: everything is queued on the caller's stream and every buffer involved outlives the call (caller's or the
+// handle's), so there is no synchronisation here -- the host runs ahead into the optimiser step's launches
+static int train_finish(dsg_handle h, bool ok, hipStream_t s) {
     HIP_TRY(h, hipGetLastError());
     if (!ok) return fail(h, DSG_ERR_HIP, "a training kernel failed to launch");
     if (t_scratch_failed(s, true)) return fail(h, DSG_ERR_HIP, "out of memory (training scratch of this stream)");
     return DSG_OK;
 }
 
+extern "C" {
+
 int dsg_train_grads(dsg_handle h, int32_t B, const float *in_adj, const float *in_node, const uint8_t *flags, const float *c_noise,
                     const float *sc_adj, const float *sc_node, const float *grad_F_adj, const float *grad_F_node, float *out_F_adj,
                     float *out_F_node, int32_t n_params, const char *const *names, float *const *grad_params, void *stream) {
-    return train_grads_core(h, B, in_adj, in_node, flags, c_noise, sc_adj, sc_node, grad_F_adj, grad_F_node, nullptr, out_F_adj, out_F_node,
-                            n_params, names, grad_params, stream);
+    // the training form reads the raw weights only, so weights re-uploaded after an optimiser step need no re-packing here
+    // (dsg_finalize_weights must have run once: block plans); the sampling-path entries still insist on `finalized`
+    if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (B < 1 || !in_adj || !in_node || !flags || !c_noise || !out_F_adj || !out_F_node) return fail(h, DSG_ERR_INVALID, "null argument");
+    const bool bwd = grad_F_adj != nullptr;
+    if (bwd && (!grad_F_node || !names || !grad_params)) return fail(h, DSG_ERR_INVALID, "backward needs both output gradients and the parameter gradient buffers");
+    hipStream_t s = (hipStream_t)stream;
+    TrainNet net{};
+    const int rc = train_net_build(h, net, B, sc_adj, sc_node, bwd, n_params, names, grad_params, s);
+    if (rc != DSG_OK) return rc;
+    bool ok = train_forward(net, TrainInputs{in_adj, in_node, flags, c_noise, sc_adj, sc_node}, StatePtrs{out_F_adj, out_F_node}, s);
+    if (ok && bwd) ok = train_backward(net, TRAIN_WEIGHT_GRADS, flags, CStatePtrs{grad_F_adj, grad_F_node}, nullptr, s);
+    return train_finish(h, ok, s);
+}
+
+// the preconditioned entries' handle-owned io buffer: c_in x, c_noise, the network's F, dL/dD and dL/dF
+namespace {
+struct TrainIo { float *in_a, *in_n, *cn, *F_a, *F_n, *dD_a, *dD_n, *dF_a, *dF_n; };
+}
+static bool train_io(dsg_handle h, int B, hipStream_t s, TrainIo &io) {
+    const size_t na = (size_t)B * h->Ca * h->N * h->N, nn = (size_t)B * h->N * h->Cn;
+    return train_carve(h->train_io, s, [&](TArena &A) {
+        io.in_a = A.get(na); io.in_n = A.get(nn); io.cn = A.get(B); io.F_a = A.get(na); io.F_n = A.get(nn);
+        io.dD_a = A.get(na); io.dD_n = A.get(nn); io.dF_a = A.get(na); io.dF_n = A.get(nn);
+    });
 }
 
 int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const float *noisy_node, const uint8_t *flags, const float *sigmas,
@@ -3613,28 +3667,27 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
         return fail(h, DSG_ERR_INVALID, "null argument");
     hipStream_t s = (hipStream_t)stream;
     const Dims d = dims_of(h, B);
-    const size_t na = (size_t)B * h->Ca * h->N * h->N, nn = (size_t)B * h->N * h->Cn;
-    // in_adj | in_node | c_noise | F_adj | F_node | dL/dD (adj, node): handle-owned, kept between calls
-    float *buf = train_buf(h, h->train_io, h->train_io_cap, 3 * na + 3 * nn + (size_t)B + 64, s);
-    if (!buf) return fail(h, DSG_ERR_HIP, "out of memory");
-    float *in_a = buf, *in_n = in_a + na, *cn = in_n + nn, *F_a = cn + ((B + 63) / 64) * 64, *F_n = F_a + na, *tmp = F_n + nn;
-    launch_precond_in(CStatePtrs{noisy_adj, noisy_node}, sigmas, StatePtrs{in_a, in_n}, cn, d, s);   // c_in * x, c_noise = ln(sigma)/4
-    const TrainMid mid = [&](const float *Fa, const float *Fn, float *dFa, float *dFn) -> int {
-        // D = mask(c_skip x + c_out F) (precond.py:101-104); per-sample losses; dL/dD; dL/dF = c_out dL/dD
-        launch_precond_out(CStatePtrs{noisy_adj, noisy_node}, CStatePtrs{Fa, Fn}, sigmas, flags, StatePtrs{out_D_adj, out_D_node},
-                           StatePtrs{nullptr, nullptr}, d, s);
-        launch_rainbow_loss(CStatePtrs{out_D_adj, out_D_node}, CStatePtrs{target_adj, target_node}, flags, loss_weight, edge_loss_weight,
-                            node_loss_weight, iou_loss_weight, iou_loss_type, out_loss_adj, out_loss_node, d, s);
-        launch_rainbow_loss_backward(CStatePtrs{out_D_adj, out_D_node}, CStatePtrs{target_adj, target_node}, flags, loss_weight,
-                                     edge_loss_weight, node_loss_weight, iou_loss_weight, iou_loss_type, sigmas, StatePtrs{tmp, tmp + na},
-                                     StatePtrs{dFa, dFn}, d, s);
-        return hipGetLastError() == hipSuccess ? DSG_OK : DSG_ERR_HIP;
-    };
+    const CStatePtrs noisy{noisy_adj, noisy_node}, target{target_adj, target_node}, D{out_D_adj, out_D_node};
     const bool want_grads = names && grad_params && n_params > 0;
-    int rc = train_grads_core(h, B, in_a, in_n, flags, cn, sc_adj, sc_node, nullptr, nullptr, want_grads ? &mid : nullptr, F_a, F_n, n_params, names,
-                              grad_params, stream);
-    if (rc == DSG_OK && !want_grads) rc = mid(F_a, F_n, in_a, in_n);   // forward only: still report D and the losses (gradients discarded)
-    return rc;
+    TrainIo io;
+    if (!train_io(h, B, s, io)) return fail(h, DSG_ERR_HIP, "out of memory");
+    launch_precond_in(noisy, sigmas, StatePtrs{io.in_a, io.in_n}, io.cn, d, s);   // c_in * x, c_noise = ln(sigma)/4
+    TrainNet net{};
+    const int rc = train_net_build(h, net, B, sc_adj, sc_node, want_grads, n_params, names, grad_params, s);
+    if (rc != DSG_OK) return rc;
+    bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, sc_adj, sc_node}, StatePtrs{io.F_a, io.F_n}, s);
+    if (ok) {
+        // D = mask(c_skip x + c_out F) (precond.py:101-104); per-sample losses; with gradients: dL/dD and dL/dF = c_out dL/dD
+        launch_precond_out(noisy, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, StatePtrs{nullptr, nullptr}, d, s);
+        launch_rainbow_loss(D, target, flags, loss_weight, edge_loss_weight, node_loss_weight, iou_loss_weight, iou_loss_type, out_loss_adj,
+                            out_loss_node, d, s);
+        if (want_grads)
+            launch_rainbow_loss_backward(D, target, flags, loss_weight, edge_loss_weight, node_loss_weight, iou_loss_weight, iou_loss_type, sigmas,
+                                         StatePtrs{io.dD_a, io.dD_n}, StatePtrs{io.dF_a, io.dF_n}, d, s);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (ok && want_grads) ok = train_backward(net, TRAIN_WEIGHT_GRADS, flags, CStatePtrs{io.dF_a, io.dF_n}, nullptr, s);
+    return train_finish(h, ok, s);
 }
 
 int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const float *noisy_node, const uint8_t *flags, const float *sigmas,
@@ -3643,14 +3696,15 @@ int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const f
     if (B < 1 || !noisy_adj || !noisy_node || !flags || !sigmas || !out_sc_adj || !out_sc_node) return fail(h, DSG_ERR_INVALID, "null argument");
     hipStream_t s = (hipStream_t)stream;
     const Dims d = dims_of(h, B);
-    const size_t na = (size_t)B * h->Ca * h->N * h->N, nn = (size_t)B * h->N * h->Cn;
-    float *buf = train_buf(h, h->train_io, h->train_io_cap, 3 * na + 3 * nn + (size_t)B + 64, s);
-    if (!buf) return fail(h, DSG_ERR_HIP, "out of memory");
-    float *in_a = buf, *in_n = in_a + na, *cn = in_n + nn, *F_a = cn + ((B + 63) / 64) * 64, *F_n = F_a + na;
-    launch_precond_in(CStatePtrs{noisy_adj, noisy_node}, sigmas, StatePtrs{in_a, in_n}, cn, d, s);
-    const int rc = train_grads_core(h, B, in_a, in_n, flags, cn, nullptr, nullptr, nullptr, nullptr, nullptr, F_a, F_n, 0, nullptr, nullptr, stream);
+    TrainIo io;
+    if (!train_io(h, B, s, io)) return fail(h, DSG_ERR_HIP, "out of memory");
+    launch_precond_in(CStatePtrs{noisy_adj, noisy_node}, sigmas, StatePtrs{io.in_a, io.in_n}, io.cn, d, s);
+    TrainNet net{};
+    int rc = train_net_build(h, net, B, nullptr, nullptr, false, 0, nullptr, nullptr, s);
     if (rc != DSG_OK) return rc;
-    launch_precond_out(CStatePtrs{noisy_adj, noisy_node}, CStatePtrs{F_a, F_n}, sigmas, flags, StatePtrs{out_sc_adj, out_sc_node},
+    const bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, nullptr, nullptr}, StatePtrs{io.F_a, io.F_n}, s);
+    if ((rc = train_finish(h, ok, s)) != DSG_OK) return rc;
+    launch_precond_out(CStatePtrs{noisy_adj, noisy_node}, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_sc_adj, out_sc_node},
                        StatePtrs{nullptr, nullptr}, d, s);
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
@@ -3667,34 +3721,38 @@ int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node
     hipStream_t s = (hipStream_t)stream;
     const Dims d = dims_of(h, B);
     const int N = h->N, Ca = h->Ca, Cn = h->Cn, E = h->E;
-    const size_t na = (size_t)B * Ca * N * N, nn = (size_t)B * N * Cn, M0 = (size_t)B * N * N;
+    const size_t M0 = (size_t)B * N * N;
     // refused before anything is enqueued: what the last kernel (t_assemble_bwd) cannot take
     if (!t_assemble_bwd_ok(Cn) || (size_t)B * N > 0x7fffffffu)
         return fail(h, DSG_ERR_INVALID, "input gradients are not built for C_node %d (partial sums beyond LDS) or B * N = %zu", Cn, (size_t)B * N);
     const int Np = t_live_cols_width(Ca, Cn);
-    // in_adj | in_node | c_noise | F_adj | F_node: the training entries' handle-owned buffer (same layout); d_tok | W_img | coef: its own
-    float *buf = train_buf(h, h->train_io, h->train_io_cap, 3 * na + 3 * nn + (size_t)B + 64, s);
-    float *vb = train_buf(h, h->train_vjp, h->train_vjp_cap, M0 * Np + (size_t)E * Np + 2 * (size_t)B + 64, s);
-    if (!buf || !vb) return fail(h, DSG_ERR_HIP, "out of memory");
-    float *in_a = buf, *in_n = in_a + na, *cn = in_n + nn, *F_a = cn + ((B + 63) / 64) * 64, *F_n = F_a + na;
-    TrainInputGrad ig{vb, vb + M0 * Np, Np};
-    float *coef = ig.img + (size_t)E * Np;
-    launch_precond_in(CStatePtrs{adj, node}, sigmas, StatePtrs{in_a, in_n}, cn, d, s);
-    int cb_rc = 0;
+    TrainIo io;
+    TrainInputGrad ig{nullptr, nullptr, Np};
+    float *coef = nullptr;   // c_skip [B] | c_in [B], left by t_precond_bwd for t_assemble_bwd
+    if (!train_io(h, B, s, io) ||
+        !train_carve(h->train_vjp, s, [&](TArena &A) { ig.d_tok = A.get(M0 * Np); ig.img = A.get((size_t)E * Np); coef = A.get(2 * (size_t)B); }))
+        return fail(h, DSG_ERR_HIP, "out of memory");
+    launch_precond_in(CStatePtrs{adj, node}, sigmas, StatePtrs{io.in_a, io.in_n}, io.cn, d, s);
+    TrainNet net{};
+    int rc = train_net_build(h, net, B, sc_adj, sc_node, false, 0, nullptr, nullptr, s);
+    if (rc != DSG_OK) return rc;
+    bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, sc_adj, sc_node}, StatePtrs{io.F_a, io.F_n}, s);
     const float *g_a = grad_D_adj, *g_n = grad_D_node;
-    const TrainMid mid = [&](const float *Fa, const float *Fn, float *dFa, float *dFn) -> int {
-        launch_precond_out(CStatePtrs{adj, node}, CStatePtrs{Fa, Fn}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, StatePtrs{nullptr, nullptr}, d, s);
+    if (ok) {
+        launch_precond_out(CStatePtrs{adj, node}, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, StatePtrs{nullptr, nullptr}, d, s);
         if (fn) {   // the callee enqueues g = dL/dD into the gradient outputs, which the last kernel below turns into the result in place
-            cb_rc = fn(user, out_D_adj, out_D_node, out_grad_adj, out_grad_node);
-            if (cb_rc != 0) return DSG_ERR_INVALID;
+            const int cb_rc = fn(user, out_D_adj, out_D_node, out_grad_adj, out_grad_node);
+            if (cb_rc != 0) {
+                (void)hipGetLastError();   // a launch error so far is this call's, not the next one's
+                return fail(h, DSG_ERR_INVALID, "the gradient callback returned %d: no backward kernel was launched", cb_rc);
+            }
             g_a = out_grad_adj; g_n = out_grad_node;
         }
-        t_precond_bwd(g_a, g_n, sigmas, flags, dFa, dFn, coef, B, N, Ca, Cn, s);
-        return hipGetLastError() == hipSuccess ? DSG_OK : DSG_ERR_HIP;
-    };
-    const int rc = train_grads_core(h, B, in_a, in_n, flags, cn, sc_adj, sc_node, nullptr, nullptr, &mid, F_a, F_n, 0, nullptr, nullptr, stream, &ig);
-    if (cb_rc != 0) return fail(h, DSG_ERR_INVALID, "the gradient callback returned %d: no backward kernel was launched", cb_rc);
-    if (rc != DSG_OK) return rc;
+        t_precond_bwd(g_a, g_n, sigmas, flags, io.dF_a, io.dF_n, coef, B, N, Ca, Cn, s);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (ok) ok = train_backward(net, TRAIN_INPUT_GRADS, flags, CStatePtrs{io.dF_a, io.dF_n}, &ig, s);
+    if ((rc = train_finish(h, ok, s)) != DSG_OK) return rc;
     if (!t_assemble_bwd(ig.d_tok, Np, flags, coef, coef + B, g_a, g_n, out_grad_adj, out_grad_node, B, N, Ca, Cn, false, s))
         return fail(h, DSG_ERR_INVALID, "the assemble backward refused B %d, N %d, C_adj %d, C_node %d, pitch %d", B, N, Ca, Cn, Np);
     HIP_TRY(h, hipGetLastError());
