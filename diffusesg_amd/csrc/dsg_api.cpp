@@ -114,6 +114,11 @@ struct Workspace {
     // what stage_flags last wrote (dedup_stage_mode below): the DedupMode of the lists, the levels whose fill is trimmed (bit k) and the
     // chain depth the trimming was worked out for -- forward_fixed checks that it reaches exactly that depth
     int dd_mode = DD_OFF, dd_trim = 0, dd_depth = 0;
+    // the sampler's table of pure-window rows (option "dedup_table", build_pure_table below): one entry per schedule index, tab_pure_cap
+    // of them; allocated by the first sampler call that shares one representative across this batch size, grown like the handle's tab_*
+    float *tab_pure = nullptr;
+    int tab_pure_cap = 0;
+    size_t tab_pure_bytes = 0;
     size_t need_ints = 0;
     NeedPlan need;
 };
@@ -171,6 +176,7 @@ struct dsg_handle_s {
     bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_opts_on below)
     int opt_dedup_batch = 1;          // ... and once for the whole batch in the sampler: 0 never, 1 from DEDUP_BATCH_MIN graphs, 2 always (dedup_stage_mode below)
     int opt_dedup_levels = 0;         // how many levels may do so: 0 every qualifying one, 1 the finest only, ... (dedup_levels below)
+    bool opt_dedup_table = true;      // where the batch shares one representative: take it from a per-step table built ahead of the loop (build_pure_table below)
     PrunePlan prune;
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
     std::vector<int> prof_list;
@@ -688,6 +694,7 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     h->opt_dedup_masked = env_on("DSG_DEDUP_MASKED", true);
     if (getenv("DSG_DEDUP_BATCH")) h->opt_dedup_batch = std::min(2, std::max(0, atoi(getenv("DSG_DEDUP_BATCH"))));
     if (getenv("DSG_DEDUP_LEVELS")) h->opt_dedup_levels = std::max(0, atoi(getenv("DSG_DEDUP_LEVELS")));
+    h->opt_dedup_table = env_on("DSG_DEDUP_TABLE", true);
     if (getenv("DSG_FUSED_MLP_MAXC")) h->opt_fused_mlp_maxc = atoi(getenv("DSG_FUSED_MLP_MAXC"));
     h->opt_gemm_bf16 = env_on("DSG_GEMM_BF16", false);
     h->opt_bf16_pipe = env_on("DSG_BF16_PIPE", true);
@@ -719,6 +726,7 @@ void dsg_destroy(dsg_handle h) {
     for (auto &kv : h->ws) {
         if (kv.second->cap_stream) (void)hipStreamDestroy(kv.second->cap_stream);
         for (void *p : kv.second->allocs) (void)hipFree(p);
+        if (kv.second->tab_pure) (void)hipFree(kv.second->tab_pure);
     }
     delete h;
     if (--g_live_handles == 0) { (void)hipDeviceSynchronize(); t_scratch_release(); }
@@ -1041,7 +1049,7 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
         size_t off = 0;
         for (int k = 0; k < nl; k++) { w->need.list_off[k] = (int)off; off += (size_t)B * prune_plan(h).items[k] + 16; }
         const bool dd = w->need.dd_n > 0;
-        w->need_ints = off + nl + (size_t)B * nl + (size_t)B * w->need.dd_n;
+        w->need_ints = off + nl + (size_t)B * nl + (size_t)B * w->need.dd_n + (dd ? 1 : 0);   // (+ the mode the lists were written for, behind dd_rep)
         if (int rc = dev_alloc(h, w->allocs, &q, sizeof(int) * w->need_ints)) return rc;
         HIP_TRY(h, hipMemset(q, 0, sizeof(int) * w->need_ints));   // counts of 0 until the first flags are staged
         w->need_lists = (int *)q; w->need_cnt = w->need_lists + off; w->need_cnt_ps = w->need_cnt + nl;
@@ -1196,6 +1204,8 @@ bool merge_fused_at(dsg_handle h, int B, int l) {
 //   of them go through precond_tab, which sets w->uniform).  From DEDUP_BATCH_MIN graphs by default: below 16 graphs no down-path
 //   list launch of the N = 64 network exceeds half a round of 512 resident GEMM tiles, so fewer rows buy no time there -- and the
 //   per-graph lists stay what small batches always had.  Results are bit-identical either way.
+//   Where the batch shares one representative the sampler takes it from a table it builds ahead of the loop, one entry per schedule
+//   index (DD_TABLE, option "dedup_table", build_pure_table): the window's rows depend on the weights and the step's row only.
 //   Trimming (bit k of *trim): level k's fill may leave out what nobody reads only when every later reader of its activation,
 //   statistics and skip goes through a list -- level k + 1 is deduplicated by the same forward (its merge takes the run list) and,
 //   from level 1 on, the up stage reads the skip through a coarse list (levels 0 .. k then have single unshifted blocks, down and up
@@ -1224,7 +1234,7 @@ int dedup_chain_depth(dsg_handle h, const Workspace *w) {
     return depth;
 }
 constexpr int DEDUP_BATCH_MIN = 16;
-int dedup_stage_mode(dsg_handle h, const Workspace *w, bool zero_padded, bool uniform_row, int *trim, int *depth) {
+int dedup_stage_mode(dsg_handle h, const Workspace *w, bool zero_padded, bool uniform_row, int *trim, int *depth, bool table = false) {
     *trim = 0; *depth = 0;
     if (!zero_padded) return DD_OFF;
     const int d = dedup_chain_depth(h, w);
@@ -1233,7 +1243,8 @@ int dedup_stage_mode(dsg_handle h, const Workspace *w, bool zero_padded, bool un
     const PrunePlan &pp = prune_plan(h);
     for (int k = 0; k + 1 < d; k++)
         if (k == 0 || pp.coarse[h->L - k] >= 0) *trim |= 1 << k;
-    return DD_BATCH;
+    // `table`: the caller has built this call's table of pure-window rows (sample_impl): nothing computes the shared representative
+    return table && h->opt_dedup_table && w->tab_pure ? DD_TABLE : DD_BATCH;
 }
 struct NeedRef { const int *list = nullptr, *cnt = nullptr; int id = -1; };
 NeedRef need_ref(dsg_handle h, const Workspace *w, int id) {
@@ -1646,9 +1657,28 @@ void forward_fixed_bx(dsg_handle h, Workspace *w, hipStream_t s) {
     readout_stage(h, w, s);
 }
 
+// One entry of the sampler's table of pure-window rows (kernels.h, "The table"; build_pure_table): per level of the plan's chain the 64
+// rows of x, from level 1 on the same rows of the skip, and room for the rows' (sum, sumsq) pairs at their widest
+struct PureTabLayout { size_t stride = 0; int off_x[1 + NEED_MAX_DD_UP] = {}, off_skip[1 + NEED_MAX_DD_UP] = {}, off_st[1 + NEED_MAX_DD_UP] = {}; };
+PureTabLayout pure_tab_layout(dsg_handle h) {
+    PureTabLayout t;
+    int o = 0;
+    for (int k = 0; k < prune_plan(h).np.dd_n; k++) {
+        const int C = h->E << k;
+        t.off_x[k] = o; o += 64 * C;
+        t.off_skip[k] = o; if (k > 0) o += 64 * C;
+        t.off_st[k] = o; o += 64 * 2 * ((C + 95) / 96);
+    }
+    t.stride = (size_t)o;
+    return t;
+}
+// a forward that builds table entries: w->aff holds one staged (scale, shift) row per graph, the forward returns behind the first
+// block of level `stop` and stores window 0 of the first n graphs at every level up to there as entries dst[0 .. n)
+struct TabBuild { int stop; float *dst; int n; };
+
 // DiffuseSG.forward on the workspace's fixed buffers: (in_adj,in_node,sc_*,flags,c_noise) -> (f_adj,f_node)
-void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
-    if (bx_on(h)) { forward_fixed_bx(h, w, s); return; }
+void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s, const TabBuild *tb = nullptr) {
+    if (bx_on(h)) { if (tb) plan_fail(h, "dedup_table: no table of pure-window rows in the bf16 pipeline"); else forward_fixed_bx(h, w, s); return; }
     // the fused PatchMerging writes the coarser level into the other activation buffer and swaps the two names; put them back
     // on every exit so that each forward (and each captured graph) starts from the same assignment
     struct SwapGuard { Workspace *w; float *x, *y; ~SwapGuard() { w->x = x; w->y = y; } } swap_guard{w, w->x, w->y};
@@ -1656,15 +1686,16 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
     char name[64];
     GemmArgs g;
     w->aff_ld = w->uniform ? 0 : h->aff_n;
-    if (!w->uniform) {
+    if (!w->uniform && !tb) {
         // noise embedding (diffusesg.py:768-771) and every block's (scale,shift) in one GEMM
         embed_rows(h, w->c_noise, B, w->pe, w->emb0, w->emb, w->aff, s);
     }
+    const PureTabLayout ptl = pure_tab_layout(h);
     // pure-window deduplication of levels 0 .. depth - 1: the producer of level l's input (PatchEmbed, or the merge into the level) and
     // the level's first block take its unique lists, then the copy fills the other pure windows
     const int depth = dedup_chain_depth(h, w);
     // lists with one representative for the batch were trimmed for one chain depth and hold for batch-uniform forwards only
-    if (depth > 0 && w->dd_mode == DD_BATCH && !g_dry_run) {
+    if (depth > 0 && (w->dd_mode == DD_BATCH || w->dd_mode == DD_TABLE) && !g_dry_run) {
         if (depth != w->dd_depth) plan_fail(h, "dedup_batch: the forward deduplicates %d levels, the lists were staged for %d", depth, w->dd_depth);
         if (!w->uniform) plan_fail(h, "dedup_batch: a forward with per-sample noise labels under lists shared across the batch");
     }
@@ -1690,8 +1721,20 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s) {
             const int parts = bo.premod ? (C + 95) / 96 : bo.stats_parts;
             if (dd) {
                 const NeedRef cp = need_ref(h, w, w->need.dd_copy[l]);
+                // (lists written under DD_TABLE: from the table entry of the running step; the launch is the same either way)
+                PureTabSrc pt;
+                if (w->tab_pure && !tb)
+                    pt = PureTabSrc{w->tab_pure, ptl.stride, w->tab_pure_cap, ptl.off_x[l], ptl.off_skip[l], ptl.off_st[l], h->tab_step, w->ctl,
+                                    w->dd_rep + (size_t)w->need.dd_n * B};
                 P_KERN(PK_ELEM, 0.0, launch_window_broadcast(w->x, l ? w->skips[l - 1] : nullptr, parts > 0 ? w->stats : nullptr, parts, B, res, C,
-                                                             cp.list, cp.cnt, w->dd_rep + (size_t)l * B, s));
+                                                             cp.list, cp.cnt, w->dd_rep + (size_t)l * B, s, pt));
+                if (tb)
+                    P_KERN(PK_ELEM, 0.0, launch_window_harvest(w->x, l ? w->skips[l - 1] : nullptr, parts > 0 ? w->stats : nullptr, parts, tb->n, res, C,
+                                                               tb->dst, ptl.stride, ptl.off_x[l], ptl.off_skip[l], ptl.off_st[l], s));
+            }
+            if (tb && j == 0 && l == tb->stop) {
+                if (!dd) plan_fail(h, "dedup_table: level %d is not deduplicated by this forward", l);
+                return;
             }
             if (j == 0 && l <= NEED_MAX_DD_UP && !g_dry_run) w->dd_fwd[l] = dd ? (parts > 0 ? 1 : 0) : -1;
             snprintf(name, sizeof(name), "down%d.block%d", l, (int)j);
@@ -1844,9 +1887,12 @@ int check_ready(dsg_handle h, int B) {
 // endpoint is zero (the sampler: its state only ever comes from its own masking kernels) -- the pure-window deduplication's condition
 // uniform_row: ... and that every one of those forwards reads the batch-uniform (scale, shift) row: one representative may then serve
 // the whole batch (dedup_stage_mode)
-int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s, bool zero_padded = false, bool uniform_row = false) {
-    HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)w->B * h->N, hipMemcpyDeviceToDevice, s));
-    w->dd_mode = dedup_stage_mode(h, w, zero_padded, uniform_row, &w->dd_trim, &w->dd_depth);
+// table: ... and that it has built the table of pure-window rows for every schedule index those forwards run at (build_pure_table)
+// flags == nullptr: the lists of the flags the workspace holds
+int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s, bool zero_padded = false, bool uniform_row = false,
+                bool table = false) {
+    if (flags) HIP_TRY(h, hipMemcpyAsync(w->flags, flags, (size_t)w->B * h->N, hipMemcpyDeviceToDevice, s));
+    w->dd_mode = dedup_stage_mode(h, w, zero_padded, uniform_row, &w->dd_trim, &w->dd_depth, table);
     if (w->need_lists)
         launch_need_lists(w->flags, w->B, h->N, w->need, w->need_cnt_ps, w->need_lists, w->need_cnt, s, w->dd_mode, w->dd_rep, w->dd_trim);
     return 0;
@@ -2035,11 +2081,12 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     size_t need = 0;   // the need lists of the masked-token pruning: every list + 16 pad entries, counts, per-sample counts
     const PrunePlan &pp = prune_plan(h);
     for (int k = 0; k < pp.np.n_lists; k++) need += sizeof(int) * ((size_t)B * pp.items[k] + 16 + 1 + (size_t)B);
-    need += sizeof(int) * (size_t)B * pp.np.dd_n;   // the representative windows of the pure-window deduplication
+    need += sizeof(int) * ((size_t)B * pp.np.dd_n + (pp.np.dd_n > 0 ? 1 : 0));   // the representative windows of the pure-window deduplication, the lists' mode
     auto it = h->ws.find(B);   // + the known tensors and masks of dsg_sample_known, once a conditioned call has allocated them
     const size_t known = it != h->ws.end() ? it->second->known_bytes : 0;
     const size_t seeds = it != h->ws.end() ? it->second->seeds_bytes : 0;   // + the graph seeds, once a seeded call has allocated them
-    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need + known + seeds;
+    const size_t pure = it != h->ws.end() ? it->second->tab_pure_bytes : 0;   // + the table of pure-window rows, once a sampler call has built one
+    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need + known + seeds + pure;
 }
 
 int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
@@ -2074,6 +2121,12 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         // acts where the lists are written (stage_flags) and nowhere else: the launches, their grids and the list addresses are the
         // same for every value, so the captured graphs stay -- one captured under either kind of list replays under the other
         h->opt_dedup_batch = value < 0 ? 0 : (value > 2 ? 2 : value);
+        return DSG_OK;
+    }
+    else if (n == "dedup_table") {
+        // likewise: the step bodies are the same for both values -- the fill launch always carries the table's address (growing the
+        // table drops them) and reads on the device which kind of list the last staging wrote
+        h->opt_dedup_table = value != 0;
         return DSG_OK;
     }
     else if (n == "batch_invariant") h->opt_batch_invariant = value != 0;
@@ -2122,6 +2175,7 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "dedup_masked") *value = dedup_opts_on(h);   // what runs (in the sampler): 0 wherever the pruning is off, or the fused C = 96 kernels are
     else if (n == "dedup_levels") *value = dedup_levels(h);   // what runs (in the sampler, where PatchMerging takes its partial-statistics form)
     else if (n == "dedup_batch") *value = dedup_opts_on(h) ? h->opt_dedup_batch : 0;   // what runs (in the sampler; 1: from 16 graphs)
+    else if (n == "dedup_table") *value = dedup_opts_on(h) && h->opt_dedup_batch > 0 && h->opt_dedup_table;   // what runs (in the sampler, where the batch shares one representative)
     else if (n == "batch_invariant") *value = h->opt_batch_invariant;
     else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
     else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
@@ -2298,6 +2352,54 @@ namespace {
 // the caller's known tensors and element masks of a conditioned run
 struct KnownArgs { const float *adj, *node; const uint8_t *mask_adj, *mask_node; };
 
+// The table of pure-window rows (option "dedup_table").  The representative window that a batch shares at every level of
+// the chain is a function of the weights and of the step's (scale, shift) row: its inputs are zero whatever the sample holds.  So it is
+// computed here for all T schedule indices, before the loop, by the down path itself: pseudo-batches of B all-padding graphs -- graph
+// g of a chunk reads row c0 + g of tab_aff, per-sample (aff_ld = aff_n) -- staged per graph (every graph's window 0 is its one unique
+// window at every level), run as far as the first block of the top chain level, window 0 of every graph harvested level by level.
+// Enqueued eagerly on the caller's stream behind embed_rows; leaves flags, lists and inputs of the pseudo-batch in the workspace:
+// the caller stages its own flags again.  Grows like the tab_* buffers (the step bodies bake the address).
+int build_pure_table(dsg_handle h, Workspace *w, int T, hipStream_t s) {
+    const int B = w->B, depth = dedup_chain_depth(h, w);
+    const PureTabLayout ptl = pure_tab_layout(h);
+    if (depth < 1 || ptl.stride == 0) return fail(h, DSG_ERR_STATE, "dedup_table: no chain to build a table for");
+    if (w->tab_pure_cap < T) {
+        drop_graphs(h);
+        w->bytes -= w->tab_pure_bytes;
+        if (w->tab_pure) { (void)hipFree(w->tab_pure); w->tab_pure = nullptr; }
+        w->tab_pure_cap = 0; w->tab_pure_bytes = 0;
+        HIP_TRY(h, hipMalloc((void **)&w->tab_pure, sizeof(float) * ptl.stride * (size_t)T));
+        w->tab_pure_cap = T;
+        w->tab_pure_bytes = sizeof(float) * ptl.stride * (size_t)T;
+        w->bytes += w->tab_pure_bytes;
+    }
+    const size_t sa = (size_t)B * h->Ca * h->N * h->N, sn = (size_t)B * h->N * h->Cn;
+    // the pseudo-batch's forwards are per-sample ones without a self-conditioning input; the workspace's host-side word on the kind
+    // of its next forward goes back to what it was on every exit: a call whose step bodies are all replayed sets none of it again,
+    // and an eager forward behind that call (dsg_profile_forward) must find the sampler's batch-uniform form
+    struct FormGuard { Workspace *w; bool uniform; const float *sca, *scn; const int *hs;
+                       ~FormGuard() { w->uniform = uniform; w->cur_sc_adj = sca; w->cur_sc_node = scn; w->cur_has_sc = hs; } }
+        form_guard{w, w->uniform, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc};
+    HIP_TRY(h, hipMemsetAsync(w->flags, 0, (size_t)B * h->N, s));
+    if (int rc = stage_flags(h, w, nullptr, s, /*zero_padded=*/true, /*uniform_row=*/false)) return rc;
+    HIP_TRY(h, hipMemsetAsync(w->in_adj, 0, sizeof(float) * sa, s));
+    HIP_TRY(h, hipMemsetAsync(w->in_node, 0, sizeof(float) * sn, s));
+    w->cur_sc_adj = nullptr; w->cur_sc_node = nullptr; w->cur_has_sc = nullptr;
+    w->uniform = false;
+    const size_t row = sizeof(float) * (size_t)h->aff_n;
+    for (int c0 = 0; c0 < T; c0 += B) {
+        const int n = std::min(B, T - c0);
+        HIP_TRY(h, hipMemcpyAsync(w->aff, h->tab_aff + (size_t)c0 * h->aff_n, row * n, hipMemcpyDeviceToDevice, s));
+        for (int g = n; g < B; g++)   // a short last chunk: the other graphs repeat its last row (computed, not harvested)
+            HIP_TRY(h, hipMemcpyAsync(w->aff + (size_t)g * h->aff_n, h->tab_aff + (size_t)(T - 1) * h->aff_n, row, hipMemcpyDeviceToDevice, s));
+        const TabBuild tb{depth - 1, w->tab_pure + (size_t)c0 * ptl.stride, n};
+        forward_fixed(h, w, s, &tb);
+        if (int rc = plan_status(h, w)) return rc;
+    }
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
 // dsg_sample (known == nullptr), dsg_sample_known, dsg_sample_walk and dsg_sample_seeded (graph_seeds != nullptr: per-graph noise
 // streams; `seed` then only draws the coins): one reverse loop.  walk == nullptr is the trivial walk (every
 // schedule index once, from pure noise); base_* (a walk's partial-noise start) only reaches the init kernel.
@@ -2396,13 +2498,27 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
         volatile float t_prime = t_hat[i] + hs[i];  // alpha = 1 (edm.py:391)
         rows[k] = StepRow{coef[k], t_hat[i], 1.0f / t_hat[i], 1.0f / t_prime, hs[i], i, ms_coef[k], 0};
     }
-    RunCtl ctl_host{0, 0, (unsigned long long)seed, noise_adj, noise_node, graph_seeds ? w->gseeds : nullptr};   // nothing sticky: rewritten by every run
+    hipEvent_t tab_ev[2] = {nullptr, nullptr};
+    RunCtl ctl_host{0, L, (unsigned long long)seed, noise_adj, noise_node, graph_seeds ? w->gseeds : nullptr};   // nothing sticky: rewritten by every run
     HIP_TRY(h, hipMemcpyAsync(h->tab_step, rows.data(), sizeof(StepRow) * L, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(w->ctl, &ctl_host, sizeof(RunCtl), hipMemcpyHostToDevice, s));
     if (!gt_adj) {
         HIP_TRY(h, hipMemcpyAsync(h->tab_sig, t_hat.data(), sizeof(float) * T, hipMemcpyHostToDevice, s));
         launch_cnoise(h->tab_sig, h->tab_cn, T, s);
         embed_rows(h, h->tab_cn, T, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff, s);
+        // where the batch shares one representative pure window per level, that window comes from a table with one entry per schedule
+        // index, built now from the rows of tab_aff; then the caller's flags again, with lists that leave the window to the fill
+        if (h->opt_dedup_table && w->dd_mode == DD_BATCH) {
+            const bool verbose = getenv("DSG_TABLE_VERBOSE") != nullptr;   // measurement: HIP events around the build of this call
+            if (verbose) {
+                HIP_TRY(h, hipEventCreate(&tab_ev[0]));
+                HIP_TRY(h, hipEventCreate(&tab_ev[1]));
+                HIP_TRY(h, hipEventRecord(tab_ev[0], s));
+            }
+            if (int rc = build_pure_table(h, w, T, s)) return rc;
+            if (int rc = stage_flags(h, w, flags, s, /*zero_padded=*/true, /*uniform_row=*/true, /*table=*/true)) return rc;
+            if (verbose) HIP_TRY(h, hipEventRecord(tab_ev[1], s));
+        }
     }
     if (known) {
         // the known tensors and masks move into workspace-owned buffers: conditioned step bodies bake these addresses and must not
@@ -2426,6 +2542,12 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
         HIP_TRY(h, hipMemcpyAsync(w->km_node, known->mask_node, sn, hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(h, hipStreamSynchronize(s));  // the host vectors above must outlive their async copies; once per sample() call
+    if (tab_ev[1]) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, tab_ev[0], tab_ev[1]);
+        fprintf(stderr, "[dsg-table] B=%d T=%d: table of pure-window rows built in %.1f us (%zu bytes)\n", B, T, ms * 1e3, w->tab_pure_bytes);
+    }
+    for (hipEvent_t e : tab_ev) if (e) (void)hipEventDestroy(e);
     // the static plan of every executed step (edm.py:350-427): buffer rotation (it simply continues across a jump: the
     // self-conditioning input is the last denoised estimate, whichever level it came from), Euler/Heun/multistep update, the pre-drawn coins
     std::vector<StepPlan> plans(L);
@@ -2630,8 +2752,15 @@ int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_ro
     return DSG_OK;
 }
 
-int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
-                                int32_t *rep, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// launch_side: the device lists as they are -- what the launches and the fill iterate; counts[3] = the DedupMode they were written for.
+// Otherwise the unique windows and the fills by meaning: under DD_TABLE the window the table stands for (rep) is listed with the unique
+// windows and runs, where DD_BATCH computes it, and not with the fills
+int dedup_level_lists(dsg_handle h, int32_t B, int32_t level, bool launch_side, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
+                      int32_t *rep, void *stream) {
     if (int rc = check_ready(h, B)) return rc;
     if (!counts || level < 0) return fail(h, DSG_ERR_INVALID, "null argument or negative level");
     auto it = h->ws.find(B);
@@ -2650,8 +2779,38 @@ int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t 
         counts[k] = cnt[ids[k]];
         if (dst[k]) memcpy(dst[k], all.data() + w->need.list_off[ids[k]], sizeof(int) * (size_t)counts[k]);
     }
-    if (rep) memcpy(rep, all.data() + (w->dd_rep - w->need_lists) + (size_t)level * B, sizeof(int) * (size_t)B);
+    const int *reps = all.data() + (w->dd_rep - w->need_lists);
+    const int mode = reps[(size_t)w->need.dd_n * B], r = reps[(size_t)level * B];
+    if (rep) memcpy(rep, reps + (size_t)level * B, sizeof(int) * (size_t)B);
+    if (launch_side) { counts[3] = mode; return DSG_OK; }
+    if (mode == DD_TABLE && r >= 0) {
+        const int res = h->N >> level, nwr = res / 8, nW = nwr * nwr, b = r / nW, v = r - b * nW;
+        if (wins) wins[counts[0]] = r;
+        counts[0] += 1;
+        for (int p = 0; p < 8; p++)
+            if (runs) runs[counts[1] + p] = b * res * nwr + ((v / nwr) * 8 + p) * nwr + v % nwr;
+        counts[1] += 8;
+        const int *cl = all.data() + w->need.list_off[ids[2]];
+        int n = 0;
+        for (int k = 0; k < counts[2]; k++)
+            if (cl[k] != r) { if (copy) copy[n] = cl[k]; n++; }
+        counts[2] = n;
+    }
     return DSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
+                                int32_t *rep, void *stream) {
+    return dedup_level_lists(h, B, level, false, counts, wins, runs, copy, rep, stream);
+}
+
+int dsg_debug_dedup_launch_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
+                                 void *stream) {
+    return dedup_level_lists(h, B, level, true, counts, wins, runs, copy, nullptr, stream);
 }
 
 int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream) {

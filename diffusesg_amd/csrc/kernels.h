@@ -215,10 +215,11 @@ struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_
                       dd_copy[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}; };
 static_assert(sizeof(NeedPlan) == sizeof(int) * (2 + 4 * NEED_MAX_OPS + NEED_MAX_LISTS + 1 + 3 * (1 + NEED_MAX_DD_UP)), "NeedPlan is a kernel argument: keep it packed");
 // cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
-// dedup (a DedupMode) / dd_rep / trim_mask: see below (dd_rep [plan.dd_n][B]; may be null when the plan has no dd_* lists)
+// dedup (a DedupMode) / dd_rep / trim_mask: see below (dd_rep [plan.dd_n][B] + 1 int, the mode; may be null when the plan has no dd_* lists)
 enum DedupMode { DD_OFF = 0,      // every window is listed as unique, nothing is copied
                  DD_GRAPH = 1,    // one representative pure window per graph
-                 DD_BATCH = 2 };  // one for the whole batch ("One representative for the batch" below)
+                 DD_BATCH = 2,    // one for the whole batch ("One representative for the batch" below)
+                 DD_TABLE = 3 };  // DD_BATCH with that one taken from a per-step table instead of being computed ("The table" below)
 void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan, int *cnt_ps, int *lists, int *cnt, hipStream_t s,
                        int dedup = DD_OFF, int *dd_rep = nullptr, int trim_mask = 0);
 
@@ -245,6 +246,12 @@ void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan,
 // up path reads level k's skip through a coarse list (which stays inside non-pure windows below a chain of unshifted single blocks).
 // A level without the bit (the top of the chain, whose next reader takes everything) fills every other pure window.  Chain premise:
 // every fine window under a unique coarse window is unique or filled, whichever graphs the representatives lie in.
+// The table (DD_TABLE, option "dedup_table").  The batch's representative depends on the weights and the step's (scale, shift) row only,
+// so the sampler computes it once per schedule index ahead of the loop (PureTab: per index and level the 64 rows of x, of the skip and
+// their (sum, sumsq) pairs).  The lists are DD_BATCH's with the representative moved from the unique lists to the fill list: dd_wins /
+// dd_runs hold the non-pure windows only, dd_copy every pure window DD_BATCH fills plus the former representative (dd_rep still names
+// it), and the fill reads the table entry of the running step's schedule index.  need_lists_kernel leaves the mode the lists were
+// written for in dd_rep[dd_n * B], where the fill reads it: the launches are the same for every mode.
 // The merge into such a level, over its run list: merged row m = (b, i, j) of y [B * (res / 2)^2, 4 C] = the LayerNorm(4 C) (no affine:
 // gamma / beta are folded into the reduction weight) of cat[x(2i,2j), x(2i+1,2j), x(2i,2j+1), x(2i+1,2j+1)], statistics from the four
 // fine rows' (sum, sumsq) partials ln_part [B * res^2][nparts][2] -- element for element the value the gather form of the GEMM
@@ -253,8 +260,19 @@ void launch_merge_norm_runs(const float *x, const float *ln_part, int nparts, fl
                             const int *run_cnt, hipStream_t s);
 // The copy of level k: rows of x [B * res * res, C], of skip (same shape; null: none -- level 0 has no skip yet) and nparts (sum, sumsq)
 // pairs per row of stats (null: none); rep [B] = that level's representatives (global window ids, of any graph).  C % 4 == 0
+// tab: where *tab.mode == DD_TABLE every listed window is filled from the table entry of schedule index steps[ctl->step].sched
+// instead (base null: no table, the mode is never DD_TABLE).  An entry is `stride` floats: per level 64 x C rows of x at off_x, of
+// the skip at off_skip and 64 x nparts pairs at off_st, window tokens in row-major order.  entries = the table's capacity (the index
+// is clamped to it, and the step to ctl->n_steps - 1: an eager forward behind a finished run reads the last step's entry)
+struct StepRow;
+struct RunCtl;
+struct PureTabSrc { const float *base = nullptr; size_t stride = 0; int entries = 0, off_x = 0, off_skip = 0, off_st = 0;
+                    const StepRow *steps = nullptr; const RunCtl *ctl = nullptr; const int *mode = nullptr; };
 void launch_window_broadcast(float *x, float *skip, float *stats, int nparts, int B, int res, int C, const int *copy_list,
-                             const int *copy_cnt, const int *rep, hipStream_t s);
+                             const int *copy_cnt, const int *rep, hipStream_t s, const PureTabSrc &tab = PureTabSrc());
+// Building the table: window 0 of each of the first n graphs -> entry g of dst (the layout above; skip / stats null: not stored)
+void launch_window_harvest(const float *x, const float *skip, const float *stats, int nparts, int n, int res, int C, float *dst,
+                           size_t stride, int off_x, int off_skip, int off_st, hipStream_t s);
 
 // ---- preconditioning / sampler elementwise kernels (adj and node parts handled in one launch) ----
 struct StatePtrs { float *adj; float *node; };
@@ -289,9 +307,10 @@ void launch_init_base_seeded(CStatePtrs init, CStatePtrs base, float scale, cons
 // ms_coef = c_k of the second-order multistep update (launch_multistep_tab); 0 in every row of every other step, where no kernel reads it.
 struct StepRow { float noise_coef, sigma, inv_t, inv_tp, h; int sched; float ms_coef; int pad; };
 static_assert(sizeof(StepRow) == 32, "StepRow is 32 bytes");
-// Per-run control block at a fixed device address: the step counter the kernels index StepRow[] / the noise streams with.
+// Per-run control block at a fixed device address: the step counter the kernels index StepRow[] / the noise streams with, and the
+// number of executed steps of the run (rows of StepRow[]).
 // graph_seeds: null -- one key (`seed`) and the global element index; device [B] (a seeded run) -- per-graph keys and local indices
-struct RunCtl { int step; int pad; unsigned long long seed; const float *noise_adj; const float *noise_node; const unsigned long long *graph_seeds; };
+struct RunCtl { int step; int n_steps; unsigned long long seed; const float *noise_adj; const float *noise_node; const unsigned long long *graph_seeds; };
 // x_hat = mask(x + coef[step]*eps), eps = recorded noise[step] (ctl->noise_*) or Philox(seed, step+1) / Philox(graph_seeds[b], step+1)
 void launch_churn_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs xhat, Dims d, hipStream_t s);
 // in = c_in(sigma[step]) * x

@@ -2840,9 +2840,12 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
     // (graph, window) order, found by every block for itself from the flags of all graphs -- B * N bytes, the same answer in every
     // block and in both phases -- and the fill of a level whose bit is set in trim_mask lists only the pure windows under a unique
     // window of level k + 1.
+    // DD_TABLE (kernels.h, "The table"): DD_BATCH's lists with that window moved from the unique lists to the fill list -- nothing
+    // computes it, the fill writes it like every other pure window that is read.
     if (plan.dd_n > 0) {
         uint8_t *pure = map_a, *runs = map_b;   // the walk above is over: its maps are free
-        if (dedup == DD_BATCH) {
+        const bool batch = dedup == DD_BATCH || dedup == DD_TABLE, table = dedup == DD_TABLE;
+        if (batch) {
             __syncthreads();
             if (tid < plan.dd_n) rep_all[tid] = 0x7fffffff;
             __syncthreads();
@@ -2880,13 +2883,13 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             __syncthreads();
             if (tid == 0) {   // the representative: the graph's first pure window; DD_BATCH: the batch's, where it lies in this graph
                 int r = -1;
-                if (dedup == DD_BATCH) { if (rep_all[k] >= b * nW && rep_all[k] < (b + 1) * nW) r = rep_all[k] - b * nW; }
+                if (batch) { if (rep_all[k] >= b * nW && rep_all[k] < (b + 1) * nW) r = rep_all[k] - b * nW; }
                 else for (int w = 0; w < nW && r < 0; w++) if (pure[w]) r = w;
                 rep_s = r;
             }
             __syncthreads();
             const int rep = rep_s;
-            for (int w = tid; w < nW; w += 256) win[w] = (!pure[w] || w == rep) ? 1 : 0;
+            for (int w = tid; w < nW; w += 256) win[w] = (!pure[w] || (w == rep && !table)) ? 1 : 0;
             __syncthreads();
             emit(win, nW, l_wins, b * nW);
             for (int idx = tid; idx < res * nwr; idx += 256) {   // run (i, jr) lies in window (i / 8, jr)
@@ -2895,9 +2898,9 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             }
             __syncthreads();
             emit(runs, res * nwr, l_runs, b * res * nwr);
-            const bool trim = dedup == DD_BATCH && ((trim_mask >> k) & 1) && k + 1 < plan.dd_n;
+            const bool trim = batch && ((trim_mask >> k) & 1) && k + 1 < plan.dd_n;
             for (int w = tid; w < nW; w += 256) {
-                bool fill = pure[w] && w != rep;
+                bool fill = pure[w] && (w != rep || table);
                 if (fill && trim) {   // only under a unique window of level k + 1: a non-pure one, or that level's representative
                     const int pi = (w / nwr) >> 1, pj = (w % nwr) >> 1, nwr1 = nwr / 2;
                     const bool up_valid = (blk_any[2 * pi] || blk_any[2 * pi + 1]) && (blk_any[2 * pj] || blk_any[2 * pj + 1]);
@@ -2908,10 +2911,12 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             __syncthreads();
             emit(win, nW, l_copy, b * nW);
             if (PHASE == 1 && tid == 0) {
-                if (dedup == DD_BATCH) dd_rep[(size_t)k * B + b] = rep_all[k] == 0x7fffffff ? -1 : rep_all[k];
+                if (batch) dd_rep[(size_t)k * B + b] = rep_all[k] == 0x7fffffff ? -1 : rep_all[k];
                 else dd_rep[(size_t)k * B + b] = rep < 0 ? -1 : b * nW + rep;
             }
         }
+        if (PHASE == 1 && b == 0 && tid == 0) dd_rep[(size_t)plan.dd_n * B] = dedup;   // what the fills of these lists read from
+
     }
 }
 
@@ -2928,22 +2933,43 @@ void launch_need_lists(const uint8_t *flags, int B, int N, const NeedPlan &plan,
 // at or beyond *copy_cnt, and entries or sources outside [0, B * nW), return.  Sources are unique windows and never listed for a fill,
 // so one launch needs no ordering inside.  C4 > 0: C / 4 at compile time (level 0's C = 96: the division by a constant measured 0.4 -
 // 0.5 us of that 7 us launch); 0: the run-time value.
+// Lists written under DD_TABLE (tab.mode): the source is the table entry of the running step's schedule index, whose rows lie in
+// window order -- the same 64 rows, statistics and skip rows the batch's representative would have held (kernels.h, "The table").
 template <int C4>
 __global__ __launch_bounds__(256) void window_broadcast_kernel(float *__restrict__ x, float *__restrict__ skip, float *__restrict__ stats,
                                                                int nparts, int B, int res, int C, const int *__restrict__ copy_list,
-                                                               const int *__restrict__ copy_cnt, const int *__restrict__ rep) {
+                                                               const int *__restrict__ copy_cnt, const int *__restrict__ rep, PureTabSrc tab) {
     const int k = blockIdx.x, tid = threadIdx.x;
     if (k >= *copy_cnt) return;
     const int nwr = res / 8, nW = nwr * nwr;
     const int dst = copy_list[k];
     if (dst < 0 || dst >= B * nW) return;
-    const int b = dst / nW, src = rep[b];
+    const int b = dst / nW;
+    const int dw = dst - b * nW;
+    const size_t d0 = (size_t)b * res * res + (size_t)(dw / nwr) * 8 * res + (dw % nwr) * 8;   // first token of the window
+    const int c4n = C4 > 0 ? C4 : C / 4;
+    if (tab.base && *tab.mode == DD_TABLE) {
+        const int st = max(0, min(tab.ctl->step, tab.ctl->n_steps - 1));
+        const float *e = tab.base + (size_t)max(0, min(tab.steps[st].sched, tab.entries - 1)) * tab.stride;
+        for (int p = tid; p < 64 * c4n; p += 256) {
+            const int t = p / c4n, c = p - c4n * t;
+            const size_t off = (size_t)(t >> 3) * res + (t & 7);
+            *reinterpret_cast<f32x4 *>(x + (d0 + off) * C + 4 * c) = *reinterpret_cast<const f32x4 *>(e + tab.off_x + (size_t)t * C + 4 * c);
+            if (skip) *reinterpret_cast<f32x4 *>(skip + (d0 + off) * C + 4 * c) = *reinterpret_cast<const f32x4 *>(e + tab.off_skip + (size_t)t * C + 4 * c);
+        }
+        if (stats)
+            for (int p = tid; p < 64 * nparts; p += 256) {
+                const int t = p / nparts, c = p - nparts * t;
+                const size_t off = (size_t)(t >> 3) * res + (t & 7);
+                *reinterpret_cast<float2 *>(stats + 2 * ((d0 + off) * nparts + c)) = *reinterpret_cast<const float2 *>(e + tab.off_st + 2 * (t * nparts + c));
+            }
+        return;
+    }
+    const int src = rep[b];
     if (src < 0 || src >= B * nW || src == dst) return;
     const int sb = src / nW;   // the source's graph: b, or with one representative for the batch any graph
-    const int dw = dst - b * nW, sw = src - sb * nW;
-    const size_t d0 = (size_t)b * res * res + (size_t)(dw / nwr) * 8 * res + (dw % nwr) * 8;   // first token of the window
+    const int sw = src - sb * nW;
     const size_t s0 = (size_t)sb * res * res + (size_t)(sw / nwr) * 8 * res + (sw % nwr) * 8;
-    const int c4n = C4 > 0 ? C4 : C / 4;
     for (int p = tid; p < 64 * c4n; p += 256) {
         const int t = p / c4n, c = p - c4n * t;
         const size_t off = (size_t)(t >> 3) * res + (t & 7);   // token t = (row t / 8, column t % 8) of the window
@@ -2959,10 +2985,39 @@ __global__ __launch_bounds__(256) void window_broadcast_kernel(float *__restrict
 }
 
 void launch_window_broadcast(float *x, float *skip, float *stats, int nparts, int B, int res, int C, const int *copy_list,
-                             const int *copy_cnt, const int *rep, hipStream_t s) {
+                             const int *copy_cnt, const int *rep, hipStream_t s, const PureTabSrc &tab) {
     const dim3 grid(B * (res / 8) * (res / 8));
-    if (C == 96) DSG_LAUNCH(window_broadcast_kernel<24>, grid, dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep);
-    else DSG_LAUNCH(window_broadcast_kernel<0>, grid, dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep);
+    if (C == 96) DSG_LAUNCH(window_broadcast_kernel<24>, grid, dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep, tab);
+    else DSG_LAUNCH(window_broadcast_kernel<0>, grid, dim3(256), 0, s, x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep, tab);
+}
+
+// Building the table of pure-window rows (kernels.h, "The table"): block g stores window 0 of graph g -- the graph's representative in
+// an all-padding pseudo-batch -- as entry g of dst, tokens in window order.
+__global__ __launch_bounds__(256) void window_harvest_kernel(const float *__restrict__ x, const float *__restrict__ skip,
+                                                             const float *__restrict__ stats, int nparts, int res, int C,
+                                                             float *__restrict__ dst, size_t stride, int off_x, int off_skip, int off_st) {
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const size_t s0 = (size_t)g * res * res;
+    float *e = dst + (size_t)g * stride;
+    const int c4n = C / 4;
+    for (int p = tid; p < 64 * c4n; p += 256) {
+        const int t = p / c4n, c = p - c4n * t;
+        const size_t off = (size_t)(t >> 3) * res + (t & 7);
+        *reinterpret_cast<f32x4 *>(e + off_x + (size_t)t * C + 4 * c) = *reinterpret_cast<const f32x4 *>(x + (s0 + off) * C + 4 * c);
+        if (skip) *reinterpret_cast<f32x4 *>(e + off_skip + (size_t)t * C + 4 * c) = *reinterpret_cast<const f32x4 *>(skip + (s0 + off) * C + 4 * c);
+    }
+    if (stats)
+        for (int p = tid; p < 64 * nparts; p += 256) {
+            const int t = p / nparts, c = p - nparts * t;
+            const size_t off = (size_t)(t >> 3) * res + (t & 7);
+            *reinterpret_cast<float2 *>(e + off_st + 2 * (t * nparts + c)) = *reinterpret_cast<const float2 *>(stats + 2 * ((s0 + off) * nparts + c));
+        }
+}
+
+void launch_window_harvest(const float *x, const float *skip, const float *stats, int nparts, int n, int res, int C, float *dst,
+                           size_t stride, int off_x, int off_skip, int off_st, hipStream_t s) {
+    if (n < 1) return;
+    DSG_LAUNCH(window_harvest_kernel, dim3(n), dim3(256), 0, s, x, skip, stats, nparts, res, C, dst, stride, off_x, off_skip, off_st);
 }
 
 // PatchMerging's gather + LayerNorm(4C) over a run list of MERGED rows (kernels.h).  Block k takes run run_list[k]: 8 consecutive merged

@@ -308,6 +308,14 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *       round of resident GEMM tiles, so fewer rows buy no time there.  2: across the batch at every size.  dsg_denoise / dsg_precond
  *       (per-sample noise labels, caller tensors) list every window as unique whatever the value.  dsg_get_option reports the value in
  *       force (0 wherever "dedup_masked" is off).  Bit-identical results whatever the value.
+ *   "dedup_table" (default 1; env DSG_DEDUP_TABLE; acts only where "dedup_batch" shares one representative across the batch): that
+ *       window's rows depend on the weights and on the step's (scale, shift) row only, so a sampler call computes them once per
+ *       schedule index before its loop -- with the down path itself, on all-padding pseudo-batches of B indices -- into a table in the
+ *       workspace (per index and level 64 rows of the activation, of the skip tensor and their row statistics; VG shape: about 330 KB
+ *       per index, counted by dsg_workspace_bytes once built), and the fill writes the window from the entry of the running step like
+ *       every other pure window; no launch of the loop computes it.  0: the batch's first pure window is computed in every forward.
+ *       The captured step bodies are the same for both values (a device-side word written with the lists selects the fill's source),
+ *       so changing the option keeps them.  dsg_get_option reports whether it would act.  Bit-identical results either way.
  *   "fused_merge" (PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path; 1: where it pays (>= 8192 merged
  *   rows), 2: at every size, 0: merge_ln kernel).
  * "batch_invariant" (default 0): 1 -- every choice the plan makes (which kernel, which tile, fused or not, any summation order) is a
@@ -379,10 +387,12 @@ int dsg_debug_need_lists(dsg_handle h, int32_t B, int32_t *roles, int32_t max_ro
  * deduplicate; 0: the copy moved activation rows; 1: also their LayerNorm partials, which the fused PatchMerging reads); wins (capacity B * nW): unique windows b * nW + w -- every
  * non-pure window and the representative; runs (B * N * N / 8): the same set as 8-token runs; copy (B * nW): the pure windows filled
  * by copy; rep [B]: each graph's representative window b * nW + w, -1 where the graph has no pure window (or the call deduplicates
- * nothing).  What is reported is what was staged, i.e. the lists the launches iterate: under "dedup_batch" (a sampler call with one
+ * nothing).  What is reported is what was staged: under "dedup_batch" (a sampler call with one
  * representative for the batch) rep holds the same global id b' * nW + w for every graph -- a window of whichever graph b' comes first
  * with a pure window -- wins / runs hold every non-pure window plus that one, and copy holds the pure windows that are filled: all
- * others at the top level of the chain, below it only those under a unique window of the next level. */
+ * others at the top level of the chain, below it only those under a unique window of the next level.  Under "dedup_table" the same
+ * is reported -- rep names the window whose rows come from the table -- although no launch computes that window and the fill writes
+ * it: dsg_debug_dedup_launch_lists below reports the lists as the launches iterate them. */
 int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream);
 /* The same for level `level` of the down path (0: exactly dsg_debug_dedup_lists).  A window of level k has 8 x 8 tokens of the grid of
  * res = N >> k tokens per side and covers 8 << k nodes per side; it is pure when no valid pair lies under it (no valid node in its row
@@ -393,6 +403,13 @@ int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *win
  * (sum, sumsq) partials, which the next block or the next PatchMerging reads).  counts [0..2] = -1: the plan has no lists for the level. */
 int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
                                 int32_t *rep, void *stream);
+/* The lists of level `level` as the launches iterate them (same capacities): wins / runs -- what PatchEmbed or the merge into the level
+ * and the level's first block compute; copy -- the windows the fill writes.  counts [3]: how the lists were written -- 0 every window
+ * unique (dsg_denoise / dsg_precond), 1 one representative per graph, 2 one for the batch, 3 one for the batch, taken from the
+ * sampler's table ("dedup_table"): wins / runs then hold the non-pure windows only and copy also holds the window that
+ * dsg_debug_dedup_level_lists reports as rep.  For 0 .. 2 the lists are those of dsg_debug_dedup_level_lists. */
+int dsg_debug_dedup_launch_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
+                                 void *stream);
 int dsg_debug_tap(dsg_handle h, const char *stage, float *dst, int64_t capacity);
 void dsg_debug_clear_taps(dsg_handle h);
 
