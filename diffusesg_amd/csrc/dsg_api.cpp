@@ -1943,13 +1943,12 @@ int precond_core(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, 
         if (int rc = run_forward(h, w, use_graph, s)) return rc;
         (*nfe)++;
         // the D of the extra pass becomes the self-cond input (written straight into the fixed sc buffers)
-        launch_precond_out(x, CStatePtrs{w->f_adj, w->f_node}, w->sig, w->flags, StatePtrs{w->sc_adj, w->sc_node},
-                           StatePtrs{nullptr, nullptr}, d, s);
+        launch_precond_out(x, CStatePtrs{w->f_adj, w->f_node}, w->sig, w->flags, StatePtrs{w->sc_adj, w->sc_node}, d, s);
         HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)w->has_sc, 1, 1, s));
     }
     if (int rc = run_forward(h, w, use_graph, s)) return rc;
     (*nfe)++;
-    launch_precond_out(x, CStatePtrs{w->f_adj, w->f_node}, w->sig, w->flags, dst, StatePtrs{nullptr, nullptr}, d, s);
+    launch_precond_out(x, CStatePtrs{w->f_adj, w->f_node}, w->sig, w->flags, dst, d, s);
     return 0;
 }
 
@@ -2188,8 +2187,8 @@ int dsg_gen_noise(dsg_handle h, int32_t B, const uint8_t *flags, uint64_t seed, 
                   float *out_node, void *stream) {
     if (!h || B < 1) return fail(h, DSG_ERR_INVALID, "batch must be >= 1");
     if (!flags || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null tensor");
-    launch_init(CStatePtrs{nullptr, nullptr}, 1.0f, seed, noise_stream, flags, StatePtrs{out_adj, out_node}, dims_of(h, B),
-                (hipStream_t)stream);
+    launch_init(CStatePtrs{nullptr, nullptr}, CStatePtrs{nullptr, nullptr}, 1.0f, seed, nullptr, noise_stream, flags, StatePtrs{out_adj, out_node},
+                dims_of(h, B), (hipStream_t)stream);
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
 }
@@ -2203,7 +2202,8 @@ int dsg_gen_noise_seeded(dsg_handle h, int32_t B, const uint8_t *flags, const ui
     Workspace *w;
     if (int rc = get_workspace(h, B, &w)) return rc;
     if (int rc = stage_seeds(h, w, graph_seeds, s)) return rc;
-    launch_init_seeded(CStatePtrs{nullptr, nullptr}, 1.0f, w->gseeds, noise_stream, flags, StatePtrs{out_adj, out_node}, dims_of(h, B), s);
+    launch_init(CStatePtrs{nullptr, nullptr}, CStatePtrs{nullptr, nullptr}, 1.0f, 0, w->gseeds, noise_stream, flags, StatePtrs{out_adj, out_node},
+                dims_of(h, B), s);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(s));   // the seeds are the caller's host memory
     return DSG_OK;
@@ -2400,32 +2400,58 @@ int build_pure_table(dsg_handle h, Workspace *w, int T, hipStream_t s) {
     return 0;
 }
 
-// dsg_sample (known == nullptr), dsg_sample_known, dsg_sample_walk and dsg_sample_seeded (graph_seeds != nullptr: per-graph noise
-// streams; `seed` then only draws the coins): one reverse loop.  walk == nullptr is the trivial walk (every
-// schedule index once, from pure noise); base_* (a walk's partial-noise start) only reaches the init kernel.
-int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags, const float *init_adj,
-                const float *init_node, const float *base_adj, const float *base_node, const float *noise_adj, const float *noise_node,
-                const uint8_t *coins, uint64_t seed, const uint64_t *graph_seeds, const float *gt_adj, const float *gt_node,
-                const KnownArgs *known, const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
-                dsg_sample_stats *stats, void *stream) {
-    if (int rc = check_ready(h, B)) return rc;
-    if (!cfg || !flags || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null argument");
-    if ((init_adj == nullptr) != (init_node == nullptr)) return fail(h, DSG_ERR_INVALID, "init_adj/init_node must both be given");
-    if ((noise_adj == nullptr) != (noise_node == nullptr)) return fail(h, DSG_ERR_INVALID, "noise_adj/noise_node must both be given");
-    if ((gt_adj == nullptr) != (gt_node == nullptr)) return fail(h, DSG_ERR_INVALID, "gt_adj/gt_node must both be given");
-    if ((base_adj == nullptr) != (base_node == nullptr)) return fail(h, DSG_ERR_INVALID, "base_adj/base_node must both be given");
-    const int T = cfg->num_steps;
+// One run of the reverse loop, as dsg_sample, dsg_sample_known, dsg_sample_walk and dsg_sample_seeded describe it.
+// walk == nullptr: the trivial walk (every schedule index once, from pure noise); base (a walk's partial-noise start) only reaches the
+// initial state.  graph_seeds != nullptr: per-graph noise streams, `seed` then only draws the coins.  known.adj == nullptr: unconditioned.
+struct SampleArgs {
+    const dsg_sampler_cfg *cfg; const dsg_walk_cfg *walk; int32_t B; const uint8_t *flags;
+    CStatePtrs init, base, noise; const uint8_t *coins; uint64_t seed; const uint64_t *graph_seeds;
+    CStatePtrs gt; KnownArgs known;
+    struct Snapshots { const int32_t *steps; int32_t n; float *adj, *node; } snapshots;
+    StatePtrs outputs; dsg_sample_stats *stats; hipStream_t stream;
+};
+
+// all four known tensors or none (required: all four)
+int known_args(dsg_handle h, const char *entry, bool required, const KnownArgs &k) {
+    const int n = (k.adj != nullptr) + (k.node != nullptr) + (k.mask_adj != nullptr) + (k.mask_node != nullptr);
+    if (n == 4 || (n == 0 && !required)) return 0;
+    return fail(h, DSG_ERR_INVALID, "%s needs known_adj, known_node, mask_adj and mask_node%s (%s is NULL)", entry,
+                required ? "" : " all given or all NULL", !k.adj ? "known_adj" : !k.node ? "known_node" : !k.mask_adj ? "mask_adj" : "mask_node");
+}
+
+// what the host works out before the device sees the run; its vectors are the source of async copies and live until the run's synchronise
+struct SamplePlan {
+    int T = 0, L = 0;              // schedule indices, executed steps
+    float x0_scale = 0.f;          // sigma the initial state is drawn at
+    std::vector<float> t_hat;      // [T] sigma of every schedule index
+    std::vector<StepRow> rows;     // [L] the loop's scalars
+    RunCtl ctl{};                  // the control block (graph_seeds: set once the seeds are staged)
+    std::vector<StepPlan> plans;   // [L] the static launch sequence of every step
+    int precond_calls = 0;
+    bool use_graph = false;
+};
+
+// Host plan: argument checks, walk, schedule, coins, rows and step plans.  No HIP call.
+int plan_sample(dsg_handle h, const SampleArgs &a, SamplePlan &p) {
+    const dsg_sampler_cfg *cfg = a.cfg;
+    if (int rc = check_ready(h, a.B)) return rc;
+    if (!cfg || !a.flags || !a.outputs.adj || !a.outputs.node) return fail(h, DSG_ERR_INVALID, "null argument");
+    if ((a.init.adj == nullptr) != (a.init.node == nullptr)) return fail(h, DSG_ERR_INVALID, "init_adj/init_node must both be given");
+    if ((a.noise.adj == nullptr) != (a.noise.node == nullptr)) return fail(h, DSG_ERR_INVALID, "noise_adj/noise_node must both be given");
+    if ((a.gt.adj == nullptr) != (a.gt.node == nullptr)) return fail(h, DSG_ERR_INVALID, "gt_adj/gt_node must both be given");
+    if ((a.base.adj == nullptr) != (a.base.node == nullptr)) return fail(h, DSG_ERR_INVALID, "base_adj/base_node must both be given");
+    const int T = p.T = cfg->num_steps;
     if (T < 1) return fail(h, DSG_ERR_INVALID, "num_steps < 1");
     // the walk: schedule index and churn coefficient of every executed step (the trivial walk: 0..T-1 with the schedule's own)
     const dsg_walk_cfg trivial{0, 1, 1, 0, 0, {0, 0, 0}};
-    if (!walk) walk = &trivial;
-    const int32_t L = dsg_walk_steps(cfg, walk, nullptr, nullptr, 0);
+    const dsg_walk_cfg *walk = a.walk ? a.walk : &trivial;
+    const int32_t L = p.L = dsg_walk_steps(cfg, walk, nullptr, nullptr, 0);
     if (L < 0)
         return fail(h, DSG_ERR_INVALID, "bad walk: start_step %d, jump_len %d, n_resample %d, resample range [%d, %d) with num_steps %d "
                     "(need 0 <= start_step < T, jump_len >= 1, n_resample >= 1, start_step <= lo <= hi <= T, at most %d executed steps)",
                     walk->start_step, walk->jump_len, walk->n_resample, walk->resample_lo, walk->resample_hi <= 0 ? T : walk->resample_hi, T,
                     DSG_WALK_MAX_STEPS);
-    if (walk->start_step > 0 && !base_adj)
+    if (walk->start_step > 0 && !a.base.adj)
         return fail(h, DSG_ERR_INVALID, "start_step %d > 0 needs base_adj / base_node (the graph the run starts from)", walk->start_step);
     std::vector<int32_t> sched(L);
     std::vector<float> coef(L), ms_coef(L);
@@ -2433,46 +2459,72 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
     if (dsg_multistep_coef(cfg, walk, ms_coef.data(), L) != L)   // the walk is good: what is left is a level with churn noise
         return fail(h, DSG_ERR_INVALID, "solver dpmpp_2m (heun = %d) needs a schedule that draws no churn noise at any level: set S_churn = 0 "
                     "(S_churn is %g)", DSG_SOLVER_DPMPP_2M, (double)cfg->S_churn);
-    hipStream_t s = (hipStream_t)stream;
-    Workspace *w;
-    if (int rc = get_workspace(h, B, &w)) return rc;
-    const Dims d = dims_of(h, B);
-    const size_t sa = (size_t)B * h->Ca * h->N * h->N, sn = (size_t)B * h->N * h->Cn;
-    std::vector<float> t_hat(T), nz(T), hs(T);
-    dsg_sigma_schedule(cfg, nullptr, t_hat.data(), nz.data(), hs.data());
-    std::vector<float> t_steps(T + 1, 0.f);
-    {
-        std::vector<double> sg(T);
-        dsg_sigma_schedule(cfg, sg.data(), nullptr, nullptr, nullptr);
-        for (int i = 0; i < T; i++) t_steps[i] = (float)sg[i];
-    }
+    std::vector<float> nz(T), hs(T);
+    std::vector<double> sg(T);
+    p.t_hat.resize(T);
+    dsg_sigma_schedule(cfg, sg.data(), p.t_hat.data(), nz.data(), hs.data());
+    p.x0_scale = (float)sg[walk->start_step];   // x0 = init * sigma(t0) (edm.py:326, :346-347); a start past 0 has a base: x = base + t_s * eps
     // preconditioned calls of the walk: two per Heun step, one where the step is the Euler step to 0 (index T - 1); Euler and multistep: one
     int ncalls = 0;
     for (int k = 0; k < L; k++) ncalls += (solver_heun(cfg) && sched[k] != T - 1) ? 2 : 1;
     std::vector<uint8_t> coin_buf(ncalls, 0);
-    if (coins) memcpy(coin_buf.data(), coins, ncalls);
+    if (a.coins) memcpy(coin_buf.data(), a.coins, ncalls);
     else if (h->cfg.self_condition) {
-        std::mt19937_64 gen(seed ^ 0x9E3779B97F4A7C15ull);
+        std::mt19937_64 gen(a.seed ^ 0x9E3779B97F4A7C15ull);
         for (int i = 0; i < ncalls; i++) coin_buf[i] = (gen() >> 63) & 1;
     }
-    h->last_stats = dsg_sample_stats{};
-    // every state the loop's forwards read (x_hat, the denoised estimates, the known-entry select) is stored as `valid ? ... : 0.f` by
-    // init_*_kernel, churn_tab_kernel, precond_out_tab*_kernel and the update kernels: zero at padded pairs whatever the caller passed
-    // ... and every forward of the loop goes through precond_tab: one sigma, one (scale, shift) row for the whole batch
-    if (int rc = stage_flags(h, w, flags, s, /*zero_padded=*/true, /*uniform_row=*/true)) return rc;
-    if (graph_seeds) if (int rc = stage_seeds(h, w, graph_seeds, s)) return rc;
-    // x0 = init * sigma(t0) (edm.py:326, :346-347)
-    if (graph_seeds && base_adj)
-        launch_init_base_seeded(CStatePtrs{init_adj, init_node}, CStatePtrs{base_adj, base_node}, t_steps[walk->start_step], w->gseeds, 0u, w->flags,
-                                StatePtrs{w->x_adj, w->x_node}, d, s);
-    else if (graph_seeds) launch_init_seeded(CStatePtrs{init_adj, init_node}, t_steps[0], w->gseeds, 0u, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
-    else if (base_adj)   // partial-noise start: x = base + t_s * eps
-        launch_init_base(CStatePtrs{init_adj, init_node}, CStatePtrs{base_adj, base_node}, t_steps[walk->start_step], seed, 0u, w->flags,
-                         StatePtrs{w->x_adj, w->x_node}, d, s);
-    else launch_init(CStatePtrs{init_adj, init_node}, t_steps[0], seed, 0u, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
-    const bool use_graph = cfg->use_graph != 0 && !gt_adj && h->taps.empty();
-    // per-step tables on the device: the loop's scalars (StepRow) and, since sigma is batch-uniform (edm.py:371), one noise
-    // embedding + (scale,shift) row per step for all blocks, computed once for all steps in three GEMMs with M = T
+    p.rows.resize(L);
+    for (int k = 0; k < L; k++) {
+        const int i = sched[k];
+        volatile float t_prime = p.t_hat[i] + hs[i];  // alpha = 1 (edm.py:391)
+        p.rows[k] = StepRow{coef[k], p.t_hat[i], 1.0f / p.t_hat[i], 1.0f / t_prime, hs[i], i, ms_coef[k], 0};
+    }
+    p.ctl = RunCtl{0, L, (unsigned long long)a.seed, a.noise.adj, a.noise.node, nullptr};   // nothing sticky: rewritten by every run
+    p.use_graph = cfg->use_graph != 0 && !a.gt.adj && h->taps.empty();
+    // the static plan of every executed step (edm.py:350-427): buffer rotation (it simply continues across a jump: the
+    // self-conditioning input is the last denoised estimate, whichever level it came from), Euler/Heun/multistep update, the pre-drawn coins
+    const bool gt = a.gt.adj != nullptr;
+    p.plans.resize(L);
+    int call = 0;
+    int sc_slot = -1;  // which d_* buffer holds the current self-cond, -1 = None
+    int last_s1 = -1;  // which d_* buffer the previous step's D went to (a network without self-conditioning keeps no sc_slot)
+    auto free_slot = [&](int s0, int s1) { for (int k = 0; k < 3; k++) if (k != s0 && k != s1) return k; return 0; };
+    for (int i = 0; i < L; i++) {
+        StepPlan &q = p.plans[i];
+        q.sc_slot = sc_slot;
+        // a multistep step (coefficient != 0, so never the first) reads the previous step's D: the self-conditioning input where the
+        // network has one (the D of a fired coin's extra pass goes to w->sc_*, not there), else the previous s1; s1 avoids both.
+        // Every other step is planned as ever (prev = -1).  Sanity-check mode: no slot is read, D_prev = D = gt
+        if (ms_coef[i] != 0.f) q.prev = gt ? 0 : (h->cfg.self_condition ? sc_slot : last_s1);
+        q.s1 = free_slot(sc_slot, q.prev);
+        q.s2 = free_slot(q.s1, -1);
+        q.euler = !solver_heun(cfg) || sched[i] == T - 1;   // edm.py:394-396
+        q.known = a.known.adj != nullptr;
+        q.coin1 = !gt && coin_buf[call] != 0;
+        q.coin2 = !gt && !q.euler && coin_buf[call + 1] != 0;
+        if (!gt) call += q.euler ? 1 : 2;
+        if (!gt && h->cfg.self_condition) sc_slot = q.euler ? q.s1 : q.s2;   // edm.py:423-424: sc <- last denoised
+        if (!gt) last_s1 = q.s1;
+    }
+    p.precond_calls = call;
+    return 0;
+}
+
+// Initial state.  Every state the loop's forwards read (x_hat, the denoised estimates, the known-entry select) is stored as
+// `valid ? ... : 0.f` by the elementwise skeleton (Init, Churn, PrecondOut and the update operations): zero at padded pairs whatever
+// the caller passed ... and every forward of the loop goes through precond_tab: one sigma, one (scale, shift) row for the whole batch
+int initial_state(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &p, hipStream_t s) {
+    if (int rc = stage_flags(h, w, a.flags, s, /*zero_padded=*/true, /*uniform_row=*/true)) return rc;
+    if (a.graph_seeds) if (int rc = stage_seeds(h, w, a.graph_seeds, s)) return rc;
+    launch_init(a.init, a.base, p.x0_scale, a.seed, a.graph_seeds ? w->gseeds : nullptr, 0u, w->flags, StatePtrs{w->x_adj, w->x_node},
+                dims_of(h, a.B), s);
+    return 0;
+}
+
+// Step tables on the device: the loop's scalars (StepRow) and, since sigma is batch-uniform (edm.py:371), one noise embedding +
+// (scale,shift) row per step for all blocks, computed once for all steps in three GEMMs with M = T
+int step_tables(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, hipStream_t s) {
+    const int T = p.T, L = p.L;
     if (h->tab_cap < T) {
         drop_graphs(h);   // the captured step bodies bake the table addresses
         for (float **q : {&h->tab_sig, &h->tab_cn, &h->tab_pe, &h->tab_e0, &h->tab_e1, &h->tab_aff}) { if (*q) (void)hipFree(*q); *q = nullptr; }
@@ -2492,108 +2544,101 @@ int sample_impl(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *wa
         HIP_TRY(h, hipMalloc((void **)&h->tab_step, sizeof(StepRow) * (size_t)L));
         h->tab_step_cap = L;
     }
-    std::vector<StepRow> rows(L);
-    for (int k = 0; k < L; k++) {
-        const int i = sched[k];
-        volatile float t_prime = t_hat[i] + hs[i];  // alpha = 1 (edm.py:391)
-        rows[k] = StepRow{coef[k], t_hat[i], 1.0f / t_hat[i], 1.0f / t_prime, hs[i], i, ms_coef[k], 0};
+    if (a.graph_seeds) p.ctl.graph_seeds = w->gseeds;
+    HIP_TRY(h, hipMemcpyAsync(h->tab_step, p.rows.data(), sizeof(StepRow) * L, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(w->ctl, &p.ctl, sizeof(RunCtl), hipMemcpyHostToDevice, s));
+    if (a.gt.adj) return 0;   // sanity-check mode: no forward reads a table
+    HIP_TRY(h, hipMemcpyAsync(h->tab_sig, p.t_hat.data(), sizeof(float) * T, hipMemcpyHostToDevice, s));
+    launch_cnoise(h->tab_sig, h->tab_cn, T, s);
+    embed_rows(h, h->tab_cn, T, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff, s);
+    return 0;
+}
+
+// Pure-window table: where the batch shares one representative pure window per level, that window comes from a table with one entry
+// per schedule index, built now from the rows of tab_aff; then the caller's flags again, with lists that leave the window to the fill.
+// DSG_TABLE_VERBOSE (measurement): HIP events around the build of this call
+int pure_window_table(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &p, hipStream_t s) {
+    if (a.gt.adj || !h->opt_dedup_table || w->dd_mode != DD_BATCH) return 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (getenv("DSG_TABLE_VERBOSE")) {
+        HIP_TRY(h, hipEventCreate(&ev[0]));
+        HIP_TRY(h, hipEventCreate(&ev[1]));
+        HIP_TRY(h, hipEventRecord(ev[0], s));
     }
-    hipEvent_t tab_ev[2] = {nullptr, nullptr};
-    RunCtl ctl_host{0, L, (unsigned long long)seed, noise_adj, noise_node, graph_seeds ? w->gseeds : nullptr};   // nothing sticky: rewritten by every run
-    HIP_TRY(h, hipMemcpyAsync(h->tab_step, rows.data(), sizeof(StepRow) * L, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(w->ctl, &ctl_host, sizeof(RunCtl), hipMemcpyHostToDevice, s));
-    if (!gt_adj) {
-        HIP_TRY(h, hipMemcpyAsync(h->tab_sig, t_hat.data(), sizeof(float) * T, hipMemcpyHostToDevice, s));
-        launch_cnoise(h->tab_sig, h->tab_cn, T, s);
-        embed_rows(h, h->tab_cn, T, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff, s);
-        // where the batch shares one representative pure window per level, that window comes from a table with one entry per schedule
-        // index, built now from the rows of tab_aff; then the caller's flags again, with lists that leave the window to the fill
-        if (h->opt_dedup_table && w->dd_mode == DD_BATCH) {
-            const bool verbose = getenv("DSG_TABLE_VERBOSE") != nullptr;   // measurement: HIP events around the build of this call
-            if (verbose) {
-                HIP_TRY(h, hipEventCreate(&tab_ev[0]));
-                HIP_TRY(h, hipEventCreate(&tab_ev[1]));
-                HIP_TRY(h, hipEventRecord(tab_ev[0], s));
-            }
-            if (int rc = build_pure_table(h, w, T, s)) return rc;
-            if (int rc = stage_flags(h, w, flags, s, /*zero_padded=*/true, /*uniform_row=*/true, /*table=*/true)) return rc;
-            if (verbose) HIP_TRY(h, hipEventRecord(tab_ev[1], s));
-        }
+    int rc = build_pure_table(h, w, p.T, s);
+    if (!rc) rc = stage_flags(h, w, a.flags, s, /*zero_padded=*/true, /*uniform_row=*/true, /*table=*/true);
+    float ms = 0.f;
+    if (!rc && ev[1] && hipEventRecord(ev[1], s) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+        hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+        fprintf(stderr, "[dsg-table] B=%d T=%d: table of pure-window rows built in %.1f us (%zu bytes)\n", a.B, p.T, ms * 1e3, w->tab_pure_bytes);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+// Known staging: the known tensors and masks move into workspace-owned buffers: conditioned step bodies bake these addresses and must
+// not reference caller memory.  Staged on the caller's stream ahead of the run's synchronise, i.e. before any body is captured
+int stage_known(dsg_handle h, Workspace *w, const KnownArgs &known, hipStream_t s) {
+    if (!known.adj) return 0;
+    const size_t sa = (size_t)w->B * h->Ca * h->N * h->N, sn = (size_t)w->B * h->N * h->Cn;
+    if (!w->kn_adj) {
+        void *q;
+        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sa)) return rc;
+        w->kn_adj = (float *)q;
+        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sn)) return rc;
+        w->kn_node = (float *)q;
+        if (int rc = dev_alloc(h, w->allocs, &q, sa)) return rc;
+        w->km_adj = (uint8_t *)q;
+        if (int rc = dev_alloc(h, w->allocs, &q, sn)) return rc;
+        w->km_node = (uint8_t *)q;
+        w->known_bytes = (sizeof(float) + 1) * (sa + sn);
+        w->bytes += w->known_bytes;
     }
-    if (known) {
-        // the known tensors and masks move into workspace-owned buffers: conditioned step bodies bake these addresses and must not
-        // reference caller memory.  Staged on the caller's stream ahead of the synchronise below, i.e. before any body is captured
-        if (!w->kn_adj) {
-            void *q;
-            if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sa)) return rc;
-            w->kn_adj = (float *)q;
-            if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sn)) return rc;
-            w->kn_node = (float *)q;
-            if (int rc = dev_alloc(h, w->allocs, &q, sa)) return rc;
-            w->km_adj = (uint8_t *)q;
-            if (int rc = dev_alloc(h, w->allocs, &q, sn)) return rc;
-            w->km_node = (uint8_t *)q;
-            w->known_bytes = (sizeof(float) + 1) * (sa + sn);
-            w->bytes += w->known_bytes;
-        }
-        HIP_TRY(h, hipMemcpyAsync(w->kn_adj, known->adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(w->kn_node, known->node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(w->km_adj, known->mask_adj, sa, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(w->km_node, known->mask_node, sn, hipMemcpyDeviceToDevice, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));  // the host vectors above must outlive their async copies; once per sample() call
-    if (tab_ev[1]) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, tab_ev[0], tab_ev[1]);
-        fprintf(stderr, "[dsg-table] B=%d T=%d: table of pure-window rows built in %.1f us (%zu bytes)\n", B, T, ms * 1e3, w->tab_pure_bytes);
-    }
-    for (hipEvent_t e : tab_ev) if (e) (void)hipEventDestroy(e);
-    // the static plan of every executed step (edm.py:350-427): buffer rotation (it simply continues across a jump: the
-    // self-conditioning input is the last denoised estimate, whichever level it came from), Euler/Heun/multistep update, the pre-drawn coins
-    std::vector<StepPlan> plans(L);
-    int call = 0, snap_k = 0, nfe = 0;
-    {
-        int sc_slot = -1;  // which d_* buffer holds the current self-cond, -1 = None
-        int last_s1 = -1;  // which d_* buffer the previous step's D went to (a network without self-conditioning keeps no sc_slot)
-        auto free_slot = [&](int a, int b2) { for (int k = 0; k < 3; k++) if (k != a && k != b2) return k; return 0; };
-        for (int i = 0; i < L; i++) {
-            StepPlan &p = plans[i];
-            p.sc_slot = sc_slot;
-            // a multistep step (coefficient != 0, so never the first) reads the previous step's D: the self-conditioning input where the
-            // network has one (the D of a fired coin's extra pass goes to w->sc_*, not there), else the previous s1; s1 avoids both.
-            // Every other step is planned as ever (prev = -1).  Sanity-check mode: no slot is read, D_prev = D = gt
-            if (ms_coef[i] != 0.f) p.prev = gt_adj ? 0 : (h->cfg.self_condition ? sc_slot : last_s1);
-            p.s1 = free_slot(sc_slot, p.prev);
-            p.s2 = free_slot(p.s1, -1);
-            p.euler = !solver_heun(cfg) || sched[i] == T - 1;   // edm.py:394-396
-            p.known = known != nullptr;
-            p.coin1 = !gt_adj && coin_buf[call] != 0;
-            p.coin2 = !gt_adj && !p.euler && coin_buf[call + 1] != 0;
-            if (!gt_adj) call += p.euler ? 1 : 2;
-            if (!gt_adj && h->cfg.self_condition) sc_slot = p.euler ? p.s1 : p.s2;   // edm.py:423-424: sc <- last denoised
-            if (!gt_adj) last_s1 = p.s1;
-        }
-    }
-    const bool step_graphs = use_graph && h->opt_loop_graph;
+    HIP_TRY(h, hipMemcpyAsync(w->kn_adj, known.adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(w->kn_node, known.node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(w->km_adj, known.mask_adj, sa, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(w->km_node, known.mask_node, sn, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// Loop: every step body captured before the first launch, then replay (or enqueue), snapshots, outputs, stats
+int run_loop(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &p, hipStream_t s) {
+    const size_t sa = (size_t)a.B * h->Ca * h->N * h->N, sn = (size_t)a.B * h->N * h->Cn;
+    const bool step_graphs = p.use_graph && h->opt_loop_graph;
     if (step_graphs)
-        for (int i = 0; i < L; i++) if (int rc = ensure_step_graph(h, w, plans[i])) return rc;   // at most ten distinct bodies
-    for (int i = 0; i < L; i++) {
-        if (step_graphs) { if (int rc = replay_step(h, w, plans[i], s, &nfe)) return rc; }
-        else if (int rc = enqueue_step(h, w, plans[i], gt_adj, gt_node, s, &nfe, use_graph)) return rc;
+        for (int i = 0; i < p.L; i++) if (int rc = ensure_step_graph(h, w, p.plans[i])) return rc;   // at most ten distinct bodies
+    int snap_k = 0, nfe = 0;
+    for (int i = 0; i < p.L; i++) {
+        if (step_graphs) { if (int rc = replay_step(h, w, p.plans[i], s, &nfe)) return rc; }
+        else if (int rc = enqueue_step(h, w, p.plans[i], a.gt.adj, a.gt.node, s, &nfe, p.use_graph)) return rc;
         // interim snapshots (edm.py:429-432)
-        while (snap_k < n_snap && snap_steps && snap_steps[snap_k] == i) {
-            if (snap_adj) HIP_TRY(h, hipMemcpyAsync(snap_adj + (size_t)snap_k * sa, w->x_adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
-            if (snap_node) HIP_TRY(h, hipMemcpyAsync(snap_node + (size_t)snap_k * sn, w->x_node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
+        while (snap_k < a.snapshots.n && a.snapshots.steps && a.snapshots.steps[snap_k] == i) {
+            if (a.snapshots.adj) HIP_TRY(h, hipMemcpyAsync(a.snapshots.adj + (size_t)snap_k * sa, w->x_adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
+            if (a.snapshots.node) HIP_TRY(h, hipMemcpyAsync(a.snapshots.node + (size_t)snap_k * sn, w->x_node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
             snap_k++;
         }
     }
-    HIP_TRY(h, hipMemcpyAsync(out_adj, w->x_adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(out_node, w->x_node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(a.outputs.adj, w->x_adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(a.outputs.node, w->x_node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipGetLastError());
-    h->last_stats.precond_calls = call;
+    h->last_stats.precond_calls = p.precond_calls;
     h->last_stats.net_forwards = nfe;
-    if (stats) *stats = h->last_stats;
+    if (a.stats) *a.stats = h->last_stats;
     return DSG_OK;
+}
+
+int sample_impl(dsg_handle h, const SampleArgs &a) {
+    SamplePlan p;
+    if (int rc = plan_sample(h, a, p)) return rc;
+    hipStream_t s = a.stream;
+    Workspace *w;
+    if (int rc = get_workspace(h, a.B, &w)) return rc;
+    h->last_stats = dsg_sample_stats{};
+    if (int rc = initial_state(h, w, a, p, s)) return rc;
+    if (int rc = step_tables(h, w, a, p, s)) return rc;
+    if (int rc = pure_window_table(h, w, a, p, s)) return rc;
+    if (int rc = stage_known(h, w, a.known, s)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(s));  // the plan's host vectors (and the caller's seeds) must outlive their async copies; once per sample() call
+    return run_loop(h, w, a, p, s);
 }
 
 }  // namespace
@@ -2604,8 +2649,11 @@ int dsg_sample(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_
                const float *init_node, const float *noise_adj, const float *noise_node, const uint8_t *coins, uint64_t seed,
                const float *gt_adj, const float *gt_node, const int32_t *snap_steps, int32_t n_snap, float *snap_adj,
                float *snap_node, float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
-    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, nullptr, gt_adj, gt_node,
-                       nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+    SampleArgs a{};
+    a.cfg = cfg; a.B = B; a.flags = flags; a.init = {init_adj, init_node}; a.noise = {noise_adj, noise_node}; a.coins = coins; a.seed = seed;
+    a.snapshots = {snap_steps, n_snap, snap_adj, snap_node}; a.outputs = {out_adj, out_node}; a.stats = stats; a.stream = (hipStream_t)stream;
+    a.gt = {gt_adj, gt_node};
+    return sample_impl(h, a);
 }
 
 int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const uint8_t *flags, const float *init_adj,
@@ -2614,12 +2662,12 @@ int dsg_sample_known(dsg_handle h, const dsg_sampler_cfg *cfg, int32_t B, const 
                      const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node, float *out_adj, float *out_node,
                      dsg_sample_stats *stats, void *stream) {
     if (!h) return DSG_ERR_INVALID;
-    if (!known_adj || !known_node || !mask_adj || !mask_node)
-        return fail(h, DSG_ERR_INVALID, "dsg_sample_known needs known_adj, known_node, mask_adj and mask_node (%s is NULL)",
-                    !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
-    const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
-    return sample_impl(h, cfg, nullptr, B, flags, init_adj, init_node, nullptr, nullptr, noise_adj, noise_node, coins, seed, nullptr, nullptr, nullptr,
-                       &known, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+    SampleArgs a{};
+    a.cfg = cfg; a.B = B; a.flags = flags; a.init = {init_adj, init_node}; a.noise = {noise_adj, noise_node}; a.coins = coins; a.seed = seed;
+    a.snapshots = {snap_steps, n_snap, snap_adj, snap_node}; a.outputs = {out_adj, out_node}; a.stats = stats; a.stream = (hipStream_t)stream;
+    a.known = {known_adj, known_node, mask_adj, mask_node};
+    if (int rc = known_args(h, "dsg_sample_known", /*required=*/true, a.known)) return rc;
+    return sample_impl(h, a);
 }
 
 int dsg_sample_walk(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
@@ -2630,13 +2678,14 @@ int dsg_sample_walk(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg
                     dsg_sample_stats *stats, void *stream) {
     if (!h) return DSG_ERR_INVALID;
     if (!walk) return fail(h, DSG_ERR_INVALID, "dsg_sample_walk needs a walk (walk is NULL)");
-    const int n_known = (known_adj != nullptr) + (known_node != nullptr) + (mask_adj != nullptr) + (mask_node != nullptr);
-    if (n_known != 0 && n_known != 4)
-        return fail(h, DSG_ERR_INVALID, "dsg_sample_walk needs known_adj, known_node, mask_adj and mask_node all given or all NULL (%s is NULL)",
-                    !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
-    const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
-    return sample_impl(h, cfg, walk, B, flags, init_adj, init_node, base_adj, base_node, noise_adj, noise_node, coins, seed, nullptr, nullptr, nullptr,
-                       n_known ? &known : nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+    SampleArgs a{};
+    a.cfg = cfg; a.B = B; a.flags = flags; a.init = {init_adj, init_node}; a.noise = {noise_adj, noise_node}; a.coins = coins; a.seed = seed;
+    a.snapshots = {snap_steps, n_snap, snap_adj, snap_node}; a.outputs = {out_adj, out_node}; a.stats = stats; a.stream = (hipStream_t)stream;
+    a.walk = walk;
+    a.base = {base_adj, base_node};
+    a.known = {known_adj, known_node, mask_adj, mask_node};
+    if (int rc = known_args(h, "dsg_sample_walk", /*required=*/false, a.known)) return rc;
+    return sample_impl(h, a);
 }
 
 int dsg_sample_seeded(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
@@ -2648,13 +2697,15 @@ int dsg_sample_seeded(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_c
                       dsg_sample_stats *stats, void *stream) {
     if (!h) return DSG_ERR_INVALID;
     if (!graph_seeds) return fail(h, DSG_ERR_INVALID, "dsg_sample_seeded needs graph_seeds (host, one per graph); graph_seeds is NULL");
-    const int n_known = (known_adj != nullptr) + (known_node != nullptr) + (mask_adj != nullptr) + (mask_node != nullptr);
-    if (n_known != 0 && n_known != 4)
-        return fail(h, DSG_ERR_INVALID, "dsg_sample_seeded needs known_adj, known_node, mask_adj and mask_node all given or all NULL (%s is NULL)",
-                    !known_adj ? "known_adj" : !known_node ? "known_node" : !mask_adj ? "mask_adj" : "mask_node");
-    const KnownArgs known{known_adj, known_node, mask_adj, mask_node};
-    return sample_impl(h, cfg, walk, B, flags, init_adj, init_node, base_adj, base_node, noise_adj, noise_node, coins, coin_seed, graph_seeds,
-                       nullptr, nullptr, n_known ? &known : nullptr, snap_steps, n_snap, snap_adj, snap_node, out_adj, out_node, stats, stream);
+    SampleArgs a{};
+    a.cfg = cfg; a.B = B; a.flags = flags; a.init = {init_adj, init_node}; a.noise = {noise_adj, noise_node}; a.coins = coins; a.seed = coin_seed;
+    a.snapshots = {snap_steps, n_snap, snap_adj, snap_node}; a.outputs = {out_adj, out_node}; a.stats = stats; a.stream = (hipStream_t)stream;
+    a.walk = walk;
+    a.base = {base_adj, base_node};
+    a.graph_seeds = graph_seeds;
+    a.known = {known_adj, known_node, mask_adj, mask_node};
+    if (int rc = known_args(h, "dsg_sample_seeded", /*required=*/false, a.known)) return rc;
+    return sample_impl(h, a);
 }
 
 int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_kind, int64_t *launches_by_kind,
@@ -3837,7 +3888,7 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
     bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, sc_adj, sc_node}, StatePtrs{io.F_a, io.F_n}, s);
     if (ok) {
         // D = mask(c_skip x + c_out F) (precond.py:101-104); per-sample losses; with gradients: dL/dD and dL/dF = c_out dL/dD
-        launch_precond_out(noisy, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, StatePtrs{nullptr, nullptr}, d, s);
+        launch_precond_out(noisy, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, d, s);
         launch_rainbow_loss(D, target, flags, loss_weight, edge_loss_weight, node_loss_weight, iou_loss_weight, iou_loss_type, out_loss_adj,
                             out_loss_node, d, s);
         if (want_grads)
@@ -3863,8 +3914,7 @@ int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const f
     if (rc != DSG_OK) return rc;
     const bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, nullptr, nullptr}, StatePtrs{io.F_a, io.F_n}, s);
     if ((rc = train_finish(h, ok, s)) != DSG_OK) return rc;
-    launch_precond_out(CStatePtrs{noisy_adj, noisy_node}, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_sc_adj, out_sc_node},
-                       StatePtrs{nullptr, nullptr}, d, s);
+    launch_precond_out(CStatePtrs{noisy_adj, noisy_node}, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_sc_adj, out_sc_node}, d, s);
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
 }
@@ -3898,7 +3948,7 @@ int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node
     bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, sc_adj, sc_node}, StatePtrs{io.F_a, io.F_n}, s);
     const float *g_a = grad_D_adj, *g_n = grad_D_node;
     if (ok) {
-        launch_precond_out(CStatePtrs{adj, node}, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, StatePtrs{nullptr, nullptr}, d, s);
+        launch_precond_out(CStatePtrs{adj, node}, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_D_adj, out_D_node}, d, s);
         if (fn) {   // the callee enqueues g = dL/dD into the gradient outputs, which the last kernel below turns into the result in place
             const int cb_rc = fn(user, out_D_adj, out_D_node, out_grad_adj, out_grad_node);
             if (cb_rc != 0) {

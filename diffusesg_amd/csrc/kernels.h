@@ -283,22 +283,17 @@ struct Dims { int B, N, Ca, Cn; };
 void launch_cnoise(const float *sigmas, float *c_noise, int n, hipStream_t s);
 // in = c_in(sigma[b]) * x ; c_noise[b] = ln(sigma[b])/4
 void launch_precond_in(CStatePtrs x, const float *sigmas, StatePtrs in, float *c_noise, Dims d, hipStream_t s);
-// D = mask(c_skip*x + c_out*F); optionally stored to a second destination
-void launch_precond_out(CStatePtrs x, CStatePtrs F, const float *sigmas, const uint8_t *flags, StatePtrs D, StatePtrs D2,
-                        Dims d, hipStream_t s);
+// D = mask(c_skip*x + c_out*F)
+void launch_precond_out(CStatePtrs x, CStatePtrs F, const float *sigmas, const uint8_t *flags, StatePtrs D, Dims d, hipStream_t s);
 // x0 = mask(eps) * scale (gen_init_sample + initial scaling); eps from `init` or Philox(seed, stream): stream 0 is the
 // initial sample, stream i+1 the churn noise of step i (launch_churn)
-void launch_init(CStatePtrs init, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
-// partial-noise start (dsg_sample_walk with base_*): x = mask(base + scale * eps), eps as launch_init's; base in the state layouts
-void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d,
-                      hipStream_t s);
-// Per-graph noise streams (dsg_sample_seeded / dsg_gen_noise_seeded): the draw of graph b is Philox(graph_seeds[b], stream, j), the
-// same generator, with j the element's index INSIDE its graph -- adjacency (c, i, k): (c N + i) N + k; node (i, c): Ca N^2 + i Cn + c,
-// i.e. the global index of the kernels above at B = 1.  graph_seeds: device [B].  Otherwise as launch_init / launch_init_base.
-void launch_init_seeded(CStatePtrs init, float scale, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags, StatePtrs x,
-                        Dims d, hipStream_t s);
-void launch_init_base_seeded(CStatePtrs init, CStatePtrs base, float scale, const unsigned long long *graph_seeds, uint32_t stream,
-                             const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
+// base given (the partial-noise start of dsg_sample_walk): x = mask(base + scale * eps); base in the state layouts
+// graph_seeds given (device [B]; per-graph noise streams, dsg_sample_seeded / dsg_gen_noise_seeded): the draw of graph b is
+// Philox(graph_seeds[b], stream, j), the same generator, with j the element's index INSIDE its graph -- adjacency (c, i, k):
+// (c N + i) N + k; node (i, c): Ca N^2 + i Cn + c, i.e. the global index of the unseeded draw at B = 1; `seed` is not read.
+// Each of the four combinations launches its own instantiation.
+void launch_init(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, const unsigned long long *graph_seeds, uint32_t stream,
+                 const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
 
 // ---- reverse-loop kernels driven by a DEVICE step counter, so that one captured step body can be replayed for every step ----
 // Per-step scalars, computed on the host up front exactly as before (dsg_sigma_schedule) and uploaded once per sample() call: one row

@@ -2081,15 +2081,37 @@ __host__ __device__ inline size_t total_elems(const Dims &d) { return (size_t)d.
 #define FADD(a, b) __fadd_rn((a), (b))
 #define FSUB(a, b) __fsub_rn((a), (b))
 
+// The skeleton of the sampler's elementwise kernels: flat index, bounds, elem_index, the element's value from a small operation
+// object, the masked store.  An operation holds its inputs and `flags` (null: no mask, every element valid); uniform() reads its
+// launch-uniform scalars (the step's row; 0 where it has none) ahead of the element's index, float operator()(u, e, idx, d) is only
+// its own arithmetic.  What selects a variant (base, seeded, known) is a template argument of the operation, so an instantiation
+// carries no load or branch of a variant it is not.  The mask's select is written around the call: the compiler skips a padded
+// element's loads and arithmetic (the stored value is the literal 0 either way).  (Register counts follow the order of the operation's
+// members, which is the order of the kernel arguments: profiles/r13/kernel_resource_usage.txt.)
+template <class P> __device__ __forceinline__ auto ld(const P &p, const ElemIdx &e) { return e.is_adj ? p.adj[e.off] : p.node[e.off]; }
+
+template <class Op> __global__ void elem_kernel(Op op, StatePtrs out, Dims d) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total_elems(d)) return;
+    const auto u = op.uniform();
+    const ElemIdx e = elem_index(idx, d, op.flags);
+    const float v = e.valid ? op(u, e, idx, d) : 0.f;
+    if (e.is_adj) out.adj[e.off] = v; else out.node[e.off] = v;
+}
+template <class Op> void launch_elem(const Op &op, StatePtrs out, const Dims &d, hipStream_t s) {
+    const size_t n = total_elems(d);
+    DSG_LAUNCH(elem_kernel<Op>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, out, d);
+}
+
+__device__ __forceinline__ float precond_c_in(float s) { return __fdiv_rn(1.0f, __fsqrt_rn(FADD(0.25f, FMUL(s, s)))); }   // objectives/edm.py:125
+// precond_in also writes c_noise for idx < B, a second output under its own bound: it keeps its own body
 __global__ void precond_in_kernel(CStatePtrs x, const float *sigmas, StatePtrs in, float *c_noise, Dims d) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < (size_t)d.B) c_noise[idx] = __fdiv_rn(logf(sigmas[idx]), 4.0f);  // objectives/edm.py:126
     if (idx >= total_elems(d)) return;
     const ElemIdx e = elem_index(idx, d, nullptr);
-    const float s = sigmas[e.b];
-    const float c_in = __fdiv_rn(1.0f, __fsqrt_rn(FADD(0.25f, FMUL(s, s))));       // objectives/edm.py:125
-    if (e.is_adj) in.adj[e.off] = FMUL(c_in, x.adj[e.off]);
-    else in.node[e.off] = FMUL(c_in, x.node[e.off]);
+    const float v = FMUL(precond_c_in(sigmas[e.b]), ld(x, e));
+    if (e.is_adj) in.adj[e.off] = v; else in.node[e.off] = v;
 }
 __global__ void cnoise_kernel(const float *sigmas, float *c_noise, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2103,25 +2125,47 @@ void launch_precond_in(CStatePtrs x, const float *sigmas, StatePtrs in, float *c
     DSG_LAUNCH(precond_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, sigmas, in, c_noise, d);
 }
 
-__global__ void precond_out_kernel(CStatePtrs x, CStatePtrs F, const float *sigmas, const uint8_t *flags, StatePtrs D,
-                                   StatePtrs D2, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, flags);
-    const float s = sigmas[e.b];
-    const float s2 = FADD(FMUL(s, s), 0.25f);
-    const float c_skip = __fdiv_rn(0.25f, s2);                                       // objectives/edm.py:123
-    const float c_out = __fdiv_rn(FMUL(s, 0.5f), __fsqrt_rn(s2));                    // objectives/edm.py:124
-    const float xv = e.is_adj ? x.adj[e.off] : x.node[e.off];
-    const float fv = e.is_adj ? F.adj[e.off] : F.node[e.off];
-    const float v = e.valid ? FADD(FMUL(c_skip, xv), FMUL(c_out, fv)) : 0.f;         // precond.py:102-105
-    if (e.is_adj) { D.adj[e.off] = v; if (D2.adj) D2.adj[e.off] = v; }
-    else { D.node[e.off] = v; if (D2.node) D2.node[e.off] = v; }
+// where an operation's sigma comes from: per sample (dsg_precond, training), or the executed step's row (the reverse loop)
+struct SampleSigma { const float *sigmas; __device__ float operator()(const ElemIdx &e) const { return sigmas[e.b]; } };
+struct StepSigma { const StepRow *tab; const RunCtl *ctl; __device__ float operator()(const ElemIdx &) const { return tab[ctl->step].sigma; } };
+
+struct PrecondInStep {
+    CStatePtrs x; StepSigma sigma;
+    static constexpr const uint8_t *flags = nullptr;
+    __device__ int uniform() const { return 0; }
+    __device__ float operator()(int, const ElemIdx &e, size_t, const Dims &) const { return FMUL(precond_c_in(sigma(e)), ld(x, e)); }
+};
+void launch_precond_in_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, StatePtrs in, Dims d, hipStream_t s) {
+    launch_elem(PrecondInStep{x, {tab, ctl}}, in, d, s);
 }
-void launch_precond_out(CStatePtrs x, CStatePtrs F, const float *sigmas, const uint8_t *flags, StatePtrs D, StatePtrs D2,
-                        Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(precond_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, F, sigmas, flags, D, D2, d);
+
+// D = c_skip x + c_out F.  known (conditional sampling, dsg_sample_known): a select in front of the store.  Where the element mask
+// is set the denoised estimate IS the known value -- copied, not blended, so it arrives bit-exact -- and known entries of the state
+// then follow known + t * eps like the sanity-check mode's (edm.py:372-377) do everywhere.
+struct NoKnown {};
+struct KnownSel { CStatePtrs value; CMaskPtrs mask; };
+template <class Sigma, bool known> struct PrecondOut {
+    std::conditional_t<known, KnownSel, NoKnown> k; CStatePtrs x, F; Sigma sigma; const uint8_t *flags;
+    __device__ int uniform() const { return 0; }
+    __device__ float operator()(int, const ElemIdx &e, size_t, const Dims &) const {
+        if constexpr (known) if (ld(k.mask, e) != 0) return ld(k.value, e);
+        const float s = sigma(e);
+        const float s2 = FADD(FMUL(s, s), 0.25f);
+        const float c_skip = __fdiv_rn(0.25f, s2);                                       // objectives/edm.py:123
+        const float c_out = __fdiv_rn(FMUL(s, 0.5f), __fsqrt_rn(s2));                    // objectives/edm.py:124
+        return FADD(FMUL(c_skip, ld(x, e)), FMUL(c_out, ld(F, e)));                      // precond.py:102-105
+    }
+};
+void launch_precond_out(CStatePtrs x, CStatePtrs F, const float *sigmas, const uint8_t *flags, StatePtrs D, Dims d, hipStream_t s) {
+    launch_elem(PrecondOut<SampleSigma, false>{{}, x, F, {sigmas}, flags}, D, d, s);
+}
+void launch_precond_out_tab(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs D, Dims d,
+                            hipStream_t s) {
+    launch_elem(PrecondOut<StepSigma, false>{{}, x, F, {tab, ctl}, flags}, D, d, s);
+}
+void launch_precond_out_tab_known(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, CStatePtrs known,
+                                  CMaskPtrs mask, StatePtrs D, Dims d, hipStream_t s) {
+    launch_elem(PrecondOut<StepSigma, true>{{known, mask}, x, F, {tab, ctl}, flags}, D, d, s);
 }
 
 // Philox4x32-10 counter-based generator -> one N(0,1) per (seed, stream, element)
@@ -2143,218 +2187,97 @@ __device__ __forceinline__ float philox_normal(uint64_t seed, uint32_t stream, u
     return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
-__global__ void init_kernel(CStatePtrs init, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, flags);
-    float v;
-    if (init.adj) v = e.is_adj ? init.adj[e.off] : init.node[e.off];
-    else v = philox_normal(seed, stream, idx);                   // stream 0: gen_init_sample, edm.py:279,285
-    v = e.valid ? FMUL(v, scale) : 0.f;                          // edm.py:346-347
-    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
-}
-void launch_init(CStatePtrs init, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, scale, seed, stream, flags, x, d);
-}
-
-// partial-noise start of a walk (SDEdit-style): the state begins at a noised copy of `base`, x = mask(base + scale * eps).  A separate
-// kernel: every run that starts from pure noise keeps launching the one above.
-__global__ void init_base_kernel(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags,
-                                 StatePtrs x, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, flags);
-    float v;
-    if (init.adj) v = e.is_adj ? init.adj[e.off] : init.node[e.off];
-    else v = philox_normal(seed, stream, idx);
-    const float bv = e.is_adj ? base.adj[e.off] : base.node[e.off];
-    v = e.valid ? FADD(bv, FMUL(v, scale)) : 0.f;
-    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
-}
-void launch_init_base(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, uint32_t stream, const uint8_t *flags, StatePtrs x, Dims d,
-                      hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(init_base_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, base, scale, seed, stream, flags, x, d);
+// the initial state.  eps from `init`, or stream 0 of Philox (gen_init_sample, edm.py:279,285) -- seeded: keyed by graph_seeds[b] and
+// the element's index inside its graph.  x0 = eps * scale (edm.py:346-347); with_base (the partial-noise start of a walk,
+// SDEdit-style): x0 = base + scale * eps
+template <bool with_base, bool seeded> struct Init {
+    CStatePtrs init, base; float scale; uint64_t seed; const unsigned long long *graph_seeds; uint32_t stream; const uint8_t *flags;
+    __device__ int uniform() const { return 0; }
+    __device__ float operator()(int, const ElemIdx &e, size_t idx, const Dims &d) const {
+        float v;
+        if (init.adj) v = ld(init, e);
+        else if constexpr (seeded) v = philox_normal(graph_seeds[e.b], stream, local_index(e, d));
+        else v = philox_normal(seed, stream, idx);
+        if constexpr (with_base) return FADD(ld(base, e), FMUL(v, scale));
+        else return FMUL(v, scale);
+    }
+};
+void launch_init(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, const unsigned long long *graph_seeds, uint32_t stream,
+                 const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
+    if (base.adj && graph_seeds) launch_elem(Init<true, true>{init, base, scale, seed, graph_seeds, stream, flags}, x, d, s);
+    else if (graph_seeds) launch_elem(Init<false, true>{init, base, scale, seed, graph_seeds, stream, flags}, x, d, s);
+    else if (base.adj) launch_elem(Init<true, false>{init, base, scale, seed, graph_seeds, stream, flags}, x, d, s);
+    else launch_elem(Init<false, false>{init, base, scale, seed, graph_seeds, stream, flags}, x, d, s);
 }
 
-// per-graph noise streams: the two kernels above keyed by graph_seeds[b] and the element's index inside its graph.  Separate kernels:
-// unseeded runs keep launching the ones above.
-__global__ void init_seeded_kernel(CStatePtrs init, float scale, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags,
-                                   StatePtrs x, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, flags);
-    float v;
-    if (init.adj) v = e.is_adj ? init.adj[e.off] : init.node[e.off];
-    else v = philox_normal(graph_seeds[e.b], stream, local_index(e, d));
-    v = e.valid ? FMUL(v, scale) : 0.f;
-    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
-}
-void launch_init_seeded(CStatePtrs init, float scale, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags, StatePtrs x,
-                        Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(init_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, scale, graph_seeds, stream, flags, x, d);
-}
-__global__ void init_base_seeded_kernel(CStatePtrs init, CStatePtrs base, float scale, const unsigned long long *graph_seeds, uint32_t stream,
-                                        const uint8_t *flags, StatePtrs x, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, flags);
-    float v;
-    if (init.adj) v = e.is_adj ? init.adj[e.off] : init.node[e.off];
-    else v = philox_normal(graph_seeds[e.b], stream, local_index(e, d));
-    const float bv = e.is_adj ? base.adj[e.off] : base.node[e.off];
-    v = e.valid ? FADD(bv, FMUL(v, scale)) : 0.f;
-    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
-}
-void launch_init_base_seeded(CStatePtrs init, CStatePtrs base, float scale, const unsigned long long *graph_seeds, uint32_t stream,
-                             const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(init_base_seeded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, init, base, scale, graph_seeds, stream, flags, x, d);
-}
-
-// ---- reverse-loop kernels: scalars from StepRow[ctl->step] (one captured step body serves every step; edm.py:355-427) ----
-__global__ void churn_tab_kernel(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs xhat, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const int step = ctl->step;
-    const float coef = tab[step].noise_coef;
-    const ElemIdx e = elem_index(idx, d, flags);
-    const float xv = e.is_adj ? x.adj[e.off] : x.node[e.off];
-    float eps;
-    if (ctl->noise_adj) {
-        const size_t sa = (size_t)d.B * d.Ca * d.N * d.N, sn = (size_t)d.B * d.N * d.Cn;
-        eps = e.is_adj ? ctl->noise_adj[(size_t)step * sa + e.off] : ctl->noise_node[(size_t)step * sn + e.off];
-    } else if (coef != 0.f && e.valid) {
-        // a seeded run (ctl->graph_seeds, uniform over the launch): the graph's own key and the element's index inside the graph
-        const unsigned long long *gs = ctl->graph_seeds;
-        eps = philox_normal(gs ? gs[e.b] : ctl->seed, (uint32_t)step + 1u, gs ? local_index(e, d) : idx);
-    } else eps = 0.f;
-    const float v = e.valid ? FADD(xv, FMUL(coef, eps)) : 0.f;  // edm.py:361-366
-    if (e.is_adj) xhat.adj[e.off] = v; else xhat.node[e.off] = v;
-}
+// ---- reverse-loop operations: scalars from StepRow[ctl->step] (one captured step body serves every step; edm.py:355-427) ----
+struct Churn {
+    CStatePtrs x; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+    struct U { int step; float coef; };
+    __device__ U uniform() const { const int step = ctl->step; return U{step, tab[step].noise_coef}; }
+    __device__ float operator()(const U &u, const ElemIdx &e, size_t idx, const Dims &d) const {
+        const int step = u.step;
+        const float xv = ld(x, e);
+        float eps;
+        if (ctl->noise_adj) {
+            const size_t sa = (size_t)d.B * d.Ca * d.N * d.N, sn = (size_t)d.B * d.N * d.Cn;
+            eps = e.is_adj ? ctl->noise_adj[(size_t)step * sa + e.off] : ctl->noise_node[(size_t)step * sn + e.off];
+        } else if (u.coef != 0.f && e.valid) {
+            // a seeded run (ctl->graph_seeds, uniform over the launch): the graph's own key and the element's index inside the graph
+            const unsigned long long *gs = ctl->graph_seeds;
+            eps = philox_normal(gs ? gs[e.b] : ctl->seed, (uint32_t)step + 1u, gs ? local_index(e, d) : idx);
+        } else eps = 0.f;
+        return FADD(xv, FMUL(u.coef, eps));  // edm.py:361-366
+    }
+};
 void launch_churn_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs xhat, Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(churn_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, tab, ctl, flags, xhat, d);
+    launch_elem(Churn{x, tab, ctl, flags}, xhat, d, s);
 }
-__global__ void precond_in_tab_kernel(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, StatePtrs in, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, nullptr);
-    const float s = tab[ctl->step].sigma;
-    const float c_in = __fdiv_rn(1.0f, __fsqrt_rn(FADD(0.25f, FMUL(s, s))));       // objectives/edm.py:125
-    if (e.is_adj) in.adj[e.off] = FMUL(c_in, x.adj[e.off]);
-    else in.node[e.off] = FMUL(c_in, x.node[e.off]);
-}
-void launch_precond_in_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, StatePtrs in, Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(precond_in_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, tab, ctl, in, d);
-}
-__global__ void precond_out_tab_kernel(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
-                                       StatePtrs D, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, flags);
-    const float s = tab[ctl->step].sigma;
-    const float s2 = FADD(FMUL(s, s), 0.25f);
-    const float c_skip = __fdiv_rn(0.25f, s2);                                       // objectives/edm.py:123
-    const float c_out = __fdiv_rn(FMUL(s, 0.5f), __fsqrt_rn(s2));                    // objectives/edm.py:124
-    const float xv = e.is_adj ? x.adj[e.off] : x.node[e.off];
-    const float fv = e.is_adj ? F.adj[e.off] : F.node[e.off];
-    const float v = e.valid ? FADD(FMUL(c_skip, xv), FMUL(c_out, fv)) : 0.f;         // precond.py:102-105
-    if (e.is_adj) D.adj[e.off] = v; else D.node[e.off] = v;
-}
-void launch_precond_out_tab(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs D, Dims d,
-                            hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(precond_out_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, F, tab, ctl, flags, D, d);
-}
-// conditional sampling (dsg_sample_known): the same D, with a select in front of the store.  Where the element mask is set the
-// denoised estimate IS the known value -- copied, not blended, so it arrives bit-exact -- and known entries of the state then
-// follow known + t * eps like the sanity-check mode's (edm.py:372-377) do everywhere.  A separate kernel: the unconditioned
-// path keeps launching the one above.
-__global__ void precond_out_tab_known_kernel(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
-                                             CStatePtrs known, CMaskPtrs mask, StatePtrs D, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const ElemIdx e = elem_index(idx, d, flags);
-    const float s = tab[ctl->step].sigma;
-    const float s2 = FADD(FMUL(s, s), 0.25f);
-    const float c_skip = __fdiv_rn(0.25f, s2);                                       // objectives/edm.py:123
-    const float c_out = __fdiv_rn(FMUL(s, 0.5f), __fsqrt_rn(s2));                    // objectives/edm.py:124
-    const float xv = e.is_adj ? x.adj[e.off] : x.node[e.off];
-    const float fv = e.is_adj ? F.adj[e.off] : F.node[e.off];
-    const bool is_known = (e.is_adj ? mask.adj[e.off] : mask.node[e.off]) != 0;
-    const float kv = e.is_adj ? known.adj[e.off] : known.node[e.off];
-    const float net = FADD(FMUL(c_skip, xv), FMUL(c_out, fv));                       // precond.py:102-105
-    const float v = e.valid ? (is_known ? kv : net) : 0.f;
-    if (e.is_adj) D.adj[e.off] = v; else D.node[e.off] = v;
-}
-void launch_precond_out_tab_known(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, CStatePtrs known,
-                                  CMaskPtrs mask, StatePtrs D, Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(precond_out_tab_known_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, F, tab, ctl, flags, known, mask, D, d);
-}
-__global__ void euler_tab_kernel(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs x,
-                                 Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const StepRow r = tab[ctl->step];
-    const ElemIdx e = elem_index(idx, d, flags);
-    const float xh = e.is_adj ? xhat.adj[e.off] : xhat.node[e.off];
-    const float dn = e.is_adj ? D.adj[e.off] : D.node[e.off];
-    const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, dn));     // edm.py:384-385
-    const float v = e.valid ? FADD(xh, FMUL(r.h, dc)) : 0.f;         // edm.py:395-396, :421-422
-    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
-}
+struct Euler {
+    CStatePtrs xhat, D; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+    __device__ StepRow uniform() const { return tab[ctl->step]; }
+    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &) const {
+        const float xh = ld(xhat, e);
+        const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, ld(D, e)));     // edm.py:384-385
+        return FADD(xh, FMUL(r.h, dc));                                         // edm.py:395-396, :421-422
+    }
+};
 void launch_euler_tab(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d,
                       hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(euler_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xhat, D, tab, ctl, flags, x, d);
+    launch_elem(Euler{xhat, D, tab, ctl, flags}, x, d, s);
 }
-__global__ void heun_tab_kernel(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRow *tab, const RunCtl *ctl,
-                                const uint8_t *flags, StatePtrs x, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const StepRow r = tab[ctl->step];
-    const ElemIdx e = elem_index(idx, d, flags);
-    const float xh = e.is_adj ? xhat.adj[e.off] : xhat.node[e.off];
-    const float d1 = e.is_adj ? D1.adj[e.off] : D1.node[e.off];
-    const float d2 = e.is_adj ? D2.adj[e.off] : D2.node[e.off];
-    const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, d1));        // edm.py:384-385
-    const float xp = FADD(xh, FMUL(r.h, dc));                           // edm.py:389-390 (alpha = 1)
-    const float dp = FSUB(FMUL(r.inv_tp, xp), FMUL(r.inv_tp, d2));      // edm.py:414-417
-    const float avg = FADD(FMUL(0.5f, dc), FMUL(0.5f, dp));
-    const float v = e.valid ? FADD(xh, FMUL(r.h, avg)) : 0.f;           // edm.py:418-422
-    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
-}
+struct Heun {
+    CStatePtrs xhat, D1, D2; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+    __device__ StepRow uniform() const { return tab[ctl->step]; }
+    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &) const {
+        const float xh = ld(xhat, e), d1 = ld(D1, e), d2 = ld(D2, e);
+        const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, d1));        // edm.py:384-385
+        const float xp = FADD(xh, FMUL(r.h, dc));                           // edm.py:389-390 (alpha = 1)
+        const float dp = FSUB(FMUL(r.inv_tp, xp), FMUL(r.inv_tp, d2));      // edm.py:414-417
+        const float avg = FADD(FMUL(0.5f, dc), FMUL(0.5f, dp));
+        return FADD(xh, FMUL(r.h, avg));                                    // edm.py:418-422
+    }
+};
 void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
                      StatePtrs x, Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(heun_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xhat, D1, D2, tab, ctl, flags, x, d);
+    launch_elem(Heun{xhat, D1, D2, tab, ctl, flags}, x, d, s);
 }
 // second-order multistep update (DPM-Solver++ 2M in EDM variables, sigma(t) = t): the Euler update above on the extrapolated estimate
 // D~ = D + c (D - Dprev), c = the row's ms_coef.  Where D == Dprev (a known entry of a conditioned run, the sanity-check mode) D~ is D
-// exactly.  A separate kernel: steps with c = 0 keep launching the Euler kernel.
-__global__ void multistep_tab_kernel(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const StepRow *tab, const RunCtl *ctl,
-                                     const uint8_t *flags, StatePtrs x, Dims d) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total_elems(d)) return;
-    const StepRow r = tab[ctl->step];
-    const ElemIdx e = elem_index(idx, d, flags);
-    const float xh = e.is_adj ? xhat.adj[e.off] : xhat.node[e.off];
-    const float dn = e.is_adj ? D.adj[e.off] : D.node[e.off];
-    const float dp = e.is_adj ? Dprev.adj[e.off] : Dprev.node[e.off];
-    const float dt = FADD(dn, FMUL(r.ms_coef, FSUB(dn, dp)));
-    const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, dt));
-    const float v = e.valid ? FADD(xh, FMUL(r.h, dc)) : 0.f;
-    if (e.is_adj) x.adj[e.off] = v; else x.node[e.off] = v;
-}
+// exactly.  Steps with c = 0 launch Euler.
+struct Multistep {
+    CStatePtrs xhat, D, Dprev; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+    __device__ StepRow uniform() const { return tab[ctl->step]; }
+    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &) const {
+        const float xh = ld(xhat, e), dn = ld(D, e), dp = ld(Dprev, e);
+        const float dt = FADD(dn, FMUL(r.ms_coef, FSUB(dn, dp)));
+        const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, dt));
+        return FADD(xh, FMUL(r.h, dc));
+    }
+};
 void launch_multistep_tab(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
                           StatePtrs x, Dims d, hipStream_t s) {
-    const size_t n = total_elems(d);
-    DSG_LAUNCH(multistep_tab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xhat, D, Dprev, tab, ctl, flags, x, d);
+    launch_elem(Multistep{xhat, D, Dprev, tab, ctl, flags}, x, d, s);
 }
 // the table has one row per SCHEDULE index; the executed step's row names it (a resampling walk visits an index more than once)
 __global__ void step_row_kernel(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst) {
