@@ -2982,6 +2982,140 @@ int dsg_debug_fused_attn96_f32(int32_t B, int32_t res, int32_t ws, int32_t shift
     return debug_finish(true, s);
 }
 
+// ---- the fp32 forward's edge and row kernels on their own (test hooks; tests/test_edge_kernels.py) ----
+static bool mult4(int32_t v) { return v >= 0 && v % 4 == 0; }
+
+int dsg_debug_patch_embed_f32(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kp, const float *adj,
+                              const float *node, const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags,
+                              const float *Wp, const float *bias, const float *gam, const float *bet, const float *aff, int32_t aff_ld,
+                              int32_t aff_off, int32_t aff_off2, float *x, const int32_t *run_list, const int32_t *run_cnt, void *stream) {
+    // the kernel gathers (self_cond ? 2 : 1) (c_adj + 2 c_node) channels into Kp / 8 fragments and reads the (scale | shift) rows 16 bytes
+    // at a time; a run list addresses 8 consecutive tokens of one row of the grid and comes with its count
+    if (B < 1 || N < 1 || c_adj < 1 || c_node < 1 || (Kp != 32 && Kp != 64) || (self_cond ? 2 : 1) * (c_adj + 2 * c_node) > Kp) return DSG_ERR_INVALID;
+    if (!adj || !node || !flags || !Wp || !bias || !gam || !bet || !aff || !x) return DSG_ERR_INVALID;
+    if (!mult4(aff_ld) || !mult4(aff_off) || (aff_off2 >= 0 && !mult4(aff_off2))) return DSG_ERR_INVALID;
+    if (run_list && (!run_cnt || N % 8 != 0)) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish(launch_fused_patch_embed96(adj, node, sc_adj, sc_node, has_sc, flags, Wp, bias, gam, bet, aff, aff_ld, aff_off, aff_off2, x, B,
+                                                   N, c_adj, c_node, self_cond, Kp, s, nullptr, run_list, run_cnt), s);
+}
+
+int dsg_debug_assemble_f32(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kp, const float *adj, const float *node,
+                           const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags, float *out, void *stream) {
+    if (B < 1 || N < 1 || c_adj < 1 || c_node < 1 || Kp < (self_cond ? 2 : 1) * (c_adj + 2 * c_node) || !adj || !node || !flags || !out)
+        return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    launch_assemble(adj, node, sc_adj, sc_node, has_sc, flags, out, B, N, c_adj, c_node, self_cond, Kp, s);
+    return debug_finish(true, s);
+}
+
+int dsg_debug_readout_f32(int32_t B, int32_t N, int32_t c_adj, const float *x, const float *gam, const float *bet, const float *Wfp, const float *fa,
+                          const float *W2p, const float *f2, const uint8_t *flags, float *out_adj, float *pool_part, float *pool_ext, void *stream) {
+    // the second product's packed weight has 32 output rows: the fold's limit on C_adj (dsg_finalize_weights)
+    if (B < 1 || N < 1 || c_adj < 1 || c_adj > 32 || !x || !gam || !bet || !Wfp || !fa || !W2p || !f2 || !flags || !out_adj || !pool_part || !pool_ext)
+        return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    launch_fused_readout96(x, gam, bet, Wfp, fa, W2p, f2, flags, out_adj, pool_part, pool_ext, B, N, c_adj, s, false);
+    return debug_finish(true, s);
+}
+
+int dsg_debug_head_f32(int32_t kind, int32_t B, int32_t N, int32_t E, int32_t c_out, const float *h, const float *W, const float *bias,
+                       const uint8_t *flags, float *out, void *stream) {
+    if (B < 1 || N < 1 || E < 1 || !h || !flags || !out || kind < DSG_HEAD_ADJ || kind > DSG_HEAD_NODE) return DSG_ERR_INVALID;
+    if (kind != DSG_HEAD_POOL && (c_out < 1 || !W || !bias)) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (kind == DSG_HEAD_ADJ) launch_head_adj(h, W, bias, flags, out, B, N, E, c_out, s);
+    else if (kind == DSG_HEAD_POOL) launch_pool(h, flags, out, B, N, E, s);
+    else launch_head_node(h, W, bias, flags, out, B, N, E, c_out, s);
+    return debug_finish(true, s);
+}
+
+int dsg_debug_row_f32(int32_t kind, int32_t B, int32_t t, int32_t C, float *x, const float *g, const float *b, const float *pg, const float *pb,
+                      const float *aff, int32_t aff_ld, int32_t aff_off, const float *ln_part, int32_t nparts, float *y, float *stats,
+                      const int32_t *run_list, const int32_t *run_cnt, void *stream) {
+    // one wave holds a row in 24 registers per lane (ROW_MAXV in kernels.hip): 1536 channels at most, in float4 pieces
+    constexpr int ROW_LIMIT = 1536;
+    if (B < 1 || t < 1 || C < 4 || C % 4 != 0 || !x) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    switch (kind) {
+        case DSG_ROW_MOD_STATS:
+            if (C > ROW_LIMIT || !aff || !stats || !mult4(aff_ld) || !mult4(aff_off)) return DSG_ERR_INVALID;
+            launch_mod_stats(x, aff, aff_ld, aff_off, stats, B, t, C, s);
+            break;
+        case DSG_ROW_LN_STATS:
+            if (C > ROW_LIMIT || !stats) return DSG_ERR_INVALID;
+            launch_ln_stats(x, stats, B * t, C, s);
+            break;
+        case DSG_ROW_LN_MOD:
+            if (C > ROW_LIMIT || !g || !b || !aff || !y || aff_ld < 0 || aff_off < 0) return DSG_ERR_INVALID;
+            launch_ln_mod(x, g, b, aff, aff_ld, aff_off, y, B, t, C, s);
+            break;
+        case DSG_ROW_MERGE_LN:      // t = tokens per side of the fine grid; the merged row has 4 C channels
+            if (4 * C > ROW_LIMIT || t % 2 != 0 || !g || !b || !y) return DSG_ERR_INVALID;
+            launch_merge_ln(x, g, b, y, B, t, C, s, false);
+            break;
+        case DSG_ROW_BREAKUP_LN:    // t = tokens per side of the coarse grid, C = the row's width D: four chunks of D / 4, each in float4 pieces
+            if (C > ROW_LIMIT || C % 16 != 0 || !g || !b || !pg || !pb || !y) return DSG_ERR_INVALID;
+            if (run_list && (!run_cnt || (B * t * t) % 8 != 0)) return DSG_ERR_INVALID;
+            launch_breakup_ln(x, g, b, pg, pb, y, B, t, C, s, false, run_list, run_cnt);
+            break;
+        case DSG_ROW_MERGE_NORM_RUNS:   // t = tokens per side of the fine grid; a run is 8 merged rows of one row of the merged grid
+            if (t % 16 != 0 || !ln_part || nparts < 1 || !y || !run_list || !run_cnt) return DSG_ERR_INVALID;
+            launch_merge_norm_runs(x, ln_part, nparts, y, B, t, C, run_list, run_cnt, s);
+            break;
+        default: return DSG_ERR_INVALID;
+    }
+    return debug_finish(true, s);
+}
+
+int dsg_debug_window_broadcast_f32(int32_t B, int32_t res, int32_t C, float *x, float *skip, float *stats, int32_t nparts, const int32_t *copy_list,
+                                   const int32_t *copy_cnt, const int32_t *rep, const float *tab_base, int32_t tab_entries, int64_t tab_stride,
+                                   int32_t off_x, int32_t off_skip, int32_t off_st, int32_t mode, int32_t step, int32_t n_steps,
+                                   const int32_t *sched, void *stream) {
+    // windows of 8 x 8 tokens, rows in float4 pieces, statistics in float2 pairs
+    if (B < 1 || res < 8 || res % 8 != 0 || C < 4 || C % 4 != 0 || !x || !copy_list || !copy_cnt || (stats && nparts < 1)) return DSG_ERR_INVALID;
+    if (mode < DD_OFF || mode > DD_TABLE || (mode == DD_TABLE && !tab_base) || (mode != DD_TABLE && !rep)) return DSG_ERR_INVALID;
+    if (tab_base && (tab_entries < 1 || n_steps < 1 || !sched || tab_stride < 0 || tab_stride % 4 != 0 || !mult4(off_x) || !mult4(off_skip) ||
+                     off_st < 0 || off_st % 2 != 0))
+        return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    PureTabSrc tab;
+    StepRow *d_steps = nullptr;
+    RunCtl *d_ctl = nullptr;
+    int *d_mode = nullptr;
+    hipError_t e = hipSuccess;
+    if (tab_base) {   // the small device records the kernel reads: tab.steps[].sched, tab.ctl->step / n_steps, *tab.mode
+        std::vector<StepRow> rows((size_t)n_steps);
+        for (int i = 0; i < n_steps; i++) { rows[i] = StepRow{0.f, 0.f, 0.f, 0.f, 0.f, sched[i], 0.f, 0}; }
+        RunCtl ctl{step, n_steps, 0ull, nullptr, nullptr, nullptr};
+        e = hipMalloc((void **)&d_steps, sizeof(StepRow) * rows.size());
+        if (e == hipSuccess) e = hipMalloc((void **)&d_ctl, sizeof(RunCtl));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_mode, sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(d_steps, rows.data(), sizeof(StepRow) * rows.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_ctl, &ctl, sizeof(RunCtl), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_mode, &mode, sizeof(int), hipMemcpyHostToDevice);
+        tab.base = tab_base; tab.stride = (size_t)tab_stride; tab.entries = tab_entries;
+        tab.off_x = off_x; tab.off_skip = off_skip; tab.off_st = off_st;
+        tab.steps = d_steps; tab.ctl = d_ctl; tab.mode = d_mode;
+    }
+    int rc = DSG_ERR_HIP;
+    if (e == hipSuccess) {
+        launch_window_broadcast(x, skip, stats, nparts, B, res, C, copy_list, copy_cnt, rep, s, tab);
+        rc = debug_finish(true, s);
+    }
+    (void)hipFree(d_steps); (void)hipFree(d_ctl); (void)hipFree(d_mode);
+    return rc;
+}
+
+int dsg_debug_window_harvest_f32(int32_t n, int32_t res, int32_t C, const float *x, const float *skip, const float *stats, int32_t nparts, float *dst,
+                                 int64_t stride, int32_t off_x, int32_t off_skip, int32_t off_st, void *stream) {
+    if (n < 1 || res < 8 || res % 8 != 0 || C < 4 || C % 4 != 0 || !x || !dst || (stats && nparts < 1)) return DSG_ERR_INVALID;
+    if (stride < 0 || stride % 4 != 0 || !mult4(off_x) || (skip && !mult4(off_skip)) || (stats && (off_st < 0 || off_st % 2 != 0))) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    launch_window_harvest(x, skip, stats, nparts, n, res, C, dst, (size_t)stride, off_x, off_skip, off_st, s);
+    return debug_finish(true, s);
+}
+
 // ---- the training kernels on their own (test hooks, csrc/train_kernels.hip): no handle, device pointers, one call of the launcher,
 // then the stream is synchronised; a form the launcher refuses (it marks the stream's scratch) is DSG_ERR_INVALID, a HIP error
 // DSG_ERR_HIP ----

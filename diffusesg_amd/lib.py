@@ -22,6 +22,8 @@ EXPORTS = [
     "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
     "dsg_sample_seeded", "dsg_gen_noise_seeded",
     "dsg_precond_vjp", "dsg_debug_t_assemble_bwd",
+    "dsg_debug_patch_embed_f32", "dsg_debug_assemble_f32", "dsg_debug_readout_f32", "dsg_debug_head_f32", "dsg_debug_row_f32",
+    "dsg_debug_window_broadcast_f32", "dsg_debug_window_harvest_f32",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -71,6 +73,10 @@ class DsgTProb(C.Structure):
 
 T_GROUP_MAX = 32
 TGROUP_NT, TGROUP_TN, TGROUP_NN, TGROUP_NN_SUM, TGROUP_SUM, TGROUP_COLSUM, TGROUP_TT = range(7)   # DSG_TGROUP_* of include/dsg.h
+
+DD_OFF, DD_GRAPH, DD_BATCH, DD_TABLE = range(4)                                                    # DedupMode of csrc/kernels.h (mode of dsg_debug_window_broadcast_f32)
+HEAD_ADJ, HEAD_POOL, HEAD_NODE = range(3)                                                          # DSG_HEAD_* (dsg_debug_head_f32)
+ROW_MOD_STATS, ROW_LN_STATS, ROW_LN_MOD, ROW_MERGE_LN, ROW_BREAKUP_LN, ROW_MERGE_NORM_RUNS = range(6)   # DSG_ROW_* (dsg_debug_row_f32)
 
 WALK_MAX_STEPS = 1 << 20   # DSG_WALK_MAX_STEPS
 
@@ -159,6 +165,13 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_debug_window_attn_f32.argtypes = [i32] * 5 + [vp] * 4
     L.dsg_debug_fused_mlp_f32.argtypes = [i32, i32] + [vp] * 11
     L.dsg_debug_fused_attn96_f32.argtypes = [i32] * 4 + [vp, vp, i32, i32] + [vp] * 7 + [i32, vp, vp, vp]
+    L.dsg_debug_patch_embed_f32.argtypes = [i32] * 6 + [vp] * 11 + [i32] * 3 + [vp] * 4
+    L.dsg_debug_assemble_f32.argtypes = [i32] * 6 + [vp] * 8
+    L.dsg_debug_readout_f32.argtypes = [i32] * 3 + [vp] * 12
+    L.dsg_debug_head_f32.argtypes = [i32] * 5 + [vp] * 6
+    L.dsg_debug_row_f32.argtypes = [i32] * 4 + [vp] * 6 + [i32, i32, vp, i32] + [vp] * 5
+    L.dsg_debug_window_broadcast_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32] + [vp] * 4 + [i32, i64] + [i32] * 6 + [vp, vp]
+    L.dsg_debug_window_harvest_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32, vp, i64] + [i32] * 3 + [vp]
     L.dsg_debug_t_gemm.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.POINTER(i32), vp]
     L.dsg_debug_t_attn.argtypes = [i32] * 6 + [vp] * 6 + [i32, vp]
     L.dsg_debug_t_ln.argtypes = [i32] * 4 + [vp] * 13

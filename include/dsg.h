@@ -40,7 +40,7 @@ extern "C" {
  * at load time (diffusesg_amd/lib.py does): round 3 inserted `iou_loss_type` into three entries, and a caller built against the older
  * header would otherwise pass shifted arguments without any error.  History: 1-3 = rounds 1-3 (unversioned), 4 = round 4
  * (dsg_decode with an encoding argument, dsg_abi_version, dsg_last_error(NULL)).  dsg_sample_seeded, dsg_gen_noise_seeded and the option
- * "batch_invariant" were added without touching an existing argument list: still 4. */
+ * "batch_invariant" were added without touching an existing argument list: still 4; so were the dsg_debug_*_f32 test hooks. */
 #define DSG_ABI_VERSION 4
 
 typedef enum {
@@ -499,6 +499,59 @@ int dsg_debug_fused_attn96_f32(int32_t B, int32_t res, int32_t ws, int32_t shift
                                int32_t aff_off, const float *gam, const float *bet, const float *Wqp, const float *bqkv, const float *biasT,
                                const float *Wpp, const float *bproj, int32_t premod, const int32_t *win_list, const int32_t *win_cnt,
                                void *stream);
+
+/* The fp32 forward's edge and row kernels on their own (test hooks, csrc/kernels.hip; same rules as above; fp32 forms only: no bf16
+ * read-out fragments, no bf16 outputs).  tests/test_edge_kernels.py compares every output element with float64.
+ * dsg_debug_patch_embed_f32: the fused PatchEmbed (E = 96): input assembly [sc_adj, adj, sc_node(i), node(i), sc_node(j), node(j)] ->
+ *   Wp . in + bias -> LayerNorm_96(gam, bet) -> silu(shift + n (1 + scale)), (scale | shift) = aff[b aff_ld + aff_off + ...], and once more
+ *   with the row at aff_off2 when aff_off2 >= 0 -> x [B N^2, 96].  Wp: patch_embed.proj.weight zero-padded to [96, Kp] ALREADY in fragment
+ *   order (the pe_wp loop of dsg_finalize_weights); Kp 32 or 64; aff_ld and the offsets multiples of 4.  sc_adj / sc_node may be NULL;
+ *   has_sc (device int32) NULL: they are used when given; *has_sc == 0: they are not read.  run_list / run_cnt (device): only those runs
+ *   of 8 tokens (N % 8 == 0; -1 pads to a multiple of 4 at least).
+ * dsg_debug_assemble_f32: the same gathered input on its own, token-major [B N^2, Kp], zero-padded. */
+int dsg_debug_patch_embed_f32(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kp, const float *adj,
+                              const float *node, const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags,
+                              const float *Wp, const float *bias, const float *gam, const float *bet, const float *aff, int32_t aff_ld,
+                              int32_t aff_off, int32_t aff_off2, float *x, const int32_t *run_list, const int32_t *run_cnt, void *stream);
+int dsg_debug_assemble_f32(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kp, const float *adj, const float *node,
+                           const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags, float *out, void *stream);
+/* the fused read-out (E = 96, c_adj <= 32): x [B N^2, 96] -> out_adj [B, c_adj, N, N] = valid (F2 gelu(Fa LN(x) + fa) + f2), and the pooling
+ * pool_ext [B N, 128] = ((1/N) sum_j valid LN(x) | f_i (#valid) / N | 0 ..).  Wfp / W2p: the folded Fa [96, 96] and F2 zero-padded to
+ * [32, 96] ALREADY in fragment order (the fap / f2p loops of dsg_finalize_weights); pool_part: scratch [B N][(N + 30) / 32 + 1][96].
+ * Rows of x of tokens with !(f_i && f_j) are not read into the result. */
+int dsg_debug_readout_f32(int32_t B, int32_t N, int32_t c_adj, const float *x, const float *gam, const float *bet, const float *Wfp, const float *fa,
+                          const float *W2p, const float *f2, const uint8_t *flags, float *out_adj, float *pool_part, float *pool_ext, void *stream);
+/* the unfused read-out tails.  DSG_HEAD_ADJ: h [B N^2, E] -> out [B, c_out, N, N] = valid (h W^T + bias); DSG_HEAD_POOL: h [B N^2, E] -> out
+ * [B N, E] = (1/N) sum_j valid h (W, bias, c_out unused); DSG_HEAD_NODE: h [B N, E] -> out [B, N, c_out] = f_i (h W^T + bias). */
+enum { DSG_HEAD_ADJ = 0, DSG_HEAD_POOL = 1, DSG_HEAD_NODE = 2 };
+int dsg_debug_head_f32(int32_t kind, int32_t B, int32_t N, int32_t E, int32_t c_out, const float *h, const float *W, const float *bias,
+                       const uint8_t *flags, float *out, void *stream);
+/* the one-wave-per-row passes; rows of at most 1536 channels, C % 4 == 0; unused pointers NULL.
+ *   DSG_ROW_MOD_STATS        x [B t, C] <- silu(shift + x (1 + scale)) in place, stats [B t, 2] = (mean, rstd) of the new row
+ *   DSG_ROW_LN_STATS         stats [B t, 2] = (mean, rstd) of x's rows
+ *   DSG_ROW_LN_MOD           y = silu(shift + LN(x; g, b) (1 + scale))
+ *   DSG_ROW_MERGE_LN         t = fine side: y [B (t/2)^2, 4C] = LN_4C(cat[x(2i,2j), x(2i+1,2j), x(2i,2j+1), x(2i+1,2j+1)]; g, b); 4C <= 1536
+ *   DSG_ROW_BREAKUP_LN       t = coarse side, C = D: LN_D(x row; g, b), chunk q -> token (2i + (q & 1), 2j + (q >> 1)) of y [B (2t)^2, D/4],
+ *                            LN_{D/4}(pg, pb); run_list / run_cnt: only those runs of 8 coarse rows (-1: none)
+ *   DSG_ROW_MERGE_NORM_RUNS  t = fine side (t % 16 == 0): the merged rows of the listed runs, y = x rstd - mean rstd with the statistics
+ *                            from the four fine rows' ln_part [B t^2][nparts][2]; run_list / run_cnt required
+ * (scale | shift) = aff[b aff_ld + aff_off + ...], b = row / t. */
+enum { DSG_ROW_MOD_STATS = 0, DSG_ROW_LN_STATS = 1, DSG_ROW_LN_MOD = 2, DSG_ROW_MERGE_LN = 3, DSG_ROW_BREAKUP_LN = 4, DSG_ROW_MERGE_NORM_RUNS = 5 };
+int dsg_debug_row_f32(int32_t kind, int32_t B, int32_t t, int32_t C, float *x, const float *g, const float *b, const float *pg, const float *pb,
+                      const float *aff, int32_t aff_ld, int32_t aff_off, const float *ln_part, int32_t nparts, float *y, float *stats,
+                      const int32_t *run_list, const int32_t *run_cnt, void *stream);
+/* the pure-window copies.  Broadcast: every window of copy_list (device, *copy_cnt entries, b nW + w) of x [B res^2, C], skip (or NULL) and
+ * stats [B res^2][nparts][2] (or NULL) is filled from window rep[b] (device [B], a global window id; -1: none), or, when mode == 3 (the
+ * table mode) from table entry sched[min(step, n_steps - 1)] (clamped to tab_entries - 1): an entry is tab_stride floats with 64 x C rows
+ * of x at off_x, of the skip at off_skip and 64 x nparts pairs at off_st, tokens in window order.  tab_base NULL: no table.  sched is a
+ * HOST array of n_steps schedule indices; the call builds the device records the kernel reads and frees them before it returns.
+ * Harvest: window 0 of each of the first n graphs -> entry g of dst in that layout. */
+int dsg_debug_window_broadcast_f32(int32_t B, int32_t res, int32_t C, float *x, float *skip, float *stats, int32_t nparts, const int32_t *copy_list,
+                                   const int32_t *copy_cnt, const int32_t *rep, const float *tab_base, int32_t tab_entries, int64_t tab_stride,
+                                   int32_t off_x, int32_t off_skip, int32_t off_st, int32_t mode, int32_t step, int32_t n_steps,
+                                   const int32_t *sched, void *stream);
+int dsg_debug_window_harvest_f32(int32_t n, int32_t res, int32_t C, const float *x, const float *skip, const float *stats, int32_t nparts, float *dst,
+                                 int64_t stride, int32_t off_x, int32_t off_skip, int32_t off_st, void *stream);
 
 /* The training kernels on their own (test hooks, csrc/train_kernels.hip; no handle, device pointers, synchronise `stream`;
  * DSG_ERR_INVALID where the launcher refuses the form, DSG_ERR_HIP on a HIP error, never an abort).  tests/test_train_kernels.py
