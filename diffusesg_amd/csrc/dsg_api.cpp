@@ -209,8 +209,9 @@ struct dsg_handle_s {
     std::vector<Tap> taps;
     // training form (dsg_train_*): saved-activation arena and backward scratch, owned by the handle and kept between calls
     // (hipMalloc / hipFree of ~10 GB per iteration cost more than a tenth of it); they only grow (train_buf).  train_io: the entries'
-    // preconditioned inputs, F and dL/dF; train_vjp: d_tok | W_img | coef of dsg_precond_vjp
-    DevBuf train_arena, train_scr, train_io, train_vjp;
+    // preconditioned inputs, F and dL/dF; train_vjp: d_tok | W_img | coef of dsg_precond_vjp; train_ode: dsg_ode_run's states, probe,
+    // gradient, sigma rows, step table and control block
+    DevBuf train_arena, train_scr, train_io, train_vjp, train_ode;
     int *train_const = nullptr;                                   // device {0, 1}: the "self-conditioning present" switch of launch_assemble
     // dsg_train_bind_params: parameters the training form reads in place (the optimiser's own device tensors) instead of the handle's copies
     std::unordered_map<std::string, const float *> train_params;
@@ -721,7 +722,7 @@ void dsg_destroy(dsg_handle h) {
     for (float *q : {h->tab_sig, h->tab_cn, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff}) if (q) (void)hipFree(q);
     drop_graphs(h);
     if (h->tab_step) (void)hipFree(h->tab_step);
-    for (DevBuf *b : {&h->train_arena, &h->train_scr, &h->train_io, &h->train_vjp}) if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : {&h->train_arena, &h->train_scr, &h->train_io, &h->train_vjp, &h->train_ode}) if (b->p) (void)hipFree(b->p);
     if (h->train_const) (void)hipFree(h->train_const);
     for (auto &kv : h->ws) {
         if (kv.second->cap_stream) (void)hipStreamDestroy(kv.second->cap_stream);
@@ -4098,6 +4099,167 @@ int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node
     if ((rc = train_finish(h, ok, s)) != DSG_OK) return rc;
     if (!t_assemble_bwd(ig.d_tok, Np, flags, coef, coef + B, g_a, g_n, out_grad_adj, out_grad_node, B, N, Ca, Cn, false, s))
         return fail(h, DSG_ERR_INVALID, "the assemble backward refused B %d, N %d, C_adj %d, C_node %d, pitch %d", B, N, Ca, Cn, Np);
+    HIP_TRY(h, hipGetLastError());
+    return DSG_OK;
+}
+
+// Host-side plan of an ODE run (include/dsg.h): the evaluation levels in execution order and the quadrature weights of int n(t)/t dt.
+// h = b - a is the fp32 difference the step table holds; the weights are formed in double from the widened fp32 values.
+int32_t dsg_ode_evals(const dsg_sampler_cfg *c, const dsg_ode_cfg *ode, float *t_eval, double *weight, int32_t cap) {
+    if (!c || !ode || c->num_steps < 2) return DSG_ERR_INVALID;
+    if (ode->direction != DSG_ODE_ENCODE && ode->direction != DSG_ODE_DECODE) return DSG_ERR_INVALID;
+    if (ode->probe < DSG_ODE_PROBE_NONE || ode->probe > DSG_ODE_PROBE_GAUSSIAN) return DSG_ERR_INVALID;
+    if (solver_2m(c)) return DSG_ERR_INVALID;
+    const int T = c->num_steps;
+    std::vector<float> t(T), nz(T);
+    dsg_sigma_schedule(c, nullptr, t.data(), nz.data(), nullptr);
+    for (int i = 0; i < T; i++) if (nz[i] != 0.f) return DSG_ERR_INVALID;
+    const bool heun = solver_heun(c);
+    const int32_t n = (heun ? 2 : 1) * (T - 1);
+    if (!t_eval && !weight) return n;
+    if (cap < n) return DSG_ERR_INVALID;
+    int e = 0;
+    for (int j = 0; j < T - 1; j++) {
+        const int k = ode->direction == DSG_ODE_ENCODE ? T - 1 - j : j;
+        const float a = t[k], b = ode->direction == DSG_ODE_ENCODE ? t[k - 1] : t[k + 1];
+        volatile float hs = b - a;
+        const double ah = std::fabs((double)hs);
+        if (t_eval) t_eval[e] = a;
+        if (weight) weight[e] = heun ? ah / (2.0 * (double)a) : ah / (double)a;
+        e++;
+        if (heun) {
+            if (t_eval) t_eval[e] = b;
+            if (weight) weight[e] = ah / (2.0 * (double)b);
+            e++;
+        }
+    }
+    return n;
+}
+
+int dsg_debug_graph_dot(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *a_adj, const float *a_node, const float *b_adj,
+                        const float *b_node, const uint8_t *flags, double *out, void *stream) {
+    if (!a_adj || !a_node || !b_adj || !b_node || !flags || !out) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (!t_graph_dot(a_adj, a_node, b_adj, b_node, flags, out, B, N, c_adj, c_node, s)) return DSG_ERR_INVALID;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return DSG_ERR_HIP;
+    return DSG_OK;
+}
+
+// The probability-flow ODE between the schedule's levels (include/dsg.h).  Every evaluation is dsg_precond_vjp's chain on the state the
+// run holds: precond_in, the training-form forward, precond_out, and with a probe the backward of eps, the assemble backward with a
+// ZERO c_skip array (what it writes is then the network part c_in c_out J_F^T eps alone) and the per-graph contraction with eps.  The
+// updates are the sampler's Euler / Heun element operations on a StepRow table of this run's (a, b) pairs, driven by a device step
+// counter.  Everything is enqueued on `stream`; the only synchronisation is the one the host seed array needs.
+int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode, int32_t B, const uint8_t *flags, const float *x_adj,
+                const float *x_node, const uint64_t *graph_seeds, const float *probe_adj, const float *probe_node, float *out_adj,
+                float *out_node, float *out_probe_adj, float *out_probe_node, double *out_net_trace, void *stream) {
+    if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (!cfg || !ode || B < 1 || !flags || !x_adj || !x_node || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null argument");
+    if (cfg->num_steps < 2) return fail(h, DSG_ERR_INVALID, "dsg_ode_run needs num_steps >= 2 (it steps between the schedule's levels; num_steps is %d)", cfg->num_steps);
+    if (solver_2m(cfg)) return fail(h, DSG_ERR_INVALID, "dsg_ode_run has no multistep solver (heun = %d): use DSG_SOLVER_EULER or DSG_SOLVER_HEUN", DSG_SOLVER_DPMPP_2M);
+    if (ode->direction != DSG_ODE_ENCODE && ode->direction != DSG_ODE_DECODE) return fail(h, DSG_ERR_INVALID, "direction %d", ode->direction);
+    if (ode->probe < DSG_ODE_PROBE_NONE || ode->probe > DSG_ODE_PROBE_GAUSSIAN) return fail(h, DSG_ERR_INVALID, "probe %d", ode->probe);
+    const int32_t n_evals = dsg_ode_evals(cfg, ode, nullptr, nullptr, 0);
+    if (n_evals < 0)   // everything else was checked above: what is left is a level with churn noise
+        return fail(h, DSG_ERR_INVALID, "dsg_ode_run follows the probability-flow ODE and needs a schedule that draws no churn noise at any level: "
+                    "set S_churn = 0 (S_churn is %g)", (double)cfg->S_churn);
+    const bool probing = ode->probe != DSG_ODE_PROBE_NONE;
+    if ((probe_adj == nullptr) != (probe_node == nullptr)) return fail(h, DSG_ERR_INVALID, "probe_adj and probe_node go together");
+    if ((out_probe_adj == nullptr) != (out_probe_node == nullptr)) return fail(h, DSG_ERR_INVALID, "out_probe_adj and out_probe_node go together");
+    if (probing && !probe_adj && !graph_seeds) return fail(h, DSG_ERR_INVALID, "a probe needs graph_seeds (host, one per graph) or recorded probe_adj / probe_node");
+    if (probing && !out_net_trace) return fail(h, DSG_ERR_INVALID, "a probe needs out_net_trace (device, [n_evals = %d, B] doubles)", n_evals);
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d = dims_of(h, B);
+    const int N = h->N, Ca = h->Ca, Cn = h->Cn, E = h->E;
+    const size_t M0 = (size_t)B * N * N, na = (size_t)B * Ca * N * N, nn = (size_t)B * N * Cn;
+    if (!t_assemble_bwd_ok(Cn) || (size_t)B * N > 0x7fffffffu)
+        return fail(h, DSG_ERR_INVALID, "input gradients are not built for C_node %d (partial sums beyond LDS) or B * N = %zu", Cn, (size_t)B * N);
+    const bool heun = solver_heun(cfg);
+    const int n_steps = cfg->num_steps - 1;
+    // host tables: the evaluation levels as [n_evals, B] sigma rows, the (a, b) pairs as StepRow rows
+    std::vector<float> t_eval(n_evals), sig((size_t)n_evals * B);
+    dsg_ode_evals(cfg, ode, t_eval.data(), nullptr, n_evals);
+    for (int e = 0; e < n_evals; e++) for (int b = 0; b < B; b++) sig[(size_t)e * B + b] = t_eval[e];
+    std::vector<float> lv(cfg->num_steps);
+    dsg_sigma_schedule(cfg, nullptr, lv.data(), nullptr, nullptr);
+    std::vector<StepRow> rows(n_steps);
+    for (int j = 0; j < n_steps; j++) {
+        const int k = ode->direction == DSG_ODE_ENCODE ? cfg->num_steps - 1 - j : j;
+        const float a = lv[k], b = ode->direction == DSG_ODE_ENCODE ? lv[k - 1] : lv[k + 1];
+        volatile float hs = b - a;
+        rows[j] = StepRow{0.f, a, 1.0f / a, 1.0f / b, hs, k, 0.f, 0};
+    }
+    // buffers: the training entries' io and vjp regions, and this entry's own
+    const int Np = t_live_cols_width(Ca, Cn);
+    TrainIo io;
+    TrainInputGrad ig{nullptr, nullptr, Np};
+    float *coef = nullptr, *zero = nullptr, *sig_d = nullptr, *tab_f = nullptr, *ctl_f = nullptr, *seeds_f = nullptr;
+    StatePtrs x{}, xp{}, D1{}, D2{}, eps{}, g{};
+    auto state = [&](TArena &A, bool on) { StatePtrs p{nullptr, nullptr}; if (on) { p.adj = A.get(na); p.node = A.get(nn); } return p; };
+    if (!train_io(h, B, s, io) ||
+        !train_carve(h->train_vjp, s, [&](TArena &A) { ig.d_tok = A.get(M0 * Np); ig.img = A.get((size_t)E * Np); coef = A.get(2 * (size_t)B); }) ||
+        !train_carve(h->train_ode, s, [&](TArena &A) {
+            x = state(A, true); D1 = state(A, true); xp = state(A, heun); D2 = state(A, heun); eps = state(A, probing); g = state(A, probing);
+            zero = A.get(B); sig_d = A.get((size_t)n_evals * B); tab_f = A.get((size_t)n_steps * (sizeof(StepRow) / sizeof(float)));
+            ctl_f = A.get((sizeof(RunCtl) + sizeof(float) - 1) / sizeof(float)); seeds_f = A.get(2 * (size_t)B);
+        }))
+        return fail(h, DSG_ERR_HIP, "out of memory");
+    StepRow *tab = (StepRow *)tab_f;
+    RunCtl *ctl = (RunCtl *)ctl_f;
+    unsigned long long *seeds_d = (unsigned long long *)seeds_f;
+    TrainNet net{};
+    int rc = train_net_build(h, net, B, nullptr, nullptr, false, 0, nullptr, nullptr, s);
+    if (rc != DSG_OK) return rc;
+    // uploads, once
+    const RunCtl ctl_h{0, n_steps, 0ull, nullptr, nullptr, nullptr};
+    HIP_TRY(h, hipMemcpyAsync(sig_d, sig.data(), sizeof(float) * sig.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(tab, rows.data(), sizeof(StepRow) * rows.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(ctl, &ctl_h, sizeof(RunCtl), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(zero, 0, sizeof(float) * B, s));
+    if (probing && !probe_adj) HIP_TRY(h, hipMemcpyAsync(seeds_d, graph_seeds, sizeof(unsigned long long) * (size_t)B, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipStreamSynchronize(s));   // the tables above are this call's host memory, the seeds the caller's
+    // the start state, masked; the probe
+    launch_init(CStatePtrs{x_adj, x_node}, CStatePtrs{nullptr, nullptr}, 1.0f, 0, nullptr, 0u, flags, x, d, s);
+    if (probing) {
+        if (probe_adj) launch_init(CStatePtrs{probe_adj, probe_node}, CStatePtrs{nullptr, nullptr}, 1.0f, 0, nullptr, 0u, flags, eps, d, s);
+        else launch_probe(ode->probe == DSG_ODE_PROBE_RADEMACHER, seeds_d, DSG_ODE_PROBE_STREAM, flags, eps, d, s);
+        if (out_probe_adj) {
+            HIP_TRY(h, hipMemcpyAsync(out_probe_adj, eps.adj, sizeof(float) * na, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(out_probe_node, eps.node, sizeof(float) * nn, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    const CStatePtrs ceps{eps.adj, eps.node};
+    bool ok = hipGetLastError() == hipSuccess;
+    g_fixed_tiles = h->opt_batch_invariant;   // the training-form GEMMs: one route at every batch size (t_gemm)
+    // D = D(at, level e) into `dst`; with a probe also row e of the traces
+    auto evaluate = [&](CStatePtrs at, int e, StatePtrs dst) {
+        const float *sg = sig_d + (size_t)e * B;
+        launch_precond_in(at, sg, StatePtrs{io.in_a, io.in_n}, io.cn, d, s);
+        ok = ok && train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, nullptr, nullptr}, StatePtrs{io.F_a, io.F_n}, s);
+        if (!ok) return;
+        launch_precond_out(at, CStatePtrs{io.F_a, io.F_n}, sg, flags, dst, d, s);
+        if (!probing) return;
+        t_precond_bwd(ceps.adj, ceps.node, sg, flags, io.dF_a, io.dF_n, coef, B, N, Ca, Cn, s);
+        ok = ok && train_backward(net, TRAIN_INPUT_GRADS, flags, CStatePtrs{io.dF_a, io.dF_n}, &ig, s);
+        ok = ok && t_assemble_bwd(ig.d_tok, Np, flags, zero, coef + B, ceps.adj, ceps.node, g.adj, g.node, B, N, Ca, Cn, false, s);
+        ok = ok && t_graph_dot(ceps.adj, ceps.node, g.adj, g.node, flags, out_net_trace + (size_t)e * B, B, N, Ca, Cn, s);
+    };
+    const CStatePtrs cx{x.adj, x.node}, cxp{xp.adj, xp.node}, cD1{D1.adj, D1.node}, cD2{D2.adj, D2.node};
+    for (int j = 0, e = 0; j < n_steps && ok; j++) {
+        evaluate(cx, e++, D1);
+        if (!ok) break;
+        if (heun) {
+            launch_euler_tab(cx, cD1, tab, ctl, flags, xp, d, s);                  // x' = x_a + h f(x_a, a)
+            evaluate(cxp, e++, D2);
+            if (!ok) break;
+            launch_heun_tab(cx, cD1, cD2, tab, ctl, flags, x, d, s);               // x_b = x_a + (h / 2)(f(x_a, a) + f(x', b)), in place
+        } else launch_euler_tab(cx, cD1, tab, ctl, flags, x, d, s);                // in place: an element is read, then written, by one thread
+        launch_step_advance(ctl, s);
+    }
+    g_fixed_tiles = false;
+    if ((rc = train_finish(h, ok, s)) != DSG_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out_adj, x.adj, sizeof(float) * na, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(out_node, x.node, sizeof(float) * nn, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
 }

@@ -11,7 +11,8 @@ namespace dsg {
 extern thread_local bool g_dry_run;
 // Option "batch_invariant" (dsg_api.cpp sets it in front of every GEMM launch): a launcher that would pick its tile from the number of
 // rows keeps ONE tile at every size, so that which kernel computes a row never depends on the batch size.  Today that is the bf16
-// GEMM's 256x96 / 128x96 choice (kernels_lp.hip: launch_gemm_lp).
+// GEMM's 256x96 / 128x96 choice (kernels_lp.hip: launch_gemm_lp), and in training form -- where only dsg_ode_run sets it -- t_gemm's
+// MFMA route from 512 rows on (train_kernels.hip).
 extern thread_local bool g_fixed_tiles;
 
 enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2,
@@ -294,6 +295,10 @@ void launch_precond_out(CStatePtrs x, CStatePtrs F, const float *sigmas, const u
 // Each of the four combinations launches its own instantiation.
 void launch_init(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, const unsigned long long *graph_seeds, uint32_t stream,
                  const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
+// the probe of dsg_ode_run drawn on the device: Philox(graph_seeds[b], stream, local index) as launch_init draws it (gaussian), or
+// its sign, +1 where the draw is >= 0 and -1 elsewhere (rademacher); 0 at padded entries.  graph_seeds: device [B], required
+void launch_probe(bool rademacher, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags, StatePtrs eps, Dims d,
+                  hipStream_t s);
 
 // ---- reverse-loop kernels driven by a DEVICE step counter, so that one captured step body can be replayed for every step ----
 // Per-step scalars, computed on the host up front exactly as before (dsg_sigma_schedule) and uploaded once per sample() call: one row
@@ -409,7 +414,13 @@ void t_live_cols(const float *W, int Cin, float *img, int E, int Ca, int Cn, boo
 bool t_assemble_bwd_ok(int Cn);
 bool t_assemble_bwd(const float *d_tok, int ld, const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj,
                     const float *g_node, float *out_adj, float *out_node, int B, int N, int Ca, int Cn, bool self_cond, hipStream_t s);
-bool t_adam_step(int n, float *const *params, float *const *grads, float *const *m, float *const *v, const int64_t *numel, int step, float lr,
+// out[b] = sum over the live entries of graph b of a_j b_j (adjacency entries whose two nodes are valid, node entries of valid nodes; the
+// flags select, so whatever sits at a padded entry -- t_assemble_bwd leaves anything there -- never reaches the sum), accumulated in
+// float64 in one fixed order by one block per graph: no atomics, and a graph's result depends neither on B nor on its position.
+// false: shape refused (B, N, Ca or Cn < 1, N beyond the flag row kept in LDS)
+bool t_graph_dot(const float *a_adj, const float *a_node, const float *b_adj, const float *b_node, const uint8_t *flags, double *out, int B,
+                 int N, int Ca, int Cn, hipStream_t s);
+bool t_adam_step(int n,float *const *params, float *const *grads, float *const *m, float *const *v, const int64_t *numel, int step, float lr,
                  float b1, float b2, float eps, float wd, float max_norm, float *host_total_norm, hipStream_t s);
 bool t_ema_update(int n, float *const *ema, const float *const *params, const int64_t *numel, float decay, hipStream_t s);
 

@@ -2210,6 +2210,24 @@ void launch_init(CStatePtrs init, CStatePtrs base, float scale, uint64_t seed, c
     else launch_elem(Init<false, false>{init, base, scale, seed, graph_seeds, stream, flags}, x, d, s);
 }
 
+// the Hutchinson probe of dsg_ode_run, drawn on the device: the per-graph draw of Init<false, true> (dsg_gen_noise_seeded) on stream
+// `stream` -- gaussian: that value itself, bit for bit; rademacher: its sign, +1 where the draw is >= 0 and -1 elsewhere.  Padded
+// entries are the skeleton's literal 0
+template <bool rademacher> struct Probe {
+    const unsigned long long *graph_seeds; uint32_t stream; const uint8_t *flags;
+    __device__ int uniform() const { return 0; }
+    __device__ float operator()(int, const ElemIdx &e, size_t, const Dims &d) const {
+        const float v = philox_normal(graph_seeds[e.b], stream, local_index(e, d));
+        if constexpr (rademacher) return v >= 0.f ? 1.f : -1.f;
+        else return v;
+    }
+};
+void launch_probe(bool rademacher, const unsigned long long *graph_seeds, uint32_t stream, const uint8_t *flags, StatePtrs eps, Dims d,
+                  hipStream_t s) {
+    if (rademacher) launch_elem(Probe<true>{graph_seeds, stream, flags}, eps, d, s);
+    else launch_elem(Probe<false>{graph_seeds, stream, flags}, eps, d, s);
+}
+
 // ---- reverse-loop operations: scalars from StepRow[ctl->step] (one captured step body serves every step; edm.py:355-427) ----
 struct Churn {
     CStatePtrs x; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;

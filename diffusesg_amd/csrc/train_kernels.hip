@@ -348,7 +348,9 @@ void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, 
     // columns; the activation rows keep their pitch, the chunk's overhang reads the next row's first values (finite) against those zeros,
     // and past the last row the buffer descriptor returns zeros)
     const int Kp = (K + 31) / 32 * 32;
-    if (use_mfma && !ta && M >= 512 && N % 32 == 0 && lda == K && (K % 32 == 0 || (tb && lda % 4 == 0 && !res && !accumulate)) && (size_t)N * Kp <= ((size_t)32 << 20)) {
+    // (g_fixed_tiles, option "batch_invariant" in dsg_ode_run: M is B x tokens, so the 512-row threshold would let the batch size pick
+    // the kernel that computes a graph's rows -- the MFMA route at every M then)
+    if (use_mfma && !ta && (M >= 512 || g_fixed_tiles) && N % 32 == 0 && lda == K && (K % 32 == 0 || (tb && lda % 4 == 0 && !res && !accumulate)) && (size_t)N * Kp <= ((size_t)32 << 20)) {
         const float *Wop = B;
         bool ok = true;
         if (tb && K % 32 != 0) {
@@ -1308,6 +1310,43 @@ bool t_assemble_bwd(const float *d_tok, int ld, const uint8_t *flags, const floa
     if (B < 1 || N < 1 || Ca < 1 || !t_assemble_bwd_ok(Cn) || ld < (self_cond ? 2 : 1) * (Ca + 2 * Cn) || (size_t)B * N > 0x7fffffffu) return false;
     hipLaunchKernelGGL(t_assemble_bwd_kernel, dim3((unsigned)(B * N)), dim3(256), lds, s, d_tok, ld, flags, c_skip, c_in, g_adj, g_node, out_adj,
                        out_node, N, Ca, Cn, (int)self_cond);
+    return true;
+}
+
+// Per-graph contraction out[b] = sum over live entries j of a_j b_j (dsg_ode_run's eps . (J^T eps) after t_assemble_bwd; kernels.h).  One
+// block per graph; the flag row sits in LDS and SELECTS the entries (the adjacency gradient at padded pairs is not zero, and NaN there
+// must not reach the sum).  A product of two floats is exact in double; thread t adds its entries j = t, t + 1024, ... ascending,
+// adjacency before node, and the 1024 partials are added by a halving tree: one fixed order, no atomics, nothing depends on B or b.
+constexpr int GDOT_T = 1024, GDOT_MAX_N = 4096;
+__global__ __launch_bounds__(GDOT_T) void t_graph_dot_kernel(const float *__restrict__ a_adj, const float *__restrict__ a_node,
+                                                             const float *__restrict__ b_adj, const float *__restrict__ b_node,
+                                                             const uint8_t *__restrict__ flags, double *out, int N, int Ca, int Cn) {
+    __shared__ double part[GDOT_T];
+    __shared__ uint8_t fl[GDOT_MAX_N];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    for (int i = tid; i < N; i += GDOT_T) fl[i] = flags[(size_t)b * N + i];
+    __syncthreads();
+    const size_t na = (size_t)Ca * N * N, nn = (size_t)N * Cn;
+    const float *pa = a_adj + (size_t)b * na, *pb = b_adj + (size_t)b * na, *qa = a_node + (size_t)b * nn, *qb = b_node + (size_t)b * nn;
+    double acc = 0.0;
+    for (size_t j = tid; j < na; j += GDOT_T) {
+        const int k = (int)(j % N), i = (int)((j / N) % N);
+        if (fl[i] && fl[k]) acc += (double)pa[j] * (double)pb[j];
+    }
+    for (size_t j = tid; j < nn; j += GDOT_T)
+        if (fl[j / Cn]) acc += (double)qa[j] * (double)qb[j];
+    part[tid] = acc;
+    __syncthreads();
+    for (int w = GDOT_T / 2; w > 0; w >>= 1) {
+        if (tid < w) part[tid] += part[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[b] = part[0];
+}
+bool t_graph_dot(const float *a_adj, const float *a_node, const float *b_adj, const float *b_node, const uint8_t *flags, double *out, int B,
+                 int N, int Ca, int Cn, hipStream_t s) {
+    if (B < 1 || N < 1 || N > GDOT_MAX_N || Ca < 1 || Cn < 1) return false;
+    hipLaunchKernelGGL(t_graph_dot_kernel, dim3((unsigned)B), dim3(GDOT_T), 0, s, a_adj, a_node, b_adj, b_node, flags, out, N, Ca, Cn);
     return true;
 }
 

@@ -24,6 +24,7 @@ EXPORTS = [
     "dsg_precond_vjp", "dsg_debug_t_assemble_bwd",
     "dsg_debug_patch_embed_f32", "dsg_debug_assemble_f32", "dsg_debug_readout_f32", "dsg_debug_head_f32", "dsg_debug_row_f32",
     "dsg_debug_window_broadcast_f32", "dsg_debug_window_harvest_f32",
+    "dsg_ode_run", "dsg_ode_evals", "dsg_debug_graph_dot",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -56,6 +57,16 @@ class DsgSampleStats(C.Structure):
 class DsgWalkCfg(C.Structure):
     _fields_ = [("start_step", C.c_int32), ("jump_len", C.c_int32), ("n_resample", C.c_int32),
                 ("resample_lo", C.c_int32), ("resample_hi", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class DsgOdeCfg(C.Structure):
+    """dsg_ode_cfg of include/dsg.h (dsg_ode_run, dsg_ode_evals)"""
+    _fields_ = [("direction", C.c_int32), ("probe", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+ODE_ENCODE, ODE_DECODE = 0, 1                                  # DSG_ODE_ENCODE / DSG_ODE_DECODE
+ODE_PROBES = {"none": 0, "rademacher": 1, "gaussian": 2}       # DSG_ODE_PROBE_*
+ODE_PROBE_STREAM = 0x0DE00000                                  # DSG_ODE_PROBE_STREAM: the noise stream of the device-drawn probe
 
 
 class DsgGemmF32Args(C.Structure):
@@ -191,6 +202,10 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_train_self_cond.argtypes = [vp, i32] + [vp] * 7
     L.dsg_precond_vjp.argtypes = [vp, i32] + [vp] * 8 + [GRAD_FN, vp] + [vp] * 5
     L.dsg_debug_t_assemble_bwd.argtypes = [i32] * 5 + [vp, i32] + [vp] * 8
+    L.dsg_ode_run.argtypes = [vp, C.POINTER(DsgSamplerCfg), C.POINTER(DsgOdeCfg), i32] + [vp] * 12
+    L.dsg_ode_evals.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgOdeCfg), vp, vp, i32]
+    L.dsg_ode_evals.restype = i32
+    L.dsg_debug_graph_dot.argtypes = [i32] * 4 + [vp] * 7
     L.dsg_train_bind_params.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
     L.dsg_adam_step.argtypes = [i32] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int64), i32] + [C.c_float] * 6 + [C.POINTER(C.c_float), vp]
     L.dsg_ema_update.argtypes = [i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, vp]
@@ -420,3 +435,26 @@ def multistep_coef(scfg: DsgSamplerCfg, walk: Optional[DsgWalkCfg] = None):
     if rc != n:
         raise DsgError(f"dsg_multistep_coef: status {rc}")
     return coef
+
+
+def make_ode_cfg(direction: str = "encode", probe: str = "none") -> DsgOdeCfg:
+    if direction not in ("encode", "decode") or probe not in ODE_PROBES:
+        raise ValueError((direction, probe))
+    return DsgOdeCfg(ODE_ENCODE if direction == "encode" else ODE_DECODE, ODE_PROBES[probe], (C.c_int32 * 6)(*([0] * 6)))
+
+
+def ode_evals(scfg: DsgSamplerCfg, ocfg: DsgOdeCfg):
+    """(t_eval float32 [n_evals], weight float64 [n_evals]) of an ODE run (dsg_ode_evals): the evaluation levels in execution order
+    and the quadrature weights w_k of sum_k w_k n_k ~ int n(t) / t dt -- host-only, no GPU needed.  DsgError when the library refuses
+    the run: fewer than two levels, the multistep solver, a schedule that draws churn noise, a bad direction or probe."""
+    import numpy as np
+    L = load()
+    n = int(L.dsg_ode_evals(C.byref(scfg), C.byref(ocfg), None, None, 0))
+    if n < 0:
+        raise DsgError(f"dsg_ode_evals: status {n}: the ODE needs num_steps >= 2 (it is {scfg.num_steps}), solver 'euler' or 'heun', "
+                       f"a schedule that draws no churn noise (S_churn = {scfg.S_churn:g}; it needs S_churn = 0) and a known direction / probe")
+    t, w = np.empty(n, np.float32), np.empty(n, np.float64)
+    rc = int(L.dsg_ode_evals(C.byref(scfg), C.byref(ocfg), t.ctypes.data, w.ctypes.data, n))
+    if rc != n:
+        raise DsgError(f"dsg_ode_evals: status {rc}")
+    return t, w

@@ -337,3 +337,25 @@ def input_grad_case(tag: str, seed: int = 29):
         g_adj = W.normal(seed, f"igrad/{tag}/g_adj", (B, cfg.c_adj, n, n))
         g_node = W.normal(seed, f"igrad/{tag}/g_node", (B, n, cfg.c_node))
     return cfg, flags, adj, node, sig, sc_adj, sc_node, g_adj, g_node, stride
+
+
+# ---- ODE / likelihood fixture (tests/golden/ode_likelihood.npz; tools/gen_ode_golden.py): value-space +-1 graphs and recorded
+# Rademacher probes, both the signs of portable-generator draws, masked.  run -> (num_steps, solver); every run has S_churn = 0
+ODE_NETS = ("nosc", "tiny", "small")
+ODE_VALID = {"nosc": [8, 3], "tiny": [8, 5, 3], "small": [16, 9]}
+ODE_RUNS = {"t8_euler": (8, "euler"), "t8_heun": (8, "heun"), "t16_heun": (16, "heun")}
+ODE_EXACT_SIGMAS = (80.0, 1.5, 0.002)     # exact net traces: `nosc` and `tiny` at these levels
+
+
+def ode_case(name: str, seed: int = 37):
+    """cfg, flags, adj, node (+-1 at live entries, 0 at padded ones), probe_adj, probe_node (the same)"""
+    cfg = CONFIGS[name]()
+    valid = ODE_VALID[name]
+    B, n = len(valid), cfg.max_node_num
+    flags = W.synth_flags(B, n, valid)
+    sign = lambda x: np.where(x >= 0, np.float32(1), np.float32(-1)).astype(np.float32)
+    adj = W.mask_adj(sign(W.normal(seed, f"ode/{name}/adj", (B, cfg.c_adj, n, n))), flags)
+    node = W.mask_node(sign(W.normal(seed, f"ode/{name}/node", (B, n, cfg.c_node))), flags)
+    p_adj = W.mask_adj(sign(W.normal(seed, f"ode/{name}/probe_adj", (B, cfg.c_adj, n, n))), flags)
+    p_node = W.mask_node(sign(W.normal(seed, f"ode/{name}/probe_node", (B, n, cfg.c_node))), flags)
+    return cfg, flags, adj, node, p_adj, p_node

@@ -40,7 +40,8 @@ extern "C" {
  * at load time (diffusesg_amd/lib.py does): round 3 inserted `iou_loss_type` into three entries, and a caller built against the older
  * header would otherwise pass shifted arguments without any error.  History: 1-3 = rounds 1-3 (unversioned), 4 = round 4
  * (dsg_decode with an encoding argument, dsg_abi_version, dsg_last_error(NULL)).  dsg_sample_seeded, dsg_gen_noise_seeded and the option
- * "batch_invariant" were added without touching an existing argument list: still 4; so were the dsg_debug_*_f32 test hooks. */
+ * "batch_invariant" were added without touching an existing argument list: still 4; so were the dsg_debug_*_f32 test hooks, and
+ * dsg_ode_run / dsg_ode_evals / dsg_debug_graph_dot. */
 #define DSG_ABI_VERSION 4
 
 typedef enum {
@@ -739,6 +740,67 @@ typedef int (*dsg_grad_fn)(void *user, const float *D_adj, const float *D_node, 
 int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node, const uint8_t *flags, const float *sigmas /*[B]*/,
                     const float *sc_adj, const float *sc_node, const float *grad_D_adj, const float *grad_D_node, dsg_grad_fn fn, void *user,
                     float *out_D_adj, float *out_D_node, float *out_grad_adj, float *out_grad_node, void *stream);
+
+/* ---- Probability-flow ODE between the noise levels: the latent of a graph, and its log-likelihood under the model.
+ * Levels: t_0 > ... > t_{T-1}, the t_hat of dsg_sigma_schedule for a cfg whose schedule draws no noise (any nonzero noise_coef:
+ *   DSG_ERR_INVALID, as for the dpmpp_2m solver -- use S_churn = 0).  T >= 2.  t_max = t_0, t_min = t_{T-1}, sigma_d = 0.5.
+ * Velocity: f(x, t) = mask((x - D(x, t)) / t), D the TRAINING-FORM preconditioned denoiser with the self-conditioning inputs NULL -- the
+ *   bits dsg_train_self_cond gives.  That holds for a network built with self_condition = 1 as well: the ODE is defined on the branch
+ *   without self-conditioning.
+ * Directions: DSG_ODE_ENCODE steps from a = t_k to b = t_{k-1}, k = T-1 ... 1 (data at t_min -> latent at t_max); DSG_ODE_DECODE from
+ *   a = t_k to b = t_{k+1}, k = 0 ... T-2, and ends at t_min: there is no step to 0.  h = b - a (fp32).
+ * Solvers (cfg->heun): DSG_SOLVER_EULER x_b = x_a + h f(x_a, a), T-1 evaluations; DSG_SOLVER_HEUN -- here the true trapezoid, not the
+ *   sampler's form -- x' = x_a + h f(x_a, a), x_b = x_a + (h/2)(f(x_a, a) + f(x', b)), 2(T-1) evaluations; DSG_SOLVER_DPMPP_2M:
+ *   DSG_ERR_INVALID.  The state arithmetic is the sampler's Euler / Heun element operations, fp32 op by op, on a step table of these
+ *   (a, b) pairs.
+ * Probe (Hutchinson's estimator of the divergence): one eps per graph, fixed for the whole run, zero at padded entries.  Recorded
+ *   (probe_adj / probe_node, device, D's layouts; masked on the way in; they win over graph_seeds) or drawn on the device from
+ *   graph_seeds (HOST, [B]): DSG_ODE_PROBE_GAUSSIAN is exactly dsg_gen_noise_seeded(graph_seeds, noise_stream = DSG_ODE_PROBE_STREAM),
+ *   DSG_ODE_PROBE_RADEMACHER is +1 where that draw is >= 0 and -1 elsewhere.  The stream lies above every churn stream of a walk.
+ * Net trace: at every evaluation (x, t), row k of out_net_trace (device, [n_evals, B] doubles) receives
+ *       n_b = sum over the live entries j of graph b of eps_j (J_D^T eps - c_skip(t) eps)_j = c_in c_out eps^T J_F eps,
+ *   c_skip = sigma_d^2 / (t^2 + sigma_d^2).  The c_skip term is never formed and subtracted (at t = 0.002 that would cancel seven
+ *   digits): the assemble backward runs with a zero c_skip array and writes the network part alone.  The sum is float64, in one fixed
+ *   order, over live entries selected by the flags (the adjacency gradient at padded pairs is not zero).
+ * Log-likelihood (assembled by the caller in float64; diffusesg_amd.ode.assemble_logp): with d_b = C_adj n_b^2 + C_node n_b live
+ *   entries, x_max / x_min the states at t_max / t_min (whichever is input and whichever output), and w_k of dsg_ode_evals,
+ *       log p_{t_min}(x_min) = -(d/2) ln(2 pi t_max^2) - |x_max|^2 / (2 t_max^2) + (d/2) ln((t_max^2 + sigma_d^2) / (t_min^2 + sigma_d^2))
+ *                              - sum_k w_k n_k.
+ *   The term d t / (t^2 + sigma_d^2) of the divergence is integrated in closed form (the third term); only the network part is
+ *   integrated numerically, by the solver's own quadrature.  The prior is the sampler's N(0, t_max^2 I); for data N(0, s^2 I) the
+ *   expression equals log N(x; 0, (s^2 + t_min^2) I) up to (d/2) ln(t_max^2 / (s^2 + t_max^2)), the known prior mismatch.  A graph
+ *   with no valid node: latent 0, traces 0, log p = 0.
+ * dsg_ode_run: x_* the state at the start level, out_* the state at the end level; out_probe_* (optional, both or none) the probe
+ *   used; out_net_trace required iff probe != DSG_ODE_PROBE_NONE.  With probe = NONE no backward runs and the end state is bit-identical
+ *   to the run with a probe.  With the option "batch_invariant" a graph's end state and traces are the same bits alone or in a batch.
+ *   Refused before anything is launched: the above, what dsg_precond_vjp refuses (C_node beyond the assemble backward; DSG_ERR_STATE
+ *   before dsg_finalize_weights), a probe with neither seeds nor recorded tensors, half a recorded probe, a missing out_net_trace.
+ *   The run is enqueued on `stream` with one synchronisation, after the uploads of its tables and ahead of the first launch; buffers
+ *   belong to the handle (the training entries' arena and scratch included) and are freed with it.
+ * dsg_ode_evals: host-only, as dsg_walk_steps is.  Returns n_evals or a negative status: a refusal above, or cap < n_evals with
+ *   an array given. t_eval [n_evals]: the evaluation levels in execution order; weight [n_evals]: w_k -- Euler |h|/a at its one
+ *   evaluation, Heun |h|/(2a) at stage 1 and |h|/(2b) at stage 2 -- in double from the widened fp32 values.  Either may be NULL. */
+#define DSG_ODE_ENCODE 0
+#define DSG_ODE_DECODE 1
+#define DSG_ODE_PROBE_NONE 0
+#define DSG_ODE_PROBE_RADEMACHER 1
+#define DSG_ODE_PROBE_GAUSSIAN 2
+#define DSG_ODE_PROBE_STREAM 0x0DE00000u   /* > DSG_WALK_MAX_STEPS + 1: never a churn stream */
+typedef struct dsg_ode_cfg {
+    int32_t direction;                 /* DSG_ODE_ENCODE / DSG_ODE_DECODE */
+    int32_t probe;                     /* DSG_ODE_PROBE_* */
+    int32_t reserved[6];
+} dsg_ode_cfg;
+int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode, int32_t B, const uint8_t *flags,
+                const float *x_adj, const float *x_node, const uint64_t *graph_seeds /* host [B] */,
+                const float *probe_adj, const float *probe_node, float *out_adj, float *out_node,
+                float *out_probe_adj, float *out_probe_node, double *out_net_trace /* device [n_evals, B] */, void *stream);
+int32_t dsg_ode_evals(const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode, float *t_eval, double *weight, int32_t cap);
+/* the per-graph contraction of dsg_ode_run on its own (test hook, no handle; device pointers, synchronises `stream`): out[b] = the sum
+ * over the live entries of graph b of a_j b_j, float64, one fixed order, independent of B and of the graph's position; padded entries
+ * are skipped by the flags (NaN there does not reach the sum).  a_adj / b_adj [B,C_adj,N,N], a_node / b_node [B,N,C_node], out [B]. */
+int dsg_debug_graph_dot(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *a_adj, const float *a_node, const float *b_adj,
+                        const float *b_node, const uint8_t *flags, double *out, void *stream);
 
 /* Let the training-form entries (dsg_train_grads, dsg_train_step_grads, dsg_train_self_cond) read these parameters IN PLACE: names[i]
  * (state-dict key) -> params[i] (device tensor of the parameter's shape, e.g. the tensor the optimiser updates), instead of the
