@@ -180,6 +180,9 @@ struct dsg_handle_s {
     PrunePlan prune;
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
     std::vector<int> prof_list;
+    int n_cu = 0;                     // multiprocessor count of the device (read once in dsg_create): the list GEMM's form rule (gemm_thin_rule)
+    int prof_next_thin_n = 0;         // N of the next profiled launch if it is a list GEMM with a thin form, else 0
+    std::vector<int> prof_thin_n;
     bool opt_fused_merge = true;      // PatchMerging: gather + LayerNorm(4C) inside the reduction GEMM's A path (no merge_ln kernel)
     bool opt_batch_invariant = false; // every choice of the plan is a function of the geometry and the other options, never of B
     bool opt_loop_graph = true;       // capture whole step bodies of the reverse loop (0: only the network forward is a graph)
@@ -264,8 +267,9 @@ enum ProfKind { PK_GEMM = 0, PK_ATTN = 1, PK_ROW = 2, PK_ELEM = 3, PK_FUSED = 4,
 struct ProfScope {
     dsg_handle h; hipStream_t s;
     ProfScope(dsg_handle h_, hipStream_t s_, int kind, double flops, const char *tag = nullptr) : h(h_), s(s_) {
-        const int need_list = h->prof_next_list;
+        const int need_list = h->prof_next_list, thin_n = h->prof_next_thin_n;
         h->prof_next_list = -1;
+        h->prof_next_thin_n = 0;
         if (!h->prof_on) return;
         while (h->prof_events.size() < h->prof_used + 2) {
             hipEvent_t e;
@@ -274,6 +278,7 @@ struct ProfScope {
         }
         h->prof_kind.push_back(kind);
         h->prof_list.push_back(need_list);
+        h->prof_thin_n.push_back(thin_n);
         h->prof_flops.push_back(flops);
         h->prof_tag.push_back(tag ? tag : "");
         (void)hipEventRecord(h->prof_events[h->prof_used], s);
@@ -702,6 +707,10 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     if (getenv("DSG_BF16_QA")) h->opt_bf16_qkv_attn = atoi(getenv("DSG_BF16_QA"));   // dev knob: 2 = the block-per-head QKV + attention kernel
     if (getenv("DSG_BF16_MLP")) h->opt_bf16_mlp = atoi(getenv("DSG_BF16_MLP"));   // dev knob: A/B of the C = 384 MLP kernels (1 LDS-DMA, 4 round 3's)
     h->opt_gemm_split = env_on("DSG_GEMM_SPLIT", false);
+    {   // the list GEMM picks its form from how many CUs a launch would fill (kernels.h: gemm_thin_rule); unknown = never thin
+        int dev = 0, n_cu = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) h->n_cu = n_cu;
+    }
     *out = h;
     g_live_handles++;
     return DSG_OK;
@@ -1077,6 +1086,7 @@ void tap(dsg_handle h, const char *name, const float *src, size_t numel, hipStre
 #define P_GEMM(g) do { (g).Ws3 = split_of(h, (g).W); (g).Wb = nullptr; P_GEMM_(g); } while (0)
 #define P_GEMM_(g) do { char tg_[96]; if (h->prof_stamps && h->prof_gemm && h->prof_gemm_used < h->prof_gemm_cap) (g).prof = h->prof_gemm + 4 * (h->prof_gemm_used++); else (g).prof = nullptr; \
     if (h->prof_on) snprintf(tg_, sizeof(tg_), "gemm M=%d N=%d K=%d ln=%d act=%d res=%d", (g).M, (g).N, (g).K, ((g).ln_stats != nullptr) + 2 * ((g).ln_part != nullptr) + 4 * ((g).stats_out != nullptr) + 8 * ((g).mod_aff != nullptr), (g).act, (g).res != nullptr); \
+    (g).n_cu = h->n_cu; h->prof_next_thin_n = gemm_has_thin(g) ? (g).N : 0; \
     ProfScope ps_(h, s, PK_GEMM, 2.0 * (double)(g).M * (double)(g).N * (double)(g).K, tg_); \
     g_fixed_tiles = h->opt_batch_invariant; const bool built_ = launch_gemm((g), s); g_fixed_tiles = false; \
     if (!built_) plan_fail(h, "gemm: argument combination not built (M=%d N=%d K=%d ln=%d act=%d res=%d bf16 A/C=%d/%d)", (g).M, (g).N, (g).K, ((g).ln_stats != nullptr) + 2 * ((g).ln_part != nullptr), (g).act, (g).res != nullptr, (g).a_bf16, (g).c_bf16); } while (0)
@@ -2748,7 +2758,7 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
     h->prof_clock_ghz = clocks.empty() ? 0.0 : clocks[clocks.size() / 2];
     // pass B: HIP-event brackets around every launch (per-class breakdown; each bracket includes dispatch latency)
     for (int iter = 0; iter < n_iters; iter++) {
-        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear(); h->prof_list.clear();
+        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear(); h->prof_list.clear(); h->prof_thin_n.clear();
         forward_fixed(h, w, s);
         const bool ok = h->prof_on;
         h->prof_on = false;
@@ -2762,8 +2772,13 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
             if (nl >= 0 && nl < w->need.n_lists) h->prof_flops[i] *= (double)need_cnt[nl] / ((double)B * (double)prune_plan(h).items[nl]);
             float ms = 0.f;
             HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_events[2 * i], h->prof_events[2 * i + 1]));
-            if (iter == n_iters - 1 && getenv("DSG_PROFILE_VERBOSE"))
-                fprintf(stderr, "[dsg-prof] %8.1f us %7.2f TF  %.60s\n", ms * 1e3, h->prof_flops[i] / (ms * 1e-3) / 1e12, h->prof_tag[i].c_str());
+            if (iter == n_iters - 1 && getenv("DSG_PROFILE_VERBOSE")) {
+                // a list GEMM with a thin form names the form its blocks chose: the kernel's rule on the count read back above
+                const char *form = "";
+                if (nl >= 0 && nl < w->need.n_lists && h->prof_thin_n[i] > 0)
+                    form = gemm_thin_rule(need_cnt[nl], h->prof_thin_n[i], h->n_cu) ? " form=thin" : " form=wide";
+                fprintf(stderr, "[dsg-prof] %8.1f us %7.2f TF  %.60s%s\n", ms * 1e3, h->prof_flops[i] / (ms * 1e-3) / 1e12, h->prof_tag[i].c_str(), form);
+            }
             ms_by_kind[h->prof_kind[i]] += ms;
             launches_by_kind[h->prof_kind[i]] += 1;
             flops_by_kind[h->prof_kind[i]] += h->prof_flops[i];
@@ -2932,8 +2947,15 @@ int dsg_debug_gemm_f32(const dsg_gemm_f32_args *a, void *stream) {
     g.stats_out = a->stats_out;
     g.a4_res = a->a4_res;
     g.row_list = a->row_list; g.row_cnt = a->row_cnt;
+    // `reserved` selects the list GEMM's form: 0 the kernel's rule (with this device's CU count), 1 wide, 2 thin
+    if (a->reserved < 0 || a->reserved > 2) return DSG_ERR_INVALID;
+    g.form = a->reserved;
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) g.n_cu = n_cu;
     return debug_finish(launch_gemm(g, s), s);
 }
+
+int32_t dsg_debug_gemm_form(int32_t cnt_runs, int32_t N, int32_t n_cu) { return gemm_thin_rule(cnt_runs, N, n_cu) ? 2 : 1; }
 
 int dsg_debug_qkv_attn_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, int32_t K, const float *x, const float *W,
                            const float *bias, const float *ln_stats, const float *ln_part, int32_t ln_nparts, const float *attn_bias,

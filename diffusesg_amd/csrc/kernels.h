@@ -71,11 +71,26 @@ struct GemmArgs {
     // full size, tiles beyond the count return at once).  One physical row indexes A, A2, res, C, ln_part / ln_stats, stats_out and the
     // mod_aff sample alike.  launch_gemm_qkv_attn: row_list is a list of window indices instead (two per tile).
     const int *row_list = nullptr, *row_cnt = nullptr;
+    // thin form of the list GEMM (64-row tiles, see kernels.hip): chosen on the device from *row_cnt by gemm_thin_rule() below.
+    // n_cu: the device's multiprocessor count (0: never thin).  form: 0 the rule, 1 always wide, 2 always thin (test hook).
+    int n_cu = 0, form = 0;
     int a_bf16 = 0, c_bf16 = 0;                  // bf16 mode only: A / C are bf16 tensors (lda / ldc in elements); see kernels_lp.hip
     const float *gelu_tab = nullptr;             // filled in by launch_gemm (table-driven GELU of the split kernel)
     unsigned long long *prof = nullptr;          // measurement mode: {min block start, max block end} in 100 MHz ticks
 };
 bool launch_gemm(const GemmArgs &g, hipStream_t s);   // false: the argument combination is not built (nothing launched)
+// The list GEMM's choice between its two forms, written once for the kernel, the launcher's grid and the host's reporting: a launch of
+// cnt_runs 8-row runs takes ceil(cnt_runs / 16) x ceil(N / 96) wide (128 x 96) tiles; when those would occupy at most half the CUs, the
+// thin form's twice as many 64 x 96 tiles still fit one per CU and each runs 2/3 of the wide tile's MFMA chain.  Above the bound two
+// thin blocks per CU would take 4/3 of it.
+__host__ __device__ inline bool gemm_thin_rule(int cnt_runs, int N, int n_cu) {
+    if (cnt_runs < 0 || N < 1 || n_cu < 1) return false;
+    return 2ll * ((cnt_runs + 15) / 16) * ((N + 95) / 96) <= (long long)n_cu;
+}
+// does launch_gemm build the thin form for these arguments?  (row list, no LayerNorm, no activation: the proj / fc2 / reduction shapes)
+inline bool gemm_has_thin(const GemmArgs &g) {
+    return g.row_list && !g.ln_stats && !g.ln_part && g.act == ACT_NONE && g.a4_res == 0 && !g.Ws3 && !g.Wb && g.batch == 1;
+}
 // fused LN1 -> QKV -> window attention for 64-token windows (fp32 kernel); returns false if the geometry is not supported
 bool launch_gemm_qkv_attn(const GemmArgs &g, hipStream_t s);
 void launch_f32_to_bf16(const float *src, void *dst, size_t n, hipStream_t s);

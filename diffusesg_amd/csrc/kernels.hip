@@ -100,12 +100,281 @@ __device__ __forceinline__ void row_partials_n(const float *const (&pp)[R], int 
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Thin form of the list GEMM (AMODE 3 without LayerNorm / attention: proj, fc2, the list PatchMerging reduction).  A list launch
+// that fills under half the CUs with 128 x 96 tiles is bound by ONE wave's serial chain of 3 K/2 MFMAs (K = 1536: 2304 x 64 cycles =
+// 70 us at 2.1 GHz) while half the chip idles.  Here the block tile is 64 x 96 -- 8 runs of the list, entries 8 tm .. 8 tm + 7 -- and
+// the four waves are 2 (M) x 2 (N): the N-waves own the 32-column slabs {0, 1} and {2}, so no wave chains more than 2 K/2 MFMAs and
+// twice as many blocks spread over the CUs.  Everything that decides a stored bit is the wide form's: the same k order per
+// accumulator, the same epilogue instructions per element, and the row statistics st_s = ((0 + v0) + v1) + v2,
+// st_q = fma(v2, v2, fma(v1, v1, fma(v0, v0, 0))) per lane -- the slab {0, 1} waves hand their v through LDS to the slab {2} wave,
+// which finishes the chain and runs the wide form's transpose and 32-lane sum.  gemm4_f32_kernel branches here block-uniformly
+// (gemm_thin_rule on the device-side count); `wave` is made provably uniform so that the two K loops, which hold the same number of
+// barriers, sit behind scalar branches.
+// -------------------------------------------------------------------------------------------------
+constexpr int TBM = 64;   // rows of the thin form's block tile
+template <int NS> struct SlabCount { static constexpr int value = NS; };
+
+template <bool RES, int EPI>
+__device__ __forceinline__ void gemm4_thin_tile(const GemmArgs &g, int bid, int tiles_n, int map_cnt, float *lds,
+                                                unsigned long long prof_t0, unsigned long long prof_c0) {
+    constexpr int BUF = (TBM + GBN) * GLD;
+    const int xcd = bid & 7, seq = bid >> 3;
+    const int tm = (seq / tiles_n) * 8 + xcd, tn = seq % tiles_n;
+    if (tm >= (g.M + TBM - 1) / TBM || tm * (TBM / 8) >= map_cnt) return;
+    const int n0 = tn * GBN;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave & 1, wn = wave >> 1;
+    const int c4 = tid & 7, r0 = tid >> 3;
+    const int rows_n = min(GBN, g.N - n0);
+    const rsrc_t rsA1 = make_rsrc(g.A, (unsigned)g.M * g.lda * 4u);
+    const rsrc_t rsA2 = make_rsrc(g.A2 ? g.A2 : g.A, g.A2 ? (unsigned)g.M * g.lda2 * 4u : 0u);
+    const rsrc_t rsW = make_rsrc(g.W + (size_t)n0 * g.K, (unsigned)rows_n * g.K * 4u);
+    unsigned voffA1[2], voffA2[2], voffW[3];
+#pragma unroll
+    for (int p = 0; p < 2; p++) {   // physical row of staging row r: run (r / 8) of the tile, position r % 8; a sentinel run reads zeros
+        const int r = r0 + 32 * p;
+        const int run = g.row_list[tm * 8 + (r >> 3)];
+        const int grow = run >= 0 ? run * 8 + (r & 7) : -1;
+        voffA1[p] = grow >= 0 ? ((unsigned)grow * g.lda + 4u * c4) * 4u : 0x7fffffffu;
+        voffA2[p] = grow >= 0 ? ((unsigned)grow * g.lda2 + 4u * c4) * 4u : 0x7fffffffu;
+    }
+#pragma unroll
+    for (int p = 0; p < 3; p++) voffW[p] = ((unsigned)(r0 + 32 * p) * g.K + 4u * c4) * 4u;
+    const int nk = g.K / GBK;
+    const int nk1 = g.A2 ? g.K1 / GBK : nk;  // chunks served by the first source
+
+    struct Stage { f32x4 a[2], w[3]; };
+    auto issue = [&](Stage &st, int kc) {
+        kc = kc < nk ? kc : nk - 1;  // the tail iterations re-load a valid chunk they never use
+        const bool second = kc >= nk1;
+        const unsigned soffA = (unsigned)(second ? kc - nk1 : kc) * (GBK * 4u), soffW = (unsigned)kc * (GBK * 4u);
+        if (second) {
+#pragma unroll
+            for (int p = 0; p < 2; p++) st.a[p] = buf_load4(rsA2, voffA2[p], soffA);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 2; p++) st.a[p] = buf_load4(rsA1, voffA1[p], soffA);
+        }
+#pragma unroll
+        for (int p = 0; p < 3; p++) st.w[p] = buf_load4(rsW, voffW[p], soffW);
+    };
+    auto write = [&](const Stage &st, int buf) {
+        float *As = lds + buf * BUF, *Ws = As + TBM * GLD;
+#pragma unroll
+        for (int p = 0; p < 2; p++) *reinterpret_cast<f32x4 *>(As + (r0 + 32 * p) * GLD + 4 * c4) = st.a[p];
+#pragma unroll
+        for (int p = 0; p < 3; p++) *reinterpret_cast<f32x4 *>(Ws + (r0 + 32 * p) * GLD + 4 * c4) = st.w[p];
+    };
+    const int lrow = lane & 31, lhalf = lane >> 5;
+    const int j0 = wn ? 2 : 0;   // first slab of this wave
+    const int a_off = (wm * 32 + lrow) * GLD + 4 * lhalf;
+    const int w_off = TBM * GLD + (32 * j0 + lrow) * GLD + 4 * lhalf;
+
+    f32x16 acc[2];   // slabs j0, j0 + 1 (the slab {2} wave uses acc[0] only)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[j][r] = 0.f;
+
+    Stage s0, s1;
+    issue(s0, 0);
+    write(s0, 0);
+    issue(s1, 1);
+    __syncthreads();
+    // one k chunk = one basic block, as in the wide form: fragment reads, the next chunk's LDS writes and the global loads of the
+    // chunk after it spread over the chunk's 16 NS MFMAs (4 NS per fragment step)
+    auto kloop = [&](auto slabs) {
+        constexpr int NS = decltype(slabs)::value;
+        struct Frag { f32x4 a, b[NS]; };
+        auto fread = [&](Frag &f, int buf, int s) {
+            const float *base = lds + buf * BUF;
+            f.a = *reinterpret_cast<const f32x4 *>(base + a_off + 8 * s);
+#pragma unroll
+            for (int j = 0; j < NS; j++) f.b[j] = *reinterpret_cast<const f32x4 *>(base + w_off + 32 * j * GLD + 8 * s);
+        };
+        auto mfmas = [&](const Frag &f) {
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int j = 0; j < NS; j++) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[t], f.b[j][t], acc[j], 0, 0, 0);
+        };
+        Frag f0, f1;
+#define GEMM4_THIN_CHUNK(CUR, ST_W, ST_L, KC)                                                          \
+    do {                                                                                               \
+        fread(f1, CUR, 1);                                                                             \
+        mfmas(f0);                                                                                     \
+        write(ST_W, 1 - (CUR));                                                                        \
+        fread(f0, CUR, 2);                                                                             \
+        mfmas(f1);                                                                                     \
+        issue(ST_L, (KC) + 2);                                                                         \
+        fread(f1, CUR, 3);                                                                             \
+        mfmas(f0);                                                                                     \
+        _Pragma("unroll") for (int q_ = 0; q_ < 12 * NS; q_++) {                                       \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                         \
+            __builtin_amdgcn_sched_group_barrier(0x3f6, NS == 2 ? 2 : 3, 0);                           \
+        }                                                                                              \
+        __syncthreads();                                                                               \
+        fread(f0, 1 - (CUR), 0);                                                                       \
+        mfmas(f1);                                                                                     \
+    } while (0)
+        fread(f0, 0, 0);
+        int kc = 0;
+        for (; kc + 1 < nk; kc += 2) {
+            GEMM4_THIN_CHUNK(0, s1, s0, kc);
+            GEMM4_THIN_CHUNK(1, s0, s1, kc + 1);
+        }
+        if (kc < nk) GEMM4_THIN_CHUNK(0, s1, s0, kc);
+#undef GEMM4_THIN_CHUNK
+    };
+    if (wn == 0) kloop(SlabCount<2>{}); else kloop(SlabCount<1>{});
+
+    // epilogue: the wide form's, per 32-column slab; the lane's 16 rows are 4 rows (r & 3) of each of the wave's 4 runs (r >> 2)
+    const rsrc_t rsC = make_rsrc(g.C, (unsigned)g.M * g.ldc * 4u);
+    const rsrc_t rsC2 = make_rsrc(g.C2 ? g.C2 : g.C, g.C2 ? (unsigned)g.M * g.ldc2 * 4u : 0u);
+    const rsrc_t rsR = make_rsrc(RES ? g.res : g.C, RES ? (unsigned)g.M * g.ldres * 4u : 0u);
+    const unsigned rowl = (unsigned)(4 * lhalf);
+    const unsigned OOB = 0x7fffffffu;
+    unsigned e_row[4];
+    bool e_ok[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int run = __builtin_amdgcn_readfirstlane(g.row_list[tm * 8 + wm * 4 + q]);
+        e_ok[q] = run >= 0;
+        e_row[q] = (unsigned)max(run, 0) * 8u;
+    }
+#define E_ROW(r) (e_row[(r) >> 2] + (unsigned)((r) & 3))
+#define E_OFF(v, r) (!e_ok[(r) >> 2] ? OOB : (v))
+    // LDS behind the K loop's tiles: [0, 4608) the two finishing waves' reduction slabs, [4608, 8704) the v of slabs 0 and 1
+    // ([wm][slab][r][lane]), [9216, 9280) the row -> sample table
+    float *pass = lds + 2 * 2304 + wm * 2048;
+    int brow[16];               // EPI == 3: sample index of each of the lane's rows
+    if (EPI >= 1) __syncthreads();   // every wave is done with the K loop's tiles
+    if (EPI == 3) {
+        int *bt = reinterpret_cast<int *>(lds) + 4 * 2304;
+        if (tid < TBM) bt[tid] = (max(g.row_list[tm * 8 + (tid >> 3)], 0) * 8 + (tid & 7)) / g.mod_T;
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 16; r++) brow[r] = bt[wm * 32 + 4 * lhalf + (r & 3) + 8 * (r >> 2)];
+    }
+    float v[16];   // the slab {2} wave keeps its stored values for the statistics
+#pragma unroll
+    for (int jj = 0; jj < 2; jj++) {
+        if (jj == 1 && wn != 0) break;
+        const int j = j0 + jj;
+        const int n = n0 + 32 * j + lrow;
+        const bool nok = n < g.N;
+        const float bias = (g.bias && nok) ? g.bias[n] : 0.f;
+        const unsigned vC = nok ? (rowl * g.ldc + (unsigned)n) * 4u : OOB;
+        const unsigned vC2 = nok ? (rowl * g.ldc2 + (unsigned)n) * 4u : OOB;
+        const unsigned vR = nok ? (rowl * g.ldres + (unsigned)n) * 4u : OOB;
+        float msc = 0.f, msh = 0.f;
+        if (EPI == 2 && nok) { msc = g.mod_aff[g.mod_off + n] + 1.0f; msh = g.mod_aff[g.mod_off + g.N + n]; }
+        float rres[16];
+        if (RES) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) rres[r] = buf_load1(rsR, E_OFF(vR, r), E_ROW(r) * g.ldres * 4u);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) { const f32x2_t t2 = (f32x2_t){acc[jj][r], acc[jj][r + 1]} + (f32x2_t){bias, bias}; v[r] = t2[0]; v[r + 1] = t2[1]; }
+        if (RES) {
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) { const f32x2_t t2 = (f32x2_t){v[r], v[r + 1]} + (f32x2_t){rres[r], rres[r + 1]}; v[r] = t2[0]; v[r + 1] = t2[1]; }
+        }
+        if (g.C2) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) buf_store1(v[r], rsC2, E_OFF(vC2, r), E_ROW(r) * g.ldc2 * 4u);
+        }
+        if (EPI >= 2) {   // silu(shift + x (1 + scale)) = a / (1 + exp(-a)), as in the wide form
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                f32x2_t sc2 = {msc, msc}, sh2 = {msh, msh};
+                if (EPI == 3 && nok) {
+                    const float *ar0 = g.mod_aff + (size_t)brow[r] * g.mod_ld + g.mod_off + n, *ar1 = g.mod_aff + (size_t)brow[r + 1] * g.mod_ld + g.mod_off + n;
+                    sc2 = (f32x2_t){ar0[0], ar1[0]} + (f32x2_t){1.0f, 1.0f}; sh2 = (f32x2_t){ar0[g.N], ar1[g.N]};
+                }
+                const f32x2_t a2 = __builtin_elementwise_fma((f32x2_t){v[r], v[r + 1]}, sc2, sh2);
+                const f32x2_t d2 = (f32x2_t){1.0f, 1.0f} + (f32x2_t){__expf(-a2[0]), __expf(-a2[1])};
+                const f32x2_t o2 = a2 * (f32x2_t){fast_rcp(d2[0]), fast_rcp(d2[1])};
+                v[r] = o2[0]; v[r + 1] = o2[1];
+            }
+        }
+        if (EPI >= 1 && wn == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) pass[(jj * 16 + r) * 64 + lane] = v[r];
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) buf_store1(v[r], rsC, E_OFF(vC, r), E_ROW(r) * g.ldc * 4u);
+    }
+#undef E_ROW
+#undef E_OFF
+    if (EPI >= 1) {
+        __syncthreads();   // the v of slabs 0 and 1 are in LDS
+        if (wn != 0) {
+            // the lane's share of (sum, sumsq) of its 16 rows over the three slabs, in the wide form's order and instructions
+            float st_s[16], st_q[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) { st_s[r] = 0.f; st_q[r] = 0.f; }
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                float vj[16];
+#pragma unroll
+                for (int r = 0; r < 16; r++) vj[r] = (j < 2) ? pass[(j * 16 + r) * 64 + lane] : v[r];
+                if (n0 + 32 * j + lrow < g.N) {
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const f32x2_t v2 = {vj[r], vj[r + 1]};
+                        const f32x2_t s2 = (f32x2_t){st_s[r], st_s[r + 1]} + v2, q2 = __builtin_elementwise_fma(v2, v2, (f32x2_t){st_q[r], st_q[r + 1]});
+                        st_s[r] = s2[0]; st_s[r + 1] = s2[1]; st_q[r] = q2[0]; st_q[r + 1] = q2[1];
+                    }
+                }
+            }
+            // transpose through this wave's LDS slab and add the 32 lane-partials of each row in the wide form's fixed order
+            float *red = lds + wm * 2304;   // [2 quantities][32 rows][36]
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                red[row * GLD + lrow] = st_s[r];
+                red[(32 + row) * GLD + lrow] = st_q[r];
+            }
+            __builtin_amdgcn_wave_barrier();
+            const float *src = red + (lhalf * 32 + lrow) * GLD;
+            float tot = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const f32x4 q4 = *reinterpret_cast<const f32x4 *>(src + 4 * i);
+                tot += (q4[0] + q4[1]) + (q4[2] + q4[3]);
+            }
+            const rsrc_t rsP = make_rsrc(g.stats_out, ((unsigned)g.M * tiles_n) * 8u);   // [M][tiles_n][2]
+            const int run = g.row_list[tm * 8 + wm * 4 + (lrow >> 3)];
+            const unsigned voffP = run >= 0 ? (unsigned)(((run * 8 + (lrow & 7)) * tiles_n + tn) * 2 + lhalf) * 4u : OOB;
+            buf_store1(tot, rsP, voffP, 0u);
+        }
+    }
+    if (g.prof && tid == 0) {
+        __builtin_amdgcn_s_waitcnt(0);  // this wave's stores have been issued and acknowledged
+        const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+        atomicMin(g.prof, prof_t0);
+        atomicMax(g.prof + 1, t1);
+        if (bid == 0) { g.prof[2] = __builtin_amdgcn_s_memtime() - prof_c0; g.prof[3] = t1 - prof_t0; }
+    }
+}
+
 template <bool LN, int ACT, bool RES, int EPI, int WS = 8, int AMODE = 0>   // WS: window side of the fused attention (EPI == 4): 8 or 10
 __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles_m, int tiles_n) {
     __shared__ __attribute__((aligned(16))) float lds[2 * (GBM + GBN) * GLD];
     constexpr int BUF = (GBM + GBN) * GLD;
 
     int bid = blockIdx.x;
+    if constexpr (AMODE == 3 && !LN && ACT == ACT_NONE && EPI != 4) {   // the list launches with a thin form: block-uniform choice (gemm_thin_rule)
+        const int cnt = *g.row_cnt;
+        if (g.form == 2 || (g.form == 0 && gemm_thin_rule(cnt, g.N, g.n_cu))) {
+            unsigned long long t0 = 0, c0 = 0;
+            if (g.prof && threadIdx.x == 0) { t0 = __builtin_amdgcn_s_memrealtime(); if (bid == 0) c0 = __builtin_amdgcn_s_memtime(); }
+            gemm4_thin_tile<RES, EPI>(g, bid, tiles_n, cnt, lds, t0, c0);
+            return;
+        }
+    }
     // AMODE 2 (training, weight gradients): `batch` independent products of the same shape in one launch -- the K slices of a
     // split-K product -- operands / outputs batch_stride{A,W,C} floats apart; everything else as AMODE 0
     const float *gA = g.A, *gW = g.W;
@@ -655,6 +924,7 @@ thread_local bool g_fixed_tiles = false;
 // validates a whole forward's launches in a dry run at plan time, so a forward never meets this half-way)
 bool launch_gemm(const GemmArgs &g, hipStream_t s) {
     if (g.M < 1 || g.N < 1 || g.K < GBK || g.K % GBK != 0 || !g.A || !g.W || !g.C) return false;
+    if (g.form < 0 || g.form > 2 || (g.form == 2 && !gemm_has_thin(g))) return false;   // the thin form exists for list launches without LayerNorm only
     if ((g.Ws3 || g.Wb) && launch_gemm_lp(g, s)) return true;   // opt-in bf16-MFMA modes (kernels_lp.hip)
     if (g.a_bf16 || g.c_bf16) return false;   // bf16 tensors need the bf16 GEMM kernel
     const int tiles_m = (g.M + GBM - 1) / GBM, tiles_n = (g.N + GBN - 1) / GBN;
@@ -671,13 +941,22 @@ bool launch_gemm(const GemmArgs &g, hipStream_t s) {
     if (g.row_list) {   // row-mapped forms (masked-token pruning): the up path's pre_linear / post_linear / proj / fc1 / fc2 shapes only
         const size_t widest = (size_t)std::max(std::max(g.lda, g.lda2), std::max(std::max(g.ldc, g.ldc2), std::max(g.ldres, 2 * tiles_n)));
         if (!g.row_cnt || g.a4_res > 0 || g.M % 8 != 0 || (size_t)g.M * widest * 4u >= 0x7fffffffull) return false;
-#define GEMM_MAP(L, A, R, E) DSG_LAUNCH((gemm4_f32_kernel<L, A, R, E, 8, 3>), grid, block, 0, s, g, tiles_m, tiles_n)
         const int epi = !g.stats_out ? 0 : (!g.mod_aff ? 1 : (g.mod_ld == 0 ? 2 : 3));
         if (ln) {
-            if (g.act != ACT_GELU || res || epi != 0 || g.C2 || g.A2) return false;
+            if (g.act != ACT_GELU || res || epi != 0 || g.C2 || g.A2 || g.form == 2) return false;   // (no thin form with LayerNorm)
+#define GEMM_MAP(L, A, R, E) DSG_LAUNCH((gemm4_f32_kernel<L, A, R, E, 8, 3>), grid, block, 0, s, g, tiles_m, tiles_n)
             GEMM_MAP(true, ACT_GELU, false, 0);
+#undef GEMM_MAP
         } else {
             if (g.act != ACT_NONE || (g.C2 && res) || (g.mod_aff && !g.stats_out)) return false;   // (dual store: the list form of PatchMerging's reduction)
+            // Both forms live in one kernel and the block picks one from the device-side count, so the grid is the larger of the two
+            // forms' shape-derived sizes.  The thin form (64-row tiles) is only ever chosen while its tiles number at most n_cu
+            // (gemm_thin_rule), so its share of the grid is capped there: a launch too large to qualify keeps the wide grid.
+            int thin_tiles_m = (g.M + TBM - 1) / TBM;
+            if (g.form == 0) thin_tiles_m = std::min(thin_tiles_m, g.n_cu > 0 ? 2 * ((g.n_cu / 2) / tiles_n) : 0);
+            if (g.form == 1) thin_tiles_m = 0;
+            const dim3 gridl(std::max(grid.x, (unsigned)(((thin_tiles_m + 7) / 8) * 8 * tiles_n)));
+#define GEMM_MAP(L, A, R, E) DSG_LAUNCH((gemm4_f32_kernel<L, A, R, E, 8, 3>), gridl, block, 0, s, g, tiles_m, tiles_n)
             if (res) { if (epi == 0) GEMM_MAP(false, ACT_NONE, true, 0); else if (epi == 1) GEMM_MAP(false, ACT_NONE, true, 1); else if (epi == 2) GEMM_MAP(false, ACT_NONE, true, 2); else GEMM_MAP(false, ACT_NONE, true, 3); }
             else { if (epi == 0) GEMM_MAP(false, ACT_NONE, false, 0); else if (epi == 1) GEMM_MAP(false, ACT_NONE, false, 1); else if (epi == 2) GEMM_MAP(false, ACT_NONE, false, 2); else GEMM_MAP(false, ACT_NONE, false, 3); }
         }

@@ -15,7 +15,7 @@ EXPORTS = [
     "dsg_create", "dsg_destroy", "dsg_last_error", "dsg_version", "dsg_abi_version", "dsg_set_weight", "dsg_finalize_weights",
     "dsg_num_weight_keys", "dsg_weight_key", "dsg_workspace_bytes", "dsg_denoise", "dsg_precond", "dsg_sample",
     "dsg_sigma_schedule", "dsg_debug_tap", "dsg_debug_clear_taps", "dsg_decode_bits", "dsg_decode", "dsg_profile_forward", "dsg_set_option",
-    "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_f32", "dsg_debug_qkv_attn_f32", "dsg_debug_window_attn_f32", "dsg_debug_fused_mlp_f32", "dsg_debug_fused_attn96_f32", "dsg_debug_t_gemm", "dsg_debug_t_attn", "dsg_debug_t_ln", "dsg_debug_t_modulate", "dsg_debug_t_colsum", "dsg_debug_t_grouped", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists", "dsg_debug_dedup_lists", "dsg_debug_dedup_level_lists",
+    "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_f32", "dsg_debug_gemm_form", "dsg_debug_qkv_attn_f32", "dsg_debug_window_attn_f32", "dsg_debug_fused_mlp_f32", "dsg_debug_fused_attn96_f32", "dsg_debug_t_gemm", "dsg_debug_t_attn", "dsg_debug_t_ln", "dsg_debug_t_modulate", "dsg_debug_t_colsum", "dsg_debug_t_grouped", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists", "dsg_debug_dedup_lists", "dsg_debug_dedup_level_lists",
     "dsg_debug_dedup_launch_lists",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
@@ -172,6 +172,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_profile_clock_ghz.restype = C.c_double
     L.dsg_debug_gemm.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     L.dsg_debug_gemm_f32.argtypes = [C.POINTER(DsgGemmF32Args), vp]
+    L.dsg_debug_gemm_form.argtypes = [i32, i32, i32]
+    L.dsg_debug_gemm_form.restype = i32
     L.dsg_debug_qkv_attn_f32.argtypes = [i32] * 6 + [vp] * 5 + [i32] + [vp] * 5
     L.dsg_debug_window_attn_f32.argtypes = [i32] * 5 + [vp] * 4
     L.dsg_debug_fused_mlp_f32.argtypes = [i32, i32] + [vp] * 11

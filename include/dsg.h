@@ -466,7 +466,10 @@ int dsg_debug_gemm(int32_t M, int32_t N, int32_t K, const float *A, const float 
  *     mod_aff          silu(shift + v (1 + scale)) on the value stored to C, (scale, shift) = mod_aff[b mod_ld + mod_off + {n, N + n}],
  *                      b = row / mod_T (mod_ld == 0: one row for the whole batch); needs stats_out
  *     a4_res > 0       PatchMerging gather: A is the fine activation [B a4_res^2, K/4], M = B (a4_res/2)^2, ln_part per fine row
- *     row_list/row_cnt only the 8-row runs listed (device int32, -1 pads to a multiple of 16), *row_cnt of them (device) */
+ *     row_list/row_cnt only the 8-row runs listed (device int32, -1 pads to a multiple of 16), *row_cnt of them (device)
+ *     reserved         form of a list launch: 0 the kernel's own rule (dsg_debug_gemm_form with the device's CU count), 1 the wide form
+ *                      (128-row tiles), 2 the thin form (64-row tiles; same bits).  2 without a list, or for a form that has no thin
+ *                      kernel (LayerNorm on the way in), is DSG_ERR_INVALID. */
 typedef struct dsg_gemm_f32_args {
     const float *A, *A2, *W, *bias, *ln_stats, *ln_part, *res;
     float *C, *C2;
@@ -476,6 +479,9 @@ typedef struct dsg_gemm_f32_args {
     int32_t lda, lda2, K1, ln_nparts, ldres, ldc, ldc2, M, N, K, act, mod_ld, mod_off, mod_T, a4_res, reserved;
 } dsg_gemm_f32_args;
 int dsg_debug_gemm_f32(const dsg_gemm_f32_args *args, void *stream);
+/* The list GEMM's form rule, from the function its kernel evaluates on the device-side count: 2 (thin) iff the wide form's
+ * ceil(cnt_runs / 16) x ceil(N / 96) tiles would occupy at most half of n_cu compute units, else 1 (wide); n_cu = 0: always 1.  Host only. */
+int32_t dsg_debug_gemm_form(int32_t cnt_runs, int32_t N, int32_t n_cu);
 /* LayerNorm-1 -> QKV -> window attention in the GEMM's epilogue (8 x 8 and 10 x 10 windows): x [B res^2, K], W [3C, K] (C = 32 heads,
  * q rows pre-scaled by d^-1/2 log2 e), bias [3C], one of ln_stats / ln_part, attn_bias the key-major log2(e)-scaled table
  * [nW | 1][heads][Wp][Wp] (-1e30 in padded key slots); win_list / win_cnt (device, 8 x 8 only): only those windows (b nW + w, -1: none)
