@@ -64,10 +64,19 @@ struct BlockPlan {
     float *qkv_wf = nullptr, *qkv_bf = nullptr, *fc1_wf = nullptr, *fc1_bf = nullptr;
 };
 
+// Every device buffer a handle or one of its workspaces owns, with what a forward may assume about it ("what a forward
+// may assume about its workspace"); owned_alloc below is the only hipMalloc of such memory.
+//   AC_SCRATCH  float / bf16 data that every entry point writes before it reads
+//   AC_FINITE   x, y, att, hid, stats: stale rows may be read into lanes whose results are discarded -- finite, not unread
+//   AC_STATE    read as an index, a count, a byte mask, a seed or an address: never filled by the test hooks
+//   AC_CONST    weights and what is derived from them
+enum AllocClass { AC_SCRATCH = 0, AC_FINITE = 1, AC_STATE = 2, AC_CONST = 3 };
+struct AllocRec { void *p; size_t bytes; AllocClass cls; };
+
 struct Workspace {
     int B = 0;
     size_t bytes = 0;
-    std::vector<void *> allocs;
+    std::vector<AllocRec> allocs;
     // network forward (fixed addresses: the captured graph reads/writes these)
     float *in_adj, *in_node, *sc_adj, *sc_node, *c_noise, *f_adj, *f_node;
     uint8_t *flags;
@@ -167,7 +176,10 @@ struct dsg_handle_s {
     float *ro_fapb = nullptr, *ro_f2pb = nullptr;   // the same two matrices in the bf16 MFMA's fragment order (fp32 here; their bf16 copies are what runs)
     float *ro0_wf = nullptr, *ro0_bf = nullptr;  // read_out.0 ([out,in]) with the final norm's gamma/beta folded in
     float *merge_wf[DSG_MAX_LAYERS] = {}, *merge_bf[DSG_MAX_LAYERS] = {};   // PatchMerging reduction with its LayerNorm(4C) folded in
-    std::vector<void *> derived_allocs;
+    std::vector<AllocRec> derived_allocs;   // freed and rebuilt by every dsg_finalize_weights
+    std::vector<AllocRec> allocs;           // everything else the handle itself owns (weights and their copies, tab_*, the train_* arenas)
+    int opt_debug_alloc_fill = 0;           // test hook: pattern every AC_SCRATCH / AC_FINITE allocation is filled with (0: none; launch_debug_fill)
+    unsigned long long debug_fill_count = 0;
     std::map<int, std::unique_ptr<Workspace>> ws;
     // kernel-selection options (dsg_set_option); defaults may be overridden once by DSG_* environment variables
     bool opt_fused_attn = true, opt_fused_mlp = true, opt_fused_readout = true, opt_fused_pe = true;
@@ -405,10 +417,29 @@ std::string strip_prefix(const char *key) {
 
 const float *WT(dsg_handle h, const std::string &key) { return h->w.at(key).p; }
 
-int dev_alloc(dsg_handle h, std::vector<void *> &pool, void **p, size_t bytes) {
-    HIP_TRY(h, hipMalloc(p, bytes ? bytes : 16));
-    pool.push_back(*p);
+// The one hipMalloc of handle- or workspace-owned memory: records pointer, size and class in `pool`.  Under the test option
+// "debug_alloc_fill" a scratch buffer starts as that pattern instead of whatever the allocator returned -- ahead of the caller's own
+// creation memsets, which therefore stay effective.  The fill runs on the null stream and is waited for: allocations happen outside
+// stream capture, before the call's first launch on the caller's stream
+int owned_alloc(dsg_handle h, std::vector<AllocRec> &pool, void **p, size_t bytes, AllocClass cls) {
+    bytes = bytes ? bytes : 16;
+    HIP_TRY(h, hipMalloc(p, bytes));
+    pool.push_back(AllocRec{*p, bytes, cls});
+    if (h->opt_debug_alloc_fill && (cls == AC_SCRATCH || cls == AC_FINITE)) {
+        launch_debug_fill(*p, bytes / 4, h->opt_debug_alloc_fill, 0x5eedull + h->debug_fill_count++, nullptr);
+        HIP_TRY(h, hipStreamSynchronize(nullptr));
+    }
     return 0;
+}
+void owned_free(std::vector<AllocRec> &pool, void *p) {
+    if (!p) return;
+    for (size_t i = 0; i < pool.size(); i++)
+        if (pool[i].p == p) { pool.erase(pool.begin() + i); break; }
+    (void)hipFree(p);
+}
+void owned_free_all(std::vector<AllocRec> &pool) {
+    for (auto &r : pool) (void)hipFree(r.p);
+    pool.clear();
 }
 
 // dense, key-major (transposed) bias+mask table of one block: [nWt][heads][Wp][Wp], entry [key][query]
@@ -450,17 +481,17 @@ int build_bias_table(dsg_handle h, BlockPlan &bp) {
         }
     }
     void *p;
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * out.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * out.size(), AC_CONST)) return rc;
     HIP_TRY(h, hipMemcpy(p, out.data(), sizeof(float) * out.size(), hipMemcpyHostToDevice));
     bp.biasT = (float *)p;
     void *pp;
-    if (int rc = dev_alloc(h, h->derived_allocs, &pp, sizeof(uint16_t) * out.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &pp, sizeof(uint16_t) * out.size(), AC_CONST)) return rc;
     launch_bias_permute_bx(bp.biasT, pp, nWt * heads, Wp, nullptr);
     HIP_TRY(h, hipStreamSynchronize(nullptr));
     bp.biasP = pp;
     if (ws == 10) {
         void *pf;
-        if (int rc = dev_alloc(h, h->derived_allocs, &pf, sizeof(float) * out.size())) return rc;
+        if (int rc = owned_alloc(h, h->derived_allocs, &pf, sizeof(float) * out.size(), AC_CONST)) return rc;
         launch_bias_permute_f32(bp.biasT, (float *)pf, nWt * heads, Wp, nullptr);
         HIP_TRY(h, hipStreamSynchronize(nullptr));
         bp.biasF = (float *)pf;
@@ -491,10 +522,10 @@ int pack_mlp_weights(dsg_handle h, BlockPlan &bp) {
                         p2[((((size_t)nt * CT + ct) * 4 + g) * 64 + lane) * 4 + t] =
                             w2[(size_t)(32 * ct + (lane & 31)) * Hd + 32 * nt + 8 * g + 4 * (lane >> 5) + t];
     void *p;
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * p1.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * p1.size(), AC_CONST)) return rc;
     bp.w1p = (float *)p;
     HIP_TRY(h, hipMemcpy(bp.w1p, p1.data(), sizeof(float) * p1.size(), hipMemcpyHostToDevice));
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * p2.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * p2.size(), AC_CONST)) return rc;
     bp.w2p = (float *)p;
     HIP_TRY(h, hipMemcpy(bp.w2p, p2.data(), sizeof(float) * p2.size(), hipMemcpyHostToDevice));
     return 0;
@@ -515,10 +546,10 @@ int fold_ln(dsg_handle h, const float *W, const float *bias, const float *gamma,
         b[n] = (float)(acc * rs);
     }
     void *p;
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * w.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * w.size(), AC_CONST)) return rc;
     *Wf = (float *)p;
     HIP_TRY(h, hipMemcpy(p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * N)) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * N, AC_CONST)) return rc;
     *bf = (float *)p;
     HIP_TRY(h, hipMemcpy(p, b.data(), sizeof(float) * N, hipMemcpyHostToDevice));
     return 0;
@@ -551,13 +582,13 @@ int pack_attn_weights(dsg_handle h, BlockPlan &bp) {
                         p2[((((size_t)hd * CT + ct) * 4 + g) * 64 + lane) * 4 + t] =
                             wp[(size_t)(32 * ct + (lane & 31)) * C + 32 * hd + 8 * g + 4 * (lane >> 5) + t];
     void *p;
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * p1.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * p1.size(), AC_CONST)) return rc;
     bp.wqp = (float *)p;
     HIP_TRY(h, hipMemcpy(bp.wqp, p1.data(), sizeof(float) * p1.size(), hipMemcpyHostToDevice));
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * p2.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * p2.size(), AC_CONST)) return rc;
     bp.wpp = (float *)p;
     HIP_TRY(h, hipMemcpy(bp.wpp, p2.data(), sizeof(float) * p2.size(), hipMemcpyHostToDevice));
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * bq.size())) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * bq.size(), AC_CONST)) return rc;
     bp.bqkv_s = (float *)p;
     HIP_TRY(h, hipMemcpy(bp.bqkv_s, bq.data(), sizeof(float) * bq.size(), hipMemcpyHostToDevice));
     return 0;
@@ -573,7 +604,7 @@ int ensure_bf16_weights(dsg_handle h) {
     for (auto &pw : h->gemm_weights) {
         if (h->w_bf16.count(pw.first)) continue;
         void *q;
-        HIP_TRY(h, hipMalloc(&q, pw.second * 2));
+        if (int rc = owned_alloc(h, h->allocs, &q, pw.second * 2, AC_CONST)) return rc;
         launch_f32_to_bf16(pw.first, q, pw.second, nullptr);
         h->w_bf16[pw.first] = q;
     }
@@ -586,7 +617,7 @@ int ensure_bf16_weights(dsg_handle h) {
                     const float *w2 = WT(h, b.prefix + ".mlp.fc2.weight"), *wp = WT(h, b.prefix + ".attn.proj.weight");
                     if (!h->w_bf16.count(b.fc1_wf) || !h->w_bf16.count(w2) || !h->w_bf16.count(wp)) continue;
                     void *q;
-                    HIP_TRY(h, hipMalloc(&q, mlp96r_image_bytes()));
+                    if (int rc = owned_alloc(h, h->allocs, &q, mlp96r_image_bytes(), AC_CONST)) return rc;
                     launch_mlp96r_image(h->w_bf16[b.fc1_wf], h->w_bf16[w2], h->w_bf16[wp], q, nullptr);
                     h->w_img96[b.fc1_wf] = q;
                 }
@@ -596,7 +627,7 @@ int ensure_bf16_weights(dsg_handle h) {
             for (auto &b : *vec) {
                 if (!b.qkv_wf || b.ws != 10 || h->w_qimg.count(b.qkv_wf) || !h->w_bf16.count(b.qkv_wf)) continue;
                 void *q;
-                HIP_TRY(h, hipMalloc(&q, (size_t)3 * b.C * b.C * 2));
+                if (int rc = owned_alloc(h, h->allocs, &q, (size_t)3 * b.C * b.C * 2, AC_CONST)) return rc;
                 launch_qkv_image(h->w_bf16[b.qkv_wf], q, b.C, b.heads, nullptr);
                 h->w_qimg[b.qkv_wf] = q;
             }
@@ -609,10 +640,10 @@ int ensure_bf16_weights(dsg_handle h) {
                     const float *w2 = WT(h, b.prefix + ".mlp.fc2.weight"), *wp = WT(h, b.prefix + ".attn.proj.weight");
                     if (!h->w_bf16.count(b.fc1_wf) || !h->w_bf16.count(w2) || !h->w_bf16.count(wp)) continue;
                     void *q;
-                    HIP_TRY(h, hipMalloc(&q, mlp384_image_bytes()));
+                    if (int rc = owned_alloc(h, h->allocs, &q, mlp384_image_bytes(), AC_CONST)) return rc;
                     launch_mlp384_images(h->w_bf16[b.fc1_wf], h->w_bf16[w2], h->w_bf16[wp], q, nullptr);
                     h->w_img[b.fc1_wf] = q;
-                    HIP_TRY(h, hipMalloc(&q, mlp384_image_bytes()));
+                    if (int rc = owned_alloc(h, h->allocs, &q, mlp384_image_bytes(), AC_CONST)) return rc;
                     launch_mlp384s_images(h->w_bf16[b.fc1_wf], h->w_bf16[w2], h->w_bf16[wp], q, nullptr);
                     h->w_img2[b.fc1_wf] = q;
                 }
@@ -638,7 +669,7 @@ int ensure_split_weights(dsg_handle h) {
     for (auto &pw : h->gemm_weights) {
         if (h->w_split.count(pw.first)) continue;
         void *q;
-        HIP_TRY(h, hipMalloc(&q, pw.second * 6));
+        if (int rc = owned_alloc(h, h->allocs, &q, pw.second * 6, AC_CONST)) return rc;
         launch_f32_split3(pw.first, q, pw.second, nullptr);
         h->w_split[pw.first] = q;
     }
@@ -718,25 +749,13 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
 
 void dsg_destroy(dsg_handle h) {
     if (!h) return;
-    for (auto &kv : h->w) (void)hipFree(kv.second.p);
-    for (auto &kv : h->w_bf16) (void)hipFree(kv.second);
-    for (auto &kv : h->w_img) (void)hipFree(kv.second);
-    for (auto &kv : h->w_img2) (void)hipFree(kv.second);
-    for (auto &kv : h->w_qimg) (void)hipFree(kv.second);
-    for (auto &kv : h->w_img96) (void)hipFree(kv.second);
-    for (auto &kv : h->w_split) (void)hipFree(kv.second);
-    for (void *p : h->derived_allocs) (void)hipFree(p);
+    owned_free_all(h->derived_allocs);
     for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
-    if (h->prof_gemm) (void)hipFree(h->prof_gemm);
-    for (float *q : {h->tab_sig, h->tab_cn, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff}) if (q) (void)hipFree(q);
     drop_graphs(h);
-    if (h->tab_step) (void)hipFree(h->tab_step);
-    for (DevBuf *b : {&h->train_arena, &h->train_scr, &h->train_io, &h->train_vjp, &h->train_ode}) if (b->p) (void)hipFree(b->p);
-    if (h->train_const) (void)hipFree(h->train_const);
+    owned_free_all(h->allocs);   // weights and their copies, prof_gemm, tab_*, tab_step, the train_* arenas, train_const
     for (auto &kv : h->ws) {
         if (kv.second->cap_stream) (void)hipStreamDestroy(kv.second->cap_stream);
-        for (void *p : kv.second->allocs) (void)hipFree(p);
-        if (kv.second->tab_pure) (void)hipFree(kv.second->tab_pure);
+        owned_free_all(kv.second->allocs);   // tab_pure and the first-use buffers included
     }
     delete h;
     if (--g_live_handles == 0) { (void)hipDeviceSynchronize(); t_scratch_release(); }
@@ -768,7 +787,7 @@ int dsg_set_weight(dsg_handle h, const char *key, const void *data, const int64_
         t.numel = numel; t.shape = sp->shape;
         return DSG_OK;
     }
-    if (!t.p) HIP_TRY(h, hipMalloc((void **)&t.p, sizeof(float) * numel));
+    if (!t.p) if (int rc = owned_alloc(h, h->allocs, (void **)&t.p, sizeof(float) * numel, AC_CONST)) return rc;
     HIP_TRY(h, hipMemcpy(t.p, data, sizeof(float) * numel, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     t.numel = numel; t.shape = sp->shape;
     h->finalized = false;
@@ -779,8 +798,7 @@ int dsg_finalize_weights(dsg_handle h) {
     if (!h) return DSG_ERR_INVALID;
     for (auto &s : h->specs)
         if (!h->w.count(s.key)) return fail(h, DSG_ERR_WEIGHTS, "missing key '%s' (strict load)", s.key.c_str());
-    for (void *p : h->derived_allocs) (void)hipFree(p);
-    h->derived_allocs.clear();
+    owned_free_all(h->derived_allocs);
     for (int l = 0; l < DSG_MAX_LAYERS; l++) { h->down[l].clear(); h->up[l].clear(); }
     const dsg_config &c = h->cfg;
     const int E = h->E, L = h->L;
@@ -804,9 +822,9 @@ int dsg_finalize_weights(dsg_handle h) {
     h->prune.built = false;
     h->aff_n = off;
     void *p;
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * (size_t)off * NOISE_EMB)) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * (size_t)off * NOISE_EMB, AC_CONST)) return rc;
     h->aff_w = (float *)p;
-    if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * (size_t)off)) return rc;
+    if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * (size_t)off, AC_CONST)) return rc;
     h->aff_b = (float *)p;
     {
         size_t o = 0;
@@ -842,7 +860,7 @@ int dsg_finalize_weights(dsg_handle h) {
         HIP_TRY(h, hipMemcpy(src.data(), WT(h, "patch_embed.proj.weight"), sizeof(float) * src.size(), hipMemcpyDeviceToHost));
         for (int e = 0; e < E; e++)
             for (int k = 0; k < h->Cin; k++) dst[(size_t)e * h->Kp + k] = src[(size_t)e * h->Cin + k];
-        if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * dst.size())) return rc;
+        if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * dst.size(), AC_CONST)) return rc;
         h->pe_w = (float *)p;
         HIP_TRY(h, hipMemcpy(h->pe_w, dst.data(), sizeof(float) * dst.size(), hipMemcpyHostToDevice));
         h->pe_wp = nullptr;
@@ -854,7 +872,7 @@ int dsg_finalize_weights(dsg_handle h) {
                     for (int lane = 0; lane < 64; lane++)
                         for (int t = 0; t < 4; t++)
                             pk[(((size_t)nt * S + sx) * 64 + lane) * 4 + t] = dst[(size_t)(32 * nt + (lane & 31)) * h->Kp + 8 * sx + 4 * (lane >> 5) + t];
-            if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * pk.size())) return rc;
+            if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * pk.size(), AC_CONST)) return rc;
             h->pe_wp = (float *)p;
             HIP_TRY(h, hipMemcpy(h->pe_wp, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice));
         }
@@ -865,7 +883,7 @@ int dsg_finalize_weights(dsg_handle h) {
         HIP_TRY(h, hipMemcpy(src.data(), WT(h, "read_out.0.weight"), sizeof(float) * src.size(), hipMemcpyDeviceToHost));
         for (int i = 0; i < E; i++)
             for (int o = 0; o < E; o++) dst[(size_t)o * E + i] = src[(size_t)i * E + o];
-        if (int rc = dev_alloc(h, h->derived_allocs, &p, sizeof(float) * dst.size())) return rc;
+        if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * dst.size(), AC_CONST)) return rc;
         h->ro0_w = (float *)p;
         HIP_TRY(h, hipMemcpy(h->ro0_w, dst.data(), sizeof(float) * dst.size(), hipMemcpyHostToDevice));
         if (int rc = fold_ln(h, h->ro0_w, WT(h, "read_out.0.bias"), WT(h, "norm.weight"), WT(h, "norm.bias"), E, E, &h->ro0_wf, &h->ro0_bf)) return rc;
@@ -916,7 +934,7 @@ int dsg_finalize_weights(dsg_handle h) {
         }
         auto up = [&](const std::vector<float> &v, float **dst) -> int {
             void *q;
-            if (int rc = dev_alloc(h, h->derived_allocs, &q, sizeof(float) * v.size())) return rc;
+            if (int rc = owned_alloc(h, h->derived_allocs, &q, sizeof(float) * v.size(), AC_CONST)) return rc;
             *dst = (float *)q;
             HIP_TRY(h, hipMemcpy(q, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice));
             return 0;
@@ -947,17 +965,17 @@ int dsg_finalize_weights(dsg_handle h) {
     }
     drop_graphs(h);   // captured graphs bake weight pointers
     // bf16 copies (opt-in mode): drop stale ones, list every GEMM weight, rebuild if the mode is on
-    for (auto &kv : h->w_bf16) (void)hipFree(kv.second);
+    for (auto &kv : h->w_bf16) owned_free(h->allocs, kv.second);
     h->w_bf16.clear();
-    for (auto &kv : h->w_img) (void)hipFree(kv.second);
+    for (auto &kv : h->w_img) owned_free(h->allocs, kv.second);
     h->w_img.clear();
-    for (auto &kv : h->w_img2) (void)hipFree(kv.second);
+    for (auto &kv : h->w_img2) owned_free(h->allocs, kv.second);
     h->w_img2.clear();
-    for (auto &kv : h->w_qimg) (void)hipFree(kv.second);
+    for (auto &kv : h->w_qimg) owned_free(h->allocs, kv.second);
     h->w_qimg.clear();
-    for (auto &kv : h->w_img96) (void)hipFree(kv.second);
+    for (auto &kv : h->w_img96) owned_free(h->allocs, kv.second);
     h->w_img96.clear();
-    for (auto &kv : h->w_split) (void)hipFree(kv.second);
+    for (auto &kv : h->w_split) owned_free(h->allocs, kv.second);
     h->w_split.clear();
     h->gemm_weights.clear();
     for (auto &kv : h->w)
@@ -1017,35 +1035,37 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
     w->B = B;
     const size_t T0 = (size_t)h->N * h->N, E = h->E;
     const size_t sa = (size_t)B * h->Ca * h->N * h->N, sn = (size_t)B * h->N * h->Cn;
-    auto A = [&](float **p, size_t n) -> int {
+    auto A = [&](float **p, size_t n, AllocClass cls) -> int {
         void *q;
-        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * n)) return rc;
+        if (int rc = owned_alloc(h, w->allocs, &q, sizeof(float) * n, cls)) return rc;
         *p = (float *)q; w->bytes += sizeof(float) * n;
         return 0;
     };
-#define ALLOC(ptr, n) do { if (int rc = A(&(ptr), (n))) return rc; } while (0)
+#define ALLOC(ptr, n) do { if (int rc = A(&(ptr), (n), AC_SCRATCH)) return rc; } while (0)
+#define ALLOC_FINITE(ptr, n) do { if (int rc = A(&(ptr), (n), AC_FINITE)) return rc; } while (0)
     ALLOC(w->in_adj, sa); ALLOC(w->in_node, sn); ALLOC(w->sc_adj, sa); ALLOC(w->sc_node, sn);
     ALLOC(w->f_adj, sa); ALLOC(w->f_node, sn); ALLOC(w->c_noise, B); ALLOC(w->sig, B);
     ALLOC(w->pe, (size_t)B * E); ALLOC(w->emb0, (size_t)B * NOISE_EMB); ALLOC(w->emb, (size_t)B * NOISE_EMB);
     ALLOC(w->aff, (size_t)B * h->aff_n);
     ALLOC(w->tok_in, (size_t)B * T0 * h->Kp);
-    ALLOC(w->x, (size_t)B * T0 * E); ALLOC(w->y, (size_t)B * T0 * E);
+    ALLOC_FINITE(w->x, (size_t)B * T0 * E); ALLOC_FINITE(w->y, (size_t)B * T0 * E);
     { float *xn_; ALLOC(xn_, (size_t)B * T0 * E / 2 + 64); w->xn = xn_; }
-    ALLOC(w->qkv, (size_t)B * 3 * T0 * E); ALLOC(w->att, (size_t)B * T0 * E);
-    ALLOC(w->hid, (size_t)B * h->cfg.mlp_ratio * T0 * E);
-    ALLOC(w->stats, (size_t)B * 2 * T0);
+    ALLOC(w->qkv, (size_t)B * 3 * T0 * E); ALLOC_FINITE(w->att, (size_t)B * T0 * E);
+    ALLOC_FINITE(w->hid, (size_t)B * h->cfg.mlp_ratio * T0 * E);
+    ALLOC_FINITE(w->stats, (size_t)B * 2 * T0);
     ALLOC(w->pool, (size_t)B * h->N * E); ALLOC(w->hn, (size_t)B * h->N * E); ALLOC(w->pool_ext, (size_t)B * h->N * 128);
     ALLOC(w->pool_part, (size_t)B * h->N * readout_pool_segments(h->N) * 96);
     for (int l = 0; l < h->L; l++) ALLOC(w->skips[l], ((size_t)B * T0 * E) >> (l + 1 < h->L ? l + 1 : l));
     ALLOC(w->x_adj, sa); ALLOC(w->x_node, sn); ALLOC(w->xh_adj, sa); ALLOC(w->xh_node, sn);
     for (int k = 0; k < 3; k++) { ALLOC(w->d_adj[k], sa); ALLOC(w->d_node[k], sn); }
 #undef ALLOC
+#undef ALLOC_FINITE
     void *q;
-    if (int rc = dev_alloc(h, w->allocs, &q, (size_t)B * h->N)) return rc;
+    if (int rc = owned_alloc(h, w->allocs, &q, (size_t)B * h->N, AC_STATE)) return rc;
     w->flags = (uint8_t *)q;
-    if (int rc = dev_alloc(h, w->allocs, &q, 16)) return rc;
+    if (int rc = owned_alloc(h, w->allocs, &q, 16, AC_STATE)) return rc;
     w->has_sc = (int *)q;
-    if (int rc = dev_alloc(h, w->allocs, &q, sizeof(RunCtl))) return rc;
+    if (int rc = owned_alloc(h, w->allocs, &q, sizeof(RunCtl), AC_STATE)) return rc;
     w->ctl = (RunCtl *)q;
     // masked-token pruning leaves the rows nobody reads untouched: they must never hold anything but finite numbers
     HIP_TRY(h, hipMemset(w->x, 0, sizeof(float) * (size_t)B * T0 * E));
@@ -1060,7 +1080,7 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
         for (int k = 0; k < nl; k++) { w->need.list_off[k] = (int)off; off += (size_t)B * prune_plan(h).items[k] + 16; }
         const bool dd = w->need.dd_n > 0;
         w->need_ints = off + nl + (size_t)B * nl + (size_t)B * w->need.dd_n + (dd ? 1 : 0);   // (+ the mode the lists were written for, behind dd_rep)
-        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(int) * w->need_ints)) return rc;
+        if (int rc = owned_alloc(h, w->allocs, &q, sizeof(int) * w->need_ints, AC_STATE)) return rc;
         HIP_TRY(h, hipMemset(q, 0, sizeof(int) * w->need_ints));   // counts of 0 until the first flags are staged
         w->need_lists = (int *)q; w->need_cnt = w->need_lists + off; w->need_cnt_ps = w->need_cnt + nl;
         if (dd) w->dd_rep = w->need_cnt_ps + (size_t)B * nl;
@@ -1914,7 +1934,7 @@ int stage_flags(dsg_handle h, Workspace *w, const uint8_t *flags, hipStream_t s,
 int stage_seeds(dsg_handle h, Workspace *w, const uint64_t *graph_seeds, hipStream_t s) {
     if (!w->gseeds) {
         void *q;
-        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(unsigned long long) * (size_t)w->B)) return rc;
+        if (int rc = owned_alloc(h, w->allocs, &q, sizeof(unsigned long long) * (size_t)w->B, AC_STATE)) return rc;
         w->gseeds = (unsigned long long *)q;
         w->seeds_bytes = sizeof(unsigned long long) * (size_t)w->B;
         w->bytes += w->seeds_bytes;
@@ -2139,6 +2159,12 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         h->opt_dedup_table = value != 0;
         return DSG_OK;
     }
+    else if (n == "debug_alloc_fill") {
+        // test hook: no launch of any entry point changes, only what later scratch allocations hold when they are first read
+        if (value < 0 || value > 4) return fail(h, DSG_ERR_INVALID, "debug_alloc_fill is 0 (off) or a pattern 1..4, not %d", value);
+        h->opt_debug_alloc_fill = value;
+        return DSG_OK;
+    }
     else if (n == "batch_invariant") h->opt_batch_invariant = value != 0;
     else if (n == "fused_merge") { h->opt_fused_merge = value != 0; h->opt_fused_merge_small = value > 1; }   // 2: at every size
     else if (n == "gemm_bf16") {
@@ -2186,11 +2212,32 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "dedup_levels") *value = dedup_levels(h);   // what runs (in the sampler, where PatchMerging takes its partial-statistics form)
     else if (n == "dedup_batch") *value = dedup_opts_on(h) ? h->opt_dedup_batch : 0;   // what runs (in the sampler; 1: from 16 graphs)
     else if (n == "dedup_table") *value = dedup_opts_on(h) && h->opt_dedup_batch > 0 && h->opt_dedup_table;   // what runs (in the sampler, where the batch shares one representative)
+    else if (n == "debug_alloc_fill") *value = h->opt_debug_alloc_fill;
     else if (n == "batch_invariant") *value = h->opt_batch_invariant;
     else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
     else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
     else if (n == "gemm_split") *value = h->opt_gemm_split;
     else return fail(h, DSG_ERR_INVALID, "unknown option '%s'", name);
+    return DSG_OK;
+}
+
+// test hook (include/dsg.h): every existing AC_SCRATCH / AC_FINITE buffer of the handle and of batch size B's workspace becomes
+// `pattern`; AC_STATE and AC_CONST buffers are never touched.  NaN is not written into the AC_FINITE buffers: their contract is "finite"
+int dsg_debug_poison(dsg_handle h, int32_t B, int32_t pattern, uint64_t seed, void *stream) {
+    if (int rc = check_ready(h, B)) return rc;
+    if (pattern < 1 || pattern > 4) return fail(h, DSG_ERR_INVALID, "pattern is 1 (zeros), 2 (NaN), 3 (1e30) or 4 (random), not %d", pattern);
+    hipStream_t s = (hipStream_t)stream;
+    Workspace *w;
+    if (int rc = get_workspace(h, B, &w)) return rc;
+    unsigned long long k = 0;
+    for (const std::vector<AllocRec> *pool : {&h->allocs, &w->allocs})
+        for (const AllocRec &r : *pool) {
+            k++;
+            if (r.cls != AC_SCRATCH && r.cls != AC_FINITE) continue;
+            if (r.cls == AC_FINITE && pattern == 2) continue;
+            launch_debug_fill(r.p, r.bytes / 4, pattern, seed * 0x100000001b3ull + k, s);
+        }
+    HIP_TRY(h, hipGetLastError());
     return DSG_OK;
 }
 
@@ -2377,9 +2424,9 @@ int build_pure_table(dsg_handle h, Workspace *w, int T, hipStream_t s) {
     if (w->tab_pure_cap < T) {
         drop_graphs(h);
         w->bytes -= w->tab_pure_bytes;
-        if (w->tab_pure) { (void)hipFree(w->tab_pure); w->tab_pure = nullptr; }
-        w->tab_pure_cap = 0; w->tab_pure_bytes = 0;
-        HIP_TRY(h, hipMalloc((void **)&w->tab_pure, sizeof(float) * ptl.stride * (size_t)T));
+        owned_free(w->allocs, w->tab_pure);
+        w->tab_pure = nullptr; w->tab_pure_cap = 0; w->tab_pure_bytes = 0;
+        if (int rc = owned_alloc(h, w->allocs, (void **)&w->tab_pure, sizeof(float) * ptl.stride * (size_t)T, AC_SCRATCH)) return rc;
         w->tab_pure_cap = T;
         w->tab_pure_bytes = sizeof(float) * ptl.stride * (size_t)T;
         w->bytes += w->tab_pure_bytes;
@@ -2538,21 +2585,19 @@ int step_tables(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, 
     const int T = p.T, L = p.L;
     if (h->tab_cap < T) {
         drop_graphs(h);   // the captured step bodies bake the table addresses
-        for (float **q : {&h->tab_sig, &h->tab_cn, &h->tab_pe, &h->tab_e0, &h->tab_e1, &h->tab_aff}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+        for (float **q : {&h->tab_sig, &h->tab_cn, &h->tab_pe, &h->tab_e0, &h->tab_e1, &h->tab_aff}) { owned_free(h->allocs, *q); *q = nullptr; }
         h->tab_cap = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->tab_sig, sizeof(float) * T));
-        HIP_TRY(h, hipMalloc((void **)&h->tab_cn, sizeof(float) * T));
-        HIP_TRY(h, hipMalloc((void **)&h->tab_pe, sizeof(float) * (size_t)T * h->E));
-        HIP_TRY(h, hipMalloc((void **)&h->tab_e0, sizeof(float) * (size_t)T * NOISE_EMB));
-        HIP_TRY(h, hipMalloc((void **)&h->tab_e1, sizeof(float) * (size_t)T * NOISE_EMB));
-        HIP_TRY(h, hipMalloc((void **)&h->tab_aff, sizeof(float) * (size_t)T * h->aff_n));
+        const std::pair<float **, size_t> tabs[] = {{&h->tab_sig, (size_t)T}, {&h->tab_cn, (size_t)T}, {&h->tab_pe, (size_t)T * h->E},
+                                                    {&h->tab_e0, (size_t)T * NOISE_EMB}, {&h->tab_e1, (size_t)T * NOISE_EMB},
+                                                    {&h->tab_aff, (size_t)T * h->aff_n}};
+        for (auto &t : tabs) if (int rc = owned_alloc(h, h->allocs, (void **)t.first, sizeof(float) * t.second, AC_SCRATCH)) return rc;
         h->tab_cap = T;
     }
     if (h->tab_step_cap < L) {   // one row per executed step: its own capacity, the tables above stay at one row per schedule index
         drop_graphs(h);
-        if (h->tab_step) { (void)hipFree(h->tab_step); h->tab_step = nullptr; }
-        h->tab_step_cap = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->tab_step, sizeof(StepRow) * (size_t)L));
+        owned_free(h->allocs, h->tab_step);
+        h->tab_step = nullptr; h->tab_step_cap = 0;
+        if (int rc = owned_alloc(h, h->allocs, (void **)&h->tab_step, sizeof(StepRow) * (size_t)L, AC_STATE)) return rc;
         h->tab_step_cap = L;
     }
     if (a.graph_seeds) p.ctl.graph_seeds = w->gseeds;
@@ -2593,13 +2638,13 @@ int stage_known(dsg_handle h, Workspace *w, const KnownArgs &known, hipStream_t 
     const size_t sa = (size_t)w->B * h->Ca * h->N * h->N, sn = (size_t)w->B * h->N * h->Cn;
     if (!w->kn_adj) {
         void *q;
-        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sa)) return rc;
+        if (int rc = owned_alloc(h, w->allocs, &q, sizeof(float) * sa, AC_SCRATCH)) return rc;
         w->kn_adj = (float *)q;
-        if (int rc = dev_alloc(h, w->allocs, &q, sizeof(float) * sn)) return rc;
+        if (int rc = owned_alloc(h, w->allocs, &q, sizeof(float) * sn, AC_SCRATCH)) return rc;
         w->kn_node = (float *)q;
-        if (int rc = dev_alloc(h, w->allocs, &q, sa)) return rc;
+        if (int rc = owned_alloc(h, w->allocs, &q, sa, AC_STATE)) return rc;
         w->km_adj = (uint8_t *)q;
-        if (int rc = dev_alloc(h, w->allocs, &q, sn)) return rc;
+        if (int rc = owned_alloc(h, w->allocs, &q, sn, AC_STATE)) return rc;
         w->km_node = (uint8_t *)q;
         w->known_bytes = (sizeof(float) + 1) * (sa + sn);
         w->bytes += w->known_bytes;
@@ -2730,7 +2775,7 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
     for (int k = 0; k < PK_COUNT; k++) { ms_by_kind[k] = 0.0; launches_by_kind[k] = 0; flops_by_kind[k] = 0.0; }
     if (!h->prof_gemm) {
         h->prof_gemm_cap = 512;
-        HIP_TRY(h, hipMalloc((void **)&h->prof_gemm, sizeof(unsigned long long) * 4 * h->prof_gemm_cap));
+        if (int rc = owned_alloc(h, h->allocs, (void **)&h->prof_gemm, sizeof(unsigned long long) * 4 * h->prof_gemm_cap, AC_STATE)) return rc;
     }
     std::vector<unsigned long long> stamps(4 * h->prof_gemm_cap);   // per launch: {min start, max end, block-0 shader cycles, block-0 ticks}
     std::vector<double> clocks;
@@ -2892,7 +2937,7 @@ int dsg_noise_embed(dsg_handle h, int32_t rows, const float *c_noise, float *out
     hipStream_t s = (hipStream_t)stream;
     float *tmp = nullptr;   // pe | emb0 | emb | aff
     const size_t n_pe = (size_t)rows * h->E, n_e = (size_t)rows * NOISE_EMB, n_a = (size_t)rows * h->aff_n;
-    HIP_TRY(h, hipMalloc((void **)&tmp, sizeof(float) * (n_pe + 2 * n_e + n_a)));
+    if (int rc = owned_alloc(h, h->allocs, (void **)&tmp, sizeof(float) * (n_pe + 2 * n_e + n_a), AC_SCRATCH)) return rc;   // this call's own
     float *pe = tmp, *emb0 = pe + n_pe, *emb = emb0 + n_e, *aff = emb + n_e;
     embed_rows(h, c_noise, rows, pe, emb0, emb, aff, s);
     hipError_t e = hipSuccess;
@@ -2900,7 +2945,7 @@ int dsg_noise_embed(dsg_handle h, int32_t rows, const float *c_noise, float *out
     if (out_emb && e == hipSuccess) e = hipMemcpyAsync(out_emb, emb, sizeof(float) * n_e, hipMemcpyDeviceToDevice, s);
     if (out_aff && e == hipSuccess) e = hipMemcpyAsync(out_aff, aff, sizeof(float) * n_a, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(tmp);
+    owned_free(h->allocs, tmp);
     HIP_TRY(h, e);
     return DSG_OK;
 }
@@ -3549,11 +3594,11 @@ struct TArena {   // bump allocator over one device buffer; without a base it on
 }  // namespace
 
 // a handle-owned device buffer of at least `need` floats (grown after draining the stream that may still read the old one)
-static float *train_buf(DevBuf &b, size_t need, hipStream_t s) {
+static float *train_buf(dsg_handle h, DevBuf &b, size_t need, hipStream_t s) {
     if (need > b.cap) {
-        if (b.p) { (void)hipStreamSynchronize(s); (void)hipFree(b.p); }
+        if (b.p) { (void)hipStreamSynchronize(s); owned_free(h->allocs, b.p); }
         b = DevBuf{};
-        if (hipMalloc((void **)&b.p, sizeof(float) * need) != hipSuccess) { b.p = nullptr; return nullptr; }
+        if (owned_alloc(h, h->allocs, (void **)&b.p, sizeof(float) * need, AC_SCRATCH) != 0) { b.p = nullptr; return nullptr; }
         b.cap = need;
     }
     return b.p;
@@ -3561,10 +3606,10 @@ static float *train_buf(DevBuf &b, size_t need, hipStream_t s) {
 
 // `carve` hands out a buffer's regions; it runs twice, over no memory to get the size and then over the grown buffer, so that the size
 // and the layout cannot disagree.  false: out of memory
-template <class Carve> static bool train_carve(DevBuf &b, hipStream_t s, Carve carve) {
+template <class Carve> static bool train_carve(dsg_handle h, DevBuf &b, hipStream_t s, Carve carve) {
     TArena A;
     carve(A);
-    if (!train_buf(b, A.off, s)) return false;
+    if (!train_buf(h, b, A.off, s)) return false;
     A = TArena{b.p, 0};
     carve(A);
     return true;
@@ -3619,7 +3664,7 @@ extern "C" int dsg_block_train(dsg_handle h, const char *block, int32_t B, const
     if (grad_out && no_grad) return fail(h, DSG_ERR_INVALID, "no gradient buffer for '%s'", no_grad);
     a.x_in = x_in; a.emb = emb; a.grad_out = grad_out; a.x_out = x_out; a.grad_in = grad_in; a.grad_emb = grad_emb;
     DevBuf scratch;   // this call's own: the saved tensors and the backward's scratch, freed below
-    const bool fits = train_carve(scratch, (hipStream_t)stream, [&](TArena &A) {
+    const bool fits = train_carve(h, scratch, (hipStream_t)stream, [&](TArena &A) {
         const size_t M = (size_t)B * a.res * a.res, C = a.C, H = a.hidden;
         carve_block_saved(A, a);
         a.d_x1 = A.get(M * C); a.t_mc = A.get(M * C); a.t_mc2 = A.get(M * C); a.t_m3c = A.get(M * 3 * C); a.t_mh = A.get(M * H);
@@ -3627,7 +3672,7 @@ extern "C" int dsg_block_train(dsg_handle h, const char *block, int32_t B, const
     if (!fits) return fail(h, DSG_ERR_HIP, "out of memory");
     const bool ok = train_block(a, (hipStream_t)stream);
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(scratch.p);
+    owned_free(h->allocs, scratch.p);
     HIP_TRY(h, e);
     if (t_scratch_failed((hipStream_t)stream, true)) return fail(h, DSG_ERR_HIP, "out of memory (training scratch of this stream)");
     if (!ok) return fail(h, DSG_ERR_HIP, "train_block failed (window larger than 128 tokens or a launch error)");
@@ -3722,7 +3767,7 @@ static int train_net_build(dsg_handle h, TrainNet &net, int32_t B, const float *
     net.self_condition = h->cfg.self_condition; net.M0 = (size_t)B * h->N * h->N;
     if (!h->train_const) {
         const int zo[2] = {0, 1};
-        HIP_TRY(h, hipMalloc((void **)&h->train_const, sizeof(zo)));
+        if (int rc = owned_alloc(h, h->allocs, (void **)&h->train_const, sizeof(zo), AC_STATE)) return rc;
         HIP_TRY(h, hipMemcpy(h->train_const, zo, sizeof(zo), hipMemcpyHostToDevice));
     }
     net.has_sc = h->train_const + ((h->cfg.self_condition && sc_adj) ? 1 : 0);
@@ -3763,8 +3808,8 @@ static int train_net_build(dsg_handle h, TrainNet &net, int32_t B, const float *
     // the saved-activation arena and the backward scratch belong to the handle and are kept between calls.  Scratch: three of the
     // widest tensors, level 0's [M0, 4E] (every level has M C constant up to the 2x of merging), and four of [M0, 2E]
     const size_t wide = net.M0 * (size_t)(4 * net.E), two = net.M0 * (size_t)net.E * 2;
-    if (!train_carve(h->train_arena, s, [&](TArena &A) { train_net_carve(net, A); A.get(16); }) ||
-        !train_carve(h->train_scr, s, [&](TArena &A) {
+    if (!train_carve(h, h->train_arena, s, [&](TArena &A) { train_net_carve(net, A); A.get(16); }) ||
+        !train_carve(h, h->train_scr, s, [&](TArena &A) {
             net.t_mh = A.get(wide); net.t_m3c = A.get(wide); net.t_w = A.get(wide); net.t_mc = A.get(two); net.t_mc2 = A.get(two);
             net.d_x = A.get(two); net.d_y = A.get(two + 4096);
         }))
@@ -4016,7 +4061,7 @@ struct TrainIo { float *in_a, *in_n, *cn, *F_a, *F_n, *dD_a, *dD_n, *dF_a, *dF_n
 }
 static bool train_io(dsg_handle h, int B, hipStream_t s, TrainIo &io) {
     const size_t na = (size_t)B * h->Ca * h->N * h->N, nn = (size_t)B * h->N * h->Cn;
-    return train_carve(h->train_io, s, [&](TArena &A) {
+    return train_carve(h, h->train_io, s, [&](TArena &A) {
         io.in_a = A.get(na); io.in_n = A.get(nn); io.cn = A.get(B); io.F_a = A.get(na); io.F_n = A.get(nn);
         io.dD_a = A.get(na); io.dD_n = A.get(nn); io.dF_a = A.get(na); io.dF_n = A.get(nn);
     });
@@ -4096,7 +4141,7 @@ int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node
     TrainInputGrad ig{nullptr, nullptr, Np};
     float *coef = nullptr;   // c_skip [B] | c_in [B], left by t_precond_bwd for t_assemble_bwd
     if (!train_io(h, B, s, io) ||
-        !train_carve(h->train_vjp, s, [&](TArena &A) { ig.d_tok = A.get(M0 * Np); ig.img = A.get((size_t)E * Np); coef = A.get(2 * (size_t)B); }))
+        !train_carve(h, h->train_vjp, s, [&](TArena &A) { ig.d_tok = A.get(M0 * Np); ig.img = A.get((size_t)E * Np); coef = A.get(2 * (size_t)B); }))
         return fail(h, DSG_ERR_HIP, "out of memory");
     launch_precond_in(CStatePtrs{adj, node}, sigmas, StatePtrs{io.in_a, io.in_n}, io.cn, d, s);
     TrainNet net{};
@@ -4219,8 +4264,8 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
     StatePtrs x{}, xp{}, D1{}, D2{}, eps{}, g{};
     auto state = [&](TArena &A, bool on) { StatePtrs p{nullptr, nullptr}; if (on) { p.adj = A.get(na); p.node = A.get(nn); } return p; };
     if (!train_io(h, B, s, io) ||
-        !train_carve(h->train_vjp, s, [&](TArena &A) { ig.d_tok = A.get(M0 * Np); ig.img = A.get((size_t)E * Np); coef = A.get(2 * (size_t)B); }) ||
-        !train_carve(h->train_ode, s, [&](TArena &A) {
+        !train_carve(h, h->train_vjp, s, [&](TArena &A) { ig.d_tok = A.get(M0 * Np); ig.img = A.get((size_t)E * Np); coef = A.get(2 * (size_t)B); }) ||
+        !train_carve(h, h->train_ode, s, [&](TArena &A) {
             x = state(A, true); D1 = state(A, true); xp = state(A, heun); D2 = state(A, heun); eps = state(A, probing); g = state(A, probing);
             zero = A.get(B); sig_d = A.get((size_t)n_evals * B); tab_f = A.get((size_t)n_steps * (sizeof(StepRow) / sizeof(float)));
             ctl_f = A.get((sizeof(RunCtl) + sizeof(float) - 1) / sizeof(float)); seeds_f = A.get(2 * (size_t)B);

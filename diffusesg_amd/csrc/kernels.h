@@ -295,6 +295,10 @@ struct StatePtrs { float *adj; float *node; };
 struct CStatePtrs { const float *adj; const float *node; };
 struct Dims { int B, N, Ca, Cn; };
 
+// test-only: n_words 32-bit words at p become pattern 1 zeros, 2 quiet NaN (0x7fc00000: both bf16 halves NaN too), 3 1.0e30f, 4 finite
+// pseudo-random values of unit scale with random sign, a function of (seed, word index)  (dsg_debug_poison, "debug_alloc_fill")
+void launch_debug_fill(void *p, size_t n_words, int pattern, unsigned long long seed, hipStream_t s);
+
 // c_noise[i] = ln(sigma[i])/4
 void launch_cnoise(const float *sigmas, float *c_noise, int n, hipStream_t s);
 // in = c_in(sigma[b]) * x ; c_noise[b] = ln(sigma[b])/4

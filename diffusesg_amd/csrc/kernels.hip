@@ -2399,6 +2399,32 @@ __global__ void cnoise_kernel(const float *sigmas, float *c_noise, int n) {
 void launch_cnoise(const float *sigmas, float *c_noise, int n, hipStream_t s) {
     DSG_LAUNCH(cnoise_kernel, dim3((n + 255) / 256), dim3(256), 0, s, sigmas, c_noise, n);
 }
+
+// test-only fill of a workspace buffer (dsg_debug_poison, option "debug_alloc_fill"): n 32-bit words.  random: word i is a function of
+// (seed, i) -- two finite bf16 halves with magnitude in [0.5, 2) and random signs, i.e. read as fp32 a value of that range as well
+__global__ void debug_fill_kernel(uint32_t *p, size_t n, uint32_t word, int random, unsigned long long seed) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t v = word;
+        if (random) {
+            unsigned long long z = seed + 0x9e3779b97f4a7c15ull * (unsigned long long)(i + 1);   // splitmix64
+            z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+            z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+            z ^= z >> 31;
+            const uint32_t r = (uint32_t)z, q = (uint32_t)(z >> 32);
+            v = ((0x3f00u | (r & 0x80ffu)) << 16) | 0x3f00u | (q & 0x80ffu);
+        }
+        p[i] = v;
+    }
+}
+void launch_debug_fill(void *p, size_t n_words, int pattern, unsigned long long seed, hipStream_t s) {
+    if (n_words == 0) return;
+    const uint32_t word = pattern == 2 ? 0x7fc00000u : (pattern == 3 ? 0x7149f2cau /* 1.0e30f */ : 0u);
+    const size_t blocks = (n_words + 255) / 256;
+    // not DSG_LAUNCH: a fill is never part of a forward's launch plan, a dry run must not drop it
+    hipLaunchKernelGGL(debug_fill_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, (uint32_t *)p, n_words, word,
+                       pattern == 4 ? 1 : 0, seed);
+}
 void launch_precond_in(CStatePtrs x, const float *sigmas, StatePtrs in, float *c_noise, Dims d, hipStream_t s) {
     const size_t n = total_elems(d);
     DSG_LAUNCH(precond_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, sigmas, in, c_noise, d);

@@ -25,6 +25,7 @@ EXPORTS = [
     "dsg_debug_patch_embed_f32", "dsg_debug_assemble_f32", "dsg_debug_readout_f32", "dsg_debug_head_f32", "dsg_debug_row_f32",
     "dsg_debug_window_broadcast_f32", "dsg_debug_window_harvest_f32",
     "dsg_ode_run", "dsg_ode_evals", "dsg_debug_graph_dot",
+    "dsg_debug_poison",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -208,6 +209,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_ode_evals.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgOdeCfg), vp, vp, i32]
     L.dsg_ode_evals.restype = i32
     L.dsg_debug_graph_dot.argtypes = [i32] * 4 + [vp] * 7
+    L.dsg_debug_poison.argtypes = [vp, i32, i32, C.c_uint64, vp]
     L.dsg_train_bind_params.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
     L.dsg_adam_step.argtypes = [i32] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int64), i32] + [C.c_float] * 6 + [C.POINTER(C.c_float), vp]
     L.dsg_ema_update.argtypes = [i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, vp]
@@ -318,6 +320,11 @@ class Handle:
         v = C.c_int32(0)
         self.check(self.L.dsg_get_option(self._h, name.encode(), C.byref(v)), f"dsg_get_option({name})")
         return int(v.value)
+
+    def poison(self, B: int, pattern: int, seed: int = 0, stream=None):
+        """Test only (dsg_debug_poison): every scratch buffer of the handle and of batch B's workspace becomes `pattern` -- 1 zeros,
+        2 NaN, 3 1e30, 4 pseudo-random finite values, a function of (seed, element) -- on `stream` (None: the null stream)."""
+        self.check(self.L.dsg_debug_poison(self._h, int(B), int(pattern), C.c_uint64(int(seed)), stream), "dsg_debug_poison")
 
     def need_lists(self, B: int, stream=None):
         """Need lists of the masked-token pruning as the flags last staged for batch B left them (dsg_debug_need_lists): a list of

@@ -342,7 +342,10 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *       windows: one wave per (window, head)), 2 the block-per-head kernel everywhere, 3 the former only where a block of four units lies in
  *       one window, 0 GEMM + attention kernel; "bf16_mlp" 1 fused fc1-GELU-fc2 (C = 384: eight waves, weight images streamed by LDS-DMA),
  *       4 round 3's eight-wave kernel, 5 the one-wave-per-SIMD LDS-DMA kernel, 6 = 1 with level 0 on the LDS-resident kernel, 2 four waves at every width, 3 GEMM pair at C = 384,
- *       0 GEMM pairs; "bf16_proj_mlp" 1 proj + residual + LayerNorm-2 in front of the MLP kernel; "bf16_readout" 1 the read-out on the bf16 pipe. */
+ *       0 GEMM pairs; "bf16_proj_mlp" 1 proj + residual + LayerNorm-2 in front of the MLP kernel; "bf16_readout" 1 the read-out on the bf16 pipe.
+ * Test only: "debug_alloc_fill" (default 0): while p = 1..4, every scratch buffer the handle or a workspace allocates from then on is
+ *   filled with pattern p (dsg_debug_poison) right after its allocation, ahead of the library's own creation memsets -- a stand-in for
+ *   whatever the allocator returns.  Index / state buffers and weights are never filled.  No launch of any entry point changes. */
 int dsg_set_option(dsg_handle h, const char *name, int32_t value);
 /* The value an option currently has on this handle (what the next forward will run with), whichever way it was set
  * (dsg_set_option or a DSG_* environment default): measurement code reports the precision mode from here. */
@@ -802,6 +805,16 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
                 const float *probe_adj, const float *probe_node, float *out_adj, float *out_node,
                 float *out_probe_adj, float *out_probe_node, double *out_net_trace /* device [n_evals, B] */, void *stream);
 int32_t dsg_ode_evals(const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode, float *t_eval, double *weight, int32_t cap);
+
+/* Test only: fills every scratch buffer that exists on the handle (step tables, training arenas) and in batch size B's workspace (created
+ * first if there is none) with `pattern`, on `stream`: 1 zeros, 2 quiet NaN (0x7fc00000; both bf16 halves are NaN too), 3 1.0e30f,
+ * 4 finite pseudo-random values of unit scale with random sign, a function of (seed, element index).  A stand-in for stale contents
+ * between two calls: every output of every entry point must be bit-identical whatever the pattern (tests/test_workspace_poison.py;
+ * the buffer classes are DESIGN.md's "what a forward may assume about its workspace").  The five buffers whose contract is "finite"
+ * (x, y, att, hid, stats) take patterns 1, 3 and 4 but not NaN; buffers read as an index, a count, a byte mask, a seed or an address,
+ * and the weights, are never written.  Not to be called during stream capture. */
+int dsg_debug_poison(dsg_handle h, int32_t B, int32_t pattern, uint64_t seed, void *stream);
+
 /* the per-graph contraction of dsg_ode_run on its own (test hook, no handle; device pointers, synchronises `stream`): out[b] = the sum
  * over the live entries of graph b of a_j b_j, float64, one fixed order, independent of B and of the graph's position; padded entries
  * are skipped by the flags (NaN there does not reach the sum).  a_adj / b_adj [B,C_adj,N,N], a_node / b_node [B,N,C_node], out [B]. */
