@@ -54,17 +54,23 @@ def completion_masks(cfg, node_flags, known_nodes, *, labels=True, boxes=True, e
 
 def complete_scene_graphs(net, sampler, q_adj, q_node, bbox, node_flags, known_nodes, n_adj_type, n_node_type, *,
                           encoding="bits", labels=True, boxes=True, edges="among_known", seed=None, resample=None, resample_range=None,
-                          graph_seeds=None, coin_seed=None):
+                          graph_seeds=None, coin_seed=None, guide=None, guide_scale=1.0):
     """Scene-graph completion: the labels / boxes of the nodes `known_nodes` marks and the relations `edges` selects are held at the
     values in q_adj [B,N,N], q_node [B,N] (integer types) and bbox [B,N,4] (in [0,1]); everything else is generated.  Values at
     unknown entries are ignored.  Returns the decoded batch (q_adj int32 [B,N,N], q_node int32 [B,N], bbox float32 [B,N,4]) on the
     device.  `net`: the NodeAdjPrecondHip network with bbox channels, `sampler`: a NodeAdjEDMSamplerHip; `encoding` is the
     network's edge and node encoding; `resample` / `resample_range`: the resampling walk (default: none); `graph_seeds` / `coin_seed`:
-    per-graph noise streams, as `NodeAdjEDMSamplerHip.sample` takes them."""
+    per-graph noise streams, as `NodeAdjEDMSamplerHip.sample` takes them; `guide` (a `guide.BoxGuide`) / `guide_scale`:
+    in-loop box guidance of the generated boxes (`sample_guided`; known boxes stay exactly as given)."""
     cfg = getattr(net, "module", net).model.config
     known_adj, known_node = _io.encode(net, q_adj, q_node, bbox, node_flags, n_adj_type, n_node_type, encoding, encoding)
     mask_adj, mask_node = completion_masks(cfg, node_flags.to(known_adj.device), known_nodes.to(known_adj.device),
                                            labels=labels, boxes=boxes, edges=edges)
+    if guide is not None:
+        adj, node = sampler.sample_guided(net, node_flags, guide, guide_scale,
+                                          known=(known_adj, known_node, mask_adj, mask_node), seed=seed, return_device=True,
+                                          flag_adj_multi_channel=True, **_walk_kw(resample, resample_range), **_seed_kw(graph_seeds, coin_seed))
+        return _io.decode(net, adj, node, node_flags, n_adj_type, n_node_type, encoding, encoding, bbox=True)
     adj, node = sampler.sample_known(net, node_flags, known_adj, known_node, mask_adj, mask_node, seed=seed, return_device=True,
                                      flag_node_multi_channel=True, flag_adj_multi_channel=True,
                                      num_node_chan=cfg.c_node, num_edge_chan=cfg.c_adj, **_walk_kw(resample, resample_range),
@@ -93,14 +99,16 @@ def _seed_kw(graph_seeds, coin_seed):
 
 
 def layout_from_graph(net, sampler, q_adj, q_node, node_flags, n_adj_type, n_node_type, *, encoding="bits", seed=None, resample=None,
-                      resample_range=None, graph_seeds=None, coin_seed=None):
+                      resample_range=None, graph_seeds=None, coin_seed=None, guide=None, guide_scale=1.0):
     """Layout generation from a graph: every label and every relation is known, the bounding boxes are generated.  Returns the
-    decoded batch like `complete_scene_graphs`; its q_adj / q_node equal the inputs at valid nodes (off the diagonal)."""
+    decoded batch like `complete_scene_graphs`; its q_adj / q_node equal the inputs at valid nodes (off the diagonal).  `guide` /
+    `guide_scale`: in-loop box guidance of the layout, as in `complete_scene_graphs`."""
     B, n = node_flags.shape[0], q_node.shape[-1]
     free_boxes = torch.full((B, n, 4), 0.5, dtype=torch.float32)   # placeholder: the box channels are unknown
     return complete_scene_graphs(net, sampler, q_adj, q_node, free_boxes, node_flags, node_flags.bool(), n_adj_type, n_node_type,
                                  encoding=encoding, labels=True, boxes=False, edges="all", seed=seed, resample=resample,
-                                 resample_range=resample_range, graph_seeds=graph_seeds, coin_seed=coin_seed)
+                                 resample_range=resample_range, graph_seeds=graph_seeds, coin_seed=coin_seed, guide=guide,
+                                 guide_scale=guide_scale)
 
 
 def start_step_for_sigma(sampler, sigma):

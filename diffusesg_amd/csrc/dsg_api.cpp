@@ -101,6 +101,18 @@ struct Workspace {
     // allocated by the first seeded call at this batch size.  RunCtl points at it for the length of a seeded run
     unsigned long long *gseeds = nullptr;
     size_t seeds_bytes = 0;
+    // box guidance (dsg_sample_guided): what guided step bodies bake -- the parameter block, one shift buffer [B,N,4] per stage plus the
+    // previous step's (the multistep solver), the reference norms [B] -- allocated by the first guided call at this batch size; and the
+    // run's tables behind the block's pointers (sel, region, the coefficient table [T], the loss trace [L,B]), which grow without
+    // touching a captured body
+    GuideParams *g_par = nullptr;
+    float *g_shift[3] = {nullptr, nullptr, nullptr};
+    double *g_ref = nullptr;
+    uint8_t *g_sel = nullptr;
+    float *g_region = nullptr, *g_coef = nullptr, *g_trace = nullptr;
+    int g_coef_cap = 0;
+    size_t g_trace_cap = 0;
+    size_t guide_bytes = 0;
     // batch-uniform noise level (the sampler): every sample shares one (scale,shift) row, taken from a table that
     // dsg_sample computes once for all steps; aff_ld == 0 broadcasts row 0 of `aff`
     bool uniform = false;
@@ -1994,9 +2006,13 @@ struct StepPlan {
     bool known = false;   // conditional sampling: every D goes through the known-entry select (w->kn_* / w->km_*)
     int prev = -1;        // second-order multistep step (DSG_SOLVER_DPMPP_2M, row coefficient != 0): d_* buffer holding the previous
                           // step's D, never s1 nor a buffer the step writes; -1 = none, the plain Euler / Heun step
-    int key() const {   // prev sits above every older bit: plans without it keep their keys
+    bool guided = false;  // box guidance (dsg_sample_guided): the guide kernel behind every D, the updates read D~ = D - shift
+    bool clip = false;    //   with the norm pass and the clip factor in front of it
+    int g1 = 0, g2 = 0;   //   w->g_shift buffers of the stage-1 / stage-2 shift
+    int gprev = -1;       //   ... and of the previous step's stage-1 shift where prev >= 0
+    int key() const {   // prev, then the guidance bits, sit above every older bit: plans without them keep their keys
         return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8) | ((int)known << 9) |
-               ((prev + 1) << 10);
+               ((prev + 1) << 10) | ((int)guided << 12) | ((int)clip << 13) | (g1 << 14) | (g2 << 16) | ((gprev + 1) << 18);
     }
 };
 
@@ -2034,6 +2050,15 @@ int precond_tab(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, c
     return 0;
 }
 
+// box guidance behind one preconditioned call: the norm pass (with the clip only), then the guide kernel on D -> w->g_shift[slot]
+int guide_call(dsg_handle h, Workspace *w, const StepPlan &p, CStatePtrs xh, CStatePtrs D, int slot, bool stage1, const Dims &d, hipStream_t s) {
+    if (p.clip && !launch_graph_diff_norm(xh, D, w->flags, w->g_ref, d, s)) return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
+    if (!launch_box_guide(w->g_par, h->tab_step, w->ctl, 0.f, D.node, w->flags, p.clip ? w->g_ref : nullptr, stage1,
+                          BoxGuideOut{w->g_shift[slot], nullptr, nullptr, nullptr, nullptr}, d, s))
+        return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
+    return 0;
+}
+
 int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_adj, const float *gt_node, hipStream_t s, int *nfe,
                  bool fwd_graph = false) {
     const Dims d = dims_of(h, w->B);
@@ -2046,11 +2071,15 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
                                  p.coin1, StatePtrs{w->d_adj[p.s1], w->d_node[p.s1]}, s, nfe, fwd_graph, p.known)) return rc;
         D1 = CStatePtrs{w->d_adj[p.s1], w->d_node[p.s1]};
     }
+    if (p.guided) if (int rc = guide_call(h, w, p, xh, D1, p.g1, /*stage1=*/true, d, s)) return rc;
+    const StatePtrs x{w->x_adj, w->x_node};
     if (p.euler && p.prev >= 0) {   // sanity-check mode: D_prev = D = gt
         const CStatePtrs Dp = gt_adj ? D1 : CStatePtrs{w->d_adj[p.prev], w->d_node[p.prev]};
-        launch_multistep_tab(xh, D1, Dp, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
+        if (p.guided) launch_multistep_tab_guided(xh, D1, Dp, w->g_shift[p.g1], w->g_shift[p.gprev], h->tab_step, w->ctl, w->flags, x, d, s);
+        else launch_multistep_tab(xh, D1, Dp, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     } else if (p.euler) {
-        launch_euler_tab(xh, D1, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
+        if (p.guided) launch_euler_tab_guided(xh, D1, w->g_shift[p.g1], h->tab_step, w->ctl, w->flags, x, d, s);
+        else launch_euler_tab(xh, D1, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     } else {
         CStatePtrs D2 = D1;
         if (!gt_adj) {   // stage 2 re-evaluates at (x_hat, sigma(t_hat)) with self-cond = D1 (edm.py:400-405)
@@ -2059,7 +2088,10 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
                                      StatePtrs{w->d_adj[p.s2], w->d_node[p.s2]}, s, nfe, fwd_graph, p.known)) return rc;
             D2 = CStatePtrs{w->d_adj[p.s2], w->d_node[p.s2]};
         }
-        launch_heun_tab(xh, D1, D2, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
+        if (p.guided) {   // stage 2 is evaluated at (x_hat, t_hat) and guided the same way
+            if (int rc = guide_call(h, w, p, xh, D2, p.g2, /*stage1=*/false, d, s)) return rc;
+            launch_heun_tab_guided(xh, D1, D2, w->g_shift[p.g1], w->g_shift[p.g2], h->tab_step, w->ctl, w->flags, x, d, s);
+        } else launch_heun_tab(xh, D1, D2, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     }
     launch_step_advance(w->ctl, s);
     return 0;
@@ -2116,7 +2148,8 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
     const size_t known = it != h->ws.end() ? it->second->known_bytes : 0;
     const size_t seeds = it != h->ws.end() ? it->second->seeds_bytes : 0;   // + the graph seeds, once a seeded call has allocated them
     const size_t pure = it != h->ws.end() ? it->second->tab_pure_bytes : 0;   // + the table of pure-window rows, once a sampler call has built one
-    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need + known + seeds + pure;
+    const size_t guide = it != h->ws.end() ? it->second->guide_bytes : 0;     // + the buffers and tables of box guidance, once a guided call has allocated them
+    return sizeof(float) * per_sample_floats(h) * (size_t)B + (size_t)B * h->N + 16 + need + known + seeds + pure + guide;
 }
 
 int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
@@ -2465,6 +2498,7 @@ struct SampleArgs {
     const dsg_sampler_cfg *cfg; const dsg_walk_cfg *walk; int32_t B; const uint8_t *flags;
     CStatePtrs init, base, noise; const uint8_t *coins; uint64_t seed; const uint64_t *graph_seeds;
     CStatePtrs gt; KnownArgs known;
+    const dsg_guide_cfg *guide = nullptr; float *loss_trace = nullptr;   // box guidance (dsg_sample_guided); null: the unguided loop
     struct Snapshots { const int32_t *steps; int32_t n; float *adj, *node; } snapshots;
     StatePtrs outputs; dsg_sample_stats *stats; hipStream_t stream;
 };
@@ -2487,7 +2521,26 @@ struct SamplePlan {
     std::vector<StepPlan> plans;   // [L] the static launch sequence of every step
     int precond_calls = 0;
     bool use_graph = false;
+    std::vector<float> guide_coef; // [T] c_i of a guided run
+    GuideParams gpar{};            // ... and its parameter block (device pointers: set once the tables are staged)
 };
+
+// the checks of a guide descriptor that need no device; `why` names the argument.  Cn < 0: not known here
+bool guide_cfg_ok(const dsg_guide_cfg *g, int N, int Cn, bool need_weights, std::string &why) {
+    char buf[256];
+    auto no = [&](const char *fmt, double v) { snprintf(buf, sizeof(buf), fmt, v); why = buf; return false; };
+    if (!g) return no("guide is NULL", 0);
+    if (Cn >= 0 && Cn < 4) return no("box guidance needs C_node >= 4 (the last four node channels are the box); C_node is %g", Cn);
+    if (N > GUIDE_MAX_N) return no("box guidance keeps a graph's boxes on chip: N = %g is beyond 64", N);
+    if (!std::isfinite(g->w_overlap)) return no("guide->w_overlap = %g is not finite", g->w_overlap);
+    if (!std::isfinite(g->w_region)) return no("guide->w_region = %g is not finite", g->w_region);
+    if (!std::isfinite(g->w_align)) return no("guide->w_align = %g is not finite", g->w_align);
+    if (g->w_align != 0.f && !(g->tau > 0.f && std::isfinite(g->tau))) return no("guide->tau = %g must be positive (w_align is not 0)", g->tau);
+    if (g->w_region != 0.f && (!g->sel || !g->region)) return no("guide->sel / guide->region are required with w_region = %g", g->w_region);
+    if (!(g->clip_ratio >= 0.f)) return no("guide->clip_ratio = %g must be >= 0, or DSG_GUIDE_CLIP_NONE", g->clip_ratio);
+    if (need_weights && !g->weights) return no("guide->weights is NULL (host, one weight per schedule index)", 0);
+    return true;
+}
 
 // Host plan: argument checks, walk, schedule, coins, rows and step plans.  No HIP call.
 int plan_sample(dsg_handle h, const SampleArgs &a, SamplePlan &p) {
@@ -2565,6 +2618,26 @@ int plan_sample(dsg_handle h, const SampleArgs &a, SamplePlan &p) {
         if (!gt) last_s1 = q.s1;
     }
     p.precond_calls = call;
+    if (a.guide) {   // box guidance: refusals, the coefficient table, the shift buffers of every step
+        std::string why;
+        if (!guide_cfg_ok(a.guide, h->N, h->Cn, /*need_weights=*/true, why)) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided: %s", why.c_str());
+        if (gt && (a.known.adj || a.graph_seeds)) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided: gt_adj / gt_node (sanity-check mode) go with neither known_* nor graph_seeds");
+        p.guide_coef.resize(T);
+        if (dsg_guide_coef(cfg, a.guide->weights, p.guide_coef.data(), T) != T)
+            return fail(h, DSG_ERR_INVALID, "dsg_sample_guided: guide->weights holds a weight that is not finite");
+        const bool clip = !std::isinf(a.guide->clip_ratio);
+        int last_g = -1;   // the shift buffer of the previous step's stage 1
+        for (int i = 0; i < L; i++) {
+            StepPlan &q = p.plans[i];
+            q.guided = true; q.clip = clip;
+            q.g1 = free_slot(last_g, -1);
+            q.g2 = free_slot(q.g1, last_g);
+            q.gprev = q.prev >= 0 ? last_g : -1;
+            last_g = q.g1;
+        }
+        p.gpar = GuideParams{a.guide->w_overlap, a.guide->w_region, a.guide->w_align, a.guide->tau, clip ? a.guide->clip_ratio : 0.f, 0,
+                             nullptr, nullptr, nullptr, nullptr, nullptr};
+    }
     return 0;
 }
 
@@ -2656,6 +2729,50 @@ int stage_known(dsg_handle h, Workspace *w, const KnownArgs &known, hipStream_t 
     return 0;
 }
 
+// Guide staging: sel, region, the coefficient table and the parameter block move into workspace-owned memory, on the caller's stream
+// ahead of the run's synchronise; guided step bodies bake the block's address and the shift / norm buffers, never caller memory
+int stage_guide(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, hipStream_t s) {
+    if (!a.guide) return 0;
+    const size_t bn = (size_t)w->B * h->N;
+    void *q;
+    auto grow = [&](void **dst, size_t bytes, size_t old_bytes, AllocClass cls) {
+        owned_free(w->allocs, *dst); *dst = nullptr;
+        if (int rc = owned_alloc(h, w->allocs, dst, bytes, cls)) return rc;
+        w->guide_bytes += bytes - old_bytes; w->bytes += bytes - old_bytes;
+        return 0;
+    };
+    if (!w->g_par) {
+        if (int rc = grow(&(q = nullptr), sizeof(GuideParams), 0, AC_STATE)) return rc;
+        w->g_par = (GuideParams *)q;
+        for (int k = 0; k < 3; k++) { if (int rc = grow(&(q = nullptr), sizeof(float) * bn * 4, 0, AC_SCRATCH)) return rc; w->g_shift[k] = (float *)q; }
+        if (int rc = grow(&(q = nullptr), sizeof(double) * (size_t)w->B, 0, AC_SCRATCH)) return rc;
+        w->g_ref = (double *)q;
+        if (int rc = grow(&(q = nullptr), bn, 0, AC_STATE)) return rc;
+        w->g_sel = (uint8_t *)q;
+        if (int rc = grow(&(q = nullptr), sizeof(float) * bn * 4, 0, AC_SCRATCH)) return rc;
+        w->g_region = (float *)q;
+    }
+    if (w->g_coef_cap < p.T) {
+        if (int rc = grow(&(q = w->g_coef), sizeof(float) * (size_t)p.T, sizeof(float) * (size_t)w->g_coef_cap, AC_SCRATCH)) return rc;
+        w->g_coef = (float *)q; w->g_coef_cap = p.T;
+    }
+    const size_t trace_n = (size_t)p.L * w->B;
+    if (a.loss_trace && w->g_trace_cap < trace_n) {
+        if (int rc = grow(&(q = w->g_trace), sizeof(float) * trace_n, sizeof(float) * w->g_trace_cap, AC_SCRATCH)) return rc;
+        w->g_trace = (float *)q; w->g_trace_cap = trace_n;
+    }
+    if (a.guide->w_region != 0.f) {
+        HIP_TRY(h, hipMemcpyAsync(w->g_sel, a.guide->sel, bn, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(w->g_region, a.guide->region, sizeof(float) * bn * 4, hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(h, hipMemcpyAsync(w->g_coef, p.guide_coef.data(), sizeof(float) * (size_t)p.T, hipMemcpyHostToDevice, s));
+    p.gpar.sel = w->g_sel; p.gpar.region = w->g_region; p.gpar.coef = w->g_coef;
+    p.gpar.trace = a.loss_trace ? w->g_trace : nullptr;
+    p.gpar.mask_node = a.known.adj ? w->km_node : nullptr;   // stage_known ran: the workspace's copy
+    HIP_TRY(h, hipMemcpyAsync(w->g_par, &p.gpar, sizeof(GuideParams), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
 // Loop: every step body captured before the first launch, then replay (or enqueue), snapshots, outputs, stats
 int run_loop(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &p, hipStream_t s) {
     const size_t sa = (size_t)a.B * h->Ca * h->N * h->N, sn = (size_t)a.B * h->N * h->Cn;
@@ -2675,6 +2792,7 @@ int run_loop(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &
     }
     HIP_TRY(h, hipMemcpyAsync(a.outputs.adj, w->x_adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(a.outputs.node, w->x_node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
+    if (a.guide && a.loss_trace) HIP_TRY(h, hipMemcpyAsync(a.loss_trace, w->g_trace, sizeof(float) * (size_t)p.L * a.B, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipGetLastError());
     h->last_stats.precond_calls = p.precond_calls;
     h->last_stats.net_forwards = nfe;
@@ -2693,6 +2811,7 @@ int sample_impl(dsg_handle h, const SampleArgs &a) {
     if (int rc = step_tables(h, w, a, p, s)) return rc;
     if (int rc = pure_window_table(h, w, a, p, s)) return rc;
     if (int rc = stage_known(h, w, a.known, s)) return rc;
+    if (int rc = stage_guide(h, w, a, p, s)) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));  // the plan's host vectors (and the caller's seeds) must outlive their async copies; once per sample() call
     return run_loop(h, w, a, p, s);
 }
@@ -2762,6 +2881,77 @@ int dsg_sample_seeded(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_c
     a.known = {known_adj, known_node, mask_adj, mask_node};
     if (int rc = known_args(h, "dsg_sample_seeded", /*required=*/false, a.known)) return rc;
     return sample_impl(h, a);
+}
+
+int32_t dsg_guide_coef(const dsg_sampler_cfg *cfg, const float *weights, float *coef, int32_t cap) {
+    if (!cfg || !weights || !coef || cfg->num_steps < 1 || cap < cfg->num_steps) return DSG_ERR_INVALID;
+    const int T = cfg->num_steps;
+    std::vector<float> t_hat(T), nz(T), hs(T);
+    std::vector<double> sg(T);
+    if (dsg_sigma_schedule(cfg, sg.data(), t_hat.data(), nz.data(), hs.data()) != DSG_OK) return DSG_ERR_INVALID;
+    for (int i = 0; i < T; i++) {
+        if (!std::isfinite(weights[i])) return DSG_ERR_INVALID;
+        // evaluated in double on the float32 level and rounded once, like dsg_multistep_coef: within half an ulp of the real value (the
+        // same formula float32 operation by operation strays up to 3.5 ulp)
+        const double t = (double)t_hat[i];
+        coef[i] = (float)((double)weights[i] * t * t * (0.25 / (t * t + 0.25)));
+    }
+    return T;
+}
+
+int dsg_sample_guided(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
+                      const uint64_t *graph_seeds, uint64_t coin_seed,
+                      const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                      const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                      const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                      const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                      const dsg_guide_cfg *guide, const float *gt_adj, const float *gt_node, float *loss_trace,
+                      float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!guide) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided needs a guide descriptor (guide is NULL)");
+    SampleArgs a{};
+    a.cfg = cfg; a.B = B; a.flags = flags; a.init = {init_adj, init_node}; a.noise = {noise_adj, noise_node}; a.coins = coins; a.seed = coin_seed;
+    a.snapshots = {snap_steps, n_snap, snap_adj, snap_node}; a.outputs = {out_adj, out_node}; a.stats = stats; a.stream = (hipStream_t)stream;
+    a.walk = walk;
+    a.base = {base_adj, base_node};
+    a.graph_seeds = graph_seeds;
+    a.known = {known_adj, known_node, mask_adj, mask_node};
+    a.gt = {gt_adj, gt_node};
+    a.guide = guide; a.loss_trace = loss_trace;
+    if (int rc = known_args(h, "dsg_sample_guided", /*required=*/false, a.known)) return rc;
+    return sample_impl(h, a);
+}
+
+int dsg_debug_box_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,
+                        const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_node,
+                        const dsg_guide_cfg *guide, float coef, float *loss, float *grad, float *shift, float *factor, float *norms,
+                        float *d_guided_node, void *stream) {
+    std::string why;
+    if (B < 1 || N < 1 || c_adj < 1) { g_create_err = "dsg_debug_box_guide: B, N and c_adj must be >= 1"; return DSG_ERR_INVALID; }
+    if (!guide_cfg_ok(guide, N, c_node, /*need_weights=*/false, why)) { g_create_err = "dsg_debug_box_guide: " + why; return DSG_ERR_INVALID; }
+    if (!std::isfinite(coef)) { g_create_err = "dsg_debug_box_guide: coef is not finite"; return DSG_ERR_INVALID; }
+    const bool clip = !std::isinf(guide->clip_ratio);
+    if (!d_node || !flags || (clip && (!xhat_adj || !xhat_node || !d_adj))) { g_create_err = "dsg_debug_box_guide: null argument (d_node, flags; with a clip also xhat_adj, xhat_node, d_adj)"; return DSG_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d{B, N, c_adj, c_node};
+    const GuideParams par{guide->w_overlap, guide->w_region, guide->w_align, guide->tau, clip ? guide->clip_ratio : 0.f, 0,
+                          guide->sel, guide->region, nullptr, nullptr, mask_node};
+    GuideParams *d_par = nullptr; double *d_ref = nullptr; float *d_shift = nullptr;
+    hipError_t e = hipMalloc((void **)&d_par, sizeof(GuideParams));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_ref, sizeof(double) * (size_t)B);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_shift, sizeof(float) * (size_t)B * N * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_par, &par, sizeof(GuideParams), hipMemcpyHostToDevice, s);
+    bool ok = e == hipSuccess;
+    if (ok && clip) ok = launch_graph_diff_norm(CStatePtrs{xhat_adj, xhat_node}, CStatePtrs{d_adj, d_node}, flags, d_ref, d, s);
+    if (ok) ok = launch_box_guide(d_par, nullptr, nullptr, coef, d_node, flags, clip ? d_ref : nullptr, false, BoxGuideOut{d_shift, grad, loss, factor, norms}, d, s);
+    if (ok && d_guided_node) launch_box_apply(d_node, d_shift, flags, d_guided_node, d, s);
+    if (ok && shift) e = hipMemcpyAsync(shift, d_shift, sizeof(float) * (size_t)B * N * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(s);   // par is a host source of an async copy: wait before it leaves scope
+    (void)hipFree(d_par); (void)hipFree(d_ref); (void)hipFree(d_shift);
+    if (e != hipSuccess || es != hipSuccess) { g_create_err = std::string("dsg_debug_box_guide: ") + hipGetErrorString(e != hipSuccess ? e : es); return DSG_ERR_HIP; }
+    if (!ok) { g_create_err = "dsg_debug_box_guide: shape refused"; return DSG_ERR_INVALID; }
+    return DSG_OK;
 }
 
 int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_kind, int64_t *launches_by_kind,

@@ -349,6 +349,35 @@ void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRo
 // DPM-Solver++ 2M in EDM variables: the Euler update with D replaced by D + ms_coef[step] * (D - Dprev), Dprev = the previous step's D
 void launch_multistep_tab(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
                           StatePtrs x, Dims d, hipStream_t s);
+// ---- box guidance through the skip path (guide_kernels.hip; dsg_sample_guided) ----
+// What a guided step body reads, at a fixed device address that the body bakes; the run rewrites the contents, so the tables behind
+// the pointers may move without invalidating a captured body.  a_o / a_r / a_a: weights of the overlap, region and alignment loss;
+// sel [B,N] / region [B,N,4] (x0, y0, x1, y1): the region loss's nodes and rectangles (read only where a_r != 0); coef [T]: c_i per
+// SCHEDULE index (dsg_guide_coef); trace [L,B] or null: L(D) of every executed step's stage-1 call; mask_node [B,N,Cn] or null: the
+// known mask of a conditioned run -- the shift is zero there
+struct GuideParams { float a_o, a_r, a_a, tau, clip_ratio; int pad; const uint8_t *sel; const float *region; const float *coef; float *trace;
+                     const uint8_t *mask_node; };
+constexpr int GUIDE_MAX_N = 64;
+// ||a_b - b_b||^2 over the live entries of each graph, float64, one fixed order (t_graph_dot's).  false: shape refused (N > GUIDE_MAX_N)
+bool launch_graph_diff_norm(CStatePtrs a, CStatePtrs b, const uint8_t *flags, double *out, Dims d, hipStream_t s);
+// per-graph outputs of the guide kernel; every pointer but shift may be null.  shift [B,N,4] = f_b c g as the update subtracts it,
+// grad [B,N,4] = dL/dD at the box channels, loss [B], factor [B] = f_b, norms [B,2] = (||c g||, ||x_hat - D||; the second 0 without clip)
+struct BoxGuideOut { float *shift, *grad, *loss, *factor, *norms; };
+// One block per graph: L(D) and g from closed forms, c = P->coef[tab[ctl->step].sched] (tab null: coef_direct), shift zero at known and
+// padded entries, f_b = guide.clip_factor from ref_norm2 [B] (launch_graph_diff_norm; null: unclipped, f_b = 1).  stage1: also writes
+// the trace row of the executed step.  false: shape refused (N > GUIDE_MAX_N, Cn < 4)
+bool launch_box_guide(const GuideParams *P, const StepRow *tab, const RunCtl *ctl, float coef_direct, const float *D_node, const uint8_t *flags,
+                      const double *ref_norm2, bool stage1, BoxGuideOut o, Dims d, hipStream_t s);
+// out = valid ? D_node - shift (box channels) : 0  -- D~ on its own, for dsg_debug_box_guide
+void launch_box_apply(const float *D_node, const float *shift, const uint8_t *flags, float *out, Dims d, hipStream_t s);
+// the update operations reading D~ = D - shift at the box channels of the node estimate (shift buffers [B,N,4] of launch_box_guide);
+// instantiations of their own: the unguided kernels carry no extra load or branch
+void launch_euler_tab_guided(CStatePtrs xhat, CStatePtrs D, const float *shift, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
+                             StatePtrs x, Dims d, hipStream_t s);
+void launch_heun_tab_guided(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const float *shift1, const float *shift2, const StepRow *tab,
+                            const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
+void launch_multistep_tab_guided(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const float *shift, const float *shift_prev, const StepRow *tab,
+                                 const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
 // dst[0..n) = table[tab[step].sched][0..n)  (the (scale,shift) row of the step's schedule index), and ctl->step += 1
 void launch_step_row(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst, hipStream_t s);
 void launch_step_advance(RunCtl *ctl, hipStream_t s);

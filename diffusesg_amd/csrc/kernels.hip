@@ -2556,14 +2556,25 @@ struct Churn {
 void launch_churn_tab(CStatePtrs x, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs xhat, Dims d, hipStream_t s) {
     launch_elem(Churn{x, tab, ctl, flags}, xhat, d, s);
 }
+// the updates' arithmetic on one element, shared by the plain and the guided operations
+__device__ __forceinline__ float euler_update(const StepRow &r, float xh, float dv) {
+    const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, dv));           // edm.py:384-385
+    return FADD(xh, FMUL(r.h, dc));                                         // edm.py:395-396, :421-422
+}
+__device__ __forceinline__ float heun_update(const StepRow &r, float xh, float d1, float d2) {
+    const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, d1));        // edm.py:384-385
+    const float xp = FADD(xh, FMUL(r.h, dc));                           // edm.py:389-390 (alpha = 1)
+    const float dp = FSUB(FMUL(r.inv_tp, xp), FMUL(r.inv_tp, d2));      // edm.py:414-417
+    const float avg = FADD(FMUL(0.5f, dc), FMUL(0.5f, dp));
+    return FADD(xh, FMUL(r.h, avg));                                    // edm.py:418-422
+}
+__device__ __forceinline__ float multistep_update(const StepRow &r, float xh, float dn, float dp) {
+    return euler_update(r, xh, FADD(dn, FMUL(r.ms_coef, FSUB(dn, dp))));
+}
 struct Euler {
     CStatePtrs xhat, D; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
     __device__ StepRow uniform() const { return tab[ctl->step]; }
-    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &) const {
-        const float xh = ld(xhat, e);
-        const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, ld(D, e)));     // edm.py:384-385
-        return FADD(xh, FMUL(r.h, dc));                                         // edm.py:395-396, :421-422
-    }
+    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &) const { return euler_update(r, ld(xhat, e), ld(D, e)); }
 };
 void launch_euler_tab(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d,
                       hipStream_t s) {
@@ -2573,12 +2584,7 @@ struct Heun {
     CStatePtrs xhat, D1, D2; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
     __device__ StepRow uniform() const { return tab[ctl->step]; }
     __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &) const {
-        const float xh = ld(xhat, e), d1 = ld(D1, e), d2 = ld(D2, e);
-        const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, d1));        // edm.py:384-385
-        const float xp = FADD(xh, FMUL(r.h, dc));                           // edm.py:389-390 (alpha = 1)
-        const float dp = FSUB(FMUL(r.inv_tp, xp), FMUL(r.inv_tp, d2));      // edm.py:414-417
-        const float avg = FADD(FMUL(0.5f, dc), FMUL(0.5f, dp));
-        return FADD(xh, FMUL(r.h, avg));                                    // edm.py:418-422
+        return heun_update(r, ld(xhat, e), ld(D1, e), ld(D2, e));
     }
 };
 void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
@@ -2592,15 +2598,56 @@ struct Multistep {
     CStatePtrs xhat, D, Dprev; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
     __device__ StepRow uniform() const { return tab[ctl->step]; }
     __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &) const {
-        const float xh = ld(xhat, e), dn = ld(D, e), dp = ld(Dprev, e);
-        const float dt = FADD(dn, FMUL(r.ms_coef, FSUB(dn, dp)));
-        const float dc = FSUB(FMUL(r.inv_t, xh), FMUL(r.inv_t, dt));
-        return FADD(xh, FMUL(r.h, dc));
+        return multistep_update(r, ld(xhat, e), ld(D, e), ld(Dprev, e));
     }
 };
 void launch_multistep_tab(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
                           StatePtrs x, Dims d, hipStream_t s) {
     launch_elem(Multistep{xhat, D, Dprev, tab, ctl, flags}, x, d, s);
+}
+// Box guidance (guide_kernels.hip): the same updates reading D~ = D - shift, shift [B, N, 4] at the last four node channels and
+// nothing elsewhere.  The d_* buffers stay unshifted -- they are the self-conditioning input of the next call -- and the operations
+// above stay as they are: an unguided run carries neither the load nor the branch.
+struct BoxShift {
+    const float *p;
+    __device__ float operator()(float dv, const ElemIdx &e, const Dims &d) const {
+        if (e.is_adj) return dv;
+        const int c = (int)(e.off % d.Cn) - (d.Cn - 4);
+        return c >= 0 ? FSUB(dv, p[(e.off / d.Cn) * 4 + c]) : dv;
+    }
+};
+struct EulerGuided {
+    CStatePtrs xhat, D; BoxShift g; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+    __device__ StepRow uniform() const { return tab[ctl->step]; }
+    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &d) const {
+        return euler_update(r, ld(xhat, e), g(ld(D, e), e, d));
+    }
+};
+void launch_euler_tab_guided(CStatePtrs xhat, CStatePtrs D, const float *shift, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
+                             StatePtrs x, Dims d, hipStream_t s) {
+    launch_elem(EulerGuided{xhat, D, {shift}, tab, ctl, flags}, x, d, s);
+}
+struct HeunGuided {
+    CStatePtrs xhat, D1, D2; BoxShift g1, g2; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+    __device__ StepRow uniform() const { return tab[ctl->step]; }
+    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &d) const {
+        return heun_update(r, ld(xhat, e), g1(ld(D1, e), e, d), g2(ld(D2, e), e, d));
+    }
+};
+void launch_heun_tab_guided(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const float *shift1, const float *shift2, const StepRow *tab,
+                            const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
+    launch_elem(HeunGuided{xhat, D1, D2, {shift1}, {shift2}, tab, ctl, flags}, x, d, s);
+}
+struct MultistepGuided {   // D~ + c (D~ - D~prev): the extrapolation reads the guided estimates of both steps
+    CStatePtrs xhat, D, Dprev; BoxShift g, gprev; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+    __device__ StepRow uniform() const { return tab[ctl->step]; }
+    __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &d) const {
+        return multistep_update(r, ld(xhat, e), g(ld(D, e), e, d), gprev(ld(Dprev, e), e, d));
+    }
+};
+void launch_multistep_tab_guided(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const float *shift, const float *shift_prev, const StepRow *tab,
+                                 const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
+    launch_elem(MultistepGuided{xhat, D, Dprev, {shift}, {shift_prev}, tab, ctl, flags}, x, d, s);
 }
 // the table has one row per SCHEDULE index; the executed step's row names it (a resampling walk visits an index more than once)
 __global__ void step_row_kernel(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst) {

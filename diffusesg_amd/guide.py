@@ -15,6 +15,12 @@ project: what guidance does to sample quality is not validated here (DESIGN.md ย
 
 The losses read boxes the way `io.decode` does: the last four node channels, * 0.5 + 0.5, (cx, cy, w, h).  They are plain torch and
 run on any device.
+
+`BoxGuide` names a weighted sum of the three box losses for the guidance that runs INSIDE the library's loop
+(`NodeAdjEDMSamplerHip.sample_guided`, `dsg_sample_guided`): the same shift with the network's Jacobian dropped from
+grad_{x_hat} L(D) = (c_skip I + c_out dF/dx_hat)^T dL/dD, evaluated by a HIP kernel with analytic gradients -- no backward, no
+training-form forward, step graphs and walks as in `sample()`.  It is an approximation of the shift above, exact only where the
+network's Jacobian vanishes (DESIGN.md ยง13); `BoxGuide.torch_loss` hands the same loss to `guided_sample`, the through-the-network form.
 """
 from __future__ import annotations
 
@@ -108,6 +114,103 @@ def box_alignment_loss(node_flags=None, tau=0.05):
         soft = -tau * torch.logsumexp(z, dim=-1) + tau * torch.log(cnt)
         return (soft * has.to(soft.dtype)).sum()
     return loss
+
+
+def box_region_loss_nodes(sel, rects, node_flags=None):
+    """`box_region_loss` with one rectangle per node: sel [B, N] (bool or integer, nonzero = the node is constrained), rects [B, N, 4]
+    (x0, y0, x1, y1); the sum over selected (and, with `node_flags`, valid) nodes of the four squared overshoots."""
+    def loss(D_adj, D_node):
+        b = _boxes(D_node)
+        if tuple(sel.shape) != tuple(b.shape[:2]) or tuple(rects.shape) != tuple(b.shape[:2]) + (4,):
+            raise ValueError(f"box_region_loss_nodes: sel {tuple(sel.shape)} / rects {tuple(rects.shape)} do not fit nodes {tuple(b.shape[:2])}")
+        l, t, r, bt = _corners(b)
+        rc = rects.to(device=b.device, dtype=b.dtype)
+        over = torch.relu(rc[..., 0] - l) ** 2 + torch.relu(rc[..., 1] - t) ** 2 + torch.relu(r - rc[..., 2]) ** 2 + torch.relu(bt - rc[..., 3]) ** 2
+        on = sel.to(device=b.device) != 0
+        if node_flags is not None:
+            on = on & node_flags.to(device=b.device).bool()
+        return torch.where(on, over, torch.zeros_like(over)).sum()
+    return loss
+
+
+class BoxGuide(object):
+    """L = overlap * L_overlap + region_weight * L_region + align * L_align on the boxes of the node estimate, always with the node
+    flags (padded nodes take no part): the loss of in-loop guidance (`NodeAdjEDMSamplerHip.sample_guided`).
+      overlap, align: weights of `box_overlap_loss` / `box_alignment_loss(tau=tau)`; 0 = the term is not evaluated.
+      region: None, or (sel [B, N], rects [B, N, 4]) -- one rectangle (x0, y0, x1, y1) per selected node, `box_region_loss_nodes` --
+              or (node_idx, rect) -- `box_region_loss`'s form: the same rectangle for that node (or those nodes) in every graph.
+      region_weight: weight of the region term where `region` is given."""
+
+    def __init__(self, overlap=0.0, region=None, align=0.0, tau=0.05, region_weight=1.0):
+        self.overlap, self.align, self.tau = float(overlap), float(align), float(tau)
+        self.region_weight = float(region_weight) if region is not None else 0.0
+        for name, v in (("overlap", self.overlap), ("align", self.align), ("region_weight", self.region_weight), ("tau", self.tau)):
+            if not np.isfinite(v):
+                raise ValueError(f"BoxGuide: {name} = {v} is not finite")
+        if self.align != 0 and not self.tau > 0:
+            raise ValueError("BoxGuide: tau must be positive")
+        self.region = None
+        if region is not None:
+            if len(region) != 2:
+                raise ValueError("BoxGuide: region = (sel [B, N], rects [B, N, 4]) or (node_idx, (x0, y0, x1, y1))")
+            a, r = region
+            if isinstance(a, (torch.Tensor, np.ndarray)) and np.ndim(a) == 2:
+                self.region = ("nodes", torch.as_tensor(a), torch.as_tensor(r).to(torch.float32))
+            else:
+                idx = [int(a)] if isinstance(a, (int, np.integer)) else [int(k) for k in a]
+                x0, y0, x1, y1 = (float(v) for v in r)
+                if not (x0 < x1 and y0 < y1):
+                    raise ValueError(f"BoxGuide: empty region {r}")
+                if not idx or min(idx) < 0:
+                    raise ValueError(f"BoxGuide: bad node index {a}")
+                self.region = ("index", idx, (x0, y0, x1, y1))
+
+    def region_tensors(self, B, n, device="cpu"):
+        """(sel uint8 [B, n], rects float32 [B, n, 4]) of the region term on `device`, None without one; ValueError on a shape that
+        does not fit the batch."""
+        if self.region is None:
+            return None
+        if self.region[0] == "nodes":
+            sel, rc = self.region[1], self.region[2]
+            if tuple(sel.shape) != (B, n) or tuple(rc.shape) != (B, n, 4):
+                raise ValueError(f"BoxGuide: region sel {tuple(sel.shape)} / rects {tuple(rc.shape)}, expected ({B}, {n}) / ({B}, {n}, 4)")
+            return (sel != 0).to(device=device, dtype=torch.uint8).contiguous(), rc.to(device=device, dtype=torch.float32).contiguous()
+        _, idx, rect = self.region
+        if max(idx) >= n:
+            raise ValueError(f"BoxGuide: node index {max(idx)} is outside the {n} nodes")
+        sel = torch.zeros((B, n), dtype=torch.uint8)
+        sel[:, idx] = 1
+        rc = torch.zeros((B, n, 4), dtype=torch.float32)
+        rc[:, idx] = torch.tensor(rect, dtype=torch.float32)
+        return sel.to(device), rc.to(device)
+
+    def descriptor(self, B, n, device, clip_ratio=1.0):
+        """(`lib.DsgGuideCfg` without its weights, the device tensors it points at -- keep them alive over the call)"""
+        reg = self.region_tensors(B, n, device)
+        clip = _lib.GUIDE_CLIP_NONE if clip_ratio is None else float(clip_ratio)
+        g = _lib.DsgGuideCfg(self.overlap, self.region_weight, self.align, self.tau, clip, 0,
+                             None if reg is None else reg[0].data_ptr(), None if reg is None else reg[1].data_ptr(), None)
+        return g, reg
+
+    def torch_loss(self, node_flags):
+        """The same loss as a `guide.py` closure loss(D_adj, D_node) -> scalar, for `guided_sample` and the tests."""
+        terms = []
+        if self.overlap != 0:
+            terms.append((self.overlap, box_overlap_loss(node_flags)))
+        if self.region is not None and self.region_weight != 0:
+            if self.region[0] == "nodes":
+                terms.append((self.region_weight, box_region_loss_nodes(self.region[1], self.region[2], node_flags)))
+            else:
+                terms.append((self.region_weight, box_region_loss(self.region[1], self.region[2], node_flags)))
+        if self.align != 0:
+            terms.append((self.align, box_alignment_loss(node_flags, self.tau)))
+
+        def loss(D_adj, D_node):
+            total = _boxes(D_node).sum() * 0.0
+            for wgt, fn in terms:
+                total = total + fn(D_adj, D_node) * wgt
+            return total
+        return loss
 
 
 # ---- host arithmetic of the guided loop (no GPU needed) -------------------------------------------------------------

@@ -26,6 +26,7 @@ EXPORTS = [
     "dsg_debug_window_broadcast_f32", "dsg_debug_window_harvest_f32",
     "dsg_ode_run", "dsg_ode_evals", "dsg_debug_graph_dot",
     "dsg_debug_poison",
+    "dsg_guide_coef", "dsg_sample_guided", "dsg_debug_box_guide",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -64,6 +65,14 @@ class DsgOdeCfg(C.Structure):
     """dsg_ode_cfg of include/dsg.h (dsg_ode_run, dsg_ode_evals)"""
     _fields_ = [("direction", C.c_int32), ("probe", C.c_int32), ("reserved", C.c_int32 * 6)]
 
+
+class DsgGuideCfg(C.Structure):
+    """dsg_guide_cfg of include/dsg.h (dsg_sample_guided, dsg_debug_box_guide): sel / region device pointers, weights a host pointer"""
+    _fields_ = [("w_overlap", C.c_float), ("w_region", C.c_float), ("w_align", C.c_float), ("tau", C.c_float), ("clip_ratio", C.c_float),
+                ("reserved", C.c_int32), ("sel", C.c_void_p), ("region", C.c_void_p), ("weights", C.c_void_p)]
+
+
+GUIDE_CLIP_NONE = float("inf")   # DSG_GUIDE_CLIP_NONE: unclipped, no norm pass
 
 ODE_ENCODE, ODE_DECODE = 0, 1                                  # DSG_ODE_ENCODE / DSG_ODE_DECODE
 ODE_PROBES = {"none": 0, "rademacher": 1, "gaussian": 2}       # DSG_ODE_PROBE_*
@@ -154,6 +163,11 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_sample_seeded.argtypes = [vp, C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), i32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp,
                                     vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
     L.dsg_gen_noise_seeded.argtypes = [vp, i32, vp, vp, C.c_uint32, vp, vp, vp]
+    L.dsg_sample_guided.argtypes = [vp, C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), i32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(DsgGuideCfg), vp, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
+    L.dsg_guide_coef.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, i32]
+    L.dsg_guide_coef.restype = i32
+    L.dsg_debug_box_guide.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DsgGuideCfg), C.c_float, vp, vp, vp, vp, vp, vp, vp]
     L.dsg_walk_steps.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, vp, i32]
     L.dsg_walk_steps.restype = i32
     L.dsg_multistep_coef.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, i32]
@@ -443,6 +457,20 @@ def multistep_coef(scfg: DsgSamplerCfg, walk: Optional[DsgWalkCfg] = None):
     rc = int(L.dsg_multistep_coef(C.byref(scfg), w, coef.ctypes.data, n))
     if rc != n:
         raise DsgError(f"dsg_multistep_coef: status {rc}")
+    return coef
+
+
+def guide_coef(scfg: DsgSamplerCfg, weights):
+    """c_i float32 [T] of box guidance (dsg_guide_coef): w_i t_hat[i]^2 c_skip(t_hat[i]) per schedule index as the guided loop stages
+    them -- host-only, no GPU needed.  DsgError when the library refuses the weights (not T of them, or one that is not finite)."""
+    import numpy as np
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.shape != (scfg.num_steps,):
+        raise DsgError(f"dsg_guide_coef: {scfg.num_steps} weights expected (one per schedule index), got shape {w.shape}")
+    coef = np.empty(scfg.num_steps, np.float32)
+    rc = int(load().dsg_guide_coef(C.byref(scfg), w.ctypes.data, coef.ctypes.data, scfg.num_steps))
+    if rc != scfg.num_steps:
+        raise DsgError(f"dsg_guide_coef: status {rc}: the weights must be finite")
     return coef
 
 

@@ -267,11 +267,55 @@ class NodeAdjEDMSamplerHip(object):
                                 flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
                                 churn_noise, coins, seed, return_device, walk, graph_seeds, coin_seed)
 
+    @torch.no_grad()
+    def sample_guided(self, model, node_flags, guide, scale, *, clip_ratio=1.0, known=None,
+                      resample=None, resample_range=None, start_step=0, base_adjs=None, base_nodes=None,
+                      graph_seeds=None, coin_seed=None, return_loss_trace=False,
+                      init_adjs=None, init_nodes=None, sanity_check_gt_adjs=None, sanity_check_gt_nodes=None,
+                      flag_interim_adjs=False, max_num_interim_adjs=None, flag_adj_multi_channel=False,
+                      num_node_chan=None, num_edge_chan=None, churn_noise=None, coins=None, seed=None, return_device=False):
+        """Box guidance through the skip path, inside the loop (`dsg_sample_guided`; not in the reference): `sample()` /
+        `sample_known()` with the denoised estimate of every preconditioned call shifted against the gradient of `guide`'s box loss,
+            D~ = D - f_b c_i dL/dD,   c_i = w_i t^2 c_skip(t),
+        the guidance of `guide.guided_sample` with the network's Jacobian dropped: an approximation (exact where that Jacobian
+        vanishes) that costs one small kernel per call, no backward, and keeps step graphs, walks, known entries and per-graph seeds.
+        guide: a `diffusesg_amd.guide.BoxGuide`; scale: w, or one w_i per schedule index; clip_ratio = r: per graph the shift never
+        exceeds r ||x_hat_b - D_b||, None: unclipped.  known = (known_adjs, known_nodes, known_adj_mask, known_node_mask) as in
+        `sample_known` (known entries win and stay bit-exact); resample / resample_range / start_step / base_*: its walk;
+        graph_seeds / coin_seed and everything after them: as in `sample()` (sanity_check_gt_*: the sanity-check mode, the guide then
+        runs on the ground truth; not with known or graph_seeds).  Channel counts default to the network's.
+        scale = 0 gives `sample()` / `sample_known()` exactly.  Returns what `sample()` returns; with return_loss_trace a float32 CPU
+        tensor [L, B] more: L(D) at the stage-1 call of every executed step."""
+        from .guide import BoxGuide, guidance_weights
+        if isinstance(model, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)):
+            model = model.module
+        if not isinstance(guide, BoxGuide):
+            raise TypeError("sample_guided needs a diffusesg_amd.guide.BoxGuide (arbitrary losses: guide.guided_sample)")
+        if clip_ratio is not None and not float(clip_ratio) >= 0:
+            raise ValueError(f"clip_ratio must be >= 0 or None, got {clip_ratio}")
+        w = guidance_weights(scale, self.num_steps)
+        gt = sanity_check_gt_adjs is not None or sanity_check_gt_nodes is not None
+        if gt and (known is not None or graph_seeds is not None):
+            raise ValueError("sample_guided: sanity_check_gt_* go with neither known= nor graph_seeds=")
+        if known is not None and (len(known) != 4 or any(k is None for k in known)):
+            raise ValueError("known = (known_adjs, known_nodes, known_adj_mask, known_node_mask)")
+        walk = None
+        if resample is not None or resample_range is not None or start_step != 0 or base_adjs is not None or base_nodes is not None:
+            walk = dict(resample=resample, resample_range=resample_range, start_step=start_step, base_adjs=base_adjs, base_nodes=base_nodes)
+        cfg = model.model.config if isinstance(model, NodeAdjPrecondHip) else None
+        return self._sample_hip(model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, known,
+                                flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel,
+                                cfg.c_node if num_node_chan is None and cfg is not None else num_node_chan,
+                                cfg.c_adj if num_edge_chan is None and cfg is not None else num_edge_chan,
+                                churn_noise, coins, seed, return_device, walk, graph_seeds, coin_seed,
+                                guide=(guide, w, clip_ratio, bool(return_loss_trace)))
+
     def _sample_hip(self, model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, known,
                     flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
-                    churn_noise, coins, seed, return_device, walk=None, graph_seeds=None, coin_seed=None):
+                    churn_noise, coins, seed, return_device, walk=None, graph_seeds=None, coin_seed=None, guide=None):
         """The loop inside libdsg.so: `dsg_sample`, or `dsg_sample_known` when `known` = (adjs, nodes, adj mask, node mask); with
-        `walk` (the walk keywords of `sample_known`) `dsg_sample_walk`; with `graph_seeds` `dsg_sample_seeded`, whatever else is given."""
+        `walk` (the walk keywords of `sample_known`) `dsg_sample_walk`; with `graph_seeds` `dsg_sample_seeded`, whatever else is given;
+        with `guide` = (BoxGuide, weights [T], clip_ratio, return_loss_trace) `dsg_sample_guided`, whatever else is given."""
         if not isinstance(model, NodeAdjPrecondHip):
             raise TypeError("NodeAdjEDMSamplerHip needs the NodeAdjPrecondHip network returned by build_network()")
         gs = None
@@ -376,7 +420,23 @@ class NodeAdjEDMSamplerHip(object):
                 h.check(h.L.dsg_gen_noise(h.raw, B, p(fl), C.c_uint64(seed_v), 0, p(ia), p(inn), C.c_void_p(st)), "dsg_gen_noise")
         snap_args = (C.c_void_p(0 if snap_steps is None else snap_steps.ctypes.data),
                      0 if snap_steps is None else len(snap_steps), p(snap_a), p(snap_n))
-        if gs is not None:
+        trace = None
+        if guide is not None:
+            bg, gw, clip_ratio, want_trace = guide
+            gw = np.ascontiguousarray(gw, dtype=np.float32)
+            gcfg, g_keep = bg.descriptor(B, n, dev, clip_ratio)   # shapes refused here, before anything is launched
+            gcfg.weights = gw.ctypes.data
+            if want_trace:
+                trace = torch.empty((L, B), dtype=torch.float32, device=dev)
+            ka, kn, ma, mn = (ka, kn, ma, mn) if known is not None else (None,) * 4
+            key = seed_v if gs is None else (self.seed if coin_seed is None else int(coin_seed))
+            h.check(h.L.dsg_sample_guided(h.raw, C.byref(scfg), C.byref(wcfg) if wcfg is not None else None, B, p(fl),
+                                          C.c_void_p(0 if gs is None else gs.ctypes.data), C.c_uint64(key & (2 ** 64 - 1)),
+                                          p(ia), p(inn), p(ba), p(bn), p(na), p(nn_), C.c_void_p(coins.ctypes.data),
+                                          p(ka), p(kn), p(ma), p(mn), *snap_args, C.byref(gcfg), p(ga), p(gn), p(trace),
+                                          p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample_guided")
+            del g_keep
+        elif gs is not None:
             ka, kn, ma, mn = (ka, kn, ma, mn) if known is not None else (None,) * 4
             coin_seed_v = self.seed if coin_seed is None else int(coin_seed)   # (the coins are always handed over: not read by the library)
             h.check(h.L.dsg_sample_seeded(h.raw, C.byref(scfg), C.byref(wcfg) if wcfg is not None else None, B, p(fl),
@@ -407,9 +467,19 @@ class NodeAdjEDMSamplerHip(object):
             oa = oa[:, 0]
         if cfg.c_node == 1:
             on = on[..., 0]
+        extra = () if trace is None else (trace.cpu(),)
         if return_device:
-            return oa, on
+            return (oa, on) + extra if extra else (oa, on)
         adjs, nodes = oa.cpu(), on.cpu()
+        if extra:
+            # the guided call's returns carry the loss trace behind what `sample()` returns
+            if flag_interim_adjs:
+                sq_n = (lambda t: t[..., 0]) if cfg.c_node == 1 else (lambda t: t)
+                sq_a = (lambda t: t[:, :, 0]) if cfg.c_adj == 1 else (lambda t: t)
+                nodes_ls = sq_n(torch.cat([inn.cpu().reshape((1,) + sn), snap_n.cpu()]))
+                adjs_ls = [None] if flag_adj_multi_channel else sq_a(torch.cat([ia.cpu().reshape((1,) + sa), snap_a.cpu()]))
+                return (adjs, nodes, adjs_ls, nodes_ls) + extra
+            return (adjs, nodes) + extra
         if flag_interim_adjs:
             # torch.stack(nodes_ls) of edm.py:441-443: slot 0 = unscaled init, then one entry per snapshot step
             sq_n = (lambda t: t[..., 0]) if cfg.c_node == 1 else (lambda t: t)

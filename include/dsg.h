@@ -40,8 +40,8 @@ extern "C" {
  * at load time (diffusesg_amd/lib.py does): round 3 inserted `iou_loss_type` into three entries, and a caller built against the older
  * header would otherwise pass shifted arguments without any error.  History: 1-3 = rounds 1-3 (unversioned), 4 = round 4
  * (dsg_decode with an encoding argument, dsg_abi_version, dsg_last_error(NULL)).  dsg_sample_seeded, dsg_gen_noise_seeded and the option
- * "batch_invariant" were added without touching an existing argument list: still 4; so were the dsg_debug_*_f32 test hooks, and
- * dsg_ode_run / dsg_ode_evals / dsg_debug_graph_dot. */
+ * "batch_invariant" were added without touching an existing argument list: still 4; so were the dsg_debug_*_f32 test hooks,
+ * dsg_ode_run / dsg_ode_evals / dsg_debug_graph_dot, and dsg_guide_cfg / dsg_sample_guided / dsg_guide_coef / dsg_debug_box_guide. */
 #define DSG_ABI_VERSION 4
 
 typedef enum {
@@ -278,6 +278,70 @@ int dsg_sample_seeded(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_c
                       const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
                       const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
                       float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream);
+
+/* Box guidance through the skip path, inside the loop.  Per preconditioned call at schedule index i, noise level
+ * t = t_hat[i], input x_hat and estimate D (after the valid mask and, in a conditioned run, the known select):
+ *     b      = D_node[..., C_node-4:] * 0.5 + 0.5, read as (cx, cy, w, h)              (dsg_decode's boxes)
+ *     L      = w_overlap L_overlap + w_region L_region + w_align L_align               (diffusesg_amd/guide.py's three box losses, always
+ *              with the node flags; the region loss with one rectangle per selected node)
+ *     g      = dL/dD_node: zero outside the four box channels and at padded nodes; relu passes where its argument is > 0, minimum and
+ *              maximum split a tie evenly (torch autograd's conventions)
+ *     c_i    = weights[i] * t^2 * c_skip(t),  c_skip = 0.25 / (t^2 + 0.25)             (dsg_guide_coef: one float32 per schedule index)
+ *     shift  = c_i g, zero at node entries whose known mask is set: known entries win and stay bit-exact
+ *     f_b    = shift-norm clip: 1 if ||shift_b|| <= clip_ratio ||x_hat_b - D_b||, else that bound over ||shift_b|| (both 2-norms per
+ *              graph, the second over the graph's whole state; fixed-order float64 sums, no atomics, independent of B)
+ *     D~     = D - f_b shift
+ * and the solver's update reads D~ wherever it reads D: Euler, both Heun stages, and the multistep extrapolation D~ + c (D~ - D~_prev).
+ * The self-conditioning input of the next call stays D, and the D of a fired coin's extra pass is not shifted.  This is the guidance of
+ * guide.guided_sample with the network's Jacobian dropped from dD/dx_hat = c_skip I + c_out dF/dx_hat: an approximation, exact where
+ * that Jacobian vanishes, at the cost of one small kernel per call (two with the clip) and no backward.
+ *   w_*: loss weights (finite); tau > 0 wherever w_align != 0; clip_ratio >= 0, or DSG_GUIDE_CLIP_NONE (any +infinity): unclipped, no norm
+ *   pass is launched; sel [B,N] uint8 / region [B,N,4] (x0, y0, x1, y1): DEVICE, required where w_region != 0, else unread -- node n of
+ *   graph b contributes where sel is set and the node is valid; weights [T]: HOST, finite, one w_i per SCHEDULE index (a walk's executed
+ *   step finds its entry through its schedule index).  sel / region / the coefficients are copied into workspace memory on `stream`
+ *   ahead of the run's synchronise (dsg_workspace_bytes counts them once allocated): step bodies never reference caller memory. */
+typedef struct dsg_guide_cfg {
+    float w_overlap, w_region, w_align;
+    float tau;
+    float clip_ratio;
+    int32_t reserved;         /* 0 */
+    const uint8_t *sel;
+    const float *region;
+    const float *weights;
+} dsg_guide_cfg;
+#define DSG_GUIDE_CLIP_NONE (__builtin_inff())
+
+/* c_i [T] as the guided loop stages them: w_i t^2 * 0.25 / (t^2 + 0.25), t = the float32 t_hat[i] of dsg_sigma_schedule, evaluated in
+ * double and rounded once to float (as dsg_multistep_coef does): within half an ulp of the real value.  Host-only.  Returns T, or DSG_ERR_INVALID (null argument, num_steps < 1, cap < T, a non-finite weight). */
+int32_t dsg_guide_coef(const dsg_sampler_cfg *cfg, const float *weights /* host [T] */, float *coef /* host [T] */, int32_t cap);
+
+/* dsg_sample_seeded's loop and argument list with the guidance above.  graph_seeds == NULL: one noise stream over the batch keyed by
+ * `coin_seed`, which then is dsg_sample_walk's `seed` (noise and coins).  gt_adj / gt_node (both or neither): dsg_sample's sanity-check
+ * mode, the guide then runs on gt; not together with known_* or graph_seeds.  loss_trace: DEVICE [L,B] or NULL -- L(D) of the stage-1
+ * call of every executed step.  Guided step bodies are captured bodies of their own: an unguided run enqueues exactly what it did, and
+ * with every weights[i] = 0 the result equals the unguided run's.
+ * Refused with DSG_ERR_INVALID before anything is launched, the message naming the argument: guide == NULL, guide->weights == NULL,
+ * C_node < 4, N > 64, tau <= 0 with w_align != 0, w_region != 0 without sel / region, a non-finite weight, a negative or NaN clip_ratio,
+ * and everything dsg_sample_seeded refuses (the multistep solver on a schedule with churn among it). */
+int dsg_sample_guided(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk /* NULL: trivial walk */,
+                      int32_t B, const uint8_t *flags,
+                      const uint64_t *graph_seeds /* host, [B], or NULL */, uint64_t coin_seed,
+                      const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                      const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                      const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                      const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                      const dsg_guide_cfg *guide, const float *gt_adj, const float *gt_node, float *loss_trace,
+                      float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream);
+
+/* The guide kernel on its own (test hook, no handle; device pointers, synchronises `stream`): one call's arithmetic on given x_hat, D,
+ * flags [B,N], node known mask [B,N,C_node] (NULL: none) and ONE coefficient `coef` in place of c_i; guide->weights is not read.
+ * Outputs (each may be NULL): loss [B], grad [B,N,4] = g at the box channels, shift [B,N,4] = f_b coef g, factor [B], norms [B,2] =
+ * (||coef g||, ||x_hat - D||; the second is 0 when unclipped), d_guided_node [B,N,C_node] = D~ (0 at padded nodes).  Rows of padded
+ * nodes are never read.  Refusals as above, before any launch; dsg_last_error(NULL) names the argument. */
+int dsg_debug_box_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,
+                        const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_node,
+                        const dsg_guide_cfg *guide, float coef, float *loss, float *grad, float *shift, float *factor, float *norms,
+                        float *d_guided_node, void *stream);
 
 /* sigma_steps (fp64, edm.py:84-88) and the fp32 per-step scalars the loop uses; out arrays of
  * length num_steps.  Host-only helper, exposed so bindings/tests can inspect the schedule. */
