@@ -2728,10 +2728,11 @@ __device__ BoxTerm box_iou_term(const float *pred4, const float *tgt4, int type,
         if (want_grad) {
             const double dw = dwf, dh = dhf, I = (double)iw * ih, U = (double)a0 + a1 - I, io = I / U;
             const double g_iou = -2.0 * io, g_I = g_iou * (U + I) / (U * U), g_A = g_iou * (-I) / (U * U);
-            gc[0] = g_I * ((dw >= 0 && p[0] > g[0]) ? -(double)ih : 0.0) + g_A * (-(double)ph);
-            gc[1] = g_I * ((dh >= 0 && p[1] > g[1]) ? -(double)iw : 0.0) + g_A * (-(double)pw);
-            gc[2] = g_I * ((dw >= 0 && p[2] < g[2]) ? (double)ih : 0.0) + g_A * (double)ph;
-            gc[3] = g_I * ((dh >= 0 && p[3] < g[3]) ? (double)iw : 0.0) + g_A * (double)pw;
+            // max(lt) / min(rb) hand the prediction's corner their whole gradient when it is selected and half of it on a tie
+            gc[0] = g_I * ((dw >= 0 && p[0] >= g[0]) ? -(double)ih * sel_gt(p[0], g[0]) : 0.0) + g_A * (-(double)ph);
+            gc[1] = g_I * ((dh >= 0 && p[1] >= g[1]) ? -(double)iw * sel_gt(p[1], g[1]) : 0.0) + g_A * (-(double)pw);
+            gc[2] = g_I * ((dw >= 0 && p[2] <= g[2]) ? (double)ih * sel_gt(g[2], p[2]) : 0.0) + g_A * (double)ph;
+            gc[3] = g_I * ((dh >= 0 && p[3] <= g[3]) ? (double)iw * sel_gt(g[3], p[3]) : 0.0) + g_A * (double)pw;
         }
     } else {
         const float eps = 1e-7f;

@@ -937,10 +937,14 @@ static float box_term(const float *pred4, const float *tgt4, int type, double *g
             const double g_iou = -2.0 * io;                              /* d/d iou of -(iou^2) */
             const double g_inter = g_iou * (U + I) / (U * U);            /* iou = I/U, dU/dI = -1 */
             const double g_area = g_iou * (-I) / (U * U);
-            gc[0] = g_inter * ((dw >= 0 && x1 > x1g) ? -(double)ih : 0.0) + g_area * (-ah);
-            gc[1] = g_inter * ((dh >= 0 && y1 > y1g) ? -(double)iw : 0.0) + g_area * (-aw);
-            gc[2] = g_inter * ((dw >= 0 && x2 < x2g) ? (double)ih : 0.0) + g_area * ah;
-            gc[3] = g_inter * ((dh >= 0 && y2 < y2g) ? (double)iw : 0.0) + g_area * aw;
+            /* max(lt) / min(rb): the whole gradient to the prediction's corner when it is selected, half of it on a tie; the overlap's
+             * clamp(min=0) passes it at 0 inclusive */
+#define TIE(a, b) ((a) == (b) ? 0.5 : 1.0)
+            gc[0] = g_inter * ((dw >= 0 && x1 >= x1g) ? -(double)ih * TIE(x1, x1g) : 0.0) + g_area * (-ah);
+            gc[1] = g_inter * ((dh >= 0 && y1 >= y1g) ? -(double)iw * TIE(y1, y1g) : 0.0) + g_area * (-aw);
+            gc[2] = g_inter * ((dw >= 0 && x2 <= x2g) ? (double)ih * TIE(x2, x2g) : 0.0) + g_area * ah;
+            gc[3] = g_inter * ((dh >= 0 && y2 <= y2g) ? (double)iw * TIE(y2, y2g) : 0.0) + g_area * aw;
+#undef TIE
         }
     } else {
         const float eps = 1e-7f;
