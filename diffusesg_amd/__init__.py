@@ -5,11 +5,11 @@ side mirroring the reference's `model/` and `runner/mcmc_sampler/` callables."""
 from .spec import ModelConfig, tiny_config, vg_config, coco_config  # noqa: F401
 
 __all__ = ["ModelConfig", "tiny_config", "vg_config", "coco_config",
-           "guided_sample", "box_region_loss", "box_overlap_loss", "box_alignment_loss",
+           "guided_sample", "box_region_loss", "box_overlap_loss", "box_alignment_loss", "box_relation_loss",
            "encode", "decode", "log_likelihood", "sample_with_logp", "graph_log_likelihood", "exact_net_trace", "interpolate",
            "assemble_logp"]
 
-_GUIDE = ("guided_sample", "box_region_loss", "box_overlap_loss", "box_alignment_loss")
+_GUIDE = ("guided_sample", "box_region_loss", "box_overlap_loss", "box_alignment_loss", "box_relation_loss")
 _ODE = ("encode", "decode", "log_likelihood", "sample_with_logp", "graph_log_likelihood", "exact_net_trace", "interpolate", "assemble_logp")
 
 

@@ -112,6 +112,8 @@ struct Workspace {
     float *g_region = nullptr, *g_coef = nullptr, *g_trace = nullptr;
     int g_coef_cap = 0;
     size_t g_trace_cap = 0;
+    uint8_t *g_kinds = nullptr, *g_predk = nullptr;   // the relation term: the given kinds [B,N,N] / the predicate -> kind table
+    int g_predk_cap = 0;
     size_t guide_bytes = 0;
     // batch-uniform noise level (the sampler): every sample shares one (scale,shift) row, taken from a table that
     // dsg_sample computes once for all steps; aff_ld == 0 broadcasts row 0 of `aff`
@@ -2010,9 +2012,10 @@ struct StepPlan {
     bool clip = false;    //   with the norm pass and the clip factor in front of it
     int g1 = 0, g2 = 0;   //   w->g_shift buffers of the stage-1 / stage-2 shift
     int gprev = -1;       //   ... and of the previous step's stage-1 shift where prev >= 0
-    int key() const {   // prev, then the guidance bits, sit above every older bit: plans without them keep their keys
+    int rel = REL_NONE;   //   the relation term (dsg_sample_guided_rel): REL_GIVEN / REL_DECODED select the guide kernel's relation variant
+    int key() const {   // prev, then the guidance bits, then the relation bits sit above every older bit: plans without them keep their keys
         return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8) | ((int)known << 9) |
-               ((prev + 1) << 10) | ((int)guided << 12) | ((int)clip << 13) | (g1 << 14) | (g2 << 16) | ((gprev + 1) << 18);
+               ((prev + 1) << 10) | ((int)guided << 12) | ((int)clip << 13) | (g1 << 14) | (g2 << 16) | ((gprev + 1) << 18) | (rel << 20);
     }
 };
 
@@ -2053,9 +2056,12 @@ int precond_tab(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, c
 // box guidance behind one preconditioned call: the norm pass (with the clip only), then the guide kernel on D -> w->g_shift[slot]
 int guide_call(dsg_handle h, Workspace *w, const StepPlan &p, CStatePtrs xh, CStatePtrs D, int slot, bool stage1, const Dims &d, hipStream_t s) {
     if (p.clip && !launch_graph_diff_norm(xh, D, w->flags, w->g_ref, d, s)) return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
-    if (!launch_box_guide(w->g_par, h->tab_step, w->ctl, 0.f, D.node, w->flags, p.clip ? w->g_ref : nullptr, stage1,
-                          BoxGuideOut{w->g_shift[slot], nullptr, nullptr, nullptr, nullptr}, d, s))
-        return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
+    const BoxGuideOut out{w->g_shift[slot], nullptr, nullptr, nullptr, nullptr};
+    const bool ok = p.rel != REL_NONE
+        ? launch_box_guide_rel(w->g_par, h->tab_step, w->ctl, 0.f, D.adj, D.node, w->flags, p.clip ? w->g_ref : nullptr, stage1, out, nullptr,
+                               p.rel == REL_DECODED, d, s)
+        : launch_box_guide(w->g_par, h->tab_step, w->ctl, 0.f, D.node, w->flags, p.clip ? w->g_ref : nullptr, stage1, out, d, s);
+    if (!ok) return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
     return 0;
 }
 
@@ -2499,6 +2505,7 @@ struct SampleArgs {
     CStatePtrs init, base, noise; const uint8_t *coins; uint64_t seed; const uint64_t *graph_seeds;
     CStatePtrs gt; KnownArgs known;
     const dsg_guide_cfg *guide = nullptr; float *loss_trace = nullptr;   // box guidance (dsg_sample_guided); null: the unguided loop
+    const dsg_rel_cfg *rel = nullptr;                                    // ... and its relation term (dsg_sample_guided_rel); null or w_rel == 0: none
     struct Snapshots { const int32_t *steps; int32_t n; float *adj, *node; } snapshots;
     StatePtrs outputs; dsg_sample_stats *stats; hipStream_t stream;
 };
@@ -2540,6 +2547,37 @@ bool guide_cfg_ok(const dsg_guide_cfg *g, int N, int Cn, bool need_weights, std:
     if (!(g->clip_ratio >= 0.f)) return no("guide->clip_ratio = %g must be >= 0, or DSG_GUIDE_CLIP_NONE", g->clip_ratio);
     if (need_weights && !g->weights) return no("guide->weights is NULL (host, one weight per schedule index)", 0);
     return true;
+}
+
+// the checks of a relation descriptor that need no device; `why` names the argument.  Ca: the adjacency channels the decode would read
+bool rel_cfg_ok(const dsg_rel_cfg *r, int Ca, std::string &why) {
+    char buf[256];
+    auto no = [&](const char *fmt, double v) { snprintf(buf, sizeof(buf), fmt, v); why = buf; return false; };
+    if (!std::isfinite(r->w_rel)) return no("rel->w_rel = %g is not finite", r->w_rel);
+    if (!(r->margin >= 0.f && std::isfinite(r->margin))) return no("rel->margin = %g must be >= 0 and finite", r->margin);
+    if (r->source != DSG_REL_GIVEN && r->source != DSG_REL_DECODED) return no("rel->source = %g is neither DSG_REL_GIVEN (0) nor DSG_REL_DECODED (1)", r->source);
+    if (r->source == DSG_REL_GIVEN) {
+        if (r->w_rel != 0.f && !r->kinds) return no("rel->kinds is NULL (device, [B,N,N]) with the given source and w_rel = %g", r->w_rel);
+        return true;
+    }
+    if (!r->pred_kind) return no("rel->pred_kind is NULL (host, one kind per predicate) with the decoded source", 0);
+    if (r->n_adj_type < 1) return no("rel->n_adj_type = %g must be >= 1", r->n_adj_type);
+    if (r->encoding < DSG_ENC_BITS || r->encoding > DSG_ENC_DDPM) return no("rel->encoding = %g must be DSG_ENC_BITS, DSG_ENC_ONE_HOT or DSG_ENC_DDPM", r->encoding);
+    // the channel counts an encoding implies, as dsg_decode checks them
+    if ((r->encoding == DSG_ENC_ONE_HOT && Ca != r->n_adj_type) || (r->encoding == DSG_ENC_DDPM && Ca != 1) ||
+        (r->encoding == DSG_ENC_BITS && (Ca > 30 || (1 << Ca) < r->n_adj_type)))
+        return no("rel->encoding with rel->n_adj_type = %g does not fit the adjacency channels", r->n_adj_type);
+    for (int k = 0; k < r->n_adj_type; k++)
+        if (r->pred_kind[k] >= REL_KINDS) { snprintf(buf, sizeof(buf), "rel->pred_kind[%d] = %d is above 7 (DSG_REL_ON)", k, (int)r->pred_kind[k]); why = buf; return false; }
+    return true;
+}
+// the part of the parameter block that a relation descriptor fills (pointers: set once staged); returns the plan's relation source
+int rel_params(const dsg_rel_cfg *r, GuideParams &g) {
+    if (!r || r->w_rel == 0.f) return REL_NONE;
+    g.a_rel = r->w_rel; g.rel_margin = r->margin;
+    g.rel_source = r->source == DSG_REL_DECODED ? REL_DECODED : REL_GIVEN;
+    g.rel_enc = r->encoding; g.rel_ntype = r->n_adj_type;
+    return g.rel_source;
 }
 
 // Host plan: argument checks, walk, schedule, coins, rows and step plans.  No HIP call.
@@ -2637,6 +2675,11 @@ int plan_sample(dsg_handle h, const SampleArgs &a, SamplePlan &p) {
         }
         p.gpar = GuideParams{a.guide->w_overlap, a.guide->w_region, a.guide->w_align, a.guide->tau, clip ? a.guide->clip_ratio : 0.f, 0,
                              nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (a.rel) {
+            if (!rel_cfg_ok(a.rel, h->Ca, why)) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided_rel: %s", why.c_str());
+            const int rel = rel_params(a.rel, p.gpar);
+            for (int i = 0; i < L; i++) p.plans[i].rel = rel;
+        }
     }
     return 0;
 }
@@ -2764,6 +2807,19 @@ int stage_guide(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, 
     if (a.guide->w_region != 0.f) {
         HIP_TRY(h, hipMemcpyAsync(w->g_sel, a.guide->sel, bn, hipMemcpyDeviceToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(w->g_region, a.guide->region, sizeof(float) * bn * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (p.gpar.rel_source == REL_GIVEN) {   // the kinds, like sel / region; a_rel != 0 here (rel_params)
+        const size_t bnn = bn * h->N;
+        if (!w->g_kinds) { if (int rc = grow(&(q = nullptr), bnn, 0, AC_STATE)) return rc; w->g_kinds = (uint8_t *)q; }
+        HIP_TRY(h, hipMemcpyAsync(w->g_kinds, a.rel->kinds, bnn, hipMemcpyDeviceToDevice, s));
+        p.gpar.kinds = w->g_kinds;
+    } else if (p.gpar.rel_source == REL_DECODED) {   // the table: the caller's host array outlives the run's synchronise
+        if (w->g_predk_cap < p.gpar.rel_ntype) {
+            if (int rc = grow(&(q = w->g_predk), (size_t)p.gpar.rel_ntype, (size_t)w->g_predk_cap, AC_STATE)) return rc;
+            w->g_predk = (uint8_t *)q; w->g_predk_cap = p.gpar.rel_ntype;
+        }
+        HIP_TRY(h, hipMemcpyAsync(w->g_predk, a.rel->pred_kind, (size_t)p.gpar.rel_ntype, hipMemcpyHostToDevice, s));
+        p.gpar.pred_kind = w->g_predk;
     }
     HIP_TRY(h, hipMemcpyAsync(w->g_coef, p.guide_coef.data(), sizeof(float) * (size_t)p.T, hipMemcpyHostToDevice, s));
     p.gpar.sel = w->g_sel; p.gpar.region = w->g_region; p.gpar.coef = w->g_coef;
@@ -2922,6 +2978,30 @@ int dsg_sample_guided(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_c
     return sample_impl(h, a);
 }
 
+int dsg_sample_guided_rel(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
+                          const uint64_t *graph_seeds, uint64_t coin_seed,
+                          const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                          const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                          const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                          const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                          const dsg_guide_cfg *guide, const float *gt_adj, const float *gt_node, float *loss_trace,
+                          float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream, const dsg_rel_cfg *rel) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!guide) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided_rel needs a guide descriptor (guide is NULL)");
+    SampleArgs a{};
+    a.cfg = cfg; a.B = B; a.flags = flags; a.init = {init_adj, init_node}; a.noise = {noise_adj, noise_node}; a.coins = coins; a.seed = coin_seed;
+    a.snapshots = {snap_steps, n_snap, snap_adj, snap_node}; a.outputs = {out_adj, out_node}; a.stats = stats; a.stream = (hipStream_t)stream;
+    a.walk = walk;
+    a.base = {base_adj, base_node};
+    a.graph_seeds = graph_seeds;
+    a.known = {known_adj, known_node, mask_adj, mask_node};
+    a.gt = {gt_adj, gt_node};
+    a.guide = guide; a.loss_trace = loss_trace;
+    a.rel = rel;
+    if (int rc = known_args(h, "dsg_sample_guided_rel", /*required=*/false, a.known)) return rc;
+    return sample_impl(h, a);
+}
+
 int dsg_debug_box_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,
                         const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_node,
                         const dsg_guide_cfg *guide, float coef, float *loss, float *grad, float *shift, float *factor, float *norms,
@@ -2951,6 +3031,54 @@ int dsg_debug_box_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, con
     (void)hipFree(d_par); (void)hipFree(d_ref); (void)hipFree(d_shift);
     if (e != hipSuccess || es != hipSuccess) { g_create_err = std::string("dsg_debug_box_guide: ") + hipGetErrorString(e != hipSuccess ? e : es); return DSG_ERR_HIP; }
     if (!ok) { g_create_err = "dsg_debug_box_guide: shape refused"; return DSG_ERR_INVALID; }
+    return DSG_OK;
+}
+
+int dsg_debug_box_guide_rel(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,
+                            const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_node,
+                            const dsg_guide_cfg *guide, float coef, float *loss, float *grad, float *shift, float *factor, float *norms,
+                            float *d_guided_node, void *stream, const dsg_rel_cfg *rel, uint8_t *kinds_out) {
+    std::string why;
+    const char *me = "dsg_debug_box_guide_rel: ";
+    if (B < 1 || N < 1 || c_adj < 1) { g_create_err = std::string(me) + "B, N and c_adj must be >= 1"; return DSG_ERR_INVALID; }
+    if (!guide_cfg_ok(guide, N, c_node, /*need_weights=*/false, why)) { g_create_err = me + why; return DSG_ERR_INVALID; }
+    if (rel && !rel_cfg_ok(rel, c_adj, why)) { g_create_err = me + why; return DSG_ERR_INVALID; }
+    if (!std::isfinite(coef)) { g_create_err = std::string(me) + "coef is not finite"; return DSG_ERR_INVALID; }
+    const bool clip = !std::isinf(guide->clip_ratio);
+    GuideParams par{guide->w_overlap, guide->w_region, guide->w_align, guide->tau, clip ? guide->clip_ratio : 0.f, 0,
+                    guide->sel, guide->region, nullptr, nullptr, mask_node};
+    const int src = rel_params(rel, par);
+    if (!d_node || !flags || (clip && (!xhat_adj || !xhat_node || !d_adj))) { g_create_err = std::string(me) + "null argument (d_node, flags; with a clip also xhat_adj, xhat_node, d_adj)"; return DSG_ERR_INVALID; }
+    if (src == REL_DECODED && !d_adj) { g_create_err = std::string(me) + "d_adj is NULL: the decoded source reads the adjacency estimate"; return DSG_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d{B, N, c_adj, c_node};
+    GuideParams *d_par = nullptr; double *d_ref = nullptr; float *d_shift = nullptr; uint8_t *d_tab = nullptr;
+    hipError_t e = hipMalloc((void **)&d_par, sizeof(GuideParams));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_ref, sizeof(double) * (size_t)B);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_shift, sizeof(float) * (size_t)B * N * 4);
+    if (src == REL_GIVEN) par.kinds = rel->kinds;
+    if (src == REL_DECODED) {
+        if (e == hipSuccess) e = hipMalloc((void **)&d_tab, (size_t)rel->n_adj_type);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_tab, rel->pred_kind, (size_t)rel->n_adj_type, hipMemcpyHostToDevice, s);
+        par.pred_kind = d_tab;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(d_par, &par, sizeof(GuideParams), hipMemcpyHostToDevice, s);
+    bool ok = e == hipSuccess;
+    if (ok && clip) ok = launch_graph_diff_norm(CStatePtrs{xhat_adj, xhat_node}, CStatePtrs{d_adj, d_node}, flags, d_ref, d, s);
+    const BoxGuideOut out{d_shift, grad, loss, factor, norms};
+    if (ok && src != REL_NONE)
+        ok = launch_box_guide_rel(d_par, nullptr, nullptr, coef, d_adj, d_node, flags, clip ? d_ref : nullptr, false, out, kinds_out, src == REL_DECODED, d, s);
+    else if (ok) {
+        ok = launch_box_guide(d_par, nullptr, nullptr, coef, d_node, flags, clip ? d_ref : nullptr, false, out, d, s);
+        if (ok && kinds_out) e = hipMemsetAsync(kinds_out, 0, (size_t)B * N * N, s);
+    }
+    if (ok && d_guided_node) launch_box_apply(d_node, d_shift, flags, d_guided_node, d, s);
+    if (ok && e == hipSuccess && shift) e = hipMemcpyAsync(shift, d_shift, sizeof(float) * (size_t)B * N * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(s);   // par and the table are host sources of async copies: wait before they leave scope
+    (void)hipFree(d_par); (void)hipFree(d_ref); (void)hipFree(d_shift); (void)hipFree(d_tab);
+    if (e != hipSuccess || es != hipSuccess) { g_create_err = me + std::string(hipGetErrorString(e != hipSuccess ? e : es)); return DSG_ERR_HIP; }
+    if (!ok) { g_create_err = std::string(me) + "shape refused"; return DSG_ERR_INVALID; }
     return DSG_OK;
 }
 

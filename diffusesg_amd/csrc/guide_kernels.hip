@@ -11,6 +11,10 @@
 // float32 gradient is the correctly rounded one up to the last bit.  Padded nodes are chosen by a select on the flags: a NaN in a
 // padded row never reaches a sum.  Every reduction has one fixed order and uses no atomics; nothing depends on B or on the graph's
 // position in the batch.
+//
+// The relation term (dsg_sample_guided_rel) is a compile-time variant of the same body: a pairwise squared hinge on
+// box pairs whose kinds are given or decoded from the adjacency estimate of the call.  A guide without relations runs the kernel
+// without it.
 #include "kernels_common.hip.h"
 
 #include <float.h>
@@ -58,9 +62,48 @@ __device__ __forceinline__ double relu_d(double v) { return v > 0.0 ? v : 0.0; }
 // Lines of a box, in guide.py's order: 0 left, 1 centre x, 2 right, 3 top, 4 centre y, 5 bottom.  Work item (q, k) = line q of node
 // k owns dL/d line_q(k) and the part of L that is attributed to it; a thread takes items tid, tid + GUIDE_T, ...
 constexpr int GUIDE_T = 512, GUIDE_LINES = 6;   // 6 x 64 items: one round, two waves per SIMD to hide the float64 exp chains
-__global__ __launch_bounds__(GUIDE_T) void box_guide_kernel(const GuideParams *__restrict__ P, const StepRow *tab, const RunCtl *ctl, float coef_direct,
-                                                           const float *__restrict__ D_node, const uint8_t *__restrict__ flags,
-                                                           const double *__restrict__ ref_norm2, int stage1, BoxGuideOut o, int N, int Cn) {
+
+// ---- the relation term: a squared hinge per ordered pair (subject s, object o) and kind ----
+// The graph's kinds in LDS, one byte per ordered pair, 64 bytes per subject row.  An item reads its node's column (lanes = consecutive
+// objects: consecutive bytes) and its node's row (lanes = consecutive subjects: 64 bytes apart, every fourth lane on one bank); the
+// word of a row is XORed with the row's low bits, which spreads a row walk over 16 banks instead of 4 and leaves a column walk alone
+__device__ __forceinline__ int kind_at(int s, int o) { return s * GUIDE_MAX_N + ((((o >> 2) ^ (s & 15)) << 2) | (o & 3)); }
+// What pair (s, o) of kind `kind` adds to dL/d line_q of its subject (subj) or of its object, and, on the subject's side, the part of
+// the pair's loss that is attributed to line q -- every elementary term is counted once, at the subject's line in it.  m: the margin
+__device__ __forceinline__ void rel_pair(int q, int kind, bool subj, const double (*ln)[GUIDE_MAX_N], int s, int o, double m, double &grad,
+                                         double &loss) {
+    if (kind >= 1 && kind <= 4) {   // left of / right of (centre x), above / below (centre y; y grows downwards)
+        const int ax = kind <= 2 ? 1 : 4;
+        if (q != ax) return;
+        const double sg = (kind & 1) ? 1.0 : -1.0;   // h(sg (c_s - c_o) + m)
+        const double r = relu_d(sg * (ln[ax][s] - ln[ax][o]) + m);
+        grad += (subj ? sg : -sg) * 2.0 * r;
+        if (subj) loss += r * r;
+    } else if (kind == 5 || kind == 6) {   // inside: the subject within the object; contains: the object within the subject
+        if (q == 1 || q == 4) return;
+        const int in = kind == 5 ? s : o, out = kind == 5 ? o : s;
+        const bool low = q == 0 || q == 3;   // h(outer - inner) at the low sides, h(inner - outer) at the high ones
+        const double r = relu_d(low ? ln[q][out] - ln[q][in] : ln[q][in] - ln[q][out]);
+        const double d_in = low ? -2.0 * r : 2.0 * r;
+        grad += (subj == (kind == 5)) ? d_in : -d_in;
+        if (subj) loss += r * r;
+    } else if (kind == 7) {   // on: (bottom_s - top_o)^2, not hinged, + the subject's centre x within the object's extent
+        if (q == 5 && subj) { const double d = ln[5][s] - ln[3][o]; grad += 2.0 * d; loss += d * d; }
+        else if (q == 3 && !subj) grad -= 2.0 * (ln[5][s] - ln[3][o]);
+        else if (q == 1 && subj) {
+            const double a = relu_d(ln[0][o] - ln[1][s]), b = relu_d(ln[1][s] - ln[2][o]);
+            grad += 2.0 * (b - a); loss += a * a + b * b;
+        } else if (q == 0 && !subj) grad += 2.0 * relu_d(ln[0][o] - ln[1][s]);
+        else if (q == 2 && !subj) grad -= 2.0 * relu_d(ln[1][s] - ln[2][o]);
+    }
+}
+
+// REL: the variant with the relation term; without it the body is the kernel as it was, and D_adj / Ca / kinds_out are not read
+template <bool REL, bool DECODED>
+__device__ __forceinline__ void box_guide_body(const GuideParams *__restrict__ P, const StepRow *tab, const RunCtl *ctl, float coef_direct,
+                                               const float *__restrict__ D_node, const uint8_t *__restrict__ flags,
+                                               const double *__restrict__ ref_norm2, int stage1, BoxGuideOut o, int N, int Cn,
+                                               const float *__restrict__ D_adj, int Ca, uint8_t *kinds_out) {
     __shared__ double ln[GUIDE_LINES][GUIDE_MAX_N];    // the six lines of every node's box
     __shared__ double am[GUIDE_LINES][GUIDE_MAX_N];    // alignment: row maximum of -d^2 / tau
     __shared__ double as[GUIDE_LINES][GUIDE_MAX_N];    //            sum of exp(z - maximum)
@@ -85,6 +128,28 @@ __global__ __launch_bounds__(GUIDE_T) void box_guide_kernel(const GuideParams *_
         ln[3][tid] = cy - 0.5 * bh; ln[4][tid] = cy; ln[5][tid] = cy + 0.5 * bh;
     }
     __syncthreads();
+    uint8_t *kd = nullptr;
+    if constexpr (REL) {
+        __shared__ uint8_t kd_s[GUIDE_MAX_N * GUIDE_MAX_N];   // kind_at(subject, object): 4 KB
+        kd = kd_s;
+        // every thread walks the N^2 ordered pairs, the object index fastest: a wave reads consecutive floats of each channel plane.
+        // A pair that is not live (a padded row or column, the diagonal) is selected away before anything of it is read
+        const size_t nn = (size_t)N * N;
+        for (int e = tid; e < (int)nn; e += GUIDE_T) {
+            const int i = e / N, j = e % N;
+            int kind = 0;
+            if (fl[i] && fl[j] && i != j) {
+                if constexpr (DECODED) {
+                    const int pr = decode_attr(D_adj + (size_t)g * Ca * nn + e, nn, Ca, p.rel_enc, p.rel_ntype);
+                    kind = (pr >= 0 && pr < p.rel_ntype) ? p.pred_kind[pr] : 0;   // a NaN under ddpm decodes to -1: none
+                } else kind = p.kinds[(size_t)g * nn + e];
+                if (kind >= REL_KINDS) kind = 0;
+            }
+            kd[kind_at(i, j)] = (uint8_t)kind;
+            if (kinds_out) kinds_out[(size_t)g * nn + e] = (uint8_t)kind;
+        }
+        __syncthreads();
+    }
     int n_valid = 0;
     for (int j = 0; j < N; j++) n_valid += fl[j] ? 1 : 0;
     const bool align = p.a_a != 0.f && n_valid >= 2;
@@ -140,6 +205,18 @@ __global__ __launch_bounds__(GUIDE_T) void box_guide_kernel(const GuideParams *_
                 grad += (double)p.a_r * ((q == 0 || q == 3) ? -2.0 * over : 2.0 * over);
                 loss += (double)p.a_r * over * over;
             }
+            if constexpr (REL) {   // relations: node k's row (k the subject) and column (k the object), the partner ascending
+                const double m = (double)p.rel_margin;
+                double gr = 0.0, lr = 0.0;
+                for (int j = 0; j < N; j++)
+                    if (j != k && fl[j]) {
+                        const int ks = kd[kind_at(k, j)], ko = kd[kind_at(j, k)];
+                        if (ks) rel_pair(q, ks, true, ln, k, j, m, gr, lr);
+                        if (ko) rel_pair(q, ko, false, ln, j, k, m, gr, lr);
+                    }
+                grad += (double)p.a_rel * gr;
+                loss += (double)p.a_rel * lr;
+            }
         }
         gl[q][k] = grad; lp[q][k] = loss;
     }
@@ -183,6 +260,30 @@ __global__ __launch_bounds__(GUIDE_T) void box_guide_kernel(const GuideParams *_
     }
     __syncthreads();
     if (tid < N * 4) o.shift[(size_t)g * N * 4 + tid] = __fmul_rn(fac, sh[tid / 4][tid % 4]);
+}
+__global__ __launch_bounds__(GUIDE_T) void box_guide_kernel(const GuideParams *__restrict__ P, const StepRow *tab, const RunCtl *ctl, float coef_direct,
+                                                           const float *__restrict__ D_node, const uint8_t *__restrict__ flags,
+                                                           const double *__restrict__ ref_norm2, int stage1, BoxGuideOut o, int N, int Cn) {
+    box_guide_body<false, false>(P, tab, ctl, coef_direct, D_node, flags, ref_norm2, stage1, o, N, Cn, nullptr, 0, nullptr);
+}
+template <bool DECODED>
+__global__ __launch_bounds__(GUIDE_T) void box_guide_rel_kernel(const GuideParams *__restrict__ P, const StepRow *tab, const RunCtl *ctl, float coef_direct,
+                                                               const float *__restrict__ D_adj, const float *__restrict__ D_node,
+                                                               const uint8_t *__restrict__ flags, const double *__restrict__ ref_norm2, int stage1,
+                                                               BoxGuideOut o, uint8_t *kinds_out, int N, int Ca, int Cn) {
+    box_guide_body<true, DECODED>(P, tab, ctl, coef_direct, D_node, flags, ref_norm2, stage1, o, N, Cn, D_adj, Ca, kinds_out);
+}
+bool launch_box_guide_rel(const GuideParams *P, const StepRow *tab, const RunCtl *ctl, float coef_direct, const float *D_adj, const float *D_node,
+                          const uint8_t *flags, const double *ref_norm2, bool stage1, BoxGuideOut o, uint8_t *kinds_out, bool decoded, Dims d,
+                          hipStream_t s) {
+    if (d.B < 1 || d.N < 1 || d.N > GUIDE_MAX_N || d.Cn < 4 || !o.shift || (decoded && (!D_adj || d.Ca < 1))) return false;
+    if (decoded)
+        hipLaunchKernelGGL(box_guide_rel_kernel<true>, dim3((unsigned)d.B), dim3(GUIDE_T), 0, s, P, tab, ctl, coef_direct, D_adj, D_node, flags,
+                           ref_norm2, (int)stage1, o, kinds_out, d.N, d.Ca, d.Cn);
+    else
+        hipLaunchKernelGGL(box_guide_rel_kernel<false>, dim3((unsigned)d.B), dim3(GUIDE_T), 0, s, P, tab, ctl, coef_direct, D_adj, D_node, flags,
+                           ref_norm2, (int)stage1, o, kinds_out, d.N, d.Ca, d.Cn);
+    return true;
 }
 bool launch_box_guide(const GuideParams *P, const StepRow *tab, const RunCtl *ctl, float coef_direct, const float *D_node, const uint8_t *flags,
                       const double *ref_norm2, bool stage1, BoxGuideOut o, Dims d, hipStream_t s) {

@@ -355,9 +355,15 @@ void launch_multistep_tab(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const
 // sel [B,N] / region [B,N,4] (x0, y0, x1, y1): the region loss's nodes and rectangles (read only where a_r != 0); coef [T]: c_i per
 // SCHEDULE index (dsg_guide_coef); trace [L,B] or null: L(D) of every executed step's stage-1 call; mask_node [B,N,Cn] or null: the
 // known mask of a conditioned run -- the shift is zero there
+// The relation term (dsg_sample_guided_rel), read only by the kernel's relation variant: a_rel its weight, rel_margin the
+// hinge margin; rel_source REL_GIVEN: kinds [B,N,N] uint8 (subject = row, object = column); REL_DECODED: the kinds are decoded from the
+// call's adjacency estimate by decode_attr(rel_enc, rel_ntype) and looked up in pred_kind [rel_ntype] (device copy of the caller's table)
 struct GuideParams { float a_o, a_r, a_a, tau, clip_ratio; int pad; const uint8_t *sel; const float *region; const float *coef; float *trace;
-                     const uint8_t *mask_node; };
+                     const uint8_t *mask_node;
+                     float a_rel, rel_margin; int rel_source, rel_enc, rel_ntype, rel_pad; const uint8_t *kinds; const uint8_t *pred_kind; };
 constexpr int GUIDE_MAX_N = 64;
+constexpr int REL_NONE = 0, REL_GIVEN = 1, REL_DECODED = 2;   // StepPlan::rel; GuideParams::rel_source holds REL_GIVEN or REL_DECODED
+constexpr int REL_KINDS = 8;                                  // 0 none, 1 left of, 2 right of, 3 above, 4 below, 5 inside, 6 contains, 7 on
 // ||a_b - b_b||^2 over the live entries of each graph, float64, one fixed order (t_graph_dot's).  false: shape refused (N > GUIDE_MAX_N)
 bool launch_graph_diff_norm(CStatePtrs a, CStatePtrs b, const uint8_t *flags, double *out, Dims d, hipStream_t s);
 // per-graph outputs of the guide kernel; every pointer but shift may be null.  shift [B,N,4] = f_b c g as the update subtracts it,
@@ -368,6 +374,12 @@ struct BoxGuideOut { float *shift, *grad, *loss, *factor, *norms; };
 // the trace row of the executed step.  false: shape refused (N > GUIDE_MAX_N, Cn < 4)
 bool launch_box_guide(const GuideParams *P, const StepRow *tab, const RunCtl *ctl, float coef_direct, const float *D_node, const uint8_t *flags,
                       const double *ref_norm2, bool stage1, BoxGuideOut o, Dims d, hipStream_t s);
+// The same with the relation term L_rel of P (a_rel, rel_*) added: the graph's kinds sit in LDS, given or decoded from D_adj [B,Ca,N,N]
+// (rows, columns and the diagonal that are not live are never read); kinds_out [B,N,N] or null: the kinds the kernel used.  A kernel of
+// its own: launch_box_guide runs what it ran.  false: shape refused (also D_adj null with the decoded source)
+bool launch_box_guide_rel(const GuideParams *P, const StepRow *tab, const RunCtl *ctl, float coef_direct, const float *D_adj, const float *D_node,
+                          const uint8_t *flags, const double *ref_norm2, bool stage1, BoxGuideOut o, uint8_t *kinds_out, bool decoded, Dims d,
+                          hipStream_t s);
 // out = valid ? D_node - shift (box channels) : 0  -- D~ on its own, for dsg_debug_box_guide
 void launch_box_apply(const float *D_node, const float *shift, const uint8_t *flags, float *out, Dims d, hipStream_t s);
 // the update operations reading D~ = D - shift at the box channels of the node estimate (shift buffers [B,N,4] of launch_box_guide);

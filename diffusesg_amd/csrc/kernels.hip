@@ -2921,20 +2921,7 @@ void launch_rainbow_loss_backward(CStatePtrs pred, CStatePtrs tgt, const uint8_t
 //           here with the correctly rounded intrinsics; classes are tried in ascending order and the last match wins, like the
 //           reference's loop; a NaN matches nothing and stays -1, the reference's fill value
 // masked entries and the adjacency diagonal are 0; bbox = node[..., -4:]*0.5+0.5 masked (sampler_node_adj.py:201-209)
-__device__ __forceinline__ int ddpm_class(float x, int k) {
-    if (x != x) return -1;
-    x = fminf(fmaxf(x, -1.0f), 1.0f);
-    const double L = __ddiv_rn(2.0, (double)(k - 1)), half = __dmul_rn(L, 0.5);
-    const int guess = (int)rintf((x + 1.0f) * 0.5f * (float)(k - 1));
-    int out = -1;
-    for (int i = max(guess - 2, 0); i <= min(guess + 2, k - 1); i++) {
-        const double center = __dadd_rn(-1.0, __dmul_rn((double)i, L));
-        const float lo = i == 0 ? -INFINITY : __double2float_rn(__dsub_rn(center, half));
-        const float hi = i == k - 1 ? INFINITY : __double2float_rn(__dadd_rn(center, half));
-        if (x > lo && x <= hi) out = i;
-    }
-    return out;
-}
+// The rule on one attribute is decode_attr (kernels_common.hip.h), which box guidance's relation term shares
 __global__ void decode_kernel(const float *adj, const float *node, const uint8_t *flags, int enc_adj, int enc_node, int n_adj_type,
                               int n_node_type, int node_chans, int32_t *out_adj, int32_t *out_node, float *out_bbox, Dims d) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2942,30 +2929,14 @@ __global__ void decode_kernel(const float *adj, const float *node, const uint8_t
     if (idx < n_a) {
         const int j = idx % d.N, i = (idx / d.N) % d.N, b = idx / ((size_t)d.N * d.N);
         int v = 0;
-        if (flags[(size_t)b * d.N + i] && flags[(size_t)b * d.N + j] && i != j) {
-            const float *a = adj + ((size_t)b * d.Ca * d.N + i) * d.N + j;
-            const size_t cs = (size_t)d.N * d.N;
-            if (enc_adj == 0) {
-                for (int c = 0; c < d.Ca; c++) v = (v << 1) | (a[c * cs] > 0.f ? 1 : 0);
-                v = min(max(v, 0), n_adj_type - 1);
-            } else if (enc_adj == 1) {
-                for (int c = d.Ca - 1; c >= 0; c--) if (a[c * cs] > 0.f) v = c;
-            } else v = ddpm_class(a[0], n_adj_type);
-        }
+        if (flags[(size_t)b * d.N + i] && flags[(size_t)b * d.N + j] && i != j)
+            v = decode_attr(adj + ((size_t)b * d.Ca * d.N + i) * d.N + j, (size_t)d.N * d.N, d.Ca, enc_adj, n_adj_type);
         out_adj[idx] = v;
     } else if (idx < n_a + n_n) {
         const size_t m = idx - n_a;
         const bool ok = flags[m];
         int v = 0;
-        if (ok) {
-            const float *x = node + m * d.Cn;
-            if (enc_node == 0) {
-                for (int c = 0; c < node_chans; c++) v = (v << 1) | (x[c] > 0.f ? 1 : 0);
-                v = min(max(v, 0), n_node_type - 1);
-            } else if (enc_node == 1) {
-                for (int c = node_chans - 1; c >= 0; c--) if (x[c] > 0.f) v = c;
-            } else v = ddpm_class(x[0], n_node_type);
-        }
+        if (ok) v = decode_attr(node + m * d.Cn, 1, node_chans, enc_node, n_node_type);
         out_node[m] = v;
         if (out_bbox)
             for (int c = 0; c < 4; c++) out_bbox[m * 4 + c] = ok ? node[m * d.Cn + (d.Cn - 4) + c] * 0.5f + 0.5f : 0.f;

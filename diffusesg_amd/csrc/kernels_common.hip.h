@@ -170,6 +170,34 @@ __device__ __forceinline__ unsigned pack_bf16(float a, float b) {   // a in the 
 }
 __device__ __forceinline__ u32x2_c pack_bf16x4(const f32x4 v) { u32x2_c r; r[0] = pack_bf16(v[0], v[1]); r[1] = pack_bf16(v[2], v[3]); return r; }
 
+// The decode rules of the three encodings (decode_kernel in kernels.hip documents them against the reference) on ONE attribute whose
+// C channels sit `stride` floats apart: shared by the post-decode of the samples and by the relation term of box guidance
+// (guide_kernels.hip), which decodes the adjacency estimate at every call.  ddpm: -1 for a NaN, the reference's fill value
+__device__ __forceinline__ int ddpm_class(float x, int k) {
+    if (x != x) return -1;
+    x = fminf(fmaxf(x, -1.0f), 1.0f);
+    const double L = __ddiv_rn(2.0, (double)(k - 1)), half = __dmul_rn(L, 0.5);
+    const int guess = (int)rintf((x + 1.0f) * 0.5f * (float)(k - 1));
+    int out = -1;
+    for (int i = max(guess - 2, 0); i <= min(guess + 2, k - 1); i++) {
+        const double center = __dadd_rn(-1.0, __dmul_rn((double)i, L));
+        const float lo = i == 0 ? -INFINITY : __double2float_rn(__dsub_rn(center, half));
+        const float hi = i == k - 1 ? INFINITY : __double2float_rn(__dadd_rn(center, half));
+        if (x > lo && x <= hi) out = i;
+    }
+    return out;
+}
+__device__ __forceinline__ int decode_attr(const float *a, size_t stride, int C, int enc, int n_type) {
+    int v = 0;
+    if (enc == 0) {
+        for (int c = 0; c < C; c++) v = (v << 1) | (a[c * stride] > 0.f ? 1 : 0);
+        v = min(max(v, 0), n_type - 1);
+    } else if (enc == 1) {
+        for (int c = C - 1; c >= 0; c--) if (a[c * stride] > 0.f) v = c;
+    } else v = ddpm_class(a[0], n_type);
+    return v;
+}
+
 // implemented in kernels_lp.hip: the bf16-MFMA GEMMs (g.Ws3: split-bf16, fp32-accurate; g.Wb: plain bf16 operands).
 // Returns false if the arguments do not select / fit one of them (the caller then runs the fp32 kernel).
 bool launch_gemm_lp(const GemmArgs &g, hipStream_t s);

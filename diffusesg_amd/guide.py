@@ -16,7 +16,10 @@ project: what guidance does to sample quality is not validated here (DESIGN.md ย
 The losses read boxes the way `io.decode` does: the last four node channels, * 0.5 + 0.5, (cx, cy, w, h).  They are plain torch and
 run on any device.
 
-`BoxGuide` names a weighted sum of the three box losses for the guidance that runs INSIDE the library's loop
+`box_relation_loss` is the fourth: a pairwise loss on box pairs that makes them agree with the spatial relation between them, the
+pairs and their kinds given as a matrix or decoded from the adjacency estimate through a predicate -> kind table (`SpatialRules`).
+
+`BoxGuide` names a weighted sum of the box losses for the guidance that runs INSIDE the library's loop
 (`NodeAdjEDMSamplerHip.sample_guided`, `dsg_sample_guided`): the same shift with the network's Jacobian dropped from
 grad_{x_hat} L(D) = (c_skip I + c_out dF/dx_hat)^T dL/dD, evaluated by a HIP kernel with analytic gradients -- no backward, no
 training-form forward, step graphs and walks as in `sample()`.  It is an approximation of the shift above, exact only where the
@@ -133,22 +136,173 @@ def box_region_loss_nodes(sel, rects, node_flags=None):
     return loss
 
 
+# ---- spatial relations between node pairs (DESIGN.md ยง14) -----------------------------------------------------------
+# The kind of an ordered pair (subject i = the row, object j = the column of a kind matrix); DSG_REL_* of include/dsg.h
+REL_NONE, REL_LEFT_OF, REL_RIGHT_OF, REL_ABOVE, REL_BELOW, REL_INSIDE, REL_CONTAINS, REL_ON = range(8)
+REL_KINDS = 8
+
+
+class SpatialRules(object):
+    """A predicate -> kind table for relation guidance whose kinds are DECODED from the adjacency estimate at every preconditioned call:
+    pred_kind [n_adj_type] integers in 0..7 (the REL_* constants), `encoding` the run's edge encoding ('bits' | 'one_hot' | 'ddpm').
+    Which predicate means what is the caller's knowledge of the dataset's vocabulary; no table ships with the project."""
+
+    def __init__(self, pred_kind, n_adj_type, encoding="bits"):
+        if encoding not in _lib.ENCODINGS:
+            raise ValueError(f"SpatialRules: encoding should be 'bits', 'one_hot' or 'ddpm', got {encoding!r}")
+        self.n_adj_type, self.encoding = int(n_adj_type), encoding
+        if self.n_adj_type < 1:
+            raise ValueError(f"SpatialRules: n_adj_type = {n_adj_type} must be >= 1")
+        t = np.asarray(pred_kind.detach().cpu().numpy() if isinstance(pred_kind, torch.Tensor) else pred_kind)
+        if t.shape != (self.n_adj_type,) or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"SpatialRules: pred_kind must hold {self.n_adj_type} integers (one kind per predicate), got shape {t.shape} {t.dtype}")
+        if t.min() < 0 or t.max() >= REL_KINDS:
+            raise ValueError(f"SpatialRules: pred_kind holds a kind outside 0..{REL_KINDS - 1}")
+        self.pred_kind = np.ascontiguousarray(t, dtype=np.uint8)
+
+
+def _live_pairs(node_flags, B, n, device):
+    """[B, N, N] bool: both nodes valid, off the diagonal"""
+    off = ~torch.eye(n, dtype=torch.bool, device=device)
+    if node_flags is None:
+        return off[None].expand(B, n, n)
+    f = node_flags.to(device=device) != 0
+    return off[None] & f[:, :, None] & f[:, None, :]
+
+
+def _decode_predicates(D_adj, rules):
+    """[B, N, N] int64 predicates of the adjacency estimate [B, C_adj, N, N] ([B, N, N]: one channel) by `dsg_decode`'s rule for the
+    encoding, evaluated on the float32 value as the library holds it; -1 where the ddpm rule meets a NaN"""
+    a = D_adj.detach().to(torch.float32)
+    if a.dim() == 3:
+        a = a[:, None]
+    C, k = a.shape[1], rules.n_adj_type
+    if rules.encoding == "bits":
+        if C > 30 or (1 << C) < k:
+            raise ValueError(f"decoded relations: {k} predicates in bits do not fit {C} adjacency channels")
+        w = torch.tensor([1 << (C - 1 - c) for c in range(C)], dtype=torch.int64, device=a.device)
+        return ((a > 0).to(torch.int64) * w[None, :, None, None]).sum(1).clamp(max=k - 1)   # MSB first, clamped
+    if rules.encoding == "one_hot":
+        if C != k:
+            raise ValueError(f"decoded relations: one_hot needs one adjacency channel per predicate, got {C} channels for {k}")
+        return torch.argmax((a > 0).to(torch.int64), dim=1)   # the first positive channel, 0 when none is
+    if C != 1:
+        raise ValueError(f"decoded relations: ddpm needs one adjacency channel, got {C}")
+    x = a[:, 0].clamp(-1.0, 1.0)
+    out = torch.full(x.shape, -1, dtype=torch.int64, device=a.device)
+    L = 2.0 / (k - 1) if k > 1 else float("inf")   # Python floats: double, like the reference's
+    for i in range(k):
+        center = -1.0 + i * L if k > 1 else -1.0
+        lo = -float("inf") if i == 0 else float(np.float32(center - L * 0.5))
+        hi = float("inf") if i == k - 1 else float(np.float32(center + L * 0.5))
+        out = torch.where((x > lo) & (x <= hi), torch.full_like(out, i), out)   # ascending, the last match wins; NaN matches nothing
+    return out
+
+
+def relation_kinds_from_graph(q_adj, node_flags, pred_kind):
+    """uint8 [B, N, N] kinds of an integer graph: pred_kind[q_adj] at live pairs (both nodes valid, off the diagonal), REL_NONE
+    elsewhere and where the predicate is outside the table.  pred_kind: a sequence of kinds, or a `SpatialRules`."""
+    table = pred_kind.pred_kind if isinstance(pred_kind, SpatialRules) else np.asarray(pred_kind)
+    q = torch.as_tensor(q_adj)
+    if q.dim() != 3 or q.shape[1] != q.shape[2]:
+        raise ValueError(f"relation_kinds_from_graph: q_adj must be [B, N, N], got {tuple(q.shape)}")
+    t = torch.as_tensor(np.ascontiguousarray(table, dtype=np.uint8), device=q.device)
+    q = q.to(torch.int64)
+    ok = (q >= 0) & (q < t.numel()) & _live_pairs(node_flags, q.shape[0], q.shape[1], q.device)
+    return torch.where(ok, t[q.clamp(0, t.numel() - 1)], torch.zeros((), dtype=torch.uint8, device=q.device))
+
+
+def decoded_relation_kinds(D_adj, node_flags, rules):
+    """uint8 [B, N, N]: the kinds the guide kernel's decoded source uses on this adjacency estimate -- every live entry decoded to a
+    predicate by the rule of `rules.encoding`, then `rules.pred_kind[predicate]`.  No gradient: the kinds are constants of the call."""
+    if not isinstance(rules, SpatialRules):
+        raise TypeError("decoded_relation_kinds needs a SpatialRules")
+    with torch.no_grad():
+        return relation_kinds_from_graph(_decode_predicates(D_adj, rules), node_flags, rules)
+
+
+def _check_kinds(kinds, who):
+    k = torch.as_tensor(kinds)
+    if k.dim() != 3 or k.shape[1] != k.shape[2] or k.dtype.is_floating_point or k.dtype == torch.bool:
+        raise ValueError(f"{who}: kinds must be an integer tensor [B, N, N], got {tuple(k.shape)} {k.dtype}")
+    if k.numel() and (int(k.min()) < 0 or int(k.max()) >= REL_KINDS):
+        raise ValueError(f"{who}: kinds holds an entry outside 0..{REL_KINDS - 1}")
+    return k
+
+
+def box_relation_loss(kinds, node_flags=None, margin=0.0):
+    """Agreement of box pairs with the spatial relation between them: the sum over graphs and ORDERED pairs (subject i, object j),
+    i != j, of a squared hinge h(v) = relu(v)^2 chosen by kinds[b, i, j] (boxes (cx, cy, w, h), lines l, r, t, bt; y grows downwards):
+        LEFT_OF h(cx_i - cx_j + m)   RIGHT_OF h(cx_j - cx_i + m)   ABOVE h(cy_i - cy_j + m)   BELOW h(cy_j - cy_i + m)
+        INSIDE  h(l_j - l_i) + h(r_i - r_j) + h(t_j - t_i) + h(bt_i - bt_j)       CONTAINS: INSIDE with i and j exchanged
+        ON      (bt_i - t_j)^2 + h(l_j - cx_i) + h(cx_i - r_j)
+    kinds: an integer tensor [B, N, N] of REL_* constants, or a `SpatialRules` -- then the kinds are recomputed from D_adj at every
+    call (`decoded_relation_kinds`), under no_grad.  margin m >= 0; `node_flags` [B, N] (optional): padded nodes take no part."""
+    m = float(margin)
+    if not (m >= 0 and np.isfinite(m)):
+        raise ValueError(f"box_relation_loss: margin = {margin} must be >= 0 and finite")
+    rules = kinds if isinstance(kinds, SpatialRules) else None
+    given = None if rules is not None else _check_kinds(kinds, "box_relation_loss")
+
+    def loss(D_adj, D_node):
+        b = _boxes(D_node)
+        B, n = b.shape[:2]
+        if rules is not None:
+            if D_adj is None:
+                raise ValueError("box_relation_loss: decoded kinds need D_adj")
+            K = decoded_relation_kinds(D_adj, node_flags, rules).to(b.device)
+        else:
+            K = given.to(b.device)
+        if tuple(K.shape) != (B, n, n):
+            raise ValueError(f"box_relation_loss: kinds {tuple(K.shape)} do not fit nodes {(B, n)}")
+        K = torch.where(_live_pairs(node_flags, B, n, b.device), K.to(torch.int64), torch.zeros((), dtype=torch.int64, device=b.device))
+        l, t, r, bt = _corners(b)
+        cx, cy = b[..., 0], b[..., 1]
+        S, O = (lambda v: v[:, :, None]), (lambda v: v[:, None, :])   # the subject's / the object's line on the [B, i, j] grid
+        h = lambda v: torch.relu(v) ** 2
+        inside = lambda I, J: h(J(l) - I(l)) + h(I(r) - J(r)) + h(J(t) - I(t)) + h(I(bt) - J(bt))
+        terms = {REL_LEFT_OF: lambda: h(S(cx) - O(cx) + m), REL_RIGHT_OF: lambda: h(O(cx) - S(cx) + m),
+                 REL_ABOVE: lambda: h(S(cy) - O(cy) + m), REL_BELOW: lambda: h(O(cy) - S(cy) + m),
+                 REL_INSIDE: lambda: inside(S, O), REL_CONTAINS: lambda: inside(O, S),
+                 REL_ON: lambda: (S(bt) - O(t)) ** 2 + h(O(l) - S(cx)) + h(S(cx) - O(r))}
+        total = b.sum() * 0.0
+        for kind, term in terms.items():
+            on = K == kind
+            if bool(on.any()):
+                v = term()
+                total = total + torch.where(on, v, torch.zeros_like(v)).sum()
+        return total
+    return loss
+
+
 class BoxGuide(object):
-    """L = overlap * L_overlap + region_weight * L_region + align * L_align on the boxes of the node estimate, always with the node
-    flags (padded nodes take no part): the loss of in-loop guidance (`NodeAdjEDMSamplerHip.sample_guided`).
+    """L = overlap * L_overlap + region_weight * L_region + align * L_align + relation_weight * L_rel on the boxes of the node estimate,
+    always with the node flags (padded nodes take no part): the loss of in-loop guidance (`NodeAdjEDMSamplerHip.sample_guided`).
       overlap, align: weights of `box_overlap_loss` / `box_alignment_loss(tau=tau)`; 0 = the term is not evaluated.
       region: None, or (sel [B, N], rects [B, N, 4]) -- one rectangle (x0, y0, x1, y1) per selected node, `box_region_loss_nodes` --
               or (node_idx, rect) -- `box_region_loss`'s form: the same rectangle for that node (or those nodes) in every graph.
-      region_weight: weight of the region term where `region` is given."""
+      region_weight: weight of the region term where `region` is given.
+      relations: None, an integer tensor [B, N, N] of REL_* kinds (subject = row, object = column), or a `SpatialRules` -- the kinds are
+              then decoded on the device from the adjacency estimate of every call; `box_relation_loss` with `relation_margin`.
+      relation_weight: weight of the relation term where `relations` is given."""
 
-    def __init__(self, overlap=0.0, region=None, align=0.0, tau=0.05, region_weight=1.0):
+    def __init__(self, overlap=0.0, region=None, align=0.0, tau=0.05, region_weight=1.0, relations=None, relation_weight=1.0,
+                 relation_margin=0.0):
         self.overlap, self.align, self.tau = float(overlap), float(align), float(tau)
         self.region_weight = float(region_weight) if region is not None else 0.0
-        for name, v in (("overlap", self.overlap), ("align", self.align), ("region_weight", self.region_weight), ("tau", self.tau)):
+        self.relation_weight = float(relation_weight) if relations is not None else 0.0
+        self.relation_margin = float(relation_margin)
+        for name, v in (("overlap", self.overlap), ("align", self.align), ("region_weight", self.region_weight), ("tau", self.tau),
+                        ("relation_weight", self.relation_weight)):
             if not np.isfinite(v):
                 raise ValueError(f"BoxGuide: {name} = {v} is not finite")
         if self.align != 0 and not self.tau > 0:
             raise ValueError("BoxGuide: tau must be positive")
+        if not (self.relation_margin >= 0 and np.isfinite(self.relation_margin)):
+            raise ValueError(f"BoxGuide: relation_margin = {relation_margin} must be >= 0 and finite")
+        self.relations = None
+        if relations is not None:
+            self.relations = relations if isinstance(relations, SpatialRules) else _check_kinds(relations, "BoxGuide")
         self.region = None
         if region is not None:
             if len(region) != 2:
@@ -192,6 +346,23 @@ class BoxGuide(object):
                              None if reg is None else reg[0].data_ptr(), None if reg is None else reg[1].data_ptr(), None)
         return g, reg
 
+    def relation_descriptor(self, B, n, device, c_adj):
+        """(`lib.DsgRelCfg`, what it points at -- keep it alive over the call) of the relation term, (None, None) without one;
+        ValueError on kinds that do not fit the batch or a table that does not fit the adjacency channels."""
+        if self.relations is None:
+            return None, None
+        if isinstance(self.relations, SpatialRules):
+            r = self.relations
+            C, k = int(c_adj), r.n_adj_type
+            if (r.encoding == "one_hot" and C != k) or (r.encoding == "ddpm" and C != 1) or (r.encoding == "bits" and (C > 30 or (1 << C) < k)):
+                raise ValueError(f"BoxGuide: relations in {r.encoding} with {k} predicates do not fit {C} adjacency channels")
+            return _lib.DsgRelCfg(self.relation_weight, self.relation_margin, _lib.REL_DECODED, _lib.ENCODINGS[r.encoding], k, 0, None,
+                                  r.pred_kind.ctypes.data), r.pred_kind
+        if tuple(self.relations.shape) != (B, n, n):
+            raise ValueError(f"BoxGuide: relations {tuple(self.relations.shape)}, expected ({B}, {n}, {n})")
+        kd = self.relations.to(device=device, dtype=torch.uint8).contiguous()
+        return _lib.DsgRelCfg(self.relation_weight, self.relation_margin, _lib.REL_GIVEN, 0, 0, 0, kd.data_ptr(), None), kd
+
     def torch_loss(self, node_flags):
         """The same loss as a `guide.py` closure loss(D_adj, D_node) -> scalar, for `guided_sample` and the tests."""
         terms = []
@@ -204,6 +375,8 @@ class BoxGuide(object):
                 terms.append((self.region_weight, box_region_loss(self.region[1], self.region[2], node_flags)))
         if self.align != 0:
             terms.append((self.align, box_alignment_loss(node_flags, self.tau)))
+        if self.relations is not None and self.relation_weight != 0:
+            terms.append((self.relation_weight, box_relation_loss(self.relations, node_flags, self.relation_margin)))
 
         def loss(D_adj, D_node):
             total = _boxes(D_node).sum() * 0.0

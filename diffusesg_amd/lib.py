@@ -27,6 +27,7 @@ EXPORTS = [
     "dsg_ode_run", "dsg_ode_evals", "dsg_debug_graph_dot",
     "dsg_debug_poison",
     "dsg_guide_coef", "dsg_sample_guided", "dsg_debug_box_guide",
+    "dsg_sample_guided_rel", "dsg_debug_box_guide_rel",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -73,6 +74,16 @@ class DsgGuideCfg(C.Structure):
 
 
 GUIDE_CLIP_NONE = float("inf")   # DSG_GUIDE_CLIP_NONE: unclipped, no norm pass
+
+
+class DsgRelCfg(C.Structure):
+    """dsg_rel_cfg of include/dsg.h (dsg_sample_guided_rel, dsg_debug_box_guide_rel): kinds a device pointer, pred_kind a host pointer"""
+    _fields_ = [("w_rel", C.c_float), ("margin", C.c_float), ("source", C.c_int32), ("encoding", C.c_int32), ("n_adj_type", C.c_int32),
+                ("reserved", C.c_int32), ("kinds", C.c_void_p), ("pred_kind", C.c_void_p)]
+
+
+REL_GIVEN, REL_DECODED = 0, 1                                  # DSG_REL_GIVEN / DSG_REL_DECODED
+REL_NONE, REL_LEFT_OF, REL_RIGHT_OF, REL_ABOVE, REL_BELOW, REL_INSIDE, REL_CONTAINS, REL_ON = range(8)   # DSG_REL_* kinds
 
 ODE_ENCODE, ODE_DECODE = 0, 1                                  # DSG_ODE_ENCODE / DSG_ODE_DECODE
 ODE_PROBES = {"none": 0, "rademacher": 1, "gaussian": 2}       # DSG_ODE_PROBE_*
@@ -168,6 +179,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_guide_coef.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, i32]
     L.dsg_guide_coef.restype = i32
     L.dsg_debug_box_guide.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DsgGuideCfg), C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    L.dsg_sample_guided_rel.argtypes = L.dsg_sample_guided.argtypes + [C.POINTER(DsgRelCfg)]
+    L.dsg_debug_box_guide_rel.argtypes = L.dsg_debug_box_guide.argtypes + [C.POINTER(DsgRelCfg), vp]
     L.dsg_walk_steps.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, vp, i32]
     L.dsg_walk_steps.restype = i32
     L.dsg_multistep_coef.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, i32]

@@ -279,8 +279,8 @@ class NodeAdjEDMSamplerHip(object):
             D~ = D - f_b c_i dL/dD,   c_i = w_i t^2 c_skip(t),
         the guidance of `guide.guided_sample` with the network's Jacobian dropped: an approximation (exact where that Jacobian
         vanishes) that costs one small kernel per call, no backward, and keeps step graphs, walks, known entries and per-graph seeds.
-        guide: a `diffusesg_amd.guide.BoxGuide`; scale: w, or one w_i per schedule index; clip_ratio = r: per graph the shift never
-        exceeds r ||x_hat_b - D_b||, None: unclipped.  known = (known_adjs, known_nodes, known_adj_mask, known_node_mask) as in
+        guide: a `diffusesg_amd.guide.BoxGuide` (with `relations=`: the pairwise relation term, `dsg_sample_guided_rel`, DESIGN.md §14);
+        scale: w, or one w_i per schedule index; clip_ratio = r: per graph the shift never exceeds r ||x_hat_b - D_b||, None: unclipped.  known = (known_adjs, known_nodes, known_adj_mask, known_node_mask) as in
         `sample_known` (known entries win and stay bit-exact); resample / resample_range / start_step / base_*: its walk;
         graph_seeds / coin_seed and everything after them: as in `sample()` (sanity_check_gt_*: the sanity-check mode, the guide then
         runs on the ground truth; not with known or graph_seeds).  Channel counts default to the network's.
@@ -426,16 +426,21 @@ class NodeAdjEDMSamplerHip(object):
             gw = np.ascontiguousarray(gw, dtype=np.float32)
             gcfg, g_keep = bg.descriptor(B, n, dev, clip_ratio)   # shapes refused here, before anything is launched
             gcfg.weights = gw.ctypes.data
+            rcfg, r_keep = bg.relation_descriptor(B, n, dev, cfg.c_adj)   # ... and the relation term's kinds / table
             if want_trace:
                 trace = torch.empty((L, B), dtype=torch.float32, device=dev)
             ka, kn, ma, mn = (ka, kn, ma, mn) if known is not None else (None,) * 4
             key = seed_v if gs is None else (self.seed if coin_seed is None else int(coin_seed))
-            h.check(h.L.dsg_sample_guided(h.raw, C.byref(scfg), C.byref(wcfg) if wcfg is not None else None, B, p(fl),
-                                          C.c_void_p(0 if gs is None else gs.ctypes.data), C.c_uint64(key & (2 ** 64 - 1)),
-                                          p(ia), p(inn), p(ba), p(bn), p(na), p(nn_), C.c_void_p(coins.ctypes.data),
-                                          p(ka), p(kn), p(ma), p(mn), *snap_args, C.byref(gcfg), p(ga), p(gn), p(trace),
-                                          p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample_guided")
-            del g_keep
+            g_args = (h.raw, C.byref(scfg), C.byref(wcfg) if wcfg is not None else None, B, p(fl),
+                      C.c_void_p(0 if gs is None else gs.ctypes.data), C.c_uint64(key & (2 ** 64 - 1)),
+                      p(ia), p(inn), p(ba), p(bn), p(na), p(nn_), C.c_void_p(coins.ctypes.data),
+                      p(ka), p(kn), p(ma), p(mn), *snap_args, C.byref(gcfg), p(ga), p(gn), p(trace),
+                      p(oa), p(on), C.byref(stats), C.c_void_p(st))
+            if bg.relations is None:   # a guide without relations makes the call it made
+                h.check(h.L.dsg_sample_guided(*g_args), "dsg_sample_guided")
+            else:
+                h.check(h.L.dsg_sample_guided_rel(*g_args, None if rcfg is None else C.byref(rcfg)), "dsg_sample_guided_rel")
+            del g_keep, r_keep
         elif gs is not None:
             ka, kn, ma, mn = (ka, kn, ma, mn) if known is not None else (None,) * 4
             coin_seed_v = self.seed if coin_seed is None else int(coin_seed)   # (the coins are always handed over: not read by the library)

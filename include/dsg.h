@@ -41,7 +41,8 @@ extern "C" {
  * header would otherwise pass shifted arguments without any error.  History: 1-3 = rounds 1-3 (unversioned), 4 = round 4
  * (dsg_decode with an encoding argument, dsg_abi_version, dsg_last_error(NULL)).  dsg_sample_seeded, dsg_gen_noise_seeded and the option
  * "batch_invariant" were added without touching an existing argument list: still 4; so were the dsg_debug_*_f32 test hooks,
- * dsg_ode_run / dsg_ode_evals / dsg_debug_graph_dot, and dsg_guide_cfg / dsg_sample_guided / dsg_guide_coef / dsg_debug_box_guide. */
+ * dsg_ode_run / dsg_ode_evals / dsg_debug_graph_dot, and dsg_guide_cfg / dsg_sample_guided / dsg_guide_coef / dsg_debug_box_guide,
+ * and dsg_rel_cfg / dsg_sample_guided_rel / dsg_debug_box_guide_rel. */
 #define DSG_ABI_VERSION 4
 
 typedef enum {
@@ -342,6 +343,66 @@ int dsg_debug_box_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, con
                         const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_node,
                         const dsg_guide_cfg *guide, float coef, float *loss, float *grad, float *shift, float *factor, float *norms,
                         float *d_guided_node, void *stream);
+
+/* Box guidance: spatial relations between node pairs.  A fourth loss on the boxes above, L = ... + w_rel L_rel, read from
+ * ordered node pairs: entry (i, j) of a kind matrix has SUBJECT i (the row) and OBJECT j (the column).  With the lines of a box in
+ * guide.py's order (l, cx, r, t, cy, bt; y grows downwards), h(v) = relu(v)^2 and m = margin >= 0, the pair adds
+ *     0 none          0                         1 LEFT_OF   h(cx_i - cx_j + m)       2 RIGHT_OF  h(cx_j - cx_i + m)
+ *     3 ABOVE         h(cy_i - cy_j + m)        4 BELOW     h(cy_j - cy_i + m)
+ *     5 INSIDE        h(l_j - l_i) + h(r_i - r_j) + h(t_j - t_i) + h(bt_i - bt_j)         6 CONTAINS  INSIDE with i and j exchanged
+ *     7 ON            (bt_i - t_j)^2 + h(l_j - cx_i) + h(cx_i - r_j)
+ * and L_rel is the sum over graphs and ordered pairs i != j of valid nodes; (i, j) and (j, i) count on their own, kinds above 7 are
+ * none.  h is C1: a pair exactly on a hinge adds exactly 0 to loss and gradient, and no tie convention is needed.  Gradients are
+ * closed forms in float64, rounded once; fixed-order sums, no atomics, nothing depends on B.
+ *   source DSG_REL_GIVEN: kinds [B,N,N] uint8, DEVICE, copied into workspace memory like sel / region.
+ *   source DSG_REL_DECODED: at every preconditioned call entry (i, j) of the D_adj the guide is handed (after the valid mask and the
+ *     known select; gt in the sanity-check mode) is decoded to an integer predicate by dsg_decode's rule for `encoding` (DSG_ENC_*) and
+ *     `n_adj_type`, and its kind is pred_kind[predicate]; pred_kind [n_adj_type] uint8, HOST, copied once per run.  A NaN under
+ *     DSG_ENC_DDPM decodes to none.  Rows, columns and the diagonal that are not live are never read.  The kinds are constants of the
+ *     call: no gradient flows through the decode thresholds, and g stays zero outside the box channels. */
+#define DSG_REL_GIVEN 0
+#define DSG_REL_DECODED 1
+#define DSG_REL_NONE 0
+#define DSG_REL_LEFT_OF 1
+#define DSG_REL_RIGHT_OF 2
+#define DSG_REL_ABOVE 3
+#define DSG_REL_BELOW 4
+#define DSG_REL_INSIDE 5
+#define DSG_REL_CONTAINS 6
+#define DSG_REL_ON 7
+typedef struct dsg_rel_cfg {
+    float w_rel, margin;
+    int32_t source;            /* DSG_REL_GIVEN 0, DSG_REL_DECODED 1 */
+    int32_t encoding;          /* DSG_ENC_* of the adjacency (decoded source) */
+    int32_t n_adj_type;        /* number of predicates = entries of pred_kind (decoded source) */
+    int32_t reserved;          /* 0 */
+    const uint8_t *kinds;      /* DEVICE [B,N,N] (given source) */
+    const uint8_t *pred_kind;  /* HOST [n_adj_type], entries 0..7 (decoded source) */
+} dsg_rel_cfg;
+
+/* dsg_sample_guided with the relation term.  rel == NULL or rel->w_rel == 0: dsg_sample_guided itself -- the same plan keys, the same
+ * captured bodies, the same bits.  Otherwise the guide kernel's relation variant runs behind every preconditioned call, in step bodies
+ * of their own.  Refused with DSG_ERR_INVALID before anything is launched, the message naming the argument: a non-finite w_rel, a
+ * negative or NaN margin, a source outside {0, 1}, kinds == NULL with the given source and w_rel != 0; with the decoded source
+ * pred_kind == NULL, n_adj_type < 1, a table entry above 7, an unknown encoding or one that does not fit the adjacency channels (as
+ * dsg_decode); and everything dsg_sample_guided refuses. */
+int dsg_sample_guided_rel(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk /* NULL: trivial walk */,
+                          int32_t B, const uint8_t *flags,
+                          const uint64_t *graph_seeds /* host, [B], or NULL */, uint64_t coin_seed,
+                          const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                          const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                          const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                          const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                          const dsg_guide_cfg *guide, const float *gt_adj, const float *gt_node, float *loss_trace,
+                          float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream, const dsg_rel_cfg *rel);
+
+/* dsg_debug_box_guide with the relation term: `rel` as above (NULL or w_rel == 0: the kernel without it), and kinds_out [B,N,N] uint8
+ * (DEVICE, may be NULL): the kinds the kernel used, 0 at pairs that are not live (all 0 where the relation variant did not run).
+ * d_adj is required with the decoded source; entries of padded rows and columns and of the diagonal are never read. */
+int dsg_debug_box_guide_rel(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,
+                            const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_node,
+                            const dsg_guide_cfg *guide, float coef, float *loss, float *grad, float *shift, float *factor, float *norms,
+                            float *d_guided_node, void *stream, const dsg_rel_cfg *rel, uint8_t *kinds_out);
 
 /* sigma_steps (fp64, edm.py:84-88) and the fp32 per-step scalars the loop uses; out arrays of
  * length num_steps.  Host-only helper, exposed so bindings/tests can inspect the schedule. */
