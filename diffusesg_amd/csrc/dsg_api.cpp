@@ -134,6 +134,9 @@ struct Workspace {
     // what this workspace's last forward did at level k: -1 no deduplication, 0 the copy moved rows of x (levels >= 1: and of the skip) only,
     // 1 also their (sum, sumsq) pairs in `stats` (the block left them for its consumer); dsg_debug_dedup_lists / dsg_debug_dedup_level_lists
     int dd_fwd[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1};
+    // option "dedup_qkv": did the last forward launch the level's second block in its switched form (the fused launch plus the projection
+    // over qk_runs and the map attention, the device picking one by qk_split_rule)?  dsg_debug_dedup_qkv_lists
+    bool qk_fwd[1 + NEED_MAX_DD_UP] = {false, false, false, false};
     // what stage_flags last wrote (dedup_stage_mode below): the DedupMode of the lists, the levels whose fill is trimmed (bit k) and the
     // chain depth the trimming was worked out for -- forward_fixed checks that it reaches exactly that depth
     int dd_mode = DD_OFF, dd_trim = 0, dd_depth = 0;
@@ -202,6 +205,7 @@ struct dsg_handle_s {
     bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_opts_on below)
     int opt_dedup_batch = 1;          // ... and once for the whole batch in the sampler: 0 never, 1 from DEDUP_BATCH_MIN graphs, 2 always (dedup_stage_mode below)
     int opt_dedup_levels = 0;         // how many levels may do so: 0 every qualifying one, 1 the finest only, ... (dedup_levels below)
+    int opt_dedup_qkv = 1;            // (2, measurement hook: the split form wherever the lists exist, whatever their share: qk_rule_rows)  the shifted block behind a deduplicated first block projects QKV of the copied pure-window rows once (qkv_dedup_at below)
     bool opt_dedup_table = true;      // where the batch shares one representative: take it from a per-step table built ahead of the loop (build_pure_table below)
     PrunePlan prune;
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
@@ -209,6 +213,11 @@ struct dsg_handle_s {
     int n_cu = 0;                     // multiprocessor count of the device (read once in dsg_create): the list GEMM's form rule (gemm_thin_rule)
     int prof_next_thin_n = 0;         // N of the next profiled launch if it is a list GEMM with a thin form, else 0
     std::vector<int> prof_thin_n;
+    // the next profiled launch belongs to a block with the "dedup_qkv" form switch: the qk_runs list whose count decides, the rows M of the
+    // rule, and the form the launch is part of (1 fused, 2 split); list -1: no switch
+    struct ProfQk { int list = -1, M = 0, role = 0; };
+    ProfQk prof_next_qk;
+    std::vector<ProfQk> prof_qk;
     bool opt_fused_merge = true;      // PatchMerging: gather + LayerNorm(4C) inside the reduction GEMM's A path (no merge_ln kernel)
     bool opt_batch_invariant = false; // every choice of the plan is a function of the geometry and the other options, never of B
     bool opt_loop_graph = true;       // capture whole step bodies of the reverse loop (0: only the network forward is a graph)
@@ -294,8 +303,10 @@ struct ProfScope {
     dsg_handle h; hipStream_t s;
     ProfScope(dsg_handle h_, hipStream_t s_, int kind, double flops, const char *tag = nullptr) : h(h_), s(s_) {
         const int need_list = h->prof_next_list, thin_n = h->prof_next_thin_n;
+        const auto qk = h->prof_next_qk;
         h->prof_next_list = -1;
         h->prof_next_thin_n = 0;
+        h->prof_next_qk = decltype(h->prof_next_qk)();
         if (!h->prof_on) return;
         while (h->prof_events.size() < h->prof_used + 2) {
             hipEvent_t e;
@@ -305,6 +316,7 @@ struct ProfScope {
         h->prof_kind.push_back(kind);
         h->prof_list.push_back(need_list);
         h->prof_thin_n.push_back(thin_n);
+        h->prof_qk.push_back(qk);
         h->prof_flops.push_back(flops);
         h->prof_tag.push_back(tag ? tag : "");
         (void)hipEventRecord(h->prof_events[h->prof_used], s);
@@ -746,6 +758,7 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     if (getenv("DSG_DEDUP_BATCH")) h->opt_dedup_batch = std::min(2, std::max(0, atoi(getenv("DSG_DEDUP_BATCH"))));
     if (getenv("DSG_DEDUP_LEVELS")) h->opt_dedup_levels = std::max(0, atoi(getenv("DSG_DEDUP_LEVELS")));
     h->opt_dedup_table = env_on("DSG_DEDUP_TABLE", true);
+    h->opt_dedup_qkv = env_on("DSG_DEDUP_QKV", true) ? 1 : 0;
     if (getenv("DSG_FUSED_MLP_MAXC")) h->opt_fused_mlp_maxc = atoi(getenv("DSG_FUSED_MLP_MAXC"));
     h->opt_gemm_bf16 = env_on("DSG_GEMM_BF16", false);
     h->opt_bf16_pipe = env_on("DSG_BF16_PIPE", true);
@@ -1196,6 +1209,15 @@ void build_prune_plan(dsg_handle h) {
         np.dd_runs[k] = new_list(res * res / 8);
         np.dd_copy[k] = new_list((res / 8) * (res / 8));
         np.dd_n = k + 1;
+        // option "dedup_qkv": a second, shifted block on the level's own 8 x 8 windows (it ends the chain) reads rows that the fill has
+        // copied; its QKV projection gets the list of distinct rows and the window map, where the plan has room for the two
+        if (h->down[k].size() >= 2 && np.n_lists + 2 <= NEED_MAX_LISTS) {
+            const BlockPlan &b1 = h->down[k][1];
+            if (b1.shift > 0 && b1.ws == 8 && b1.res == res && res >= 16) {
+                np.qk_runs[k] = new_list(res * res / 8);
+                np.qk_src[k] = new_list((res / 8) * (res / 8));
+            }
+        }
     }
     P = Q;
     P.np = np;
@@ -1278,6 +1300,17 @@ int dedup_chain_depth(dsg_handle h, const Workspace *w) {
     while (depth < n && merge_fused_at(h, w->B, depth - 1)) depth++;   // (the plan has made sure of the blocks: build_prune_plan)
     return depth;
 }
+// Option "dedup_qkv": block j of level l projects QKV over the distinct rows only (run_block, the split form) when it stands directly
+// behind the deduplicated first block of a level of this forward's chain -- the fill has just left every pure window of a content class
+// with equal rows and statistics --, is shifted (an unshifted block would have been deduplicated whole) and takes the fused QKV +
+// attention GEMM on 8 x 8 windows in fp32.  Which form runs is then the device's choice from the staged lists (kernels.h: qk_split_rule).
+// the rows the rule compares the listed rows with: the launch's M; "dedup_qkv" 2 (measurement of the rule's bound) takes the split form always
+int qk_rule_rows(dsg_handle h, int M) { return h->opt_dedup_qkv == 2 ? 0x7fffffff : M; }
+bool qkv_dedup_at(dsg_handle h, const Workspace *w, int l, int j, int depth) {
+    if (j != 1 || l >= depth || l > NEED_MAX_DD_UP || !h->opt_dedup_qkv || !dedup_opts_on(h) || w->need.qk_runs[l] < 0 || w->need.qk_src[l] < 0) return false;
+    const BlockPlan &b = h->down[l][1];
+    return b.shift > 0 && b.ws == 8 && !(h->opt_fused_attn && b.wqp) && h->opt_fused_qkv_attn && !h->opt_gemm_bf16 && !h->opt_gemm_split;
+}
 constexpr int DEDUP_BATCH_MIN = 16;
 int dedup_stage_mode(dsg_handle h, const Workspace *w, bool zero_padded, bool uniform_row, int *trim, int *depth, bool table = false) {
     *trim = 0; *depth = 0;
@@ -1296,7 +1329,7 @@ NeedRef need_ref(dsg_handle h, const Workspace *w, int id) {
     if (id < 0 || !prune_on(h, w)) return NeedRef();
     return NeedRef{w->need_lists + w->need.list_off[id], w->need_cnt + id, id};
 }
-struct BlockNeed { NeedRef rows, wins; };
+struct BlockNeed { NeedRef rows, wins; NeedRef qk_runs = NeedRef(), qk_src = NeedRef(); };   // qk_*: qkv_dedup_at
 // attach "modulate for block nb + row statistics" to the GEMM that writes nb's input (M rows = B * T tokens of nb's level)
 void attach_premod(dsg_handle h, Workspace *w, GemmArgs &g, const BlockPlan *nb) {
     if (!wants_premod(h, nb)) return;
@@ -1343,13 +1376,34 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
             g.attn_bias = b.biasT; g.wg = wg; g.attn_batch = B; g.C = w->att; g.ldc = C;
             g.row_list = need.wins.list; g.row_cnt = need.wins.cnt;   // (a window list here)
             h->prof_next_list = need.wins.id;
+            g.qk_cnt = need.qk_runs.cnt; g.qk_M = qk_rule_rows(h, M);   // "dedup_qkv": this launch returns at once where the split form below runs
+            if (need.qk_runs.list) h->prof_next_qk = {need.qk_runs.id, g.qk_M, 1};
             char tg_[96];
             if (h->prof_stamps && h->prof_gemm && h->prof_gemm_used < h->prof_gemm_cap) g.prof = h->prof_gemm + 4 * (h->prof_gemm_used++);
             if (h->prof_on) snprintf(tg_, sizeof(tg_), "gemm+attn M=%d N=%d K=%d ln=%d heads=%d", g.M, g.N, g.K, g.ln_part ? 2 : 1, b.heads);
             ProfScope ps_(h, s, PK_GEMM, 2.0 * (double)M * 3.0 * C * C + 4.0 * (double)M * (double)(b.ws * b.ws) * (double)C, tg_);
             attn_done = launch_gemm_qkv_attn(g, s);
         }
-        if (!attn_done && need.wins.list) plan_fail(h, "%s: fused QKV + window attention with a window list not built", p.c_str());
+        if (attn_done && need.qk_runs.list) {
+            // the split form (qkv_dedup_at; rule and lists: kernels.h): q, k, v of the listed rows -- LayerNorm in the A path from the
+            // same statistics, the fused kernel's K order and bias add -- into w->qkv, then the fused kernel's attention phase from there
+            // through the window map.  Both launches return at once where the fused launch above runs.
+            GemmArgs q;
+            q.A = w->x; q.lda = C; q.K1 = C; q.K = C; q.M = M; q.N = 3 * C;
+            q.ln_part = g.ln_part; q.ln_nparts = g.ln_nparts; q.ln_stats = g.ln_stats;
+            q.W = b.qkv_wf; q.bias = b.qkv_bf; q.C = w->qkv; q.ldc = 3 * C;
+            q.row_list = need.qk_runs.list; q.row_cnt = need.qk_runs.cnt; q.qk_cnt = need.qk_runs.cnt; q.qk_M = g.qk_M;
+            h->prof_next_list = need.qk_runs.id; h->prof_next_qk = {need.qk_runs.id, g.qk_M, 2};
+            P_GEMM(q);
+            GemmArgs a = g;
+            a.prof = nullptr;
+            h->prof_next_qk = {need.qk_runs.id, g.qk_M, 2};
+            char ta_[96];
+            if (h->prof_on) snprintf(ta_, sizeof(ta_), "attn(map) M=%d C=%d heads=%d", M, C, b.heads);
+            ProfScope pa_(h, s, PK_ATTN, 4.0 * (double)M * (double)(b.ws * b.ws) * (double)C, ta_);
+            if (!launch_window_attn_map(a, w->qkv, need.qk_src.list, s)) plan_fail(h, "%s: attention through the window map not built", p.c_str());
+        }
+        if (!attn_done && (need.wins.list || need.qk_runs.list)) plan_fail(h, "%s: fused QKV + window attention with a window list not built", p.c_str());
         if (!attn_done) {
             g.attn_bias = nullptr; g.prof = nullptr; g.row_list = nullptr; g.row_cnt = nullptr;
             g.C = w->qkv; g.ldc = 3 * C;
@@ -1758,7 +1812,10 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s, const TabBuild *tb
             // the level's last block leaves row statistics for the fused PatchMerging
             const bool for_merge = !next && merge_fused_at(h, B, l);
             const bool dd = j == 0 && l < depth;   // the level's input came over its run list
-            const BlockNeed bn = dd ? BlockNeed{need_ref(h, w, w->need.dd_runs[l]), need_ref(h, w, w->need.dd_wins[l])} : BlockNeed();
+            BlockNeed bn = dd ? BlockNeed{need_ref(h, w, w->need.dd_runs[l]), need_ref(h, w, w->need.dd_wins[l])} : BlockNeed();
+            const bool qk = qkv_dedup_at(h, w, l, (int)j, depth);
+            if (qk) { bn.qk_runs = need_ref(h, w, w->need.qk_runs[l]); bn.qk_src = need_ref(h, w, w->need.qk_src[l]); }
+            if (j == 1 && l <= NEED_MAX_DD_UP && !g_dry_run) w->qk_fwd[l] = qk;
             const BlockOut bo = run_block(h, w, h->down[l][j], premod, next, for_merge, s, bn);
             premod = bo.premod; merge_parts = bo.stats_parts;
             // behind the copy x, the skip (level 0 has none yet) and the partials the next launch reads (a following block's LN1 partials
@@ -2166,9 +2223,9 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         return std::tie(h->opt_fused_attn, h->opt_fused_mlp, h->opt_fused_mlp_maxc, h->opt_fused_readout, h->opt_fused_pe, h->opt_fused_rowstats,
                         h->opt_fused_qkv_attn, h->opt_loop_graph, h->opt_bf16_act, h->opt_bf16_pipe, h->opt_bf16_mlp, h->opt_bf16_qkv_attn,
                         h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked,
-                        h->opt_batch_invariant, h->opt_dedup_masked, h->opt_dedup_levels, h->opt_dedup_batch);
+                        h->opt_batch_invariant, h->opt_dedup_masked, h->opt_dedup_levels, h->opt_dedup_batch, h->opt_dedup_qkv);
     };
-    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool, int, int> saved = opts();
+    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool, int, int, int> saved = opts();
     if (n == "fused_attn") h->opt_fused_attn = value != 0;
     else if (n == "fused_mlp") h->opt_fused_mlp = value != 0;
     else if (n == "fused_mlp_maxc") h->opt_fused_mlp_maxc = value;
@@ -2186,6 +2243,7 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     else if (n == "prune_masked") h->opt_prune_masked = value != 0;
     else if (n == "dedup_masked") h->opt_dedup_masked = value != 0;
     else if (n == "dedup_levels") h->opt_dedup_levels = value > 0 ? value : 0;
+    else if (n == "dedup_qkv") h->opt_dedup_qkv = value < 0 ? 0 : (value > 2 ? 2 : value);   // 0: the parent's launches exactly (the step bodies differ: captured graphs are dropped)
     else if (n == "dedup_batch") {
         // acts where the lists are written (stage_flags) and nowhere else: the launches, their grids and the list addresses are the
         // same for every value, so the captured graphs stay -- one captured under either kind of list replays under the other
@@ -2249,6 +2307,7 @@ int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     else if (n == "prune_masked") *value = prune_opts_on(h);   // what runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
     else if (n == "dedup_masked") *value = dedup_opts_on(h);   // what runs (in the sampler): 0 wherever the pruning is off, or the fused C = 96 kernels are
     else if (n == "dedup_levels") *value = dedup_levels(h);   // what runs (in the sampler, where PatchMerging takes its partial-statistics form)
+    else if (n == "dedup_qkv") *value = dedup_opts_on(h) ? h->opt_dedup_qkv : 0;   // what runs, at the blocks that qualify (qkv_dedup_at)
     else if (n == "dedup_batch") *value = dedup_opts_on(h) ? h->opt_dedup_batch : 0;   // what runs (in the sampler; 1: from 16 graphs)
     else if (n == "dedup_table") *value = dedup_opts_on(h) && h->opt_dedup_batch > 0 && h->opt_dedup_table;   // what runs (in the sampler, where the batch shares one representative)
     else if (n == "debug_alloc_fill") *value = h->opt_debug_alloc_fill;
@@ -3121,7 +3180,7 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
     h->prof_clock_ghz = clocks.empty() ? 0.0 : clocks[clocks.size() / 2];
     // pass B: HIP-event brackets around every launch (per-class breakdown; each bracket includes dispatch latency)
     for (int iter = 0; iter < n_iters; iter++) {
-        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear(); h->prof_list.clear(); h->prof_thin_n.clear();
+        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear(); h->prof_list.clear(); h->prof_thin_n.clear(); h->prof_qk.clear();
         forward_fixed(h, w, s);
         const bool ok = h->prof_on;
         h->prof_on = false;
@@ -3133,6 +3192,10 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
         for (size_t i = 0; i < h->prof_kind.size(); i++) {
             const int nl = h->prof_list[i];
             if (nl >= 0 && nl < w->need.n_lists) h->prof_flops[i] *= (double)need_cnt[nl] / ((double)B * (double)prune_plan(h).items[nl]);
+            {   // the launches of the form that the "dedup_qkv" switch did not take returned at once
+                const auto &qk = h->prof_qk[i];
+                if (qk.list >= 0 && qk.list < w->need.n_lists && (qk_split_rule(need_cnt[qk.list], qk.M) ? 2 : 1) != qk.role) h->prof_flops[i] = 0.0;
+            }
             float ms = 0.f;
             HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_events[2 * i], h->prof_events[2 * i + 1]));
             if (iter == n_iters - 1 && getenv("DSG_PROFILE_VERBOSE")) {
@@ -3140,6 +3203,9 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
                 const char *form = "";
                 if (nl >= 0 && nl < w->need.n_lists && h->prof_thin_n[i] > 0)
                     form = gemm_thin_rule(need_cnt[nl], h->prof_thin_n[i], h->n_cu) ? " form=thin" : " form=wide";
+                // a block with the "dedup_qkv" switch names the form its blocks chose (qk_split_rule on the count read back above)
+                const auto &qk = h->prof_qk[i];
+                if (qk.list >= 0 && qk.list < w->need.n_lists) form = qk_split_rule(need_cnt[qk.list], qk.M) ? " form=split" : " form=fused";
                 fprintf(stderr, "[dsg-prof] %8.1f us %7.2f TF  %.60s%s\n", ms * 1e3, h->prof_flops[i] / (ms * 1e-3) / 1e12, h->prof_tag[i].c_str(), form);
             }
             ms_by_kind[h->prof_kind[i]] += ms;
@@ -3242,6 +3308,30 @@ int dsg_debug_dedup_launch_lists(dsg_handle h, int32_t B, int32_t level, int32_t
                                  void *stream) {
     return dedup_level_lists(h, B, level, true, counts, wins, runs, copy, nullptr, stream);
 }
+
+int dsg_debug_dedup_qkv_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *runs, int32_t *src, void *stream) {
+    if (int rc = check_ready(h, B)) return rc;
+    if (!counts || level < 0) return fail(h, DSG_ERR_INVALID, "null argument or negative level");
+    auto it = h->ws.find(B);
+    if (it == h->ws.end()) return fail(h, DSG_ERR_STATE, "no workspace for batch %d: run dsg_denoise/dsg_sample first", B);
+    Workspace *w = it->second.get();
+    counts[0] = counts[1] = counts[2] = counts[3] = -1;
+    if (!w->dd_rep || level >= w->need.dd_n || w->need.qk_runs[level] < 0 || w->need.qk_src[level] < 0) return DSG_OK;
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    std::vector<int> all(w->need_ints);
+    HIP_TRY(h, hipMemcpy(all.data(), w->need_lists, sizeof(int) * w->need_ints, hipMemcpyDeviceToHost));
+    const int *cnt = all.data() + (w->need_cnt - w->need_lists);
+    const int res = h->N >> level;
+    counts[0] = cnt[w->need.qk_runs[level]];
+    counts[1] = cnt[w->need.qk_src[level]];
+    counts[2] = qk_split_rule(counts[0], B * res * res) ? 1 : 0;
+    counts[3] = w->qk_fwd[level] ? (qk_split_rule(counts[0], qk_rule_rows(h, B * res * res)) ? 1 : 0) : -1;
+    if (runs) memcpy(runs, all.data() + w->need.list_off[w->need.qk_runs[level]], sizeof(int) * (size_t)counts[0]);
+    if (src) memcpy(src, all.data() + w->need.list_off[w->need.qk_src[level]], sizeof(int) * (size_t)counts[1]);
+    return DSG_OK;
+}
+
+int32_t dsg_debug_qk_split(int32_t listed_runs, int32_t M) { return qk_split_rule(listed_runs, M) ? 1 : 0; }
 
 int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream) {
     return dsg_debug_dedup_level_lists(h, B, 0, counts, wins, runs, copy, rep, stream);

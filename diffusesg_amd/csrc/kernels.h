@@ -74,6 +74,11 @@ struct GemmArgs {
     // thin form of the list GEMM (64-row tiles, see kernels.hip): chosen on the device from *row_cnt by gemm_thin_rule() below.
     // n_cu: the device's multiprocessor count (0: never thin).  form: 0 the rule, 1 always wide, 2 always thin (test hook).
     int n_cu = 0, form = 0;
+    // form switch of the deduplicated QKV projection (qk_split_rule below; dsg_api.cpp: run_block): qk_cnt = the device-side count of the
+    // level's qk_runs list.  The fused QKV + attention launch over all rows (8 x 8 windows, no window list) returns at once where the rule
+    // holds, the LayerNorm list GEMM without activation (the projection over qk_runs) where it does not.  null: no switch
+    // qk_M: the rows the rule compares the listed rows with -- the launch's M (a measurement hook passes INT_MAX: split wherever a list exists)
+    const int *qk_cnt = nullptr; int qk_M = 0;
     int a_bf16 = 0, c_bf16 = 0;                  // bf16 mode only: A / C are bf16 tensors (lda / ldc in elements); see kernels_lp.hip
     const float *gelu_tab = nullptr;             // filled in by launch_gemm (table-driven GELU of the split kernel)
     unsigned long long *prof = nullptr;          // measurement mode: {min block start, max block end} in 100 MHz ticks
@@ -87,12 +92,24 @@ __host__ __device__ inline bool gemm_thin_rule(int cnt_runs, int N, int n_cu) {
     if (cnt_runs < 0 || N < 1 || n_cu < 1) return false;
     return 2ll * ((cnt_runs + 15) / 16) * ((N + 95) / 96) <= (long long)n_cu;
 }
+// The form of a shifted block behind a deduplicated first block (option "dedup_qkv"): its QKV projection is row-wise and the fill has
+// left most of its input rows as copies, so where the listed rows -- the non-pure windows plus one source pure window per content
+// class, 8 rows per run -- are at most half of the M rows, the projection runs over the list and window_attn_map_kernel reads q, k, v
+// through the window map (two launches, the attention re-reads w->qkv); above that the fused kernel over all rows is the cheaper form.
+__host__ __device__ inline bool qk_split_rule(int listed_runs, int M) {
+    return listed_runs > 0 && 2ll * 8 * listed_runs <= (long long)M;
+}
 // does launch_gemm build the thin form for these arguments?  (row list, no LayerNorm, no activation: the proj / fc2 / reduction shapes)
 inline bool gemm_has_thin(const GemmArgs &g) {
     return g.row_list && !g.ln_stats && !g.ln_part && g.act == ACT_NONE && g.a4_res == 0 && !g.Ws3 && !g.Wb && g.batch == 1;
 }
 // fused LN1 -> QKV -> window attention for 64-token windows (fp32 kernel); returns false if the geometry is not supported
 bool launch_gemm_qkv_attn(const GemmArgs &g, hipStream_t s);
+// The attention of that launch on its own, from q, k, v rows already in qkv [B * T, 3 C] (the list GEMM over qk_runs wrote them): a block
+// loads the tile's rows of its head into the same LDS slabs and runs the fused kernel's attention phase.  Token rows whose unshifted
+// window w (b * nW + w) is not listed are read from the same position of window qk_src[b * nW + w].  Blocks return at once unless
+// qk_split_rule(*qk_cnt, B * T).  g: as for launch_gemm_qkv_attn (wg, attn_batch, attn_bias, C / ldc the output); false: not built
+bool launch_window_attn_map(const GemmArgs &g, const float *qkv, const int *qk_src, hipStream_t s);
 void launch_f32_to_bf16(const float *src, void *dst, size_t n, hipStream_t s);
 
 // ---- bf16 block pipeline (kernels_bx.hip; "gemm_bf16" mode): C = epilogue(A[M,K] . W[N,K]^T), A and W bf16 in HBM ----
@@ -228,8 +245,13 @@ struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_
                   // pure-window deduplication (below), levels 0 .. dd_n - 1 of the down path (0: none): level k's unique 8-token runs,
                   // its unique windows and the pure windows that are filled by copy; -1 = the level has no such lists
                   int dd_n = 0, dd_runs[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}, dd_wins[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1},
-                      dd_copy[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}; };
-static_assert(sizeof(NeedPlan) == sizeof(int) * (2 + 4 * NEED_MAX_OPS + NEED_MAX_LISTS + 1 + 3 * (1 + NEED_MAX_DD_UP)), "NeedPlan is a kernel argument: keep it packed");
+                      dd_copy[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1},
+                  // option "dedup_qkv" (qk_split_rule above), for a level whose second block is shifted: qk_runs -- the 8-token runs of every
+                  // non-pure window plus those of one source pure window per content class (the batch's representative window under
+                  // DD_BATCH / DD_TABLE, the graph's first pure window under DD_GRAPH; DD_OFF lists every window); qk_src [B * nW] -- for
+                  // every window the window whose rows of the QKV tensor hold its q, k, v: itself when listed, else its class's source
+                      qk_runs[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}, qk_src[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}; };
+static_assert(sizeof(NeedPlan) == sizeof(int) * (2 + 4 * NEED_MAX_OPS + NEED_MAX_LISTS + 1 + 5 * (1 + NEED_MAX_DD_UP)), "NeedPlan is a kernel argument: keep it packed");
 // cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
 // dedup (a DedupMode) / dd_rep / trim_mask: see below (dd_rep [plan.dd_n][B] + 1 int, the mode; may be null when the plan has no dd_* lists)
 enum DedupMode { DD_OFF = 0,      // every window is listed as unique, nothing is copied

@@ -360,12 +360,95 @@ __device__ __forceinline__ void gemm4_thin_tile(const GemmArgs &g, int bid, int 
     }
 }
 
+// The attention phase of the fused QKV + window attention (gemm4_f32_kernel, EPI == 4) and of window_attn_map_kernel, which reads the
+// same q, k, v from the QKV tensor: Qs / Ks / Vs hold q, k, v of (the tile's windows, head tn) as [128][GLD] slabs, toks the token row
+// of every tile row (-1: none).  Wave `wave` takes window wave / A_KT of the tile (global id gw) and its 32-query block wave % A_KT:
+// S^T = K Q^T + the bias tile, packed softmax, P V, and the store of the head's 32 columns through the token table.  A textual copy
+// of the EPI == 4 branch of gemm4_f32_kernel behind its second barrier, which keeps its own text (calling this function there moved
+// its register allocation); the two must stay the same instruction for instruction: tests/test_dedup_qkv.py compares their outputs.
+template <int WS>
+__device__ __forceinline__ void qkv_attn_phase(const float *Qs, const float *Ks, const float *Vs, const int *toks, int wave, int lrow, int lhalf,
+                                               int gw, int a_nwin, int a_nW, int tn, int shift, int heads, const float *attn_bias, float *out,
+                                               int M, int ldc) {
+    constexpr int A_WT = WS * WS, A_WP = (A_WT + 31) / 32 * 32, A_KT = A_WP / 32;
+    const int wl = wave / A_KT, qh = wave % A_KT;   // window of the tile / 32-query block inside the window
+    if (gw < a_nwin && gw >= 0 && 32 * qh < A_WT) {   // wave-uniform: the last tile's second window may not exist
+        const int wbase = A_WP * wl;
+        f32x4 qf[4];
+#pragma unroll
+        for (int sx = 0; sx < 4; sx++) qf[sx] = *reinterpret_cast<const f32x4 *>(Qs + (32 * wave + lrow) * GLD + 8 * sx + 4 * lhalf);
+        const int wtype = shift > 0 ? gw % a_nW : 0;
+        const rsrc_t rsB = make_rsrc(attn_bias + ((size_t)wtype * heads + tn) * (A_WP * A_WP), (unsigned)(A_WP * A_WP) * 4u);
+        const unsigned boff = (unsigned)(4 * lhalf * A_WP + 32 * qh + lrow) * 4u;
+        f32x16 sacc[A_KT];
+        float mx = -3.0e38f;
+#pragma unroll
+        for (int kt = 0; kt < A_KT; kt++) {
+            f32x4 kf[4];
+#pragma unroll
+            for (int sx = 0; sx < 4; sx++)
+                kf[sx] = *reinterpret_cast<const f32x4 *>(Ks + (wbase + 32 * kt + lrow) * GLD + 8 * sx + 4 * lhalf);
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                sacc[kt][r] = buf_load1(rsB, boff, (unsigned)((32 * kt + (r & 3) + 8 * (r >> 2)) * A_WP) * 4u);
+#pragma unroll
+            for (int sx = 0; sx < 4; sx++)
+#pragma unroll
+                for (int t = 0; t < 4; t++) sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[sx][t], qf[sx][t], sacc[kt], 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 16; r++) mx = fmaxf(mx, sacc[kt][r]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float sum = 0.f;
+        f32x2_t sum2 = {0.f, 0.f};
+        const f32x2_t mx2 = {mx, mx};
+#pragma unroll
+        for (int kt = 0; kt < A_KT; kt++)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {   // (subtract and sum on packed fp32; the sum's association changes: pairs of lanes' partials)
+                const f32x2_t d2 = (f32x2_t){sacc[kt][r], sacc[kt][r + 1]} - mx2;
+                const f32x2_t e2 = {__builtin_amdgcn_exp2f(d2[0]), __builtin_amdgcn_exp2f(d2[1])};   // scores carry the log2(e) factor
+                sacc[kt][r] = e2[0]; sacc[kt][r + 1] = e2[1];
+                sum2 += e2;
+            }
+        sum = sum2[0] + sum2[1];
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = fast_rcp(sum);
+        f32x16 oacc;
+#pragma unroll
+        for (int r = 0; r < 16; r++) oacc[r] = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < A_KT; kt++) {
+            float vf[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) vf[r] = Vs[(wbase + 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * lhalf) * GLD + lrow];
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const f32x2_t p2 = (f32x2_t){sacc[kt][r], sacc[kt][r + 1]} * (f32x2_t){inv, inv};
+                oacc = __builtin_amdgcn_mfma_f32_32x32x2f32(p2[0], vf[r], oacc, 0, 0, 0);
+                oacc = __builtin_amdgcn_mfma_f32_32x32x2f32(p2[1], vf[r + 1], oacc, 0, 0, 0);
+            }
+        }
+        // O tile: column d = lrow of head tn, row = query (r&3)+8(r>>2)+4*half of this wave's 32 tokens
+        const rsrc_t rsO = make_rsrc(out, (unsigned)M * ldc * 4u);
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int tok = toks[32 * wave + (r & 3) + 8 * (r >> 2) + 4 * lhalf];
+            buf_store1(oacc[r], rsO, tok >= 0 ? ((unsigned)tok * ldc + (unsigned)(tn * 32 + lrow)) * 4u : 0x7fffffffu, 0u);
+        }
+    }
+}
+
 template <bool LN, int ACT, bool RES, int EPI, int WS = 8, int AMODE = 0>   // WS: window side of the fused attention (EPI == 4): 8 or 10
 __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles_m, int tiles_n) {
     __shared__ __attribute__((aligned(16))) float lds[2 * (GBM + GBN) * GLD];
     constexpr int BUF = (GBM + GBN) * GLD;
 
     int bid = blockIdx.x;
+    // the form switch of the deduplicated QKV projection (qk_split_rule on the device-side count; captured bodies keep both forms'
+    // launches): the fused launch over all rows does nothing where the split form runs, the projection over qk_runs nothing elsewhere
+    if constexpr (EPI == 4 && WS == 8 && AMODE == 0) { if (g.qk_cnt && qk_split_rule(*g.qk_cnt, g.qk_M)) return; }
+    if constexpr (LN && ACT == ACT_NONE && !RES && EPI == 0 && AMODE == 3) { if (g.qk_cnt && !qk_split_rule(*g.qk_cnt, g.qk_M)) return; }
     if constexpr (AMODE == 3 && !LN && ACT == ACT_NONE && EPI != 4) {   // the list launches with a thin form: block-uniform choice (gemm_thin_rule)
         const int cnt = *g.row_cnt;
         if (g.form == 2 || (g.form == 0 && gemm_thin_rule(cnt, g.N, g.n_cu))) {
@@ -664,6 +747,8 @@ __global__ __launch_bounds__(256, 2) void gemm4_f32_kernel(GemmArgs g, int tiles
         }
         if (tid < GBM) toks[tid] = my_tok;
         __syncthreads();
+        // (The attention phase.  qkv_attn_phase above is a textual copy of it for window_attn_map_kernel: calling the function here
+        // moved this kernel's register allocation, 186 -> 188 VGPRs.  Change both together; tests/test_dedup_qkv.py holds them equal.)
         const int wl = wave / A_KT, qh = wave % A_KT;   // window of the tile / 32-query block inside the window
         const int gw = tile_win(wl);
         if (gw < a_nwin && gw >= 0 && 32 * qh < A_WT) {   // wave-uniform: the last tile's second window may not exist
@@ -943,9 +1028,11 @@ bool launch_gemm(const GemmArgs &g, hipStream_t s) {
         if (!g.row_cnt || g.a4_res > 0 || g.M % 8 != 0 || (size_t)g.M * widest * 4u >= 0x7fffffffull) return false;
         const int epi = !g.stats_out ? 0 : (!g.mod_aff ? 1 : (g.mod_ld == 0 ? 2 : 3));
         if (ln) {
-            if (g.act != ACT_GELU || res || epi != 0 || g.C2 || g.A2 || g.form == 2) return false;   // (no thin form with LayerNorm)
+            // fc1 (GELU), and without activation the QKV projection over qk_runs (the only launch that takes the form switch qk_cnt)
+            if ((g.act != ACT_GELU && g.act != ACT_NONE) || res || epi != 0 || g.C2 || g.A2 || g.form == 2) return false;   // (no thin form with LayerNorm)
+            if (g.qk_cnt && g.act != ACT_NONE) return false;
 #define GEMM_MAP(L, A, R, E) DSG_LAUNCH((gemm4_f32_kernel<L, A, R, E, 8, 3>), grid, block, 0, s, g, tiles_m, tiles_n)
-            GEMM_MAP(true, ACT_GELU, false, 0);
+            if (g.act == ACT_GELU) GEMM_MAP(true, ACT_GELU, false, 0); else GEMM_MAP(true, ACT_NONE, false, 0);
 #undef GEMM_MAP
         } else {
             if (g.act != ACT_NONE || (g.C2 && res) || (g.mod_aff && !g.stats_out)) return false;   // (dual store: the list form of PatchMerging's reduction)
@@ -1007,6 +1094,7 @@ bool launch_gemm_qkv_attn(const GemmArgs &g, hipStream_t s) {
     const int wpt = wg.ws == 8 ? 2 : 1;   // windows per 128-row tile: two of 64 tokens, or one of 100 padded to 128
     const int tiles_m = (n_windows + wpt - 1) / wpt, tiles_n = wg.heads;
     const dim3 grid(((tiles_m + 7) / 8) * 8 * tiles_n), block(256);
+    if (g.qk_cnt && (g.row_list || wg.ws != 8)) return false;   // the form switch: all rows of 8 x 8 windows only
     if (g.row_list) {   // windows through a window list (masked-token pruning)
         if (wg.ws != 8 || !g.row_cnt) return false;
         DSG_LAUNCH((gemm4_f32_kernel<true, ACT_NONE, false, 4, 8, 3>), grid, block, 0, s, g, tiles_m, tiles_n);
@@ -1014,6 +1102,75 @@ bool launch_gemm_qkv_attn(const GemmArgs &g, hipStream_t s) {
     }
     if (wg.ws == 8) DSG_LAUNCH((gemm4_f32_kernel<true, ACT_NONE, false, 4, 8>), grid, block, 0, s, g, tiles_m, tiles_n);
     else DSG_LAUNCH((gemm4_f32_kernel<true, ACT_NONE, false, 4, 10>), grid, block, 0, s, g, tiles_m, tiles_n);
+    return true;
+}
+
+// The attention of the fused launch above from the QKV tensor (kernels.h: launch_window_attn_map; option "dedup_qkv").  Grid, tile and
+// window / shift index math are the fused kernel's: block = (two 8 x 8 windows of the shifted partition, head tn).  Thread (r0, c4) loads
+// four floats of q, k and v of tile rows r0 + 32 p into the [128][GLD] slabs.  A token (b, ti, tj) lies in the UNSHIFTED window
+// b * nW + (ti / 8) * nwr + tj / 8 of the level; where qk_src names another window for it, the projection over qk_runs has not written
+// the token's row and the row at the same position (ti % 8, tj % 8) of that window holds the same q, k, v bit for bit (the fill copied
+// the projection's input row and its LayerNorm partials from there, or both are copies of one source).  Then qkv_attn_phase.
+__global__ __launch_bounds__(256, 2) void window_attn_map_kernel(GemmArgs g, const float *__restrict__ qkv, const int *__restrict__ qk_src,
+                                                                 int tiles_m) {
+    constexpr int QKV = GBM * GLD;
+    __shared__ __attribute__((aligned(16))) float lds[3 * QKV + GBM];
+    if (!qk_split_rule(*g.qk_cnt, g.qk_M)) return;
+    const int bid = blockIdx.x, tiles_n = g.wg.heads;
+    const int xcd = bid & 7, seq = bid >> 3;
+    const int tm = (seq / tiles_n) * 8 + xcd, tn = seq % tiles_n;
+    if (tm >= tiles_m) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c4 = tid & 7, r0 = tid >> 3;
+    const int res = g.wg.res, nwr = res / 8, nW = nwr * nwr, T = res * res, nwin = g.attn_batch * nW, C = g.wg.C;
+    float *Qs = lds, *Ks = lds + QKV, *Vs = lds + 2 * QKV;
+    int *toks = reinterpret_cast<int *>(lds + 3 * QKV);
+    // tile row r -> (token row for the output scatter, row of qkv that holds the token's q, k, v); -1: the window does not exist
+    auto rows_of = [&](int r, int &tok, int &srow) {
+        const int gw = 2 * tm + (r >> 6), pos = r & 63;
+        tok = -1; srow = -1;
+        if (gw >= nwin) return;
+        const int b = gw / nW, w = gw - b * nW, wi = w / nwr, wj = w - wi * nwr;
+        int ti = wi * 8 + (pos >> 3) + g.wg.shift, tj = wj * 8 + (pos & 7) + g.wg.shift;
+        if (ti >= res) ti -= res;
+        if (tj >= res) tj -= res;
+        tok = b * T + ti * res + tj;
+        const int own = b * nW + (ti >> 3) * nwr + (tj >> 3), src = qk_src[own];
+        srow = tok;
+        if (src != own && src >= 0 && src < nwin) {
+            const int sb = src / nW, sw = src - sb * nW;
+            srow = sb * T + ((sw / nwr) * 8 + (ti & 7)) * res + (sw % nwr) * 8 + (tj & 7);
+        }
+    };
+    const rsrc_t rsQ = make_rsrc(qkv, (unsigned)g.M * (unsigned)(3 * C) * 4u);
+    f32x4 st[3][4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        int tok, srow;
+        rows_of(r0 + 32 * p, tok, srow);
+        const unsigned voff = srow >= 0 ? ((unsigned)srow * (unsigned)(3 * C) + (unsigned)(tn * 32 + 4 * c4)) * 4u : 0x7fffffffu;
+#pragma unroll
+        for (int j = 0; j < 3; j++) st[j][p] = buf_load4(rsQ, voff, (unsigned)(j * C) * 4u);   // q | k | v of head tn
+    }
+    if (tid < GBM) { int tok, srow; rows_of(tid, tok, srow); toks[tid] = tok; }
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+#pragma unroll
+        for (int p = 0; p < 4; p++) *reinterpret_cast<f32x4 *>(lds + j * QKV + (r0 + 32 * p) * GLD + 4 * c4) = st[j][p];
+    __syncthreads();
+    qkv_attn_phase<8>(Qs, Ks, Vs, toks, wave, lane & 31, lane >> 5, 2 * tm + (wave >> 1), nwin, nW, tn, g.wg.shift, g.wg.heads, g.attn_bias,
+                      g.C, g.M, g.ldc);
+}
+
+bool launch_window_attn_map(const GemmArgs &g, const float *qkv, const int *qk_src, hipStream_t s) {
+    const WinGeom &wg = g.wg;
+    if (wg.ws != 8 || wg.res % 8 != 0 || wg.C != 32 * wg.heads || !g.attn_bias || !g.qk_cnt || !qk_src || !qkv || !g.C || g.attn_batch < 1 ||
+        g.M != g.attn_batch * wg.res * wg.res || (size_t)g.M * (size_t)(3 * wg.C) * 4u >= 0x7fffffffull)
+        return false;
+    const int n_windows = g.attn_batch * (wg.res / 8) * (wg.res / 8);
+    const int tiles_m = (n_windows + 1) / 2, tiles_n = wg.heads;
+    const dim3 grid(((tiles_m + 7) / 8) * 8 * tiles_n), block(256);
+    DSG_LAUNCH(window_attn_map_kernel, grid, block, 0, s, g, qkv, qk_src, tiles_m);
     return true;
 }
 
@@ -3175,6 +3332,27 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             }
             __syncthreads();
             emit(win, nW, l_copy, b * nW);
+            // option "dedup_qkv" (kernels.h: NeedPlan::qk_runs / qk_src): behind the fill the level's QKV projection is needed for the
+            // non-pure windows and for ONE pure window per content class -- the representative named above, also where the table fills
+            // it (any filled pure window holds the class's rows); every other pure window reads that one's q, k, v
+            if (plan.qk_runs[k] >= 0) {
+                for (int w = tid; w < nW; w += 256) win[w] = (!pure[w] || w == rep) ? 1 : 0;
+                __syncthreads();
+                for (int idx = tid; idx < res * nwr; idx += 256) {
+                    const int i = idx / nwr, jr = idx - i * nwr;
+                    runs[idx] = win[(i >> 3) * nwr + jr];
+                }
+                __syncthreads();
+                emit(runs, res * nwr, plan.qk_runs[k], b * res * nwr);
+                const int l_src = plan.qk_src[k];
+                if (PHASE == 0) {
+                    if (tid == 0) cnt_ps[b * plan.n_lists + l_src] = 0;   // a fixed-size map: nothing to compact
+                } else {
+                    const int cls = batch ? (rep_all[k] == 0x7fffffff ? -1 : rep_all[k]) : (rep < 0 ? -1 : b * nW + rep);
+                    for (int w = tid; w < nW; w += 256) lists[plan.list_off[l_src] + b * nW + w] = pure[w] ? cls : b * nW + w;
+                    if (b == B - 1 && tid == 0) cnt[l_src] = B * nW;
+                }
+            }
             if (PHASE == 1 && tid == 0) {
                 if (batch) dd_rep[(size_t)k * B + b] = rep_all[k] == 0x7fffffff ? -1 : rep_all[k];
                 else dd_rep[(size_t)k * B + b] = rep < 0 ? -1 : b * nW + rep;

@@ -16,7 +16,7 @@ EXPORTS = [
     "dsg_num_weight_keys", "dsg_weight_key", "dsg_workspace_bytes", "dsg_denoise", "dsg_precond", "dsg_sample",
     "dsg_sigma_schedule", "dsg_debug_tap", "dsg_debug_clear_taps", "dsg_decode_bits", "dsg_decode", "dsg_profile_forward", "dsg_set_option",
     "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_f32", "dsg_debug_gemm_form", "dsg_debug_qkv_attn_f32", "dsg_debug_window_attn_f32", "dsg_debug_fused_mlp_f32", "dsg_debug_fused_attn96_f32", "dsg_debug_t_gemm", "dsg_debug_t_attn", "dsg_debug_t_ln", "dsg_debug_t_modulate", "dsg_debug_t_colsum", "dsg_debug_t_grouped", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists", "dsg_debug_dedup_lists", "dsg_debug_dedup_level_lists",
-    "dsg_debug_dedup_launch_lists",
+    "dsg_debug_dedup_launch_lists", "dsg_debug_dedup_qkv_lists", "dsg_debug_qk_split",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
     "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
@@ -193,6 +193,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_debug_dedup_lists.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.dsg_debug_dedup_level_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.dsg_debug_dedup_launch_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.dsg_debug_dedup_qkv_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.dsg_debug_qk_split.argtypes = [i32, i32]
+    L.dsg_debug_qk_split.restype = i32
     L.dsg_set_option.argtypes = [vp, C.c_char_p, i32]
     L.dsg_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
     L.dsg_gen_noise.argtypes = [vp, i32, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
@@ -409,6 +412,22 @@ class Handle:
         if counts[0] < 0:
             return None
         return dict(wins=wins[:counts[0]].copy(), runs=runs[:counts[1]].copy(), copy=copy[:counts[2]].copy(), mode=int(counts[3]))
+
+    def dedup_qkv_lists(self, B: int, level: int, stream=None):
+        """Option "dedup_qkv" at level `level`'s second block (dsg_debug_dedup_qkv_lists): runs -- the 8-row runs whose q, k, v the split
+        form projects, src [B * nW] -- the window that holds every window's q, k, v, split -- what the device's rule picks for these
+        lists, form -- what the last forward took there ('split' | 'fused' | None: no switch at that block).  None: no such lists."""
+        import numpy as np
+        res = self.cfg.max_node_num >> level
+        nw = max(1, (res // 8) ** 2)
+        counts = np.zeros(4, np.int32)
+        runs, src = np.zeros(max(1, B * res * res // 8), np.int32), np.zeros(B * nw, np.int32)
+        self.check(self.L.dsg_debug_dedup_qkv_lists(self._h, B, level, counts.ctypes.data, runs.ctypes.data, src.ctypes.data, stream),
+                   "dsg_debug_dedup_qkv_lists")
+        if counts[0] < 0:
+            return None
+        return dict(runs=runs[:counts[0]].copy(), src=src[:counts[1]].copy(), split=bool(counts[2]),
+                    form={1: "split", 0: "fused"}.get(int(counts[3])))
 
     def precision_mode(self) -> str:
         """'f32' | 'f32-split' | 'bf16': the GEMM arithmetic the handle will actually run (options or DSG_* env defaults)."""

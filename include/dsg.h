@@ -539,6 +539,17 @@ int dsg_debug_dedup_level_lists(dsg_handle h, int32_t B, int32_t level, int32_t 
  * dsg_debug_dedup_level_lists reports as rep.  For 0 .. 2 the lists are those of dsg_debug_dedup_level_lists. */
 int dsg_debug_dedup_launch_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy,
                                  void *stream);
+/* Option "dedup_qkv": the lists of level `level`'s second, shifted block as the flags last staged for batch B left them.  runs: the 8-row
+ * runs whose q, k, v the split form projects (every non-pure window, plus one source pure window per content class: of the batch where it
+ * shares a representative, of each graph otherwise; every window under mode 0).  src [B nW]: for every window b nW + w of the level the
+ * window whose rows of the QKV tensor hold its q, k, v (itself when listed).  counts[0] = entries of runs, counts[1] = entries of src,
+ * counts[2] = 1 where the device's rule picks the split form for these lists (dsg_debug_qk_split(counts[0], B res^2)), counts[3] = the
+ * form the batch size's last forward took at that block: 1 split (the rule, or "dedup_qkv" 2: whatever the share), 0 fused, -1 the block ran without the switch (option off, another
+ * kernel path, or the level not deduplicated).  All -1: the plan has no such lists for the level. */
+int dsg_debug_dedup_qkv_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *runs, int32_t *src, void *stream);
+/* The rule of that switch, from the function the kernels evaluate on the device-side count: 1 (split) iff listed_runs > 0 and the listed
+ * rows, 8 per run, are at most half of the M rows.  Host only. */
+int32_t dsg_debug_qk_split(int32_t listed_runs, int32_t M);
 int dsg_debug_tap(dsg_handle h, const char *stage, float *dst, int64_t capacity);
 void dsg_debug_clear_taps(dsg_handle h);
 
