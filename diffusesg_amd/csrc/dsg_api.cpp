@@ -165,6 +165,14 @@ struct PrunePlan {
     std::vector<PruneRole> roles;                                    // the same assignment as a flat table (dsg_debug_need_lists)
 };
 
+// The kernel-selection options (dsg_set_option): one int32_t per option, named after it, so that one pointer-to-member type serves
+// g_options below -- the table that says what each one is, with its default, DSG_* environment default and range (dsg_create fills these)
+struct Options {
+    int32_t fused_attn, fused_mlp, fused_mlp_maxc, fused_readout, fused_patch_embed, fused_rowstats, fused_qkv_attn, fused_merge, loop_graph,
+        prune_masked, dedup_masked, dedup_levels, dedup_batch, dedup_table, dedup_qkv, batch_invariant, gemm_bf16, gemm_split, bf16_act,
+        bf16_pipe, bf16_mlp, bf16_qkv_attn, bf16_proj_mlp, bf16_readout, debug_alloc_fill;
+};
+
 }  // namespace
 
 struct dsg_handle_s {
@@ -195,18 +203,9 @@ struct dsg_handle_s {
     float *merge_wf[DSG_MAX_LAYERS] = {}, *merge_bf[DSG_MAX_LAYERS] = {};   // PatchMerging reduction with its LayerNorm(4C) folded in
     std::vector<AllocRec> derived_allocs;   // freed and rebuilt by every dsg_finalize_weights
     std::vector<AllocRec> allocs;           // everything else the handle itself owns (weights and their copies, tab_*, the train_* arenas)
-    int opt_debug_alloc_fill = 0;           // test hook: pattern every AC_SCRATCH / AC_FINITE allocation is filled with (0: none; launch_debug_fill)
     unsigned long long debug_fill_count = 0;
     std::map<int, std::unique_ptr<Workspace>> ws;
-    // kernel-selection options (dsg_set_option); defaults may be overridden once by DSG_* environment variables
-    bool opt_fused_attn = true, opt_fused_mlp = true, opt_fused_readout = true, opt_fused_pe = true;
-    bool opt_fused_merge_small = false;   // also fuse PatchMerging below the size where it pays (tests force it on)
-    bool opt_prune_masked = true;     // up path: skip rows / windows that only feed masked (padded) tokens (prune_on below)
-    bool opt_dedup_masked = true;     // down path: compute a graph's identical all-padding windows once (dedup_opts_on below)
-    int opt_dedup_batch = 1;          // ... and once for the whole batch in the sampler: 0 never, 1 from DEDUP_BATCH_MIN graphs, 2 always (dedup_stage_mode below)
-    int opt_dedup_levels = 0;         // how many levels may do so: 0 every qualifying one, 1 the finest only, ... (dedup_levels below)
-    int opt_dedup_qkv = 1;            // (2, measurement hook: the split form wherever the lists exist, whatever their share: qk_rule_rows)  the shifted block behind a deduplicated first block projects QKV of the copied pure-window rows once (qkv_dedup_at below)
-    bool opt_dedup_table = true;      // where the batch shares one representative: take it from a per-step table built ahead of the loop (build_pure_table below)
+    Options opt{};   // kernel-selection options (dsg_set_option): dsg_create fills them from g_options -- the defaults, overridden once by DSG_* environment variables
     PrunePlan prune;
     int prof_next_list = -1;          // need list of the next profiled launch (its FLOP figure is scaled by the executed share)
     std::vector<int> prof_list;
@@ -218,27 +217,13 @@ struct dsg_handle_s {
     struct ProfQk { int list = -1, M = 0, role = 0; };
     ProfQk prof_next_qk;
     std::vector<ProfQk> prof_qk;
-    bool opt_fused_merge = true;      // PatchMerging: gather + LayerNorm(4C) inside the reduction GEMM's A path (no merge_ln kernel)
-    bool opt_batch_invariant = false; // every choice of the plan is a function of the geometry and the other options, never of B
-    bool opt_loop_graph = true;       // capture whole step bodies of the reverse loop (0: only the network forward is a graph)
-    bool opt_fused_qkv_attn = true;   // QKV projection + 64-token window attention in one kernel (q, k, v never reach HBM)
-    bool opt_fused_rowstats = true;   // modulate+SiLU and LayerNorm statistics in the producing GEMM's epilogue (fp32 kernel)
-    bool opt_gemm_bf16 = false;                                   // bf16-MFMA GEMMs (fp32 accumulate), opt-in precision mode
-    int opt_bf16_act = 2;                                         // in that mode: 1 hidden / attention-output tensors stored as bf16 (bit-identical), 2 also qkv
-    bool opt_bf16_pipe = true;                                    // in that mode: the bf16 block pipeline of kernels_bx.hip (0: round 2's kernels_lp.hip path)
-    bool opt_bf16_readout = true;                                 // in that pipeline: the read-out's two products on the bf16 matrix pipe
-    bool opt_bf16_proj_mlp = true;                                // in that pipeline: proj + residual + LayerNorm-2 in front of the fused MLP kernel (0: the proj GEMM)
-    int opt_bf16_qkv_attn = 1;                                    // in that pipeline: QKV projection + window attention in one kernel (0: GEMM + attn_bx_kernel through a bf16 qkv tensor)
-    int opt_bf16_mlp = 1;                                         // in that pipeline: the fused fc1-GELU-fc2 kernels (0: two GEMMs with a bf16 hidden tensor; 1: C <= 192 on 4 waves, C = 384 on 8; 2: C = 384 on the 4-wave kernel too; 3: GEMM pair at C = 384)
     std::vector<std::pair<const float *, size_t>> gemm_weights;   // every fp32 GEMM weight (pointer, numel)
     std::map<const float *, void *> w_bf16;                       // bf16 copies, built when the mode is switched on
     std::map<const float *, void *> w_img96;                      // per C = 96 block (key: its fc1_wf): W1 | W2 | Wp in fragment order for mlp96r_bx_kernel
     std::map<const float *, void *> w_qimg;                       // per block (key: its qkv_wf): the QKV weight in qkv_attn_wx_kernel's streaming order
     std::map<const float *, void *> w_img2;                       // the same weights chunk-major for mlp384s_bx_kernel (bf16_mlp = 5)
     std::map<const float *, void *> w_img;                        // per C = 384 block (key: its fc1_wf): W1 | W2 | Wp pre-arranged for mlp384d_bx_kernel's LDS-DMA ring
-    bool opt_gemm_split = false;                                  // split-bf16 GEMMs (3 planes, 6 products): fp32-accurate, opt-in
     std::map<const float *, void *> w_split;                      // [3][N][K] bf16 planes
-    int opt_fused_mlp_maxc = 96;   // at C = 192 the plain GEMM pair is faster than the one-wave-per-SIMD fused kernel
     // per-step (scale,shift) table of the sampler (batch-uniform sigma): [cap][aff_n] and its staging buffers
     int tab_cap = 0;
     int tab_step_cap = 0;          // rows of tab_step: one per EXECUTED step (a resampling walk has more of them than schedule indices)
@@ -451,8 +436,8 @@ int owned_alloc(dsg_handle h, std::vector<AllocRec> &pool, void **p, size_t byte
     bytes = bytes ? bytes : 16;
     HIP_TRY(h, hipMalloc(p, bytes));
     pool.push_back(AllocRec{*p, bytes, cls});
-    if (h->opt_debug_alloc_fill && (cls == AC_SCRATCH || cls == AC_FINITE)) {
-        launch_debug_fill(*p, bytes / 4, h->opt_debug_alloc_fill, 0x5eedull + h->debug_fill_count++, nullptr);
+    if (h->opt.debug_alloc_fill && (cls == AC_SCRATCH || cls == AC_FINITE)) {
+        launch_debug_fill(*p, bytes / 4, h->opt.debug_alloc_fill, 0x5eedull + h->debug_fill_count++, nullptr);
         HIP_TRY(h, hipStreamSynchronize(nullptr));
     }
     return 0;
@@ -621,7 +606,7 @@ int pack_attn_weights(dsg_handle h, BlockPlan &bp) {
 }
 
 const void *bf16_of(dsg_handle h, const float *W) {
-    if (!h->opt_gemm_bf16) return nullptr;
+    if (!h->opt.gemm_bf16) return nullptr;
     auto it = h->w_bf16.find(W);
     return it == h->w_bf16.end() ? nullptr : it->second;
 }
@@ -686,7 +671,7 @@ const void *img2_of(dsg_handle h, const float *fc1_wf) {
 }
 
 const void *split_of(dsg_handle h, const float *W) {
-    if (!h->opt_gemm_split) return nullptr;
+    if (!h->opt.gemm_split) return nullptr;
     auto it = h->w_split.find(W);
     return it == h->w_split.end() ? nullptr : it->second;
 }
@@ -703,9 +688,77 @@ int ensure_split_weights(dsg_handle h) {
     return 0;
 }
 
-bool env_on(const char *name, bool dflt) {
-    const char *v = getenv(name);
-    return v ? (v[0] != '0') : dflt;
+// ---- the option table: dsg_create (defaults and DSG_* environment defaults), dsg_set_option, dsg_get_option and dsg_option_info all
+// walk it, so an option is one row here plus, where what runs differs from what is stored, one `effective` hook
+bool bx_on(dsg_handle h), prune_opts_on(dsg_handle h), dedup_opts_on(dsg_handle h);
+int dedup_levels(dsg_handle h);
+
+enum OptEnv { ENV_FLAG, ENV_INT };      // the environment variable, where set: first character != '0'; or atoi
+enum OptNorm { NORM_ON, NORM_CLAMP };   // what a value becomes: 0 stays 0 and anything else goes to 1..hi; or lo..hi
+// flags.  KEEPS_GRAPHS: the launches and their arguments are the same for every value, so no drop_graphs and no validate_plan;
+// STRICT: a value outside lo..hi is refused, not clamped
+enum : unsigned { OPT_KEEPS_GRAPHS = 1, OPT_STRICT = 2 };
+struct OptRow {
+    const char *name, *env;   // env NULL: no environment default
+    OptEnv env_parse;
+    int32_t dflt;
+    OptNorm norm;
+    int32_t lo, hi;
+    int32_t Options::*field;
+    unsigned flags;
+    int (*effective)(dsg_handle);   // what dsg_get_option reports; NULL: the stored value
+    int32_t normalised(int32_t v) const { return norm == NORM_ON && v == 0 ? 0 : std::min(hi, std::max(norm == NORM_ON ? 1 : lo, v)); }
+};
+#define OPT_FLAG NORM_ON, 0, 1
+#define OPT_WHEN(cond, v) [](dsg_handle h) -> int { return (cond) ? (v) : 0; }
+const OptRow g_options[] = {
+    // the register-resident fused kernels of the narrow levels; at C = 192 the plain GEMM pair is faster than the one-wave-per-SIMD fused MLP
+    {"fused_attn", "DSG_FUSED_ATTN", ENV_FLAG, 1, OPT_FLAG, &Options::fused_attn, 0, nullptr},
+    {"fused_mlp", "DSG_FUSED_MLP", ENV_FLAG, 1, OPT_FLAG, &Options::fused_mlp, 0, nullptr},
+    {"fused_mlp_maxc", "DSG_FUSED_MLP_MAXC", ENV_INT, 96, NORM_CLAMP, INT32_MIN, INT32_MAX, &Options::fused_mlp_maxc, 0, nullptr},
+    {"fused_readout", "DSG_FUSED_READOUT", ENV_FLAG, 1, OPT_FLAG, &Options::fused_readout, 0, nullptr},
+    {"fused_patch_embed", "DSG_FUSED_PE", ENV_FLAG, 1, OPT_FLAG, &Options::fused_patch_embed, 0, nullptr},
+    {"fused_rowstats", "DSG_FUSED_ROWSTATS", ENV_FLAG, 1, OPT_FLAG, &Options::fused_rowstats, 0, nullptr},   // modulate+SiLU and LayerNorm statistics in the producing GEMM's epilogue (fp32 kernel)
+    {"fused_qkv_attn", "DSG_FUSED_QKV_ATTN", ENV_FLAG, 1, OPT_FLAG, &Options::fused_qkv_attn, 0, nullptr},   // QKV projection + 64-token window attention in one kernel (q, k, v never reach HBM)
+    {"fused_merge", "DSG_FUSED_MERGE", ENV_FLAG, 1, NORM_ON, 0, 2, &Options::fused_merge, 0, nullptr},   // PatchMerging: gather + LayerNorm(4C) inside the reduction GEMM's A path (no merge_ln kernel); 2: also below the size where it pays (tests force it on)
+    {"loop_graph", "DSG_LOOP_GRAPH", ENV_FLAG, 1, OPT_FLAG, &Options::loop_graph, 0, nullptr},   // capture whole step bodies of the reverse loop (0: only the network forward is a graph)
+    {"prune_masked", "DSG_PRUNE_MASKED", ENV_FLAG, 1, OPT_FLAG, &Options::prune_masked, 0, OPT_WHEN(prune_opts_on(h), 1)},   // up path: skip rows / windows that only feed masked (padded) tokens (prune_on).  What runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
+    {"dedup_masked", "DSG_DEDUP_MASKED", ENV_FLAG, 1, OPT_FLAG, &Options::dedup_masked, 0, OPT_WHEN(dedup_opts_on(h), 1)},   // down path: compute a graph's identical all-padding windows once (dedup_opts_on).  What runs (in the sampler): 0 wherever the pruning is off, or the fused C = 96 kernels are
+    {"dedup_levels", "DSG_DEDUP_LEVELS", ENV_INT, 0, NORM_CLAMP, 0, INT32_MAX, &Options::dedup_levels, 0, dedup_levels},   // how many levels may do so: 0 every qualifying one, 1 the finest only, ...  What runs (in the sampler, where PatchMerging takes its partial-statistics form)
+    // ... and once for the whole batch in the sampler: 0 never, 1 from DEDUP_BATCH_MIN graphs, 2 always (dedup_stage_mode).  Acts where the lists
+    // are written (stage_flags) and nowhere else: the launches, their grids and the list addresses are the same for every value, so the
+    // captured graphs stay -- one captured under either kind of list replays under the other
+    {"dedup_batch", "DSG_DEDUP_BATCH", ENV_INT, 1, NORM_CLAMP, 0, 2, &Options::dedup_batch, OPT_KEEPS_GRAPHS, OPT_WHEN(dedup_opts_on(h), h->opt.dedup_batch)},
+    // where the batch shares one representative: take it from a per-step table built ahead of the loop (build_pure_table).  Likewise: the step
+    // bodies are the same for both values -- the fill launch always carries the table's address (growing the table drops them) and reads
+    // on the device which kind of list the last staging wrote
+    {"dedup_table", "DSG_DEDUP_TABLE", ENV_FLAG, 1, OPT_FLAG, &Options::dedup_table, OPT_KEEPS_GRAPHS, OPT_WHEN(dedup_opts_on(h) && h->opt.dedup_batch > 0, h->opt.dedup_table)},
+    // the shifted block behind a deduplicated first block projects QKV of the copied pure-window rows once (qkv_dedup_at: the blocks that qualify);
+    // 2, measurement hook: the split form wherever the lists exist, whatever their share (qk_rule_rows).  The step bodies differ: graphs are dropped
+    {"dedup_qkv", "DSG_DEDUP_QKV", ENV_FLAG, 1, NORM_CLAMP, 0, 2, &Options::dedup_qkv, 0, OPT_WHEN(dedup_opts_on(h), h->opt.dedup_qkv)},
+    {"batch_invariant", nullptr, ENV_FLAG, 0, OPT_FLAG, &Options::batch_invariant, 0, nullptr},   // every choice of the plan is a function of the geometry and the other options, never of B
+    {"gemm_bf16", "DSG_GEMM_BF16", ENV_FLAG, 0, OPT_FLAG, &Options::gemm_bf16, 0, OPT_WHEN(!h->opt.gemm_split, h->opt.gemm_bf16)},   // bf16-MFMA GEMMs (fp32 accumulate) / split-bf16 GEMMs (3 planes, 6 products; fp32-accurate): opt-in precision modes, the second takes precedence
+    {"gemm_split", "DSG_GEMM_SPLIT", ENV_FLAG, 0, OPT_FLAG, &Options::gemm_split, 0, nullptr},
+    // in the bf16 mode: 1 hidden / attention-output tensors stored as bf16 (bit-identical), 2 also qkv.  Acts whenever round 2's bf16 path is what
+    // runs (pipeline off, or a width it does not take)
+    {"bf16_act", nullptr, ENV_INT, 2, NORM_CLAMP, 0, 2, &Options::bf16_act, 0, OPT_WHEN(h->opt.gemm_bf16 && !h->opt.gemm_split && !bx_on(h), h->opt.bf16_act)},
+    {"bf16_pipe", "DSG_BF16_PIPE", ENV_FLAG, 1, OPT_FLAG, &Options::bf16_pipe, 0, OPT_WHEN(bx_on(h), 1)},   // in that mode: the bf16 block pipeline of kernels_bx.hip (0: round 2's kernels_lp.hip path)
+    // in that pipeline: the fused fc1-GELU-fc2 kernels (0: two GEMMs with a bf16 hidden tensor; 1: C <= 192 on 4 waves, C = 384 on 8; 2: C = 384 on the
+    // 4-wave kernel too; 3: GEMM pair at C = 384).  The variable is a dev knob: A/B of the C = 384 MLP kernels (1 LDS-DMA, 4 round 3's)
+    {"bf16_mlp", "DSG_BF16_MLP", ENV_INT, 1, NORM_CLAMP, 0, 6, &Options::bf16_mlp, 0, OPT_WHEN(bx_on(h), h->opt.bf16_mlp)},
+    {"bf16_qkv_attn", "DSG_BF16_QA", ENV_INT, 1, NORM_CLAMP, 0, 3, &Options::bf16_qkv_attn, 0, OPT_WHEN(bx_on(h), h->opt.bf16_qkv_attn)},   // QKV projection + window attention in one kernel (0: GEMM + attn_bx_kernel through a bf16 qkv tensor; dev knob: 2 = the block-per-head kernel)
+    {"bf16_proj_mlp", nullptr, ENV_FLAG, 1, OPT_FLAG, &Options::bf16_proj_mlp, 0, OPT_WHEN(bx_on(h) && h->opt.bf16_mlp && h->opt.bf16_proj_mlp, 1)},   // proj + residual + LayerNorm-2 in front of the fused MLP kernel (0: the proj GEMM)
+    {"bf16_readout", nullptr, ENV_FLAG, 1, OPT_FLAG, &Options::bf16_readout, 0, OPT_WHEN(bx_on(h) && h->opt.bf16_readout && h->opt.fused_readout, 1)},   // the read-out's two products on the bf16 matrix pipe
+    {"debug_alloc_fill", nullptr, ENV_INT, 0, NORM_CLAMP, 0, 4, &Options::debug_alloc_fill, OPT_KEEPS_GRAPHS | OPT_STRICT, nullptr},   // test hook: the pattern every AC_SCRATCH / AC_FINITE allocation is filled with (0: none; launch_debug_fill).  No launch of any entry point changes
+};
+#undef OPT_FLAG
+#undef OPT_WHEN
+const int N_OPTIONS = sizeof(g_options) / sizeof(g_options[0]);
+
+const OptRow *find_option(const char *name) {
+    for (const OptRow &r : g_options)
+        if (strcmp(r.name, name) == 0) return &r;
+    return nullptr;
 }
 
 }  // namespace
@@ -745,26 +798,10 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     h->Kp = ((h->Cin + 31) / 32) * 32;
     build_specs(h);
     if (!gelu_table()) { delete h; return DSG_ERR_HIP; }
-    h->opt_fused_attn = env_on("DSG_FUSED_ATTN", true);
-    h->opt_fused_mlp = env_on("DSG_FUSED_MLP", true);
-    h->opt_fused_readout = env_on("DSG_FUSED_READOUT", true);
-    h->opt_fused_pe = env_on("DSG_FUSED_PE", true);
-    h->opt_fused_rowstats = env_on("DSG_FUSED_ROWSTATS", true);
-    h->opt_fused_qkv_attn = env_on("DSG_FUSED_QKV_ATTN", true);
-    h->opt_loop_graph = env_on("DSG_LOOP_GRAPH", true);
-    h->opt_fused_merge = env_on("DSG_FUSED_MERGE", true);
-    h->opt_prune_masked = env_on("DSG_PRUNE_MASKED", true);
-    h->opt_dedup_masked = env_on("DSG_DEDUP_MASKED", true);
-    if (getenv("DSG_DEDUP_BATCH")) h->opt_dedup_batch = std::min(2, std::max(0, atoi(getenv("DSG_DEDUP_BATCH"))));
-    if (getenv("DSG_DEDUP_LEVELS")) h->opt_dedup_levels = std::max(0, atoi(getenv("DSG_DEDUP_LEVELS")));
-    h->opt_dedup_table = env_on("DSG_DEDUP_TABLE", true);
-    h->opt_dedup_qkv = env_on("DSG_DEDUP_QKV", true) ? 1 : 0;
-    if (getenv("DSG_FUSED_MLP_MAXC")) h->opt_fused_mlp_maxc = atoi(getenv("DSG_FUSED_MLP_MAXC"));
-    h->opt_gemm_bf16 = env_on("DSG_GEMM_BF16", false);
-    h->opt_bf16_pipe = env_on("DSG_BF16_PIPE", true);
-    if (getenv("DSG_BF16_QA")) h->opt_bf16_qkv_attn = atoi(getenv("DSG_BF16_QA"));   // dev knob: 2 = the block-per-head QKV + attention kernel
-    if (getenv("DSG_BF16_MLP")) h->opt_bf16_mlp = atoi(getenv("DSG_BF16_MLP"));   // dev knob: A/B of the C = 384 MLP kernels (1 LDS-DMA, 4 round 3's)
-    h->opt_gemm_split = env_on("DSG_GEMM_SPLIT", false);
+    for (const OptRow &r : g_options) {   // the default, or the environment's: read the row's way and normalised like dsg_set_option's values
+        const char *v = r.env ? getenv(r.env) : nullptr;
+        h->opt.*r.field = !v ? r.dflt : r.normalised(r.env_parse == ENV_INT ? atoi(v) : v[0] != '0');
+    }
     {   // the list GEMM picks its form from how many CUs a launch would fill (kernels.h: gemm_thin_rule); unknown = never thin
         int dev = 0, n_cu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) h->n_cu = n_cu;
@@ -1020,8 +1057,8 @@ int dsg_finalize_weights(dsg_handle h) {
     if (h->ro_gext) h->gemm_weights.push_back({h->ro_gext, (size_t)E * 128});
     if (h->ro_fapb) h->gemm_weights.push_back({h->ro_fapb, (size_t)3 * 6 * 64 * 8});
     if (h->ro_f2pb) h->gemm_weights.push_back({h->ro_f2pb, (size_t)3 * 2 * 64 * 8});
-    if (h->opt_gemm_bf16) if (int rc = ensure_bf16_weights(h)) return rc;
-    if (h->opt_gemm_split) if (int rc = ensure_split_weights(h)) return rc;
+    if (h->opt.gemm_bf16) if (int rc = ensure_bf16_weights(h)) return rc;
+    if (h->opt.gemm_split) if (int rc = ensure_split_weights(h)) return rc;
     h->finalized = true;
     h->ever_finalized = true;
     return DSG_OK;
@@ -1135,14 +1172,14 @@ void tap(dsg_handle h, const char *name, const float *src, size_t numel, hipStre
     if (h->prof_on) snprintf(tg_, sizeof(tg_), "gemm M=%d N=%d K=%d ln=%d act=%d res=%d", (g).M, (g).N, (g).K, ((g).ln_stats != nullptr) + 2 * ((g).ln_part != nullptr) + 4 * ((g).stats_out != nullptr) + 8 * ((g).mod_aff != nullptr), (g).act, (g).res != nullptr); \
     (g).n_cu = h->n_cu; h->prof_next_thin_n = gemm_has_thin(g) ? (g).N : 0; \
     ProfScope ps_(h, s, PK_GEMM, 2.0 * (double)(g).M * (double)(g).N * (double)(g).K, tg_); \
-    g_fixed_tiles = h->opt_batch_invariant; const bool built_ = launch_gemm((g), s); g_fixed_tiles = false; \
+    g_fixed_tiles = h->opt.batch_invariant; const bool built_ = launch_gemm((g), s); g_fixed_tiles = false; \
     if (!built_) plan_fail(h, "gemm: argument combination not built (M=%d N=%d K=%d ln=%d act=%d res=%d bf16 A/C=%d/%d)", (g).M, (g).N, (g).K, ((g).ln_stats != nullptr) + 2 * ((g).ln_part != nullptr), (g).act, (g).res != nullptr, (g).a_bf16, (g).c_bf16); } while (0)
 #define P_KERN(kind, flops, call) do { ProfScope ps_(h, s, (kind), (flops), #call); call; } while (0)
 
 // Row-kernel fusion (fp32 GEMM kernel only; off while debug taps want the un-modulated block outputs): the GEMM that produces
 // a block's input also applies that block's modulate+SiLU and leaves per-column-tile (sum, sumsq) partials of the stored rows
 // in w->stats, from which the consuming GEMM forms the LayerNorm statistics -- mod_stats / ln_stats launches disappear.
-bool rowstats_on(dsg_handle h) { return h->opt_fused_rowstats && !h->opt_gemm_split && h->taps.empty(); }   // fp32 and bf16 GEMM kernels
+bool rowstats_on(dsg_handle h) { return h->opt.fused_rowstats && !h->opt.gemm_split && h->taps.empty(); }   // fp32 and bf16 GEMM kernels
 // does block `nb` take its input pre-modulated?  Generic blocks also read the LN1 partials the producer leaves; the C = 96 fused
 // attention kernel only skips its own modulate+SiLU (twice: prologue and shortcut) and keeps computing LN1 itself.
 bool wants_premod(dsg_handle h, const BlockPlan *nb) { return nb && rowstats_on(h); }
@@ -1226,8 +1263,8 @@ const PrunePlan &prune_plan(dsg_handle h) { if (!h->prune.built) build_prune_pla
 // Decided at plan time.  Off with debug taps (they return whole tensors: the same rule as rowstats_on), in the split / bf16 modes,
 // and whenever a launch of the up path is not one of the kernels that take a list.
 bool prune_opts_on(dsg_handle h) {
-    return h->opt_prune_masked && h->taps.empty() && !h->opt_gemm_split && !h->opt_gemm_bf16 && rowstats_on(h) && h->opt_fused_qkv_attn &&
-           h->opt_fused_readout && h->ro_fap && prune_plan(h).np.n_lists > 0;
+    return h->opt.prune_masked && h->taps.empty() && !h->opt.gemm_split && !h->opt.gemm_bf16 && rowstats_on(h) && h->opt.fused_qkv_attn &&
+           h->opt.fused_readout && h->ro_fap && prune_plan(h).np.n_lists > 0;
 }
 bool prune_on(dsg_handle h, const Workspace *w) {
     // (the row-mapped GEMM addresses whole tensors through one buffer descriptor: the widest one must stay below 2 GiB)
@@ -1238,8 +1275,8 @@ bool prune_on(dsg_handle h, const Workspace *w) {
 // long K loop costs more than the small merge_ln launch it replaces: measured 103 vs 81 + 13 us at M = 4096, K = 1536)
 bool merge_fused_at(dsg_handle h, int B, int l) {
     const int C = h->E << l, res = h->N >> l;
-    return l < h->L - 1 && h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16 && C % 32 == 0 &&
-           (B * res * res / 4 >= 8192 || h->opt_fused_merge_small || h->opt_batch_invariant);   // "batch_invariant": the size plays no part
+    return l < h->L - 1 && h->opt.fused_merge != 0 && rowstats_on(h) && !h->opt.gemm_bf16 && C % 32 == 0 &&
+           (B * res * res / 4 >= 8192 || h->opt.fused_merge > 1 || h->opt.batch_invariant);   // "batch_invariant": the size plays no part
 }
 // Pure-window deduplication of the down path (options "dedup_masked", "dedup_levels", "dedup_batch"; rule and list formats: kernels.h).
 // At a token (i, j) with a padded endpoint fused_patch_embed96_kernel zeroes the node channels itself, and the adjacency channels it
@@ -1280,18 +1317,18 @@ bool merge_fused_at(dsg_handle h, int B, int l) {
 // * Forward time (forward_fixed): nothing is decided.  The lists are whatever the last staging wrote; under DD_BATCH the forward
 //   checks that it runs at the depth they were trimmed for and reads the batch-uniform row.
 bool dedup_opts_on(dsg_handle h) {
-    if (!h->opt_dedup_masked || !prune_opts_on(h) || prune_plan(h).np.dd_n == 0) return false;
+    if (!h->opt.dedup_masked || !prune_opts_on(h) || prune_plan(h).np.dd_n == 0) return false;
     const BlockPlan &b0 = h->down[0][0];
-    return h->opt_fused_pe && h->pe_wp && (h->Kp == 32 || h->Kp == 64) && h->opt_fused_attn && b0.wqp && h->opt_fused_mlp && b0.w1p &&
-           b0.C <= h->opt_fused_mlp_maxc;
+    return h->opt.fused_patch_embed && h->pe_wp && (h->Kp == 32 || h->Kp == 64) && h->opt.fused_attn && b0.wqp && h->opt.fused_mlp && b0.w1p &&
+           b0.C <= h->opt.fused_mlp_maxc;
 }
 // how many levels may deduplicate (option "dedup_levels": 0 = every qualifying one), the finest included; 0 when none does
 int dedup_levels(dsg_handle h) {
     if (!dedup_opts_on(h)) return 0;
     int n = 1;
-    if (h->opt_fused_merge && rowstats_on(h) && !h->opt_gemm_bf16)
+    if (h->opt.fused_merge != 0 && rowstats_on(h) && !h->opt.gemm_bf16)
         while (n < prune_plan(h).np.dd_n && (h->E << (n - 1)) % 32 == 0) n++;
-    return h->opt_dedup_levels > 0 ? std::min(n, h->opt_dedup_levels) : n;
+    return h->opt.dedup_levels > 0 ? std::min(n, h->opt.dedup_levels) : n;
 }
 int dedup_chain_depth(dsg_handle h, const Workspace *w) {
     if (!w->dd_rep || !prune_on(h, w)) return 0;
@@ -1305,24 +1342,24 @@ int dedup_chain_depth(dsg_handle h, const Workspace *w) {
 // with equal rows and statistics --, is shifted (an unshifted block would have been deduplicated whole) and takes the fused QKV +
 // attention GEMM on 8 x 8 windows in fp32.  Which form runs is then the device's choice from the staged lists (kernels.h: qk_split_rule).
 // the rows the rule compares the listed rows with: the launch's M; "dedup_qkv" 2 (measurement of the rule's bound) takes the split form always
-int qk_rule_rows(dsg_handle h, int M) { return h->opt_dedup_qkv == 2 ? 0x7fffffff : M; }
+int qk_rule_rows(dsg_handle h, int M) { return h->opt.dedup_qkv == 2 ? 0x7fffffff : M; }
 bool qkv_dedup_at(dsg_handle h, const Workspace *w, int l, int j, int depth) {
-    if (j != 1 || l >= depth || l > NEED_MAX_DD_UP || !h->opt_dedup_qkv || !dedup_opts_on(h) || w->need.qk_runs[l] < 0 || w->need.qk_src[l] < 0) return false;
+    if (j != 1 || l >= depth || l > NEED_MAX_DD_UP || !h->opt.dedup_qkv || !dedup_opts_on(h) || w->need.qk_runs[l] < 0 || w->need.qk_src[l] < 0) return false;
     const BlockPlan &b = h->down[l][1];
-    return b.shift > 0 && b.ws == 8 && !(h->opt_fused_attn && b.wqp) && h->opt_fused_qkv_attn && !h->opt_gemm_bf16 && !h->opt_gemm_split;
+    return b.shift > 0 && b.ws == 8 && !(h->opt.fused_attn && b.wqp) && h->opt.fused_qkv_attn && !h->opt.gemm_bf16 && !h->opt.gemm_split;
 }
 constexpr int DEDUP_BATCH_MIN = 16;
 int dedup_stage_mode(dsg_handle h, const Workspace *w, bool zero_padded, bool uniform_row, int *trim, int *depth, bool table = false) {
     *trim = 0; *depth = 0;
     if (!zero_padded) return DD_OFF;
     const int d = dedup_chain_depth(h, w);
-    if (!uniform_row || d == 0 || h->opt_dedup_batch == 0 || (h->opt_dedup_batch == 1 && w->B < DEDUP_BATCH_MIN)) return DD_GRAPH;
+    if (!uniform_row || d == 0 || h->opt.dedup_batch == 0 || (h->opt.dedup_batch == 1 && w->B < DEDUP_BATCH_MIN)) return DD_GRAPH;
     *depth = d;
     const PrunePlan &pp = prune_plan(h);
     for (int k = 0; k + 1 < d; k++)
         if (k == 0 || pp.coarse[h->L - k] >= 0) *trim |= 1 << k;
     // `table`: the caller has built this call's table of pure-window rows (sample_impl): nothing computes the shared representative
-    return table && h->opt_dedup_table && w->tab_pure ? DD_TABLE : DD_BATCH;
+    return table && h->opt.dedup_table && w->tab_pure ? DD_TABLE : DD_BATCH;
 }
 struct NeedRef { const int *list = nullptr, *cnt = nullptr; int id = -1; };
 NeedRef need_ref(dsg_handle h, const Workspace *w, int id) {
@@ -1348,14 +1385,14 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
     const int B = w->B, T = b.res * b.res, C = b.C, M = B * T, Hd = h->cfg.mlp_ratio * C;
     const std::string &p = b.prefix;
     const bool fuse = rowstats_on(h);
-    const bool mlp_fused = h->opt_fused_mlp && b.w1p && C <= h->opt_fused_mlp_maxc;
+    const bool mlp_fused = h->opt.fused_mlp && b.w1p && C <= h->opt.fused_mlp_maxc;
     // bf16 mode: a tensor whose only consumer is the bf16 GEMM (which rounds its A operand to bf16 on the way into LDS) is stored as
     // bf16 by its producer -- same values bit for bit, half the bytes, no conversion in the consumer (kernels_lp.hip ABF / CBF)
     auto bf16_tensor_ok = [&](const float *W, int K) {
-        return h->opt_gemm_bf16 && !h->opt_gemm_split && h->opt_bf16_act && K % 64 == 0 && h->taps.empty() && bf16_of(h, W) != nullptr;
+        return h->opt.gemm_bf16 && !h->opt.gemm_split && h->opt.bf16_act && K % 64 == 0 && h->taps.empty() && bf16_of(h, W) != nullptr;
     };
     GemmArgs g;
-    if (h->opt_fused_attn && b.wqp) {
+    if (h->opt.fused_attn && b.wqp) {
         // modulate+SiLU, LN1, QKV, window attention, proj and the residual in one register-resident kernel
         WinGeom wg{b.res, b.ws, b.shift, b.heads, C};
         h->prof_next_list = need.wins.id;
@@ -1371,7 +1408,7 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
         g.W = b.qkv_wf; g.bias = b.qkv_bf; g.N = 3 * C;
         WinGeom wg{b.res, b.ws, b.shift, b.heads, C};
         bool attn_done = false, att_bf16 = false;
-        if (h->opt_fused_qkv_attn && (b.ws == 8 || b.ws == 10) && !h->opt_gemm_bf16 && !h->opt_gemm_split) {
+        if (h->opt.fused_qkv_attn && (b.ws == 8 || b.ws == 10) && !h->opt.gemm_bf16 && !h->opt.gemm_split) {
             // LN1 -> QKV -> softmax(q k^T + bias) v in one kernel: q, k, v of (two windows, one head) stay in LDS
             g.attn_bias = b.biasT; g.wg = wg; g.attn_batch = B; g.C = w->att; g.ldc = C;
             g.row_list = need.wins.list; g.row_cnt = need.wins.cnt;   // (a window list here)
@@ -1410,7 +1447,7 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
             att_bf16 = bf16_tensor_ok(WT(h, p + ".attn.proj.weight"), C);
             // level 2: q, k, v leave the QKV GEMM as bf16 too (the attention math stays fp32 on the widened values; this one
             // changes results -- within the bf16 mode's stated bar -- because the fp32 attention kernel is the consumer)
-            const bool qkv_bf16 = att_bf16 && h->opt_bf16_act >= 2 && bf16_of(h, b.qkv_wf) != nullptr;
+            const bool qkv_bf16 = att_bf16 && h->opt.bf16_act >= 2 && bf16_of(h, b.qkv_wf) != nullptr;
             g.c_bf16 = qkv_bf16;
             P_GEMM_LP(g);
             P_KERN(PK_ATTN, 4.0 * (double)M * (double)(b.ws * b.ws) * (double)C,
@@ -1435,7 +1472,7 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
                                 WT(h, p + ".mlp.fc2.bias"), M, C, st ? w->stats : nullptr, s, need.rows.list, need.rows.cnt));
         return BlockOut{false, st ? 1 : 0};   // the fused MLP has no modulate epilogue: the next block runs its own mod_stats
     }
-    const bool ln2_part = fuse && !(h->opt_fused_attn && b.wqp);   // the proj GEMM above left the partials
+    const bool ln2_part = fuse && !(h->opt.fused_attn && b.wqp);   // the proj GEMM above left the partials
     if (!ln2_part) P_KERN(PK_ROW, 0.0, launch_ln_stats(w->x, w->stats, M, C, s));
     g = GemmArgs();
     g.A = w->x; g.lda = C; g.K1 = C; g.K = C; g.M = M; g.N = Hd;
@@ -1443,17 +1480,23 @@ BlockOut run_block(dsg_handle h, Workspace *w, const BlockPlan &b, bool premod, 
     else g.ln_stats = w->stats;   // gamma/beta of norm2 are folded into fc1_wf / fc1_bf
     g.W = b.fc1_wf; g.bias = b.fc1_bf; g.act = ACT_GELU;
     g.C = w->hid; g.ldc = Hd;
+#ifdef DSG_MEASURE
     // measurement only (DSG_HID_EXP=1, wrong results): a leading dimension of 0 gives the kernels an empty buffer range -- fc1's stores of the
     // 4C-wide hidden tensor are dropped and fc2's loads of it return zeros without memory traffic, every instruction still issues: the
-    // upper bound of what a fused fc1 -> GELU -> fc2 kernel could gain by keeping the hidden tensor on the chip (profiles/r4/fp32_upper_bounds.txt)
+    // upper bound of what a fused fc1 -> GELU -> fc2 kernel could gain by keeping the hidden tensor on the chip (profiles/r4/fp32_upper_bounds.txt).
+    // Not in the product build: `make CXXFLAGS+=-DDSG_MEASURE` brings it back for such runs
     static const bool hid_exp = getenv("DSG_HID_EXP") != nullptr;
     if (hid_exp) g.ldc = 0;
+#endif
     const bool hid_bf16 = bf16_tensor_ok(WT(h, p + ".mlp.fc2.weight"), Hd) && bf16_of(h, b.fc1_wf) != nullptr;
     g.c_bf16 = hid_bf16;
     g.row_list = need.rows.list; g.row_cnt = need.rows.cnt; h->prof_next_list = need.rows.id;
     P_GEMM_LP(g);
     g = GemmArgs();
-    g.A = w->hid; g.lda = hid_exp ? 0 : Hd; g.K1 = Hd; g.K = Hd; g.M = M; g.N = C;
+    g.A = w->hid; g.lda = Hd; g.K1 = Hd; g.K = Hd; g.M = M; g.N = C;
+#ifdef DSG_MEASURE
+    if (hid_exp) g.lda = 0;
+#endif
     g.a_bf16 = hid_bf16;
     g.W = WT(h, p + ".mlp.fc2.weight"); g.bias = WT(h, p + ".mlp.fc2.bias");
     g.res = w->x; g.ldres = C; g.C = w->x; g.ldc = C;
@@ -1490,12 +1533,12 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
     const int B = w->B, N = h->N, E = h->E, T0 = N * N;
     GemmArgs g;
     bool pe_done = false, pe_premod = false;
-    if (h->opt_fused_pe && h->pe_wp) {
+    if (h->opt.fused_patch_embed && h->pe_wp) {
         h->prof_next_list = pe_runs.id;
         ProfScope ps_(h, s, PK_FUSED, 2.0 * (double)B * T0 * E * h->Cin, "launch_fused_patch_embed96");
         // the first block's modulate+SiLU rides along when that block is the fused C = 96 attention kernel (which then skips it)
         const BlockPlan *b0 = h->down[0].empty() ? nullptr : &h->down[0][0];
-        pe_premod = wants_premod(h, b0) && (fp32_rule ? (h->opt_fused_attn && b0->wqp) : true);
+        pe_premod = wants_premod(h, b0) && (fp32_rule ? (h->opt.fused_attn && b0->wqp) : true);
         pe_done = launch_fused_patch_embed96(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
                                              WT(h, "patch_embed.proj.bias"), WT(h, "patch_embed.norm.weight"),
                                              WT(h, "patch_embed.norm.bias"), w->aff, w->aff_ld, h->pe_aff_off, pe_premod ? b0->aff_off : -1,
@@ -1520,20 +1563,19 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
 }
 
 // final norm + read_out + heads (diffusesg.py:758-761, :806-825): w->x -> (f_adj, f_node)
-bool bx_on(dsg_handle h);
 void readout_stage(dsg_handle h, Workspace *w, hipStream_t s) {
     const int B = w->B, N = h->N, E = h->E, T0 = N * N;
     GemmArgs g;
     const int M0 = B * T0;
-    if (h->opt_fused_readout && h->ro_fap && h->taps.empty()) {
+    if (h->opt.fused_readout && h->ro_fap && h->taps.empty()) {
         // the pooling partials of node row r go to slot (32-token tile) - (r N) / 32: where a graph's rows sit relative to the tiles, and with
         // it the order its partials are added in, is the same for every b only if a graph is a whole number of tiles
-        if (h->opt_batch_invariant && T0 % 32 != 0)
+        if (h->opt.batch_invariant && T0 % 32 != 0)
             plan_fail(h, "batch_invariant: the fused read-out's pooling slots depend on a graph's position in the batch unless N * N is a multiple "
                          "of 32 (N = %d); set \"fused_readout\" = 0 or leave the option off", N);
         // one pass over x: LN, folded read_out+fc1, GELU, fc2, masked adjacency store; pooled LN(x) for the node head
         // (the bf16 block pipeline runs the two products of the read-out on the bf16 matrix pipe as well: option bf16_readout)
-        const float *fap_b = (bx_on(h) && h->opt_bf16_readout && h->ro_fapb) ? (const float *)bf16_of(h, h->ro_fapb) : nullptr;
+        const float *fap_b = (bx_on(h) && h->opt.bf16_readout && h->ro_fapb) ? (const float *)bf16_of(h, h->ro_fapb) : nullptr;
         const float *f2p_b = fap_b ? (const float *)bf16_of(h, h->ro_f2pb) : nullptr;
         const bool ro_bf = fap_b && f2p_b;
         P_KERN(PK_FUSED, 2.0 * (double)M0 * E * (E + 32.0),
@@ -1585,7 +1627,7 @@ void readout_stage(dsg_handle h, Workspace *w, hipStream_t s) {
 enum BxState { BX_RAW = 0, BX_MOD = 1, BX_READY = 2 };
 // (the pipeline's kernels are built and tested for embed_dim = 96 -- every configuration of the reference; any other width keeps
 // round 2's kernels_lp.hip path instead of meeting an uncovered shape half-way through a forward, and get_option reports that)
-bool bx_on(dsg_handle h) { return h->opt_gemm_bf16 && !h->opt_gemm_split && h->opt_bf16_pipe && h->E == 96; }
+bool bx_on(dsg_handle h) { return h->opt.gemm_bf16 && !h->opt.gemm_split && h->opt.bf16_pipe && h->E == 96; }
 
 #define P_BX(g, tag)                                                                                                           \
     do {                                                                                                                       \
@@ -1621,13 +1663,13 @@ BxState run_block_bx(dsg_handle h, Workspace *w, const BlockPlan &b, BxState st,
     BxGemm g;
     WinGeom wg{b.res, b.ws, b.shift, b.heads, C};
     bool fused_qa = false;
-    if (h->opt_bf16_qkv_attn && h->taps.empty()) {   // (the qkv tap wants the tensor)
+    if (h->opt.bf16_qkv_attn && h->taps.empty()) {   // (the qkv tap wants the tensor)
         BxQkvAttn qa;
         qa.xn = w->xn; qa.W = bf16_of(h, b.qkv_wf); qa.bias = b.qkv_bf; qa.biasP = b.biasP; qa.out = w->att; qa.B = B; qa.g = wg;
         { auto it = h->w_qimg.find(b.qkv_wf); qa.Wimg = it == h->w_qimg.end() ? nullptr : it->second; }
         qa.biasF = b.biasF;
         // 10 x 10 windows: 1 the wave-per-unit kernel, 2 the block-per-head kernel (its A/B), 3 wave-per-unit only where a block lies in one window (heads % 4 == 0)
-        qa.variant = (h->opt_bf16_qkv_attn == 2 || (h->opt_bf16_qkv_attn == 3 && b.heads % 4 != 0)) ? 1 : 0;
+        qa.variant = (h->opt.bf16_qkv_attn == 2 || (h->opt.bf16_qkv_attn == 3 && b.heads % 4 != 0)) ? 1 : 0;
         ProfScope ps_(h, s, PK_ATTN, 2.0 * (double)M * 3.0 * C * C + 4.0 * (double)M * (double)(b.ws * b.ws) * (double)C, "qkv_attn_bx");
         fused_qa = launch_qkv_attn_bx(qa, s);
     }
@@ -1640,8 +1682,8 @@ BxState run_block_bx(dsg_handle h, Workspace *w, const BlockPlan &b, BxState st,
             plan_fail(h, "bf16 pipeline: %s: window attention not built (window %d, C=%d)", p.c_str(), b.ws, C);
     }
     // the fused MLP kernel can take the proj linear, the residual and LayerNorm-2 in front (x + proj(att) never goes to HBM)
-    const bool mlp_fused = h->opt_bf16_mlp && h->cfg.mlp_ratio == 4 && (C == 96 || C == 192 || (C == 384 && h->opt_bf16_mlp != 3));
-    const bool proj_in_mlp = mlp_fused && h->opt_bf16_proj_mlp && h->taps.empty() && (C == 96 || C == 192 || (C == 384 && (h->opt_bf16_mlp == 1 || h->opt_bf16_mlp == 4 || h->opt_bf16_mlp == 5 || h->opt_bf16_mlp == 6)));
+    const bool mlp_fused = h->opt.bf16_mlp && h->cfg.mlp_ratio == 4 && (C == 96 || C == 192 || (C == 384 && h->opt.bf16_mlp != 3));
+    const bool proj_in_mlp = mlp_fused && h->opt.bf16_proj_mlp && h->taps.empty() && (C == 96 || C == 192 || (C == 384 && (h->opt.bf16_mlp == 1 || h->opt.bf16_mlp == 4 || h->opt.bf16_mlp == 5 || h->opt.bf16_mlp == 6)));
     const bool full = bx_full_row(C);
     if (!proj_in_mlp) {
         g = BxGemm();
@@ -1659,10 +1701,10 @@ BxState run_block_bx(dsg_handle h, Workspace *w, const BlockPlan &b, BxState st,
     if (mlp_fused) {
         BxMlp m;
         // C = 384: 1 -> the LDS-DMA kernel on pre-arranged weight images (round 4), 4 -> round 3's eight-wave kernel, 2 -> the four-wave one
-        m.wide8 = h->opt_bf16_mlp == 2 ? 0 : (h->opt_bf16_mlp == 4 ? 2 : (h->opt_bf16_mlp == 5 ? 3 : 1));
+        m.wide8 = h->opt.bf16_mlp == 2 ? 0 : (h->opt.bf16_mlp == 4 ? 2 : (h->opt.bf16_mlp == 5 ? 3 : 1));
         m.img = C == 384 ? img_of(h, b.fc1_wf) : nullptr;
         m.img2 = C == 384 ? img2_of(h, b.fc1_wf) : nullptr;
-        if (C == 96 && h->opt_bf16_mlp == 6) { auto it = h->w_img96.find(b.fc1_wf); m.img96 = it == h->w_img96.end() ? nullptr : it->second; }   // (6: level 0 on the LDS-resident kernel -- measured at par, not the default)
+        if (C == 96 && h->opt.bf16_mlp == 6) { auto it = h->w_img96.find(b.fc1_wf); m.img96 = it == h->w_img96.end() ? nullptr : it->second; }   // (6: level 0 on the LDS-resident kernel -- measured at par, not the default)
         if (proj_in_mlp) { m.att = w->att; m.Wp = bf16_of(h, WT(h, p + ".attn.proj.weight")); m.bp = WT(h, p + ".attn.proj.bias"); }
         m.xn = w->xn; m.x = w->x; m.W1 = bf16_of(h, b.fc1_wf); m.b1 = b.fc1_bf;
         m.W2 = bf16_of(h, WT(h, p + ".mlp.fc2.weight")); m.b2 = WT(h, p + ".mlp.fc2.bias"); m.M = M; m.C = C;
@@ -2217,62 +2259,19 @@ size_t dsg_workspace_bytes(dsg_handle h, int32_t B) {
 
 int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     if (!h || !name) return DSG_ERR_INVALID;
-    const std::string n(name);
-    // the option set as it stands: restored if the new selection meets a shape no kernel covers (below)
-    auto opts = [h]() {
-        return std::tie(h->opt_fused_attn, h->opt_fused_mlp, h->opt_fused_mlp_maxc, h->opt_fused_readout, h->opt_fused_pe, h->opt_fused_rowstats,
-                        h->opt_fused_qkv_attn, h->opt_loop_graph, h->opt_bf16_act, h->opt_bf16_pipe, h->opt_bf16_mlp, h->opt_bf16_qkv_attn,
-                        h->opt_bf16_proj_mlp, h->opt_bf16_readout, h->opt_fused_merge, h->opt_fused_merge_small, h->opt_gemm_bf16, h->opt_gemm_split, h->opt_prune_masked,
-                        h->opt_batch_invariant, h->opt_dedup_masked, h->opt_dedup_levels, h->opt_dedup_batch, h->opt_dedup_qkv);
-    };
-    const std::tuple<bool, bool, int, bool, bool, bool, bool, bool, int, bool, int, bool, bool, bool, bool, bool, bool, bool, bool, bool, bool, int, int, int> saved = opts();
-    if (n == "fused_attn") h->opt_fused_attn = value != 0;
-    else if (n == "fused_mlp") h->opt_fused_mlp = value != 0;
-    else if (n == "fused_mlp_maxc") h->opt_fused_mlp_maxc = value;
-    else if (n == "fused_readout") h->opt_fused_readout = value != 0;
-    else if (n == "fused_patch_embed") h->opt_fused_pe = value != 0;
-    else if (n == "fused_rowstats") h->opt_fused_rowstats = value != 0;
-    else if (n == "fused_qkv_attn") h->opt_fused_qkv_attn = value != 0;
-    else if (n == "loop_graph") h->opt_loop_graph = value != 0;
-    else if (n == "bf16_act") h->opt_bf16_act = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (n == "bf16_pipe") h->opt_bf16_pipe = value != 0;
-    else if (n == "bf16_mlp") h->opt_bf16_mlp = value < 0 ? 0 : (value > 6 ? 6 : value);
-    else if (n == "bf16_qkv_attn") h->opt_bf16_qkv_attn = value < 0 ? 0 : (value > 3 ? 3 : value);
-    else if (n == "bf16_proj_mlp") h->opt_bf16_proj_mlp = value != 0;
-    else if (n == "bf16_readout") h->opt_bf16_readout = value != 0;
-    else if (n == "prune_masked") h->opt_prune_masked = value != 0;
-    else if (n == "dedup_masked") h->opt_dedup_masked = value != 0;
-    else if (n == "dedup_levels") h->opt_dedup_levels = value > 0 ? value : 0;
-    else if (n == "dedup_qkv") h->opt_dedup_qkv = value < 0 ? 0 : (value > 2 ? 2 : value);   // 0: the parent's launches exactly (the step bodies differ: captured graphs are dropped)
-    else if (n == "dedup_batch") {
-        // acts where the lists are written (stage_flags) and nowhere else: the launches, their grids and the list addresses are the
-        // same for every value, so the captured graphs stay -- one captured under either kind of list replays under the other
-        h->opt_dedup_batch = value < 0 ? 0 : (value > 2 ? 2 : value);
-        return DSG_OK;
+    const OptRow *r = find_option(name);
+    if (!r) return fail(h, DSG_ERR_INVALID, "unknown option '%s'", name);
+    if ((r->flags & OPT_STRICT) && (value < r->lo || value > r->hi))
+        return fail(h, DSG_ERR_INVALID, "debug_alloc_fill is 0 (off) or a pattern 1..4, not %d", value);   // (the one strict row)
+    const Options saved = h->opt;   // restored if the new selection cannot run (below)
+    h->opt.*r->field = r->normalised(value);
+    if (h->finalized) {   // the precision modes run on copies of the weights
+        int rc = 0;
+        if (r->field == &Options::gemm_bf16 && h->opt.gemm_bf16) rc = ensure_bf16_weights(h);
+        if (r->field == &Options::gemm_split && h->opt.gemm_split) rc = ensure_split_weights(h);
+        if (rc) { h->opt = saved; return rc; }
     }
-    else if (n == "dedup_table") {
-        // likewise: the step bodies are the same for both values -- the fill launch always carries the table's address (growing the
-        // table drops them) and reads on the device which kind of list the last staging wrote
-        h->opt_dedup_table = value != 0;
-        return DSG_OK;
-    }
-    else if (n == "debug_alloc_fill") {
-        // test hook: no launch of any entry point changes, only what later scratch allocations hold when they are first read
-        if (value < 0 || value > 4) return fail(h, DSG_ERR_INVALID, "debug_alloc_fill is 0 (off) or a pattern 1..4, not %d", value);
-        h->opt_debug_alloc_fill = value;
-        return DSG_OK;
-    }
-    else if (n == "batch_invariant") h->opt_batch_invariant = value != 0;
-    else if (n == "fused_merge") { h->opt_fused_merge = value != 0; h->opt_fused_merge_small = value > 1; }   // 2: at every size
-    else if (n == "gemm_bf16") {
-        h->opt_gemm_bf16 = value != 0;
-        if (h->opt_gemm_bf16 && h->finalized) if (int rc = ensure_bf16_weights(h)) return rc;
-    }
-    else if (n == "gemm_split") {
-        h->opt_gemm_split = value != 0;
-        if (h->opt_gemm_split && h->finalized) if (int rc = ensure_split_weights(h)) return rc;
-    }
-    else return fail(h, DSG_ERR_INVALID, "unknown option '%s'", name);
+    if (r->flags & OPT_KEEPS_GRAPHS) return DSG_OK;
     drop_graphs(h);   // captured graphs bake the kernel selection
     // plan time: every batch size in use must still be covered by the kernels the new selection launches; if not, the option keeps
     // its old value and the caller gets DSG_ERR_INVALID with the layer / shape in dsg_last_error
@@ -2280,7 +2279,7 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         for (auto &kv : h->ws)
             if (int rc = validate_plan(h, kv.second.get())) {
                 const std::string why = h->err;
-                opts() = saved;
+                h->opt = saved;
                 drop_graphs(h);
                 return fail(h, rc, "option '%s' = %d rejected: %s", name, value, why.c_str());
             }
@@ -2289,33 +2288,21 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
 
 int dsg_get_option(dsg_handle h, const char *name, int32_t *value) {
     if (!h || !name || !value) return DSG_ERR_INVALID;
-    const std::string n(name);
-    if (n == "fused_attn") *value = h->opt_fused_attn;
-    else if (n == "fused_mlp") *value = h->opt_fused_mlp;
-    else if (n == "fused_mlp_maxc") *value = h->opt_fused_mlp_maxc;
-    else if (n == "fused_readout") *value = h->opt_fused_readout;
-    else if (n == "fused_patch_embed") *value = h->opt_fused_pe;
-    else if (n == "fused_rowstats") *value = h->opt_fused_rowstats;
-    else if (n == "fused_qkv_attn") *value = h->opt_fused_qkv_attn;
-    else if (n == "loop_graph") *value = h->opt_loop_graph;
-    else if (n == "bf16_act") *value = (h->opt_gemm_bf16 && !h->opt_gemm_split && !bx_on(h)) ? h->opt_bf16_act : 0;   // acts whenever round 2's bf16 path is what runs (pipeline off, or a width it does not take)
-    else if (n == "bf16_pipe") *value = bx_on(h);   // the bf16 block pipeline runs (bf16 mode only)
-    else if (n == "bf16_mlp") *value = bx_on(h) ? h->opt_bf16_mlp : 0;
-    else if (n == "bf16_qkv_attn") *value = bx_on(h) ? h->opt_bf16_qkv_attn : 0;
-    else if (n == "bf16_proj_mlp") *value = (bx_on(h) && h->opt_bf16_mlp && h->opt_bf16_proj_mlp) ? 1 : 0;
-    else if (n == "bf16_readout") *value = (bx_on(h) && h->opt_bf16_readout && h->opt_fused_readout) ? 1 : 0;
-    else if (n == "prune_masked") *value = prune_opts_on(h);   // what runs: 0 with debug taps, in the split / bf16 modes, for 10 x 10 windows
-    else if (n == "dedup_masked") *value = dedup_opts_on(h);   // what runs (in the sampler): 0 wherever the pruning is off, or the fused C = 96 kernels are
-    else if (n == "dedup_levels") *value = dedup_levels(h);   // what runs (in the sampler, where PatchMerging takes its partial-statistics form)
-    else if (n == "dedup_qkv") *value = dedup_opts_on(h) ? h->opt_dedup_qkv : 0;   // what runs, at the blocks that qualify (qkv_dedup_at)
-    else if (n == "dedup_batch") *value = dedup_opts_on(h) ? h->opt_dedup_batch : 0;   // what runs (in the sampler; 1: from 16 graphs)
-    else if (n == "dedup_table") *value = dedup_opts_on(h) && h->opt_dedup_batch > 0 && h->opt_dedup_table;   // what runs (in the sampler, where the batch shares one representative)
-    else if (n == "debug_alloc_fill") *value = h->opt_debug_alloc_fill;
-    else if (n == "batch_invariant") *value = h->opt_batch_invariant;
-    else if (n == "fused_merge") *value = h->opt_fused_merge ? (h->opt_fused_merge_small ? 2 : 1) : 0;
-    else if (n == "gemm_bf16") *value = h->opt_gemm_bf16 && !h->opt_gemm_split;   // "gemm_split" takes precedence
-    else if (n == "gemm_split") *value = h->opt_gemm_split;
-    else return fail(h, DSG_ERR_INVALID, "unknown option '%s'", name);
+    const OptRow *r = find_option(name);
+    if (!r) return fail(h, DSG_ERR_INVALID, "unknown option '%s'", name);
+    *value = r->effective ? r->effective(h) : h->opt.*r->field;
+    return DSG_OK;
+}
+
+// host only, no handle: row `index` of the option table (any out pointer may be NULL); DSG_ERR_INVALID past the end
+int dsg_option_info(int32_t index, const char **name, const char **env, int32_t *dflt, int32_t *lo, int32_t *hi) {
+    if (index < 0 || index >= N_OPTIONS) return DSG_ERR_INVALID;
+    const OptRow &r = g_options[index];
+    if (name) *name = r.name;
+    if (env) *env = r.env;
+    if (dflt) *dflt = r.dflt;
+    if (lo) *lo = r.lo;
+    if (hi) *hi = r.hi;
     return DSG_OK;
 }
 
@@ -2789,7 +2776,7 @@ int step_tables(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, 
 // per schedule index, built now from the rows of tab_aff; then the caller's flags again, with lists that leave the window to the fill.
 // DSG_TABLE_VERBOSE (measurement): HIP events around the build of this call
 int pure_window_table(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &p, hipStream_t s) {
-    if (a.gt.adj || !h->opt_dedup_table || w->dd_mode != DD_BATCH) return 0;
+    if (a.gt.adj || !h->opt.dedup_table || w->dd_mode != DD_BATCH) return 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     if (getenv("DSG_TABLE_VERBOSE")) {
         HIP_TRY(h, hipEventCreate(&ev[0]));
@@ -2891,7 +2878,7 @@ int stage_guide(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, 
 // Loop: every step body captured before the first launch, then replay (or enqueue), snapshots, outputs, stats
 int run_loop(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &p, hipStream_t s) {
     const size_t sa = (size_t)a.B * h->Ca * h->N * h->N, sn = (size_t)a.B * h->N * h->Cn;
-    const bool step_graphs = p.use_graph && h->opt_loop_graph;
+    const bool step_graphs = p.use_graph && h->opt.loop_graph;
     if (step_graphs)
         for (int i = 0; i < p.L; i++) if (int rc = ensure_step_graph(h, w, p.plans[i])) return rc;   // at most ten distinct bodies
     int snap_k = 0, nfe = 0;
@@ -4705,7 +4692,7 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
     }
     const CStatePtrs ceps{eps.adj, eps.node};
     bool ok = hipGetLastError() == hipSuccess;
-    g_fixed_tiles = h->opt_batch_invariant;   // the training-form GEMMs: one route at every batch size (t_gemm)
+    g_fixed_tiles = h->opt.batch_invariant;   // the training-form GEMMs: one route at every batch size (t_gemm)
     // D = D(at, level e) into `dst`; with a probe also row e of the traces
     auto evaluate = [&](CStatePtrs at, int e, StatePtrs dst) {
         const float *sg = sig_d + (size_t)e * B;

@@ -28,6 +28,7 @@ EXPORTS = [
     "dsg_debug_poison",
     "dsg_guide_coef", "dsg_sample_guided", "dsg_debug_box_guide",
     "dsg_sample_guided_rel", "dsg_debug_box_guide_rel",
+    "dsg_option_info",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -198,6 +199,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_debug_qk_split.restype = i32
     L.dsg_set_option.argtypes = [vp, C.c_char_p, i32]
     L.dsg_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
+    L.dsg_option_info.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)] + [C.POINTER(i32)] * 3
     L.dsg_gen_noise.argtypes = [vp, i32, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
     L.dsg_profile_clock_ghz.argtypes = [vp]
     L.dsg_profile_clock_ghz.restype = C.c_double
@@ -435,6 +437,16 @@ class Handle:
 
     def finalize(self):
         self.check(self.L.dsg_finalize_weights(self._h), "dsg_finalize_weights")
+
+
+def option_table():
+    """The library's option table (dsg_option_info), in its order: a list of dicts {name, env (None: no environment default), default,
+    lo, hi} -- host-only, no GPU needed."""
+    L, rows = load(), []
+    name, env, dflt, lo, hi = C.c_char_p(), C.c_char_p(), C.c_int32(), C.c_int32(), C.c_int32()
+    while L.dsg_option_info(len(rows), C.byref(name), C.byref(env), C.byref(dflt), C.byref(lo), C.byref(hi)) == 0:
+        rows.append(dict(name=name.value.decode(), env=env.value.decode() if env.value else None, default=dflt.value, lo=lo.value, hi=hi.value))
+    return rows
 
 
 def sigma_schedule(scfg: DsgSamplerCfg):

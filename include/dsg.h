@@ -42,7 +42,7 @@ extern "C" {
  * (dsg_decode with an encoding argument, dsg_abi_version, dsg_last_error(NULL)).  dsg_sample_seeded, dsg_gen_noise_seeded and the option
  * "batch_invariant" were added without touching an existing argument list: still 4; so were the dsg_debug_*_f32 test hooks,
  * dsg_ode_run / dsg_ode_evals / dsg_debug_graph_dot, and dsg_guide_cfg / dsg_sample_guided / dsg_guide_coef / dsg_debug_box_guide,
- * and dsg_rel_cfg / dsg_sample_guided_rel / dsg_debug_box_guide_rel. */
+ * dsg_rel_cfg / dsg_sample_guided_rel / dsg_debug_box_guide_rel, and dsg_option_info. */
 #define DSG_ABI_VERSION 4
 
 typedef enum {
@@ -409,31 +409,46 @@ int dsg_debug_box_guide_rel(int32_t B, int32_t N, int32_t c_adj, int32_t c_node,
 int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t_hat, float *noise_coef,
                        float *h_step);
 
-/* Kernel selection.  The narrow levels (C = 96 / 192) have register-resident fused kernels; each can be switched off to
- * fall back to the generic GEMM + attention + row-kernel path (all combinations are parity-tested):
- *   "fused_attn" (C=96 attention block), "fused_mlp", "fused_mlp_maxc" (96|192), "fused_readout", "fused_patch_embed",
- *   "fused_rowstats" (modulate+SiLU and LayerNorm statistics in the producing GEMM's epilogue instead of row kernels),
- *   "fused_qkv_attn" (8x8 / 10x10 windows: QKV projection + window attention in one kernel, q/k/v never reach HBM),
- *   "prune_masked" (default 1): the up path computes only rows / windows that can reach an unmasked output (see
+/* Kernel selection.  One entry per option, in the order of the library's table (dsg_option_info below); "env": the DSG_* environment
+ * variable that replaces the default of every handle created in the process -- read as a flag (first character not '0') unless the
+ * entry says integer, and brought into the option's range like a value passed here.  A flag option stores value != 0.
+ * The narrow levels (C = 96 / 192) have register-resident fused kernels; each can be switched off to fall back to the generic GEMM +
+ * attention + row-kernel path (all combinations are parity-tested):
+ *   "fused_attn" (default 1; env DSG_FUSED_ATTN): the C = 96 attention block.
+ *   "fused_mlp" (default 1; env DSG_FUSED_MLP): the fused MLP, at widths up to
+ *   "fused_mlp_maxc" (96 | 192, default 96, stored as given; env DSG_FUSED_MLP_MAXC, integer).
+ *   "fused_readout" (default 1; env DSG_FUSED_READOUT).
+ *   "fused_patch_embed" (default 1; env DSG_FUSED_PE).
+ *   "fused_rowstats" (default 1; env DSG_FUSED_ROWSTATS): modulate+SiLU and LayerNorm statistics in the producing GEMM's epilogue instead
+ *       of row kernels.
+ *   "fused_qkv_attn" (default 1; env DSG_FUSED_QKV_ATTN): 8x8 / 10x10 windows: QKV projection + window attention in one kernel, q/k/v
+ *       never reach HBM.
+ *   "fused_merge" (0..2, default 1; env DSG_FUSED_MERGE): PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path;
+ *       1: where it pays (>= 8192 merged rows), 2 (or more): at every size, 0: merge_ln kernel.
+ *   "loop_graph" (default 1; env DSG_LOOP_GRAPH): the reverse loop -- 1: dsg_sample replays one captured hipGraph per step (a handful of
+ *       distinct step bodies: first / steady / last step x the two self-conditioning coins); 0: the round-1 scheme, only the network
+ *       forward is a graph.
+ *   "prune_masked" (default 1; env DSG_PRUNE_MASKED): the up path computes only rows / windows that can reach an unmasked output (see
  *       dsg_debug_need_lists below); 0: every row.  Bit-identical results either way.
- *   "dedup_masked" (default 1; acts in the sampler entry points only, and only where "prune_masked" does): a graph's level-0
- *       windows that hold nothing but padded pairs are computed once through PatchEmbed and the first Swin block and copied (see
- *       dsg_debug_dedup_lists below); 0: every window is computed.  Bit-identical results either way.
- *   "dedup_levels" (default 0 = every qualifying level; env DSG_DEDUP_LEVELS): how many levels "dedup_masked" may reach, the finest
+ *   "dedup_masked" (default 1; env DSG_DEDUP_MASKED; acts in the sampler entry points only, and only where "prune_masked" does): a
+ *       graph's level-0 windows that hold nothing but padded pairs are computed once through PatchEmbed and the first Swin block and
+ *       copied (see dsg_debug_dedup_lists below); 0: every window is computed.  Bit-identical results either way.
+ *   "dedup_levels" (>= 0, default 0 = every qualifying level; env DSG_DEDUP_LEVELS, integer): how many levels "dedup_masked" may reach, the finest
  *       included; 1: PatchEmbed and level 0's first block only.  Level k >= 1 qualifies when level k - 1 does and has no second
  *       (shifted) block, its own first block is unshifted on at least 2 x 2 windows of 8 x 8, and the PatchMerging into it is the partial-statistics form ("fused_merge" where
  *       it applies: 8192 merged rows, or value 2, or "batch_invariant"): that merge then computes only the merged rows of the level's
  *       unique windows, the first block runs over the same lists, and a copy fills the other pure windows of the activation, of the
  *       skip tensor and of the row statistics (dsg_debug_dedup_level_lists below).  dsg_get_option reports the number of levels that
  *       deduplicate under the present options (0: none).  Bit-identical results whatever the value.
- *   "dedup_batch" (default 1; env DSG_DEDUP_BATCH; acts in the sampler entry points only, where sigma -- and with it every block's
+ *   "dedup_batch" (0..2, default 1; env DSG_DEDUP_BATCH, integer; acts in the sampler entry points only, where sigma -- and with it every block's
  *       (scale, shift) row -- is the same for the whole batch): the pure windows of ALL graphs of a batch share one computed
  *       representative per level, the batch's first pure window, and a level below the top of the chain fills only the pure windows
  *       that a unique window of the next level lies over (nothing reads the others).  0: one representative per graph.  1: across the
  *       batch from 16 graphs on, per graph below -- below 16 graphs no list launch of the N = 64 network's down path exceeds half a
  *       round of resident GEMM tiles, so fewer rows buy no time there.  2: across the batch at every size.  dsg_denoise / dsg_precond
  *       (per-sample noise labels, caller tensors) list every window as unique whatever the value.  dsg_get_option reports the value in
- *       force (0 wherever "dedup_masked" is off).  Bit-identical results whatever the value.
+ *       force (0 wherever "dedup_masked" is off).  The captured step bodies are the same for every value, so changing the option
+ *       keeps them.  Bit-identical results whatever the value.
  *   "dedup_table" (default 1; env DSG_DEDUP_TABLE; acts only where "dedup_batch" shares one representative across the batch): that
  *       window's rows depend on the weights and on the step's (scale, shift) row only, so a sampler call computes them once per
  *       schedule index before its loop -- with the down path itself, on all-padding pseudo-batches of B indices -- into a table in the
@@ -442,39 +457,53 @@ int dsg_sigma_schedule(const dsg_sampler_cfg *cfg, double *sigma_steps, float *t
  *       every other pure window; no launch of the loop computes it.  0: the batch's first pure window is computed in every forward.
  *       The captured step bodies are the same for both values (a device-side word written with the lists selects the fill's source),
  *       so changing the option keeps them.  dsg_get_option reports whether it would act.  Bit-identical results either way.
- *   "fused_merge" (PatchMerging's 2x2 gather + LayerNorm(4C) inside the reduction GEMM's A path; 1: where it pays (>= 8192 merged
- *   rows), 2: at every size, 0: merge_ln kernel).
- * "batch_invariant" (default 0): 1 -- every choice the plan makes (which kernel, which tile, fused or not, any summation order) is a
- *   function of the network geometry and the other options only, never of the batch size: PatchMerging is fused wherever "fused_merge"
- *   is on, at every size, and the bf16 GEMM of the "gemm_bf16" / bf16_pipe = 0 path keeps its 128 x 96 tile.  A sample's result then
- *   does not depend on B or on its position.  A geometry whose fused read-out would place a graph's pooling partials by
- *   its position (N * N not a multiple of 32) is refused with DSG_ERR_INVALID.  Holds on the default fp32 path and under "gemm_bf16";
- *   not under "gemm_split", whose kernel orders a row's partial products by the row's index mod 64.  0: the previous behaviour, bit for bit.
- * Reverse loop: "loop_graph" = 1 (default): dsg_sample replays one captured hipGraph per step (a handful of distinct step bodies:
- *   first / steady / last step x the two self-conditioning coins); 0: the round-1 scheme, only the network forward is a graph.
+ *   "dedup_qkv" (0..2, default 1; env DSG_DEDUP_QKV gives 0 or 1; acts only where "dedup_masked" does): the shifted block right behind a
+ *       deduplicated first block projects QKV of the copied pure-window rows once (see dsg_debug_dedup_qkv_lists below); 2, a
+ *       measurement hook: the split form wherever the lists exist, whatever their share; 0: the fused form everywhere.  Changing it
+ *       drops the captured graphs.  Bit-identical results whatever the value.
+ *   "batch_invariant" (default 0): 1 -- every choice the plan makes (which kernel, which tile, fused or not, any summation order) is a
+ *       function of the network geometry and the other options only, never of the batch size: PatchMerging is fused wherever "fused_merge"
+ *       is on, at every size, and the bf16 GEMM of the "gemm_bf16" / bf16_pipe = 0 path keeps its 128 x 96 tile.  A sample's result then
+ *       does not depend on B or on its position.  A geometry whose fused read-out would place a graph's pooling partials by
+ *       its position (N * N not a multiple of 32) is refused with DSG_ERR_INVALID.  Holds on the default fp32 path and under "gemm_bf16";
+ *       not under "gemm_split", whose kernel orders a row's partial products by the row's index mod 64.  0: the previous behaviour, bit for bit.
  * Precision modes (default: exact fp32 MFMA everywhere):
- *   "gemm_split" = 1: every GEMM as six bf16-MFMA partial products of hi/mid/lo (3 x bf16 = 24-bit) operand splits with
- *       fp32 accumulation -- fp32-level accuracy, the 1e-4 parity bar still holds; 1.3-1.6x faster GEMMs (power-bound).
- *   "gemm_bf16" = 1: the block/merge/breakup GEMMs on bf16 MFMA with operands rounded to bf16 (activations, LayerNorm,
- *       softmax and the sampler stay fp32) -- BASELINE config 5; parity against the fp32 oracle then holds to 1.5e-2 RMS /
- *       5e-2 max-abs of the output scale, not 1e-4.  "gemm_split" takes precedence if both are set.
+ *   "gemm_bf16" (default 0; env DSG_GEMM_BF16) = 1: the block/merge/breakup GEMMs on bf16 MFMA with operands rounded to bf16 (activations,
+ *       LayerNorm, softmax and the sampler stay fp32) -- BASELINE config 5; parity against the fp32 oracle then holds to 1.5e-2 RMS /
+ *       5e-2 max-abs of the output scale, not 1e-4.  "gemm_split" takes precedence if both are set (dsg_get_option then reports 0).
+ *   "gemm_split" (default 0; env DSG_GEMM_SPLIT) = 1: every GEMM as six bf16-MFMA partial products of hi/mid/lo (3 x bf16 = 24-bit)
+ *       operand splits with fp32 accumulation -- fp32-level accuracy, the 1e-4 parity bar still holds; 1.3-1.6x faster GEMMs (power-bound).
  *   "bf16_act" (0 / 1 / 2, default 2; acts only with "gemm_bf16"): 1 -- tensors whose only consumer is the bf16 GEMM (the MLP's
  *       hidden activations, the attention output) are stored as bf16 by their producer; the consumer rounds its A operand to bf16
  *       anyway, so results are bit-identical to 0, with half the bytes and no conversion in the consumer.  2 -- q, k, v are
  *       stored as bf16 as well; the attention arithmetic stays fp32 on the widened values, results move within the mode's bar.
- *   "bf16_pipe" (default 1; acts only with "gemm_bf16"): the bf16 block pipeline -- a Swin block is two kernels with bf16 tensors between
- *       them; its kernel choices (all parity-tested, same bar): "bf16_qkv_attn" 1 QKV projection + window attention in one kernel (10 x 10
- *       windows: one wave per (window, head)), 2 the block-per-head kernel everywhere, 3 the former only where a block of four units lies in
- *       one window, 0 GEMM + attention kernel; "bf16_mlp" 1 fused fc1-GELU-fc2 (C = 384: eight waves, weight images streamed by LDS-DMA),
- *       4 round 3's eight-wave kernel, 5 the one-wave-per-SIMD LDS-DMA kernel, 6 = 1 with level 0 on the LDS-resident kernel, 2 four waves at every width, 3 GEMM pair at C = 384,
- *       0 GEMM pairs; "bf16_proj_mlp" 1 proj + residual + LayerNorm-2 in front of the MLP kernel; "bf16_readout" 1 the read-out on the bf16 pipe.
- * Test only: "debug_alloc_fill" (default 0): while p = 1..4, every scratch buffer the handle or a workspace allocates from then on is
- *   filled with pattern p (dsg_debug_poison) right after its allocation, ahead of the library's own creation memsets -- a stand-in for
- *   whatever the allocator returns.  Index / state buffers and weights are never filled.  No launch of any entry point changes. */
+ *   "bf16_pipe" (default 1; env DSG_BF16_PIPE; acts only with "gemm_bf16"): the bf16 block pipeline -- a Swin block is two kernels with
+ *       bf16 tensors between them; its kernel choices (all parity-tested, same bar) are the four options below, reported as 0 wherever
+ *       the pipeline does not run:
+ *   "bf16_mlp" (0..6, default 1; env DSG_BF16_MLP, integer): 1 fused fc1-GELU-fc2 (C = 384: eight waves, weight images streamed by
+ *       LDS-DMA), 4 round 3's eight-wave kernel, 5 the one-wave-per-SIMD LDS-DMA kernel, 6 = 1 with level 0 on the LDS-resident kernel,
+ *       2 four waves at every width, 3 GEMM pair at C = 384, 0 GEMM pairs.
+ *   "bf16_qkv_attn" (0..3, default 1; env DSG_BF16_QA, integer): 1 QKV projection + window attention in one kernel (10 x 10 windows: one
+ *       wave per (window, head)), 2 the block-per-head kernel everywhere, 3 the former only where a block of four units lies in one
+ *       window, 0 GEMM + attention kernel.
+ *   "bf16_proj_mlp" (default 1): 1 proj + residual + LayerNorm-2 in front of the MLP kernel.
+ *   "bf16_readout" (default 1): 1 the read-out on the bf16 pipe.
+ * Test only:
+ *   "debug_alloc_fill" (0..4, default 0; any other value is refused with DSG_ERR_INVALID): while p = 1..4, every scratch buffer the
+ *       handle or a workspace allocates from then on is filled with pattern p (dsg_debug_poison) right after its allocation, ahead of
+ *       the library's own creation memsets -- a stand-in for whatever the allocator returns.  Index / state buffers and weights are
+ *       never filled.  No launch of any entry point changes.
+ * Except for "dedup_batch", "dedup_table" and "debug_alloc_fill", setting an option drops the captured graphs and, once the weights are
+ * finalized, checks every batch size in use against the kernels the new selection launches: if one is not covered the whole option set
+ * stays as it was and the call returns DSG_ERR_INVALID with the layer / shape in dsg_last_error. */
 int dsg_set_option(dsg_handle h, const char *name, int32_t value);
 /* The value an option currently has on this handle (what the next forward will run with), whichever way it was set
  * (dsg_set_option or a DSG_* environment default): measurement code reports the precision mode from here. */
 int dsg_get_option(dsg_handle h, const char *name, int32_t *value);
+/* Row `index` (0, 1, ...) of the option table, without a handle or a device: the option's name, its environment variable (NULL: none),
+ * its default and the range lo..hi that values are brought into (flags: 0..1).  Any out pointer may be NULL.  DSG_ERR_INVALID past
+ * the end of the table. */
+int dsg_option_info(int32_t index, const char **name, const char **env, int32_t *dflt, int32_t *lo, int32_t *hi);
 
 /* Measurement: runs n_iters eager network forwards on the batch-B workspace (whatever inputs the last call left
  * there) with HIP events bracketing every kernel launch on `stream`, and accumulates per kernel class
