@@ -3397,6 +3397,53 @@ int dsg_debug_gemm_f32(const dsg_gemm_f32_args *a, void *stream) {
 
 int32_t dsg_debug_gemm_form(int32_t cnt_runs, int32_t N, int32_t n_cu) { return gemm_thin_rule(cnt_runs, N, n_cu) ? 2 : 1; }
 
+// ---- the bf16-MFMA GEMMs on their own: launch_gemm_lp directly, so a refused form is an error and never the fp32 kernel ----
+int dsg_debug_gemm_lp(const dsg_gemm_lp_args *a, void *stream) {
+    if (a && a->tile_used) *a->tile_used = 0;
+    if (!a || !a->A || !a->W || !a->C || a->act < ACT_NONE || a->act > ACT_SILU) return DSG_ERR_INVALID;
+    if (a->mode < 1 || a->mode > 2 || a->tile < 0 || a->tile > 2 || (a->tile && a->mode == 2) || (a->tile == 2 && a->M < 256)) return DSG_ERR_INVALID;
+    if (a->M < 1 || a->N < 1 || a->K < 32 || a->K % 32 != 0 || a->row_list || a->row_cnt || a->reserved != 0) return DSG_ERR_INVALID;
+    // what the kernels take on trust from the forward: pitches that hold a row and keep its 16-byte loads aligned
+    const int K1 = a->A2 ? a->K1 : a->K;
+    if (a->A2 && (K1 < 1 || K1 >= a->K || a->lda2 < a->K - K1 || a->lda2 % 4 != 0)) return DSG_ERR_INVALID;
+    if (a->a4_res == 0 && (a->lda < K1 || a->lda % (a->a_bf16 ? 8 : 4) != 0)) return DSG_ERR_INVALID;
+    if (a->ldc < a->N || (a->C2 && a->ldc2 < a->N) || (a->res && a->ldres < a->N)) return DSG_ERR_INVALID;
+    if ((a->ln_part && a->ln_nparts < 1) || (a->ln_part && a->ln_stats) || (a->mod_aff && !a->stats_out)) return DSG_ERR_INVALID;
+    if (!gelu_table()) return DSG_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nw = (size_t)a->N * a->K;
+    void *wlp = nullptr;
+    if (hipMalloc(&wlp, nw * (a->mode == 1 ? 2 : 6)) != hipSuccess) return DSG_ERR_HIP;
+    if (a->mode == 1) launch_f32_to_bf16(a->W, wlp, nw, s); else launch_f32_split3(a->W, wlp, nw, s);
+    GemmArgs g;
+    g.A = static_cast<const float *>(a->A); g.lda = a->lda; g.A2 = a->A2; g.lda2 = a->lda2; g.K1 = K1;
+    g.W = a->W; g.bias = a->bias;
+    if (a->mode == 1) g.Wb = wlp; else g.Ws3 = wlp;
+    g.ln_stats = a->ln_stats; g.ln_part = a->ln_part; g.ln_nparts = a->ln_nparts;
+    g.res = a->res; g.ldres = a->ldres; g.C = static_cast<float *>(a->C); g.ldc = a->ldc; g.C2 = a->C2; g.ldc2 = a->ldc2;
+    g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act;
+    g.mod_aff = a->mod_aff; g.mod_ld = a->mod_ld; g.mod_off = a->mod_off; g.mod_T = a->mod_T > 0 ? a->mod_T : 1;
+    g.stats_out = a->stats_out;
+    g.a4_res = a->a4_res;
+    g.a_bf16 = a->a_bf16 != 0; g.c_bf16 = a->c_bf16 != 0;
+    g_lp_tile_hook = a->tile;
+    const bool built = launch_gemm_lp(g, s);
+    g_lp_tile_hook = 0;
+    if (a->tile_used) *a->tile_used = built ? g_lp_tile_rows : 0;
+    const int rc = debug_finish(built, s);
+    (void)hipFree(wlp);
+    return rc;
+}
+
+int dsg_debug_convert(int32_t kind, const void *src, void *dst, int64_t n, void *stream) {
+    if (kind < 0 || kind > 2 || !src || !dst || n < 1 || n >= ((int64_t)1 << 31)) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (kind == 0) launch_f32_to_bf16(static_cast<const float *>(src), dst, (size_t)n, s);
+    else if (kind == 1) launch_f32_split3(static_cast<const float *>(src), dst, (size_t)n, s);
+    else launch_bf16_to_f32(src, static_cast<float *>(dst), (size_t)n, s);
+    return debug_finish(true, s);
+}
+
 int dsg_debug_qkv_attn_f32(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, int32_t K, const float *x, const float *W,
                            const float *bias, const float *ln_stats, const float *ln_part, int32_t ln_nparts, const float *attn_bias,
                            const int32_t *win_list, const int32_t *win_cnt, float *out, void *stream) {
@@ -3529,6 +3576,40 @@ int dsg_debug_row_f32(int32_t kind, int32_t B, int32_t t, int32_t C, float *x, c
         default: return DSG_ERR_INVALID;
     }
     return debug_finish(true, s);
+}
+
+// the row passes' bf16-tensor forms (the fp32 forms: dsg_debug_row_f32 above, dsg_debug_window_attn_f32)
+int dsg_debug_row_lp(int32_t kind, int32_t B, int32_t t, int32_t C, float *x, const float *g, const float *b, const float *pg, const float *pb,
+                     const float *aff, int32_t aff_ld, int32_t aff_off, void *y, const int32_t *run_list, const int32_t *run_cnt, void *stream) {
+    constexpr int ROW_LIMIT = 1536;   // as dsg_debug_row_f32: a wave holds 24 values per lane
+    if (B < 1 || t < 1 || C < 4 || C % 4 != 0 || !x || !y) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    switch (kind) {
+        case DSG_ROWLP_MERGE_LN:
+            if (4 * C > ROW_LIMIT || t % 2 != 0 || !g || !b) return DSG_ERR_INVALID;
+            launch_merge_ln(x, g, b, static_cast<float *>(y), B, t, C, s, true);
+            break;
+        case DSG_ROWLP_BREAKUP_LN:
+            if (C > ROW_LIMIT || C % 16 != 0 || !g || !b || !pg || !pb) return DSG_ERR_INVALID;
+            if (run_list && (!run_cnt || (B * t * t) % 8 != 0)) return DSG_ERR_INVALID;
+            launch_breakup_ln(x, g, b, pg, pb, static_cast<float *>(y), B, t, C, s, true, run_list, run_cnt);
+            break;
+        case DSG_ROWLP_LN_BX:
+        case DSG_ROWLP_COPY_BX:
+            if (C > ROW_LIMIT || (aff && (!mult4(aff_ld) || !mult4(aff_off)))) return DSG_ERR_INVALID;
+            launch_ln_bx(x, aff, aff_ld, aff_off, y, B, t, C, kind == DSG_ROWLP_LN_BX, s);
+            break;
+        default: return DSG_ERR_INVALID;
+    }
+    return debug_finish(true, s);
+}
+
+int dsg_debug_window_attn_lp(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const void *qkv, const float *biasT, void *out,
+                             int32_t in_bf16, int32_t out_bf16, void *stream) {
+    if (B < 1 || res < 1 || ws < 1 || heads < 1 || shift < 0 || shift >= ws || !qkv || !biasT || !out) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish(launch_window_attn(static_cast<const float *>(qkv), biasT, static_cast<float *>(out), B, WinGeom{res, ws, shift, heads, 32 * heads}, s,
+                                           out_bf16 != 0, in_bf16 != 0), s);
 }
 
 int dsg_debug_window_broadcast_f32(int32_t B, int32_t res, int32_t C, float *x, float *skip, float *stats, int32_t nparts, const int32_t *copy_list,

@@ -14,6 +14,13 @@ extern thread_local bool g_dry_run;
 // GEMM's 256x96 / 128x96 choice (kernels_lp.hip: launch_gemm_lp), and in training form -- where only dsg_ode_run sets it -- t_gemm's
 // MFMA route from 512 rows on (train_kernels.hip).
 extern thread_local bool g_fixed_tiles;
+// Test hook of the bf16 GEMM's tile choice (dsg_debug_gemm_lp sets it around its one launch; nothing else writes it): 0 the launcher's
+// own rule, 1 the 128x96 tile, 2 the 256x96 tile.  launch_gemm_lp reads it ahead of g_fixed_tiles and its DSG_BF16_* statics, and
+// leaves the block rows of the tile it chose in g_lp_tile_rows (128 or 256; meaningful when it returned true).  Both live in kernels_lp.hip.
+extern thread_local int g_lp_tile_hook;
+extern thread_local int g_lp_tile_rows;
+struct GemmArgs;
+bool launch_gemm_lp(const GemmArgs &g, hipStream_t s);   // kernels_lp.hip; false: the form is not built (nothing launched)
 
 enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2,
            // training-form products of the fp32 GEMM only (launch_gemm): GELU whose pre-activation is kept in C2 (the backward needs it);
@@ -214,7 +221,7 @@ void launch_ln_mod(const float *x, const float *g, const float *b, const float *
 void launch_merge_ln(const float *x, const float *g, const float *b, float *y, int B, int res, int C, hipStream_t s, bool out_bf16 = false);
 // PatchBreakup middle: LN(D) -> 4 chunks scattered 2x2 -> LN(D/4): y [B,res*res,D] -> z [B,(2res)^2,D/4]
 void launch_breakup_ln(const float *y, const float *g, const float *b, const float *pg, const float *pb, float *z,
-                       int B, int res, int D, hipStream_t s, bool out_bf16 = false,   // out_bf16: y / z are bf16 tensors
+                       int B, int res, int D, hipStream_t s, bool out_bf16 = false,   // out_bf16: z is a bf16 tensor (y stays fp32)
                        const int *run_list = nullptr, const int *run_cnt = nullptr);   // run list over the COARSE rows of y
 // positional embedding of the noise label: pe [B,E]
 void launch_noise_pe(const float *c_noise, float *pe, int B, int E, hipStream_t s);

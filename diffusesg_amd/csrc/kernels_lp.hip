@@ -518,8 +518,15 @@ void launch_bf16_to_f32(const void *src, float *dst, size_t n, hipStream_t s) { 
 
 static int round_up8(int x) { return (x + 7) / 8 * 8; }
 
+thread_local int g_lp_tile_hook = 0;
+thread_local int g_lp_tile_rows = 0;
+
 bool launch_gemm_lp(const GemmArgs &g_in, hipStream_t s) {
+    g_lp_tile_rows = 0;
     if (!g_in.Ws3 && !(g_in.Wb && (!g_in.A2 || g_in.K1 % HBK == 0))) return false;
+    // the split kernel switches sources at chunk K1 / SBK: a K1 inside a chunk would read the wrong columns of both (no caller has one:
+    // the forward's concat widths are multiples of 96)
+    if (g_in.Ws3 && g_in.A2 && g_in.K1 % SBK != 0) return false;
     GemmArgs g = g_in;
     g.gelu_tab = gelu_table();
     const int tiles_n = (g.N + GBN - 1) / GBN;
@@ -528,9 +535,11 @@ bool launch_gemm_lp(const GemmArgs &g_in, hipStream_t s) {
     static const bool narrow_only = getenv("DSG_BF16_NARROW") != nullptr;   // dev knob: A/B against the 128x96 tile
     static const bool force_wide = getenv("DSG_BF16_WIDE") != nullptr;      // tests: the wide tile at every size
     // (g_fixed_tiles, option "batch_invariant": the choice below depends on M, i.e. on the batch size -- the 128x96 tile at every size)
-    const bool wide = !split && !narrow_only && !g_fixed_tiles && (force_wide ? g.M >= 256 : (size_t)((g.M + 255) / 256) * tiles_n >= 512);
+    const bool rule_wide = !narrow_only && !g_fixed_tiles && (force_wide ? g.M >= 256 : (size_t)((g.M + 255) / 256) * tiles_n >= 512);
+    const bool wide = !split && (g_lp_tile_hook ? g_lp_tile_hook == 2 : rule_wide);   // (the test hook of kernels.h comes first; 0: the rule)
     const int tile_m = split ? 256 : (wide ? 2 * GBM : GBM);
     const int tiles_m = (g.M + tile_m - 1) / tile_m;
+    g_lp_tile_rows = tile_m;
     const dim3 grid(round_up8(tiles_m) * tiles_n), block(256);
 #define LAUNCH_BF16(L, A, R, E, AB, CB)                                                                                           \
     do {                                                                                                                          \

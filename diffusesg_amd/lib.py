@@ -29,6 +29,7 @@ EXPORTS = [
     "dsg_guide_coef", "dsg_sample_guided", "dsg_debug_box_guide",
     "dsg_sample_guided_rel", "dsg_debug_box_guide_rel",
     "dsg_option_info",
+    "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -97,6 +98,19 @@ class DsgGemmF32Args(C.Structure):
                                            "row_list", "row_cnt")] +
                 [(n, C.c_int32) for n in ("lda", "lda2", "K1", "ln_nparts", "ldres", "ldc", "ldc2", "M", "N", "K", "act", "mod_ld",
                                           "mod_off", "mod_T", "a4_res", "reserved")])
+
+
+class DsgGemmLpArgs(C.Structure):
+    """dsg_gemm_lp_args of include/dsg.h (dsg_debug_gemm_lp): the fields of DsgGemmF32Args, the host pointer tile_used behind the device
+    pointers, and mode / tile / a_bf16 / c_bf16 behind the int32 fields"""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "W", "bias", "ln_stats", "ln_part", "res", "C", "C2", "mod_aff", "stats_out",
+                                           "row_list", "row_cnt", "tile_used")] +
+                [(n, C.c_int32) for n in ("lda", "lda2", "K1", "ln_nparts", "ldres", "ldc", "ldc2", "M", "N", "K", "act", "mod_ld",
+                                          "mod_off", "mod_T", "a4_res", "reserved", "mode", "tile", "a_bf16", "c_bf16")])
+
+
+ROWLP_MERGE_LN, ROWLP_BREAKUP_LN, ROWLP_LN_BX, ROWLP_COPY_BX = range(4)                            # DSG_ROWLP_* (dsg_debug_row_lp)
+CONVERT_BF16, CONVERT_SPLIT3, CONVERT_WIDEN = range(3)                                             # kinds of dsg_debug_convert
 
 
 class DsgTProb(C.Structure):
@@ -206,6 +220,10 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_debug_gemm.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     L.dsg_debug_gemm_f32.argtypes = [C.POINTER(DsgGemmF32Args), vp]
     L.dsg_debug_gemm_form.argtypes = [i32, i32, i32]
+    L.dsg_debug_gemm_lp.argtypes = [C.POINTER(DsgGemmLpArgs), vp]
+    L.dsg_debug_convert.argtypes = [i32, vp, vp, C.c_int64, vp]
+    L.dsg_debug_row_lp.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.dsg_debug_window_attn_lp.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     L.dsg_debug_gemm_form.restype = i32
     L.dsg_debug_qkv_attn_f32.argtypes = [i32] * 6 + [vp] * 5 + [i32] + [vp] * 5
     L.dsg_debug_window_attn_f32.argtypes = [i32] * 5 + [vp] * 4

@@ -650,6 +650,38 @@ int dsg_debug_gemm_f32(const dsg_gemm_f32_args *args, void *stream);
 /* The list GEMM's form rule, from the function its kernel evaluates on the device-side count: 2 (thin) iff the wide form's
  * ceil(cnt_runs / 16) x ceil(N / 96) tiles would occupy at most half of n_cu compute units, else 1 (wide); n_cu = 0: always 1.  Host only. */
 int32_t dsg_debug_gemm_form(int32_t cnt_runs, int32_t N, int32_t n_cu);
+/* The two bf16-MFMA GEMMs on their own (test hooks, csrc/kernels_lp.hip: gemm_bf16_kernel and gemm_split2_kernel; tests/test_lp_kernels.py
+ * compares every output element with float64).  dsg_debug_gemm_lp: one launch through launch_gemm_lp DIRECTLY -- a form that launcher
+ * refuses is DSG_ERR_INVALID with nothing launched and no output written; there is no fall-back to the fp32 kernel (launch_gemm, and so
+ * dsg_debug_gemm, does fall back).  The fields of dsg_gemm_f32_args -- row_list / row_cnt must be NULL and reserved 0: these kernels take
+ * no list -- and
+ *     mode       1 bf16 operands ("gemm_bf16"), 2 three-way split ("gemm_split"); W is given as fp32 [N,K] and converted inside
+ *                (dsg_debug_convert kind 0 / 1), as dsg_debug_gemm does
+ *     tile       bf16 kernel only: 0 the launcher's rule, 1 the 128-row tile (K step 64), 2 the 256-row tile (K step 32; needs M >= 256)
+ *     a_bf16     A is a bf16 tensor [M, lda], lda in elements and a multiple of 8
+ *     c_bf16     C is a bf16 tensor [M, ldc], ldc in elements
+ *     tile_used  host int32 or NULL: the block rows of the kernel launched (128 or 256; 0 when refused)
+ * fp32 leading dimensions are multiples of 4 floats; K % 32 == 0. */
+typedef struct dsg_gemm_lp_args {
+    const void *A;
+    const float *A2, *W, *bias, *ln_stats, *ln_part, *res;
+    void *C;
+    float *C2;
+    const float *mod_aff;
+    float *stats_out;
+    const int32_t *row_list, *row_cnt;
+    int32_t *tile_used;
+    int32_t lda, lda2, K1, ln_nparts, ldres, ldc, ldc2, M, N, K, act, mod_ld, mod_off, mod_T, a4_res, reserved;
+    int32_t mode, tile, a_bf16, c_bf16;
+} dsg_gemm_lp_args;
+int dsg_debug_gemm_lp(const dsg_gemm_lp_args *args, void *stream);
+/* The conversion kernels of that file on n elements (device pointers, n in [1, 2^31)): kind 0 fp32 -> bf16 [n], round to nearest even
+ * on the integer pipe: bits + 0x7fff + (bit 16), upper half.  Finite values and infinities round as IEEE does (the largest finite
+ * values go to inf); a NaN is NOT special-cased: the quiet NaN 0x7fc00000 stays 0x7fc0, but a payload whose upper mantissa bits are all
+ * ones carries into the exponent and sign (0x7fff8000 and above -> 0x8000, i.e. -0).  kind 1 fp32 -> three bf16 planes [3][n]
+ * (hi | mid | lo, by truncation: hi + mid + lo == the input exactly for 0 and for |x| >= 2^-110; below that, bits under 2^-133, the last
+ * bit of a bf16 denormal, are cut; an infinity gives hi = itself and NaN in the other planes).  kind 2 bf16 [n] -> fp32 (exact). */
+int dsg_debug_convert(int32_t kind, const void *src, void *dst, int64_t n, void *stream);
 /* LayerNorm-1 -> QKV -> window attention in the GEMM's epilogue (8 x 8 and 10 x 10 windows): x [B res^2, K], W [3C, K] (C = 32 heads,
  * q rows pre-scaled by d^-1/2 log2 e), bias [3C], one of ln_stats / ln_part, attn_bias the key-major log2(e)-scaled table
  * [nW | 1][heads][Wp][Wp] (-1e30 in padded key slots); win_list / win_cnt (device, 8 x 8 only): only those windows (b nW + w, -1: none)
@@ -715,6 +747,20 @@ enum { DSG_ROW_MOD_STATS = 0, DSG_ROW_LN_STATS = 1, DSG_ROW_LN_MOD = 2, DSG_ROW_
 int dsg_debug_row_f32(int32_t kind, int32_t B, int32_t t, int32_t C, float *x, const float *g, const float *b, const float *pg, const float *pb,
                       const float *aff, int32_t aff_ld, int32_t aff_off, const float *ln_part, int32_t nparts, float *y, float *stats,
                       const int32_t *run_list, const int32_t *run_cnt, void *stream);
+/* The bf16-tensor forms of the row passes ("gemm_bf16" mode; tests/test_lp_kernels.py).  y is a bf16 tensor, rounded to nearest even
+ * from the fp32 value; x, the parameters and all arithmetic stay fp32.
+ *   DSG_ROWLP_MERGE_LN    as DSG_ROW_MERGE_LN, y bf16 [B (t/2)^2, 4C]
+ *   DSG_ROWLP_BREAKUP_LN  as DSG_ROW_BREAKUP_LN, y bf16 [B (2t)^2, D/4]; the input row x stays fp32
+ *   DSG_ROWLP_LN_BX       x [B t, C] <- silu(shift + x (1 + scale)) in place when aff != NULL (aff_ld == 0: one (scale | shift) row for
+ *                         the whole batch), then y bf16 [B t, C] = LayerNorm of the row without affine
+ *   DSG_ROWLP_COPY_BX     the same with y = the plain bf16 copy of the (modulated) row */
+enum { DSG_ROWLP_MERGE_LN = 0, DSG_ROWLP_BREAKUP_LN = 1, DSG_ROWLP_LN_BX = 2, DSG_ROWLP_COPY_BX = 3 };
+int dsg_debug_row_lp(int32_t kind, int32_t B, int32_t t, int32_t C, float *x, const float *g, const float *b, const float *pg, const float *pb,
+                     const float *aff, int32_t aff_ld, int32_t aff_off, void *y, const int32_t *run_list, const int32_t *run_cnt, void *stream);
+/* window attention as dsg_debug_window_attn_f32 with out (out_bf16) or qkv and out (in_bf16 and out_bf16) as bf16 tensors; bf16 qkv is
+ * widened on load and the arithmetic is unchanged.  in_bf16 without out_bf16 is not built: DSG_ERR_INVALID. */
+int dsg_debug_window_attn_lp(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const void *qkv, const float *biasT, void *out,
+                             int32_t in_bf16, int32_t out_bf16, void *stream);
 /* the pure-window copies.  Broadcast: every window of copy_list (device, *copy_cnt entries, b nW + w) of x [B res^2, C], skip (or NULL) and
  * stats [B res^2][nparts][2] (or NULL) is filled from window rep[b] (device [B], a global window id; -1: none), or, when mode == 3 (the
  * table mode) from table entry sched[min(step, n_steps - 1)] (clamped to tab_entries - 1): an entry is tab_stride floats with 64 x C rows
