@@ -137,6 +137,7 @@ struct Workspace {
     // option "dedup_qkv": did the last forward launch the level's second block in its switched form (the fused launch plus the projection
     // over qk_runs and the map attention, the device picking one by qk_split_rule)?  dsg_debug_dedup_qkv_lists
     bool qk_fwd[1 + NEED_MAX_DD_UP] = {false, false, false, false};
+    int ro_fwd = -1;   // the form the last forward's fused read-out took (1 list, 0 positional; -1: none yet).  dsg_debug_readout_tiles
     // what stage_flags last wrote (dedup_stage_mode below): the DedupMode of the lists, the levels whose fill is trimmed (bit k) and the
     // chain depth the trimming was worked out for -- forward_fixed checks that it reaches exactly that depth
     int dd_mode = DD_OFF, dd_trim = 0, dd_depth = 0;
@@ -212,6 +213,8 @@ struct dsg_handle_s {
     int n_cu = 0;                     // multiprocessor count of the device (read once in dsg_create): the list GEMM's form rule (gemm_thin_rule)
     int prof_next_thin_n = 0;         // N of the next profiled launch if it is a list GEMM with a thin form, else 0
     std::vector<int> prof_thin_n;
+    const char *prof_next_form = nullptr;   // the form the next profiled launch was given on the host (" form=..." of its [dsg-prof] line), or null
+    std::vector<const char *> prof_form;
     // the next profiled launch belongs to a block with the "dedup_qkv" form switch: the qk_runs list whose count decides, the rows M of the
     // rule, and the form the launch is part of (1 fused, 2 split); list -1: no switch
     struct ProfQk { int list = -1, M = 0, role = 0; };
@@ -289,6 +292,8 @@ struct ProfScope {
     ProfScope(dsg_handle h_, hipStream_t s_, int kind, double flops, const char *tag = nullptr) : h(h_), s(s_) {
         const int need_list = h->prof_next_list, thin_n = h->prof_next_thin_n;
         const auto qk = h->prof_next_qk;
+        const char *form = h->prof_next_form;
+        h->prof_next_form = nullptr;
         h->prof_next_list = -1;
         h->prof_next_thin_n = 0;
         h->prof_next_qk = decltype(h->prof_next_qk)();
@@ -302,6 +307,7 @@ struct ProfScope {
         h->prof_list.push_back(need_list);
         h->prof_thin_n.push_back(thin_n);
         h->prof_qk.push_back(qk);
+        h->prof_form.push_back(form);
         h->prof_flops.push_back(flops);
         h->prof_tag.push_back(tag ? tag : "");
         (void)hipEventRecord(h->prof_events[h->prof_used], s);
@@ -1256,6 +1262,8 @@ void build_prune_plan(dsg_handle h) {
             }
         }
     }
+    // the read-out's working 32-token tiles (readout_stage), behind everything else (the plan stands without it where there is no room)
+    if (np.n_lists < NEED_MAX_LISTS) np.ro_tiles = new_list(N * N / 32);
     P = Q;
     P.np = np;
 }
@@ -1578,9 +1586,16 @@ void readout_stage(dsg_handle h, Workspace *w, hipStream_t s) {
         const float *fap_b = (bx_on(h) && h->opt.bf16_readout && h->ro_fapb) ? (const float *)bf16_of(h, h->ro_fapb) : nullptr;
         const float *f2p_b = fap_b ? (const float *)bf16_of(h, h->ro_f2pb) : nullptr;
         const bool ro_bf = fap_b && f2p_b;
+        // the list form, wherever the pruning runs and the plan has the list (need_ref): the tiles with a valid pair, packed at the front
+        // of the same grid.  "prune_masked" 0, debug taps and the split / bf16 modes keep the positional form
+        const NeedRef tiles = ro_bf ? NeedRef() : need_ref(h, w, w->need.ro_tiles);
+        if (!g_dry_run) w->ro_fwd = tiles.list ? 1 : 0;
+        h->prof_next_list = tiles.id;
+        h->prof_next_form = tiles.list ? " form=list" : " form=pos";
         P_KERN(PK_FUSED, 2.0 * (double)M0 * E * (E + 32.0),
                launch_fused_readout96(w->x, WT(h, "norm.weight"), WT(h, "norm.bias"), ro_bf ? fap_b : h->ro_fap, h->ro_fa, ro_bf ? f2p_b : h->ro_f2p,
-                                      WT(h, "readout_adj_mlp.fc2.bias"), w->flags, w->f_adj, w->pool_part, w->pool_ext, B, N, h->Ca, s, ro_bf));
+                                      WT(h, "readout_adj_mlp.fc2.bias"), w->flags, w->f_adj, w->pool_part, w->pool_ext, B, N, h->Ca, s, ro_bf,
+                                      tiles.list, tiles.cnt));
         g = GemmArgs();
         g.A = w->pool_ext; g.lda = 128; g.K1 = 128; g.K = 128; g.M = B * N; g.N = E; g.act = ACT_GELU;
         g.W = h->ro_gext; g.bias = WT(h, "readout_node_mlp.fc1.bias"); g.C = w->hn; g.ldc = E;
@@ -3167,7 +3182,7 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
     h->prof_clock_ghz = clocks.empty() ? 0.0 : clocks[clocks.size() / 2];
     // pass B: HIP-event brackets around every launch (per-class breakdown; each bracket includes dispatch latency)
     for (int iter = 0; iter < n_iters; iter++) {
-        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear(); h->prof_list.clear(); h->prof_thin_n.clear(); h->prof_qk.clear();
+        h->prof_on = true; h->prof_used = 0; h->prof_kind.clear(); h->prof_flops.clear(); h->prof_tag.clear(); h->prof_list.clear(); h->prof_thin_n.clear(); h->prof_qk.clear(); h->prof_form.clear();
         forward_fixed(h, w, s);
         const bool ok = h->prof_on;
         h->prof_on = false;
@@ -3187,7 +3202,7 @@ int dsg_profile_forward(dsg_handle h, int32_t B, int32_t n_iters, double *ms_by_
             HIP_TRY(h, hipEventElapsedTime(&ms, h->prof_events[2 * i], h->prof_events[2 * i + 1]));
             if (iter == n_iters - 1 && getenv("DSG_PROFILE_VERBOSE")) {
                 // a list GEMM with a thin form names the form its blocks chose: the kernel's rule on the count read back above
-                const char *form = "";
+                const char *form = h->prof_form[i] ? h->prof_form[i] : "";
                 if (nl >= 0 && nl < w->need.n_lists && h->prof_thin_n[i] > 0)
                     form = gemm_thin_rule(need_cnt[nl], h->prof_thin_n[i], h->n_cu) ? " form=thin" : " form=wide";
                 // a block with the "dedup_qkv" switch names the form its blocks chose (qk_split_rule on the count read back above)
@@ -3315,6 +3330,23 @@ int dsg_debug_dedup_qkv_lists(dsg_handle h, int32_t B, int32_t level, int32_t *c
     counts[3] = w->qk_fwd[level] ? (qk_split_rule(counts[0], qk_rule_rows(h, B * res * res)) ? 1 : 0) : -1;
     if (runs) memcpy(runs, all.data() + w->need.list_off[w->need.qk_runs[level]], sizeof(int) * (size_t)counts[0]);
     if (src) memcpy(src, all.data() + w->need.list_off[w->need.qk_src[level]], sizeof(int) * (size_t)counts[1]);
+    return DSG_OK;
+}
+
+int dsg_debug_readout_tiles(dsg_handle h, int32_t B, int32_t *counts, int32_t *tiles, void *stream) {
+    if (int rc = check_ready(h, B)) return rc;
+    if (!counts) return fail(h, DSG_ERR_INVALID, "null argument");
+    auto it = h->ws.find(B);
+    if (it == h->ws.end()) return fail(h, DSG_ERR_STATE, "no workspace for batch %d: run dsg_denoise/dsg_sample first", B);
+    Workspace *w = it->second.get();
+    counts[0] = counts[1] = -1;
+    if (!w->need_lists || w->need.ro_tiles < 0) return DSG_OK;
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    std::vector<int> all(w->need_ints);
+    HIP_TRY(h, hipMemcpy(all.data(), w->need_lists, sizeof(int) * w->need_ints, hipMemcpyDeviceToHost));
+    counts[0] = all[(w->need_cnt - w->need_lists) + w->need.ro_tiles];
+    counts[1] = w->ro_fwd;
+    if (tiles) memcpy(tiles, all.data() + w->need.list_off[w->need.ro_tiles], sizeof(int) * (size_t)counts[0]);
     return DSG_OK;
 }
 

@@ -200,7 +200,8 @@ bool launch_fused_patch_embed96(const float *adj, const float *node, const float
 int readout_pool_segments(int N);
 void launch_fused_readout96(const float *x, const float *gam, const float *bet, const float *Wfp, const float *fa, const float *W2p,
                             const float *f2, const uint8_t *flags, float *out_adj, float *pool_part, float *pool_ext, int B, int N,
-                            int Ca, hipStream_t s, bool bf16_frags = false);   // bf16_frags: Wfp / W2p are bf16 fragments (dsg_api.cpp: ro_fapb / ro_f2pb)
+                            int Ca, hipStream_t s, bool bf16_frags = false,   // bf16_frags: Wfp / W2p are bf16 fragments (dsg_api.cpp: ro_fapb / ro_f2pb)
+                            const int *tile_list = nullptr, const int *tile_cnt = nullptr);   // the list form (NeedPlan::ro_tiles; fp32 fragments only)
 // whole attention half of a C=96 Swin block in one kernel (modulate+SiLU, LN1, QKV, window attention, proj, residual);
 // windows of at most 64 tokens; packed weights from pack_attn_weights in dsg_api.cpp
 void launch_fused_attn96(float *x, const float *aff, int aff_ld, int aff_off, const float *gam, const float *bet, const float *Wqp,
@@ -257,8 +258,11 @@ struct NeedPlan { int n_ops = 0, n_lists = 0; NeedOp op[NEED_MAX_OPS]; int list_
                   // non-pure window plus those of one source pure window per content class (the batch's representative window under
                   // DD_BATCH / DD_TABLE, the graph's first pure window under DD_GRAPH; DD_OFF lists every window); qk_src [B * nW] -- for
                   // every window the window whose rows of the QKV tensor hold its q, k, v: itself when listed, else its class's source
-                      qk_runs[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}, qk_src[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}; };
-static_assert(sizeof(NeedPlan) == sizeof(int) * (2 + 4 * NEED_MAX_OPS + NEED_MAX_LISTS + 1 + 5 * (1 + NEED_MAX_DD_UP)), "NeedPlan is a kernel argument: keep it packed");
+                      qk_runs[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1}, qk_src[1 + NEED_MAX_DD_UP] = {-1, -1, -1, -1},
+                  // the fused read-out's working tiles (its list form) -- tile t is tokens [32 t, 32 t + 32) of the flattened [B * N * N]
+                  // index (a graph is a whole number of tiles: N % 8 == 0), listed when one of them has flag_i && flag_j; -1: no such list
+                      ro_tiles = -1; };
+static_assert(sizeof(NeedPlan) == sizeof(int) * (2 + 4 * NEED_MAX_OPS + NEED_MAX_LISTS + 1 + 5 * (1 + NEED_MAX_DD_UP) + 1), "NeedPlan is a kernel argument: keep it packed");
 // cnt_ps [B][n_lists] scratch, lists / cnt [n_lists] as above; two small launches, to be enqueued wherever the flags are staged
 // dedup (a DedupMode) / dd_rep / trim_mask: see below (dd_rep [plan.dd_n][B] + 1 int, the mode; may be null when the plan has no dd_* lists)
 enum DedupMode { DD_OFF = 0,      // every window is listed as unique, nothing is copied

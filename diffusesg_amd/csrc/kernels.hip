@@ -1575,26 +1575,32 @@ __device__ __forceinline__ void t96_store_rows_bf16(const float *tile, unsigned 
     }
 }
 
-template <bool BF>
+// LIST (wherever the masked-token pruning runs): tile_list holds, ascending, the 32-token tiles with a valid pair (need_lists_kernel: NeedPlan::ro_tiles),
+// *tile_cnt of them.  The grid stays the positional one.  A wave writes the exact zeros of its own tile blockIdx.x * 4 + wave where that
+// tile holds no valid pair (and nothing where it does), and then, where blockIdx.x * 4 + wave < *tile_cnt, computes the listed tile of
+// that index: every tile is written by one wave, with the arithmetic and the pooling slots of the positional form, and the working
+// waves stand four to a block at the front of the grid.
+template <bool BF, bool LIST = false>
 __global__ __launch_bounds__(256, 2) void fused_readout96_kernel(const float *__restrict__ x, const float *__restrict__ gam,
                                                                  const float *__restrict__ bet, const float *__restrict__ Wfp,
                                                                  const float *__restrict__ fa, const float *__restrict__ W2p,
                                                                  const float *__restrict__ f2, const uint8_t *__restrict__ flags,
                                                                  float *__restrict__ out_adj, float *__restrict__ pool_part,
-                                                                 int nseg, int B, int N, int Ca) {
+                                                                 int nseg, int B, int N, int Ca, const int *__restrict__ tile_list,
+                                                                 const int *__restrict__ tile_cnt) {
     constexpr int C = 96, S = 12;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lrow = lane & 31, lhalf = lane >> 5;
     const int T = N * N, M = B * T;
-    const int m = (blockIdx.x * 4 + wave) * 32 + lrow;
-    const bool ok = m < M;
-    const int mc = ok ? m : M - 1;
-    const int b = mc / T, i = (mc / N) % N, j = mc % N;
+    int tile = blockIdx.x * 4 + wave;
+    int m = tile * 32 + lrow;
+    bool ok = m < M;
+    int mc = ok ? m : M - 1;
+    int b = mc / T, i = (mc / N) % N, j = mc % N;
     if (!BF && __ballot(ok && flags[(size_t)b * N + i] != 0 && flags[(size_t)b * N + j] != 0) == 0) {
         // no valid pair among the wave's 32 tokens: the adjacency output and the pooling partials are exact zeros whatever x holds
         // (with masked-token pruning these rows of x are not computed at all), so the LayerNorm and both products are skipped.
         // Same slots as below: pool_finish_kernel's summation order does not change.
-        const int tile = blockIdx.x * 4 + wave;
         const int rowid = ok ? b * N + i : -1;
         const int r_first = __shfl(rowid, 0, 64);
         int r_last = __shfl(rowid, 31, 64);
@@ -1611,7 +1617,17 @@ __global__ __launch_bounds__(256, 2) void fused_readout96_kernel(const float *__
                 if (c < Ca) out_adj[(((size_t)b * Ca + c) * N + i) * N + j] = 0.f;
             }
         }
-        return;
+        if (!LIST) return;
+    }
+    if (LIST) {
+        // the wave's own tile is settled (zeroed above, or left to the wave that finds it in the list); now the listed tile of this index
+        if (tile >= *tile_cnt) return;
+        tile = tile_list[tile];
+        if (tile < 0 || tile > (M - 1) / 32) return;   // (never: the list holds tiles of this launch's flags)
+        m = tile * 32 + lrow;
+        ok = m < M;
+        mc = ok ? m : M - 1;
+        b = mc / T; i = (mc / N) % N; j = mc % N;
     }
     const float *xr = x + (size_t)mc * C + 4 * lhalf;
     f32x4 xn[S];
@@ -1648,7 +1664,6 @@ __global__ __launch_bounds__(256, 2) void fused_readout96_kernel(const float *__
     // partial for row r into slot (tile - first tile of r) of pool_part[r]; pool_finish_kernel adds a row's slots in slot
     // order, so the node head is bitwise reproducible.
     {
-        const int tile = blockIdx.x * 4 + wave;
         const int rowid = ok ? b * N + i : -1;
         const int r_first = __shfl(rowid, 0, 64);
         int r_last = __shfl(rowid, 31, 64);
@@ -1759,14 +1774,17 @@ int readout_pool_segments(int N) { return (N + 30) / 32 + 1; }  // most 32-token
 
 void launch_fused_readout96(const float *x, const float *gam, const float *bet, const float *Wfp, const float *fa, const float *W2p,
                             const float *f2, const uint8_t *flags, float *out_adj, float *pool_part, float *pool_ext, int B, int N,
-                            int Ca, hipStream_t s, bool bf16_frags) {
+                            int Ca, hipStream_t s, bool bf16_frags, const int *tile_list, const int *tile_cnt) {
     const int M = B * N * N, nseg = readout_pool_segments(N);
     if (bf16_frags)
         DSG_LAUNCH(fused_readout96_kernel<true>, dim3((M + 127) / 128), dim3(256), 0, s, x, gam, bet, Wfp, fa, W2p, f2, flags, out_adj,
-                           pool_part, nseg, B, N, Ca);
+                           pool_part, nseg, B, N, Ca, nullptr, nullptr);
+    else if (tile_list && tile_cnt)   // same grid: a captured launch is replayed with other flags, whatever the list then holds
+        DSG_LAUNCH((fused_readout96_kernel<false, true>), dim3((M + 127) / 128), dim3(256), 0, s, x, gam, bet, Wfp, fa, W2p, f2, flags, out_adj,
+                           pool_part, nseg, B, N, Ca, tile_list, tile_cnt);
     else
         DSG_LAUNCH(fused_readout96_kernel<false>, dim3((M + 127) / 128), dim3(256), 0, s, x, gam, bet, Wfp, fa, W2p, f2, flags, out_adj,
-                           pool_part, nseg, B, N, Ca);
+                           pool_part, nseg, B, N, Ca, nullptr, nullptr);
     const int n = B * N * 128;
     DSG_LAUNCH(pool_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, s, flags, pool_part, nseg, pool_ext, B, N);
 }
@@ -3213,6 +3231,12 @@ __global__ __launch_bounds__(256) void need_lists_kernel(const uint8_t *__restri
             cur[idx] = (flags[(size_t)b * N + i] != 0 && any) ? 1 : 0;
         }
         __syncthreads();
+    }
+    if (plan.ro_tiles >= 0) {   // the read-out's working tiles: 32 tokens = 4 consecutive runs of the graph's N * N / 8 (a multiple of 8)
+        const int nt = N * N / 32;
+        for (int t = tid; t < nt; t += 256) nxt[t] = (cur[4 * t] | cur[4 * t + 1] | cur[4 * t + 2] | cur[4 * t + 3]) ? 1 : 0;
+        __syncthreads();
+        emit(nxt, nt, plan.ro_tiles, b * nt);
     }
     for (int o = 0; o < plan.n_ops; o++) {
         const NeedOp op = plan.op[o];

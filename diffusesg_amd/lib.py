@@ -16,7 +16,7 @@ EXPORTS = [
     "dsg_num_weight_keys", "dsg_weight_key", "dsg_workspace_bytes", "dsg_denoise", "dsg_precond", "dsg_sample",
     "dsg_sigma_schedule", "dsg_debug_tap", "dsg_debug_clear_taps", "dsg_decode_bits", "dsg_decode", "dsg_profile_forward", "dsg_set_option",
     "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_f32", "dsg_debug_gemm_form", "dsg_debug_qkv_attn_f32", "dsg_debug_window_attn_f32", "dsg_debug_fused_mlp_f32", "dsg_debug_fused_attn96_f32", "dsg_debug_t_gemm", "dsg_debug_t_attn", "dsg_debug_t_ln", "dsg_debug_t_modulate", "dsg_debug_t_colsum", "dsg_debug_t_grouped", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists", "dsg_debug_dedup_lists", "dsg_debug_dedup_level_lists",
-    "dsg_debug_dedup_launch_lists", "dsg_debug_dedup_qkv_lists", "dsg_debug_qk_split",
+    "dsg_debug_dedup_launch_lists", "dsg_debug_dedup_qkv_lists", "dsg_debug_qk_split", "dsg_debug_readout_tiles",
     "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
     "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
     "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
@@ -209,6 +209,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_debug_dedup_level_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.dsg_debug_dedup_launch_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.dsg_debug_dedup_qkv_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.dsg_debug_readout_tiles.argtypes = [vp, i32, vp, vp, vp]
     L.dsg_debug_qk_split.argtypes = [i32, i32]
     L.dsg_debug_qk_split.restype = i32
     L.dsg_set_option.argtypes = [vp, C.c_char_p, i32]
@@ -448,6 +449,19 @@ class Handle:
             return None
         return dict(runs=runs[:counts[0]].copy(), src=src[:counts[1]].copy(), split=bool(counts[2]),
                     form={1: "split", 0: "fused"}.get(int(counts[3])))
+
+    def readout_tiles(self, B: int, stream=None):
+        """The fused read-out's working tiles (dsg_debug_readout_tiles): tiles -- ascending ids t of the 32-token tiles [32 t, 32 t + 32) of the
+        flattened [B * N * N] token index that hold a pair with flag_i and flag_j, as the flags last staged for batch B left them;
+        form -- what the last forward's fused read-out took ('list' | 'pos' | None: none yet).  None: the plan has no such list."""
+        import numpy as np
+        n = self.cfg.max_node_num
+        counts = np.zeros(2, np.int32)
+        tiles = np.zeros(max(1, (B * n * n + 31) // 32), np.int32)
+        self.check(self.L.dsg_debug_readout_tiles(self._h, B, counts.ctypes.data, tiles.ctypes.data, stream), "dsg_debug_readout_tiles")
+        if counts[0] < 0:
+            return None
+        return dict(tiles=tiles[:counts[0]].copy(), form={1: "list", 0: "pos"}.get(int(counts[1])))
 
     def precision_mode(self) -> str:
         """'f32' | 'f32-split' | 'bf16': the GEMM arithmetic the handle will actually run (options or DSG_* env defaults)."""

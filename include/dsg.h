@@ -576,6 +576,16 @@ int dsg_debug_dedup_launch_lists(dsg_handle h, int32_t B, int32_t level, int32_t
  * form the batch size's last forward took at that block: 1 split (the rule, or "dedup_qkv" 2: whatever the share), 0 fused, -1 the block ran without the switch (option off, another
  * kernel path, or the level not deduplicated).  All -1: the plan has no such lists for the level. */
 int dsg_debug_dedup_qkv_lists(dsg_handle h, int32_t B, int32_t level, int32_t *counts, int32_t *runs, int32_t *src, void *stream);
+/* The fused read-out (E = 96) under "prune_masked": it takes the list of its 32-token tiles that hold a valid pair (written with the need
+ * lists wherever the flags are staged) and computes them four to a block at the front of its grid; every wave still writes the exact zeros
+ * of its own positional tile where that tile holds no valid pair, so each tile is written once and the grid does not depend on the flags.
+ * Where the pruning does not run, every wave decides on its positional tile alone.  Bit-identical results either way.
+ * This call: the working tiles as the flags last staged for batch B left them.  tiles (room for B N N / 32):
+ * ascending ids t of the 32-token tiles [32 t, 32 t + 32) of the flattened [B N N] token index in which some (b, i, j) has
+ * flag_i && flag_j.  counts[0] = entries of tiles, counts[1] = the form the batch size's last forward's read-out took: 1 list,
+ * 0 positional, -1 no fused read-out yet.  Both -1: the plan has no such list (N % 8 != 0, 10 x 10 windows, or no room for it).
+ * The list is not among the records of dsg_debug_need_lists. */
+int dsg_debug_readout_tiles(dsg_handle h, int32_t B, int32_t *counts, int32_t *tiles, void *stream);
 /* The rule of that switch, from the function the kernels evaluate on the device-side count: 1 (split) iff listed_runs > 0 and the listed
  * rows, 8 per run, are at most half of the M rows.  Host only. */
 int32_t dsg_debug_qk_split(int32_t listed_runs, int32_t M);
