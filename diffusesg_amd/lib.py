@@ -1,4 +1,4 @@
-"""ctypes binding of libdsg.so (include/dsg.h).  There is NO fallback: if the HIP library is
+"""ctypes binding of libdsg.so (include/dsg.h, and include/dsg_debug.h for the test bench).  There is NO fallback: if the HIP library is
 missing or no GPU is visible, construction fails loudly."""
 from __future__ import annotations
 
@@ -10,26 +10,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdsg.so")
 MAX_LAYERS = 8
 
-# every symbol include/dsg.h declares (tests/test_abi.py checks the built library exports them)
+# every symbol include/dsg.h declares (tests/test_abi.py holds the header to this list and the built library to both lists)
 EXPORTS = [
     "dsg_create", "dsg_destroy", "dsg_last_error", "dsg_version", "dsg_abi_version", "dsg_set_weight", "dsg_finalize_weights",
-    "dsg_num_weight_keys", "dsg_weight_key", "dsg_workspace_bytes", "dsg_denoise", "dsg_precond", "dsg_sample",
-    "dsg_sigma_schedule", "dsg_debug_tap", "dsg_debug_clear_taps", "dsg_decode_bits", "dsg_decode", "dsg_profile_forward", "dsg_set_option",
-    "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss", "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads", "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_debug_gemm", "dsg_debug_gemm_f32", "dsg_debug_gemm_form", "dsg_debug_qkv_attn_f32", "dsg_debug_window_attn_f32", "dsg_debug_fused_mlp_f32", "dsg_debug_fused_attn96_f32", "dsg_debug_t_gemm", "dsg_debug_t_attn", "dsg_debug_t_ln", "dsg_debug_t_modulate", "dsg_debug_t_colsum", "dsg_debug_t_grouped", "dsg_debug_gemm_bx", "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz", "dsg_debug_need_lists", "dsg_debug_dedup_lists", "dsg_debug_dedup_level_lists",
-    "dsg_debug_dedup_launch_lists", "dsg_debug_dedup_qkv_lists", "dsg_debug_qk_split", "dsg_debug_readout_tiles",
-    "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep", "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd",
-    "dsg_sgstat_triplet_counts", "dsg_sgstat_layout", "dsg_sgstat_f1_rowstats",
-    "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
-    "dsg_sample_seeded", "dsg_gen_noise_seeded",
-    "dsg_precond_vjp", "dsg_debug_t_assemble_bwd",
-    "dsg_debug_patch_embed_f32", "dsg_debug_assemble_f32", "dsg_debug_readout_f32", "dsg_debug_head_f32", "dsg_debug_row_f32",
-    "dsg_debug_window_broadcast_f32", "dsg_debug_window_harvest_f32",
-    "dsg_ode_run", "dsg_ode_evals", "dsg_debug_graph_dot",
-    "dsg_debug_poison",
-    "dsg_guide_coef", "dsg_sample_guided", "dsg_debug_box_guide",
-    "dsg_sample_guided_rel", "dsg_debug_box_guide_rel",
-    "dsg_option_info",
-    "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp",
+    "dsg_num_weight_keys", "dsg_weight_key", "dsg_workspace_bytes", "dsg_denoise", "dsg_precond", "dsg_sample", "dsg_sigma_schedule",
+    "dsg_decode_bits", "dsg_decode", "dsg_set_option", "dsg_get_option", "dsg_gen_noise", "dsg_train_inputs", "dsg_rainbow_loss",
+    "dsg_rainbow_loss_backward", "dsg_noise_embed", "dsg_affine_width", "dsg_block_train", "dsg_train_grads", "dsg_train_step_grads",
+    "dsg_train_self_cond", "dsg_train_bind_params", "dsg_adam_step", "dsg_ema_update", "dsg_eval_bbox_prep_bytes", "dsg_eval_bbox_prep",
+    "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd", "dsg_sgstat_triplet_counts", "dsg_sgstat_layout",
+    "dsg_sgstat_f1_rowstats", "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
+    "dsg_sample_seeded", "dsg_gen_noise_seeded", "dsg_precond_vjp", "dsg_ode_run", "dsg_ode_evals", "dsg_guide_coef", "dsg_sample_guided",
+    "dsg_sample_guided_rel", "dsg_option_info",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -92,8 +83,25 @@ ODE_PROBES = {"none": 0, "rademacher": 1, "gaussian": 2}       # DSG_ODE_PROBE_*
 ODE_PROBE_STREAM = 0x0DE00000                                  # DSG_ODE_PROBE_STREAM: the noise stream of the device-drawn probe
 
 
+WALK_MAX_STEPS = 1 << 20   # DSG_WALK_MAX_STEPS
+
+
+# ---- the test bench: include/dsg_debug.h (every dsg_debug_* / dsg_profile_* entry of the same library, its structs and selectors) ----
+DEBUG_EXPORTS = [
+    "dsg_debug_tap", "dsg_debug_clear_taps", "dsg_profile_forward", "dsg_debug_gemm", "dsg_debug_gemm_f32", "dsg_debug_gemm_form",
+    "dsg_debug_qkv_attn_f32", "dsg_debug_window_attn_f32", "dsg_debug_fused_mlp_f32", "dsg_debug_fused_attn96_f32", "dsg_debug_t_gemm",
+    "dsg_debug_t_attn", "dsg_debug_t_ln", "dsg_debug_t_modulate", "dsg_debug_t_colsum", "dsg_debug_t_grouped", "dsg_debug_gemm_bx",
+    "dsg_debug_attn_bx", "dsg_debug_qkv_attn_bx", "dsg_debug_projmlp_bx", "dsg_debug_mlp_bx", "dsg_profile_clock_ghz",
+    "dsg_debug_need_lists", "dsg_debug_dedup_lists", "dsg_debug_dedup_level_lists", "dsg_debug_dedup_launch_lists",
+    "dsg_debug_dedup_qkv_lists", "dsg_debug_qk_split", "dsg_debug_readout_tiles", "dsg_debug_t_assemble_bwd", "dsg_debug_patch_embed_f32",
+    "dsg_debug_assemble_f32", "dsg_debug_readout_f32", "dsg_debug_head_f32", "dsg_debug_row_f32", "dsg_debug_window_broadcast_f32",
+    "dsg_debug_window_harvest_f32", "dsg_debug_graph_dot", "dsg_debug_poison", "dsg_debug_box_guide", "dsg_debug_box_guide_rel",
+    "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp",
+]
+
+
 class DsgGemmF32Args(C.Structure):
-    """dsg_gemm_f32_args of include/dsg.h (dsg_debug_gemm_f32): device pointers as integers, leading dimensions in floats"""
+    """dsg_gemm_f32_args of include/dsg_debug.h (dsg_debug_gemm_f32): device pointers as integers, leading dimensions in floats"""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "W", "bias", "ln_stats", "ln_part", "res", "C", "C2", "mod_aff", "stats_out",
                                            "row_list", "row_cnt")] +
                 [(n, C.c_int32) for n in ("lda", "lda2", "K1", "ln_nparts", "ldres", "ldc", "ldc2", "M", "N", "K", "act", "mod_ld",
@@ -101,7 +109,7 @@ class DsgGemmF32Args(C.Structure):
 
 
 class DsgGemmLpArgs(C.Structure):
-    """dsg_gemm_lp_args of include/dsg.h (dsg_debug_gemm_lp): the fields of DsgGemmF32Args, the host pointer tile_used behind the device
+    """dsg_gemm_lp_args of include/dsg_debug.h (dsg_debug_gemm_lp): the fields of DsgGemmF32Args, the host pointer tile_used behind the device
     pointers, and mode / tile / a_bf16 / c_bf16 behind the int32 fields"""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "W", "bias", "ln_stats", "ln_part", "res", "C", "C2", "mod_aff", "stats_out",
                                            "row_list", "row_cnt", "tile_used")] +
@@ -114,18 +122,74 @@ CONVERT_BF16, CONVERT_SPLIT3, CONVERT_WIDEN = range(3)                          
 
 
 class DsgTProb(C.Structure):
-    """dsg_t_prob of include/dsg.h (dsg_debug_t_grouped): one problem of a grouped launch"""
+    """dsg_t_prob of include/dsg_debug.h (dsg_debug_t_grouped): one problem of a grouped launch"""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "B", "bias", "C")] + [(n, C.c_int32) for n in ("lda", "ldb", "ldc", "M", "N", "K")])
 
 
 T_GROUP_MAX = 32
-TGROUP_NT, TGROUP_TN, TGROUP_NN, TGROUP_NN_SUM, TGROUP_SUM, TGROUP_COLSUM, TGROUP_TT = range(7)   # DSG_TGROUP_* of include/dsg.h
+TGROUP_NT, TGROUP_TN, TGROUP_NN, TGROUP_NN_SUM, TGROUP_SUM, TGROUP_COLSUM, TGROUP_TT = range(7)   # DSG_TGROUP_* of include/dsg_debug.h
 
 DD_OFF, DD_GRAPH, DD_BATCH, DD_TABLE = range(4)                                                    # DedupMode of csrc/kernels.h (mode of dsg_debug_window_broadcast_f32)
 HEAD_ADJ, HEAD_POOL, HEAD_NODE = range(3)                                                          # DSG_HEAD_* (dsg_debug_head_f32)
 ROW_MOD_STATS, ROW_LN_STATS, ROW_LN_MOD, ROW_MERGE_LN, ROW_BREAKUP_LN, ROW_MERGE_NORM_RUNS = range(6)   # DSG_ROW_* (dsg_debug_row_f32)
 
-WALK_MAX_STEPS = 1 << 20   # DSG_WALK_MAX_STEPS
+# DSG_BXK_*: the `kernel` argument of dsg_debug_mlp_bx / dsg_debug_projmlp_bx / dsg_debug_qkv_attn_bx (BXK_DEFAULT: what the forward runs)
+(BXK_DEFAULT, BXK_MLP384_DMA, BXK_MLP384_WAVE, BXK_MLP384_R3, BXK_MLP384_SOLO, BXK_MLP96_STAGED, BXK_MLP96_RESIDENT, BXK_QA10_WAVE,
+ BXK_QA10_HEAD) = range(9)
+
+
+def _declare_debug(L: C.CDLL) -> None:
+    """the prototypes of include/dsg_debug.h; load() calls this on the library it has just opened"""
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.dsg_debug_box_guide.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DsgGuideCfg), C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    L.dsg_debug_box_guide_rel.argtypes = L.dsg_debug_box_guide.argtypes + [C.POINTER(DsgRelCfg), vp]
+    L.dsg_debug_tap.argtypes = [vp, C.c_char_p, vp, i64]
+    L.dsg_debug_clear_taps.argtypes = [vp]
+    L.dsg_debug_clear_taps.restype = None
+    L.dsg_debug_need_lists.argtypes = [vp, i32, vp, i32, C.POINTER(i32), vp, i64, vp]
+    L.dsg_debug_dedup_lists.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.dsg_debug_dedup_level_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.dsg_debug_dedup_launch_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.dsg_debug_dedup_qkv_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.dsg_debug_readout_tiles.argtypes = [vp, i32, vp, vp, vp]
+    L.dsg_debug_qk_split.argtypes = [i32, i32]
+    L.dsg_debug_qk_split.restype = i32
+    L.dsg_profile_clock_ghz.argtypes = [vp]
+    L.dsg_profile_clock_ghz.restype = C.c_double
+    L.dsg_debug_gemm.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    L.dsg_debug_gemm_f32.argtypes = [C.POINTER(DsgGemmF32Args), vp]
+    L.dsg_debug_gemm_form.argtypes = [i32, i32, i32]
+    L.dsg_debug_gemm_lp.argtypes = [C.POINTER(DsgGemmLpArgs), vp]
+    L.dsg_debug_convert.argtypes = [i32, vp, vp, C.c_int64, vp]
+    L.dsg_debug_row_lp.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.dsg_debug_window_attn_lp.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
+    L.dsg_debug_gemm_form.restype = i32
+    L.dsg_debug_qkv_attn_f32.argtypes = [i32] * 6 + [vp] * 5 + [i32] + [vp] * 5
+    L.dsg_debug_window_attn_f32.argtypes = [i32] * 5 + [vp] * 4
+    L.dsg_debug_fused_mlp_f32.argtypes = [i32, i32] + [vp] * 11
+    L.dsg_debug_fused_attn96_f32.argtypes = [i32] * 4 + [vp, vp, i32, i32] + [vp] * 7 + [i32, vp, vp, vp]
+    L.dsg_debug_patch_embed_f32.argtypes = [i32] * 6 + [vp] * 11 + [i32] * 3 + [vp] * 4
+    L.dsg_debug_assemble_f32.argtypes = [i32] * 6 + [vp] * 8
+    L.dsg_debug_readout_f32.argtypes = [i32] * 3 + [vp] * 12
+    L.dsg_debug_head_f32.argtypes = [i32] * 5 + [vp] * 6
+    L.dsg_debug_row_f32.argtypes = [i32] * 4 + [vp] * 6 + [i32, i32, vp, i32] + [vp] * 5
+    L.dsg_debug_window_broadcast_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32] + [vp] * 4 + [i32, i64] + [i32] * 6 + [vp, vp]
+    L.dsg_debug_window_harvest_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32, vp, i64] + [i32] * 3 + [vp]
+    L.dsg_debug_t_gemm.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.POINTER(i32), vp]
+    L.dsg_debug_t_attn.argtypes = [i32] * 6 + [vp] * 6 + [i32, vp]
+    L.dsg_debug_t_ln.argtypes = [i32] * 4 + [vp] * 13
+    L.dsg_debug_t_modulate.argtypes = [i32] * 4 + [vp] * 6
+    L.dsg_debug_t_colsum.argtypes = [vp, i32, vp, i32, i32, vp]
+    L.dsg_debug_t_grouped.argtypes = [i32, i32, C.POINTER(DsgTProb), vp, i32, vp]
+    L.dsg_debug_gemm_bx.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, C.POINTER(C.c_float), vp]
+    L.dsg_debug_attn_bx.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_float), vp]
+    L.dsg_debug_projmlp_bx.argtypes = [i32, i32] + [vp] * 9 + [i32, vp, i32, i32, C.POINTER(C.c_float), vp]
+    L.dsg_debug_qkv_attn_bx.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, C.POINTER(C.c_float), vp]
+    L.dsg_debug_mlp_bx.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, C.POINTER(C.c_float), vp]
+    L.dsg_debug_t_assemble_bwd.argtypes = [i32] * 5 + [vp, i32] + [vp] * 8
+    L.dsg_debug_graph_dot.argtypes = [i32] * 4 + [vp] * 7
+    L.dsg_debug_poison.argtypes = [vp, i32, i32, C.c_uint64, vp]
+    L.dsg_profile_forward.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
 
 
 _lib = None
@@ -133,11 +197,11 @@ _lib = None
 
 # ABI generation of include/dsg.h this binding was written against (DSG_ABI_VERSION there): argument lists changed between rounds
 # (e.g. iou_loss_type in the loss entries), and a stale libdsg.so would take shifted arguments without any error
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 def load(path: Optional[str] = None) -> C.CDLL:
-    """dlopen libdsg.so and declare the prototypes of include/dsg.h.  `path`: another build of the library -- the kernel-variant
+    """dlopen libdsg.so and declare the prototypes of include/dsg.h and include/dsg_debug.h.  `path`: another build of the library -- the kernel-variant
     A/B builds of the dev tools pass it explicitly (tools/bx_bench.py); the product and the tests always load the in-tree one, and
     no environment variable redirects the load."""
     global _lib
@@ -193,61 +257,16 @@ def load(path: Optional[str] = None) -> C.CDLL:
                                     vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(DsgGuideCfg), vp, vp, vp, vp, vp, C.POINTER(DsgSampleStats), vp]
     L.dsg_guide_coef.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, i32]
     L.dsg_guide_coef.restype = i32
-    L.dsg_debug_box_guide.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DsgGuideCfg), C.c_float, vp, vp, vp, vp, vp, vp, vp]
     L.dsg_sample_guided_rel.argtypes = L.dsg_sample_guided.argtypes + [C.POINTER(DsgRelCfg)]
-    L.dsg_debug_box_guide_rel.argtypes = L.dsg_debug_box_guide.argtypes + [C.POINTER(DsgRelCfg), vp]
     L.dsg_walk_steps.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, vp, i32]
     L.dsg_walk_steps.restype = i32
     L.dsg_multistep_coef.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, i32]
     L.dsg_multistep_coef.restype = i32
     L.dsg_sigma_schedule.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, vp, vp]
-    L.dsg_debug_tap.argtypes = [vp, C.c_char_p, vp, i64]
-    L.dsg_debug_clear_taps.argtypes = [vp]
-    L.dsg_debug_clear_taps.restype = None
-    L.dsg_debug_need_lists.argtypes = [vp, i32, vp, i32, C.POINTER(i32), vp, i64, vp]
-    L.dsg_debug_dedup_lists.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
-    L.dsg_debug_dedup_level_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.dsg_debug_dedup_launch_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
-    L.dsg_debug_dedup_qkv_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-    L.dsg_debug_readout_tiles.argtypes = [vp, i32, vp, vp, vp]
-    L.dsg_debug_qk_split.argtypes = [i32, i32]
-    L.dsg_debug_qk_split.restype = i32
     L.dsg_set_option.argtypes = [vp, C.c_char_p, i32]
     L.dsg_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
     L.dsg_option_info.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)] + [C.POINTER(i32)] * 3
     L.dsg_gen_noise.argtypes = [vp, i32, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
-    L.dsg_profile_clock_ghz.argtypes = [vp]
-    L.dsg_profile_clock_ghz.restype = C.c_double
-    L.dsg_debug_gemm.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
-    L.dsg_debug_gemm_f32.argtypes = [C.POINTER(DsgGemmF32Args), vp]
-    L.dsg_debug_gemm_form.argtypes = [i32, i32, i32]
-    L.dsg_debug_gemm_lp.argtypes = [C.POINTER(DsgGemmLpArgs), vp]
-    L.dsg_debug_convert.argtypes = [i32, vp, vp, C.c_int64, vp]
-    L.dsg_debug_row_lp.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.dsg_debug_window_attn_lp.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
-    L.dsg_debug_gemm_form.restype = i32
-    L.dsg_debug_qkv_attn_f32.argtypes = [i32] * 6 + [vp] * 5 + [i32] + [vp] * 5
-    L.dsg_debug_window_attn_f32.argtypes = [i32] * 5 + [vp] * 4
-    L.dsg_debug_fused_mlp_f32.argtypes = [i32, i32] + [vp] * 11
-    L.dsg_debug_fused_attn96_f32.argtypes = [i32] * 4 + [vp, vp, i32, i32] + [vp] * 7 + [i32, vp, vp, vp]
-    L.dsg_debug_patch_embed_f32.argtypes = [i32] * 6 + [vp] * 11 + [i32] * 3 + [vp] * 4
-    L.dsg_debug_assemble_f32.argtypes = [i32] * 6 + [vp] * 8
-    L.dsg_debug_readout_f32.argtypes = [i32] * 3 + [vp] * 12
-    L.dsg_debug_head_f32.argtypes = [i32] * 5 + [vp] * 6
-    L.dsg_debug_row_f32.argtypes = [i32] * 4 + [vp] * 6 + [i32, i32, vp, i32] + [vp] * 5
-    L.dsg_debug_window_broadcast_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32] + [vp] * 4 + [i32, i64] + [i32] * 6 + [vp, vp]
-    L.dsg_debug_window_harvest_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32, vp, i64] + [i32] * 3 + [vp]
-    L.dsg_debug_t_gemm.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.POINTER(i32), vp]
-    L.dsg_debug_t_attn.argtypes = [i32] * 6 + [vp] * 6 + [i32, vp]
-    L.dsg_debug_t_ln.argtypes = [i32] * 4 + [vp] * 13
-    L.dsg_debug_t_modulate.argtypes = [i32] * 4 + [vp] * 6
-    L.dsg_debug_t_colsum.argtypes = [vp, i32, vp, i32, i32, vp]
-    L.dsg_debug_t_grouped.argtypes = [i32, i32, C.POINTER(DsgTProb), vp, i32, vp]
-    L.dsg_debug_gemm_bx.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, C.POINTER(C.c_float), vp]
-    L.dsg_debug_attn_bx.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_float), vp]
-    L.dsg_debug_projmlp_bx.argtypes = [i32, i32] + [vp] * 9 + [i32, vp, i32, C.POINTER(C.c_float), vp]
-    L.dsg_debug_qkv_attn_bx.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_float), vp]
-    L.dsg_debug_mlp_bx.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.POINTER(C.c_float), vp]
     L.dsg_train_inputs.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp]
     L.dsg_rainbow_loss.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp]
     L.dsg_block_train.argtypes = [vp, C.c_char_p, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), vp]
@@ -255,12 +274,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_train_step_grads.argtypes = [vp, i32] + [vp] * 9 + [C.c_float] * 3 + [i32] + [vp] * 4 + [i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), vp]
     L.dsg_train_self_cond.argtypes = [vp, i32] + [vp] * 7
     L.dsg_precond_vjp.argtypes = [vp, i32] + [vp] * 8 + [GRAD_FN, vp] + [vp] * 5
-    L.dsg_debug_t_assemble_bwd.argtypes = [i32] * 5 + [vp, i32] + [vp] * 8
     L.dsg_ode_run.argtypes = [vp, C.POINTER(DsgSamplerCfg), C.POINTER(DsgOdeCfg), i32] + [vp] * 12
     L.dsg_ode_evals.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgOdeCfg), vp, vp, i32]
     L.dsg_ode_evals.restype = i32
-    L.dsg_debug_graph_dot.argtypes = [i32] * 4 + [vp] * 7
-    L.dsg_debug_poison.argtypes = [vp, i32, i32, C.c_uint64, vp]
     L.dsg_train_bind_params.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
     L.dsg_adam_step.argtypes = [i32] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int64), i32] + [C.c_float] * 6 + [C.POINTER(C.c_float), vp]
     L.dsg_ema_update.argtypes = [i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, vp]
@@ -268,7 +284,6 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_affine_width.argtypes = [vp]
     L.dsg_affine_width.restype = i32
     L.dsg_rainbow_loss_backward.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp]
-    L.dsg_profile_forward.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.dsg_decode_bits.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.dsg_decode.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     L.dsg_encode.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
@@ -282,6 +297,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_sgstat_triplet_counts.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.dsg_sgstat_layout.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp]
     L.dsg_sgstat_f1_rowstats.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    _declare_debug(L)
     _lib = L
     return L
 

@@ -1,8 +1,10 @@
-"""CPU: the C-ABI library loads and exports every symbol include/dsg.h declares; the host-only schedule helper
+"""CPU: the C-ABI library loads and exports every symbol include/dsg.h and include/dsg_debug.h declare; the host-only schedule helper
 matches the reference's sigma tables; the state-dict layout matches the golden generator's check."""
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -14,14 +16,69 @@ from util import load
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _declared(header):
+    hdr = open(os.path.join(ROOT, "include", header)).read()
+    return set(re.findall(r"\b(dsg_[a-z_0-9]+)\s*\(", hdr)) - {"dsg_handle_s"}
+
+
+def _is_bench(name):
+    return name.startswith(("dsg_debug_", "dsg_profile_"))
+
+
 def test_header_symbols_exported():
+    """each header against its own list, both ways; the product header declares no test or measurement hook, the test-bench header
+    nothing else; the library exports all of both"""
+    product, bench = _declared("dsg.h"), _declared("dsg_debug.h")
+    assert product == set(lib.EXPORTS), product ^ set(lib.EXPORTS)
+    assert bench == set(lib.DEBUG_EXPORTS), bench ^ set(lib.DEBUG_EXPORTS)
+    assert len(set(lib.EXPORTS)) == len(lib.EXPORTS) and len(set(lib.DEBUG_EXPORTS)) == len(lib.DEBUG_EXPORTS)
+    assert not [n for n in product if _is_bench(n)]
+    assert not [n for n in bench if not _is_bench(n)]
     hdr = open(os.path.join(ROOT, "include", "dsg.h")).read()
-    declared = set(re.findall(r"\b(dsg_[a-z_0-9]+)\s*\(", hdr)) - {"dsg_handle_s"}
-    assert declared == set(lib.EXPORTS), declared ^ set(lib.EXPORTS)
+    assert "dsg_debug_" not in hdr and "dsg_profile_" not in hdr and not re.search(r"#\s*include\s*\"dsg_debug\.h\"", hdr)
     L = lib.load()
-    for name in declared:
+    for name in product | bench:
         assert hasattr(L, name), f"libdsg.so does not export {name}"
     assert b"gfx950" in L.dsg_version()
+    assert L.dsg_abi_version() == lib.ABI_VERSION == int(re.search(r"#define DSG_ABI_VERSION (\d+)", hdr).group(1)) == 5
+
+
+@pytest.mark.parametrize("lang", ["c", "c++"])
+@pytest.mark.parametrize("includes", [("dsg.h",), ("dsg_debug.h",), ("dsg.h", "dsg_debug.h")])
+def test_headers_compile_on_their_own(lang, includes, tmp_path):
+    """each public header is self-contained C and C++: the host compiler's syntax pass over a file that only includes it
+    (dsg_debug.h with and without dsg.h in front)"""
+    names = ("gcc", "cc", "clang", "/opt/rocm/lib/llvm/bin/clang") if lang == "c" else ("g++", "c++", "clang++", "/opt/rocm/lib/llvm/bin/clang++")
+    cc = next((shutil.which(n) for n in names if shutil.which(n)), None)
+    assert cc, "no host compiler"
+    src = tmp_path / ("t.c" if lang == "c" else "t.cpp")
+    src.write_text("".join(f'#include "{h}"\n' for h in includes))
+    r = subprocess.run([cc, "-x", lang, "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_bx_kernel_selectors_are_checked():
+    """a kernel name a bf16-pipeline hook cannot honour for the shape is DSG_ERR_INVALID, not ignored: the check runs ahead of any
+    device call, so no GPU is needed (the operand pointers are never read)"""
+    L = lib.load()
+    buf = (C.c_float * 4)()
+    p = C.cast(buf, C.c_void_p)
+    mlp = lambda Cc, mod, k: L.dsg_debug_mlp_bx(8, Cc, p, p, p, p, p, p, p if mod else None, 0, None, k, 0, None, None)
+    proj = lambda Cc, mod, k: L.dsg_debug_projmlp_bx(8, Cc, p, p, p, p, p, p, p, p, p if mod else None, 0, None, k, 0, None, None)
+    qa = lambda ws, k: L.dsg_debug_qkv_attn_bx(1, 2 * ws, ws, 0, 3, p, p, p, p, p, k, 0, None, None)
+    bad = lib.DSG_ERR_INVALID
+    for k in (lib.BXK_MLP384_DMA, lib.BXK_MLP384_WAVE, lib.BXK_MLP384_R3, lib.BXK_MLP384_SOLO):
+        assert mlp(96, 0, k) == bad and mlp(192, 1, k) == bad and proj(96, 0, k) == bad
+    assert proj(384, 0, lib.BXK_MLP384_WAVE) == bad                     # the proj form has no one-wave-per-SIMD kernel
+    for k in (lib.BXK_MLP96_STAGED, lib.BXK_MLP96_RESIDENT, lib.BXK_QA10_WAVE, lib.BXK_QA10_HEAD, 9, -1):
+        assert mlp(96, 0, k) == bad and mlp(384, 0, k) == bad           # not kernels of the plain MLP hook
+    for k in (lib.BXK_MLP96_STAGED, lib.BXK_MLP96_RESIDENT):
+        assert proj(192, 0, k) == bad and proj(384, 0, k) == bad
+    assert proj(96, 1, lib.BXK_MLP96_RESIDENT) == bad                   # the LDS-resident kernel has no modulate
+    for k in (lib.BXK_QA10_WAVE, lib.BXK_QA10_HEAD):
+        assert qa(8, k) == bad and qa(4, k) == bad
+    assert qa(10, lib.BXK_MLP384_DMA) == bad and qa(10, 9) == bad and proj(96, 0, 9) == bad
 
 
 @pytest.mark.parametrize("T", [50, 100, 256, 1000])
@@ -45,6 +102,11 @@ def test_structs_match_header_layout():
     assert C.sizeof(lib.DsgSampleStats) == 24
     assert C.sizeof(lib.DsgGemmF32Args) == 13 * 8 + 16 * 4      # dsg_gemm_f32_args: thirteen pointers, sixteen int32
     assert lib.DsgGemmF32Args.lda.offset == 13 * 8 and lib.DsgGemmF32Args.reserved.offset == 13 * 8 + 15 * 4
+    assert C.sizeof(lib.DsgGemmLpArgs) == 14 * 8 + 20 * 4       # dsg_gemm_lp_args: fourteen pointers (tile_used last), twenty int32
+    assert lib.DsgGemmLpArgs.tile_used.offset == 13 * 8 and lib.DsgGemmLpArgs.lda.offset == 14 * 8
+    assert lib.DsgGemmLpArgs.mode.offset == 14 * 8 + 16 * 4 and lib.DsgGemmLpArgs.c_bf16.offset == 14 * 8 + 19 * 4
+    assert C.sizeof(lib.DsgTProb) == 4 * 8 + 6 * 4              # dsg_t_prob: four pointers, six int32
+    assert lib.DsgTProb.C.offset == 3 * 8 and lib.DsgTProb.lda.offset == 4 * 8 and lib.DsgTProb.K.offset == 4 * 8 + 5 * 4
 
 
 def test_param_counts_and_flops():

@@ -114,19 +114,26 @@ def test_attn_bx_vs_torch(B, res, ws, shift, heads):
     assert worst <= 2e-3, f"attention: {worst:.2e} beyond bf16 rounding of the output"
 
 
-@pytest.mark.parametrize("B,res,ws,shift,heads", [(3, 10, 10, 0, 12), (5, 20, 10, 5, 6), (2, 40, 10, 0, 3), (4, 16, 8, 4, 12), (3, 8, 8, 0, 24),
-                                                  (5, 16, 8, 0, 3), (2, 16, 4, 2, 3), (7, 4, 4, 0, 6), (3, 10, 5, 2, 3),
-                                                  (48, 20, 10, 5, 6), (41, 16, 8, 4, 12),    # > 512 (window group, head) tiles
-                                                  (3, 10, 10, 1000, 12), (5, 20, 10, 1005, 6), (2, 40, 10, 1000, 3),   # shift + 1000: the block-per-head kernel at 10 x 10
-                                                  (1, 10, 10, 0, 3), (7, 10, 10, 0, 6), (3, 20, 10, 5, 3)])            # units not a multiple of 4, blocks across two windows
-def test_qkv_attn_bx_vs_torch(B, res, ws, shift, heads):
+def _qa(B, res, ws, shift, heads, kernel="DEFAULT"):
+    """a case of test_qkv_attn_bx_vs_torch.  Its id stays what it was while the block-per-head kernel was selected by shift + 1000, so
+    that results line up across the history."""
+    return pytest.param(B, res, ws, shift, heads, kernel, id=f"{B}-{res}-{ws}-{shift + (1000 if kernel == 'QA10_HEAD' else 0)}-{heads}")
+
+
+@pytest.mark.parametrize("B,res,ws,shift,heads,kernel", [
+    _qa(3, 10, 10, 0, 12), _qa(5, 20, 10, 5, 6), _qa(2, 40, 10, 0, 3), _qa(4, 16, 8, 4, 12), _qa(3, 8, 8, 0, 24),
+    _qa(5, 16, 8, 0, 3), _qa(2, 16, 4, 2, 3), _qa(7, 4, 4, 0, 6), _qa(3, 10, 5, 2, 3),
+    _qa(48, 20, 10, 5, 6), _qa(41, 16, 8, 4, 12),    # > 512 (window group, head) tiles
+    _qa(3, 10, 10, 0, 12, "QA10_HEAD"), _qa(5, 20, 10, 5, 6, "QA10_HEAD"), _qa(2, 40, 10, 0, 3, "QA10_HEAD"),   # the block-per-head kernel at 10 x 10
+    _qa(1, 10, 10, 0, 3), _qa(7, 10, 10, 0, 6), _qa(3, 20, 10, 5, 3)])            # units not a multiple of 4, blocks across two windows
+def test_qkv_attn_bx_vs_torch(B, res, ws, shift, heads, kernel):
     """QKV projection + window attention in one kernel against fp64 on the bf16-rounded operands: q, k, v are formed in fp32, rounded
     to bf16 (as the kernel hands them to the second and third product) and then follow test_attn_bx_vs_torch's reference.  Odd unit
     counts (the last block is partly empty), two / four windows per block (64- / 16- / 25-token windows), shifted masks, C = 96 (K ends
     inside a 64-deep chunk) up to 768."""
     from diffusesg_amd import lib as L
     lib = L.load()
-    variant, shift = divmod(shift, 1000)               # 10 x 10 windows: 0 the wave-per-unit kernel, 1 the block-per-head kernel
+    variant = 1 if kernel == "QA10_HEAD" else 0        # 10 x 10 windows: 0 the wave-per-unit kernel (the default), 1 the block-per-head kernel
     Cc, T, Wt = 32 * heads, res * res, ws * ws
     Wp = (Wt + 31) // 32 * 32
     nW = (res // ws) ** 2
@@ -141,7 +148,7 @@ def test_qkv_attn_bx_vs_torch(B, res, ws, shift, heads):
         bias[torch.rand(nWt, 1, Wp, Wp, device="cuda", generator=gen).expand(-1, heads, -1, -1) < 0.2] -= 144.0
     bias[:, :, Wt:, :] = -1.0e30
     out = torch.full((B * T, Cc), float("nan"), device="cuda")
-    rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift + 1000 * variant, heads, _p(xn), _p(W), _p(bqkv), _p(bias.contiguous()), _p(out), 0, None, None)
+    rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift, heads, _p(xn), _p(W), _p(bqkv), _p(bias.contiguous()), _p(out), getattr(L, "BXK_" + kernel), 0, None, None)
     assert rc == 0
     qkv = _bf((_bf(xn).double() @ _bf(W).double().t() + bqkv.double()).float())
     tok = torch.from_numpy(_window_tokens(res, ws, shift)).cuda()
@@ -164,11 +171,22 @@ def test_qkv_attn_bx_vs_torch(B, res, ws, shift, heads):
     assert worst <= 4e-3, f"qkv + attention: {worst:.2e} beyond bf16 rounding of the output"
 
 
-@pytest.mark.parametrize("M,C,mod,out_mode", [(51200, 384, 1, 1), (20037, 192, 1, 1), (65541, 96, 0, 2), (300, 96, 1, 1), (4096, 384, 0, 0),
-                                               (1000, 192, 0, 2), (20037, 384, 0, 2), (51200, 384, 1, 1 + 16), (4100, 384, 0, 2 + 16),
-                                               (51200, 384, 1, 1 + 32), (20037, 384, 0, 2 + 32), (130, 384, 1, 1),
-                                               (51200, 384, 1, 1 + 64), (20037, 384, 0, 2 + 64), (4096, 384, 0, 0 + 64), (130, 384, 2, 1 + 64)])
-def test_mlp_bx_whole_matrix(M, C, mod, out_mode):
+_MLP_OLD_ID = {"DEFAULT": 0, "MLP384_WAVE": 16, "MLP384_R3": 32, "MLP384_SOLO": 64, "MLP96_RESIDENT": 128}
+
+
+def _mlp(M, C, mod, out_mode, kernel="DEFAULT"):
+    """a case of the two fused-MLP tests.  Its id stays what it was while the kernel was selected by a number added to out_mode, so that
+    results line up across the history."""
+    return pytest.param(M, C, mod, out_mode, kernel, id=f"{M}-{C}-{mod}-{out_mode + _MLP_OLD_ID[kernel]}")
+
+
+@pytest.mark.parametrize("M,C,mod,out_mode,kernel", [
+    _mlp(51200, 384, 1, 1), _mlp(20037, 192, 1, 1), _mlp(65541, 96, 0, 2), _mlp(300, 96, 1, 1), _mlp(4096, 384, 0, 0),
+    _mlp(1000, 192, 0, 2), _mlp(20037, 384, 0, 2), _mlp(51200, 384, 1, 1, "MLP384_WAVE"), _mlp(4100, 384, 0, 2, "MLP384_WAVE"),
+    _mlp(51200, 384, 1, 1, "MLP384_R3"), _mlp(20037, 384, 0, 2, "MLP384_R3"), _mlp(130, 384, 1, 1),
+    _mlp(51200, 384, 1, 1, "MLP384_SOLO"), _mlp(20037, 384, 0, 2, "MLP384_SOLO"), _mlp(4096, 384, 0, 0, "MLP384_SOLO"),
+    _mlp(130, 384, 2, 1, "MLP384_SOLO")])
+def test_mlp_bx_whole_matrix(M, C, mod, out_mode, kernel):
     """the fused fc1 -> GELU -> fc2 -> + residual -> [modulate] -> [LayerNorm | copy] kernel at its three widths against fp64 on the
     bf16-rounded operands, with the hidden activations rounded to bf16 between the two products as the kernel does"""
     from diffusesg_amd import lib as L
@@ -183,11 +201,11 @@ def test_mlp_bx_whole_matrix(M, C, mod, out_mode):
     aff = (torch.randn(2 * C, device="cuda", generator=gen) * 0.5) if mod else None
     x_io = x.clone()
     out_xn = torch.full((M, C), float("nan"), device="cuda")
-    # C = 384: the eight-wave LDS-DMA kernel on pre-arranged weight images (round 4); out_mode + 32 selects round 3's eight-wave kernel
-    # (register-staged weights), + 16 the one-wave-per-SIMD kernel
-    rc = lib.dsg_debug_mlp_bx(M, C, _p(xn), _p(x_io), _p(W1), _p(b1), _p(W2), _p(b2), _p(aff), out_mode, _p(out_xn) if out_mode else None, 0, None, None)
+    # C = 384: the default is the eight-wave LDS-DMA kernel on pre-arranged weight images (round 4); MLP384_R3 round 3's eight-wave kernel
+    # (register-staged weights), MLP384_WAVE the one-wave-per-SIMD kernel, MLP384_SOLO four waves solo (DSG_BXK_* of include/dsg_debug.h)
+    rc = lib.dsg_debug_mlp_bx(M, C, _p(xn), _p(x_io), _p(W1), _p(b1), _p(W2), _p(b2), _p(aff), out_mode, _p(out_xn) if out_mode else None,
+                              getattr(L, "BXK_" + kernel), 0, None, None)
     assert rc == 0
-    out_mode &= 15
     hid = torch.nn.functional.gelu(_bf(xn).double() @ _bf(W1).double().t() + b1.double())
     v = _bf(hid.float()).double() @ _bf(W2).double().t() + b2.double() + x.double()
     if aff is not None:
@@ -204,13 +222,15 @@ def test_mlp_bx_whole_matrix(M, C, mod, out_mode):
         assert worst <= 1e-3, f"bf16 output: {worst:.2e} beyond bf16 rounding"
 
 
-@pytest.mark.parametrize("M,C,mod,out_mode", [(20037, 192, 1, 1), (65541, 96, 0, 2), (300, 96, 1, 1), (4096, 192, 0, 0), (51200, 96, 1, 1),
-                                               (51200, 384, 1, 1), (20037, 384, 0, 2), (300, 384, 0, 0),
-                                               (51200, 384, 1, 1 + 32), (20037, 384, 0, 2 + 32), (129, 384, 1, 1),
-                                               (51200, 384, 1, 1 + 64), (20037, 384, 0, 2 + 64), (300, 384, 0, 0 + 64), (129, 384, 1, 1 + 64),
-                                               (65541, 96, 0, 2 + 128), (4096, 96, 0, 0 + 128), (129, 96, 0, 1 + 128), (100003, 96, 0, 1 + 128), (31, 96, 0, 2 + 128),   # + 128: C = 96 on the LDS-resident kernel
-                                               (4096, 96, 0, 0), (129, 96, 0, 1)])
-def test_projmlp_bx_whole_matrix(M, C, mod, out_mode):
+@pytest.mark.parametrize("M,C,mod,out_mode,kernel", [
+    _mlp(20037, 192, 1, 1), _mlp(65541, 96, 0, 2), _mlp(300, 96, 1, 1), _mlp(4096, 192, 0, 0), _mlp(51200, 96, 1, 1),
+    _mlp(51200, 384, 1, 1), _mlp(20037, 384, 0, 2), _mlp(300, 384, 0, 0),
+    _mlp(51200, 384, 1, 1, "MLP384_R3"), _mlp(20037, 384, 0, 2, "MLP384_R3"), _mlp(129, 384, 1, 1),
+    _mlp(51200, 384, 1, 1, "MLP384_SOLO"), _mlp(20037, 384, 0, 2, "MLP384_SOLO"), _mlp(300, 384, 0, 0, "MLP384_SOLO"), _mlp(129, 384, 1, 1, "MLP384_SOLO"),
+    _mlp(65541, 96, 0, 2, "MLP96_RESIDENT"), _mlp(4096, 96, 0, 0, "MLP96_RESIDENT"), _mlp(129, 96, 0, 1, "MLP96_RESIDENT"),   # C = 96 on the LDS-resident kernel
+    _mlp(100003, 96, 0, 1, "MLP96_RESIDENT"), _mlp(31, 96, 0, 2, "MLP96_RESIDENT"),
+    _mlp(4096, 96, 0, 0), _mlp(129, 96, 0, 1)])
+def test_projmlp_bx_whole_matrix(M, C, mod, out_mode, kernel):
     """proj + residual + LayerNorm-2 + fc1 + GELU + fc2 + residual [+ modulate] [+ LayerNorm | copy] in one kernel against fp64 on the
     bf16-rounded operands: x1 = x + att Wp^T + bp stays in the accumulators (fp32), its LayerNorm is rounded to bf16 as fc1's operand,
     the hidden activations are rounded to bf16 between the two products"""
@@ -228,11 +248,10 @@ def test_projmlp_bx_whole_matrix(M, C, mod, out_mode):
     aff = (torch.randn(2 * C, device="cuda", generator=gen) * 0.5) if mod else None
     x_io = x.clone()
     out_xn = torch.full((M, C), float("nan"), device="cuda")
-    # (C = 384: out_mode + 32 selects round 3's eight-wave kernel instead of the LDS-DMA one)
+    # (C = 384: MLP384_R3 selects round 3's eight-wave kernel instead of the LDS-DMA one)
     rc = lib.dsg_debug_projmlp_bx(M, C, _p(att), _p(x_io), _p(Wp), _p(bp), _p(W1), _p(b1), _p(W2), _p(b2), _p(aff), out_mode,
-                                  _p(out_xn) if out_mode else None, 0, None, None)
+                                  _p(out_xn) if out_mode else None, getattr(L, "BXK_" + kernel), 0, None, None)
     assert rc == 0
-    out_mode &= 15
     x1 = x.double() + _bf(att).double() @ _bf(Wp).double().t() + bp.double()
     xn = _bf(torch.nn.functional.layer_norm(x1, (C,), eps=1e-5).float()).double()
     hid = torch.nn.functional.gelu(xn @ _bf(W1).double().t() + b1.double())

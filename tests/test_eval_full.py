@@ -156,7 +156,7 @@ def test_sgstat_symbols_declared_exported_and_loadable():
     L = lib.load()
     for name in SGSTAT_SYMBOLS:
         assert hasattr(L, name)
-    assert L.dsg_abi_version() == 4
+    assert L.dsg_abi_version() == lib.ABI_VERSION
 
 
 def test_sgstat_entries_refuse_bad_arguments():

@@ -37,4 +37,4 @@ def test_headline_launches():
     assert lib.dsg_debug_gemm_form(513, 384, 256) == 1
     assert lib.dsg_debug_gemm_form(528, 384, 256) == 1
     assert lib.dsg_debug_gemm_form(512, 1536, 256) == 1
-    assert "dsg_debug_gemm_form" in L.EXPORTS
+    assert "dsg_debug_gemm_form" in L.DEBUG_EXPORTS

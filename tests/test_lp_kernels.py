@@ -240,7 +240,7 @@ def _values():
 
 def test_convert_round_to_nearest_even_bits():
     """f32_to_bf16_kernel: ties to even in both directions, +-0, denormals, the largest finite values (to inf), +-inf, a random million;
-    the quiet NaN stays 0x7fc0 (other payloads are not special-cased: include/dsg.h)"""
+    the quiet NaN stays 0x7fc0 (other payloads are not special-cased: include/dsg_debug.h)"""
     from diffusesg_amd import lib as L
     x = np.concatenate([_values(), np.array([NAN32], np.uint32).view(np.float32)])
     got = _convert(L.CONVERT_BF16, torch.from_numpy(x).cuda(), x.size, torch.bfloat16).view(torch.int16).cpu().numpy().view(np.uint16)

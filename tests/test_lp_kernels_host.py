@@ -72,7 +72,7 @@ def test_binding_struct_matches_header_layout():
     from diffusesg_amd import lib
     assert C.sizeof(lib.DsgGemmLpArgs) == 14 * 8 + 20 * 4      # dsg_gemm_lp_args: fourteen pointers, twenty int32
     assert lib.DsgGemmLpArgs.tile_used.offset == 13 * 8 and lib.DsgGemmLpArgs.lda.offset == 14 * 8 and lib.DsgGemmLpArgs.c_bf16.offset == 14 * 8 + 19 * 4
-    assert {"dsg_debug_gemm_lp", "dsg_debug_convert"} <= set(lib.EXPORTS)
+    assert {"dsg_debug_gemm_lp", "dsg_debug_convert"} <= set(lib.DEBUG_EXPORTS)
 
 
 def test_every_mistake_has_its_cases():

@@ -122,7 +122,7 @@ def test_structs_solver_codes_and_exports():
     assert scfg(8, "heun", 40.0).heun == 1 and scfg(8, "euler", 0.0).heun == 0 and scfg(8, "dpmpp_2m", 0.0).heun == 2
     assert lib.SOLVERS == {"euler": 0, "heun": 1, "dpmpp_2m": 2}
     assert "dsg_multistep_coef" in lib.EXPORTS
-    assert lib.load().dsg_abi_version() == 4
+    assert lib.load().dsg_abi_version() == lib.ABI_VERSION
     # the schedule and the walk do not depend on the solver code
     for f in (lambda c: lib.sigma_schedule(c), lambda c: lib.walk_steps(c, walk(0, (2, 3)))):
         for a, b in zip(f(scfg(8, "euler", 0.0)), f(scfg(8, "dpmpp_2m", 0.0))):

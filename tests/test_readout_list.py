@@ -1,4 +1,4 @@
-"""The list form of the fused read-out (include/dsg.h: dsg_debug_readout_tiles): wherever the masked-token pruning
+"""The list form of the fused read-out (include/dsg_debug.h: dsg_debug_readout_tiles): wherever the masked-token pruning
 runs, it computes the 32-token tiles that hold a valid pair from a device-side list, packed four to a block at the front of its grid, and every wave writes the exact zeros of its own positional tile
 where that tile holds none.  Tile t is tokens [32 t, 32 t + 32) of the flattened [B * N * N] index; it is listed iff one of its tokens
 (b, i, j) has flag_i and flag_j.  Nothing in a tile's arithmetic or in the pooling slots changes, so everything here is torch.equal,

@@ -126,7 +126,7 @@ def test_structs_and_exports():
     import ctypes as C
     assert C.sizeof(lib.DsgWalkCfg) == 32
     assert "dsg_sample_walk" in lib.EXPORTS and "dsg_walk_steps" in lib.EXPORTS
-    assert lib.load().dsg_abi_version() == 4
+    assert lib.load().dsg_abi_version() == lib.ABI_VERSION
 
 
 class StubSampler:

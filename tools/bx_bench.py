@@ -35,7 +35,7 @@ def gemm(tag, M, N, K, act=0, res=0, mod=0, ln=0, c32=0, cb=1, c2=0):
           f"{by / ms.value / 1e9:6.2f} TB/s", flush=True)
 
 
-def mlp(tag, M, Cc, mod=1, out_mode=1):
+def mlp(tag, M, Cc, mod=1, out_mode=1, kernel=L.BXK_DEFAULT):
     g = torch.Generator(device="cuda").manual_seed(3)
     xn = torch.randn(M, Cc, device="cuda", generator=g)
     x = torch.randn(M, Cc, device="cuda", generator=g)
@@ -46,7 +46,7 @@ def mlp(tag, M, Cc, mod=1, out_mode=1):
     aff = torch.randn(2 * Cc, device="cuda", generator=g) * 0.1 if mod else None
     o = torch.empty(M, Cc, device="cuda")
     ms = C.c_float(0)
-    rc = lib.dsg_debug_mlp_bx(M, Cc, p(xn), p(x), p(W1), p(b1), p(W2), p(b2), p(aff), out_mode, p(o), ITERS, C.byref(ms), None)
+    rc = lib.dsg_debug_mlp_bx(M, Cc, p(xn), p(x), p(W1), p(b1), p(W2), p(b2), p(aff), out_mode, p(o), kernel, ITERS, C.byref(ms), None)
     assert rc == 0, rc
     fl = 16.0 * M * Cc * Cc
     by = M * Cc * (2 + 4 + 4 + 2)
@@ -54,7 +54,7 @@ def mlp(tag, M, Cc, mod=1, out_mode=1):
           f"{by / ms.value / 1e9:6.2f} TB/s", flush=True)
 
 
-def projmlp(tag, M, Cc, mod=1, out_mode=1):
+def projmlp(tag, M, Cc, mod=1, out_mode=1, kernel=L.BXK_DEFAULT):
     g = torch.Generator(device="cuda").manual_seed(3)
     att = torch.randn(M, Cc, device="cuda", generator=g)
     x = torch.randn(M, Cc, device="cuda", generator=g)
@@ -67,7 +67,7 @@ def projmlp(tag, M, Cc, mod=1, out_mode=1):
     aff = torch.randn(2 * Cc, device="cuda", generator=g) * 0.1 if mod else None
     o = torch.empty(M, Cc, device="cuda")
     ms = C.c_float(0)
-    rc = lib.dsg_debug_projmlp_bx(M, Cc, p(att), p(x), p(Wp), p(bp), p(W1), p(b1), p(W2), p(b2), p(aff), out_mode, p(o), ITERS, C.byref(ms), None)
+    rc = lib.dsg_debug_projmlp_bx(M, Cc, p(att), p(x), p(Wp), p(bp), p(W1), p(b1), p(W2), p(b2), p(aff), out_mode, p(o), kernel, ITERS, C.byref(ms), None)
     assert rc == 0, rc
     fl = 18.0 * M * Cc * Cc
     by = M * Cc * (2 + 4 + 4 + 2)
@@ -94,11 +94,11 @@ def attn(tag, B, res, ws, shift, heads):
           f"{by / ms.value / 1e9:6.2f} TB/s", flush=True)
 
 
-def qkv_attn(tag, B, res, ws, shift, heads):
+def qkv_attn(tag, B, res, ws, shift, heads, kernel=L.BXK_DEFAULT):
     g = torch.Generator(device="cuda").manual_seed(4)
     Cc, T = 32 * heads, res * res
     Wp = (ws * ws + 31) // 32 * 32
-    nWt = (res // ws) ** 2 if shift % 1000 else 1
+    nWt = (res // ws) ** 2 if shift else 1
     xn = torch.randn(B * T, Cc, device="cuda", generator=g)
     W = torch.randn(3 * Cc, Cc, device="cuda", generator=g) / Cc ** 0.5
     W[:Cc] *= 0.25
@@ -107,7 +107,7 @@ def qkv_attn(tag, B, res, ws, shift, heads):
     bias[:, :, ws * ws:, :] = -1e30
     out = torch.empty(B * T, Cc, device="cuda")
     ms = C.c_float(0)
-    rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift, heads, p(xn), p(W), p(bq), p(bias), p(out), ITERS, C.byref(ms), None)
+    rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift, heads, p(xn), p(W), p(bq), p(bias), p(out), kernel, ITERS, C.byref(ms), None)
     assert rc == 0, rc
     fl = 4.0 * B * T * ws * ws * Cc + 6.0 * B * T * Cc * Cc
     by = B * T * 2 * Cc * 2
@@ -124,21 +124,21 @@ if __name__ == "__main__":
         projmlp("L2 proj + MLP (mod, LN), LDS-DMA", M2, 384)
         sys.exit(0)
     if only == "mlp384s":  # the one-wave-per-SIMD LDS-DMA kernel alone
-        projmlp("L2 proj + MLP (mod, LN), 4 waves solo", M2, 384, out_mode=1 + 64)
+        projmlp("L2 proj + MLP (mod, LN), 4 waves solo", M2, 384, kernel=L.BXK_MLP384_SOLO)
         sys.exit(0)
     if only == "mlpb":  # the level-0 / level-1 fused (proj +) MLP kernels alone (tools/mlpb_exp.sh)
         projmlp("L1 proj + MLP fused (mod, LN)", M1, 192)
         projmlp("L1 proj + MLP fused (copy)", M1, 192, mod=0, out_mode=2)
         projmlp("L0 proj + MLP fused (copy)", M0, 96, mod=0, out_mode=2)
-        projmlp("L0 proj + MLP fused (copy), LDS-resident", M0, 96, mod=0, out_mode=2 + 128)
+        projmlp("L0 proj + MLP fused (copy), LDS-resident", M0, 96, mod=0, out_mode=2, kernel=L.BXK_MLP96_RESIDENT)
         sys.exit(0)
     if only == "mlp":   # the fused MLP kernels alone
         mlp("L2 fused MLP (mod, LN), 8 waves LDS-DMA", M2, 384)
-        mlp("L2 fused MLP (mod, LN), 8 waves round 3", M2, 384, out_mode=1 + 32)
-        mlp("L2 fused MLP (mod, LN), 4 waves solo", M2, 384, out_mode=1 + 64)
+        mlp("L2 fused MLP (mod, LN), 8 waves round 3", M2, 384, kernel=L.BXK_MLP384_R3)
+        mlp("L2 fused MLP (mod, LN), 4 waves solo", M2, 384, kernel=L.BXK_MLP384_SOLO)
         projmlp("L2 proj + MLP (mod, LN), LDS-DMA", M2, 384)
-        projmlp("L2 proj + MLP (mod, LN), round 3", M2, 384, out_mode=1 + 32)
-        projmlp("L2 proj + MLP (mod, LN), 4 waves solo", M2, 384, out_mode=1 + 64)
+        projmlp("L2 proj + MLP (mod, LN), round 3", M2, 384, kernel=L.BXK_MLP384_R3)
+        projmlp("L2 proj + MLP (mod, LN), 4 waves solo", M2, 384, kernel=L.BXK_MLP384_SOLO)
         projmlp("L1 proj + MLP fused (mod, LN)", M1, 192)
         projmlp("L0 proj + MLP fused (copy)", M0, 96, mod=0, out_mode=2)
         sys.exit(0)
@@ -152,10 +152,10 @@ if __name__ == "__main__":
         qkv_attn("L1 qkv + attn fused", B, 20, 10, 0, 6)
         qkv_attn("L1 qkv + attn fused, shifted", B, 20, 10, 5, 6)
         qkv_attn("L0 qkv + attn fused", B, 40, 10, 0, 3)
-        qkv_attn("L2 qkv + attn, block per head", B, 10, 10, 1000, 12)
-        qkv_attn("L1 qkv + attn, block per head", B, 20, 10, 1000, 6)
-        qkv_attn("L1 qkv + attn, block per head, shifted", B, 20, 10, 1005, 6)
-        qkv_attn("L0 qkv + attn, block per head", B, 40, 10, 1000, 3)
+        qkv_attn("L2 qkv + attn, block per head", B, 10, 10, 0, 12, L.BXK_QA10_HEAD)
+        qkv_attn("L1 qkv + attn, block per head", B, 20, 10, 0, 6, L.BXK_QA10_HEAD)
+        qkv_attn("L1 qkv + attn, block per head, shifted", B, 20, 10, 5, 6, L.BXK_QA10_HEAD)
+        qkv_attn("L0 qkv + attn, block per head", B, 40, 10, 0, 3, L.BXK_QA10_HEAD)
         sys.exit(0)
     gemm("L2 qkv", M2, 1152, 384)
     gemm("L2 proj (res, LN)", M2, 384, 384, res=1, ln=1)
@@ -173,7 +173,7 @@ if __name__ == "__main__":
     gemm("pre_linear L2->L1 (fp32 out)", M2, 768, 768, c32=1, cb=0)
     gemm("post_linear L1 (mod, LN)", M1, 192, 192, c32=1, mod=1, ln=1)
     mlp("L2 fused MLP (mod, LN), 8 waves", M2, 384)
-    mlp("L2 fused MLP (mod, LN), 4 waves", M2, 384, out_mode=1 + 16)
+    mlp("L2 fused MLP (mod, LN), 4 waves", M2, 384, kernel=L.BXK_MLP384_WAVE)
     mlp("L1 fused MLP (mod, LN)", M1, 192)
     mlp("L0 fused MLP (copy)", M0, 96, mod=0, out_mode=2)
     projmlp("L2 proj + MLP fused (mod, LN)", M2, 384)

@@ -19,7 +19,7 @@ bqkv = torch.randn(3 * Cc, device="cuda", generator=gen) * 0.2
 bias = torch.randn(nWt, heads, Wp, Wp, device="cuda", generator=gen) * float(os.environ.get("QA_BIAS", "1.5"))
 bias[:, :, Wt:, :] = -1.0e30
 out = torch.full((B * T, Cc), float("nan"), device="cuda")
-rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift, heads, _p(xn), _p(W), _p(bqkv), _p(bias.contiguous()), _p(out), 0, None, None)
+rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift, heads, _p(xn), _p(W), _p(bqkv), _p(bias.contiguous()), _p(out), L.BXK_DEFAULT, 0, None, None)
 assert rc == 0
 qkv = _bf((_bf(xn).double() @ _bf(W).double().t() + bqkv.double()).float())
 tok = torch.from_numpy(_window_tokens(res, ws, shift)).cuda()
@@ -51,7 +51,7 @@ for qq in range(Wt):
     bias2[:, :, (qq + 7) % Wt, qq] = 60.0
 bias2[:, :, Wt:, :] = -1.0e30
 out2 = torch.full((B * T, Cc), float("nan"), device="cuda")
-rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift, heads, _p(xn), _p(W), _p(bqkv), _p(bias2.contiguous()), _p(out2), 0, None, None)
+rc = lib.dsg_debug_qkv_attn_bx(B, res, ws, shift, heads, _p(xn), _p(W), _p(bqkv), _p(bias2.contiguous()), _p(out2), L.BXK_DEFAULT, 0, None, None)
 got2 = out2.double().view(B, T, heads, 32)[:, tok].permute(0, 1, 3, 2, 4)[0, 0, 0]    # [Wt, 32]
 v0 = v[0, 0, 0]                                                                       # [Wt, 32]
 d2 = (got2[:, None, :] - v0[None, :, :]).abs().max(dim=2).values                       # [query, key]
