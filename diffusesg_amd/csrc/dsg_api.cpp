@@ -136,6 +136,7 @@ struct Workspace {
     // option "dedup_qkv": did the last forward launch the level's second block in its switched form (the fused launch plus the projection
     // over qk_runs and the map attention, the device picking one by qk_split_rule)?  dsg_debug_dedup_qkv_lists
     bool qk_fwd[1 + NEED_MAX_DD_UP] = {false, false, false, false};
+    int patch_fwd[2] = {-1, -1};   // the form PatchEmbed / the read-out took in the last forward (1 fused kernel, 0 chain; -1: none yet).  dsg_debug_patch_forms
     int ro_fwd = -1;   // the form the last forward's fused read-out took (1 list, 0 positional; -1: none yet).  dsg_debug_readout_tiles
     // what stage_flags last wrote (dedup_stage_mode below): the DedupMode of the lists, the levels whose fill is trimmed (bit k) and the
     // chain depth the trimming was worked out for -- forward_fixed checks that it reaches exactly that depth
@@ -178,6 +179,9 @@ struct Options {
 struct dsg_handle_s {
     dsg_config cfg;
     int N, Ca, Cn, E, L, Cin, Kp;
+    // patch_size (dsg_create_patch) and the level-0 token resolution R0 = N / P: N is the side of the STATE (flags, adjacency, node rows,
+    // the read-out's pixel rows), R0 >> l the side of level l's token grid.  P == 1: R0 == N.  Kp pads P * P * Cin
+    int P = 1, R0 = 0;
     std::vector<WSpec> specs;
     std::map<std::string, DevTensor> w;
     bool finalized = false;
@@ -198,6 +202,11 @@ struct dsg_handle_s {
     float *ro0_w = nullptr;     // read_out.0 transposed to [out,in]
     // folded read-out (E = 96): Fa = F1.W2.W1.W0^T packed fragment-major, fa; F2 padded+packed; node: Gext [E,128]
     float *ro_fap = nullptr, *ro_fa = nullptr, *ro_f2p = nullptr, *ro_gext = nullptr;
+    // patch_size 2 (E = 96): pe_wp / ro_fap hold the four sub-pixels' fragment packs (launch_fused_patch_embed96_p2 / _readout96_p2), pe_kps the
+    // per-sub-pixel K (in_chans rounded up to 32); ro_gext2[a] [E, 256]: the node fc1 weight of node rows of parity a over pool_ext's columns
+    // (G1 F[a, 0] | G1 F[a, 1] | G1 c | G1 c | 0 ..)
+    float *ro_gext2[2] = {nullptr, nullptr};
+    int pe_kps = 0;
     float *ro_fapb = nullptr, *ro_f2pb = nullptr;   // the same two matrices in the bf16 MFMA's fragment order (fp32 here; their bf16 copies are what runs)
     float *ro0_wf = nullptr, *ro0_bf = nullptr;  // read_out.0 ([out,in]) with the final norm's gamma/beta folded in
     float *merge_wf[DSG_MAX_LAYERS] = {}, *merge_bf[DSG_MAX_LAYERS] = {};   // PatchMerging reduction with its LayerNorm(4C) folded in
@@ -330,12 +339,13 @@ void drop_graphs(dsg_handle h) {
     }
 }
 
-int level_window(const dsg_config &c, int lvl) {
-    const int r = c.max_node_num >> lvl;
+// (r0: the level-0 token resolution, max_node_num / patch_size)
+int level_window(const dsg_config &c, int r0, int lvl) {
+    const int r = r0 >> lvl;
     return r <= c.window_size ? r : c.window_size;
 }
-int block_shift(const dsg_config &c, int lvl, int j) {
-    const int r = c.max_node_num >> lvl;
+int block_shift(const dsg_config &c, int r0, int lvl, int j) {
+    const int r = r0 >> lvl;
     if (r <= c.window_size) return 0;
     return (j % 2 == 0) ? 0 : c.window_size / 2;
 }
@@ -371,15 +381,15 @@ void build_specs(dsg_handle h) {
     auto &s = h->specs;
     s.push_back({"patch_embed.affine.weight", {2 * E, NOISE_EMB}});
     s.push_back({"patch_embed.affine.bias", {2 * E}});
-    s.push_back({"patch_embed.proj.weight", {E, h->Cin, 1, 1}});
+    s.push_back({"patch_embed.proj.weight", {E, h->Cin, h->P, h->P}});
     s.push_back({"patch_embed.proj.bias", {E}});
     s.push_back({"patch_embed.norm.weight", {E}});
     s.push_back({"patch_embed.norm.bias", {E}});
     for (int l = 0; l < L; l++) {
-        const int C = E << l, res = c.max_node_num >> l, ws = level_window(c, l);
+        const int C = E << l, res = h->R0 >> l, ws = level_window(c, h->R0, l);
         for (int j = 0; j < c.depths[l]; j++)
             add_block_specs(s, "down_layers." + std::to_string(l) + ".blocks." + std::to_string(j), C, c.num_heads[l], ws, res,
-                            block_shift(c, l, j), mr);
+                            block_shift(c, h->R0, l, j), mr);
         if (l < L - 1) {
             const std::string p = "down_layers." + std::to_string(l) + ".downsample";
             s.push_back({p + ".reduction.weight", {2 * C, 4 * C}});
@@ -389,7 +399,7 @@ void build_specs(dsg_handle h) {
     }
     for (int i = 0; i < L; i++) {
         const int l = L - 1 - i;
-        const int C = E << l, res = c.max_node_num >> l, ws = level_window(c, l);
+        const int C = E << l, res = h->R0 >> l, ws = level_window(c, h->R0, l);
         if (i > 0) {
             const int D = 4 * C;
             const std::string p = "up_layers." + std::to_string(i) + ".upsample";
@@ -402,10 +412,11 @@ void build_specs(dsg_handle h) {
         }
         for (int j = 0; j < c.depths[l]; j++)
             add_block_specs(s, "up_layers." + std::to_string(i) + ".blocks." + std::to_string(j), C, c.num_heads[l], ws, res,
-                            block_shift(c, l, j), mr);
+                            block_shift(c, h->R0, l, j), mr);
     }
     for (int k = 0; k < 3; k++) {
-        s.push_back({"read_out." + std::to_string(k) + ".weight", {E, E, 1, 1}});
+        const int ps = k == 0 ? h->P : 1;   // read_out.0 is the ConvTranspose2d(E, E, p, p)
+        s.push_back({"read_out." + std::to_string(k) + ".weight", {E, E, ps, ps}});
         s.push_back({"read_out." + std::to_string(k) + ".bias", {E}});
     }
     s.push_back({"map_layer0.weight", {NOISE_EMB, E}});
@@ -778,7 +789,9 @@ static thread_local std::string g_create_err;
 // (train_kernels.hip keeps it per hipStream_t and it only grows; a destroyed stream's address may be reused by a later stream)
 static std::atomic<int> g_live_handles{0};
 
-int dsg_create(const dsg_config *cfg, dsg_handle *out) {
+int dsg_create(const dsg_config *cfg, dsg_handle *out) { return dsg_create_patch(cfg, 1, out); }
+
+int dsg_create_patch(const dsg_config *cfg, int32_t patch_size, dsg_handle *out) {
     if (!cfg || !out) { g_create_err = "dsg_create: null argument"; return DSG_ERR_INVALID; }
     *out = nullptr;
     g_create_err.clear();
@@ -792,15 +805,24 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out) {
     if (h->E % 32 != 0 || h->E < 64) return bad("embed_dim must be a multiple of 32");
     if (cfg->mlp_ratio < 1 || h->N < 1 || h->Ca < 1 || h->Cn < 1) return bad("sizes");
     if (h->N % (1 << (h->L - 1)) != 0) return bad("max_node_num not divisible by 2^(L-1)");
+    if (patch_size != 1 && patch_size != 2 && patch_size != 4) return bad("patch_size must be 1, 2 or 4");
+    if (h->N % patch_size != 0) return bad("max_node_num not divisible by patch_size");
+    h->P = patch_size; h->R0 = h->N / patch_size;
+    if (h->P > 1) {
+        if (h->R0 % (1 << (h->L - 1)) != 0) return bad("patch_size: max_node_num / patch_size not divisible by 2^(L-1)");
+        // the reference's PatchBreakup asserts an even resolution on its input (diffusesg.py:381): the coarsest level's
+        if (h->L >= 2 && (h->R0 >> (h->L - 1)) % 2 != 0)
+            return bad("patch_size: the coarsest resolution (max_node_num / patch_size) >> (L-1) is odd, the reference's PatchBreakup refuses it");
+    }
     for (int l = 0; l < h->L; l++) {
-        const int C = h->E << l, res = h->N >> l, ws = level_window(*cfg, l);
+        const int C = h->E << l, res = h->R0 >> l, ws = level_window(*cfg, h->R0, l);
         if (cfg->num_heads[l] * 32 != C) return bad("head_dim must be 32");
         if (res % ws != 0) return bad("resolution not divisible by window");
         if (!(ws == 2 || ws == 4 || ws == 5 || ws == 8 || ws == 10)) return bad("window side must be one of 2, 4, 5, 8, 10");
         if (C > 1536 || (l < h->L - 1 && 4 * C > 1536)) return bad("row wider than 1536 channels");
     }
     h->Cin = (cfg->self_condition ? 2 : 1) * (h->Ca + 2 * h->Cn);
-    h->Kp = ((h->Cin + 31) / 32) * 32;
+    h->Kp = ((h->P * h->P * h->Cin + 31) / 32) * 32;
     build_specs(h);
     if (!gelu_table()) { delete h; return DSG_ERR_HIP; }
     for (const OptRow &r : g_options) {   // the default, or the environment's: read the row's way and normalised like dsg_set_option's values
@@ -877,8 +899,8 @@ int dsg_finalize_weights(dsg_handle h) {
     h->pe_aff_off = off; aff_prefixes.push_back("patch_embed"); off += 2 * E;
     auto mk = [&](const std::string &p, int l, int j) {
         BlockPlan b;
-        b.prefix = p; b.lvl = l; b.C = E << l; b.res = c.max_node_num >> l; b.ws = level_window(c, l);
-        b.shift = block_shift(c, l, j); b.heads = c.num_heads[l]; b.aff_off = off;
+        b.prefix = p; b.lvl = l; b.C = E << l; b.res = h->R0 >> l; b.ws = level_window(c, h->R0, l);
+        b.shift = block_shift(c, h->R0, l, j); b.heads = c.num_heads[l]; b.aff_off = off;
         aff_prefixes.push_back(p); off += 2 * b.C;
         return b;
     };
@@ -923,17 +945,19 @@ int dsg_finalize_weights(dsg_handle h) {
         if (int rc = fold_ln(h, WT(h, pm + ".reduction.weight"), nullptr, WT(h, pm + ".norm.weight"), WT(h, pm + ".norm.bias"), 2 * C, 4 * C,
                              &h->merge_wf[l], &h->merge_bf[l])) return rc;
     }
-    // patch_embed.proj [E,Cin,1,1] -> [E,Kp] zero padded
+    // patch_embed.proj [E,Cin,p,p] -> [E,Kp] zero padded, k = (a p + b) Cin + c: launch_assemble_patch's order (p = 1: k = c)
     {
-        std::vector<float> src((size_t)E * h->Cin), dst((size_t)E * h->Kp, 0.f);
+        const int P = h->P, PP = P * P;
+        std::vector<float> src((size_t)E * h->Cin * PP), dst((size_t)E * h->Kp, 0.f);
         HIP_TRY(h, hipMemcpy(src.data(), WT(h, "patch_embed.proj.weight"), sizeof(float) * src.size(), hipMemcpyDeviceToHost));
         for (int e = 0; e < E; e++)
-            for (int k = 0; k < h->Cin; k++) dst[(size_t)e * h->Kp + k] = src[(size_t)e * h->Cin + k];
+            for (int k = 0; k < h->Cin; k++)
+                for (int ab = 0; ab < PP; ab++) dst[(size_t)e * h->Kp + (size_t)ab * h->Cin + k] = src[((size_t)e * h->Cin + k) * PP + ab];
         if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * dst.size(), AC_CONST)) return rc;
         h->pe_w = (float *)p;
         HIP_TRY(h, hipMemcpy(h->pe_w, dst.data(), sizeof(float) * dst.size(), hipMemcpyHostToDevice));
         h->pe_wp = nullptr;
-        if (E == 96 && h->Kp <= 64) {
+        if (E == 96 && h->Kp <= 64 && P == 1) {   // (the fused kernel gathers one pixel per token)
             const int S = h->Kp / 8;
             std::vector<float> pk(dst.size());
             for (int nt = 0; nt < E / 32; nt++)
@@ -945,23 +969,53 @@ int dsg_finalize_weights(dsg_handle h) {
             h->pe_wp = (float *)p;
             HIP_TRY(h, hipMemcpy(h->pe_wp, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice));
         }
+        h->pe_kps = ((h->Cin + 31) / 32) * 32;
+        if (E == 96 && P == 2 && h->pe_kps <= 64) {   // the fused p = 2 kernel: one fragment pack per sub-pixel, each zero-padded to pe_kps
+            const int S = h->pe_kps / 8;
+            std::vector<float> pk((size_t)4 * E * h->pe_kps, 0.f);
+            for (int sub = 0; sub < 4; sub++)
+                for (int nt = 0; nt < E / 32; nt++)
+                    for (int sx = 0; sx < S; sx++)
+                        for (int lane = 0; lane < 64; lane++)
+                            for (int t = 0; t < 4; t++) {
+                                const int c = 8 * sx + 4 * (lane >> 5) + t;
+                                if (c < h->Cin)
+                                    pk[((((size_t)sub * 3 + nt) * S + sx) * 64 + lane) * 4 + t] = src[((size_t)(32 * nt + (lane & 31)) * h->Cin + c) * 4 + sub];
+                            }
+            if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * pk.size(), AC_CONST)) return rc;
+            h->pe_wp = (float *)p;
+            HIP_TRY(h, hipMemcpy(h->pe_wp, pk.data(), sizeof(float) * pk.size(), hipMemcpyHostToDevice));
+        }
     }
     // read_out.0 is a ConvTranspose2d: weight [in,out,1,1] (diffusesg.py:706) -> [out,in]
+    // patch_size p: [in,out,p,p] -> [p^2 out, in], row (a p + b) E + o, so that one GEMM writes the p^2 pixels of a token side by side:
+    // its [B R^2, p^2 E] result read as [B N^2, E] is r0 with rows in (token, a, b) order; the bias repeats per sub-pixel
     {
-        std::vector<float> src((size_t)E * E), dst((size_t)E * E);
+        const int PP = h->P * h->P;
+        std::vector<float> src((size_t)E * E * PP), dst((size_t)PP * E * E), b0(E), b0r((size_t)PP * E);
         HIP_TRY(h, hipMemcpy(src.data(), WT(h, "read_out.0.weight"), sizeof(float) * src.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(b0.data(), WT(h, "read_out.0.bias"), sizeof(float) * E, hipMemcpyDeviceToHost));
         for (int i = 0; i < E; i++)
-            for (int o = 0; o < E; o++) dst[(size_t)o * E + i] = src[(size_t)i * E + o];
+            for (int o = 0; o < E; o++)
+                for (int ab = 0; ab < PP; ab++) dst[((size_t)ab * E + o) * E + i] = src[((size_t)i * E + o) * PP + ab];
+        for (int ab = 0; ab < PP; ab++)
+            for (int o = 0; o < E; o++) b0r[(size_t)ab * E + o] = b0[o];
         if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * dst.size(), AC_CONST)) return rc;
         h->ro0_w = (float *)p;
         HIP_TRY(h, hipMemcpy(h->ro0_w, dst.data(), sizeof(float) * dst.size(), hipMemcpyHostToDevice));
-        if (int rc = fold_ln(h, h->ro0_w, WT(h, "read_out.0.bias"), WT(h, "norm.weight"), WT(h, "norm.bias"), E, E, &h->ro0_wf, &h->ro0_bf)) return rc;
+        const float *bias0 = WT(h, "read_out.0.bias");
+        if (PP > 1) {
+            if (int rc = owned_alloc(h, h->derived_allocs, &p, sizeof(float) * b0r.size(), AC_CONST)) return rc;
+            HIP_TRY(h, hipMemcpy(p, b0r.data(), sizeof(float) * b0r.size(), hipMemcpyHostToDevice));
+            bias0 = (const float *)p;
+        }
+        if (int rc = fold_ln(h, h->ro0_w, bias0, WT(h, "norm.weight"), WT(h, "norm.bias"), PP * E, E, &h->ro0_wf, &h->ro0_bf)) return rc;
     }
     // Folded read-out (E = 96, C_adj <= 32): final-LN output -> read_out.0/1/2 -> readout_adj_mlp.fc1 is affine up to the
     // GELU, and the node head's pooled shared_rep is an affine image of the pooled LN output.  Fold in double precision.
     h->ro_fap = h->ro_fa = h->ro_f2p = h->ro_gext = nullptr;
     h->ro_fapb = h->ro_f2pb = nullptr;
-    if (E == 96 && h->Ca <= 32) {
+    if (E == 96 && h->Ca <= 32 && h->P == 1) {   // (patch_size > 1 runs the chain: DESIGN.md §15)
         auto dl = [&](const char *k, size_t n) { std::vector<float> v(n); (void)hipMemcpy(v.data(), WT(h, k), sizeof(float) * n, hipMemcpyDeviceToHost); return v; };
         const std::vector<float> r0 = dl("read_out.0.weight", (size_t)E * E), r1 = dl("read_out.1.weight", (size_t)E * E),
                                  r2 = dl("read_out.2.weight", (size_t)E * E), b0 = dl("read_out.0.bias", E), b1 = dl("read_out.1.bias", E),
@@ -1032,6 +1086,66 @@ int dsg_finalize_weights(dsg_handle h) {
         if (int rc = up(fapb, &h->ro_fapb)) return rc;
         if (int rc = up(f2pb, &h->ro_f2pb)) return rc;
     }
+    // The same fold at patch_size 2: A = W2 W1, Fa[a, b] = F1 A W0[:, :, a, b]^T per sub-pixel, the constant c = A b0 + W2 b1 + b2
+    // (fa = F1 c + f1 is the same for the four), and for the node head G1 A W0[:, :, a, b]^T over the pooled LN(x) of column parity b
+    h->ro_gext2[0] = h->ro_gext2[1] = nullptr;
+    if (E == 96 && h->Ca <= 32 && h->P == 2) {
+        auto dl = [&](const char *k, size_t n) { std::vector<float> v(n); (void)hipMemcpy(v.data(), WT(h, k), sizeof(float) * n, hipMemcpyDeviceToHost); return v; };
+        const std::vector<float> r0 = dl("read_out.0.weight", (size_t)E * E * 4), r1 = dl("read_out.1.weight", (size_t)E * E),
+                                 r2 = dl("read_out.2.weight", (size_t)E * E), b0 = dl("read_out.0.bias", E), b1 = dl("read_out.1.bias", E),
+                                 b2 = dl("read_out.2.bias", E), F1 = dl("readout_adj_mlp.fc1.weight", (size_t)E * E),
+                                 f1 = dl("readout_adj_mlp.fc1.bias", E), F2 = dl("readout_adj_mlp.fc2.weight", (size_t)h->Ca * E),
+                                 G1 = dl("readout_node_mlp.fc1.weight", (size_t)E * E);
+        typedef std::vector<double> dv;
+        auto matmul = [&](const dv &X, const dv &Y) { dv Z((size_t)E * E, 0.0); for (int i = 0; i < E; i++) for (int k = 0; k < E; k++) { const double a = X[(size_t)i * E + k]; for (int j = 0; j < E; j++) Z[(size_t)i * E + j] += a * Y[(size_t)k * E + j]; } return Z; };
+        auto matvec = [&](const dv &X, const dv &v) { dv z(E, 0.0); for (int i = 0; i < E; i++) for (int k = 0; k < E; k++) z[i] += X[(size_t)i * E + k] * v[k]; return z; };
+        const dv W1(r1.begin(), r1.end()), W2(r2.begin(), r2.end()), dF1(F1.begin(), F1.end()), dG1(G1.begin(), G1.end());
+        const dv A = matmul(W2, W1);
+        dv t1 = matvec(W1, dv(b0.begin(), b0.end()));
+        for (int i = 0; i < E; i++) t1[i] += b1[i];
+        dv cc = matvec(W2, t1);
+        for (int i = 0; i < E; i++) cc[i] += b2[i];
+        dv fa = matvec(dF1, cc);
+        for (int i = 0; i < E; i++) fa[i] += f1[i];
+        const dv ga = matvec(dG1, cc);
+        const int S = E / 8;
+        std::vector<float> fap((size_t)4 * E * E), f2p((size_t)3 * 4 * 64 * 4, 0.f), faf(E), gx[2] = {std::vector<float>((size_t)E * 256, 0.f), std::vector<float>((size_t)E * 256, 0.f)};
+        for (int sub = 0; sub < 4; sub++) {
+            dv W0t((size_t)E * E);
+            for (int i = 0; i < E; i++) for (int o = 0; o < E; o++) W0t[(size_t)o * E + i] = r0[((size_t)i * E + o) * 4 + sub];   // ConvTranspose2d [in,out,a,b]
+            const dv Aab = matmul(A, W0t), Fa = matmul(dF1, Aab), Gn = matmul(dG1, Aab);
+            for (int nt = 0; nt < 3; nt++)
+                for (int sx = 0; sx < S; sx++)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int t = 0; t < 4; t++)
+                            fap[((((size_t)sub * 3 + nt) * S + sx) * 64 + lane) * 4 + t] = (float)Fa[(size_t)(32 * nt + (lane & 31)) * E + 8 * sx + 4 * (lane >> 5) + t];
+            for (int i = 0; i < E; i++)
+                for (int k = 0; k < E; k++) gx[sub >> 1][(size_t)i * 256 + 96 * (sub & 1) + k] = (float)Gn[(size_t)i * E + k];
+        }
+        for (int nt = 0; nt < 3; nt++)
+            for (int g = 0; g < 4; g++)
+                for (int lane = 0; lane < 64; lane++)
+                    for (int t = 0; t < 4; t++) {
+                        const int c = lane & 31;
+                        f2p[(((size_t)nt * 4 + g) * 64 + lane) * 4 + t] = c < h->Ca ? F2[(size_t)c * E + 32 * nt + 8 * g + 4 * (lane >> 5) + t] : 0.f;
+                    }
+        for (int i = 0; i < E; i++) {
+            faf[i] = (float)fa[i];
+            for (int a = 0; a < 2; a++) gx[a][(size_t)i * 256 + 192] = gx[a][(size_t)i * 256 + 193] = (float)ga[i];
+        }
+        auto up = [&](const std::vector<float> &v, float **dst) -> int {
+            void *q;
+            if (int rc = owned_alloc(h, h->derived_allocs, &q, sizeof(float) * v.size(), AC_CONST)) return rc;
+            *dst = (float *)q;
+            HIP_TRY(h, hipMemcpy(q, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice));
+            return 0;
+        };
+        if (int rc = up(fap, &h->ro_fap)) return rc;
+        if (int rc = up(faf, &h->ro_fa)) return rc;
+        if (int rc = up(f2p, &h->ro_f2p)) return rc;
+        if (int rc = up(gx[0], &h->ro_gext2[0])) return rc;
+        if (int rc = up(gx[1], &h->ro_gext2[1])) return rc;
+    }
     drop_graphs(h);   // captured graphs bake weight pointers
     // bf16 copies (opt-in mode): drop stale ones, list every GEMM weight, rebuild if the mode is on
     for (auto &kv : h->w_bf16) owned_free(h->allocs, kv.second);
@@ -1058,7 +1172,7 @@ int dsg_finalize_weights(dsg_handle h) {
     for (int l = 0; l + 1 < L; l++) h->gemm_weights.push_back({h->merge_wf[l], (size_t)8 * (E << l) * (E << l)});
     h->gemm_weights.push_back({h->aff_w, (size_t)h->aff_n * NOISE_EMB});
     h->gemm_weights.push_back({h->pe_w, (size_t)E * h->Kp});
-    h->gemm_weights.push_back({h->ro0_wf, (size_t)E * E});
+    h->gemm_weights.push_back({h->ro0_wf, (size_t)h->P * h->P * E * E});
     if (h->ro_gext) h->gemm_weights.push_back({h->ro_gext, (size_t)E * 128});
     if (h->ro_fapb) h->gemm_weights.push_back({h->ro_fapb, (size_t)3 * 6 * 64 * 8});
     if (h->ro_f2pb) h->gemm_weights.push_back({h->ro_f2pb, (size_t)3 * 2 * 64 * 8});
@@ -1073,19 +1187,23 @@ int dsg_finalize_weights(dsg_handle h) {
 
 namespace {
 
+// rows per sample of the activation buffers x / y / att: the level-0 tokens, or at patch_size > 1 the N^2 pixel rows of the read-out chain
+// (p^2 times as many; x and y trade names under the fused PatchMerging, so all three have the size)
+size_t act_rows(dsg_handle h) { return h->P > 1 ? (size_t)h->N * h->N : (size_t)h->R0 * h->R0; }
+
 size_t per_sample_floats(dsg_handle h, std::vector<size_t> *parts = nullptr) {
-    const size_t T0 = (size_t)h->N * h->N, E = h->E;
+    const size_t T0 = (size_t)h->R0 * h->R0, E = h->E, TA = act_rows(h);
     const size_t sa = (size_t)h->Ca * h->N * h->N, sn = (size_t)h->N * h->Cn;
     std::vector<size_t> v = {
         sa, sn, sa, sn, sa, sn,                  // in, sc, f
         (size_t)E, NOISE_EMB, NOISE_EMB, (size_t)h->aff_n,   // pe, emb0, emb, aff
         T0 * h->Kp,                              // tok_in
-        T0 * E, T0 * E, T0 * E / 2,              // x, y, xn (bf16)
-        3 * T0 * E, T0 * E,                      // qkv, att
+        TA * E, TA * E, T0 * E / 2,              // x, y, xn (bf16)
+        3 * T0 * E, TA * E,                      // qkv, att
         (size_t)h->cfg.mlp_ratio * T0 * E,       // hid
         2 * T0,                                  // stats
         (size_t)h->N * E, (size_t)h->N * E,      // pool, hn
-        (size_t)h->N * 128, (size_t)h->N * readout_pool_segments(h->N) * 96,   // pool_ext, pool_part
+        (size_t)h->N * (h->P == 2 ? 256 : 128), (size_t)h->N * readout_pool_segments(h->N) * 96,   // pool_ext (p = 2: two parities), pool_part
         sa, sn, sa, sn, 3 * sa, 3 * sn,          // sampler x, xhat, d[3]
     };
     size_t tot = 0;
@@ -1102,7 +1220,7 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
     if (it != h->ws.end()) { *out = it->second.get(); return validate_plan(h, *out); }
     auto w = std::make_unique<Workspace>();
     w->B = B;
-    const size_t T0 = (size_t)h->N * h->N, E = h->E;
+    const size_t T0 = (size_t)h->R0 * h->R0, E = h->E, TA = act_rows(h);
     const size_t sa = (size_t)B * h->Ca * h->N * h->N, sn = (size_t)B * h->N * h->Cn;
     auto A = [&](float **p, size_t n, AllocClass cls) -> int {
         void *q;
@@ -1117,12 +1235,12 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
     ALLOC(w->pe, (size_t)B * E); ALLOC(w->emb0, (size_t)B * NOISE_EMB); ALLOC(w->emb, (size_t)B * NOISE_EMB);
     ALLOC(w->aff, (size_t)B * h->aff_n);
     ALLOC(w->tok_in, (size_t)B * T0 * h->Kp);
-    ALLOC_FINITE(w->x, (size_t)B * T0 * E); ALLOC_FINITE(w->y, (size_t)B * T0 * E);
+    ALLOC_FINITE(w->x, (size_t)B * TA * E); ALLOC_FINITE(w->y, (size_t)B * TA * E);
     { float *xn_; ALLOC(xn_, (size_t)B * T0 * E / 2 + 64); w->xn = xn_; }
-    ALLOC(w->qkv, (size_t)B * 3 * T0 * E); ALLOC_FINITE(w->att, (size_t)B * T0 * E);
+    ALLOC(w->qkv, (size_t)B * 3 * T0 * E); ALLOC_FINITE(w->att, (size_t)B * TA * E);
     ALLOC_FINITE(w->hid, (size_t)B * h->cfg.mlp_ratio * T0 * E);
     ALLOC_FINITE(w->stats, (size_t)B * 2 * T0);
-    ALLOC(w->pool, (size_t)B * h->N * E); ALLOC(w->hn, (size_t)B * h->N * E); ALLOC(w->pool_ext, (size_t)B * h->N * 128);
+    ALLOC(w->pool, (size_t)B * h->N * E); ALLOC(w->hn, (size_t)B * h->N * E); ALLOC(w->pool_ext, (size_t)B * h->N * (h->P == 2 ? 256 : 128));
     ALLOC(w->pool_part, (size_t)B * h->N * readout_pool_segments(h->N) * 96);
     for (int l = 0; l < h->L; l++) ALLOC(w->skips[l], ((size_t)B * T0 * E) >> (l + 1 < h->L ? l + 1 : l));
     ALLOC(w->x_adj, sa); ALLOC(w->x_node, sn); ALLOC(w->xh_adj, sa); ALLOC(w->xh_node, sn);
@@ -1137,9 +1255,9 @@ int get_workspace(dsg_handle h, int B, Workspace **out) {
     if (int rc = owned_alloc(h, w->allocs, &q, sizeof(RunCtl), AC_STATE)) return rc;
     w->ctl = (RunCtl *)q;
     // masked-token pruning leaves the rows nobody reads untouched: they must never hold anything but finite numbers
-    HIP_TRY(h, hipMemset(w->x, 0, sizeof(float) * (size_t)B * T0 * E));
-    HIP_TRY(h, hipMemset(w->y, 0, sizeof(float) * (size_t)B * T0 * E));
-    HIP_TRY(h, hipMemset(w->att, 0, sizeof(float) * (size_t)B * T0 * E));
+    HIP_TRY(h, hipMemset(w->x, 0, sizeof(float) * (size_t)B * TA * E));
+    HIP_TRY(h, hipMemset(w->y, 0, sizeof(float) * (size_t)B * TA * E));
+    HIP_TRY(h, hipMemset(w->att, 0, sizeof(float) * (size_t)B * TA * E));
     HIP_TRY(h, hipMemset(w->hid, 0, sizeof(float) * (size_t)B * h->cfg.mlp_ratio * T0 * E));
     HIP_TRY(h, hipMemset(w->stats, 0, sizeof(float) * (size_t)B * 2 * T0));
     w->need = prune_plan(h).np;
@@ -1203,6 +1321,7 @@ void build_prune_plan(dsg_handle h) {
     const int L = h->L, N = h->N;
     for (int i = 0; i < DSG_MAX_LAYERS; i++) { P.fine[i] = P.coarse[i] = -1; }
     for (int i = 0; i < L; i++) { P.rows[i].assign(h->up[i].size(), -1); P.wins[i].assign(h->up[i].size(), -1); }
+    if (h->P != 1) return;   // the lists are derived from pixel flags at token resolution: no plan at patch_size > 1
     if (N % 8 != 0 || N * N / 8 > NEED_MAX_RUNS) return;
     for (int i = 0; i < L; i++)
         for (auto &b : h->up[i]) if (b.ws != 8 || b.res % 8 != 0) return;   // 10 x 10 windows (COCO): not covered
@@ -1270,7 +1389,7 @@ const PrunePlan &prune_plan(dsg_handle h) { if (!h->prune.built) build_prune_pla
 // Decided at plan time.  Off with debug taps (they return whole tensors: the same rule as rowstats_on), in the split / bf16 modes,
 // and whenever a launch of the up path is not one of the kernels that take a list.
 bool prune_opts_on(dsg_handle h) {
-    return h->opt.prune_masked && h->taps.empty() && !h->opt.gemm_split && !h->opt.gemm_bf16 && rowstats_on(h) && h->opt.fused_qkv_attn &&
+    return h->P == 1 && h->opt.prune_masked && h->taps.empty() && !h->opt.gemm_split && !h->opt.gemm_bf16 && rowstats_on(h) && h->opt.fused_qkv_attn &&
            h->opt.fused_readout && h->ro_fap && prune_plan(h).np.n_lists > 0;
 }
 bool prune_on(dsg_handle h, const Workspace *w) {
@@ -1281,7 +1400,7 @@ bool prune_on(dsg_handle h, const Workspace *w) {
 // (below ~8k merged rows the reduction GEMM is a single partial wave of tiles and the gather + LayerNorm FMA in its
 // long K loop costs more than the small merge_ln launch it replaces: measured 103 vs 81 + 13 us at M = 4096, K = 1536)
 bool merge_fused_at(dsg_handle h, int B, int l) {
-    const int C = h->E << l, res = h->N >> l;
+    const int C = h->E << l, res = h->R0 >> l;
     return l < h->L - 1 && h->opt.fused_merge != 0 && rowstats_on(h) && !h->opt.gemm_bf16 && C % 32 == 0 &&
            (B * res * res / 4 >= 8192 || h->opt.fused_merge > 1 || h->opt.batch_invariant);   // "batch_invariant": the size plays no part
 }
@@ -1324,7 +1443,7 @@ bool merge_fused_at(dsg_handle h, int B, int l) {
 // * Forward time (forward_fixed): nothing is decided.  The lists are whatever the last staging wrote; under DD_BATCH the forward
 //   checks that it runs at the depth they were trimmed for and reads the batch-uniform row.
 bool dedup_opts_on(dsg_handle h) {
-    if (!h->opt.dedup_masked || !prune_opts_on(h) || prune_plan(h).np.dd_n == 0) return false;
+    if (h->P != 1 || !h->opt.dedup_masked || !prune_opts_on(h) || prune_plan(h).np.dd_n == 0) return false;
     const BlockPlan &b0 = h->down[0][0];
     return h->opt.fused_patch_embed && h->pe_wp && (h->Kp == 32 || h->Kp == 64) && h->opt.fused_attn && b0.wqp && h->opt.fused_mlp && b0.w1p &&
            b0.C <= h->opt.fused_mlp_maxc;
@@ -1537,7 +1656,7 @@ void embed_rows(dsg_handle h, const float *c_noise, int rows, float *pe, float *
 // any_first_block: whatever the first block is (the bf16 block pipeline normalises the modulated tensor in its own row pass).
 bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s, bool *xn_done = nullptr, const NeedRef &pe_runs = NeedRef()) {
     const dsg_config &c = h->cfg;
-    const int B = w->B, N = h->N, E = h->E, T0 = N * N;
+    const int B = w->B, N = h->N, E = h->E, T0 = h->R0 * h->R0;   // N: the state's side; T0: level-0 tokens
     GemmArgs g;
     bool pe_done = false, pe_premod = false;
     if (h->opt.fused_patch_embed && h->pe_wp) {
@@ -1546,6 +1665,12 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
         // the first block's modulate+SiLU rides along when that block is the fused C = 96 attention kernel (which then skips it)
         const BlockPlan *b0 = h->down[0].empty() ? nullptr : &h->down[0][0];
         pe_premod = wants_premod(h, b0) && (fp32_rule ? (h->opt.fused_attn && b0->wqp) : true);
+        if (h->P == 2)
+            pe_done = launch_fused_patch_embed96_p2(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
+                                                    WT(h, "patch_embed.proj.bias"), WT(h, "patch_embed.norm.weight"), WT(h, "patch_embed.norm.bias"),
+                                                    w->aff, w->aff_ld, h->pe_aff_off, pe_premod ? b0->aff_off : -1, w->x, B, N, h->Ca, h->Cn,
+                                                    c.self_condition, h->pe_kps, s);
+        else
         pe_done = launch_fused_patch_embed96(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
                                              WT(h, "patch_embed.proj.bias"), WT(h, "patch_embed.norm.weight"),
                                              WT(h, "patch_embed.norm.bias"), w->aff, w->aff_ld, h->pe_aff_off, pe_premod ? b0->aff_off : -1,
@@ -1555,13 +1680,19 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
         pe_premod = pe_premod && pe_done;
         if (xn_done) *xn_done = pe_premod;
     }
+    if (!g_dry_run) w->patch_fwd[0] = pe_done ? 1 : 0;
     if (!pe_done) {
-        P_KERN(PK_ELEM, 0.0, launch_assemble(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, w->tok_in, B, N, h->Ca, h->Cn,
-                        c.self_condition, h->Kp, s));
+        if (h->P > 1)   // the p^2 sub-pixels' channels side by side: the strided convolution is the same GEMM over R0^2 tokens
+            P_KERN(PK_ELEM, 0.0, if (!launch_assemble_patch(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, w->tok_in, B,
+                                                            N, h->P, h->Ca, h->Cn, c.self_condition, h->Kp, s))
+                                     plan_fail(h, "patch_embed: assembly refused (N=%d patch_size=%d Kp=%d)", N, h->P, h->Kp));
+        else
+            P_KERN(PK_ELEM, 0.0, launch_assemble(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, w->tok_in, B, N, h->Ca,
+                                                 h->Cn, c.self_condition, h->Kp, s));
         g = GemmArgs();
         g.A = w->tok_in; g.lda = h->Kp; g.K1 = h->Kp; g.K = h->Kp; g.M = B * T0; g.N = E;
         g.W = h->pe_w; g.bias = WT(h, "patch_embed.proj.bias"); g.C = w->y; g.ldc = E;
-        P_KERN(PK_GEMM, 2.0 * (double)g.M * (double)g.N * (double)h->Cin,   // padded K is not algorithmic work
+        P_KERN(PK_GEMM, 2.0 * (double)g.M * (double)g.N * (double)h->Cin * h->P * h->P,   // padded K is not algorithmic work
                if (!launch_gemm(g, s)) plan_fail(h, "patch_embed.proj: GEMM not built (M=%d N=%d K=%d)", g.M, g.N, g.K));
         P_KERN(PK_ROW, 0.0, launch_ln_mod(w->y, WT(h, "patch_embed.norm.weight"), WT(h, "patch_embed.norm.bias"), w->aff, w->aff_ld, h->pe_aff_off,
                       w->x, B, T0, E, s));
@@ -1571,10 +1702,29 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
 
 // final norm + read_out + heads (diffusesg.py:758-761, :806-825): w->x -> (f_adj, f_node)
 void readout_stage(dsg_handle h, Workspace *w, hipStream_t s) {
-    const int B = w->B, N = h->N, E = h->E, T0 = N * N;
+    const int B = w->B, N = h->N, E = h->E, T0 = h->R0 * h->R0, PP = h->P * h->P;
     GemmArgs g;
-    const int M0 = B * T0;
-    if (h->opt.fused_readout && h->ro_fap && h->taps.empty()) {
+    const int M0 = B * T0, Mp = B * N * N;   // token rows (the final norm, read_out.0's input); pixel rows (everything behind it)
+    const bool fused = h->opt.fused_readout && h->ro_fap && h->taps.empty();
+    if (!g_dry_run) w->patch_fwd[1] = fused ? 1 : 0;
+    if (fused && h->P == 2) {
+        // the p = 2 form: LN(x) of 32 tokens held once, the folded chain once per sub-pixel, per-pixel masked stores, pooling partials per
+        // (token row, column parity); then the node fc1 over pool_ext [B N, 256] with the row-parity weight: two strided-row launches
+        P_KERN(PK_FUSED, 2.0 * (double)Mp * E * (E + 32.0),
+               if (!launch_fused_readout96_p2(w->x, WT(h, "norm.weight"), WT(h, "norm.bias"), h->ro_fap, h->ro_fa, h->ro_f2p,
+                                              WT(h, "readout_adj_mlp.fc2.bias"), w->flags, w->f_adj, w->pool_part, w->pool_ext, B, N, h->Ca, s))
+                   plan_fail(h, "read-out: the fused p = 2 kernel refused N=%d C_adj=%d", N, h->Ca));
+        for (int a = 0; a < 2; a++) {
+            g = GemmArgs();
+            g.A = w->pool_ext + (size_t)a * 256; g.lda = 512; g.K1 = 256; g.K = 256; g.M = B * N / 2; g.N = E; g.act = ACT_GELU;
+            g.W = h->ro_gext2[a]; g.bias = WT(h, "readout_node_mlp.fc1.bias"); g.C = w->hn + (size_t)a * E; g.ldc = 2 * E;
+            P_GEMM(g);
+        }
+        P_KERN(PK_ROW, 0.0, launch_head_node(w->hn, WT(h, "readout_node_mlp.fc2.weight"), WT(h, "readout_node_mlp.fc2.bias"), w->flags,
+                                             w->f_node, B, N, E, h->Cn, s));
+        return;
+    }
+    if (fused) {
         // the pooling partials of node row r go to slot (32-token tile) - (r N) / 32: where a graph's rows sit relative to the tiles, and with
         // it the order its partials are added in, is the same for every b only if a graph is a whole number of tiles
         if (h->opt.batch_invariant && T0 % 32 != 0)
@@ -1608,23 +1758,40 @@ void readout_stage(dsg_handle h, Workspace *w, hipStream_t s) {
     g = GemmArgs();
     g.A = w->x; g.lda = E; g.K1 = E; g.K = E; g.M = M0; g.N = E;
     g.ln_stats = w->stats;   // final norm's gamma/beta folded into ro0_wf / ro0_bf
-    g.W = h->ro0_wf; g.bias = h->ro0_bf; g.C = w->y; g.ldc = E;
+    // patch_size p: p^2 E output columns, (a p + b) E + o -- the [M0, p^2 E] result is r0 [Mp, E] with rows in (token, a, b) order
+    g.N = PP * E;
+    g.W = h->ro0_wf; g.bias = h->ro0_bf; g.C = w->y; g.ldc = PP * E;
     P_GEMM(g);
     g = GemmArgs();
-    g.A = w->y; g.lda = E; g.K1 = E; g.K = E; g.M = M0; g.N = E;
+    g.A = w->y; g.lda = E; g.K1 = E; g.K = E; g.M = Mp; g.N = E;
     g.W = WT(h, "read_out.1.weight"); g.bias = WT(h, "read_out.1.bias"); g.C = w->att; g.ldc = E;
     P_GEMM(g);
     g.A = w->att; g.W = WT(h, "read_out.2.weight"); g.bias = WT(h, "read_out.2.bias"); g.C = w->y;
     P_GEMM(g);  // y = shared_rep, token-major
-    tap(h, "read_out", w->y, (size_t)M0 * E, s);
+    if (h->P == 1) tap(h, "read_out", w->y, (size_t)M0 * E, s);
+    else if (!g_dry_run)   // the tap is in pixel order [B, N^2, E]: un-shuffle the (token, a, b) rows on the way out (debug taps only)
+        for (auto &t : h->taps)
+            if (t.name == "read_out" && (int64_t)Mp * E <= t.cap)
+                for (int ab = 0; ab < PP; ab++)   // sub-pixel (a, b): a strided 3-D copy [B R0][R0][E floats] per pixel row
+                    for (int ti = 0; ti < B * h->R0; ti++)
+                        (void)hipMemcpy2DAsync(t.dst + (((size_t)ti * h->P + ab / h->P) * N + ab % h->P) * E, sizeof(float) * h->P * E,
+                                               w->y + ((size_t)ti * h->R0 * PP + ab) * E, sizeof(float) * PP * E, sizeof(float) * E, h->R0,
+                                               hipMemcpyDeviceToDevice, s);
     // adjacency head (diffusesg.py:806-809, :825)
     g.A = w->y; g.W = WT(h, "readout_adj_mlp.fc1.weight"); g.bias = WT(h, "readout_adj_mlp.fc1.bias"); g.act = ACT_GELU;
     g.C = w->att;
     P_GEMM(g);
-    P_KERN(PK_ROW, 0.0, launch_head_adj(w->att, WT(h, "readout_adj_mlp.fc2.weight"), WT(h, "readout_adj_mlp.fc2.bias"), w->flags, w->f_adj, B, N, E,
-                    h->Ca, s));
+    if (h->P > 1)   // rows in (token, a, b) order: the store and the pooling carry the map to (I, J) and mask per pixel
+        P_KERN(PK_ROW, 0.0, if (!launch_head_adj_patch(w->att, WT(h, "readout_adj_mlp.fc2.weight"), WT(h, "readout_adj_mlp.fc2.bias"), w->flags, w->f_adj,
+                                                       B, N, h->P, E, h->Ca, s)) plan_fail(h, "read-out: adjacency head refused (N=%d patch_size=%d)", N, h->P));
+    else
+        P_KERN(PK_ROW, 0.0, launch_head_adj(w->att, WT(h, "readout_adj_mlp.fc2.weight"), WT(h, "readout_adj_mlp.fc2.bias"), w->flags, w->f_adj, B, N,
+                                            E, h->Ca, s));
     // node head (diffusesg.py:812-822)
-    P_KERN(PK_ELEM, 0.0, launch_pool(w->y, w->flags, w->pool, B, N, E, s));
+    if (h->P > 1)
+        P_KERN(PK_ELEM, 0.0, if (!launch_pool_patch(w->y, w->flags, w->pool, B, N, h->P, E, s)) plan_fail(h, "read-out: pooling refused (N=%d patch_size=%d)", N, h->P));
+    else
+        P_KERN(PK_ELEM, 0.0, launch_pool(w->y, w->flags, w->pool, B, N, E, s));
     g = GemmArgs();
     g.A = w->pool; g.lda = E; g.K1 = E; g.K = E; g.M = B * N; g.N = E; g.act = ACT_GELU;
     g.W = WT(h, "readout_node_mlp.fc1.weight"); g.bias = WT(h, "readout_node_mlp.fc1.bias"); g.C = w->hn; g.ldc = E;
@@ -1832,12 +1999,22 @@ PureTabLayout pure_tab_layout(dsg_handle h) {
 struct TabBuild { int stop; float *dst; int n; };
 
 // DiffuseSG.forward on the workspace's fixed buffers: (in_adj,in_node,sc_*,flags,c_noise) -> (f_adj,f_node)
+// patch_size > 1 runs the fp32 kernels only: the option that cannot run there, or null
+const char *patch_refused_option(dsg_handle h) {
+    if (h->P == 1) return nullptr;
+    return h->opt.gemm_split ? "gemm_split" : h->opt.gemm_bf16 ? "gemm_bf16" : h->opt.batch_invariant ? "batch_invariant" : nullptr;
+}
+
 void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s, const TabBuild *tb = nullptr) {
+    if (const char *o = patch_refused_option(h)) {
+        plan_fail(h, "option \"%s\" is not built at patch_size %d (patch_size > 1 runs the fp32 kernels only)", o, h->P);
+        return;
+    }
     if (bx_on(h)) { if (tb) plan_fail(h, "dedup_table: no table of pure-window rows in the bf16 pipeline"); else forward_fixed_bx(h, w, s); return; }
     // the fused PatchMerging writes the coarser level into the other activation buffer and swaps the two names; put them back
     // on every exit so that each forward (and each captured graph) starts from the same assignment
     struct SwapGuard { Workspace *w; float *x, *y; ~SwapGuard() { w->x = x; w->y = y; } } swap_guard{w, w->x, w->y};
-    const int B = w->B, N = h->N, E = h->E, L = h->L, T0 = N * N;
+    const int B = w->B, N = h->R0, E = h->E, L = h->L, T0 = N * N;   // N: the level-0 TOKEN resolution in this function
     char name[64];
     GemmArgs g;
     w->aff_ld = w->uniform ? 0 : h->aff_n;
@@ -2279,6 +2456,15 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
         return fail(h, DSG_ERR_INVALID, "debug_alloc_fill is 0 (off) or a pattern 1..4, not %d", value);   // (the one strict row)
     const Options saved = h->opt;   // restored if the new selection cannot run (below)
     h->opt.*r->field = r->normalised(value);
+    // patch_size > 1: switching one of the modes it does not build ON is refused here, ahead of the weight copies and whether or not a batch
+    // size is in use yet.  Any other change passes -- a mode stored from an environment default is refused by the plan check of the first
+    // forward (forward_fixed), and setting it to 0 is how a caller clears it
+    const bool patch_mode_on = (r->field == &Options::gemm_split || r->field == &Options::gemm_bf16 || r->field == &Options::batch_invariant) &&
+                               (h->opt.*r->field) != 0;
+    if (const char *o = patch_mode_on ? patch_refused_option(h) : nullptr) {
+        h->opt = saved;
+        return fail(h, DSG_ERR_INVALID, "option '%s' = %d rejected: \"%s\" is not built at patch_size %d (patch_size > 1 runs the fp32 kernels only)", name, value, o, h->P);
+    }
     if (h->finalized) {   // the precision modes run on copies of the weights
         int rc = 0;
         if (r->field == &Options::gemm_bf16 && h->opt.gemm_bf16) rc = ensure_bf16_weights(h);
@@ -2289,7 +2475,9 @@ int dsg_set_option(dsg_handle h, const char *name, int32_t value) {
     drop_graphs(h);   // captured graphs bake the kernel selection
     // plan time: every batch size in use must still be covered by the kernels the new selection launches; if not, the option keeps
     // its old value and the caller gets DSG_ERR_INVALID with the layer / shape in dsg_last_error
-    if (h->finalized)
+    // (a patch_size > 1 handle still holding a refused mode from its environment default has no valid plan whatever this call set: the
+    // next forward says so; this call is not blamed for it)
+    if (h->finalized && !patch_refused_option(h))
         for (auto &kv : h->ws)
             if (int rc = validate_plan(h, kv.second.get())) {
                 const std::string why = h->err;
@@ -3349,6 +3537,14 @@ int dsg_debug_readout_tiles(dsg_handle h, int32_t B, int32_t *counts, int32_t *t
     return DSG_OK;
 }
 
+int dsg_debug_patch_forms(dsg_handle h, int32_t B, int32_t forms[2]) {
+    if (!h || !forms) return DSG_ERR_INVALID;
+    auto it = h->ws.find(B);
+    forms[0] = it == h->ws.end() ? -1 : it->second->patch_fwd[0];
+    forms[1] = it == h->ws.end() ? -1 : it->second->patch_fwd[1];
+    return DSG_OK;
+}
+
 int dsg_debug_dedup_lists(dsg_handle h, int32_t B, int32_t *counts, int32_t *wins, int32_t *runs, int32_t *copy, int32_t *rep, void *stream) {
     return dsg_debug_dedup_level_lists(h, B, 0, counts, wins, runs, copy, rep, stream);
 }
@@ -3417,6 +3613,11 @@ int dsg_rainbow_loss_backward(int32_t B, int32_t N, int32_t c_adj, int32_t c_nod
 
 // ---- training form: what one block and the whole network share ----
 namespace {
+// the training form (weight and input gradients, the ODE encoder) is built for patch_size 1: refused before anything is enqueued
+static int patch_no_training(dsg_handle h, const char *entry) {
+    return fail(h, DSG_ERR_INVALID, "%s: the training form is not built at patch_size %d (patch_size > 1 covers the sampling entries only)", entry, h->P);
+}
+
 struct TArena {   // bump allocator over one device buffer; without a base it only sizes (every get returns null)
     float *base = nullptr; size_t off = 0;
     float *get(size_t n) { n = (n + 63) / 64 * 64; float *p = base ? base + off : nullptr; off += n; return p; }
@@ -3873,6 +4074,7 @@ int dsg_train_grads(dsg_handle h, int32_t B, const float *in_adj, const float *i
     // the training form reads the raw weights only, so weights re-uploaded after an optimiser step need no re-packing here
     // (dsg_finalize_weights must have run once: block plans); the sampling-path entries still insist on `finalized`
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (h->P != 1) return patch_no_training(h, "dsg_train_grads");
     if (B < 1 || !in_adj || !in_node || !flags || !c_noise || !out_F_adj || !out_F_node) return fail(h, DSG_ERR_INVALID, "null argument");
     const bool bwd = grad_F_adj != nullptr;
     if (bwd && (!grad_F_node || !names || !grad_params)) return fail(h, DSG_ERR_INVALID, "backward needs both output gradients and the parameter gradient buffers");
@@ -3903,6 +4105,7 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
                          int32_t iou_loss_type, float *out_D_adj, float *out_D_node, float *out_loss_adj, float *out_loss_node,
                          int32_t n_params, const char *const *names, float *const *grad_params, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (h->P != 1) return patch_no_training(h, "dsg_train_step_grads");
     if (iou_loss_type < DSG_IOU_IOU || iou_loss_type > DSG_IOU_CIOU) return fail(h, DSG_ERR_INVALID, "iou_loss_type %d", iou_loss_type);
     if (B < 1 || !noisy_adj || !noisy_node || !flags || !sigmas || !target_adj || !target_node || !out_D_adj || !out_D_node || !out_loss_adj ||
         !out_loss_node)
@@ -3935,6 +4138,7 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
 int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const float *noisy_node, const uint8_t *flags, const float *sigmas,
                         float *out_sc_adj, float *out_sc_node, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (h->P != 1) return patch_no_training(h, "dsg_train_self_cond");
     if (B < 1 || !noisy_adj || !noisy_node || !flags || !sigmas || !out_sc_adj || !out_sc_node) return fail(h, DSG_ERR_INVALID, "null argument");
     hipStream_t s = (hipStream_t)stream;
     const Dims d = dims_of(h, B);
@@ -3955,6 +4159,7 @@ int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node
                     const float *sc_adj, const float *sc_node, const float *grad_D_adj, const float *grad_D_node, dsg_grad_fn fn, void *user,
                     float *out_D_adj, float *out_D_node, float *out_grad_adj, float *out_grad_node, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (h->P != 1) return patch_no_training(h, "dsg_precond_vjp");
     if (B < 1 || !adj || !node || !flags || !sigmas || !out_D_adj || !out_D_node || !out_grad_adj || !out_grad_node)
         return fail(h, DSG_ERR_INVALID, "null argument");
     if ((grad_D_adj == nullptr) != (grad_D_node == nullptr)) return fail(h, DSG_ERR_INVALID, "grad_D_adj and grad_D_node go together");
@@ -4042,6 +4247,7 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
                 const float *x_node, const uint64_t *graph_seeds, const float *probe_adj, const float *probe_node, float *out_adj,
                 float *out_node, float *out_probe_adj, float *out_probe_node, double *out_net_trace, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
+    if (h->P != 1) return patch_no_training(h, "dsg_ode_run");
     if (!cfg || !ode || B < 1 || !flags || !x_adj || !x_node || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null argument");
     if (cfg->num_steps < 2) return fail(h, DSG_ERR_INVALID, "dsg_ode_run needs num_steps >= 2 (it steps between the schedule's levels; num_steps is %d)", cfg->num_steps);
     if (solver_2m(cfg)) return fail(h, DSG_ERR_INVALID, "dsg_ode_run has no multistep solver (heun = %d): use DSG_SOLVER_EULER or DSG_SOLVER_HEUN", DSG_SOLVER_DPMPP_2M);

@@ -229,6 +229,44 @@ int dsg_debug_head_f32(int32_t kind, int32_t B, int32_t N, int32_t E, int32_t c_
     return debug_finish(true, s);
 }
 
+// ---- the edge kernels of the patch_size > 1 forward (kernels_patch.hip; tests/test_patch_kernels.py) ----
+
+int dsg_debug_assemble_patch_f32(int32_t B, int32_t N, int32_t p, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kp, const float *adj,
+                                 const float *node, const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags,
+                                 float *out, void *stream) {
+    if ((p != 1 && p != 2 && p != 4) || !adj || !node || !flags || !out) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish(launch_assemble_patch(adj, node, sc_adj, sc_node, has_sc, flags, out, B, N, p, c_adj, c_node, self_cond, Kp, s), s);
+}
+
+int dsg_debug_head_patch_f32(int32_t kind, int32_t B, int32_t N, int32_t p, int32_t E, int32_t c_out, const float *h, const float *W,
+                             const float *bias, const uint8_t *flags, float *out, void *stream) {
+    if ((p != 1 && p != 2 && p != 4) || !h || !flags || !out || (kind != DSG_HEAD_ADJ && kind != DSG_HEAD_POOL)) return DSG_ERR_INVALID;
+    if (kind == DSG_HEAD_ADJ && (c_out < 1 || !W || !bias)) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish(kind == DSG_HEAD_ADJ ? launch_head_adj_patch(h, W, bias, flags, out, B, N, p, E, c_out, s)
+                                             : launch_pool_patch(h, flags, out, B, N, p, E, s), s);
+}
+
+int dsg_debug_patch_embed_patch_f32(int32_t B, int32_t N, int32_t p, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kps, const float *adj,
+                                    const float *node, const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags,
+                                    const float *Wp, const float *bias, const float *gam, const float *bet, const float *aff, int32_t aff_ld,
+                                    int32_t aff_off, int32_t aff_off2, float *x, void *stream) {
+    if (p != 2 || !adj || !node || !flags || !Wp || !bias || !gam || !bet || !aff || !x) return DSG_ERR_INVALID;
+    if (!mult4(aff_ld) || !mult4(aff_off) || (aff_off2 >= 0 && !mult4(aff_off2))) return DSG_ERR_INVALID;   // 16-byte reads of the (scale | shift) rows
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish(launch_fused_patch_embed96_p2(adj, node, sc_adj, sc_node, has_sc, flags, Wp, bias, gam, bet, aff, aff_ld, aff_off, aff_off2, x,
+                                                      B, N, c_adj, c_node, self_cond, Kps, s), s);
+}
+
+int dsg_debug_readout_patch_f32(int32_t B, int32_t N, int32_t p, int32_t c_adj, const float *x, const float *gam, const float *bet, const float *Wfp,
+                                const float *fa, const float *W2p, const float *f2, const uint8_t *flags, float *out_adj, float *pool_part,
+                                float *pool_ext, void *stream) {
+    if (p != 2 || !x || !gam || !bet || !Wfp || !fa || !W2p || !f2 || !flags || !out_adj || !pool_part || !pool_ext) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_finish(launch_fused_readout96_p2(x, gam, bet, Wfp, fa, W2p, f2, flags, out_adj, pool_part, pool_ext, B, N, c_adj, s), s);
+}
+
 int dsg_debug_row_f32(int32_t kind, int32_t B, int32_t t, int32_t C, float *x, const float *g, const float *b, const float *pg, const float *pb,
                       const float *aff, int32_t aff_ld, int32_t aff_off, const float *ln_part, int32_t nparts, float *y, float *stats,
                       const int32_t *run_list, const int32_t *run_cnt, void *stream) {

@@ -238,6 +238,32 @@ void launch_pool(const float *rep, const uint8_t *flags, float *pool, int B, int
 void launch_head_node(const float *h, const float *W, const float *bias, const uint8_t *flags, float *out,
                       int B, int N, int E, int Cn, hipStream_t s);
 
+// ---- patch_size p > 1 (kernels_patch.hip): token t = ti R + tj of the R = N / p grid covers the pixels (p ti + a, p tj + b); the rows
+// of the read-out chain are in (token, a, b) order, row m = (b R^2 + t) p^2 + a p + b.  false: arguments refused (nothing launched) ----
+// input assembly: out [B R^2, Kp], k = (a p + b) Cin + c (c in launch_assemble's channel order), zero padded from p^2 Cin
+bool launch_assemble_patch(const float *adj, const float *node, const float *sc_adj, const float *sc_node, const int *has_sc,
+                           const uint8_t *flags, float *out, int B, int N, int p, int Ca, int Cn, int self_cond, int Kp, hipStream_t s);
+// adjacency head tail: h [B N^2, E] rows in (token, a, b) order -> out [B,Ca,N,N] = valid(I, J) ? h @ W^T + b : 0
+bool launch_head_adj_patch(const float *h, const float *W, const float *bias, const uint8_t *flags, float *out, int B, int N, int p, int E,
+                           int Ca, hipStream_t s);
+// masked mean pooling over the N pixels J of node row I: rep [B N^2, E] in (token, a, b) order -> pool [B N, E]
+bool launch_pool_patch(const float *rep, const uint8_t *flags, float *pool, int B, int N, int p, int E, hipStream_t s);
+
+// The fused forms for E = 96, p = 2.  PatchEmbed: Wp [4][3][Kps / 8][64] float4, sub-pixel sub = 2 a + b, each launch_fused_patch_embed96's
+// fragment order of patch_embed.proj.weight[:, :, a, b] zero-padded to Kps = 32 | 64 >= in_chans; the rest as launch_fused_patch_embed96
+// (no xn, no run list); x [B (N/2)^2, 96].
+bool launch_fused_patch_embed96_p2(const float *adj, const float *node, const float *sc_adj, const float *sc_node, const int *has_sc,
+                                   const uint8_t *flags, const float *Wp, const float *bias, const float *gam, const float *bet,
+                                   const float *aff, int aff_ld, int aff_off, int aff_off2, float *x, int B, int N, int Ca, int Cn,
+                                   int self_cond, int Kps, hipStream_t s);
+// Read-out: x [B (N/2)^2, 96]; Wfp [4][3][12][64] float4: the folded Fa[a, b] per sub-pixel in launch_fused_readout96's fragment order;
+// fa, W2p, f2 as there.  pool_part: scratch [B N/2][readout_pool_segments_p2(N)][2][96]; pool_ext [B N, 256]: per node row
+// (s[ti, 0] | s[ti, 1] | flag_I cnt_0 / N | flag_I cnt_1 / N | 0 ..), s[ti, q] = (1/N) sum_tj flag_{2 tj + q} LN(x)[ti, tj]
+int readout_pool_segments_p2(int N);
+bool launch_fused_readout96_p2(const float *x, const float *gam, const float *bet, const float *Wfp, const float *fa, const float *W2p,
+                               const float *f2, const uint8_t *flags, float *out_adj, float *pool_part, float *pool_ext, int B, int N,
+                               int Ca, hipStream_t s);
+
 // ---- masked-token pruning: device-side need lists (kernels.hip: need_lists_kernel) ----
 // A plan is a short program on one sample's set of needed 8-token runs, starting from the last level's output need (runs that hold a
 // pair with flag_i && flag_j) and walking the up path backwards.  Lists are compacted over the whole batch: run lists hold

@@ -20,7 +20,7 @@ EXPORTS = [
     "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd", "dsg_sgstat_triplet_counts", "dsg_sgstat_layout",
     "dsg_sgstat_f1_rowstats", "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
     "dsg_sample_seeded", "dsg_gen_noise_seeded", "dsg_precond_vjp", "dsg_ode_run", "dsg_ode_evals", "dsg_guide_coef", "dsg_sample_guided",
-    "dsg_sample_guided_rel", "dsg_option_info",
+    "dsg_sample_guided_rel", "dsg_option_info", "dsg_create_patch",
 ]
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
@@ -96,7 +96,8 @@ DEBUG_EXPORTS = [
     "dsg_debug_dedup_qkv_lists", "dsg_debug_qk_split", "dsg_debug_readout_tiles", "dsg_debug_t_assemble_bwd", "dsg_debug_patch_embed_f32",
     "dsg_debug_assemble_f32", "dsg_debug_readout_f32", "dsg_debug_head_f32", "dsg_debug_row_f32", "dsg_debug_window_broadcast_f32",
     "dsg_debug_window_harvest_f32", "dsg_debug_graph_dot", "dsg_debug_poison", "dsg_debug_box_guide", "dsg_debug_box_guide_rel",
-    "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp",
+    "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp", "dsg_debug_patch_forms",
+    "dsg_debug_assemble_patch_f32", "dsg_debug_head_patch_f32", "dsg_debug_patch_embed_patch_f32", "dsg_debug_readout_patch_f32",
 ]
 
 
@@ -152,6 +153,11 @@ def _declare_debug(L: C.CDLL) -> None:
     L.dsg_debug_dedup_launch_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.dsg_debug_dedup_qkv_lists.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     L.dsg_debug_readout_tiles.argtypes = [vp, i32, vp, vp, vp]
+    L.dsg_debug_patch_forms.argtypes = [vp, i32, vp]
+    L.dsg_debug_assemble_patch_f32.argtypes = [i32] * 7 + [vp] * 8
+    L.dsg_debug_head_patch_f32.argtypes = [i32] * 6 + [vp] * 6
+    L.dsg_debug_patch_embed_patch_f32.argtypes = [i32] * 7 + [vp] * 11 + [i32] * 3 + [vp] * 2
+    L.dsg_debug_readout_patch_f32.argtypes = [i32] * 4 + [vp] * 12
     L.dsg_debug_qk_split.argtypes = [i32, i32]
     L.dsg_debug_qk_split.restype = i32
     L.dsg_profile_clock_ghz.argtypes = [vp]
@@ -230,6 +236,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
         raise DsgError(f"{lib_path} has ABI generation {abi}, this binding needs {ABI_VERSION}: rebuild it "
                        f"(python -c 'import __graft_entry__ as g; g.build()')")
     L.dsg_create.argtypes = [C.POINTER(DsgConfig), C.POINTER(vp)]
+    L.dsg_create_patch.argtypes = [C.POINTER(DsgConfig), i32, C.POINTER(vp)]
     L.dsg_destroy.argtypes = [vp]
     L.dsg_destroy.restype = None
     L.dsg_last_error.argtypes = [vp]
@@ -348,7 +355,9 @@ class Handle:
         self.cfg = cfg
         self._c = make_config(cfg)
         self._h = C.c_void_p()
-        rc = self.L.dsg_create(C.byref(self._c), C.byref(self._h))
+        ps = int(getattr(cfg, "patch_size", 1))   # the reference's patch_size is not a field of dsg_config: its own entry point
+        rc = (self.L.dsg_create(C.byref(self._c), C.byref(self._h)) if ps == 1 else
+              self.L.dsg_create_patch(C.byref(self._c), ps, C.byref(self._h)))
         if rc != 0:
             why = self.L.dsg_last_error(None)
             raise DsgError(f"dsg_create failed with status {rc}: {why.decode() if why else ''} (there is no CPU fallback)")
@@ -478,6 +487,13 @@ class Handle:
         if counts[0] < 0:
             return None
         return dict(tiles=tiles[:counts[0]].copy(), form={1: "list", 0: "pos"}.get(int(counts[1])))
+
+    def patch_forms(self, B: int):
+        """The route batch B's last forward took through (PatchEmbed, the read-out): 'fused' | 'chain' | None (no forward yet)
+        (dsg_debug_patch_forms)."""
+        forms = (C.c_int32 * 2)()
+        self.check(self.L.dsg_debug_patch_forms(self._h, B, forms), "dsg_debug_patch_forms")
+        return tuple({1: "fused", 0: "chain"}.get(int(f)) for f in forms)
 
     def precision_mode(self) -> str:
         """'f32' | 'f32-split' | 'bf16': the GEMM arithmetic the handle will actually run (options or DSG_* env defaults)."""

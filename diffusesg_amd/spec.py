@@ -24,7 +24,7 @@ HEAD_DIM = 32    # embed_dim / num_heads[0] = 96 / 3 at every level (learning_ut
 @dataclass(frozen=True)
 class ModelConfig:
     """Mirror of the kwargs `get_network` passes to `DiffuseSG` (learning_utils.py:47-64)."""
-    max_node_num: int            # img_size == N (patch_size is always 1 in the reference configs)
+    max_node_num: int            # img_size == N (patch_size is 1 in both reference YAMLs; 2 and 4 are `--patch_size`)
     c_adj: int                   # out_chans_adj == adjacency channels of the state
     c_node: int                  # out_chans_node == node channels of the state
     embed_dim: int = 96
@@ -36,8 +36,10 @@ class ModelConfig:
     patch_size: int = 1
 
     def __post_init__(self):
-        if self.patch_size != 1:
-            raise NotImplementedError("only patch_size=1 (both reference YAMLs) is supported")
+        if self.patch_size not in (1, 2, 4):
+            raise NotImplementedError("patch_size must be 1, 2 or 4")
+        if self.max_node_num % self.patch_size != 0:
+            raise ValueError("max_node_num must be divisible by patch_size")
         if len(self.depths) > len(self.num_heads):
             raise ValueError("depths longer than num_heads")
         for i in range(len(self.depths)):
@@ -60,8 +62,13 @@ class ModelConfig:
     def level_dim(self, lvl: int) -> int:
         return self.embed_dim << lvl
 
+    @property
+    def token_res(self) -> int:
+        """Tokens per side at level 0: N / patch_size (diffusesg.py:556-577)."""
+        return self.max_node_num // self.patch_size
+
     def level_res(self, lvl: int) -> int:
-        return self.max_node_num >> lvl
+        return self.token_res >> lvl
 
     def level_window(self, lvl: int) -> int:
         """Effective window (diffusesg.py:189-192): clipped to the resolution."""
@@ -199,7 +206,8 @@ def state_dict_spec(cfg: ModelConfig) -> List[TensorSpec]:
     s: List[TensorSpec] = [
         TensorSpec("patch_embed.affine.weight", (2 * e, NOISE_EMB), "matrix", NOISE_EMB),
         TensorSpec("patch_embed.affine.bias", (2 * e,), "bias"),
-        TensorSpec("patch_embed.proj.weight", (e, cfg.in_chans, 1, 1), "conv", cfg.in_chans),
+        TensorSpec("patch_embed.proj.weight", (e, cfg.in_chans, cfg.patch_size, cfg.patch_size), "conv",
+                   cfg.in_chans * cfg.patch_size ** 2),
         TensorSpec("patch_embed.proj.bias", (e,), "bias"),
         TensorSpec("patch_embed.norm.weight", (e,), "ln_w"),
         TensorSpec("patch_embed.norm.bias", (e,), "ln_b"),
@@ -230,7 +238,7 @@ def state_dict_spec(cfg: ModelConfig) -> List[TensorSpec]:
             s += _block_specs(f"up_layers.{i}.blocks.{j}", c, cfg.num_heads[lvl], ws, res,
                               cfg.block_shift(lvl, j), cfg.mlp_ratio)
     s += [
-        TensorSpec("read_out.0.weight", (e, e, 1, 1), "convT", e),   # ConvTranspose2d: [in,out,1,1]
+        TensorSpec("read_out.0.weight", (e, e, cfg.patch_size, cfg.patch_size), "convT", e),   # ConvTranspose2d: [in,out,p,p]
         TensorSpec("read_out.0.bias", (e,), "bias"),
         TensorSpec("read_out.1.weight", (e, e, 1, 1), "conv", e),
         TensorSpec("read_out.1.bias", (e,), "bias"),
@@ -260,11 +268,11 @@ def num_parameters(cfg: ModelConfig) -> int:
 
 def flops_per_forward(cfg: ModelConfig) -> int:
     """2*MAC over linears, 1x1 convs, QK^T and PV for one sample, one network forward."""
-    e, n = cfg.embed_dim, cfg.max_node_num
-    t0 = n * n
+    e, n, ps = cfg.embed_dim, cfg.max_node_num, cfg.patch_size
+    t0, tr = n * n, cfg.token_res ** 2                               # pixels, level-0 tokens
     f = 0
     f += 2 * (e * NOISE_EMB + NOISE_EMB * NOISE_EMB)                 # noise-embedding MLP
-    f += 2 * t0 * cfg.in_chans * e                                   # patch-embed conv
+    f += 2 * tr * cfg.in_chans * ps * ps * e                         # patch-embed conv
     f += 2 * NOISE_EMB * 2 * e                                       # patch-embed affine
 
     def block(lvl):
@@ -280,7 +288,7 @@ def flops_per_forward(cfg: ModelConfig) -> int:
             f += 2 * (t // 4) * 4 * c * 2 * c                        # PatchMerging
             d, tc = 4 * c, cfg.level_res(lvl + 1) ** 2
             f += 2 * tc * d * d + 2 * (4 * tc) * (d // 4) ** 2       # PatchBreakup
-    f += 3 * 2 * t0 * e * e                                          # read_out
+    f += 2 * tr * e * e * ps * ps + 2 * 2 * t0 * e * e               # read_out: the transposed conv from tokens, two 1x1 convs per pixel
     f += 2 * t0 * (e * e + e * cfg.c_adj)                            # adj head
     f += 2 * n * (e * e + e * cfg.c_node)                            # node head
     return f

@@ -37,6 +37,40 @@ CONFIGS = {"tiny": S.tiny_config, "small": small_config, "nosc": nosc_config,
 # ragged numbers of valid nodes per sample used by the forward / precond goldens
 VALID = {"tiny": [8, 5], "small": [16, 9], "nosc": [8, 3], "vg": [30, 11], "coco": [20, 40], "onehot": [8, 5]}
 
+# patch_size > 1 (the reference's `--patch_size`; tests/golden/fwd_patch_<name>.npz, tools/gen_patch_golden.py): name -> (N, p, c_adj,
+# c_node, depths, window, self-conditioning).  tiny_p2: R = 4, a 64-lane wave spans two graphs; small_p2: R = 8, a shifted, masked block;
+# small_p4: R = 4, shift 1; nosc_p2: squeezed layouts, K = 12; coco2_p2: R = 20, 100-token windows, R^2 no multiple of 32; vg_p2: the
+# full-size shape, K = 240 -> 256.  Odd valid counts put a token with valid and padded pixels in every case.
+_PATCH = {
+    "tiny_p2": (8, 2, 6, 12, (1, 1), 4, True),
+    "small_p2": (16, 2, 3, 5, (2, 1), 4, True),
+    "small_p4": (16, 4, 3, 5, (2, 1), 2, True),
+    "nosc_p2": (8, 2, 1, 1, (1, 1), 4, False),
+    "coco2_p2": (40, 2, 3, 12, (1, 2), 10, True),
+    "vg_p2": (64, 2, 6, 12, (1, 1, 3, 1), 8, True),
+}
+
+
+def _patch_config(name: str):
+    def mk() -> S.ModelConfig:
+        n, p, ca, cn, depths, ws, sc = _PATCH[name]
+        return S.ModelConfig(max_node_num=n, c_adj=ca, c_node=cn, depths=depths, num_heads=(3, 6, 12, 24)[:len(depths)],
+                             window_size=ws, self_condition=sc, patch_size=p)
+    return mk
+
+
+PATCH_CONFIGS = {name: _patch_config(name) for name in _PATCH}
+PATCH_VALID = {"tiny_p2": [8, 5], "small_p2": [16, 9], "small_p4": [16, 9], "nosc_p2": [8, 3], "coco2_p2": [21, 40], "vg_p2": [30, 11]}
+PATCH_ROW_SAMPLED = ("coco2_p2", "vg_p2")     # their intermediates are stored as inter_rows() row samples
+# sampler_patch.npz: tiny_p2, B = 4, (name, T, solver, S_churn)
+PATCH_SAMPLER_RUNS = (("t8_heun", 8, "heun", 40.0), ("t8_euler", 8, "euler", 0.0))
+
+
+def patch_fwd_case(name: str):
+    cfg = PATCH_CONFIGS[name]()
+    return (cfg,) + case_inputs(cfg, 2, PATCH_VALID[name], 1, f"fwd/{name}")
+
+
 FWD_C_NOISE = np.array([0.35, -1.2], dtype=np.float32)
 PRECOND_SIGMAS = (80.0, 1.5, 0.002)
 
@@ -95,10 +129,19 @@ def inter_rows(n_rows: int) -> np.ndarray:
     return np.sort(np.unique(idx.astype(np.int64))[:INTER_ROWS]) if n_rows > INTER_ROWS else np.arange(n_rows)
 
 
+def patch_owner_rows(cfg: S.ModelConfig, B: int) -> np.ndarray:
+    """Token rows (of [B * R^2, E]) that own the pixel rows inter_rows(B * N^2) of the read-out tap, in that order (duplicates kept):
+    pixel (b, I, J) belongs to token (b, I // p, J // p).  The row-sampled patch fixtures keep the final norm's output there."""
+    n, p, R = cfg.max_node_num, cfg.patch_size, cfg.token_res
+    px = inter_rows(B * n * n)
+    b, i, j = px // (n * n), (px // n) % n, px % n
+    return b * R * R + (i // p) * R + j // p
+
+
 def tap_shapes(cfg: S.ModelConfig) -> dict:
     """name -> (tokens per sample, channels) of every named intermediate activation (dsg_debug_tap / the oracle's taps)."""
-    n, E, L = cfg.max_node_num, cfg.embed_dim, len(cfg.depths)
-    out = {"patch_embed": (n * n, E), "read_out": (n * n, E)}
+    npix, n, E, L = cfg.max_node_num, cfg.token_res, cfg.embed_dim, len(cfg.depths)
+    out = {"patch_embed": (n * n, E), "read_out": (npix * npix, E)}   # tokens of the R x R grid; read_out: pixel order
     for l in range(L):
         T, C = (n >> l) ** 2, E << l
         for j in range(cfg.depths[l]):
@@ -298,7 +341,7 @@ def block_case(cfg, prefix: str, B: int, seed: int = 11):
     realistic scale, and the upstream gradient dY [B, T, C] (tools/gen_golden.py::gen_block_backward, tests)."""
     parts = prefix.split(".")
     lvl = int(parts[1]) if parts[0] == "down_layers" else cfg.num_layers - 1 - int(parts[1])
-    res, C = cfg.max_node_num >> lvl, cfg.embed_dim << lvl
+    res, C = cfg.level_res(lvl), cfg.embed_dim << lvl
     x = W.normal(seed, f"blk/{prefix}/x", (B, res * res, C))
     emb = (0.3 * W.normal(seed, f"blk/{prefix}/emb", (B, 512))).astype(np.float32)
     dy = W.normal(seed, f"blk/{prefix}/dy", (B, res * res, C))

@@ -58,7 +58,7 @@ typedef struct dsg_handle_s *dsg_handle;
 
 /* Mirrors the kwargs of DiffuseSG(...) as passed by get_network (learning_utils.py:47-64). */
 typedef struct dsg_config {
-    int32_t max_node_num;              /* img_size (N); patch_size is 1 */
+    int32_t max_node_num;              /* img_size (N); patch_size is 1 under dsg_create, dsg_create_patch takes it */
     int32_t c_adj;                     /* out_chans_adj */
     int32_t c_node;                    /* out_chans_node */
     int32_t embed_dim;                 /* feature_dims[-1], 96 */
@@ -95,7 +95,22 @@ typedef struct dsg_sample_stats {
     int64_t graph_replays;             /* network forwards that ran from replayed graphs (== net_forwards with use_graph) */
 } dsg_sample_stats;
 
-int dsg_create(const dsg_config *cfg, dsg_handle *out);
+int dsg_create(const dsg_config *cfg, dsg_handle *out);   /* == dsg_create_patch(cfg, 1, out) */
+/* The reference's `patch_size` (p in {1, 2, 4}; N % p == 0): the U-Net runs on R x R tokens, R = N / p; token t = ti R + tj covers the
+ * pixels (I, J) = (p ti + a, p tj + b), 0 <= a, b < p.  Level l has resolution R >> l; windows and shifts are clipped at that
+ * resolution.  States, flags and every entry point's tensors keep their [B, C, N, N] / [B, N, C] shapes.  Weights:
+ *   patch_embed.proj.weight [E, Cin, p, p]   (Conv2d, stride p: y[t, e] = bias[e] + sum_{c,a,b} W[e, c, a, b] img[c, p ti + a, p tj + b])
+ *   read_out.0.weight       [E, E, p, p]     (ConvTranspose2d, [in, out, a, b]: r0[(I, J), o] = b0[o] + sum_i LN(x)[t, i] W0[i, o, a, b])
+ * Inside the library the rows of the read-out chain stay in (token, a, b) order; adjacency outputs and the node pooling are masked per
+ * pixel by flag_I && flag_J, and the node mean is over the N pixels of a row.
+ * At p > 1: with two levels or more the coarsest resolution R >> (L - 1) must be even (the reference's PatchBreakup asserts it on its
+ * input) -- DSG_ERR_INVALID otherwise; "prune_masked" / "dedup_masked" report 0 (their lists are derived at pixel resolution);
+ * "gemm_split", "gemm_bf16" and "batch_invariant" are refused (dsg_set_option keeps the old value; a handle created under such an
+ * environment default is refused by its first forward until the option is set to 0); "fused_patch_embed" / "fused_readout" select the
+ * fused E = 96 kernels at p = 2 (in_chans <= 64, C_adj <= 32; default) or the chain of kernels, p = 4 always runs the chain; and
+ * dsg_train_grads,
+ * dsg_train_step_grads, dsg_train_self_cond, dsg_precond_vjp and dsg_ode_run return DSG_ERR_INVALID (messages name patch_size). */
+int dsg_create_patch(const dsg_config *cfg, int32_t patch_size, dsg_handle *out);
 void dsg_destroy(dsg_handle h);
 /* h == NULL: the reason the last dsg_create on the calling thread failed (there is no handle to ask then) */
 const char *dsg_last_error(dsg_handle h);

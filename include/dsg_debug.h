@@ -99,6 +99,11 @@ int dsg_debug_dedup_qkv_lists(dsg_handle h, int32_t B, int32_t level, int32_t *c
  * 0 positional, -1 no fused read-out yet.  Both -1: the plan has no such list (N % 8 != 0, 10 x 10 windows, or no room for it).
  * The list is not among the records of dsg_debug_need_lists. */
 int dsg_debug_readout_tiles(dsg_handle h, int32_t B, int32_t *counts, int32_t *tiles, void *stream);
+/* The route the batch size's last forward took through PatchEmbed (forms[0]) and the read-out (forms[1]): 1 the fused kernel
+ * (fused_patch_embed96 / fused_readout96, at patch_size 2 their _p2 forms), 0 the chain of assembly, GEMMs and row passes, -1 no
+ * forward yet.  The fused forms exist for E = 96 at patch_size 1 and 2 (in_chans <= 64, C_adj <= 32) and follow "fused_patch_embed" /
+ * "fused_readout"; debug taps take the read-out's chain; patch_size 4 always runs the chain.  Host only. */
+int dsg_debug_patch_forms(dsg_handle h, int32_t B, int32_t forms[2]);
 
 /* Measurement: runs n_iters eager network forwards on the batch-B workspace (whatever inputs the last call left
  * there) with HIP events bracketing every kernel launch on `stream`, and accumulates per kernel class
@@ -197,6 +202,34 @@ int dsg_debug_readout_f32(int32_t B, int32_t N, int32_t c_adj, const float *x, c
 enum { DSG_HEAD_ADJ = 0, DSG_HEAD_POOL = 1, DSG_HEAD_NODE = 2 };
 int dsg_debug_head_f32(int32_t kind, int32_t B, int32_t N, int32_t E, int32_t c_out, const float *h, const float *W, const float *bias,
                        const uint8_t *flags, float *out, void *stream);
+/* The edge kernels of the patch_size p > 1 forward on their own (csrc/kernels_patch.hip; p in {1, 2, 4} here, N % p == 0, R = N / p).
+ * Token t = ti R + tj covers the pixels (p ti + a, p tj + b); rows "in (token, a, b) order" are m = (b_graph R^2 + t) p^2 + a p + b.
+ * dsg_debug_assemble_patch_f32: out [B R^2, Kp], column (a p + b) Cin + c = channel c (dsg_debug_assemble_f32's order) of the token's
+ *   pixel (a, b), zero from p^2 Cin up to Kp; the node channels are selected by the PIXEL's flag_I && flag_J.
+ * dsg_debug_head_patch_f32: DSG_HEAD_ADJ: h [B N^2, E] in (token, a, b) order -> out [B, c_out, N, N] = valid(I, J) ? h W^T + bias : 0;
+ *   DSG_HEAD_POOL: h likewise -> out [B N, E] = (1/N) sum_J valid(I, J) h[row(I, J)] (W, bias, c_out unused).  Rows of h at pixels
+ *   that are not valid are not read into a result. */
+int dsg_debug_assemble_patch_f32(int32_t B, int32_t N, int32_t p, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kp, const float *adj,
+                                 const float *node, const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags,
+                                 float *out, void *stream);
+int dsg_debug_head_patch_f32(int32_t kind, int32_t B, int32_t N, int32_t p, int32_t E, int32_t c_out, const float *h, const float *W,
+                             const float *bias, const uint8_t *flags, float *out, void *stream);
+/* The fused forms for E = 96, p = 2 (any other p: DSG_ERR_INVALID), weights ALREADY packed as dsg_finalize_weights packs them.
+ * dsg_debug_patch_embed_patch_f32: dsg_debug_patch_embed_f32 on the R x R token grid: the four sub-pixel gathers accumulate into one set of
+ *   accumulators; Wp [4][3][Kps / 8][64][4]: for sub-pixel sub = 2 a + b the fragment order of dsg_debug_patch_embed_f32 applied to
+ *   patch_embed.proj.weight[:, :, a, b] zero-padded to [96, Kps], Kps = 32 | 64 >= in_chans -> x [B R^2, 96].  No run list.
+ * dsg_debug_readout_patch_f32: x [B R^2, 96] -> out_adj [B, c_adj, N, N] = valid(I, J) (F2 gelu(Fa[a, b] LN(x)[t] + fa) + f2) and the pooling
+ *   pool_ext [B N, 256], row (b, I = 2 ti + a) = (s[ti, 0] | s[ti, 1] | f_I cnt_0 / N | f_I cnt_1 / N | 0 ..) with
+ *   s[ti, q] = (1/N) sum_tj f_{2 tj + q} LN(x)[ti, tj] and cnt_q the valid pixel columns of parity q.  Wfp [4][3][12][64][4]: the folded
+ *   Fa[a, b] [96, 96] per sub-pixel in dsg_debug_readout_f32's fragment order; fa, W2p, f2 as there; pool_part: scratch
+ *   [B R][(R + 30) / 32 + 1][2][96].  Rows of x of tokens without a valid pixel are not read into a result. */
+int dsg_debug_patch_embed_patch_f32(int32_t B, int32_t N, int32_t p, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t Kps, const float *adj,
+                                    const float *node, const float *sc_adj, const float *sc_node, const int32_t *has_sc, const uint8_t *flags,
+                                    const float *Wp, const float *bias, const float *gam, const float *bet, const float *aff, int32_t aff_ld,
+                                    int32_t aff_off, int32_t aff_off2, float *x, void *stream);
+int dsg_debug_readout_patch_f32(int32_t B, int32_t N, int32_t p, int32_t c_adj, const float *x, const float *gam, const float *bet, const float *Wfp,
+                                const float *fa, const float *W2p, const float *f2, const uint8_t *flags, float *out_adj, float *pool_part,
+                                float *pool_ext, void *stream);
 /* the one-wave-per-row passes; rows of at most 1536 channels, C % 4 == 0; unused pointers NULL.
  *   DSG_ROW_MOD_STATS        x [B t, C] <- silu(shift + x (1 + scale)) in place, stats [B t, 2] = (mean, rstd) of the new row
  *   DSG_ROW_LN_STATS         stats [B t, 2] = (mean, rstd) of x's rows
