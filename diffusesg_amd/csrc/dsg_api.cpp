@@ -246,6 +246,11 @@ struct dsg_handle_s {
     // preconditioned inputs, F and dL/dF; train_vjp: d_tok | W_img | coef of dsg_precond_vjp; train_ode: dsg_ode_run's states, probe,
     // gradient, sigma rows, step table and control block
     DevBuf train_arena, train_scr, train_io, train_vjp, train_ode;
+    // bf16 mode of the training entries (dsg_train_set_precision): the mode, the bf16 weight planes of the covered linears -- rebuilt by
+    // every entry call in bf16 mode, the parameters may have changed in place -- and the route counts of the last training entry
+    int train_precision = DSG_TRAIN_F32;
+    DevBuf train_lp;
+    std::vector<TLpCount> train_counts;
     int *train_const = nullptr;                                   // device {0, 1}: the "self-conditioning present" switch of launch_assemble
     // dsg_train_bind_params: parameters the training form reads in place (the optimiser's own device tensors) instead of the handle's copies
     std::unordered_map<std::string, const float *> train_params;
@@ -3737,6 +3742,7 @@ struct TrainNet {
     const int *has_sc;                // device 0 / 1: the "self-conditioning present" switch of launch_assemble
     const float *xL;                  // the last block's output, left by train_forward for train_backward
     float *t_mh, *t_m3c, *t_w, *t_mc, *t_mc2, *d_x, *d_y;   // backward scratch
+    TrainLp *lp;                      // bf16 mode of the covered products (train_lp_begin); null: fp32 everywhere
 };
 struct TrainInputs { const float *adj, *node; const uint8_t *flags; const float *c_noise, *sc_adj, *sc_node; };
 // input-gradient mode (dsg_precond_vjp): the backward carries dL/d(activation) only -- no dW / db product, no affine or noise-embedding
@@ -3849,14 +3855,61 @@ static int train_net_build(dsg_handle h, TrainNet &net, int32_t B, const float *
 }
 
 // y [M, out] = x [M, in] W^T + bias (W [out, in]); its backward: dW = dy^T x and db = colsum(dy) when `wg`, dx = dy W when dx is given
-static void lin_fwd(const float *x, const float *W, const float *bias, float *y, size_t M, int in, int out, hipStream_t s) {
-    t_gemm(false, true, x, in, W, in, bias, y, out, (int)M, out, in, false, s);
+// lp: the call site is covered by the bf16 mode (downsample.reduction, upsample.pre_linear / post_linear; the blocks' four through a.lp)
+static void lin_fwd(const float *x, const float *W, const float *bias, float *y, size_t M, int in, int out, hipStream_t s, TrainLp *lp = nullptr) {
+    t_gemm(false, true, x, in, W, in, bias, y, out, (int)M, out, in, false, s, nullptr, nullptr, ACT_NONE, nullptr, nullptr, -1, lp);
 }
 static void lin_bwd(bool wg, const float *x, const float *W, const float *dy, float *dx, float *dW, float *db, size_t M, int in, int out,
-                    hipStream_t s) {
-    if (wg) t_gemm(true, false, dy, out, x, in, nullptr, dW, in, out, in, (int)M, false, s, db);
-    if (dx) t_gemm(false, false, dy, out, W, in, nullptr, dx, in, (int)M, in, out, false, s);
+                    hipStream_t s, TrainLp *lp = nullptr) {
+    if (wg) t_gemm(true, false, dy, out, x, in, nullptr, dW, in, out, in, (int)M, false, s, db, nullptr, ACT_NONE, nullptr, nullptr, -1, lp);
+    if (dx) t_gemm(false, false, dy, out, W, in, nullptr, dx, in, (int)M, in, out, false, s, nullptr, nullptr, ACT_NONE, nullptr, nullptr, -1, lp);
 }
+
+// bf16 mode of a training entry: carves the handle's plane buffer and enqueues the casts of every covered weight whose products the
+// shape rule admits at this batch size -- W [out, in] for y = x W^T, W^T [in, out] for dx = dy W -- in grouped launches, and hands the
+// planes to the covered call sites (net.lp, a.lp).  The parameters are read in place and may have changed since the last call, so
+// nothing is kept between calls.  With the mode off nothing is enqueued and net.lp stays null.  false: out of memory
+static bool train_lp_begin(dsg_handle h, TrainNet &net, TrainLp &lp, hipStream_t s) {
+    h->train_counts.clear();
+    if (h->train_precision != DSG_TRAIN_BF16) return true;
+    struct Job { const float *w; int out, in; };
+    std::vector<Job> jobs;
+    auto add = [&](const float *w, size_t rows, int in, int out) { if (w && t_lp_rule(rows, in, out)) jobs.push_back(Job{w, out, in}); };
+    for (const TrainStage &st : net.stages) {
+        const TrainBlockArgs &a = st.a;
+        const size_t M = (size_t)a.B * a.res * a.res;
+        add(a.W.qkv_w, M, a.C, 3 * a.C); add(a.W.proj_w, M, a.C, a.C); add(a.W.fc1_w, M, a.C, a.hidden); add(a.W.fc2_w, M, a.hidden, a.C);
+    }
+    int res = net.N, C = net.E;
+    for (int l = 0; l < net.L - 1; l++) {   // merging after encoder level l: [M / 4, 4C] -> 2C
+        res /= 2;
+        add(net.mrg_red[l].w, (size_t)net.B * res * res, 4 * C, 2 * C);
+        C *= 2;
+    }
+    for (int i = 1; i < net.L; i++) {       // breakup before up layer i: pre_linear [Mi, D] -> D at the coarse grid, post_linear [4 Mi, D / 4] at the fine one
+        const size_t Mi = (size_t)net.B * res * res; const int D = 2 * C;
+        add(net.up_pre[i].w, Mi, D, D); add(net.up_post[i].w, 4 * Mi, D / 4, D / 4);
+        res *= 2; C /= 2;
+    }
+    std::vector<unsigned short *> at(jobs.size());
+    const bool fits = jobs.empty() || train_carve(h, h->train_lp, s, [&](TArena &A) {   // (no job: every covered product stays fp32, and is counted)
+        for (size_t k = 0; k < jobs.size(); k++) at[k] = reinterpret_cast<unsigned short *>(A.get((size_t)jobs[k].out * jobs[k].in));   // two bf16 planes in out * in floats
+    });
+    if (!fits) return false;
+    TCastGroup g;
+    for (size_t k = 0; k < jobs.size(); k++) {
+        const size_t n = (size_t)jobs[k].out * jobs[k].in;
+        if (lp.planes.count(jobs[k].w)) continue;   // (a tensor bound twice)
+        lp.planes[jobs[k].w] = TLpPlane{at[k], at[k] + n};
+        t_cast_lp_add(g, jobs[k].w, at[k], at[k] + n, jobs[k].out, jobs[k].in);
+        if (g.n == T_CAST_MAX) { t_cast_lp(g, s); g = TCastGroup{}; }
+    }
+    t_cast_lp(g, s);
+    net.lp = &lp;
+    for (TrainStage &st : net.stages) st.a.lp = &lp;
+    return true;
+}
+static void train_lp_end(dsg_handle h, const TrainLp &lp) { h->train_counts = lp.counts; }
 
 // F = network(in) in training form, every activation the backward needs left in the arena; false: a block refused to launch
 static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F, hipStream_t s) {
@@ -3899,7 +3952,7 @@ static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F,
             const size_t M2 = (size_t)B * (res / 2) * (res / 2);
             t_regroup(x, Bf.mcat[l], B, res, C, true, s);
             t_ln_fwd(Bf.mcat[l], net.mrg_norm[l].w, net.mrg_norm[l].b, Bf.mnrm[l], Bf.mstats[l], (int)M2, 4 * C, s);
-            lin_fwd(Bf.mnrm[l], net.mrg_red[l].w, nullptr, Bf.mout[l], M2, 4 * C, 2 * C, s);
+            lin_fwd(Bf.mnrm[l], net.mrg_red[l].w, nullptr, Bf.mout[l], M2, 4 * C, 2 * C, s, net.lp);
             x = Bf.mout[l]; res /= 2; C *= 2;
         }
         skip[l] = x;
@@ -3908,11 +3961,11 @@ static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F,
         if (i > 0) {
             const size_t Mi = (size_t)B * res * res; const int D = 2 * C, Co = D / 4;
             t_concat(x, skip[L - 1 - i], Bf.ucat[i], Mi, C, s);
-            lin_fwd(Bf.ucat[i], net.up_pre[i].w, nullptr, Bf.uy[i], Mi, D, D, s);
+            lin_fwd(Bf.ucat[i], net.up_pre[i].w, nullptr, Bf.uy[i], Mi, D, D, s, net.lp);
             t_ln_fwd(Bf.uy[i], net.up_norm[i].w, net.up_norm[i].b, Bf.un[i], Bf.ustats[i], (int)Mi, D, s);
             t_regroup(Bf.un[i], Bf.usc[i], B, 2 * res, Co, false, s);   // scatter: fine [4 Mi, Co] <- coarse [Mi, 4 Co]
             t_ln_fwd(Bf.usc[i], net.up_pn[i].w, net.up_pn[i].b, Bf.upn[i], Bf.upstats[i], (int)(4 * Mi), Co, s);
-            lin_fwd(Bf.upn[i], net.up_post[i].w, nullptr, Bf.uout[i], 4 * Mi, Co, Co, s);
+            lin_fwd(Bf.upn[i], net.up_post[i].w, nullptr, Bf.uout[i], 4 * Mi, Co, Co, s, net.lp);
             x = Bf.uout[i]; res *= 2; C /= 2;
         }
         run_blocks(L + i);
@@ -3989,11 +4042,11 @@ static bool train_backward(TrainNet &net, TrainBackward mode, const uint8_t *fla
             // here res, C are the FINE values (after the breakup); the coarse input had res/2, 2C per source
             const int rc = res / 2, Cc = 2 * C; const size_t Mi = (size_t)B * rc * rc; const int D = 2 * Cc, Co = D / 4;
             float *d_upn = t_mh, *d_usc = t_m3c, *d_un = t_w, *d_uy = t_mh, *d_cat = t_m3c;
-            lin_bwd(wg, Bf.upn[i], net.up_post[i].w, dcur, d_upn, net.up_post[i].dw, nullptr, 4 * Mi, Co, Co, s);
+            lin_bwd(wg, Bf.upn[i], net.up_post[i].w, dcur, d_upn, net.up_post[i].dw, nullptr, 4 * Mi, Co, Co, s, net.lp);
             t_ln_bwd(Bf.usc[i], net.up_pn[i].w, Bf.upstats[i], d_upn, nullptr, d_usc, net.up_pn[i].dw, net.up_pn[i].db, (int)(4 * Mi), Co, s);
             t_regroup(d_usc, d_un, B, res, Co, true, s);   // transpose of the scatter = gather
             t_ln_bwd(Bf.uy[i], net.up_norm[i].w, Bf.ustats[i], d_un, nullptr, d_uy, net.up_norm[i].dw, net.up_norm[i].db, (int)Mi, D, s);
-            lin_bwd(wg, Bf.ucat[i], net.up_pre[i].w, d_uy, d_cat, net.up_pre[i].dw, nullptr, Mi, D, D, s);
+            lin_bwd(wg, Bf.ucat[i], net.up_pre[i].w, d_uy, d_cat, net.up_pre[i].dw, nullptr, Mi, D, D, s, net.lp);
             t_split(d_cat, dnext, Bf.d_skip[L - 1 - i], Mi, Cc, s);
             std::swap(dcur, dnext);
             res = rc; C = Cc;
@@ -4005,7 +4058,7 @@ static bool train_backward(TrainNet &net, TrainBackward mode, const uint8_t *fla
         if (l < L - 1) {
             const int rf = res * 2, Cf = C / 2; const size_t M2 = (size_t)B * res * res;
             float *d_nrm = t_mh, *d_cat = t_m3c;
-            lin_bwd(wg, Bf.mnrm[l], net.mrg_red[l].w, dcur, d_nrm, net.mrg_red[l].dw, nullptr, M2, 4 * Cf, 2 * Cf, s);
+            lin_bwd(wg, Bf.mnrm[l], net.mrg_red[l].w, dcur, d_nrm, net.mrg_red[l].dw, nullptr, M2, 4 * Cf, 2 * Cf, s, net.lp);
             t_ln_bwd(Bf.mcat[l], net.mrg_norm[l].w, Bf.mstats[l], d_nrm, nullptr, d_cat, net.mrg_norm[l].dw, net.mrg_norm[l].db, (int)M2, 4 * Cf, s);
             t_regroup(d_cat, dnext, B, rf, Cf, false, s);   // transpose of the gather = scatter back to the fine grid
             std::swap(dcur, dnext);
@@ -4082,8 +4135,11 @@ int dsg_train_grads(dsg_handle h, int32_t B, const float *in_adj, const float *i
     TrainNet net{};
     const int rc = train_net_build(h, net, B, sc_adj, sc_node, bwd, n_params, names, grad_params, s);
     if (rc != DSG_OK) return rc;
+    TrainLp lp;
+    if (!train_lp_begin(h, net, lp, s)) return fail(h, DSG_ERR_HIP, "out of memory");
     bool ok = train_forward(net, TrainInputs{in_adj, in_node, flags, c_noise, sc_adj, sc_node}, StatePtrs{out_F_adj, out_F_node}, s);
     if (ok && bwd) ok = train_backward(net, TRAIN_WEIGHT_GRADS, flags, CStatePtrs{grad_F_adj, grad_F_node}, nullptr, s);
+    train_lp_end(h, lp);
     return train_finish(h, ok, s);
 }
 
@@ -4120,6 +4176,8 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
     TrainNet net{};
     const int rc = train_net_build(h, net, B, sc_adj, sc_node, want_grads, n_params, names, grad_params, s);
     if (rc != DSG_OK) return rc;
+    TrainLp lp;
+    if (!train_lp_begin(h, net, lp, s)) return fail(h, DSG_ERR_HIP, "out of memory");
     bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, sc_adj, sc_node}, StatePtrs{io.F_a, io.F_n}, s);
     if (ok) {
         // D = mask(c_skip x + c_out F) (precond.py:101-104); per-sample losses; with gradients: dL/dD and dL/dF = c_out dL/dD
@@ -4132,6 +4190,7 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
         ok = hipGetLastError() == hipSuccess;
     }
     if (ok && want_grads) ok = train_backward(net, TRAIN_WEIGHT_GRADS, flags, CStatePtrs{io.dF_a, io.dF_n}, nullptr, s);
+    train_lp_end(h, lp);
     return train_finish(h, ok, s);
 }
 
@@ -4148,7 +4207,10 @@ int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const f
     TrainNet net{};
     int rc = train_net_build(h, net, B, nullptr, nullptr, false, 0, nullptr, nullptr, s);
     if (rc != DSG_OK) return rc;
+    TrainLp lp;
+    if (!train_lp_begin(h, net, lp, s)) return fail(h, DSG_ERR_HIP, "out of memory");
     const bool ok = train_forward(net, TrainInputs{io.in_a, io.in_n, flags, io.cn, nullptr, nullptr}, StatePtrs{io.F_a, io.F_n}, s);
+    train_lp_end(h, lp);
     if ((rc = train_finish(h, ok, s)) != DSG_OK) return rc;
     launch_precond_out(CStatePtrs{noisy_adj, noisy_node}, CStatePtrs{io.F_a, io.F_n}, sigmas, flags, StatePtrs{out_sc_adj, out_sc_node}, d, s);
     HIP_TRY(h, hipGetLastError());
@@ -4356,6 +4418,29 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
     HIP_TRY(h, hipMemcpyAsync(out_node, x.node, sizeof(float) * nn, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
+}
+
+int dsg_train_set_precision(dsg_handle h, int32_t mode) {
+    if (!h) return DSG_ERR_INVALID;
+    if (mode != DSG_TRAIN_F32 && mode != DSG_TRAIN_BF16) return fail(h, DSG_ERR_INVALID, "training precision %d (DSG_TRAIN_F32 = 0 or DSG_TRAIN_BF16 = 1)", mode);
+    h->train_precision = mode;
+    return DSG_OK;
+}
+
+int dsg_train_get_precision(dsg_handle h, int32_t *mode) {
+    if (!h || !mode) return fail(h, DSG_ERR_INVALID, "null argument");
+    *mode = h->train_precision;
+    return DSG_OK;
+}
+
+int32_t dsg_debug_train_routes(dsg_handle h, int32_t *out, int32_t cap) {
+    if (!h || cap < 0 || (cap > 0 && !out)) return DSG_ERR_INVALID;
+    const int32_t n = (int32_t)h->train_counts.size();
+    for (int32_t k = 0; k < n && k < cap; k++) {
+        const TLpCount &c = h->train_counts[k];
+        out[4 * k] = c.rows; out[4 * k + 1] = c.cls; out[4 * k + 2] = c.n_bf16; out[4 * k + 3] = c.n_f32;
+    }
+    return n;
 }
 
 int dsg_train_bind_params(dsg_handle h, int32_t n_params, const char *const *names, const float *const *params) {

@@ -403,6 +403,44 @@ int dsg_debug_t_gemm(int32_t ta, int32_t tb, const float *A, int32_t lda, const 
     return debug_t_finish(true, s);
 }
 
+int dsg_debug_t_cast_lp(const float *W, int32_t R, int32_t Cc, uint16_t *out_nk, uint16_t *out_kn, void *stream) {
+    if (!W || R < 1 || Cc < 1 || (!out_nk && !out_kn)) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    TCastGroup g;
+    t_cast_lp_add(g, W, out_nk, out_kn, R, Cc);
+    t_cast_lp(g, s);
+    return debug_t_finish(true, s);
+}
+
+int dsg_debug_t_gemm_lp(int32_t ta, int32_t tb, const float *A, int32_t lda, const float *B, int32_t ldb, const float *bias, float *C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t accumulate, float *a_colsum, const float *res, int32_t act,
+                        float *c2, int32_t any_rows, int32_t *route_out, void *stream) {
+    if (route_out) { route_out[0] = 0; route_out[1] = 0; }
+    if (!A || !B || !C || M < 1 || N < 1 || K < 1 || lda < 1 || ldb < 1 || ldc < N) return DSG_ERR_INVALID;
+    if (act != ACT_NONE && act != ACT_GELU_KEEP && act != ACT_DGELU) return DSG_ERR_INVALID;
+    if ((act == ACT_GELU_KEEP && !c2) || (act == ACT_DGELU && !res) || (a_colsum && !(ta && !tb))) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    TrainLp lp;
+    lp.any_rows = any_rows != 0; lp.only = true;
+    void *planes = nullptr;
+    // the weight planes of an activation-side product whose weight is contiguous (anything else the route refuses below)
+    if (!ta && ldb == (tb ? K : N) && (size_t)N * K <= ((size_t)32 << 20)) {
+        const size_t n = (size_t)N * K;
+        if (hipMalloc(&planes, 2 * n * sizeof(uint16_t)) != hipSuccess) return DSG_ERR_HIP;
+        uint16_t *nk = static_cast<uint16_t *>(planes), *kn = nk + n;
+        TCastGroup g;
+        t_cast_lp_add(g, B, nk, kn, tb ? N : K, tb ? K : N);   // B as stored: [N, K] (tb) or [K, N]
+        t_cast_lp(g, s);
+        lp.planes[B] = TLpPlane{nk, kn};
+    }
+    int route[2] = {0, 0};
+    t_gemm(ta != 0, tb != 0, A, lda, B, ldb, bias, C, ldc, M, N, K, accumulate != 0, s, a_colsum, res, act, c2, route, 0, &lp);
+    if (route_out) { route_out[0] = route[0]; route_out[1] = route[1]; }
+    const int rc = debug_t_finish(route[0] != 0, s);
+    if (planes) (void)hipFree(planes);
+    return rc;
+}
+
 int dsg_debug_t_attn(int32_t bwd, int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const float *qkv, const float *table,
                      float *out, const float *d_out, float *d_qkv, float *d_table, int32_t force_plain, void *stream) {
     if (B < 1 || ws < 1 || res < ws || res % ws != 0 || ws * ws > 128 || shift < 0 || shift >= ws || heads < 1 || !qkv || !table)

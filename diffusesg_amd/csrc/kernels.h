@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <unordered_map>
+#include <vector>
 
 namespace dsg {
 
@@ -480,6 +482,8 @@ struct TrainBlockArgs {
     // backward without the weight-gradient products (dW, db, d_gamma, d_beta, d_table, and the affine linear's own backward): only
     // grad_in is produced, G is not touched (input gradients, dsg_precond_vjp)
     bool no_wgrad = false;
+    // bf16 mode of the covered products (qkv, proj, fc1, fc2: y, dx and dW); null: fp32.  See TrainLp below
+    struct TrainLp *lp = nullptr;
 };
 // a group of small products in one launch (t_gemm_grouped / t_colsum_grouped): C = op(A) op(B) (+ bias)
 struct TGemmProb { const float *A, *B, *bias; float *C; int lda, ldb, ldc, M, N, K; };
@@ -494,10 +498,45 @@ bool train_block_backward(const TrainBlockArgs &a, hipStream_t s);   // backward
 // a_colsum (weight-gradient products, ta && !tb): also out[m] = sum_k A[k][m], the bias gradient that goes with dW = dy^T x
 void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K,
             bool accumulate, hipStream_t s, float *a_colsum = nullptr, const float *res = nullptr, int act = ACT_NONE, float *c2 = nullptr,
-            int *route = nullptr, int force_plain = -1);
+            int *route = nullptr, int force_plain = -1, struct TrainLp *lp = nullptr);
 // res: C = res + product (same pitch as C); act = ACT_GELU_KEEP: c2 = product + bias, C = GELU(c2); act = ACT_DGELU: C = product * GELU'(res)
 // route (test hook, host): route[0] = the path taken -- 1 the sampling GEMM (launch_gemm), 2 gemm_tn_f32_kernel + reduce, 3 the plain
 // kernel, 4 the plain kernel with split-K, 0 refused --, route[1] = its slice count S; force_plain >= 0 replaces DSG_TRAIN_PLAIN_GEMM
+// ---- bf16 mode of the training products (train_kernels_lp.hip; dsg_train_set_precision) ----
+// A call site that is covered passes the entry's TrainLp to t_gemm.  The product then runs with both operands rounded to bf16 (RNE) on
+// v_mfma_f32_32x32x16_bf16, fp32 accumulation and an fp32 result, wherever t_lp_rule holds and -- for y = x W^T and dx = dy W -- the
+// weight's bf16 plane is in `planes`; everywhere else it silently takes the fp32 route it has without the mode.
+//   y  (cls 0, !ta &&  tb): launch_gemm_lp on plane nk = bf16 of W [out, in]
+//   dx (cls 1, !ta && !tb): launch_gemm_lp on plane kn = bf16 of W^T [in, out]
+//   dW (cls 2,  ta && !tb): gemm_tn_bf16_kernel + t_splitk_reduce; a_colsum from the unrounded fp32 values
+// The fused activations (ACT_GELU_KEEP, ACT_DGELU) are finished by t_gelu's elementwise pass.
+struct TLpPlane { const void *nk = nullptr, *kn = nullptr; };
+struct TLpCount { int rows, cls, n_bf16, n_f32; };   // products of class cls over `rows` tokens that took the bf16 / the fp32 route
+struct TrainLp {
+    std::unordered_map<const float *, TLpPlane> planes;   // by fp32 weight pointer
+    std::vector<TLpCount> counts;
+    bool any_rows = false;   // test hook: waive the 512-row threshold (the kernels take any row count)
+    bool only = false;       // test hook: a product the bf16 route does not take is refused (nothing launched) instead of run in fp32
+    void count(int rows, int cls, bool lp) {
+        for (TLpCount &c : counts) if (c.rows == rows && c.cls == cls) { (lp ? c.n_bf16 : c.n_f32)++; return; }
+        counts.push_back(TLpCount{rows, cls, lp ? 1 : 0, lp ? 0 : 1});
+    }
+};
+// the shape rule on top of the call sites: what t_gemm's MFMA form takes today -- 512 token rows, both channel extents multiples of 32
+inline bool t_lp_rule(size_t rows, int c0, int c1) { return rows >= 512 && c0 > 0 && c1 > 0 && c0 % 32 == 0 && c1 % 32 == 0; }
+// false: the bf16 route does not take this product (nothing launched).  route as t_gemm's: 5 launch_gemm_lp, 6 gemm_tn_bf16_kernel + reduce
+bool t_gemm_lp(TrainLp &lp, bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N,
+               int K, bool accumulate, hipStream_t s, float *a_colsum, const float *res, int act, float *c2, int *route);
+// up to T_CAST_MAX weights W [R, Cc] (contiguous fp32) -> bf16 planes nk [R, Cc] and kn [Cc, R] (either may be null), RNE, one launch
+struct TCastJob { const float *src; void *nk, *kn; int R, Cc, tile0; };   // tile0: the job's first 32 x 32 tile in the launch's grid
+constexpr int T_CAST_MAX = 64;
+struct TCastGroup { TCastJob j[T_CAST_MAX]; int n = 0, tiles = 0; };
+void t_cast_lp_add(TCastGroup &g, const float *src, void *nk, void *kn, int R, int Cc);   // (the caller flushes a full group)
+void t_cast_lp(const TCastGroup &g, hipStream_t s);
+// pieces of train_kernels.hip that the bf16 route shares
+float *t_scratch_sk(hipStream_t s, size_t need);   // the stream's split-K scratch grown to `need` floats; null: out of memory (marked)
+void t_scratch_mark_failed(hipStream_t s);
+void t_splitk_reduce(const float *part, float *C, int ldc, int M, int N, int S, bool accumulate, const float *cs_part, float *cs_out, hipStream_t s);
 // scratch of the training kernels is kept per stream (train_kernels.hip); a failed allocation is reported here, once
 bool t_scratch_failed(hipStream_t s, bool clear);
 void t_scratch_release();

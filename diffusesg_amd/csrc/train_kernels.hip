@@ -54,6 +54,11 @@ bool t_scratch_failed(hipStream_t s, bool clear) {
     if (clear) ts.failed = false;
     return f;
 }
+float *t_scratch_sk(hipStream_t s, size_t need) {
+    TScratch &ts = t_scratch(s);
+    return t_scratch_get(s, ts.sk, ts.sk_cap, need, ts);
+}
+void t_scratch_mark_failed(hipStream_t s) { t_scratch(s).failed = true; }
 void t_scratch_release() {   // dsg_destroy of the last handle / tests
     std::lock_guard<std::mutex> lk(g_ts_mutex);
     for (auto &kv : g_ts) { (void)hipFree(kv.second.sk); (void)hipFree(kv.second.wt); (void)hipFree(kv.second.cs); (void)hipFree(kv.second.opt); }
@@ -188,7 +193,7 @@ __global__ __launch_bounds__(256) void t_splitk_reduce_kernel(const float *part,
         else { const size_t m = i / N, n = i % N; C[m * ldc + n] = (accumulate ? C[m * ldc + n] : 0.f) + t; }
     }
 }
-static void t_splitk_reduce(const float *part, float *C, int ldc, int M, int N, int S, bool accumulate, const float *cs_part, float *cs_out, hipStream_t s) {
+void t_splitk_reduce(const float *part, float *C, int ldc, int M, int N, int S, bool accumulate, const float *cs_part, float *cs_out, hipStream_t s) {
     const size_t mn = (size_t)M * N;
     // slice lanes so that the launch has >= ~1024 blocks' worth of threads where the output is small and the slices are many
     const int zl = (S >= 64 && mn < ((size_t)1 << 17)) ? 16 : ((S >= 16 && mn < ((size_t)1 << 19)) ? 4 : 1);
@@ -322,12 +327,18 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f32_kernel(const float *__rest
 }
 
 void t_gemm(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K,
-            bool accumulate, hipStream_t s, float *a_colsum, const float *res, int act, float *c2, int *route, int force_plain) {
+            bool accumulate, hipStream_t s, float *a_colsum, const float *res, int act, float *c2, int *route, int force_plain, TrainLp *lp) {
     if (route) { route[0] = 0; route[1] = 0; }
     // res (activation-side products only): C = res + product, res a tensor of C's shape and pitch -- the MFMA kernel reads it in its
     // epilogue; the fallbacks copy it into C first and accumulate
     if (act == ACT_NONE && res && res == C) { res = nullptr; accumulate = true; }
     TScratch &ts = t_scratch(s);
+    // a covered call site in bf16 mode (kernels.h: TrainLp): the bf16 route where it takes the product, otherwise the fp32 routes below
+    if (lp) {
+        const bool took = t_gemm_lp(*lp, ta, tb, A, lda, B, ldb, bias, C, ldc, M, N, K, accumulate, s, a_colsum, res, act, c2, route);
+        lp->count(ta ? K : M, ta ? 2 : (tb ? 0 : 1), took);
+        if (took || lp->only) return;
+    }
     // the fallbacks below form the plain product; the fused activation forms are finished by an elementwise pass afterwards
     struct ActAfter { int act; const float *res; float *C, *c2; size_t n; hipStream_t s; bool done;
         ~ActAfter() {
@@ -1146,12 +1157,12 @@ bool train_block(const TrainBlockArgs &a, hipStream_t s) {
     if (!a.aff_grouped)   // params = affine(emb); the whole-network step computes all blocks' rows in one grouped launch up front
         t_gemm(false, true, a.emb, NOISE_EMB, a.W.aff_w, NOISE_EMB, a.W.aff_b, a.aff, 2 * C, B, 2 * C, NOISE_EMB, false, s);
     t_ln_fwd_launch(a.x_in, a.aff, a.x_mod, a.W.n1_w, a.W.n1_b, a.xn1, a.stats1, M, C, T, s);   // x_mod = modulate(x_in), xn1 = LayerNorm-1(x_mod): one row pass
-    t_gemm(false, true, a.xn1, C, a.W.qkv_w, C, a.W.qkv_b, a.qkv, 3 * C, M, 3 * C, C, false, s);
+    t_gemm(false, true, a.xn1, C, a.W.qkv_w, C, a.W.qkv_b, a.qkv, 3 * C, M, 3 * C, C, false, s, nullptr, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);
     if (!t_attn_launch(false, a.qkv, a.W.rpb, a.att, nullptr, nullptr, nullptr, B, g, s)) return false;
-    t_gemm(false, true, a.att, C, a.W.proj_w, C, a.W.proj_b, a.x1, C, M, C, C, false, s, nullptr, a.x_mod);                  // x1 = shortcut + proj(att)
+    t_gemm(false, true, a.att, C, a.W.proj_w, C, a.W.proj_b, a.x1, C, M, C, C, false, s, nullptr, a.x_mod, ACT_NONE, nullptr, nullptr, -1, a.lp);                  // x1 = shortcut + proj(att)
     t_ln_fwd_launch(a.x1, nullptr, nullptr, a.W.n2_w, a.W.n2_b, a.xn2, a.stats2, M, C, T, s);
-    t_gemm(false, true, a.xn2, C, a.W.fc1_w, C, a.W.fc1_b, a.hid, H, M, H, C, false, s, nullptr, nullptr, ACT_GELU_KEEP, a.pre);   // pre = fc1(xn2), hid = GELU(pre)
-    t_gemm(false, true, a.hid, H, a.W.fc2_w, H, a.W.fc2_b, a.x_out, C, M, C, H, false, s, nullptr, a.x1);                    // x_out = x1 + fc2(gelu(fc1(ln2)))
+    t_gemm(false, true, a.xn2, C, a.W.fc1_w, C, a.W.fc1_b, a.hid, H, M, H, C, false, s, nullptr, nullptr, ACT_GELU_KEEP, a.pre, nullptr, -1, a.lp);   // pre = fc1(xn2), hid = GELU(pre)
+    t_gemm(false, true, a.hid, H, a.W.fc2_w, H, a.W.fc2_b, a.x_out, C, M, C, H, false, s, nullptr, a.x1, ACT_NONE, nullptr, nullptr, -1, a.lp);                    // x_out = x1 + fc2(gelu(fc1(ln2)))
     if (!a.grad_out) return hipGetLastError() == hipSuccess;
     return train_block_backward(a, s);
 }
@@ -1164,18 +1175,18 @@ bool train_block_backward(const TrainBlockArgs &a, hipStream_t s) {
     const float *dY = a.grad_out;
     const bool wg = !a.no_wgrad;   // false: only the activation-side chain (input gradients); a.G is not touched
     // MLP: x_out = x1 + hid W2^T + b2
-    if (wg) t_gemm(true, false, dY, C, a.hid, H, nullptr, a.G.fc2_w, H, C, H, M, false, s, a.G.fc2_b);  // dW2 [C,H] = dY^T hid, db2 = colsum(dY)
-    t_gemm(false, false, dY, C, a.W.fc2_w, H, nullptr, a.t_mh, H, M, H, C, false, s, nullptr, a.pre, ACT_DGELU);   // d_pre = (dY W2) GELU'(pre)
-    if (wg) t_gemm(true, false, a.t_mh, H, a.xn2, C, nullptr, a.G.fc1_w, C, H, C, M, false, s, a.G.fc1_b);   // dW1 [H,C] = d_pre^T xn2, db1
-    t_gemm(false, false, a.t_mh, H, a.W.fc1_w, C, nullptr, a.t_mc, C, M, C, H, false, s);       // d_xn2 = d_pre W1
+    if (wg) t_gemm(true, false, dY, C, a.hid, H, nullptr, a.G.fc2_w, H, C, H, M, false, s, a.G.fc2_b, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);  // dW2 [C,H] = dY^T hid, db2 = colsum(dY)
+    t_gemm(false, false, dY, C, a.W.fc2_w, H, nullptr, a.t_mh, H, M, H, C, false, s, nullptr, a.pre, ACT_DGELU, nullptr, nullptr, -1, a.lp);   // d_pre = (dY W2) GELU'(pre)
+    if (wg) t_gemm(true, false, a.t_mh, H, a.xn2, C, nullptr, a.G.fc1_w, C, H, C, M, false, s, a.G.fc1_b, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);   // dW1 [H,C] = d_pre^T xn2, db1
+    t_gemm(false, false, a.t_mh, H, a.W.fc1_w, C, nullptr, a.t_mc, C, M, C, H, false, s, nullptr, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);       // d_xn2 = d_pre W1
     t_ln_bwd(a.x1, a.W.n2_w, a.stats2, a.t_mc, dY, a.d_x1, wg ? a.G.n2_w : nullptr, wg ? a.G.n2_b : nullptr, M, C, s);   // d_x1 = dY (residual branch) + LN2 backward; d_gamma2, d_beta2
     // attention half: x1 = x_mod + att Wp^T + bp
-    if (wg) t_gemm(true, false, a.d_x1, C, a.att, C, nullptr, a.G.proj_w, C, C, C, M, false, s, a.G.proj_b);
-    t_gemm(false, false, a.d_x1, C, a.W.proj_w, C, nullptr, a.t_mc, C, M, C, C, false, s);      // d_att
+    if (wg) t_gemm(true, false, a.d_x1, C, a.att, C, nullptr, a.G.proj_w, C, C, C, M, false, s, a.G.proj_b, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);
+    t_gemm(false, false, a.d_x1, C, a.W.proj_w, C, nullptr, a.t_mc, C, M, C, C, false, s, nullptr, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);      // d_att
     if (wg && hipMemsetAsync(a.G.rpb, 0, sizeof(float) * (size_t)(2 * a.ws - 1) * (2 * a.ws - 1) * a.heads, s) != hipSuccess) return false;
     if (!t_attn_launch(true, a.qkv, a.W.rpb, nullptr, a.t_mc, a.t_m3c, wg ? a.G.rpb : nullptr, B, g, s)) return false;   // d_qkv, d_table
-    if (wg) t_gemm(true, false, a.t_m3c, 3 * C, a.xn1, C, nullptr, a.G.qkv_w, C, 3 * C, C, M, false, s, a.G.qkv_b);
-    t_gemm(false, false, a.t_m3c, 3 * C, a.W.qkv_w, C, nullptr, a.t_mc, C, M, C, 3 * C, false, s);   // d_xn1
+    if (wg) t_gemm(true, false, a.t_m3c, 3 * C, a.xn1, C, nullptr, a.G.qkv_w, C, 3 * C, C, M, false, s, a.G.qkv_b, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);
+    t_gemm(false, false, a.t_m3c, 3 * C, a.W.qkv_w, C, nullptr, a.t_mc, C, M, C, 3 * C, false, s, nullptr, nullptr, ACT_NONE, nullptr, nullptr, -1, a.lp);   // d_xn1
     // d_xmod = d_x1 (shortcut) + LN1 backward
     t_ln_bwd(a.x_mod, a.W.n1_w, a.stats1, a.t_mc, a.d_x1, a.d_x1, wg ? a.G.n1_w : nullptr, wg ? a.G.n1_b : nullptr, M, C, s);
     // modulate: x_mod = silu(shift + x (1 + scale)); params = emb Wa^T + ba

@@ -20,8 +20,10 @@ EXPORTS = [
     "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd", "dsg_sgstat_triplet_counts", "dsg_sgstat_layout",
     "dsg_sgstat_f1_rowstats", "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
     "dsg_sample_seeded", "dsg_gen_noise_seeded", "dsg_precond_vjp", "dsg_ode_run", "dsg_ode_evals", "dsg_guide_coef", "dsg_sample_guided",
-    "dsg_sample_guided_rel", "dsg_option_info", "dsg_create_patch",
+    "dsg_sample_guided_rel", "dsg_option_info", "dsg_create_patch", "dsg_train_set_precision", "dsg_train_get_precision",
 ]
+
+TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}   # DSG_TRAIN_F32 / DSG_TRAIN_BF16 of include/dsg.h
 
 # dsg_grad_fn of include/dsg.h (dsg_precond_vjp): int fn(void *user, const float *D_adj, const float *D_node, float *g_adj, float *g_node)
 GRAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -98,6 +100,7 @@ DEBUG_EXPORTS = [
     "dsg_debug_window_harvest_f32", "dsg_debug_graph_dot", "dsg_debug_poison", "dsg_debug_box_guide", "dsg_debug_box_guide_rel",
     "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp", "dsg_debug_patch_forms",
     "dsg_debug_assemble_patch_f32", "dsg_debug_head_patch_f32", "dsg_debug_patch_embed_patch_f32", "dsg_debug_readout_patch_f32",
+    "dsg_debug_t_gemm_lp", "dsg_debug_t_cast_lp", "dsg_debug_train_routes",
 ]
 
 
@@ -182,6 +185,9 @@ def _declare_debug(L: C.CDLL) -> None:
     L.dsg_debug_window_broadcast_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32] + [vp] * 4 + [i32, i64] + [i32] * 6 + [vp, vp]
     L.dsg_debug_window_harvest_f32.argtypes = [i32] * 3 + [vp] * 3 + [i32, vp, i64] + [i32] * 3 + [vp]
     L.dsg_debug_t_gemm.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.POINTER(i32), vp]
+    L.dsg_debug_t_gemm_lp.argtypes = L.dsg_debug_t_gemm.argtypes
+    L.dsg_debug_t_cast_lp.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.dsg_debug_train_routes.argtypes = [vp, vp, i32]
     L.dsg_debug_t_attn.argtypes = [i32] * 6 + [vp] * 6 + [i32, vp]
     L.dsg_debug_t_ln.argtypes = [i32] * 4 + [vp] * 13
     L.dsg_debug_t_modulate.argtypes = [i32] * 4 + [vp] * 6
@@ -285,6 +291,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_ode_evals.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgOdeCfg), vp, vp, i32]
     L.dsg_ode_evals.restype = i32
     L.dsg_train_bind_params.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+    L.dsg_train_set_precision.argtypes = [vp, i32]
+    L.dsg_train_get_precision.argtypes = [vp, C.POINTER(i32)]
     L.dsg_adam_step.argtypes = [i32] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int64), i32] + [C.c_float] * 6 + [C.POINTER(C.c_float), vp]
     L.dsg_ema_update.argtypes = [i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, vp]
     L.dsg_noise_embed.argtypes = [vp, i32, vp, vp, vp, vp, vp]
@@ -396,6 +404,26 @@ class Handle:
         v = C.c_int32(0)
         self.check(self.L.dsg_get_option(self._h, name.encode(), C.byref(v)), f"dsg_get_option({name})")
         return int(v.value)
+
+    def set_train_precision(self, precision: str):
+        """Precision of the training entries' large products (dsg_train_set_precision): "fp32" (default) or "bf16"."""
+        if precision not in TRAIN_PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(TRAIN_PRECISIONS)}, not {precision!r}")
+        self.check(self.L.dsg_train_set_precision(self._h, TRAIN_PRECISIONS[precision]), "dsg_train_set_precision")
+
+    def get_train_precision(self) -> str:
+        v = C.c_int32(0)
+        self.check(self.L.dsg_train_get_precision(self._h, C.byref(v)), "dsg_train_get_precision")
+        return {m: name for name, m in TRAIN_PRECISIONS.items()}[int(v.value)]
+
+    def train_routes(self):
+        """Test only (dsg_debug_train_routes): {(token rows, class): (products on the bf16 route, on an fp32 route)} of the covered
+        products of the last training entry; class 0 y = x W^T, 1 dx = dy W, 2 dW = dy^T x.  Empty with the mode off."""
+        buf = (C.c_int32 * (4 * 64))()
+        n = self.L.dsg_debug_train_routes(self._h, buf, 64)
+        if n < 0:
+            raise DsgError("dsg_debug_train_routes failed")
+        return {(buf[4 * k], buf[4 * k + 1]): (buf[4 * k + 2], buf[4 * k + 3]) for k in range(min(n, 64))}
 
     def poison(self, B: int, pattern: int, seed: int = 0, stream=None):
         """Test only (dsg_debug_poison): every scratch buffer of the handle and of batch B's workspace becomes `pattern` -- 1 zeros,

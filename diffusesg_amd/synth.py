@@ -308,6 +308,34 @@ def train_case(name: str = "tiny", B: int = 4, seed: int = 7):
     return cfg, flags, clean_adj, clean_node, rnd, eps_adj, eps_node, coin
 
 
+# ---- mixed-precision training fixtures (tests/golden/train_bf16.npz, tools/gen_train_bf16_golden.py): name -> (config, B, valid nodes
+# per graph, the self-conditioning coin).  The batch puts level 0 -- and in `small_b8` level 1 too -- at or above the 512 token rows from
+# which the bf16 mode takes a product (small: 2048 / 512 rows; tiny: 512 / 128, the mixed case); coin 0.3 fires, 0.7 does not.
+TRAIN_BF16_CASES = {"small_b8": ("small", 8, [16, 9, 12, 5, 14, 7, 16, 3], 0.3),
+                    "tiny_b8": ("tiny", 8, [8, 5, 3, 6, 7, 4, 8, 2], 0.7)}
+TRAIN_BF16_MAX_SAMPLE = 256      # stored gradient elements per tensor (every stride-th, train_backward.npz's format)
+
+
+def train_bf16_case(name: str, seed: int = 11):
+    """train_case's tuple for a case of TRAIN_BF16_CASES, plus flip [2]: the +-1 patterns (adjacency, node) of the last-bit input
+    perturbation the fixture's rounding-sensitivity run multiplies the noisy inputs by (1 + 2^-22 u)."""
+    cfg_name, B, valid, coin = TRAIN_BF16_CASES[name]
+    cfg = CONFIGS[cfg_name]()
+    n = cfg.max_node_num
+    flags = W.synth_flags(B, n, valid)
+    tag = f"trnlp/{name}"
+    clean_adj = W.mask_adj(np.sign(W.normal(seed, f"{tag}/adj", (B, cfg.c_adj, n, n))).astype(np.float32), flags)
+    node = np.sign(W.normal(seed, f"{tag}/node", (B, n, cfg.c_node))).astype(np.float32)
+    node[..., -4:] = (2.0 * W.uniform01(seed, f"{tag}/bbox", B * n * 4) - 1.0).astype(np.float32).reshape(B, n, 4) * 0.8
+    clean_node = W.mask_node(node, flags)
+    rnd = W.normal(seed, f"{tag}/rnd", (B,))
+    eps_adj = W.normal(seed, f"{tag}/eps_adj", (B, cfg.c_adj, n, n))
+    eps_node = W.normal(seed, f"{tag}/eps_node", (B, n, cfg.c_node))
+    u_adj = np.where(W.normal(seed, f"{tag}/flip_adj", (B, cfg.c_adj, n, n)) < 0, -1.0, 1.0).astype(np.float32)
+    u_node = np.where(W.normal(seed, f"{tag}/flip_node", (B, n, cfg.c_node)) < 0, -1.0, 1.0).astype(np.float32)
+    return cfg, flags, clean_adj, clean_node, rnd, eps_adj, eps_node, coin, (u_adj, u_node)
+
+
 IOU_TYPES = ("iou", "giou", "giou_squared", "diou", "ciou")   # trainer_node_adj.py:138-153
 
 

@@ -17,6 +17,7 @@ v_mfma_f32_32x32x2_f32); LayerNorm / modulate / optimiser are HBM-bound row and 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import torch
@@ -28,6 +29,22 @@ P_MEAN, P_STD, SIGMA_DATA = -1.2, 1.2, 0.5   # get_edm_params(), objectives/edm.
 
 def _p(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+@contextlib.contextmanager
+def _train_precision(h, precision):
+    """the handle's training precision ("fp32" | "bf16": lib.Handle.set_train_precision) for the duration of a call, then what it was"""
+    if precision not in _lib.TRAIN_PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(_lib.TRAIN_PRECISIONS)}, not {precision!r}")
+    before = h.get_train_precision()
+    if before == precision:
+        yield
+        return
+    h.set_train_precision(precision)
+    try:
+        yield
+    finally:
+        h.set_train_precision(before)
 
 
 class NodeAdjEDMObjectiveGeneratorHip(object):
@@ -168,15 +185,19 @@ class NodeAdjRainbowLossHip(torch.nn.Module):
 
 
 def eval_loss_step(model, train_obj_gen, loss_func, adjs_gt, nodes_gt, node_flags, mode="test", iou_loss_type="iou",
-                   iou_loss_weight=0.0, **replay):
+                   iou_loss_weight=0.0, precision="fp32", **replay):
     """One iteration of node_adj_move_forward_one_epoch in 'test' mode (trainer_node_adj.py:96-167): objective -> model pass
-    under no_grad -> per-sample losses -> loss = adj.mean() + node.mean().  Returns (loss, reg_loss_adj, reg_loss_node, sigmas)."""
+    under no_grad -> per-sample losses -> loss = adj.mean() + node.mean().  Returns (loss, reg_loss_adj, reg_loss_node, sigmas).
+    precision ("fp32" | "bf16"): the training entries' precision (see train_step_grads); it reaches mode='train' only -- the 'test'
+    pass runs on the sampling path, whose precision is the handle's options'."""
+    if precision not in _lib.TRAIN_PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(_lib.TRAIN_PRECISIONS)}, not {precision!r}")
     if mode == "train":
         if replay.get("optimizer") is None:
             raise ValueError("mode='train' needs optimizer=AdamHip(model) (and optionally ema_helper=[EMAHip(model, beta), ...])")
         optimizer, ema_helper = replay.pop("optimizer"), replay.pop("ema_helper", None)
         loss, ra, rn, sg, _ = train_one_iteration(model, train_obj_gen, loss_func, optimizer, ema_helper, adjs_gt, nodes_gt, node_flags,
-                                                  iou_loss_weight=iou_loss_weight, iou_loss_type=iou_loss_type, **replay)
+                                                  iou_loss_weight=iou_loss_weight, iou_loss_type=iou_loss_type, precision=precision, **replay)
         return loss, ra, rn, sg
     if mode != "test":
         raise NotImplementedError(mode)
@@ -262,12 +283,15 @@ def _train_handle(m):
 
 @torch.no_grad()
 def train_step_grads(model, loss_func, net_input_a, net_input_x, node_flags, sigmas, net_target_a, net_target_x, loss_weight,
-                     iou_loss_weight=0.0, want_grads=True, iou_loss_type="iou"):
+                     iou_loss_weight=0.0, want_grads=True, iou_loss_type="iou", precision="fp32"):
     """One training iteration up to and including `loss.backward()` (trainer_node_adj.py:96-170) on the device:
     `model(adjs=net_input_a, nodes=net_input_x, node_flags=..., sigmas=...)` with the network in training form (the self-conditioning
     coin is drawn from NumPy's global generator like precond.py:90; the detached self-conditioning pass runs in training form too --
     `dsg_train_self_cond` -- so an iteration never rebuilds the sampling path's packed weights), per-sample losses, and the gradient of
     `loss_adj.mean() + loss_node.mean()` for every parameter.
+    precision="bf16": mixed precision for the duration of this call (dsg_train_set_precision; the handle's mode is restored afterwards)
+    -- the large products of the blocks, merging and breakup linears round their operands to bf16 and accumulate in fp32; parameters,
+    gradients, activations and everything else stay fp32.  The self-conditioning pass runs in the same mode.
     -> (net_output_a, net_output_x, reg_loss_adj [B], reg_loss_node [B], GradDict {state-dict key: gradient})."""
     import numpy as np
     m = model.model
@@ -281,7 +305,8 @@ def train_step_grads(model, loss_func, net_input_a, net_input_x, node_flags, sig
     sa = sx = None
     if model.self_condition and np.random.rand() < 0.5:   # precond.py:90-98: D of a no-grad pass becomes the (detached) self-cond input
         sa, sx = torch.empty_like(a), torch.empty_like(x)
-        h.check(h.L.dsg_train_self_cond(h.raw, B, _p(a), _p(x), _p(fl), _p(sg), _p(sa), _p(sx), st), "dsg_train_self_cond")
+        with _train_precision(h, precision):
+            h.check(h.L.dsg_train_self_cond(h.raw, B, _p(a), _p(x), _p(fl), _p(sg), _p(sa), _p(sx), st), "dsg_train_self_cond")
     grads = GradDict()
     names = ptrs = None
     n_keys = 0
@@ -301,10 +326,11 @@ def train_step_grads(model, loss_func, net_input_a, net_input_x, node_flags, sig
         ptrs = (C.c_void_p * len(keys))(*[base + 4 * o for o in offs])
     da, dx_ = torch.empty_like(a), torch.empty_like(x)
     la, ln = torch.empty(B, device=dev), torch.empty(B, device=dev)
-    h.check(h.L.dsg_train_step_grads(h.raw, B, _p(a), _p(x), _p(fl), _p(sg), _p(sa), _p(sx), _p(ta), _p(tx), _p(w),
-                                     float(loss_func.edge_loss_weight), float(loss_func.node_loss_weight), float(iou_loss_weight),
-                                     _lib.iou_loss_type_code(iou_loss_type), _p(da), _p(dx_), _p(la), _p(ln), n_keys, names, ptrs, st),
-            "dsg_train_step_grads")
+    with _train_precision(h, precision):
+        h.check(h.L.dsg_train_step_grads(h.raw, B, _p(a), _p(x), _p(fl), _p(sg), _p(sa), _p(sx), _p(ta), _p(tx), _p(w),
+                                         float(loss_func.edge_loss_weight), float(loss_func.node_loss_weight), float(iou_loss_weight),
+                                         _lib.iou_loss_type_code(iou_loss_type), _p(da), _p(dx_), _p(la), _p(ln), n_keys, names, ptrs, st),
+                "dsg_train_step_grads")
     oa, on = m._shape_out(da, dx_)
     return oa, on, la, ln, grads
 
@@ -439,16 +465,17 @@ class EMAHip(object):
 
 
 def train_one_iteration(model, train_obj_gen, loss_func, optimizer, ema_helper, adjs_gt, nodes_gt, node_flags, iou_loss_weight=0.0,
-                        max_grad_norm=10.0, iou_loss_type="iou", **replay):
+                        max_grad_norm=10.0, iou_loss_type="iou", precision="fp32", **replay):
     """One iteration of node_adj_move_forward_one_epoch in 'train' mode (trainer_node_adj.py:96-175): objective -> model pass ->
     per-sample losses -> loss.backward() -> clip_grad_norm_(10) -> optimizer.step() -> EMA updates.
+    precision="bf16": the forward / backward products in mixed precision (train_step_grads); the all-reduce, clip, Adam and EMA are fp32.
     -> (loss, reg_loss_adj, reg_loss_node, sigmas, total_grad_norm)"""
     net_input_a, net_input_x, net_cond, net_target_a, net_target_x, (c_skip, c_out, c_in, c_noise, sigmas, weights) = \
         train_obj_gen.get_input_output(adjs_gt, nodes_gt, node_flags, **replay)
     optimizer.zero_grad(set_to_none=True)
     oa, on, reg_loss_adj, reg_loss_node, grads = train_step_grads(model, loss_func, net_input_a, net_input_x, node_flags, sigmas,
                                                                   net_target_a, net_target_x, weights, iou_loss_weight=iou_loss_weight,
-                                                                  iou_loss_type=iou_loss_type)
+                                                                  iou_loss_type=iou_loss_type, precision=precision)
     loss = reg_loss_adj.mean() + reg_loss_node.mean()
     from . import dist as _dist
     _dist.all_reduce_mean(grads)   # data parallel: the mean over ranks, what DDP's backward leaves (identity on one rank)

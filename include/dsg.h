@@ -704,6 +704,27 @@ int32_t dsg_ode_evals(const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode, float 
  * affected: they use what dsg_set_weight + dsg_finalize_weights installed. */
 int dsg_train_bind_params(dsg_handle h, int32_t n_params, const char *const *names, const float *const *params);
 
+/* Precision of the training entries' large matrix products (mixed precision: fp32 master weights, fp32 accumulation, bf16 operands).
+ * The mode is handle state, off by default, and acts on dsg_train_grads, dsg_train_step_grads and dsg_train_self_cond only;
+ * dsg_precond_vjp, dsg_ode_run and every sampling entry are the same bits whatever it is.  Setting it enqueues nothing, invalidates
+ * nothing and touches neither the options nor the packed weights.  It is not an option: no dsg_set_option key, no environment variable.
+ * DSG_TRAIN_BF16: the three products of the four linears of every Swin block (attn.qkv, attn.proj, mlp.fc1, mlp.fc2), of
+ *   downsample.reduction and of upsample.pre_linear / post_linear -- y = x W^T, dx = dy W, dW = dy^T x -- round both operands to bf16
+ *   (nearest even), accumulate in fp32 on the bf16 matrix pipe and store fp32, wherever the product has at least 512 token rows and
+ *   channel extents that are multiples of 32; a covered product of any other shape silently stays on its fp32 route.  db = colsum(dy)
+ *   is formed from the unrounded fp32 dy.  Everything else stays fp32: PatchEmbed, the read-out chain and both heads, the noise
+ *   embedding and every `affine` linear, window attention, LayerNorm / modulate / GELU, loss, all saved activations (the arena keeps
+ *   its size), the gradient buffers, clip / Adam / EMA.  No loss scaling: bf16 has fp32's exponent range.
+ *   The parameters are read in place and may change between calls, so every entry call in this mode re-rounds the covered weights into
+ *   handle-owned bf16 planes (both orientations) before its first product; nothing is cached across calls.
+ * dsg_train_set_precision: DSG_ERR_INVALID for any other value, the old mode kept.  Handles with patch_size > 1 accept the setter and
+ *   keep refusing the training entries.  No trained weights exist for this model offline: nothing is claimed about the convergence or
+ *   the quality of models trained in this mode. */
+#define DSG_TRAIN_F32  0   /* default */
+#define DSG_TRAIN_BF16 1
+int dsg_train_set_precision(dsg_handle h, int32_t mode);
+int dsg_train_get_precision(dsg_handle h, int32_t *mode);
+
 /* The rest of a training iteration (R/runner/trainer/trainer_node_adj.py:170-175), on caller-owned device tensors, no handle:
  * dsg_adam_step <-> nn.utils.clip_grad_norm_(parameters, max_norm) followed by torch.optim.Adam.step()  (utils/learning_utils.py:137-140:
  *   betas (0.9, 0.999), eps 1e-8, L2 weight_decay; gradients are scaled in place by the clip coefficient like the reference;

@@ -377,6 +377,22 @@ int dsg_debug_mlp_bx(int32_t M, int32_t C, const float *xn, float *x, const floa
 int dsg_debug_t_gemm(int32_t ta, int32_t tb, const float *A, int32_t lda, const float *B, int32_t ldb, const float *bias, float *C, int32_t ldc,
                      int32_t M, int32_t N, int32_t K, int32_t accumulate, float *a_colsum, const float *res, int32_t act, float *c2,
                      int32_t force_plain, int32_t *route_out, void *stream);
+/* dsg_debug_t_gemm_lp: ONE product in the bf16 mode of the training entries (dsg_train_set_precision; csrc/train_kernels_lp.hip), on
+ *   caller buffers with dsg_debug_t_gemm's argument conventions: y = x W^T (ta 0, tb 1), dx = dy W (ta 0, tb 0; B [K, N] contiguous),
+ *   dW = dy^T x (ta 1, tb 0).  The bf16 planes of B are built inside for the two activation-side forms.  any_rows != 0 waives the
+ *   512-row threshold of the shape rule (the kernels take any row count; the channel rule stays).  route_out (HOST, two values or
+ *   NULL): [0] 5 the bf16 GEMM on the weight plane, 6 gemm_tn_bf16_kernel + reduction, 0 not taken; [1] the number of K slices.
+ *   A product the bf16 route does not take returns DSG_ERR_INVALID and writes nothing (it never falls back to fp32 here).
+ * dsg_debug_t_cast_lp: W [R, Cc] contiguous fp32 -> out_nk [R, Cc] and out_kn [Cc, R] bf16 bit patterns (uint16; either may be NULL),
+ *   the plane builder of that mode.
+ * dsg_debug_train_routes (HOST out, rows of four int32: token rows, class 0 y / 1 dx / 2 dW, products on the bf16 route, products on
+ *   an fp32 route): the covered products of the handle's LAST training entry, grouped by (rows, class); returns the number of groups
+ *   (at most `cap` are written).  Products of call sites the mode does not cover are not listed; with the mode off the list is empty. */
+int dsg_debug_t_gemm_lp(int32_t ta, int32_t tb, const float *A, int32_t lda, const float *B, int32_t ldb, const float *bias, float *C,
+                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t accumulate, float *a_colsum, const float *res, int32_t act,
+                        float *c2, int32_t any_rows, int32_t *route_out, void *stream);
+int dsg_debug_t_cast_lp(const float *W, int32_t R, int32_t Cc, uint16_t *out_nk, uint16_t *out_kn, void *stream);
+int32_t dsg_debug_train_routes(dsg_handle h, int32_t *out, int32_t cap);
 /* window attention of the training block, forward (bwd == 0: qkv [B res^2, 3C], C = 32 heads, table [(2 ws - 1)^2, heads] -> out
  * [B res^2, C]) or backward (d_out [B res^2, C] -> d_qkv [B res^2, 3C] written, d_table ADDED to: the caller zeroes it).
  * S = q k^T / sqrt(32) + table[index][h] (- 100 where the shifted window's regions differ).  force_plain != 0: the scalar kernel. */
