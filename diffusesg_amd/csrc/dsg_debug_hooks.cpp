@@ -684,6 +684,66 @@ int dsg_debug_projmlp_bx(int32_t M, int32_t C, const float *att, float *x, const
     return mlp_bx_hook(M, C, att, Wp, bp, x, W1, b1, W2, b2, mod, out_mode, out_xn, wide8, resident96, time_iters, out_ms, (hipStream_t)stream);
 }
 
+// ---- the same kernels on the caller's own bf16 tensors: every field of the launcher's argument block, no scratch in between ----
+int dsg_debug_gemm_bx_args(const dsg_bx_gemm_args *a, void *stream) {
+    if (a && a->geo_used) *a->geo_used = -1;
+    if (!a || !a->A || !a->W || (!a->C && !a->Cb)) return DSG_ERR_INVALID;
+    // what the kernel takes on trust from the forward: pitches that hold a row, 16-byte aligned (scale | shift) rows, a sample length
+    const int K1 = a->A2 ? a->K1 : a->K;
+    if (a->M < 1 || a->N < 1 || a->K < 1 || a->lda < K1 || (a->A2 && (K1 < 1 || K1 >= a->K || a->lda2 < a->K - K1))) return DSG_ERR_INVALID;
+    if ((a->C && a->ldc < a->N) || (a->Cb && a->ldcb < a->N) || (a->C2b && a->ldc2b < a->N) || (a->res && a->ldres < a->N)) return DSG_ERR_INVALID;
+    if ((a->C && a->ldc % 4 != 0) || (a->res && a->ldres % 4 != 0)) return DSG_ERR_INVALID;
+    if (a->mod_aff && (!mult4(a->mod_ld) || !mult4(a->mod_off) || a->mod_T < 1 || (a->mod_ld && a->mod_ld < a->mod_off + 2 * a->N))) return DSG_ERR_INVALID;
+    BxGemm g;
+    g.A = a->A; g.lda = a->lda; g.A2 = a->A2; g.lda2 = a->lda2; g.K1 = a->K1; g.W = a->W; g.bias = a->bias;
+    g.res = a->res; g.ldres = a->ldres; g.C = a->C; g.ldc = a->ldc; g.Cb = a->Cb; g.ldcb = a->ldcb; g.C2b = a->C2b; g.ldc2b = a->ldc2b;
+    g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act;
+    g.mod_aff = a->mod_aff; g.mod_ld = a->mod_ld; g.mod_off = a->mod_off; g.mod_T = a->mod_T > 0 ? a->mod_T : 1;
+    g.ln_out = a->ln_out;
+    const int geo = bx_gemm_geo(g);
+    if (geo < 0) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const bool ok = launch_gemm_bx(g, s);
+    if (ok && a->geo_used) *a->geo_used = geo;
+    return debug_finish(ok, s);
+}
+
+int dsg_debug_mlp_bx_args(const dsg_bx_mlp_args *a, void *stream) {
+    if (!a || (!a->xn && !a->att) || (a->xn && a->att) || !a->x || !a->W1 || !a->b1 || !a->W2 || !a->b2 || a->M < 1) return DSG_ERR_INVALID;
+    if (a->out_mode < 0 || a->out_mode > 2 || (a->out_mode && !a->xn_out)) return DSG_ERR_INVALID;
+    const bool proj = a->att != nullptr;
+    const int32_t C = a->C, kernel = a->kernel;
+    if (C != 96 && C != 192 && C != 384) return DSG_ERR_INVALID;
+    int wide8;
+    bool resident96 = false;
+    if (!proj) {   // dsg_debug_mlp_bx's rule
+        wide8 = mlp384_wide8(kernel);
+        if (wide8 < 0 || (kernel != DSG_BXK_DEFAULT && C != 384)) return DSG_ERR_INVALID;
+    } else {       // dsg_debug_projmlp_bx's rule
+        const bool k96 = kernel == DSG_BXK_MLP96_STAGED || kernel == DSG_BXK_MLP96_RESIDENT;
+        resident96 = kernel == DSG_BXK_MLP96_RESIDENT;
+        wide8 = k96 ? 1 : mlp384_wide8(kernel);
+        if (wide8 < 1 || (k96 ? C != 96 : (kernel != DSG_BXK_DEFAULT && C != 384)) || (resident96 && a->mod_aff) || !a->Wp || !a->bp) return DSG_ERR_INVALID;
+    }
+    if (a->mod_aff && (!mult4(a->mod_ld) || !mult4(a->mod_off) || a->mod_T < 1 || (a->mod_ld && a->mod_ld < a->mod_off + 2 * C))) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    BxMlp g;
+    if (proj) { g.att = a->att; g.Wp = a->Wp; g.bp = a->bp; } else g.xn = a->xn;
+    g.x = a->x; g.W1 = a->W1; g.b1 = a->b1; g.W2 = a->W2; g.b2 = a->b2; g.M = a->M; g.C = C;
+    if (a->out_mode) { g.xn_out = a->xn_out; g.out_mode = a->out_mode; }
+    g.wide8 = wide8;
+    g.mod_aff = a->mod_aff; g.mod_ld = a->mod_ld; g.mod_off = a->mod_off; g.mod_T = a->mod_T > 0 ? a->mod_T : 1;
+    // the weight images of the kernels that stream pre-arranged weights, from the row-major tensors
+    Scratch sc;
+    const bool img384 = C == 384 && (wide8 == 1 || wide8 == 3);
+    void *imgb = img384 ? sc.get(mlp384_image_bytes()) : (resident96 ? sc.get(mlp96r_image_bytes()) : nullptr);
+    if (!sc.ok) return DSG_ERR_HIP;
+    if (img384 && wide8 == 1) { launch_mlp384_images(a->W1, a->W2, a->Wp, imgb, s); g.img = imgb; }
+    if (img384 && wide8 == 3) { launch_mlp384s_images(a->W1, a->W2, a->Wp, imgb, s); g.img2 = imgb; }
+    if (resident96) { launch_mlp96r_image(a->W1, a->W2, a->Wp, imgb, s); g.img96 = imgb; }
+    return debug_finish(launch_mlp_bx(g, s), s);
+}
+
 int dsg_debug_attn_bx(int32_t B, int32_t res, int32_t ws, int32_t shift, int32_t heads, const float *qkv, const float *biasT, float *out,
                       int32_t time_iters, float *out_ms, void *stream) {
     if (B < 1 || res < 1 || ws < 1 || res % ws != 0 || heads < 1 || !qkv || !biasT || !out) return DSG_ERR_INVALID;

@@ -140,6 +140,7 @@ struct BxGemm {
     unsigned long long *dbg = nullptr;            // DSG_BX_EXP == 4 builds only: per-block phase clocks [grid][8] (tools/bx_exp.sh)
 };
 bool launch_gemm_bx(const BxGemm &g, hipStream_t s);   // false: shape not covered (nothing launched)
+int bx_gemm_geo(const BxGemm &g);                      // the launcher's rule on its own: tile geometry 0 / 2 / 3, -1 where it refuses
 // x <- [modulate_next] (x + fc2(GELU(fc1(xn)))) in one kernel (mlp_ratio 4, C in {96, 192, 384}); xn = LayerNorm-2 of x as bf16
 // (gamma / beta folded into W1 / b1), W1 [4C, C] and W2 [C, 4C] bf16; xn_out (optional) receives the LayerNorm (out_mode 1) or the
 // plain bf16 copy (out_mode 2) of the stored row; mod_* as BxGemm.  false: width not covered.

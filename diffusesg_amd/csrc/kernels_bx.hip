@@ -406,26 +406,33 @@ static int bx_cu_count() {
     return n;
 }
 
-bool launch_gemm_bx(const BxGemm &g, hipStream_t s) {
-    if (!g.A || !g.W || g.M < 1 || g.N < 1 || g.K < 8 || g.K % 8 != 0 || g.N % 4 != 0 || (g.act != ACT_NONE && g.act != ACT_GELU)) return false;
-    if (g.lda % 8 != 0 || (g.A2 && (g.lda2 % 8 != 0 || g.K1 <= 0))) return false;
-    if ((g.Cb || g.C2b) && (g.N % 8 != 0 || (g.Cb && g.ldcb % 8 != 0) || (g.C2b && g.ldc2b % 8 != 0))) return false;   // bf16 outputs leave in 16-byte row pieces
-    if (g.act == ACT_GELU && g.res) return false;   // the epilogue adds the residual before bias / activation (fc1 has none)
+// the tile geometry launch_gemm_bx runs a form on (0 / 2 / 3 below), -1: the form is not covered
+int bx_gemm_geo(const BxGemm &g) {
+    if (!g.A || !g.W || g.M < 1 || g.N < 1 || g.K < 8 || g.K % 8 != 0 || g.N % 4 != 0 || (g.act != ACT_NONE && g.act != ACT_GELU)) return -1;
+    if (g.lda % 8 != 0 || (g.A2 && (g.lda2 % 8 != 0 || g.K1 <= 0))) return -1;
+    if ((g.Cb || g.C2b) && (g.N % 8 != 0 || (g.Cb && g.ldcb % 8 != 0) || (g.C2b && g.ldc2b % 8 != 0))) return -1;   // bf16 outputs leave in 16-byte row pieces
+    if (g.act == ACT_GELU && g.res) return -1;   // the epilogue adds the residual before bias / activation (fc1 has none)
     // geometry (wave grid WM x WN, block tile 64 WM x 96 WN): the tile spans the whole row when a LayerNorm output is asked for;
     // otherwise 128 x 192 where N splits into 192s, 256 x 96 for the narrow / odd widths (N = 96, 288)
     //   0: <2,2,64> 128x192 (4 waves, 2 blocks / CU)   2: <4,1,32> 256x96 (4 waves, 2 blocks / CU)   3: <2,4,64> 128x384 (8 waves)
     // (measured against 64x384 on 4 waves with 64- and 32-deep chunks and 256x192 on 8 waves: profiles/r3/bx_experiments.txt)
     int geo;
     if (g.ln_out) {
-        if (!g.Cb) return false;
-        if (g.N == 96) geo = 2; else if (g.N == 192) geo = 0; else if (g.N == 384) geo = 3; else return false;
+        if (!g.Cb) return -1;
+        if (g.N == 96) geo = 2; else if (g.N == 192) geo = 0; else if (g.N == 384) geo = 3; else return -1;
     } else {
         geo = (g.N % 192 == 0) ? 0 : 2;
     }
     const int kb = geo == 2 ? 32 : 64;
-    if (g.A2 && g.K1 % kb != 0) return false;
-    if (geo == 2 && g.K % 32 != 0) return false;
-    if ((g.K + kb - 1) / kb < 2) return false;      // the chunk loop assumes at least two chunks per tile
+    if (g.A2 && g.K1 % kb != 0) return -1;
+    if (geo == 2 && g.K % 32 != 0) return -1;
+    if ((g.K + kb - 1) / kb < 2) return -1;      // the chunk loop assumes at least two chunks per tile
+    return geo;
+}
+
+bool launch_gemm_bx(const BxGemm &g, hipStream_t s) {
+    const int geo = bx_gemm_geo(g);
+    if (geo < 0) return false;
     const int bm = geo == 0 ? 128 : (geo == 2 ? 256 : 128), bn = geo == 0 ? 192 : (geo == 2 ? 96 : 384);
     const int tiles_m = (g.M + bm - 1) / bm, tiles_n = (g.N + bn - 1) / bn;
     const int tiles_total = round_up8(tiles_m) * tiles_n;

@@ -100,7 +100,7 @@ DEBUG_EXPORTS = [
     "dsg_debug_window_harvest_f32", "dsg_debug_graph_dot", "dsg_debug_poison", "dsg_debug_box_guide", "dsg_debug_box_guide_rel",
     "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp", "dsg_debug_patch_forms",
     "dsg_debug_assemble_patch_f32", "dsg_debug_head_patch_f32", "dsg_debug_patch_embed_patch_f32", "dsg_debug_readout_patch_f32",
-    "dsg_debug_t_gemm_lp", "dsg_debug_t_cast_lp", "dsg_debug_train_routes",
+    "dsg_debug_t_gemm_lp", "dsg_debug_t_cast_lp", "dsg_debug_train_routes", "dsg_debug_gemm_bx_args", "dsg_debug_mlp_bx_args",
 ]
 
 
@@ -119,6 +119,20 @@ class DsgGemmLpArgs(C.Structure):
                                            "row_list", "row_cnt", "tile_used")] +
                 [(n, C.c_int32) for n in ("lda", "lda2", "K1", "ln_nparts", "ldres", "ldc", "ldc2", "M", "N", "K", "act", "mod_ld",
                                           "mod_off", "mod_T", "a4_res", "reserved", "mode", "tile", "a_bf16", "c_bf16")])
+
+
+class DsgBxGemmArgs(C.Structure):
+    """dsg_bx_gemm_args of include/dsg_debug.h (dsg_debug_gemm_bx_args): device pointers as integers (geo_used: a host int32), leading
+    dimensions in elements of the tensor they belong to"""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "A2", "W", "bias", "res", "C", "Cb", "C2b", "mod_aff", "geo_used")] +
+                [(n, C.c_int32) for n in ("lda", "lda2", "K1", "ldres", "ldc", "ldcb", "ldc2b", "M", "N", "K", "act", "mod_ld", "mod_off",
+                                          "mod_T", "ln_out")])
+
+
+class DsgBxMlpArgs(C.Structure):
+    """dsg_bx_mlp_args of include/dsg_debug.h (dsg_debug_mlp_bx_args)"""
+    _fields_ = ([(n, C.c_void_p) for n in ("xn", "att", "x", "W1", "W2", "Wp", "b1", "b2", "bp", "xn_out", "mod_aff")] +
+                [(n, C.c_int32) for n in ("out_mode", "mod_ld", "mod_off", "mod_T", "M", "C", "kernel")])
 
 
 ROWLP_MERGE_LN, ROWLP_BREAKUP_LN, ROWLP_LN_BX, ROWLP_COPY_BX = range(4)                            # DSG_ROWLP_* (dsg_debug_row_lp)
@@ -198,6 +212,8 @@ def _declare_debug(L: C.CDLL) -> None:
     L.dsg_debug_projmlp_bx.argtypes = [i32, i32] + [vp] * 9 + [i32, vp, i32, i32, C.POINTER(C.c_float), vp]
     L.dsg_debug_qkv_attn_bx.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, C.POINTER(C.c_float), vp]
     L.dsg_debug_mlp_bx.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, C.POINTER(C.c_float), vp]
+    L.dsg_debug_gemm_bx_args.argtypes = [C.POINTER(DsgBxGemmArgs), vp]
+    L.dsg_debug_mlp_bx_args.argtypes = [C.POINTER(DsgBxMlpArgs), vp]
     L.dsg_debug_t_assemble_bwd.argtypes = [i32] * 5 + [vp, i32] + [vp] * 8
     L.dsg_debug_graph_dot.argtypes = [i32] * 4 + [vp] * 7
     L.dsg_debug_poison.argtypes = [vp, i32, i32, C.c_uint64, vp]

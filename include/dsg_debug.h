@@ -363,6 +363,43 @@ int dsg_debug_projmlp_bx(int32_t M, int32_t C, const float *att, float *x, const
 int dsg_debug_mlp_bx(int32_t M, int32_t C, const float *xn, float *x, const float *W1, const float *b1, const float *W2, const float *b2,
                      const float *mod, int32_t out_mode, float *out_xn, int32_t kernel, int32_t time_iters, float *out_ms, void *stream);
 
+/* The same GEMM and fused-MLP kernels on the caller's OWN tensors (tests/test_bx_forms.py): bf16 tensors are taken as they are, nothing is
+ * converted, no scratch sits between the caller and the kernel, and only what the kernel writes is written.  A form the launcher
+ * refuses is DSG_ERR_INVALID with nothing launched and nothing written.
+ * dsg_debug_gemm_bx_args: launch_gemm_bx on a BxGemm filled field by field.  A [M, lda], A2 [M, lda2] (second source for k >= K1; NULL:
+ *   K1 is ignored), W [N, K] bf16; bias [N], res [M, ldres] fp32; C [M, ldc] fp32 (may alias res), Cb [M, ldcb] and C2b [M, ldc2b] bf16
+ *   (C2b: the value before the modulate); leading dimensions in elements.  act 0 | 1 GELU.  mod_aff: silu(shift + v (1 + scale)),
+ *   (scale, shift) = mod_aff[b mod_ld + mod_off + {n, N + n}], b = row / mod_T; mod_ld == 0: one row for the batch (staged in LDS),
+ *   mod_ld > 0: per sample, read in the epilogue; mod_ld and mod_off multiples of 4.  ln_out: Cb = LayerNorm of the stored row.
+ *   What the kernel takes on trust from the forward is checked here (DSG_ERR_INVALID): pitches that hold a row, fp32 pitches and the
+ *   (scale | shift) offsets in multiples of 4, mod_T >= 1, a per-sample row pitch that holds mod_off + 2N.
+ *   geo_used (HOST, may be NULL): the tile geometry launched -- 0 128 x 192 (k chunk 64), 2 256 x 96 (k chunk 32), 3 128 x 384
+ *   (k chunk 64) -- or -1 when refused.
+ * dsg_debug_mlp_bx_args: launch_mlp_bx.  Exactly one of xn / att (bf16 [M, C]); with att the proj stage (Wp [C, C] bf16, bp) rides in
+ *   front.  x [M, C] fp32 in place; W1 [4C, C], W2 [C, 4C] bf16 row-major; xn_out bf16 [M, C] with out_mode 1 (LayerNorm of the stored
+ *   row) or 2 (its copy); mod_* as above; kernel: DSG_BXK_* with the meaning and the refusals of dsg_debug_mlp_bx (xn) and
+ *   dsg_debug_projmlp_bx (att).  The weight images of the kernels that stream pre-arranged weights are built inside. */
+typedef struct dsg_bx_gemm_args {
+    const void *A, *A2, *W;
+    const float *bias, *res;
+    float *C;
+    void *Cb, *C2b;
+    const float *mod_aff;
+    int32_t *geo_used;
+    int32_t lda, lda2, K1, ldres, ldc, ldcb, ldc2b, M, N, K, act, mod_ld, mod_off, mod_T, ln_out;
+} dsg_bx_gemm_args;
+int dsg_debug_gemm_bx_args(const dsg_bx_gemm_args *args, void *stream);
+typedef struct dsg_bx_mlp_args {
+    const void *xn, *att;
+    float *x;
+    const void *W1, *W2, *Wp;
+    const float *b1, *b2, *bp;
+    void *xn_out;
+    const float *mod_aff;
+    int32_t out_mode, mod_ld, mod_off, mod_T, M, C, kernel;
+} dsg_bx_mlp_args;
+int dsg_debug_mlp_bx_args(const dsg_bx_mlp_args *args, void *stream);
+
 /* ======== the training kernels ======== */
 
 /* The training kernels on their own (test hooks, csrc/train_kernels.hip; no handle, device pointers, synchronise `stream`;
