@@ -113,6 +113,15 @@ struct Workspace {
     size_t g_trace_cap = 0;
     uint8_t *g_kinds = nullptr, *g_predk = nullptr;   // the relation term: the given kinds [B,N,N] / the predicate -> kind table
     int g_predk_cap = 0;
+    // content guidance (dsg_sample_guided_content): its parameter block and the full-state shift of every slot (adjacency [B,Ca,N,N],
+    // label channels: room for [B,N,Cn-4], used as [B,N,Cl] with the row stride Cl of the run), what the launches of the
+    // content kernel's grid form hand over [B,CONTENT_STATS_PER_GRAPH], all baked by content-guided bodies; the run's targets and weights and the trace sit
+    // behind the block's pointers and grow without touching a captured body.  Counted in guide_bytes
+    ContentParams *c_par = nullptr;
+    float *c_shift_adj[3] = {nullptr, nullptr, nullptr}, *c_shift_label[3] = {nullptr, nullptr, nullptr};
+    double *c_stats = nullptr;
+    float *c_tgt = nullptr, *c_trace = nullptr;
+    size_t c_tgt_cap = 0, c_trace_cap = 0;
     size_t guide_bytes = 0;
     // batch-uniform noise level (the sampler): every sample shares one (scale,shift) row, taken from a table that
     // dsg_sample computes once for all steps; aff_ld == 0 broadcasts row 0 of `aff`
@@ -2308,9 +2317,14 @@ struct StepPlan {
     int g1 = 0, g2 = 0;   //   w->g_shift buffers of the stage-1 / stage-2 shift
     int gprev = -1;       //   ... and of the previous step's stage-1 shift where prev >= 0
     int rel = REL_NONE;   //   the relation term (dsg_sample_guided_rel): REL_GIVEN / REL_DECODED select the guide kernel's relation variant
-    int key() const {   // prev, then the guidance bits, then the relation bits sit above every older bit: plans without them keep their keys
+    bool content = false; //   content guidance (dsg_sample_guided_content): the content kernel behind every D too, the updates read both
+                          //   shifts; its shift buffers rotate with g1 / g2 / gprev
+    bool cclip = false;   //   ... with the content shift's own clip factor
+    int cgrid = 0;        //   ... 0: the content kernel's one-block-per-graph form; K: its (graph, item) grid, whose launch bakes K
+    int key() const {   // prev, then the guidance bits, the relation bits, the content bits sit above every older bit: plans without them keep their keys
         return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8) | ((int)known << 9) |
-               ((prev + 1) << 10) | ((int)guided << 12) | ((int)clip << 13) | (g1 << 14) | (g2 << 16) | ((gprev + 1) << 18) | (rel << 20);
+               ((prev + 1) << 10) | ((int)guided << 12) | ((int)clip << 13) | (g1 << 14) | (g2 << 16) | ((gprev + 1) << 18) | (rel << 20) |
+               ((int)content << 22) | ((int)cclip << 23) | (cgrid << 24);
     }
 };
 
@@ -2350,13 +2364,19 @@ int precond_tab(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, c
 
 // box guidance behind one preconditioned call: the norm pass (with the clip only), then the guide kernel on D -> w->g_shift[slot]
 int guide_call(dsg_handle h, Workspace *w, const StepPlan &p, CStatePtrs xh, CStatePtrs D, int slot, bool stage1, const Dims &d, hipStream_t s) {
-    if (p.clip && !launch_graph_diff_norm(xh, D, w->flags, w->g_ref, d, s)) return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
+    if ((p.clip || p.cclip) && !launch_graph_diff_norm(xh, D, w->flags, w->g_ref, d, s)) return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
     const BoxGuideOut out{w->g_shift[slot], nullptr, nullptr, nullptr, nullptr};
     const bool ok = p.rel != REL_NONE
         ? launch_box_guide_rel(w->g_par, h->tab_step, w->ctl, 0.f, D.adj, D.node, w->flags, p.clip ? w->g_ref : nullptr, stage1, out, nullptr,
                                p.rel == REL_DECODED, d, s)
         : launch_box_guide(w->g_par, h->tab_step, w->ctl, 0.f, D.node, w->flags, p.clip ? w->g_ref : nullptr, stage1, out, d, s);
     if (!ok) return fail(h, DSG_ERR_INVALID, "box guidance: shape refused");
+    if (p.content) {   // the content term: a kernel and a full-state shift of its own, clipped on its own against the same norm
+        const ContentOut co{w->c_shift_adj[slot], w->c_shift_label[slot], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (!launch_content_guide(w->c_par, h->tab_step, w->ctl, 0.f, D.adj, D.node, w->flags, p.cclip ? w->g_ref : nullptr, stage1, co, p.cgrid,
+                                  w->c_stats, d, s))
+            return fail(h, DSG_ERR_INVALID, "content guidance: shape refused");
+    }
     return 0;
 }
 
@@ -2364,6 +2384,7 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
                  bool fwd_graph = false) {
     const Dims d = dims_of(h, w->B);
     const CStatePtrs xh{w->xh_adj, w->xh_node};
+    auto cshift = [&](int slot) { return ContentShiftPtrs{w->c_shift_adj[slot], w->c_shift_label[slot]}; };
     launch_churn_tab(CStatePtrs{w->x_adj, w->x_node}, h->tab_step, w->ctl, w->flags, StatePtrs{w->xh_adj, w->xh_node}, d, s);   // edm.py:355-366
     CStatePtrs D1{gt_adj, gt_node};   // sanity-check mode (edm.py:372-377): the denoiser is bypassed
     if (!gt_adj) {
@@ -2376,10 +2397,12 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
     const StatePtrs x{w->x_adj, w->x_node};
     if (p.euler && p.prev >= 0) {   // sanity-check mode: D_prev = D = gt
         const CStatePtrs Dp = gt_adj ? D1 : CStatePtrs{w->d_adj[p.prev], w->d_node[p.prev]};
-        if (p.guided) launch_multistep_tab_guided(xh, D1, Dp, w->g_shift[p.g1], w->g_shift[p.gprev], h->tab_step, w->ctl, w->flags, x, d, s);
+        if (p.content) launch_multistep_tab_guided2(xh, D1, Dp, w->g_shift[p.g1], w->g_shift[p.gprev], cshift(p.g1), cshift(p.gprev), w->c_par, h->tab_step, w->ctl, w->flags, x, d, s);
+        else if (p.guided) launch_multistep_tab_guided(xh, D1, Dp, w->g_shift[p.g1], w->g_shift[p.gprev], h->tab_step, w->ctl, w->flags, x, d, s);
         else launch_multistep_tab(xh, D1, Dp, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     } else if (p.euler) {
-        if (p.guided) launch_euler_tab_guided(xh, D1, w->g_shift[p.g1], h->tab_step, w->ctl, w->flags, x, d, s);
+        if (p.content) launch_euler_tab_guided2(xh, D1, w->g_shift[p.g1], cshift(p.g1), w->c_par, h->tab_step, w->ctl, w->flags, x, d, s);
+        else if (p.guided) launch_euler_tab_guided(xh, D1, w->g_shift[p.g1], h->tab_step, w->ctl, w->flags, x, d, s);
         else launch_euler_tab(xh, D1, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     } else {
         CStatePtrs D2 = D1;
@@ -2391,7 +2414,8 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
         }
         if (p.guided) {   // stage 2 is evaluated at (x_hat, t_hat) and guided the same way
             if (int rc = guide_call(h, w, p, xh, D2, p.g2, /*stage1=*/false, d, s)) return rc;
-            launch_heun_tab_guided(xh, D1, D2, w->g_shift[p.g1], w->g_shift[p.g2], h->tab_step, w->ctl, w->flags, x, d, s);
+            if (p.content) launch_heun_tab_guided2(xh, D1, D2, w->g_shift[p.g1], w->g_shift[p.g2], cshift(p.g1), cshift(p.g2), w->c_par, h->tab_step, w->ctl, w->flags, x, d, s);
+            else launch_heun_tab_guided(xh, D1, D2, w->g_shift[p.g1], w->g_shift[p.g2], h->tab_step, w->ctl, w->flags, x, d, s);
         } else launch_heun_tab(xh, D1, D2, h->tab_step, w->ctl, w->flags, StatePtrs{w->x_adj, w->x_node}, d, s);
     }
     launch_step_advance(w->ctl, s);
@@ -2759,6 +2783,7 @@ struct SampleArgs {
     CStatePtrs gt; KnownArgs known;
     const dsg_guide_cfg *guide = nullptr; float *loss_trace = nullptr;   // box guidance (dsg_sample_guided); null: the unguided loop
     const dsg_rel_cfg *rel = nullptr;                                    // ... and its relation term (dsg_sample_guided_rel); null or w_rel == 0: none
+    const dsg_content_cfg *content = nullptr; float *content_trace = nullptr;   // content guidance (dsg_sample_guided_content); null: none
     struct Snapshots { const int32_t *steps; int32_t n; float *adj, *node; } snapshots;
     StatePtrs outputs; dsg_sample_stats *stats; hipStream_t stream;
 };
@@ -2783,6 +2808,7 @@ struct SamplePlan {
     bool use_graph = false;
     std::vector<float> guide_coef; // [T] c_i of a guided run
     GuideParams gpar{};            // ... and its parameter block (device pointers: set once the tables are staged)
+    ContentParams cpar{};          // the content term's block, likewise
 };
 
 // the checks of a guide descriptor that need no device; `why` names the argument.  Cn < 0: not known here
@@ -2822,6 +2848,30 @@ bool rel_cfg_ok(const dsg_rel_cfg *r, int Ca, std::string &why) {
         return no("rel->encoding with rel->n_adj_type = %g does not fit the adjacency channels", r->n_adj_type);
     for (int k = 0; k < r->n_adj_type; k++)
         if (r->pred_kind[k] >= REL_KINDS) { snprintf(buf, sizeof(buf), "rel->pred_kind[%d] = %d is above 7 (DSG_REL_ON)", k, (int)r->pred_kind[k]); why = buf; return false; }
+    return true;
+}
+// the checks of a content descriptor that need no device; `why` names the argument
+bool content_cfg_ok(const dsg_content_cfg *c, int B, int N, int Ca, int Cn, std::string &why) {
+    char buf[256];
+    auto no = [&](const char *fmt, double v) { snprintf(buf, sizeof(buf), fmt, v); why = buf; return false; };
+    if (!std::isfinite(c->w_content)) return no("content->w_content = %g is not finite", c->w_content);
+    if (!(c->tau > 0.f && std::isfinite(c->tau))) return no("content->tau = %g must be positive and finite", c->tau);
+    if (!(c->clip_ratio >= 0.f)) return no("content->clip_ratio = %g must be >= 0, or DSG_GUIDE_CLIP_NONE", c->clip_ratio);
+    if (c->n_items < 1 || c->n_items > DSG_CONTENT_MAX_ITEMS) return no("content->n_items = %g must be 1..16 (DSG_CONTENT_MAX_ITEMS)", c->n_items);
+    if (Cn < 5 || c->node_chans < 1 || c->node_chans > Cn - 4) return no("content->node_chans = %g must be 1..C_node-4 (the label channels of a node row)", c->node_chans);
+    if (N > GUIDE_MAX_N) return no("content guidance keeps a graph's pair tile on chip: N = %g is beyond 64", N);
+    if (!c->subj) return no("content->subj is NULL (host, [B,K,node_chans])", 0);
+    if (!c->obj) return no("content->obj is NULL (host, [B,K,node_chans])", 0);
+    if (!c->pred) return no("content->pred is NULL (host, [B,K,C_adj])", 0);
+    if (!c->w_spo) return no("content->w_spo is NULL (host, [B,K,3])", 0);
+    const size_t bk = (size_t)B * c->n_items;
+    for (size_t i = 0; i < bk * c->node_chans; i++) {
+        if (!std::isfinite(c->subj[i])) return no("content->subj holds a target that is not finite (entry %g)", (double)i);
+        if (!std::isfinite(c->obj[i])) return no("content->obj holds a target that is not finite (entry %g)", (double)i);
+    }
+    for (size_t i = 0; i < bk * Ca; i++) if (!std::isfinite(c->pred[i])) return no("content->pred holds a target that is not finite (entry %g)", (double)i);
+    for (size_t i = 0; i < bk * 3; i++)
+        if (!(c->w_spo[i] >= 0.f && std::isfinite(c->w_spo[i]))) return no("content->w_spo holds a weight that is negative or not finite (entry %g)", (double)i);
     return true;
 }
 // the part of the parameter block that a relation descriptor fills (pointers: set once staged); returns the plan's relation source
@@ -2932,6 +2982,14 @@ int plan_sample(dsg_handle h, const SampleArgs &a, SamplePlan &p) {
             if (!rel_cfg_ok(a.rel, h->Ca, why)) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided_rel: %s", why.c_str());
             const int rel = rel_params(a.rel, p.gpar);
             for (int i = 0; i < L; i++) p.plans[i].rel = rel;
+        }
+        if (a.content) {   // the content term rides on the guided plan: the same coefficients, the same slot rotation
+            if (!content_cfg_ok(a.content, a.B, h->N, h->Ca, h->Cn, why)) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided_content: %s", why.c_str());
+            const bool cclip = !std::isinf(a.content->clip_ratio);
+            const int cgrid = content_grid_items(a.content->n_items);
+            for (int i = 0; i < L; i++) { p.plans[i].content = true; p.plans[i].cclip = cclip; p.plans[i].cgrid = cgrid; }
+            p.cpar = ContentParams{a.content->w_content, a.content->tau, cclip ? a.content->clip_ratio : 0.f, a.content->n_items,
+                                   a.content->node_chans, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         }
     }
     return 0;
@@ -3079,6 +3137,41 @@ int stage_guide(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, 
     p.gpar.trace = a.loss_trace ? w->g_trace : nullptr;
     p.gpar.mask_node = a.known.adj ? w->km_node : nullptr;   // stage_known ran: the workspace's copy
     HIP_TRY(h, hipMemcpyAsync(w->g_par, &p.gpar, sizeof(GuideParams), hipMemcpyHostToDevice, s));
+    if (!a.content) return 0;
+    // the content term: block and shift buffers once, the targets and weights of this run behind the block's pointers
+    const size_t sa = bn * h->N * h->Ca, sl = bn * (size_t)(h->Cn - 4);
+    if (!w->c_par) {   // the block is allocated last: a call after a failed allocation starts over instead of launching on null buffers
+        for (int k = 0; k < 3; k++) {
+            if (!w->c_shift_adj[k]) { if (int rc = grow(&(q = nullptr), sizeof(float) * sa, 0, AC_SCRATCH)) return rc; w->c_shift_adj[k] = (float *)q; }
+            if (!w->c_shift_label[k]) { if (int rc = grow(&(q = nullptr), sizeof(float) * sl, 0, AC_SCRATCH)) return rc; w->c_shift_label[k] = (float *)q; }
+        }
+        if (!w->c_stats) {
+            if (int rc = grow(&(q = nullptr), sizeof(double) * (size_t)w->B * CONTENT_STATS_PER_GRAPH, 0, AC_SCRATCH)) return rc;
+            w->c_stats = (double *)q;
+        }
+        if (int rc = grow(&(q = nullptr), sizeof(ContentParams), 0, AC_STATE)) return rc;
+        w->c_par = (ContentParams *)q;
+    }
+    const size_t bk = (size_t)w->B * p.cpar.K, n_lab = bk * p.cpar.Cl, n_pred = bk * h->Ca, n_tgt = 2 * n_lab + n_pred + 3 * bk;
+    if (w->c_tgt_cap < n_tgt) {
+        if (int rc = grow(&(q = w->c_tgt), sizeof(float) * n_tgt, sizeof(float) * w->c_tgt_cap, AC_SCRATCH)) return rc;
+        w->c_tgt = (float *)q; w->c_tgt_cap = n_tgt;
+    }
+    if (a.content_trace && w->c_trace_cap < trace_n) {
+        if (int rc = grow(&(q = w->c_trace), sizeof(float) * trace_n, sizeof(float) * w->c_trace_cap, AC_SCRATCH)) return rc;
+        w->c_trace = (float *)q; w->c_trace_cap = trace_n;
+    }
+    float *t_subj = w->c_tgt, *t_obj = t_subj + n_lab, *t_pred = t_obj + n_lab, *t_w = t_pred + n_pred;
+    HIP_TRY(h, hipMemcpyAsync(t_subj, a.content->subj, sizeof(float) * n_lab, hipMemcpyHostToDevice, s));   // the caller's host arrays outlive the run's synchronise
+    HIP_TRY(h, hipMemcpyAsync(t_obj, a.content->obj, sizeof(float) * n_lab, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(t_pred, a.content->pred, sizeof(float) * n_pred, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(t_w, a.content->w_spo, sizeof(float) * 3 * bk, hipMemcpyHostToDevice, s));
+    p.cpar.subj = t_subj; p.cpar.obj = t_obj; p.cpar.pred = t_pred; p.cpar.w_spo = t_w;
+    p.cpar.coef = w->g_coef;
+    p.cpar.trace = a.content_trace ? w->c_trace : nullptr;
+    p.cpar.mask_adj = a.known.adj ? w->km_adj : nullptr;
+    p.cpar.mask_node = a.known.adj ? w->km_node : nullptr;
+    HIP_TRY(h, hipMemcpyAsync(w->c_par, &p.cpar, sizeof(ContentParams), hipMemcpyHostToDevice, s));
     return 0;
 }
 
@@ -3102,6 +3195,7 @@ int run_loop(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &
     HIP_TRY(h, hipMemcpyAsync(a.outputs.adj, w->x_adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(a.outputs.node, w->x_node, sizeof(float) * sn, hipMemcpyDeviceToDevice, s));
     if (a.guide && a.loss_trace) HIP_TRY(h, hipMemcpyAsync(a.loss_trace, w->g_trace, sizeof(float) * (size_t)p.L * a.B, hipMemcpyDeviceToDevice, s));
+    if (a.content && a.content_trace) HIP_TRY(h, hipMemcpyAsync(a.content_trace, w->c_trace, sizeof(float) * (size_t)p.L * a.B, hipMemcpyDeviceToDevice, s));
     HIP_TRY(h, hipGetLastError());
     h->last_stats.precond_calls = p.precond_calls;
     h->last_stats.net_forwards = nfe;
@@ -3253,6 +3347,81 @@ int dsg_sample_guided_rel(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_wa
     a.rel = rel;
     if (int rc = known_args(h, "dsg_sample_guided_rel", /*required=*/false, a.known)) return rc;
     return sample_impl(h, a);
+}
+
+int dsg_sample_guided_content(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk, int32_t B, const uint8_t *flags,
+                              const uint64_t *graph_seeds, uint64_t coin_seed,
+                              const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                              const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                              const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                              const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                              const dsg_guide_cfg *guide, const float *gt_adj, const float *gt_node, float *loss_trace,
+                              float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream, const dsg_rel_cfg *rel,
+                              const dsg_content_cfg *content, float *content_trace) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!guide) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided_content needs a guide descriptor (guide is NULL)");
+    SampleArgs a{};
+    a.cfg = cfg; a.B = B; a.flags = flags; a.init = {init_adj, init_node}; a.noise = {noise_adj, noise_node}; a.coins = coins; a.seed = coin_seed;
+    a.snapshots = {snap_steps, n_snap, snap_adj, snap_node}; a.outputs = {out_adj, out_node}; a.stats = stats; a.stream = (hipStream_t)stream;
+    a.walk = walk;
+    a.base = {base_adj, base_node};
+    a.graph_seeds = graph_seeds;
+    a.known = {known_adj, known_node, mask_adj, mask_node};
+    a.gt = {gt_adj, gt_node};
+    a.guide = guide; a.loss_trace = loss_trace;
+    a.rel = rel;
+    if (content && content->w_content != 0.f) { a.content = content; a.content_trace = content_trace; }   // else: dsg_sample_guided_rel itself
+    if (int rc = known_args(h, "dsg_sample_guided_content", /*required=*/false, a.known)) return rc;
+    return sample_impl(h, a);
+}
+
+int dsg_debug_content_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,
+                            const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_adj, const uint8_t *mask_node,
+                            const dsg_content_cfg *content, float coef, float *loss, float *item_loss, float *grad_adj, float *grad_label,
+                            float *shift_adj, float *shift_label, float *factor, float *norms, int32_t *best, float *d_guided_adj,
+                            float *d_guided_node, void *stream) {
+    std::string why;
+    const char *me = "dsg_debug_content_guide: ";
+    if (B < 1 || N < 1 || c_adj < 1) { g_create_err = std::string(me) + "B, N and c_adj must be >= 1"; return DSG_ERR_INVALID; }
+    if (!content) { g_create_err = std::string(me) + "content is NULL"; return DSG_ERR_INVALID; }
+    if (!content_cfg_ok(content, B, N, c_adj, c_node, why)) { g_create_err = me + why; return DSG_ERR_INVALID; }
+    if (!std::isfinite(coef)) { g_create_err = std::string(me) + "coef is not finite"; return DSG_ERR_INVALID; }
+    const bool clip = !std::isinf(content->clip_ratio);
+    if (!d_adj || !d_node || !flags || (clip && (!xhat_adj || !xhat_node))) { g_create_err = std::string(me) + "null argument (d_adj, d_node, flags; with a clip also xhat_adj, xhat_node)"; return DSG_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    const Dims d{B, N, c_adj, c_node};
+    const int K = content->n_items, Cl = content->node_chans;
+    const size_t bk = (size_t)B * K, n_lab = bk * Cl, n_pred = bk * c_adj, n_tgt = 2 * n_lab + n_pred + 3 * bk;
+    const size_t sa = (size_t)B * c_adj * N * N, sl = (size_t)B * N * Cl;
+    ContentParams *d_par = nullptr; double *d_ref = nullptr, *d_st = nullptr; float *d_tgt = nullptr, *d_sa = nullptr, *d_sl = nullptr;
+    const int cgrid = content_grid_items(K);
+    hipError_t e = hipMalloc((void **)&d_par, sizeof(ContentParams));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_ref, sizeof(double) * (size_t)B);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_tgt, sizeof(float) * n_tgt);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_sa, sizeof(float) * sa);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_sl, sizeof(float) * sl);
+    if (e == hipSuccess && cgrid) e = hipMalloc((void **)&d_st, sizeof(double) * (size_t)B * CONTENT_STATS_PER_GRAPH);
+    float *t_subj = d_tgt, *t_obj = d_tgt + n_lab, *t_pred = d_tgt + 2 * n_lab, *t_w = d_tgt + 2 * n_lab + n_pred;
+    if (e == hipSuccess) e = hipMemcpyAsync(t_subj, content->subj, sizeof(float) * n_lab, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(t_obj, content->obj, sizeof(float) * n_lab, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(t_pred, content->pred, sizeof(float) * n_pred, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(t_w, content->w_spo, sizeof(float) * 3 * bk, hipMemcpyHostToDevice, s);
+    const ContentParams par{content->w_content, content->tau, clip ? content->clip_ratio : 0.f, K, Cl, 0, t_subj, t_obj, t_pred, t_w, nullptr, nullptr,
+                            mask_adj, mask_node};
+    if (e == hipSuccess) e = hipMemcpyAsync(d_par, &par, sizeof(ContentParams), hipMemcpyHostToDevice, s);
+    bool ok = e == hipSuccess;
+    if (ok && clip) ok = launch_graph_diff_norm(CStatePtrs{xhat_adj, xhat_node}, CStatePtrs{d_adj, d_node}, flags, d_ref, d, s);
+    if (ok) ok = launch_content_guide(d_par, nullptr, nullptr, coef, d_adj, d_node, flags, clip ? d_ref : nullptr, false,
+                                      ContentOut{d_sa, d_sl, grad_adj, grad_label, loss, item_loss, factor, norms, best}, cgrid, d_st, d, s);
+    if (ok && (d_guided_adj || d_guided_node)) launch_content_apply(d_adj, d_node, d_sa, d_sl, flags, d_guided_adj, d_guided_node, Cl, d, s);
+    if (ok && shift_adj) e = hipMemcpyAsync(shift_adj, d_sa, sizeof(float) * sa, hipMemcpyDeviceToDevice, s);
+    if (ok && e == hipSuccess && shift_label) e = hipMemcpyAsync(shift_label, d_sl, sizeof(float) * sl, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(s);   // par and the caller's arrays are host sources of async copies: wait before they leave scope
+    (void)hipFree(d_par); (void)hipFree(d_ref); (void)hipFree(d_tgt); (void)hipFree(d_sa); (void)hipFree(d_sl); (void)hipFree(d_st);
+    if (e != hipSuccess || es != hipSuccess) { g_create_err = me + std::string(hipGetErrorString(e != hipSuccess ? e : es)); return DSG_ERR_HIP; }
+    if (!ok) { g_create_err = std::string(me) + "shape refused"; return DSG_ERR_INVALID; }
+    return DSG_OK;
 }
 
 int dsg_debug_box_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,

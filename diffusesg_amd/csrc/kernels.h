@@ -452,6 +452,44 @@ void launch_heun_tab_guided(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const
                             const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
 void launch_multistep_tab_guided(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const float *shift, const float *shift_prev, const StepRow *tab,
                                  const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
+// ---- content guidance (guide_content_kernels.hip; dsg_sample_guided_content) ----
+// What a content-guided step body reads, at a fixed device address that the body bakes; the run rewrites the contents.  w: the weight
+// of L_content; K items per graph, Cl label channels; subj / obj [B,K,Cl], pred [B,K,Ca], w_spo [B,K,3] (a_s, a_o, a_p): workspace
+// copies of the caller's host arrays; coef [T]: c_i per SCHEDULE index; trace [L,B] or null; mask_adj [B,Ca,N,N] / mask_node [B,N,Cn]
+// or null: the known masks of a conditioned run -- the shift is zero there
+constexpr int CONTENT_MAX_ITEMS = 16;
+struct ContentParams { float w, tau, clip_ratio; int K, Cl, pad; const float *subj, *obj, *pred, *w_spo; const float *coef; float *trace;
+                       const uint8_t *mask_adj, *mask_node; };
+// outputs of the content kernel; every pointer but the two shifts may be null.  shift_adj [B,Ca,N,N] / shift_label [B,N,Cl] = f_b c w g as
+// the update subtracts it, grad_* = g, loss [B], item_loss [B,K], factor [B] = f_b, norms [B,2] = (||c w g||, ||x_hat - D||; the second 0
+// without clip), best [B,K,2] = the pair with the largest pi_k (lowest flat index among equals; -1, -1: no live pair, inactive item)
+struct ContentOut { float *shift_adj, *shift_label, *grad_adj, *grad_label, *loss, *item_loss, *factor, *norms; int *best; };
+// One block per graph; c = P->coef[tab[ctl->step].sched] (tab null: coef_direct); f_b from ref_norm2 [B] (launch_graph_diff_norm; null:
+// unclipped).  stage1: also writes the trace row of the executed step.  false: shape refused (N > GUIDE_MAX_N, Cn < 5)
+// grid_items 0: that one launch; grid_items = K: the grid form -- K x B blocks for the item phase, N^2 / 512 x B blocks for the
+// pair-major phase, then one block per graph for the label channels, the norm and the clip; `stats` holds CONTENT_STATS_PER_GRAPH
+// doubles per graph between the launches.  The same arithmetic in the same order: the same bits.  content_grid_items(K): the form
+// a run takes, 0 or K
+constexpr int CONTENT_STAT_DOUBLES = 4 + 4 * 64, CONTENT_GRID_MIN_ITEMS = 1;
+constexpr size_t CONTENT_STATS_PER_GRAPH = (size_t)CONTENT_MAX_ITEMS * CONTENT_STAT_DOUBLES + 64 * 64;
+int content_grid_items(int K);
+bool launch_content_guide(const ContentParams *P, const StepRow *tab, const RunCtl *ctl, float coef_direct, const float *D_adj, const float *D_node,
+                          const uint8_t *flags, const double *ref_norm2, bool stage1, ContentOut o, int grid_items, double *stats, Dims d,
+                          hipStream_t s);
+// out = valid ? D - shift : 0 (adjacency entries and label channels) -- D~ on its own, for dsg_debug_content_guide; either output may be null
+void launch_content_apply(const float *D_adj, const float *D_node, const float *sh_adj, const float *sh_label, const uint8_t *flags,
+                          float *out_adj, float *out_node, int Cl, Dims d, hipStream_t s);
+// the content shift of one stage as the update operations read it: adjacency entries and label channels (c < P->Cl) of the node estimate
+struct ContentShiftPtrs { const float *adj, *label; };
+// the guided updates with both shifts, box [B,N,4] and content: kernels of their own next to the box-only ones above
+void launch_euler_tab_guided2(CStatePtrs xhat, CStatePtrs D, const float *shift, ContentShiftPtrs cs, const ContentParams *P, const StepRow *tab,
+                              const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
+void launch_heun_tab_guided2(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const float *shift1, const float *shift2, ContentShiftPtrs cs1,
+                             ContentShiftPtrs cs2, const ContentParams *P, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
+                             StatePtrs x, Dims d, hipStream_t s);
+void launch_multistep_tab_guided2(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const float *shift, const float *shift_prev,
+                                  ContentShiftPtrs cs, ContentShiftPtrs cs_prev, const ContentParams *P, const StepRow *tab, const RunCtl *ctl,
+                                  const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s);
 // dst[0..n) = table[tab[step].sched][0..n)  (the (scale,shift) row of the step's schedule index), and ctl->step += 1
 void launch_step_row(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst, hipStream_t s);
 void launch_step_advance(RunCtl *ctl, hipStream_t s);

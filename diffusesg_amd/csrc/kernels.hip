@@ -2791,8 +2791,23 @@ struct BoxShift {
         return c >= 0 ? FSUB(dv, p[(e.off / d.Cn) * 4 + c]) : dv;
     }
 };
-struct EulerGuided {
-    CStatePtrs xhat, D; BoxShift g; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+// Content guidance (guide_content_kernels.hip) shifts adjacency entries and the label channels c < Cl of the node estimate; box and
+// label channels are disjoint, so an entry meets at most one of the two shifts.  Cl is read from the run's parameter block (a uniform,
+// cached load per wave): a captured body serves runs with another Cl.  pl is [B,N,Cl]: the row stride is Cl, not Cn - 4
+struct ContentShift {
+    const float *pa, *pl; const ContentParams *P;
+    __device__ float operator()(float dv, const ElemIdx &e, const Dims &d) const {
+        if (e.is_adj) return FSUB(dv, pa[e.off]);
+        const int Cl = P->Cl, c = (int)(e.off % d.Cn);
+        return c < Cl ? FSUB(dv, pl[(e.off / d.Cn) * Cl + c]) : dv;
+    }
+};
+struct BothShift {
+    BoxShift box; ContentShift content;
+    __device__ float operator()(float dv, const ElemIdx &e, const Dims &d) const { return content(box(dv, e, d), e, d); }
+};
+template <class G> struct EulerGuided {
+    CStatePtrs xhat, D; G g; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
     __device__ StepRow uniform() const { return tab[ctl->step]; }
     __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &d) const {
         return euler_update(r, ld(xhat, e), g(ld(D, e), e, d));
@@ -2800,10 +2815,14 @@ struct EulerGuided {
 };
 void launch_euler_tab_guided(CStatePtrs xhat, CStatePtrs D, const float *shift, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
                              StatePtrs x, Dims d, hipStream_t s) {
-    launch_elem(EulerGuided{xhat, D, {shift}, tab, ctl, flags}, x, d, s);
+    launch_elem(EulerGuided<BoxShift>{xhat, D, {shift}, tab, ctl, flags}, x, d, s);
 }
-struct HeunGuided {
-    CStatePtrs xhat, D1, D2; BoxShift g1, g2; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+void launch_euler_tab_guided2(CStatePtrs xhat, CStatePtrs D, const float *shift, ContentShiftPtrs cs, const ContentParams *P, const StepRow *tab,
+                              const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
+    launch_elem(EulerGuided<BothShift>{xhat, D, {{shift}, {cs.adj, cs.label, P}}, tab, ctl, flags}, x, d, s);
+}
+template <class G> struct HeunGuided {
+    CStatePtrs xhat, D1, D2; G g1, g2; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
     __device__ StepRow uniform() const { return tab[ctl->step]; }
     __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &d) const {
         return heun_update(r, ld(xhat, e), g1(ld(D1, e), e, d), g2(ld(D2, e), e, d));
@@ -2811,10 +2830,16 @@ struct HeunGuided {
 };
 void launch_heun_tab_guided(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const float *shift1, const float *shift2, const StepRow *tab,
                             const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
-    launch_elem(HeunGuided{xhat, D1, D2, {shift1}, {shift2}, tab, ctl, flags}, x, d, s);
+    launch_elem(HeunGuided<BoxShift>{xhat, D1, D2, {shift1}, {shift2}, tab, ctl, flags}, x, d, s);
 }
-struct MultistepGuided {   // D~ + c (D~ - D~prev): the extrapolation reads the guided estimates of both steps
-    CStatePtrs xhat, D, Dprev; BoxShift g, gprev; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
+void launch_heun_tab_guided2(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const float *shift1, const float *shift2, ContentShiftPtrs cs1,
+                             ContentShiftPtrs cs2, const ContentParams *P, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,
+                             StatePtrs x, Dims d, hipStream_t s) {
+    launch_elem(HeunGuided<BothShift>{xhat, D1, D2, {{shift1}, {cs1.adj, cs1.label, P}}, {{shift2}, {cs2.adj, cs2.label, P}}, tab, ctl, flags},
+                x, d, s);
+}
+template <class G> struct MultistepGuided {   // D~ + c (D~ - D~prev): the extrapolation reads the guided estimates of both steps
+    CStatePtrs xhat, D, Dprev; G g, gprev; const StepRow *tab; const RunCtl *ctl; const uint8_t *flags;
     __device__ StepRow uniform() const { return tab[ctl->step]; }
     __device__ float operator()(const StepRow &r, const ElemIdx &e, size_t, const Dims &d) const {
         return multistep_update(r, ld(xhat, e), g(ld(D, e), e, d), gprev(ld(Dprev, e), e, d));
@@ -2822,7 +2847,13 @@ struct MultistepGuided {   // D~ + c (D~ - D~prev): the extrapolation reads the 
 };
 void launch_multistep_tab_guided(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const float *shift, const float *shift_prev, const StepRow *tab,
                                  const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
-    launch_elem(MultistepGuided{xhat, D, Dprev, {shift}, {shift_prev}, tab, ctl, flags}, x, d, s);
+    launch_elem(MultistepGuided<BoxShift>{xhat, D, Dprev, {shift}, {shift_prev}, tab, ctl, flags}, x, d, s);
+}
+void launch_multistep_tab_guided2(CStatePtrs xhat, CStatePtrs D, CStatePtrs Dprev, const float *shift, const float *shift_prev,
+                                  ContentShiftPtrs cs, ContentShiftPtrs cs_prev, const ContentParams *P, const StepRow *tab, const RunCtl *ctl,
+                                  const uint8_t *flags, StatePtrs x, Dims d, hipStream_t s) {
+    launch_elem(MultistepGuided<BothShift>{xhat, D, Dprev, {{shift}, {cs.adj, cs.label, P}}, {{shift_prev}, {cs_prev.adj, cs_prev.label, P}}, tab,
+                                           ctl, flags}, x, d, s);
 }
 // the table has one row per SCHEDULE index; the executed step's row names it (a resampling walk visits an index more than once)
 __global__ void step_row_kernel(const float *table, int n, const StepRow *tab, const RunCtl *ctl, float *dst) {

@@ -24,6 +24,10 @@ pairs and their kinds given as a matrix or decoded from the adjacency estimate t
 grad_{x_hat} L(D) = (c_skip I + c_out dF/dx_hat)^T dL/dD, evaluated by a HIP kernel with analytic gradients -- no backward, no
 training-form forward, step graphs and walks as in `sample()`.  It is an approximation of the shift above, exact only where the
 network's Jacobian vanishes; `BoxGuide.torch_loss` hands the same loss to `guided_sample`, the through-the-network form.
+
+`ContentGuide` is the in-loop guide of the label and predicate channels (`sample_guided(content=...)`, `dsg_sample_guided_content`,
+DESIGN.md §17): "samples that contain these triplets", a soft minimum over all node slots; `content_loss` is its torch form,
+`label_codes` the value-space codes it aims at, `items_present` the check on decoded graphs.
 """
 from __future__ import annotations
 
@@ -384,6 +388,198 @@ class BoxGuide(object):
                 total = total + fn(D_adj, D_node) * wgt
             return total
         return loss
+
+
+# ---- content guidance: samples that contain given triplets -------------------------------------------
+def label_codes(n_type, encoding, chans):
+    """float32 [n_type, chans]: the value-space code of every integer label 0..n_type-1 under `encoding`, `dsg_encode`'s three rules --
+    'bits': the MSB-first binary digits b of the label over `chans` channels, 2 b - 1; 'one_hot': 2 onehot - 1 over chans = n_type
+    channels; 'ddpm': 2 i / (n_type - 1) - 1 in one channel, float32 operation by operation."""
+    n_type, chans = int(n_type), int(chans)
+    if n_type < 1 or chans < 1:
+        raise ValueError(f"label_codes: n_type = {n_type} and chans = {chans} must be >= 1")
+    q = np.arange(n_type, dtype=np.int64)
+    if encoding == "bits":
+        if chans > 30 or (1 << chans) < n_type:
+            raise ValueError(f"label_codes: {n_type} labels do not fit {chans} bits")
+        b = (q[:, None] >> (chans - 1 - np.arange(chans))[None, :]) & 1
+        return np.where(b != 0, np.float32(1), np.float32(-1)).astype(np.float32)
+    if encoding == "one_hot":
+        if chans != n_type:
+            raise ValueError(f"label_codes: one_hot needs chans = n_type, got {chans} and {n_type}")
+        return np.where(np.eye(n_type, dtype=bool), np.float32(1), np.float32(-1)).astype(np.float32)
+    if encoding == "ddpm":
+        if chans != 1 or n_type < 2:
+            raise ValueError(f"label_codes: ddpm needs one channel and at least two labels, got {chans} and {n_type}")
+        v = (2 * q).astype(np.float32) / np.float32(n_type - 1) - np.float32(1)
+        return v.astype(np.float32)[:, None]
+    raise ValueError("encoding should be 'ddpm', 'bits' or 'one_hot'")
+
+
+def _code_chans(n_type, encoding, chans, what):
+    """the channel count `encoding` implies for n_type labels in a tensor with `chans` channels for them; ValueError if it does not fit"""
+    if (encoding == "one_hot" and chans != n_type) or (encoding == "ddpm" and chans != 1) or \
+            (encoding == "bits" and (chans < 1 or chans > 30 or (1 << chans) < n_type)):
+        raise ValueError(f"ContentGuide: {n_type} {what} in {encoding} do not fit {chans} channels")
+    return chans
+
+
+def content_loss(subj, obj, pred, w_spo, node_flags, tau):
+    """L_content as a differentiable torch closure loss(D_adj, D_node) -> scalar (the through-the-network form of content guidance):
+    subj / obj [B, K, Cl], pred [B, K, C_adj] targets in value space, w_spo [B, K, 3] = (a_s, a_o, a_p) >= 0.  Per graph and item the soft
+    minimum -tau log mean exp(-d / tau) over the live ordered pairs (i != j, both valid) of
+        d(i, j) = a_s |D_node[i, :Cl] - s|^2 + a_o |D_node[j, :Cl] - o|^2 + a_p |D_adj[:, i, j] - p|^2,
+    summed over active items (a weight > 0) and graphs; a graph without a live pair adds exactly 0.  Entries that are not live are
+    selected away before they are read."""
+    tau = float(tau)
+    if not tau > 0:
+        raise ValueError("content_loss: tau must be positive")
+    subj, obj, pred, w_spo = (torch.as_tensor(v) for v in (subj, obj, pred, w_spo))
+    Cl = subj.shape[-1]
+
+    def loss(D_adj, D_node):
+        dt, dv = D_node.dtype, D_node.device
+        s, o, p, a = (v.to(device=dv, dtype=dt) for v in (subj, obj, pred, w_spo))
+        n = D_node.shape[1]
+        f = node_flags.to(device=dv).bool()
+        live = f[:, :, None] & f[:, None, :] & ~torch.eye(n, dtype=torch.bool, device=dv)[None]          # [B, N, N]
+        zero = torch.zeros((), dtype=dt, device=dv)
+        Dn = torch.where(f[:, :, None], D_node[..., :Cl], zero)
+        Da = torch.where(live[:, None], D_adj, zero)
+        ds = ((Dn[:, None] - s[:, :, None]) ** 2).sum(-1)                                                 # [B, K, N]
+        do = ((Dn[:, None] - o[:, :, None]) ** 2).sum(-1)
+        dp = torch.stack([((Da - p[:, k, :, None, None]) ** 2).sum(1) for k in range(p.shape[1])], dim=1)  # [B, K, N, N]
+        d = a[:, :, 0, None, None] * ds[:, :, :, None] + a[:, :, 1, None, None] * do[:, :, None, :] + a[:, :, 2, None, None] * dp
+        cnt = live.flatten(1).sum(1)
+        has = cnt > 0
+        z = torch.where(live[:, None], -d / tau, torch.full_like(d, -float("inf")))
+        z = torch.where(has[:, None, None, None], z, torch.zeros_like(z))     # graphs without a pair: finite, dropped below
+        soft = -tau * (torch.logsumexp(z.flatten(2), dim=-1) - torch.log(cnt.clamp(min=1).to(dt))[:, None])   # [B, K]
+        on = (a.sum(-1) > 0) & has[:, None]
+        return torch.where(on, soft, torch.zeros_like(soft)).sum()
+    return loss
+
+
+class ContentGuide(object):
+    """"Samples that contain these triplets": the loss of content guidance inside the library's loop (`sample_guided(content=...)`,
+    `dsg_sample_guided_content`) -- a soft minimum over all node slots on the label and predicate channels, so that the
+    caller names labels, never slots.
+      items: per graph a list of (subject_label | None, predicate | None, object_label | None), integers as `io.encode` takes them;
+             None drops that term: (l, None, None) is "some node has label l", (None, p, None) "some pair carries predicate p".  Shorter
+             lists are padded with inactive items; at most `lib.CONTENT_MAX_ITEMS` per graph.
+      n_node_type, n_adj_type, node_encoding, edge_encoding: how labels and predicates are coded (`label_codes`).
+      weight: w_content, the weight of the term; tau: the temperature of the soft minimum, in units of squared code distance (two 'bits'
+             codes that differ in one bit are 4 apart); clip_ratio: the content shift's own clip against ||x_hat - D||, None: unclipped;
+      term_weights: (subject, predicate, object) weights of the three squared distances of an item.
+    No trained weights ship with the project: what this does to sample quality is not validated."""
+
+    def __init__(self, items, n_node_type, n_adj_type, node_encoding="bits", edge_encoding="bits", weight=1.0, tau=0.5, clip_ratio=1.0,
+                 term_weights=(1.0, 1.0, 1.0)):
+        self.n_node_type, self.n_adj_type = int(n_node_type), int(n_adj_type)
+        self.node_encoding, self.edge_encoding = node_encoding, edge_encoding
+        for e in (node_encoding, edge_encoding):
+            if e not in _lib.ENCODINGS:
+                raise ValueError("encoding should be 'ddpm', 'bits' or 'one_hot'")
+        self.weight, self.tau = float(np.float32(weight)), float(np.float32(tau))   # as the descriptor holds them: float32
+        if not np.isfinite(self.weight):
+            raise ValueError(f"ContentGuide: weight = {weight} is not finite")
+        if not (self.tau > 0 and np.isfinite(self.tau)):
+            raise ValueError(f"ContentGuide: tau = {tau} must be positive")
+        if clip_ratio is not None and not float(clip_ratio) >= 0:
+            raise ValueError(f"ContentGuide: clip_ratio must be >= 0 or None, got {clip_ratio}")
+        self.clip_ratio = None if clip_ratio is None else float(np.float32(clip_ratio))
+        tw = tuple(float(v) for v in term_weights)
+        if len(tw) != 3 or not all(np.isfinite(v) and v >= 0 for v in tw):
+            raise ValueError(f"ContentGuide: term_weights = {term_weights} must be three finite weights >= 0 (subject, predicate, object)")
+        self.term_weights = tw
+        self.items = []
+        for b, lst in enumerate(items):
+            row = []
+            for it in lst:
+                if len(it) != 3:
+                    raise ValueError(f"ContentGuide: item {it} of graph {b} is not (subject, predicate, object)")
+                s, p, o = (None if v is None else int(v) for v in it)
+                for v, k, what in ((s, self.n_node_type, "subject label"), (o, self.n_node_type, "object label"), (p, self.n_adj_type, "predicate")):
+                    if v is not None and not 0 <= v < k:
+                        raise ValueError(f"ContentGuide: {what} {v} of graph {b} is outside 0..{k - 1}")
+                row.append((s, p, o))
+            if len(row) > _lib.CONTENT_MAX_ITEMS:
+                raise ValueError(f"ContentGuide: graph {b} has {len(row)} items, at most {_lib.CONTENT_MAX_ITEMS}")
+            self.items.append(row)
+        self.n_items = max(1, max((len(r) for r in self.items), default=1))
+
+    def tensors(self, c_adj, node_chans):
+        """(subj [B, K, Cl], obj [B, K, Cl], pred [B, K, C_adj], w_spo [B, K, 3] = (a_s, a_o, a_p)) float32 NumPy arrays; a dropped term
+        and a padding item have weight 0 and an all-zero target"""
+        Cl = _code_chans(self.n_node_type, self.node_encoding, int(node_chans), "node labels")
+        Ca = _code_chans(self.n_adj_type, self.edge_encoding, int(c_adj), "predicates")
+        ncode, pcode = label_codes(self.n_node_type, self.node_encoding, Cl), label_codes(self.n_adj_type, self.edge_encoding, Ca)
+        B, K = len(self.items), self.n_items
+        subj, obj = np.zeros((B, K, Cl), np.float32), np.zeros((B, K, Cl), np.float32)
+        pred, w = np.zeros((B, K, Ca), np.float32), np.zeros((B, K, 3), np.float32)
+        a_s, a_p, a_o = self.term_weights
+        for b, row in enumerate(self.items):
+            for k, (s, p, o) in enumerate(row):
+                if s is not None:
+                    subj[b, k], w[b, k, 0] = ncode[s], a_s
+                if o is not None:
+                    obj[b, k], w[b, k, 1] = ncode[o], a_o
+                if p is not None:
+                    pred[b, k], w[b, k, 2] = pcode[p], a_p
+        return subj, obj, pred, w
+
+    def descriptor(self, B, cfg, node_chans=None):
+        """(`lib.DsgContentCfg`, the host arrays it points at -- keep them alive over the call) for a batch of B graphs of the network
+        configuration `cfg` (c_adj, c_node); node_chans defaults to c_node - 4, the label channels in front of the box"""
+        if len(self.items) != B:
+            raise ValueError(f"ContentGuide: items for {len(self.items)} graphs, the batch has {B}")
+        Cl = int(cfg.c_node) - 4 if node_chans is None else int(node_chans)
+        if Cl < 1 or Cl > int(cfg.c_node) - 4:
+            raise ValueError(f"ContentGuide: node_chans = {Cl} must be 1..C_node-4 = {int(cfg.c_node) - 4}")
+        keep = tuple(np.ascontiguousarray(v) for v in self.tensors(cfg.c_adj, Cl))
+        clip = _lib.GUIDE_CLIP_NONE if self.clip_ratio is None else self.clip_ratio
+        c = _lib.DsgContentCfg(self.weight, self.tau, clip, self.n_items, Cl, 0, *(v.ctypes.data for v in keep))
+        return c, keep
+
+    def torch_loss(self, node_flags, node_chans=None):
+        """weight * L_content as a `guide.py` closure loss(D_adj, D_node) -> scalar, for `guided_sample` and the tests; the channel
+        counts are read off the tensors it is called with (node_chans defaults to C_node - 4)"""
+        wgt, fns = self.weight, {}
+
+        def loss(D_adj, D_node):
+            key = (int(D_adj.shape[1]), int(D_node.shape[-1]) - 4 if node_chans is None else int(node_chans))
+            if key not in fns:
+                fns[key] = content_loss(*self.tensors(*key), node_flags, self.tau)
+            return fns[key](D_adj, D_node) * wgt
+        return loss
+
+
+def items_present(q_adj, q_node, node_flags, items):
+    """Host check on decoded integer graphs (q_adj [B, N, N], q_node [B, N] as `io.decode` returns them): bool [B, K], K the longest
+    item list -- whether graph b has an ordered pair (i, j), i != j, both valid, with q_node[i] = subject, q_adj[i, j] = predicate and
+    q_node[j] = object, a None leaving its term free.  Like the loss it reads pairs: a graph with fewer than two valid nodes holds
+    nothing.  Padding and all-None items count as present."""
+    qa, qn, f = (np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in (q_adj, q_node, node_flags))
+    B, n = qn.shape[0], qn.shape[1]
+    if len(items) != B:
+        raise ValueError(f"items_present: items for {len(items)} graphs, the batch has {B}")
+    K = max(1, max((len(r) for r in items), default=1))
+    out = np.ones((B, K), dtype=bool)
+    f = f.astype(bool)
+    for b, row in enumerate(items):
+        live = f[b][:, None] & f[b][None, :] & ~np.eye(n, dtype=bool)
+        for k, (s, p, o) in enumerate(row):
+            if s is None and p is None and o is None:
+                continue
+            hit = live.copy()
+            if s is not None:
+                hit &= (qn[b] == int(s))[:, None]
+            if o is not None:
+                hit &= (qn[b] == int(o))[None, :]
+            if p is not None:
+                hit &= qa[b].reshape(n, n) == int(p)
+            out[b, k] = bool(hit.any())
+    return out
 
 
 # ---- host arithmetic of the guided loop (no GPU needed) -------------------------------------------------------------

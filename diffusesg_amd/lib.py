@@ -20,7 +20,7 @@ EXPORTS = [
     "dsg_eval_bbox_f1", "dsg_eval_type_hist", "dsg_eval_degree_hist", "dsg_eval_hist_mmd", "dsg_sgstat_triplet_counts", "dsg_sgstat_layout",
     "dsg_sgstat_f1_rowstats", "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
     "dsg_sample_seeded", "dsg_gen_noise_seeded", "dsg_precond_vjp", "dsg_ode_run", "dsg_ode_evals", "dsg_guide_coef", "dsg_sample_guided",
-    "dsg_sample_guided_rel", "dsg_option_info", "dsg_create_patch", "dsg_train_set_precision", "dsg_train_get_precision",
+    "dsg_sample_guided_rel", "dsg_sample_guided_content", "dsg_option_info", "dsg_create_patch", "dsg_train_set_precision", "dsg_train_get_precision",
 ]
 
 TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}   # DSG_TRAIN_F32 / DSG_TRAIN_BF16 of include/dsg.h
@@ -77,6 +77,14 @@ class DsgRelCfg(C.Structure):
                 ("reserved", C.c_int32), ("kinds", C.c_void_p), ("pred_kind", C.c_void_p)]
 
 
+class DsgContentCfg(C.Structure):
+    """dsg_content_cfg of include/dsg.h (dsg_sample_guided_content, dsg_debug_content_guide): subj / obj / pred / w_spo host pointers"""
+    _fields_ = [("w_content", C.c_float), ("tau", C.c_float), ("clip_ratio", C.c_float), ("n_items", C.c_int32), ("node_chans", C.c_int32),
+                ("reserved", C.c_int32), ("subj", C.c_void_p), ("obj", C.c_void_p), ("pred", C.c_void_p), ("w_spo", C.c_void_p)]
+
+
+CONTENT_MAX_ITEMS = 16   # DSG_CONTENT_MAX_ITEMS
+
 REL_GIVEN, REL_DECODED = 0, 1                                  # DSG_REL_GIVEN / DSG_REL_DECODED
 REL_NONE, REL_LEFT_OF, REL_RIGHT_OF, REL_ABOVE, REL_BELOW, REL_INSIDE, REL_CONTAINS, REL_ON = range(8)   # DSG_REL_* kinds
 
@@ -98,6 +106,7 @@ DEBUG_EXPORTS = [
     "dsg_debug_dedup_qkv_lists", "dsg_debug_qk_split", "dsg_debug_readout_tiles", "dsg_debug_t_assemble_bwd", "dsg_debug_patch_embed_f32",
     "dsg_debug_assemble_f32", "dsg_debug_readout_f32", "dsg_debug_head_f32", "dsg_debug_row_f32", "dsg_debug_window_broadcast_f32",
     "dsg_debug_window_harvest_f32", "dsg_debug_graph_dot", "dsg_debug_poison", "dsg_debug_box_guide", "dsg_debug_box_guide_rel",
+    "dsg_debug_content_guide",
     "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp", "dsg_debug_patch_forms",
     "dsg_debug_assemble_patch_f32", "dsg_debug_head_patch_f32", "dsg_debug_patch_embed_patch_f32", "dsg_debug_readout_patch_f32",
     "dsg_debug_t_gemm_lp", "dsg_debug_t_cast_lp", "dsg_debug_train_routes", "dsg_debug_gemm_bx_args", "dsg_debug_mlp_bx_args",
@@ -161,6 +170,7 @@ def _declare_debug(L: C.CDLL) -> None:
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.dsg_debug_box_guide.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(DsgGuideCfg), C.c_float, vp, vp, vp, vp, vp, vp, vp]
     L.dsg_debug_box_guide_rel.argtypes = L.dsg_debug_box_guide.argtypes + [C.POINTER(DsgRelCfg), vp]
+    L.dsg_debug_content_guide.argtypes = [i32, i32, i32, i32] + [vp] * 7 + [C.POINTER(DsgContentCfg), C.c_float] + [vp] * 12
     L.dsg_debug_tap.argtypes = [vp, C.c_char_p, vp, i64]
     L.dsg_debug_clear_taps.argtypes = [vp]
     L.dsg_debug_clear_taps.restype = None
@@ -287,6 +297,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_guide_coef.argtypes = [C.POINTER(DsgSamplerCfg), vp, vp, i32]
     L.dsg_guide_coef.restype = i32
     L.dsg_sample_guided_rel.argtypes = L.dsg_sample_guided.argtypes + [C.POINTER(DsgRelCfg)]
+    L.dsg_sample_guided_content.argtypes = L.dsg_sample_guided_rel.argtypes + [C.POINTER(DsgContentCfg), vp]
     L.dsg_walk_steps.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, vp, i32]
     L.dsg_walk_steps.restype = i32
     L.dsg_multistep_coef.argtypes = [C.POINTER(DsgSamplerCfg), C.POINTER(DsgWalkCfg), vp, i32]

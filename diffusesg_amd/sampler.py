@@ -270,7 +270,7 @@ class NodeAdjEDMSamplerHip(object):
     @torch.no_grad()
     def sample_guided(self, model, node_flags, guide, scale, *, clip_ratio=1.0, known=None,
                       resample=None, resample_range=None, start_step=0, base_adjs=None, base_nodes=None,
-                      graph_seeds=None, coin_seed=None, return_loss_trace=False,
+                      graph_seeds=None, coin_seed=None, return_loss_trace=False, content=None,
                       init_adjs=None, init_nodes=None, sanity_check_gt_adjs=None, sanity_check_gt_nodes=None,
                       flag_interim_adjs=False, max_num_interim_adjs=None, flag_adj_multi_channel=False,
                       num_node_chan=None, num_edge_chan=None, churn_noise=None, coins=None, seed=None, return_device=False):
@@ -284,13 +284,18 @@ class NodeAdjEDMSamplerHip(object):
         `sample_known` (known entries win and stay bit-exact); resample / resample_range / start_step / base_*: its walk;
         graph_seeds / coin_seed and everything after them: as in `sample()` (sanity_check_gt_*: the sanity-check mode, the guide then
         runs on the ground truth; not with known or graph_seeds).  Channel counts default to the network's.
+        content: None, or a `diffusesg_amd.guide.ContentGuide` -- content guidance (`dsg_sample_guided_content`): a second
+        shift, on the label and predicate channels, towards samples that contain the guide's triplets; it shares `scale` with the box
+        terms and has a weight, a temperature and a clip of its own.  A content-only run passes guide=BoxGuide().
         scale = 0 gives `sample()` / `sample_known()` exactly.  Returns what `sample()` returns; with return_loss_trace a float32 CPU
-        tensor [L, B] more: L(D) at the stage-1 call of every executed step."""
-        from .guide import BoxGuide, guidance_weights
+        tensor [L, B] more: L(D) at the stage-1 call of every executed step -- and, with `content`, a second one behind it: L_content(D)."""
+        from .guide import BoxGuide, ContentGuide, guidance_weights
         if isinstance(model, (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)):
             model = model.module
         if not isinstance(guide, BoxGuide):
             raise TypeError("sample_guided needs a diffusesg_amd.guide.BoxGuide (arbitrary losses: guide.guided_sample)")
+        if content is not None and not isinstance(content, ContentGuide):
+            raise TypeError("sample_guided: content must be a diffusesg_amd.guide.ContentGuide or None")
         if clip_ratio is not None and not float(clip_ratio) >= 0:
             raise ValueError(f"clip_ratio must be >= 0 or None, got {clip_ratio}")
         w = guidance_weights(scale, self.num_steps)
@@ -308,14 +313,15 @@ class NodeAdjEDMSamplerHip(object):
                                 cfg.c_node if num_node_chan is None and cfg is not None else num_node_chan,
                                 cfg.c_adj if num_edge_chan is None and cfg is not None else num_edge_chan,
                                 churn_noise, coins, seed, return_device, walk, graph_seeds, coin_seed,
-                                guide=(guide, w, clip_ratio, bool(return_loss_trace)))
+                                guide=(guide, w, clip_ratio, bool(return_loss_trace), content))
 
     def _sample_hip(self, model, node_flags, init_adjs, init_nodes, sanity_check_gt_adjs, sanity_check_gt_nodes, known,
                     flag_interim_adjs, max_num_interim_adjs, flag_adj_multi_channel, num_node_chan, num_edge_chan,
                     churn_noise, coins, seed, return_device, walk=None, graph_seeds=None, coin_seed=None, guide=None):
         """The loop inside libdsg.so: `dsg_sample`, or `dsg_sample_known` when `known` = (adjs, nodes, adj mask, node mask); with
         `walk` (the walk keywords of `sample_known`) `dsg_sample_walk`; with `graph_seeds` `dsg_sample_seeded`, whatever else is given;
-        with `guide` = (BoxGuide, weights [T], clip_ratio, return_loss_trace) `dsg_sample_guided`, whatever else is given."""
+        with `guide` = (BoxGuide, weights [T], clip_ratio, return_loss_trace, ContentGuide | None) `dsg_sample_guided` (`_rel` with
+        relations, `_content` with a ContentGuide), whatever else is given."""
         if not isinstance(model, NodeAdjPrecondHip):
             raise TypeError("NodeAdjEDMSamplerHip needs the NodeAdjPrecondHip network returned by build_network()")
         gs = None
@@ -420,9 +426,9 @@ class NodeAdjEDMSamplerHip(object):
                 h.check(h.L.dsg_gen_noise(h.raw, B, p(fl), C.c_uint64(seed_v), 0, p(ia), p(inn), C.c_void_p(st)), "dsg_gen_noise")
         snap_args = (C.c_void_p(0 if snap_steps is None else snap_steps.ctypes.data),
                      0 if snap_steps is None else len(snap_steps), p(snap_a), p(snap_n))
-        trace = None
+        trace = ctrace = None
         if guide is not None:
-            bg, gw, clip_ratio, want_trace = guide
+            bg, gw, clip_ratio, want_trace, cg = guide
             gw = np.ascontiguousarray(gw, dtype=np.float32)
             gcfg, g_keep = bg.descriptor(B, n, dev, clip_ratio)   # shapes refused here, before anything is launched
             gcfg.weights = gw.ctypes.data
@@ -436,7 +442,14 @@ class NodeAdjEDMSamplerHip(object):
                       p(ia), p(inn), p(ba), p(bn), p(na), p(nn_), C.c_void_p(coins.ctypes.data),
                       p(ka), p(kn), p(ma), p(mn), *snap_args, C.byref(gcfg), p(ga), p(gn), p(trace),
                       p(oa), p(on), C.byref(stats), C.c_void_p(st))
-            if bg.relations is None:   # a guide without relations makes the call it made
+            if cg is not None:   # shapes and codes refused here, before anything is launched
+                ccfg, c_keep = cg.descriptor(B, cfg)
+                if want_trace:   # zeros: with weight = 0 the call is dsg_sample_guided_rel, which writes no content trace
+                    ctrace = torch.zeros((L, B), dtype=torch.float32, device=dev)
+                h.check(h.L.dsg_sample_guided_content(*g_args, None if rcfg is None else C.byref(rcfg), C.byref(ccfg), p(ctrace)),
+                        "dsg_sample_guided_content")
+                del c_keep
+            elif bg.relations is None:   # a guide without relations makes the call it made
                 h.check(h.L.dsg_sample_guided(*g_args), "dsg_sample_guided")
             else:
                 h.check(h.L.dsg_sample_guided_rel(*g_args, None if rcfg is None else C.byref(rcfg)), "dsg_sample_guided_rel")
@@ -472,7 +485,7 @@ class NodeAdjEDMSamplerHip(object):
             oa = oa[:, 0]
         if cfg.c_node == 1:
             on = on[..., 0]
-        extra = () if trace is None else (trace.cpu(),)
+        extra = () if trace is None else (trace.cpu(),) if ctrace is None else (trace.cpu(), ctrace.cpu())
         if return_device:
             return (oa, on) + extra if extra else (oa, on)
         adjs, nodes = oa.cpu(), on.cpu()

@@ -43,7 +43,8 @@ extern "C" {
  * "batch_invariant" were added without touching an existing argument list: still 4; so were the single-kernel test hooks,
  * dsg_ode_run / dsg_ode_evals, dsg_guide_cfg / dsg_sample_guided / dsg_guide_coef, dsg_rel_cfg / dsg_sample_guided_rel, and
  * dsg_option_info.  5 = the test and measurement hooks moved to dsg_debug.h (the same library exports them, this header no longer
- * declares them) and three bf16-pipeline hooks there took a `kernel` argument.  The number covers both headers. */
+ * declares them) and three bf16-pipeline hooks there took a `kernel` argument.  The number covers both headers.  dsg_content_cfg /
+ * dsg_sample_guided_content (and its test hook) were added without touching an existing argument list: still 5. */
 #define DSG_ABI_VERSION 5
 
 typedef enum {
@@ -401,6 +402,63 @@ int dsg_sample_guided_rel(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_wa
                           const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
                           const dsg_guide_cfg *guide, const float *gt_adj, const float *gt_node, float *loss_trace,
                           float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream, const dsg_rel_cfg *rel);
+
+/* Content guidance: steer samples to contain given triplets.  A loss on the LABEL channels of the node estimate (the
+ * first Cl = node_chans <= C_node - 4 channels of a row; the box comes last, as in dsg_decode / dsg_encode) and on the adjacency
+ * estimate, a soft minimum over all node slots so that the caller picks none.  Graph b has K = n_items items; item k is three targets in
+ * value space (dsg_encode's codes: s_k [Cl] the subject's label, o_k [Cl] the object's, p_k [C_adj] the predicate) and three weights
+ * a_s, a_o, a_p >= 0; all three 0: the item is inactive.  With Dn = D_node[..., :Cl], Da = D_adj (the estimate the guide is handed: after
+ * the valid mask and the known select; gt in the sanity-check mode) and the sums over the live ordered pairs (i, j), i != j, both nodes
+ * valid, P of them:
+ *     d_k(i,j) = a_s sum_c (Dn[i,c] - s_k[c])^2 + a_o sum_c (Dn[j,c] - o_k[c])^2 + a_p sum_c (Da[c,i,j] - p_k[c])^2
+ *     L_k      = -tau log((1/P) sum_(i,j) exp(-d_k(i,j) / tau))          (max-subtracted; min d_k <= L_k <= min d_k + tau log P)
+ *     L        = sum_k L_k                                                (a graph with P = 0 contributes exactly 0 and a zero gradient)
+ *     pi_k     = softmax over the live pairs of -d_k / tau
+ *     g_adj[c,i,j] = sum_k pi_k(i,j) 2 a_p (Da[c,i,j] - p_k[c])
+ *     g_node[i,c]  = sum_k (sum_j pi_k(i,j)) 2 a_s (Dn[i,c] - s_k[c]) + (sum_j pi_k(j,i)) 2 a_o (Dn[i,c] - o_k[c])     (c < Cl, else 0)
+ * a_o = a_p = 0 is "some node has this label", a_s = a_o = 0 "some pair carries this predicate".  Everything is evaluated in float64
+ * from the float32 inputs and rounded once; fixed-order sums, no atomics, nothing depends on B.  Then, with c_i of dsg_guide_coef (the
+ * schedule weights stay in guide->weights),
+ *     shift = (c_i * w_content) g, zero at entries whose mask_adj / mask_node bit is set (known entries win and stay bit-exact), at padded
+ *             rows and columns, on the adjacency diagonal and at node channels >= Cl
+ *     f_b   = the content shift's OWN clip factor: dsg_guide_cfg's form on the same ||x_hat_b - D_b||, against content->clip_ratio
+ *     D~    = D - f_b shift
+ * Box channels and label channels are disjoint: the box shift and the content shift never meet in one entry, and the two families are
+ * clipped independently.  Padded rows and columns and the diagonal are chosen by selects and never read.  The network's Jacobian is
+ * dropped as in dsg_sample_guided: an approximation, and nothing is claimed about sample quality.
+ *   subj / obj [B,K,Cl], pred [B,K,C_adj], w_spo [B,K,3] (a_s, a_o, a_p): HOST, so that they can be checked; copied into workspace
+ *   memory on `stream` ahead of the run's synchronise (dsg_workspace_bytes counts the buffers once allocated). */
+#define DSG_CONTENT_MAX_ITEMS 16
+typedef struct dsg_content_cfg {
+    float w_content;      /* weight of L_content; 0: the term is off */
+    float tau;            /* > 0 */
+    float clip_ratio;     /* >= 0, or DSG_GUIDE_CLIP_NONE */
+    int32_t n_items;      /* K, 1..DSG_CONTENT_MAX_ITEMS */
+    int32_t node_chans;   /* Cl, 1..C_node-4 */
+    int32_t reserved;     /* 0 */
+    const float *subj;    /* HOST [B,K,Cl] */
+    const float *obj;     /* HOST [B,K,Cl] */
+    const float *pred;    /* HOST [B,K,C_adj] */
+    const float *w_spo;   /* HOST [B,K,3] (a_s,a_o,a_p), finite, >= 0 */
+} dsg_content_cfg;
+
+/* dsg_sample_guided_rel with the content term.  content == NULL or content->w_content == 0: dsg_sample_guided_rel itself -- the same plan
+ * keys, the same captured bodies, the same bits.  Otherwise the content kernel runs behind every preconditioned call next to the box
+ * guide, in step bodies of their own, and the updates read both shifts.  content_trace: DEVICE [L,B] or NULL -- L_content(D) of the
+ * stage-1 call of every executed step.  A content-only run passes a guide whose loss weights are all 0.
+ * Refused with DSG_ERR_INVALID before anything is launched, the message naming the argument: a non-finite w_content, tau <= 0 or NaN, a
+ * negative or NaN clip_ratio, n_items or node_chans out of range, a null array, a non-finite target, a negative or non-finite weight,
+ * N > 64, and everything dsg_sample_guided_rel refuses. */
+int dsg_sample_guided_content(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_walk_cfg *walk /* NULL: trivial walk */,
+                              int32_t B, const uint8_t *flags,
+                              const uint64_t *graph_seeds /* host, [B], or NULL */, uint64_t coin_seed,
+                              const float *init_adj, const float *init_node, const float *base_adj, const float *base_node,
+                              const float *noise_adj, const float *noise_node, const uint8_t *coins,
+                              const float *known_adj, const float *known_node, const uint8_t *mask_adj, const uint8_t *mask_node,
+                              const int32_t *snap_steps, int32_t n_snap, float *snap_adj, float *snap_node,
+                              const dsg_guide_cfg *guide, const float *gt_adj, const float *gt_node, float *loss_trace,
+                              float *out_adj, float *out_node, dsg_sample_stats *stats, void *stream, const dsg_rel_cfg *rel,
+                              const dsg_content_cfg *content, float *content_trace /* DEVICE [L,B] or NULL */);
 
 /* sigma_steps (fp64, edm.py:84-88) and the fp32 per-step scalars the loop uses; out arrays of
  * length num_steps.  Host-only helper, exposed so bindings/tests can inspect the schedule. */

@@ -494,6 +494,21 @@ int dsg_debug_box_guide_rel(int32_t B, int32_t N, int32_t c_adj, int32_t c_node,
                             const dsg_guide_cfg *guide, float coef, float *loss, float *grad, float *shift, float *factor, float *norms,
                             float *d_guided_node, void *stream, const dsg_rel_cfg *rel, uint8_t *kinds_out);
 
+/* The content kernel of dsg.h's dsg_sample_guided_content on its own (test hook, no handle; device pointers but the descriptor's host
+ * arrays; synchronises `stream`): one call's arithmetic on given x_hat, D, flags [B,N], both known masks (mask_adj [B,C_adj,N,N],
+ * mask_node [B,N,C_node]; NULL: none) and ONE coefficient `coef` in place of c_i.  Outputs (each may be NULL), K = n_items, Cl =
+ * node_chans: loss [B], item_loss [B,K], grad_adj [B,C_adj,N,N], grad_label [B,N,Cl] = g, shift_adj / shift_label = f_b (coef w_content) g
+ * as the update subtracts it, factor [B], norms [B,2] = (||coef w_content g||, ||x_hat - D||; the second is 0 when unclipped), best
+ * [B,K,2] int32 = the pair (i, j) with the largest pi_k (the lowest flat index i N + j on an exact tie; -1, -1 where P = 0 or the item
+ * is inactive), d_guided_adj [B,C_adj,N,N] / d_guided_node [B,N,C_node] = D~ (0 at padded entries).  Padded rows and columns and the
+ * adjacency diagonal of D are never read by the kernel.  Refusals as dsg_sample_guided_content's, before any launch; dsg_last_error of a
+ * NULL handle names the argument. */
+int dsg_debug_content_guide(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, const float *xhat_adj, const float *xhat_node,
+                            const float *d_adj, const float *d_node, const uint8_t *flags, const uint8_t *mask_adj, const uint8_t *mask_node,
+                            const dsg_content_cfg *content, float coef, float *loss, float *item_loss, float *grad_adj, float *grad_label,
+                            float *shift_adj, float *shift_label, float *factor, float *norms, int32_t *best, float *d_guided_adj,
+                            float *d_guided_node, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
