@@ -133,7 +133,14 @@ struct Workspace {
     // per (self-cond slot, output slots, Euler/Heun update, coin of stage 1, coin of stage 2, known, multistep D_prev slot) combination
     // that occurs
     RunCtl *ctl = nullptr;
-    std::map<int, std::pair<hipGraphExec_t, int>> step_graphs;   // key -> (exec, network forwards inside)
+    struct StepBody { hipGraphExec_t exec; int forwards, guide_forwards; };   // network forwards inside: the handle's own, its guide's
+    std::map<int, StepBody> step_graphs;   // key -> captured body
+    // autoguidance (dsg_attach_guide): set on the GUIDE handle's workspace for the length of a forward it runs inside its main handle's
+    // preconditioned call -- the c_in x the main workspace holds, and the main run's step table and control block (one step counter);
+    // null: the workspace's own.  Only kernel-only forwards run under them, never the workspace's forward-only graphs
+    const float *ext_in_adj = nullptr, *ext_in_node = nullptr;
+    const StepRow *ext_step = nullptr;
+    const RunCtl *ext_ctl = nullptr;
     long plan_gen = -1;   // h->plan_gen this workspace's launch plan was last validated against (validate_plan)
     // masked-token pruning: the need lists derived from `flags` whenever they are staged (stage_flags), at fixed addresses -- captured
     // graphs read them -- and this batch size's list offsets; cnt [n_lists], cnt_ps [B][n_lists] scratch of the list kernel
@@ -264,6 +271,12 @@ struct dsg_handle_s {
     // dsg_train_bind_params: parameters the training form reads in place (the optimiser's own device tensors) instead of the handle's copies
     std::unordered_map<std::string, const float *> train_params;
     dsg_sample_stats last_stats{};
+    // autoguidance (dsg_attach_guide): the guide handle of this one with its scale s (guide_sm1 = s - 1 in float32) and
+    // noise-level interval; guide_of: the handle this one guides.  At most one of the two is set (a guide has no guide)
+    dsg_handle guide = nullptr, guide_of = nullptr;
+    float guide_scale = 1.f, guide_sm1 = 0.f, guide_lo = 0.f, guide_hi = 0.f;
+    int64_t last_guide_forwards = 0;   // the guide's network forwards in the last dsg_sample* call (dsg_guide_forwards)
+    int device = -1;                   // the HIP device current at dsg_create
     // per-kernel-class timing (dsg_profile_forward): HIP events bracketing every launch on the launch stream
     bool prof_on = false;          // HIP-event brackets around every launch
     bool prof_stamps = false;      // in-kernel start/end stamps of the GEMM launches (no events: launches stay back to back)
@@ -341,6 +354,17 @@ struct ProfScope {
     }
 };
 
+// the captured step bodies that run a guide's forwards (StepPlan::autoguide, the key's top bit): dropped on attach, on detach and by
+// whatever drops the guide's own graphs
+constexpr int STEP_KEY_AUTOGUIDE = 1 << 29;
+void drop_guided_bodies(dsg_handle h) {
+    for (auto &kv : h->ws) {
+        auto &m = kv.second->step_graphs;
+        for (auto it = m.begin(); it != m.end();)
+            if (it->first & STEP_KEY_AUTOGUIDE) { (void)hipGraphExecDestroy(it->second.exec); it = m.erase(it); } else ++it;
+    }
+}
+
 // captured graphs bake weight pointers, kernel selection and table addresses: drop them whenever one of those changes
 void drop_graphs(dsg_handle h) {
     h->plan_gen++;   // ... and the launch plans are validated again before their next use (validate_plan)
@@ -348,9 +372,10 @@ void drop_graphs(dsg_handle h) {
         Workspace *w = kv.second.get();
         if (w->graph) { (void)hipGraphExecDestroy(w->graph); w->graph = nullptr; }
         if (w->graph_uniform) { (void)hipGraphExecDestroy(w->graph_uniform); w->graph_uniform = nullptr; }
-        for (auto &g : w->step_graphs) (void)hipGraphExecDestroy(g.second.first);
+        for (auto &g : w->step_graphs) (void)hipGraphExecDestroy(g.second.exec);
         w->step_graphs.clear();
     }
+    if (h->guide_of) drop_guided_bodies(h->guide_of);   // ... and a guide's are baked into its main handle's guided step bodies
 }
 
 // (r0: the level-0 token resolution, max_node_num / patch_size)
@@ -846,6 +871,7 @@ int dsg_create_patch(const dsg_config *cfg, int32_t patch_size, dsg_handle *out)
     {   // the list GEMM picks its form from how many CUs a launch would fill (kernels.h: gemm_thin_rule); unknown = never thin
         int dev = 0, n_cu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) h->n_cu = n_cu;
+        h->device = dev;
     }
     *out = h;
     g_live_handles++;
@@ -854,6 +880,8 @@ int dsg_create_patch(const dsg_config *cfg, int32_t patch_size, dsg_handle *out)
 
 void dsg_destroy(dsg_handle h) {
     if (!h) return;
+    if (h->guide) (void)dsg_detach_guide(h);
+    if (h->guide_of) (void)dsg_detach_guide(h->guide_of);
     owned_free_all(h->derived_allocs);
     for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
     drop_graphs(h);
@@ -1673,6 +1701,8 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
     const int B = w->B, N = h->N, E = h->E, T0 = h->R0 * h->R0;   // N: the state's side; T0: level-0 tokens
     GemmArgs g;
     bool pe_done = false, pe_premod = false;
+    // (a guide's forward inside its main handle's call reads the main workspace's c_in x)
+    const float *in_adj = w->ext_in_adj ? w->ext_in_adj : w->in_adj, *in_node = w->ext_in_node ? w->ext_in_node : w->in_node;
     if (h->opt.fused_patch_embed && h->pe_wp) {
         h->prof_next_list = pe_runs.id;
         ProfScope ps_(h, s, PK_FUSED, 2.0 * (double)B * T0 * E * h->Cin, "launch_fused_patch_embed96");
@@ -1680,12 +1710,12 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
         const BlockPlan *b0 = h->down[0].empty() ? nullptr : &h->down[0][0];
         pe_premod = wants_premod(h, b0) && (fp32_rule ? (h->opt.fused_attn && b0->wqp) : true);
         if (h->P == 2)
-            pe_done = launch_fused_patch_embed96_p2(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
+            pe_done = launch_fused_patch_embed96_p2(in_adj, in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
                                                     WT(h, "patch_embed.proj.bias"), WT(h, "patch_embed.norm.weight"), WT(h, "patch_embed.norm.bias"),
                                                     w->aff, w->aff_ld, h->pe_aff_off, pe_premod ? b0->aff_off : -1, w->x, B, N, h->Ca, h->Cn,
                                                     c.self_condition, h->pe_kps, s);
         else
-        pe_done = launch_fused_patch_embed96(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
+        pe_done = launch_fused_patch_embed96(in_adj, in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, h->pe_wp,
                                              WT(h, "patch_embed.proj.bias"), WT(h, "patch_embed.norm.weight"),
                                              WT(h, "patch_embed.norm.bias"), w->aff, w->aff_ld, h->pe_aff_off, pe_premod ? b0->aff_off : -1,
                                              w->x, B, N, h->Ca, h->Cn, c.self_condition, h->Kp, s, (xn_done && pe_premod) ? w->xn : nullptr,
@@ -1697,11 +1727,11 @@ bool patch_embed_stage(dsg_handle h, Workspace *w, bool fp32_rule, hipStream_t s
     if (!g_dry_run) w->patch_fwd[0] = pe_done ? 1 : 0;
     if (!pe_done) {
         if (h->P > 1)   // the p^2 sub-pixels' channels side by side: the strided convolution is the same GEMM over R0^2 tokens
-            P_KERN(PK_ELEM, 0.0, if (!launch_assemble_patch(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, w->tok_in, B,
+            P_KERN(PK_ELEM, 0.0, if (!launch_assemble_patch(in_adj, in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, w->tok_in, B,
                                                             N, h->P, h->Ca, h->Cn, c.self_condition, h->Kp, s))
                                      plan_fail(h, "patch_embed: assembly refused (N=%d patch_size=%d Kp=%d)", N, h->P, h->Kp));
         else
-            P_KERN(PK_ELEM, 0.0, launch_assemble(w->in_adj, w->in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, w->tok_in, B, N, h->Ca,
+            P_KERN(PK_ELEM, 0.0, launch_assemble(in_adj, in_node, w->cur_sc_adj, w->cur_sc_node, w->cur_has_sc, w->flags, w->tok_in, B, N, h->Ca,
                                                  h->Cn, c.self_condition, h->Kp, s));
         g = GemmArgs();
         g.A = w->tok_in; g.lda = h->Kp; g.K1 = h->Kp; g.K = h->Kp; g.M = B * T0; g.N = E;
@@ -2073,7 +2103,8 @@ void forward_fixed(dsg_handle h, Workspace *w, hipStream_t s, const TabBuild *tb
                 // (lists written under DD_TABLE: from the table entry of the running step; the launch is the same either way)
                 PureTabSrc pt;
                 if (w->tab_pure && !tb)
-                    pt = PureTabSrc{w->tab_pure, ptl.stride, w->tab_pure_cap, ptl.off_x[l], ptl.off_skip[l], ptl.off_st[l], h->tab_step, w->ctl,
+                    pt = PureTabSrc{w->tab_pure, ptl.stride, w->tab_pure_cap, ptl.off_x[l], ptl.off_skip[l], ptl.off_st[l], w->ext_step ? w->ext_step : h->tab_step,
+                                    w->ext_ctl ? w->ext_ctl : w->ctl,
                                     w->dd_rep + (size_t)w->need.dd_n * B};
                 P_KERN(PK_ELEM, 0.0, launch_window_broadcast(w->x, l ? w->skips[l - 1] : nullptr, parts > 0 ? w->stats : nullptr, parts, B, res, C,
                                                              cp.list, cp.cnt, w->dd_rep + (size_t)l * B, s, pt));
@@ -2281,6 +2312,7 @@ int stage_inputs(dsg_handle h, Workspace *w, const float *adj, const float *node
 
 // NodeAdjPrecond.forward on workspace state: x (xh_adj/xh_node), sigmas (w->sig) -> D (dst), optionally
 // mirrored into the fixed self-cond input of the next forward.  sc: current self-cond or null.
+// dst.adj == nullptr: stop behind the last forward, F is left in w->f_* (the two legs of an autoguided dsg_precond)
 int precond_core(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, const float *sc_node, bool coin, StatePtrs dst,
                  bool use_graph, hipStream_t s, int64_t *nfe, const float *aff_row = nullptr) {
     const Dims d = dims_of(h, w->B);
@@ -2297,9 +2329,12 @@ int precond_core(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, 
     }
     if (int rc = run_forward(h, w, use_graph, s)) return rc;
     (*nfe)++;
-    launch_precond_out(x, CStatePtrs{w->f_adj, w->f_node}, w->sig, w->flags, dst, d, s);
+    if (dst.adj) launch_precond_out(x, CStatePtrs{w->f_adj, w->f_node}, w->sig, w->flags, dst, d, s);
     return 0;
 }
+
+// a call of the main handle that its guide refused: the guide's own message, prefixed so that the caller sees which handle it was
+int guide_fail(dsg_handle h, dsg_handle g, int rc) { return fail(h, rc, "guide handle: %s", g->err.c_str()); }
 
 // ---- one step of the reverse loop (edm.py:350-427) as a static launch sequence ------------------------------------------
 // Everything that changes from step to step is read on the device from StepRow[ctl->step] / the step's (scale,shift) row, so
@@ -2321,10 +2356,12 @@ struct StepPlan {
                           //   shifts; its shift buffers rotate with g1 / g2 / gprev
     bool cclip = false;   //   ... with the content shift's own clip factor
     int cgrid = 0;        //   ... 0: the content kernel's one-block-per-graph form; K: its (graph, item) grid, whose launch bakes K
-    int key() const {   // prev, then the guidance bits, the relation bits, the content bits sit above every older bit: plans without them keep their keys
+    bool autoguide = false;   // autoguidance (dsg_attach_guide): every preconditioned call of the step runs the guide's forwards behind
+                              // the main network's and stores the composite D~; clear on a step outside the interval, whose body is the plain one
+    int key() const {   // prev, then the guidance bits, the relation bits, the content bits, the autoguide bit sit above every older bit: plans without them keep their keys
         return (sc_slot + 1) | (s1 << 2) | (s2 << 4) | ((int)euler << 6) | ((int)coin1 << 7) | ((int)coin2 << 8) | ((int)known << 9) |
                ((prev + 1) << 10) | ((int)guided << 12) | ((int)clip << 13) | (g1 << 14) | (g2 << 16) | ((gprev + 1) << 18) | (rel << 20) |
-               ((int)content << 22) | ((int)cclip << 23) | (cgrid << 24);
+               ((int)content << 22) | ((int)cclip << 23) | (cgrid << 24) | (autoguide ? STEP_KEY_AUTOGUIDE : 0);
     }
 };
 
@@ -2338,8 +2375,12 @@ void precond_out_step(dsg_handle h, Workspace *w, CStatePtrs x, StatePtrs dst, b
 // NodeAdjPrecond.forward at sigma[step] on workspace state x -> dst; forwards run inline on `s` (capturable)
 // fwd_graph: replay the captured network forward (round-1 scheme: only the forward is a graph, the loop is host-enqueued)
 // known: conditional sampling -- both D writes (the extra self-conditioning pass's too) take the known entries from the workspace
+// wg (autoguidance, a guided step): the guide handle's workspace.  Behind the main network's last forward, on the same stream, the
+// guide runs NodeAdjPrecond at the same x, sigma, sc and coin outcome -- its forwards read the main workspace's c_in x, its extra
+// pass goes through the existing kernel into its own sc_* -- and one kernel forms D_m and D_g from the two F and stores D~.  The
+// guide's forwards are always enqueued as kernels, also where the main network's replay its forward-only graph
 int precond_tab(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, const float *sc_node, bool coin, StatePtrs dst,
-                hipStream_t s, int *nfe, bool fwd_graph, bool known) {
+                hipStream_t s, int *nfe, bool fwd_graph, bool known, Workspace *wg = nullptr, int *gfe = nullptr) {
     const Dims d = dims_of(h, w->B);
     w->uniform = true;
     launch_precond_in_tab(x, h->tab_step, w->ctl, StatePtrs{w->in_adj, w->in_node}, d, s);
@@ -2358,7 +2399,31 @@ int precond_tab(dsg_handle h, Workspace *w, CStatePtrs x, const float *sc_adj, c
     }
     if (int rc = run_forward(h, w, fwd_graph, s)) return rc;
     (*nfe)++;
-    precond_out_step(h, w, x, dst, known, d, s);
+    if (!wg) { precond_out_step(h, w, x, dst, known, d, s); return 0; }
+    dsg_handle g = h->guide;
+    // on every exit the guide's workspace holds no address of the main handle, and its host-side word on the kind of its next forward
+    // is what it was (build_pure_table's FormGuard: an eager forward of the guide on its own may follow)
+    struct ExtGuard { Workspace *w; bool uniform; const float *sca, *scn; const int *hs;
+                      ~ExtGuard() { w->ext_in_adj = w->ext_in_node = nullptr; w->ext_step = nullptr; w->ext_ctl = nullptr;
+                                    w->uniform = uniform; w->cur_sc_adj = sca; w->cur_sc_node = scn; w->cur_has_sc = hs; } }
+        ext_guard{wg, wg->uniform, wg->cur_sc_adj, wg->cur_sc_node, wg->cur_has_sc};
+    wg->ext_in_adj = w->in_adj; wg->ext_in_node = w->in_node; wg->ext_step = h->tab_step; wg->ext_ctl = w->ctl;
+    wg->uniform = true;
+    wg->cur_sc_adj = has ? sc_adj : nullptr; wg->cur_sc_node = has ? sc_node : nullptr; wg->cur_has_sc = nullptr;
+    const CStatePtrs Fg{wg->f_adj, wg->f_node}, kn{w->kn_adj, w->kn_node};
+    const CMaskPtrs km{w->km_adj, w->km_node};
+    if (g->cfg.self_condition && coin) {   // the guide's own extra pass, from its own F
+        if (int rc = run_forward(g, wg, false, s)) return guide_fail(h, g, rc);
+        (*gfe)++;
+        if (known) launch_precond_out_tab_known(x, Fg, h->tab_step, w->ctl, w->flags, kn, km, StatePtrs{wg->sc_adj, wg->sc_node}, d, s);
+        else launch_precond_out_tab(x, Fg, h->tab_step, w->ctl, w->flags, StatePtrs{wg->sc_adj, wg->sc_node}, d, s);
+        wg->cur_sc_adj = wg->sc_adj; wg->cur_sc_node = wg->sc_node;
+    }
+    if (int rc = run_forward(g, wg, false, s)) return guide_fail(h, g, rc);
+    (*gfe)++;
+    const CStatePtrs Fm{w->f_adj, w->f_node};
+    if (known) launch_precond_out_mix_tab_known(x, Fm, Fg, h->guide_sm1, h->tab_step, w->ctl, w->flags, kn, km, dst, d, s);
+    else launch_precond_out_mix_tab(x, Fm, Fg, h->guide_sm1, h->tab_step, w->ctl, w->flags, dst, d, s);
     return 0;
 }
 
@@ -2381,16 +2446,22 @@ int guide_call(dsg_handle h, Workspace *w, const StepPlan &p, CStatePtrs xh, CSt
 }
 
 int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_adj, const float *gt_node, hipStream_t s, int *nfe,
-                 bool fwd_graph = false) {
+                 int *gfe, bool fwd_graph = false) {
     const Dims d = dims_of(h, w->B);
+    Workspace *wg = nullptr;   // a guided step of an autoguided run: the guide's workspace (sample_impl created and staged it)
+    if (p.autoguide && !gt_adj) {
+        if (h->guide) { auto it = h->guide->ws.find(w->B); if (it != h->guide->ws.end()) wg = it->second.get(); }
+        if (!wg) return fail(h, DSG_ERR_STATE, "autoguided step without a staged guide workspace");
+    }
     const CStatePtrs xh{w->xh_adj, w->xh_node};
     auto cshift = [&](int slot) { return ContentShiftPtrs{w->c_shift_adj[slot], w->c_shift_label[slot]}; };
     launch_churn_tab(CStatePtrs{w->x_adj, w->x_node}, h->tab_step, w->ctl, w->flags, StatePtrs{w->xh_adj, w->xh_node}, d, s);   // edm.py:355-366
     CStatePtrs D1{gt_adj, gt_node};   // sanity-check mode (edm.py:372-377): the denoiser is bypassed
     if (!gt_adj) {
         launch_step_row(h->tab_aff, h->aff_n, h->tab_step, w->ctl, w->aff, s);   // this step's (scale,shift) row for every block
+        if (wg) launch_step_row(h->guide->tab_aff, h->guide->aff_n, h->tab_step, w->ctl, wg->aff, s);   // ... and for every block of the guide, from its own table
         if (int rc = precond_tab(h, w, xh, p.sc_slot >= 0 ? w->d_adj[p.sc_slot] : nullptr, p.sc_slot >= 0 ? w->d_node[p.sc_slot] : nullptr,
-                                 p.coin1, StatePtrs{w->d_adj[p.s1], w->d_node[p.s1]}, s, nfe, fwd_graph, p.known)) return rc;
+                                 p.coin1, StatePtrs{w->d_adj[p.s1], w->d_node[p.s1]}, s, nfe, fwd_graph, p.known, wg, gfe)) return rc;
         D1 = CStatePtrs{w->d_adj[p.s1], w->d_node[p.s1]};
     }
     if (p.guided) if (int rc = guide_call(h, w, p, xh, D1, p.g1, /*stage1=*/true, d, s)) return rc;
@@ -2409,7 +2480,7 @@ int enqueue_step(dsg_handle h, Workspace *w, const StepPlan &p, const float *gt_
         if (!gt_adj) {   // stage 2 re-evaluates at (x_hat, sigma(t_hat)) with self-cond = D1 (edm.py:400-405)
             const bool sc = h->cfg.self_condition;
             if (int rc = precond_tab(h, w, xh, sc ? w->d_adj[p.s1] : nullptr, sc ? w->d_node[p.s1] : nullptr, p.coin2,
-                                     StatePtrs{w->d_adj[p.s2], w->d_node[p.s2]}, s, nfe, fwd_graph, p.known)) return rc;
+                                     StatePtrs{w->d_adj[p.s2], w->d_node[p.s2]}, s, nfe, fwd_graph, p.known, wg, gfe)) return rc;
             D2 = CStatePtrs{w->d_adj[p.s2], w->d_node[p.s2]};
         }
         if (p.guided) {   // stage 2 is evaluated at (x_hat, t_hat) and guided the same way
@@ -2429,9 +2500,9 @@ int ensure_step_graph(dsg_handle h, Workspace *w, const StepPlan &p) {
     if (w->step_graphs.count(p.key())) return 0;
     if (!w->cap_stream) HIP_TRY(h, hipStreamCreateWithFlags(&w->cap_stream, hipStreamNonBlocking));
     hipGraph_t graph;
-    int n = 0;
+    int n = 0, ng = 0;
     HIP_TRY(h, hipStreamBeginCapture(w->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_step(h, w, p, nullptr, nullptr, w->cap_stream, &n);
+    const int rc = enqueue_step(h, w, p, nullptr, nullptr, w->cap_stream, &n, &ng);
     const hipError_t ec = hipStreamEndCapture(w->cap_stream, &graph);
     if (rc) { if (ec == hipSuccess) (void)hipGraphDestroy(graph); return rc; }
     if (ec != hipSuccess) return fail(h, DSG_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ec));
@@ -2439,19 +2510,20 @@ int ensure_step_graph(dsg_handle h, Workspace *w, const StepPlan &p) {
     const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(h, DSG_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-    w->step_graphs.emplace(p.key(), std::make_pair(exec, n));
+    w->step_graphs.emplace(p.key(), Workspace::StepBody{exec, n, ng});
     if (getenv("DSG_GRAPH_VERBOSE")) fprintf(stderr, "[dsg-graph] captured step body key=%d (sc %d s1 %d s2 %d euler %d coins %d%d known %d prev %d): %d forwards\n",
                                              p.key(), p.sc_slot, p.s1, p.s2, (int)p.euler, (int)p.coin1, (int)p.coin2, (int)p.known, p.prev, n);
     return 0;
 }
 
 // replay the step body of plan p on the caller's stream
-int replay_step(dsg_handle h, Workspace *w, const StepPlan &p, hipStream_t s, int *nfe) {
+int replay_step(dsg_handle h, Workspace *w, const StepPlan &p, hipStream_t s, int *nfe, int *gfe) {
     auto it = w->step_graphs.find(p.key());
     if (it == w->step_graphs.end()) return fail(h, DSG_ERR_STATE, "step body %d was not captured", p.key());
-    HIP_TRY(h, hipGraphLaunch(it->second.first, s));
-    *nfe += it->second.second;
-    h->last_stats.graph_replays += it->second.second;
+    HIP_TRY(h, hipGraphLaunch(it->second.exec, s));
+    *nfe += it->second.forwards;
+    *gfe += it->second.guide_forwards;
+    h->last_stats.graph_replays += it->second.forwards;
     return 0;
 }
 
@@ -2616,11 +2688,27 @@ int dsg_precond(dsg_handle h, int32_t B, const float *adj, const float *node, co
     hipStream_t s = (hipStream_t)stream;
     Workspace *w;
     if (int rc = get_workspace(h, B, &w)) return rc;
+    dsg_handle g = h->guide;
+    Workspace *wg = nullptr;
+    if (g) {   // (refused by the guide before anything is enqueued)
+        if (int rc = check_ready(g, B)) return guide_fail(h, g, rc);
+        if (int rc = get_workspace(g, B, &wg)) return guide_fail(h, g, rc);
+    }
     if (int rc = stage_flags(h, w, flags, s)) return rc;
     HIP_TRY(h, hipMemcpyAsync(w->sig, sigmas, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
     int64_t nfe = 0;
-    if (int rc = precond_core(h, w, CStatePtrs{adj, node}, sc_adj, sc_node, coin != 0, StatePtrs{out_adj, out_node}, false, s, &nfe))
+    const CStatePtrs x{adj, node};
+    if (int rc = precond_core(h, w, x, sc_adj, sc_node, coin != 0, g ? StatePtrs{nullptr, nullptr} : StatePtrs{out_adj, out_node}, false, s, &nfe))
         return rc;
+    if (g) {
+        // the guide's leg at the same x, sigmas, sc and coin outcome, behind the main network's on the same stream; sigmas are per
+        // sample here, so the guide always runs and the store selects s_b - 1 per sample
+        if (int rc = stage_flags(g, wg, flags, s)) return guide_fail(h, g, rc);
+        if (hipMemcpyAsync(wg->sig, sigmas, sizeof(float) * B, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, DSG_ERR_HIP, "guide handle: copy of sigmas failed");
+        if (int rc = precond_core(g, wg, x, sc_adj, sc_node, coin != 0, StatePtrs{nullptr, nullptr}, false, s, &nfe)) return guide_fail(h, g, rc);
+        launch_precond_out_mix(x, CStatePtrs{w->f_adj, w->f_node}, CStatePtrs{wg->f_adj, wg->f_node}, w->sig, h->guide_sm1, h->guide_lo, h->guide_hi,
+                               w->flags, StatePtrs{out_adj, out_node}, dims_of(h, B), s);
+    }
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
 }
@@ -2809,6 +2897,7 @@ struct SamplePlan {
     std::vector<float> guide_coef; // [T] c_i of a guided run
     GuideParams gpar{};            // ... and its parameter block (device pointers: set once the tables are staged)
     ContentParams cpar{};          // the content term's block, likewise
+    bool autoguide = false;        // some step of the run is autoguided (dsg_attach_guide): the guide's workspace and tables are staged
 };
 
 // the checks of a guide descriptor that need no device; `why` names the argument.  Cn < 0: not known here
@@ -2959,6 +3048,14 @@ int plan_sample(dsg_handle h, const SampleArgs &a, SamplePlan &p) {
         if (!gt) last_s1 = q.s1;
     }
     p.precond_calls = call;
+    // autoguidance: sigma is batch-uniform in the loop, so the host decides per schedule index, from the float32 t_hat, whether the step
+    // is guided.  Scale 1 or a level outside the interval: the bit stays clear and the step is the plain one, no guide forward at all
+    if (h->guide && !gt && h->guide_sm1 != 0.f)
+        for (int i = 0; i < L; i++) {
+            const float t = p.t_hat[sched[i]];
+            p.plans[i].autoguide = t >= h->guide_lo && t <= h->guide_hi;
+            p.autoguide = p.autoguide || p.plans[i].autoguide;
+        }
     if (a.guide) {   // box guidance: refusals, the coefficient table, the shift buffers of every step
         std::string why;
         if (!guide_cfg_ok(a.guide, h->N, h->Cn, /*need_weights=*/true, why)) return fail(h, DSG_ERR_INVALID, "dsg_sample_guided: %s", why.c_str());
@@ -3008,8 +3105,10 @@ int initial_state(dsg_handle h, Workspace *w, const SampleArgs &a, const SampleP
 
 // Step tables on the device: the loop's scalars (StepRow) and, since sigma is batch-uniform (edm.py:371), one noise embedding +
 // (scale,shift) row per step for all blocks, computed once for all steps in three GEMMs with M = T
-int step_tables(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, hipStream_t s) {
-    const int T = p.T, L = p.L;
+int pure_window_table(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &p, hipStream_t s);
+// the per-schedule-index tables of handle h: its noise embedding and (scale, shift) rows at the run's levels
+int noise_tables(dsg_handle h, const SamplePlan &p, hipStream_t s) {
+    const int T = p.T;
     if (h->tab_cap < T) {
         drop_graphs(h);   // the captured step bodies bake the table addresses
         for (float **q : {&h->tab_sig, &h->tab_cn, &h->tab_pe, &h->tab_e0, &h->tab_e1, &h->tab_aff}) { owned_free(h->allocs, *q); *q = nullptr; }
@@ -3020,6 +3119,14 @@ int step_tables(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, 
         for (auto &t : tabs) if (int rc = owned_alloc(h, h->allocs, (void **)t.first, sizeof(float) * t.second, AC_SCRATCH)) return rc;
         h->tab_cap = T;
     }
+    HIP_TRY(h, hipMemcpyAsync(h->tab_sig, p.t_hat.data(), sizeof(float) * T, hipMemcpyHostToDevice, s));
+    launch_cnoise(h->tab_sig, h->tab_cn, T, s);
+    embed_rows(h, h->tab_cn, T, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff, s);
+    return 0;
+}
+
+int step_tables(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, hipStream_t s) {
+    const int L = p.L;
     if (h->tab_step_cap < L) {   // one row per executed step: its own capacity, the tables above stay at one row per schedule index
         drop_graphs(h);
         owned_free(h->allocs, h->tab_step);
@@ -3031,10 +3138,16 @@ int step_tables(dsg_handle h, Workspace *w, const SampleArgs &a, SamplePlan &p, 
     HIP_TRY(h, hipMemcpyAsync(h->tab_step, p.rows.data(), sizeof(StepRow) * L, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(w->ctl, &p.ctl, sizeof(RunCtl), hipMemcpyHostToDevice, s));
     if (a.gt.adj) return 0;   // sanity-check mode: no forward reads a table
-    HIP_TRY(h, hipMemcpyAsync(h->tab_sig, p.t_hat.data(), sizeof(float) * T, hipMemcpyHostToDevice, s));
-    launch_cnoise(h->tab_sig, h->tab_cn, T, s);
-    embed_rows(h, h->tab_cn, T, h->tab_pe, h->tab_e0, h->tab_e1, h->tab_aff, s);
-    return 0;
+    return noise_tables(h, p, s);
+}
+
+// Autoguidance: what the guide's forwards of this run read, staged in the guide handle's workspace before any body is captured -- the
+// flags and their lists, the guide's own (scale, shift) table from its own affine linears on the same schedule, its table of pure-window
+// rows.  The step table and the control block are the main handle's
+int stage_autoguide(dsg_handle g, Workspace *wg, const SampleArgs &a, const SamplePlan &p, hipStream_t s) {
+    if (int rc = stage_flags(g, wg, a.flags, s, /*zero_padded=*/true, /*uniform_row=*/true)) return rc;
+    if (int rc = noise_tables(g, p, s)) return rc;
+    return pure_window_table(g, wg, a, p, s);
 }
 
 // Pure-window table: where the batch shares one representative pure window per level, that window comes from a table with one entry
@@ -3181,10 +3294,10 @@ int run_loop(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &
     const bool step_graphs = p.use_graph && h->opt.loop_graph;
     if (step_graphs)
         for (int i = 0; i < p.L; i++) if (int rc = ensure_step_graph(h, w, p.plans[i])) return rc;   // at most ten distinct bodies
-    int snap_k = 0, nfe = 0;
+    int snap_k = 0, nfe = 0, gfe = 0;
     for (int i = 0; i < p.L; i++) {
-        if (step_graphs) { if (int rc = replay_step(h, w, p.plans[i], s, &nfe)) return rc; }
-        else if (int rc = enqueue_step(h, w, p.plans[i], a.gt.adj, a.gt.node, s, &nfe, p.use_graph)) return rc;
+        if (step_graphs) { if (int rc = replay_step(h, w, p.plans[i], s, &nfe, &gfe)) return rc; }
+        else if (int rc = enqueue_step(h, w, p.plans[i], a.gt.adj, a.gt.node, s, &nfe, &gfe, p.use_graph)) return rc;
         // interim snapshots (edm.py:429-432)
         while (snap_k < a.snapshots.n && a.snapshots.steps && a.snapshots.steps[snap_k] == i) {
             if (a.snapshots.adj) HIP_TRY(h, hipMemcpyAsync(a.snapshots.adj + (size_t)snap_k * sa, w->x_adj, sizeof(float) * sa, hipMemcpyDeviceToDevice, s));
@@ -3199,6 +3312,7 @@ int run_loop(dsg_handle h, Workspace *w, const SampleArgs &a, const SamplePlan &
     HIP_TRY(h, hipGetLastError());
     h->last_stats.precond_calls = p.precond_calls;
     h->last_stats.net_forwards = nfe;
+    h->last_guide_forwards = gfe;
     if (a.stats) *a.stats = h->last_stats;
     return DSG_OK;
 }
@@ -3209,10 +3323,18 @@ int sample_impl(dsg_handle h, const SampleArgs &a) {
     hipStream_t s = a.stream;
     Workspace *w;
     if (int rc = get_workspace(h, a.B, &w)) return rc;
+    dsg_handle g = p.autoguide ? h->guide : nullptr;
+    Workspace *wg = nullptr;   // the guide's workspace: created, and its launch plan validated, before anything is enqueued
+    if (g) {
+        if (int rc = check_ready(g, a.B)) return guide_fail(h, g, rc);
+        if (int rc = get_workspace(g, a.B, &wg)) return guide_fail(h, g, rc);
+    }
     h->last_stats = dsg_sample_stats{};
+    h->last_guide_forwards = 0;
     if (int rc = initial_state(h, w, a, p, s)) return rc;
     if (int rc = step_tables(h, w, a, p, s)) return rc;
     if (int rc = pure_window_table(h, w, a, p, s)) return rc;
+    if (g) if (int rc = stage_autoguide(g, wg, a, p, s)) return guide_fail(h, g, rc);
     if (int rc = stage_known(h, w, a.known, s)) return rc;
     if (int rc = stage_guide(h, w, a, p, s)) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));  // the plan's host vectors (and the caller's seeds) must outlive their async copies; once per sample() call
@@ -4593,6 +4715,59 @@ int dsg_train_set_precision(dsg_handle h, int32_t mode) {
     if (!h) return DSG_ERR_INVALID;
     if (mode != DSG_TRAIN_F32 && mode != DSG_TRAIN_BF16) return fail(h, DSG_ERR_INVALID, "training precision %d (DSG_TRAIN_F32 = 0 or DSG_TRAIN_BF16 = 1)", mode);
     h->train_precision = mode;
+    return DSG_OK;
+}
+
+// ---- autoguidance ----
+int dsg_attach_guide(dsg_handle h, dsg_handle guide, float scale, float sigma_lo, float sigma_hi) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!guide) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide is NULL");
+    if (guide == h) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide is the handle itself (guide == h)");
+    if (guide->guide) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide has a guide of its own (one level only)");
+    if (h->guide_of) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: h is itself the guide of another handle (one level only)");
+    if (guide->guide_of && guide->guide_of != h) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide is already attached to another handle");
+    if (!guide->finalized) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide is not finalized (dsg_finalize_weights)");
+    if (guide->N != h->N) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide's max_node_num %d differs from %d", guide->N, h->N);
+    if (guide->Ca != h->Ca) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide's c_adj %d differs from %d", guide->Ca, h->Ca);
+    if (guide->Cn != h->Cn) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide's c_node %d differs from %d", guide->Cn, h->Cn);
+    if ((guide->cfg.self_condition != 0) != (h->cfg.self_condition != 0))
+        return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide's self_condition %d differs from %d", guide->cfg.self_condition, h->cfg.self_condition);
+    if (guide->device != h->device) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: guide was created on device %d, h on device %d", guide->device, h->device);
+    if (!std::isfinite(scale)) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: scale = %g is not finite", (double)scale);
+    if (std::isnan(sigma_lo)) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: sigma_lo is NaN");
+    if (std::isnan(sigma_hi)) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: sigma_hi is NaN");
+    if (sigma_lo > sigma_hi) return fail(h, DSG_ERR_INVALID, "dsg_attach_guide: sigma_lo = %g is above sigma_hi = %g", (double)sigma_lo, (double)sigma_hi);
+    if (h->guide) (void)dsg_detach_guide(h);
+    drop_guided_bodies(h);
+    h->guide = guide; guide->guide_of = h;
+    volatile float sm1 = scale - 1.0f;   // float32, one rounding
+    h->guide_scale = scale; h->guide_sm1 = sm1; h->guide_lo = sigma_lo; h->guide_hi = sigma_hi;
+    return DSG_OK;
+}
+
+int dsg_detach_guide(dsg_handle h) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!h->guide) return DSG_OK;
+    drop_guided_bodies(h);
+    h->guide->guide_of = nullptr;
+    h->guide = nullptr;
+    h->guide_scale = 1.f; h->guide_sm1 = 0.f; h->guide_lo = 0.f; h->guide_hi = 0.f;
+    return DSG_OK;
+}
+
+int dsg_guide_info(dsg_handle h, dsg_handle *guide, float *scale, float *sigma_lo, float *sigma_hi) {
+    if (!h) return DSG_ERR_INVALID;
+    if (guide) *guide = h->guide;
+    if (scale) *scale = h->guide_scale;
+    if (sigma_lo) *sigma_lo = h->guide_lo;
+    if (sigma_hi) *sigma_hi = h->guide_hi;
+    return DSG_OK;
+}
+
+int dsg_guide_forwards(dsg_handle h, int64_t *n) {
+    if (!h) return DSG_ERR_INVALID;
+    if (!n) return fail(h, DSG_ERR_INVALID, "dsg_guide_forwards: n is NULL");
+    *n = h->last_guide_forwards;
     return DSG_OK;
 }
 

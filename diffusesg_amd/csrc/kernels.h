@@ -404,6 +404,17 @@ void launch_precond_out_tab(CStatePtrs x, CStatePtrs F, const StepRow *tab, cons
 struct CMaskPtrs { const uint8_t *adj; const uint8_t *node; };
 void launch_precond_out_tab_known(CStatePtrs x, CStatePtrs F, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, CStatePtrs known,
                                   CMaskPtrs mask, StatePtrs D, Dims d, hipStream_t s);
+// autoguidance (dsg_attach_guide): the composite D~ = fadd(D_m, fmul(sm1, fsub(D_m, D_g))) in the store of the same
+// skeleton -- D_m and D_g each formed from x and its network's F by the operations of launch_precond_out*, in registers; x, F_main and
+// F_guide are read once, no D_m / D_g tensor exists.  sm1 = s - 1 in float32.
+// The per-sample form (dsg_precond) takes sm1 where lo <= sigma[b] <= hi and 0 elsewhere; the table forms (the reverse loop) belong
+// to a step the host found inside the interval.  known: the select runs on D_m and on D_g, so a known entry is the known value itself
+void launch_precond_out_mix(CStatePtrs x, CStatePtrs F_main, CStatePtrs F_guide, const float *sigmas, float sm1, float lo, float hi,
+                            const uint8_t *flags, StatePtrs D, Dims d, hipStream_t s);
+void launch_precond_out_mix_tab(CStatePtrs x, CStatePtrs F_main, CStatePtrs F_guide, float sm1, const StepRow *tab, const RunCtl *ctl,
+                                const uint8_t *flags, StatePtrs D, Dims d, hipStream_t s);
+void launch_precond_out_mix_tab_known(CStatePtrs x, CStatePtrs F_main, CStatePtrs F_guide, float sm1, const StepRow *tab, const RunCtl *ctl,
+                                      const uint8_t *flags, CStatePtrs known, CMaskPtrs mask, StatePtrs D, Dims d, hipStream_t s);
 void launch_euler_tab(CStatePtrs xhat, CStatePtrs D, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags, StatePtrs x, Dims d,
                       hipStream_t s);
 void launch_heun_tab(CStatePtrs xhat, CStatePtrs D1, CStatePtrs D2, const StepRow *tab, const RunCtl *ctl, const uint8_t *flags,

@@ -2648,6 +2648,38 @@ void launch_precond_out_tab_known(CStatePtrs x, CStatePtrs F, const StepRow *tab
     launch_elem(PrecondOut<StepSigma, true>{{known, mask}, x, F, {tab, ctl}, flags}, D, d, s);
 }
 
+// Autoguidance: D~ = D_m + (s - 1) (D_m - D_g), both D from the same x and sigma by the operations of PrecondOut, one rounding per
+// operation.  Interval: the per-sample form's select of s - 1 (0 outside [lo, hi]); NoInterval: the step is guided as a whole
+struct NoInterval { __device__ float operator()(float sm1, float) const { return sm1; } };
+struct SigmaInterval { float lo, hi; __device__ float operator()(float sm1, float s) const { return (s >= lo && s <= hi) ? sm1 : 0.f; } };
+template <class Sigma, class Interval, bool known> struct PrecondOutMix {
+    std::conditional_t<known, KnownSel, NoKnown> k; CStatePtrs x, Fm, Fg; Sigma sigma; Interval in; float sm1; const uint8_t *flags;
+    __device__ int uniform() const { return 0; }
+    __device__ float operator()(int, const ElemIdx &e, size_t, const Dims &) const {
+        if constexpr (known) if (ld(k.mask, e) != 0) return ld(k.value, e);   // D_m == D_g == known: the difference is 0
+        const float s = sigma(e);
+        const float s2 = FADD(FMUL(s, s), 0.25f);
+        const float c_skip = __fdiv_rn(0.25f, s2);
+        const float c_out = __fdiv_rn(FMUL(s, 0.5f), __fsqrt_rn(s2));
+        const float sx = FMUL(c_skip, ld(x, e));
+        const float Dm = FADD(sx, FMUL(c_out, ld(Fm, e)));
+        const float Dg = FADD(sx, FMUL(c_out, ld(Fg, e)));
+        return FADD(Dm, FMUL(in(sm1, s), FSUB(Dm, Dg)));
+    }
+};
+void launch_precond_out_mix(CStatePtrs x, CStatePtrs F_main, CStatePtrs F_guide, const float *sigmas, float sm1, float lo, float hi,
+                            const uint8_t *flags, StatePtrs D, Dims d, hipStream_t s) {
+    launch_elem(PrecondOutMix<SampleSigma, SigmaInterval, false>{{}, x, F_main, F_guide, {sigmas}, {lo, hi}, sm1, flags}, D, d, s);
+}
+void launch_precond_out_mix_tab(CStatePtrs x, CStatePtrs F_main, CStatePtrs F_guide, float sm1, const StepRow *tab, const RunCtl *ctl,
+                                const uint8_t *flags, StatePtrs D, Dims d, hipStream_t s) {
+    launch_elem(PrecondOutMix<StepSigma, NoInterval, false>{{}, x, F_main, F_guide, {tab, ctl}, {}, sm1, flags}, D, d, s);
+}
+void launch_precond_out_mix_tab_known(CStatePtrs x, CStatePtrs F_main, CStatePtrs F_guide, float sm1, const StepRow *tab, const RunCtl *ctl,
+                                      const uint8_t *flags, CStatePtrs known, CMaskPtrs mask, StatePtrs D, Dims d, hipStream_t s) {
+    launch_elem(PrecondOutMix<StepSigma, NoInterval, true>{{known, mask}, x, F_main, F_guide, {tab, ctl}, {}, sm1, flags}, D, d, s);
+}
+
 // Philox4x32-10 counter-based generator -> one N(0,1) per (seed, stream, element)
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;

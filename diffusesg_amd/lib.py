@@ -21,6 +21,7 @@ EXPORTS = [
     "dsg_sgstat_f1_rowstats", "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
     "dsg_sample_seeded", "dsg_gen_noise_seeded", "dsg_precond_vjp", "dsg_ode_run", "dsg_ode_evals", "dsg_guide_coef", "dsg_sample_guided",
     "dsg_sample_guided_rel", "dsg_sample_guided_content", "dsg_option_info", "dsg_create_patch", "dsg_train_set_precision", "dsg_train_get_precision",
+    "dsg_attach_guide", "dsg_detach_guide", "dsg_guide_info", "dsg_guide_forwards",
 ]
 
 TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}   # DSG_TRAIN_F32 / DSG_TRAIN_BF16 of include/dsg.h
@@ -320,6 +321,10 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_train_bind_params.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
     L.dsg_train_set_precision.argtypes = [vp, i32]
     L.dsg_train_get_precision.argtypes = [vp, C.POINTER(i32)]
+    L.dsg_attach_guide.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float]
+    L.dsg_detach_guide.argtypes = [vp]
+    L.dsg_guide_info.argtypes = [vp, C.POINTER(vp)] + [C.POINTER(C.c_float)] * 3
+    L.dsg_guide_forwards.argtypes = [vp, C.POINTER(i64)]
     L.dsg_adam_step.argtypes = [i32] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int64), i32] + [C.c_float] * 6 + [C.POINTER(C.c_float), vp]
     L.dsg_ema_update.argtypes = [i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, vp]
     L.dsg_noise_embed.argtypes = [vp, i32, vp, vp, vp, vp, vp]
@@ -442,6 +447,26 @@ class Handle:
         v = C.c_int32(0)
         self.check(self.L.dsg_train_get_precision(self._h, C.byref(v)), "dsg_train_get_precision")
         return {m: name for name, m in TRAIN_PRECISIONS.items()}[int(v.value)]
+
+    def attach_guide(self, guide: "Handle", scale: float, sigma_lo: float, sigma_hi: float):
+        """Autoguidance (dsg_attach_guide): `guide` becomes this handle's weaker network, D~ = D + (scale - 1)(D - D_guide) at the noise
+        levels in [sigma_lo, sigma_hi].  The caller keeps `guide` alive while it is attached."""
+        self.check(self.L.dsg_attach_guide(self._h, guide._h, float(scale), float(sigma_lo), float(sigma_hi)), "dsg_attach_guide")
+
+    def detach_guide(self):
+        self.check(self.L.dsg_detach_guide(self._h), "dsg_detach_guide")
+
+    def guide_info(self):
+        """(guide handle address or None, scale, sigma_lo, sigma_hi) of the attachment (dsg_guide_info)."""
+        g, s, lo, hi = C.c_void_p(), C.c_float(), C.c_float(), C.c_float()
+        self.check(self.L.dsg_guide_info(self._h, C.byref(g), C.byref(s), C.byref(lo), C.byref(hi)), "dsg_guide_info")
+        return g.value, float(s.value), float(lo.value), float(hi.value)
+
+    def guide_forwards(self) -> int:
+        """The guide's network forwards in this handle's last dsg_sample* call (dsg_guide_forwards)."""
+        n = C.c_int64(0)
+        self.check(self.L.dsg_guide_forwards(self._h, C.byref(n)), "dsg_guide_forwards")
+        return int(n.value)
 
     def train_routes(self):
         """Test only (dsg_debug_train_routes): {(token rows, class): (products on the bf16 route, on an fp32 route)} of the covered

@@ -65,6 +65,8 @@ class DiffuseSGHip(nn.Module):
                 _attach(self, t.key, torch.zeros(t.shape, dtype=torch.float32), False)
         self._handle: Optional[_lib.Handle] = None
         self._synced_version = None
+        self._guide = None            # autoguidance (NodeAdjPrecondHip.attach_guide): (guide DiffuseSGHip, scale, sigma_lo, sigma_hi)
+        self._guide_attached = None   # ... and what the library handle currently holds: (guide Handle, scale, sigma_lo, sigma_hi)
 
     # -- weights ---------------------------------------------------------------------------------
     def _weights_version(self):
@@ -103,7 +105,23 @@ class DiffuseSGHip(nn.Module):
         if finalize and not getattr(self, "_finalized_ok", False):
             self._handle.finalize()
             self._finalized_ok = True
+        self._sync_guide()
         return self._handle
+
+    def _sync_guide(self):
+        """The handle's attachment follows `self._guide`: the guide's handle carries its module's current weights, and is attached
+        (again) whenever the guide, its handle or the parameters changed."""
+        want = None
+        if self._guide is not None:
+            gm, scale, lo, hi = self._guide
+            want = (gm._ensure_handle(), scale, lo, hi)
+        if want == self._guide_attached:
+            return
+        if want is None:
+            self._handle.detach_guide()
+        else:
+            self._handle.attach_guide(*want)
+        self._guide_attached = want
 
     def load_numpy_state_dict(self, sd):
         own = self.state_dict()
@@ -276,6 +294,48 @@ class NodeAdjPrecondHip(nn.Module):
                                      p(oa), p(on), p(ga), p(gn), C.c_void_p(st))
         h.check(rc, "dsg_precond_vjp")
         return (*m._shape_out(oa, on), box["loss"], *m._shape_out(ga, gn))
+
+    # -- autoguidance (dsg_attach_guide) ------------------------------------------------
+    def attach_guide(self, guide_net: "NodeAdjPrecondHip", scale: float = 2.0, sigma_range=None):
+        """Every preconditioned call of this network -- forward() and each call inside the sampler's loop, whatever entry runs it --
+        becomes D~ = D + (scale - 1)(D - D_guide), with `guide_net` (a second, weaker NodeAdjPrecondHip: an earlier checkpoint, the raw
+        weights next to the EMA copy, a narrower or a patch_size = 2 net) evaluated at the same input, noise level, self-conditioning
+        input and coin outcome.  sigma_range = (lo, hi): only at noise levels lo <= sigma <= hi; None: at every level.  The guide must
+        share max_node_num, the channel counts and self_condition; it is kept alive by this network while attached.
+        Refusals (ValueError / DsgError) name the argument.  Nothing is claimed about sample quality."""
+        if not isinstance(guide_net, NodeAdjPrecondHip):
+            raise TypeError("attach_guide: guide_net must be a NodeAdjPrecondHip (build_network / io.load_model)")
+        if guide_net is self or guide_net.model is self.model:
+            raise ValueError("attach_guide: guide_net is the network itself")
+        if guide_net.model._guide is not None:
+            raise ValueError("attach_guide: guide_net has a guide of its own (one level only)")
+        lo, hi = (-float("inf"), float("inf")) if sigma_range is None else (float(sigma_range[0]), float(sigma_range[1]))
+        scale = float(scale)
+        if not np.isfinite(scale):
+            raise ValueError(f"attach_guide: scale = {scale} is not finite")
+        if np.isnan(lo) or np.isnan(hi) or lo > hi:
+            raise ValueError(f"attach_guide: sigma_range = ({lo}, {hi}) needs lo <= hi, neither NaN")
+        a, b = self.model.config, guide_net.model.config
+        for f in ("max_node_num", "c_adj", "c_node", "self_condition"):
+            if getattr(a, f) != getattr(b, f):
+                raise ValueError(f"attach_guide: guide_net's {f} = {getattr(b, f)} differs from the network's {getattr(a, f)}")
+        self.model._guide = (guide_net.model, scale, lo, hi)
+        object.__setattr__(self, "_guide_net", guide_net)   # keeps the guide alive; not a submodule: state_dict() stays the network's own
+        if self.model._handle is not None:
+            self.model._ensure_handle()
+
+    def detach_guide(self):
+        self.model._guide = None
+        object.__setattr__(self, "_guide_net", None)
+        if self.model._handle is not None:
+            self.model._sync_guide()
+
+    def guide_info(self):
+        """None, or dict(guide=<NodeAdjPrecondHip>, scale=, sigma_range=(lo, hi))."""
+        if self.model._guide is None:
+            return None
+        _, scale, lo, hi = self.model._guide
+        return dict(guide=getattr(self, "_guide_net", None), scale=scale, sigma_range=(lo, hi))
 
     @staticmethod
     def round_sigma(sigma):

@@ -83,6 +83,7 @@ class NodeAdjEDMSamplerHip(object):
         self.use_graph = use_graph
         self.seed = 1234
         self.last_stats = None
+        self.last_guide_forwards = None   # autoguidance (net.attach_guide): the guide network's forwards in the last run
         self.sigma_steps = torch.from_numpy(_lib.sigma_schedule(self._cfg())[0])
 
     def _cfg(self) -> _lib.DsgSamplerCfg:
@@ -186,6 +187,7 @@ class NodeAdjEDMSamplerHip(object):
             if flag_interim_adjs and i in ts_snap:
                 snaps_a.append(xa.cpu()); snaps_n.append(xn.cpu())
         self.last_stats = {"precond_calls": 0, "net_forwards": 0, "graph_replays": 0}
+        self.last_guide_forwards = 0
         sq_a = (lambda t: t[:, 0]) if cfg.c_adj == 1 else (lambda t: t)
         sq_n = (lambda t: t[..., 0]) if cfg.c_node == 1 else (lambda t: t)
         adjs, nodes = sq_a(xa.cpu()), sq_n(xn.cpu())
@@ -480,6 +482,7 @@ class NodeAdjEDMSamplerHip(object):
                                          p(oa), p(on), C.byref(stats), C.c_void_p(st)), "dsg_sample_known")
         self.last_stats = {"precond_calls": stats.precond_calls, "net_forwards": stats.net_forwards,
                            "graph_replays": stats.graph_replays}
+        self.last_guide_forwards = h.guide_forwards()
         logging.info("Done with EDM-NodeAdj MCMC (HIP).")
         if cfg.c_adj == 1:
             oa = oa[:, 0]

@@ -430,3 +430,35 @@ def ode_case(name: str, seed: int = 37):
     p_adj = W.mask_adj(sign(W.normal(seed, f"ode/{name}/probe_adj", (B, cfg.c_adj, n, n))), flags)
     p_node = W.mask_node(sign(W.normal(seed, f"ode/{name}/probe_node", (B, n, cfg.c_node))), flags)
     return cfg, flags, adj, node, p_adj, p_node
+
+
+# ---- autoguidance (tests/golden/autoguide.npz, tools/gen_autoguide_golden.py) -------------------------------------
+# pair -> guide configuration; the main network of every pair is the tiny config with weight seed 0, the guide has weight seed 1.
+# a: the same geometry; b: a narrower net (E = 64, heads 2 and 4); c: patch_size 2 (R = 4)
+AUTOGUIDE_PAIRS = ("a", "b", "c")
+AUTOGUIDE_SCALE = 2.0
+AUTOGUIDE_VALID = [8, 1, 5]          # B = 3, ragged, one graph with a single valid node
+AUTOGUIDE_RUNS = (("t8_heun", 8, "heun", 40.0), ("t8_euler", 8, "euler", 0.0))
+AUTOGUIDE_MAIN_SEED, AUTOGUIDE_GUIDE_SEED = 0, 1
+
+
+def autoguide_guide_config(pair: str) -> S.ModelConfig:
+    if pair == "a":
+        return S.tiny_config()
+    if pair == "b":
+        return S.ModelConfig(max_node_num=8, c_adj=6, c_node=12, embed_dim=64, depths=(1, 1), num_heads=(2, 4), window_size=4,
+                             self_condition=True)
+    if pair == "c":
+        return PATCH_CONFIGS["tiny_p2"]()
+    raise KeyError(pair)
+
+
+def autoguide_sampler_case(tag: str, T: int, solver: str):
+    """sampler_case of the fixture's runs (the same inputs for every pair): flags, init, churn noise, coin draws in (0, 1)"""
+    return sampler_case(S.tiny_config(), T, 3, AUTOGUIDE_VALID, 5, f"autoguide/{tag}", solver)
+
+
+def autoguide_precond_case(si: int):
+    """inputs of the fixture's composite calls at PRECOND_SIGMAS[si]: sigma, flags, adj, node, sc_adj, sc_node"""
+    sigma = PRECOND_SIGMAS[si]
+    return (sigma,) + case_inputs(S.tiny_config(), 3, AUTOGUIDE_VALID, 6, f"autoguide/pre/{si}", sigma_scale=float(np.sqrt(sigma ** 2 + 0.25)))

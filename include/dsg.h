@@ -783,6 +783,42 @@ int dsg_train_bind_params(dsg_handle h, int32_t n_params, const char *const *nam
 int dsg_train_set_precision(dsg_handle h, int32_t mode);
 int dsg_train_get_precision(dsg_handle h, int32_t *mode);
 
+/* ---- Autoguidance (Karras et al. 2024, "Guiding a diffusion model with a bad version of itself") ----
+ * A main handle h can have a second, weaker network -- the guide handle -- attached, with a scale s and a noise-level interval
+ * [sigma_lo, sigma_hi].  While attached, a preconditioned call of h at (x, sigma, sc, coin) is the composite
+ *     D_m = NodeAdjPrecond_h(x, sigma, sc, coin)      as without a guide, h's own extra self-conditioning pass included
+ *     D_g = NodeAdjPrecond_guide(x, sigma, sc, coin)  the same x, sigma, sc and coin OUTCOME; the guide's extra pass is its own
+ *     s_b = s where sigma_lo <= sigma_b <= sigma_hi, else 1
+ *     D~  = fadd(D_m, fmul(s_b - 1, fsub(D_m, D_g)))  float32, one rounding per operation (s - 1 rounded once); exactly 0 at masked entries
+ * and every D the reverse loop reads, stores or hands on is D~: both Heun stages, the multistep extrapolation, the next call's
+ * self-conditioning input of BOTH networks, and the tensor the box / relation / content guide kernels are handed.  With known entries
+ * the select runs on D_m and D_g, so a known entry arrives bit-exact.  This is what the reference's sampler computes when it is given
+ * one nn.Module that wraps two NodeAdjPrecond and forces one coin per call on both.
+ * Acts on dsg_precond (per-sample sigmas: the guide always runs, s_b is selected per sample) and on every dsg_sample* entry -- plain,
+ * known, walk, seeded, guided, guided_rel, guided_content -- with all three solvers, step graphs on and off; the sanity-check mode
+ * bypasses the denoiser and is unchanged.  In the loop sigma is batch-uniform: a step is guided iff the float32 t_hat of its schedule
+ * index (dsg_sigma_schedule) lies in the interval; a step outside it, and every step of a run with s == 1, runs no guide forward at all
+ * and replays the plain captured step body.  The guide's forwards are enqueued behind the main network's on the same stream.
+ * Does NOT act on dsg_denoise, the training entries (dsg_train_*), dsg_precond_vjp or dsg_ode_run: they are the same bits attached or not.
+ * The attachment is handle state (like dsg_train_set_precision): no option, no environment variable.
+ * dsg_attach_guide: DSG_ERR_INVALID, nothing changed and nothing enqueued, the message naming the argument, for guide == h; a guide
+ *   that has a guide of its own (or h being a guide, or the guide serving another handle); a guide that is not finalized; a different
+ *   max_node_num, c_adj, c_node or self_condition; a handle created on another device; a scale that is not finite; a NaN bound or
+ *   sigma_lo > sigma_hi (-INFINITY / INFINITY: every level).  Everything else may differ: embed_dim, depths, heads, window, patch_size,
+ *   weights, options.  Attaching over an existing attachment replaces it.  An entry call whose option combination the guide cannot run
+ *   (batch_invariant on a patch_size > 1 guide, ...) fails before anything is enqueued with the guide's own message behind "guide handle: ".
+ * dsg_detach_guide: back to the plain handle (no guide attached: DSG_OK).  dsg_destroy of either handle detaches first.
+ * dsg_guide_info: the attachment (guide NULL, scale 1, bounds 0 when there is none); any output pointer may be NULL.
+ * dsg_guide_forwards: the GUIDE's network forwards in the last dsg_sample* call of h.  dsg_sample_stats keeps its layout and its
+ *   counters keep counting the main network only.
+ * Non-re-entrancy extends to the guide: while attached, the guide handle is busy whenever h is -- no call on the guide from another
+ * thread or stream while a call on h runs; between calls of h the guide may be used on its own.
+ * Nothing is claimed about sample quality: no trained weights exist for this model offline. */
+int dsg_attach_guide(dsg_handle h, dsg_handle guide, float scale, float sigma_lo, float sigma_hi);
+int dsg_detach_guide(dsg_handle h);
+int dsg_guide_info(dsg_handle h, dsg_handle *guide, float *scale, float *sigma_lo, float *sigma_hi);
+int dsg_guide_forwards(dsg_handle h, int64_t *n);
+
 /* The rest of a training iteration (R/runner/trainer/trainer_node_adj.py:170-175), on caller-owned device tensors, no handle:
  * dsg_adam_step <-> nn.utils.clip_grad_norm_(parameters, max_norm) followed by torch.optim.Adam.step()  (utils/learning_utils.py:137-140:
  *   betas (0.9, 0.999), eps 1e-8, L2 weight_decay; gradients are scaled in place by the clip coefficient like the reference;
