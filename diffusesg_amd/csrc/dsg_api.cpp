@@ -265,6 +265,7 @@ struct dsg_handle_s {
     // bf16 mode of the training entries (dsg_train_set_precision): the mode, the bf16 weight planes of the covered linears -- rebuilt by
     // every entry call in bf16 mode, the parameters may have changed in place -- and the route counts of the last training entry
     int train_precision = DSG_TRAIN_F32;
+    int train_patch = 0;   // dsg_train_enable_patch: the training form at patch_size > 1 (no effect at patch_size 1)
     DevBuf train_lp;
     std::vector<TLpCount> train_counts;
     int *train_const = nullptr;                                   // device {0, 1}: the "self-conditioning present" switch of launch_assemble
@@ -3909,9 +3910,17 @@ int dsg_rainbow_loss_backward(int32_t B, int32_t N, int32_t c_adj, int32_t c_nod
 
 // ---- training form: what one block and the whole network share ----
 namespace {
-// the training form (weight and input gradients, the ODE encoder) is built for patch_size 1: refused before anything is enqueued
-static int patch_no_training(dsg_handle h, const char *entry) {
-    return fail(h, DSG_ERR_INVALID, "%s: the training form is not built at patch_size %d (patch_size > 1 covers the sampling entries only)", entry, h->P);
+// the training form (weight and input gradients, the ODE encoder) at patch_size > 1 is handle state, off by default
+// (dsg_train_enable_patch), and runs fp32 products only: refused before any other check and before anything is enqueued
+static int patch_training_gate(dsg_handle h, const char *entry) {
+    if (h->P == 1) return DSG_OK;
+    if (!h->train_patch)
+        return fail(h, DSG_ERR_INVALID, "%s: the training form is not built at patch_size %d (patch_size > 1 covers the sampling entries only) "
+                    "until dsg_train_enable_patch(h, 1) switches it on", entry, h->P);
+    if (h->train_precision == DSG_TRAIN_BF16)
+        return fail(h, DSG_ERR_INVALID, "%s: the training form at patch_size %d (dsg_train_enable_patch) runs fp32 products only: "
+                    "dsg_train_set_precision(h, DSG_TRAIN_BF16) is not built there", entry, h->P);
+    return DSG_OK;
 }
 
 struct TArena {   // bump allocator over one device buffer; without a base it only sizes (every get returns null)
@@ -4017,11 +4026,14 @@ struct TrainBufs {   // saved activations outside the blocks
     float *ucat[8], *uy[8], *un[8], *ustats[8], *usc[8], *upn[8], *upstats[8], *uout[8];   // PatchBreakup per up layer
     float *fy, *fstats, *z1, *z2, *rep, *ha_pre, *ha, *oa, *pool, *hn_pre, *hn, *on;
     float *d_skip[8];
+    float *pe_img, *pe_dimg, *ro_img, *ro_dimg, *ro_bias;   // patch_size > 1: the per-call weight images of PatchEmbed and read_out.0 and their gradients
 };
 struct TrainStage { TrainBlockArgs a; float *x_out, *d_emb; };
 struct TrainNet {
     int B, N, E, L, Ca, Cn, Cin, self_condition;
-    size_t M0;                        // B N N: tokens of level 0
+    int P, R0, Kp;                    // patch_size, the level-0 token resolution N / P, and the width of PatchEmbed's input rows (P == 1: Cin)
+    size_t M0;                        // B R0 R0: tokens of level 0
+    size_t Mp;                        // B N N: pixel rows of the read-out chain, (token, a, b) order at P > 1 (P == 1: M0)
     std::vector<TrainStage> stages;   // the blocks in execution order: encoder level l is [first[l], first[l + 1]), up layer i starts at first[L + i]
     int first[2 * DSG_MAX_LAYERS + 1];
     bool grouped;                     // every `affine` linear of the network in one grouped launch (at most T_GROUP_MAX - 1 blocks)
@@ -4038,7 +4050,7 @@ struct TrainNet {
 struct TrainInputs { const float *adj, *node; const uint8_t *flags; const float *c_noise, *sc_adj, *sc_node; };
 // input-gradient mode (dsg_precond_vjp): the backward carries dL/d(activation) only -- no dW / db product, no affine or noise-embedding
 // backward, no parameter gradient buffer -- and ends in d_tok [B N N, ld] = d_pe_lin W_img, the gradient of the live columns of the
-// assembled input (img [E][ld]: scratch for the weight image of t_live_cols)
+// assembled input (img [E][ld]: scratch for the weight image of t_live_cols; patch_size > 1: the p^2 groups of t_live_cols_patch)
 struct TrainInputGrad { float *d_tok, *img; int ld; };
 enum TrainBackward { TRAIN_WEIGHT_GRADS, TRAIN_INPUT_GRADS };
 }  // namespace
@@ -4047,7 +4059,7 @@ enum TrainBackward { TRAIN_WEIGHT_GRADS, TRAIN_INPUT_GRADS };
 static void train_net_carve(TrainNet &net, TArena &A) {
     TrainBufs &Bf = net.Bf;
     const int B = net.B, N = net.N, E = net.E, L = net.L;
-    const size_t M0 = net.M0;
+    const size_t M0 = net.M0, Mp = net.Mp;
     auto carve_stages = [&](int g) {
         for (int k = net.first[g]; k < net.first[g + 1]; k++) {
             TrainStage &st = net.stages[k];
@@ -4058,9 +4070,9 @@ static void train_net_carve(TrainNet &net, TArena &A) {
     Bf.pe = A.get((size_t)B * E); Bf.m0 = A.get((size_t)B * NOISE_EMB); Bf.s0 = A.get((size_t)B * NOISE_EMB);
     Bf.m1 = A.get((size_t)B * NOISE_EMB); Bf.emb = A.get((size_t)B * NOISE_EMB); Bf.d_emb = A.get((size_t)B * NOISE_EMB);
     Bf.pe_demb = A.get((size_t)B * NOISE_EMB);
-    Bf.tok = A.get(M0 * net.Cin); Bf.pe_lin = A.get(M0 * E); Bf.pe_ln = A.get(M0 * E); Bf.pe_stats = A.get(M0 * 2);
+    Bf.tok = A.get(M0 * net.Kp); Bf.pe_lin = A.get(M0 * E); Bf.pe_ln = A.get(M0 * E); Bf.pe_stats = A.get(M0 * 2);
     Bf.pe_aff = A.get((size_t)B * 2 * E); Bf.pe_daff = A.get((size_t)B * 2 * E); Bf.x0 = A.get(M0 * E);
-    int res = N, C = E;
+    int res = net.R0, C = E;
     for (int l = 0; l < L; l++) {
         carve_stages(l);
         if (l < L - 1) {
@@ -4080,9 +4092,15 @@ static void train_net_carve(TrainNet &net, TArena &A) {
         }
         carve_stages(L + i);
     }
-    Bf.fy = A.get(M0 * E); Bf.fstats = A.get(M0 * 2); Bf.z1 = A.get(M0 * E); Bf.z2 = A.get(M0 * E); Bf.rep = A.get(M0 * E);
-    Bf.ha_pre = A.get(M0 * E); Bf.ha = A.get(M0 * E); Bf.oa = A.get(M0 * net.Ca);
+    Bf.fy = A.get(M0 * E); Bf.fstats = A.get(M0 * 2); Bf.z1 = A.get(Mp * E); Bf.z2 = A.get(Mp * E); Bf.rep = A.get(Mp * E);
+    Bf.ha_pre = A.get(Mp * E); Bf.ha = A.get(Mp * E); Bf.oa = A.get(Mp * net.Ca);
     Bf.pool = A.get((size_t)B * N * E); Bf.hn_pre = A.get((size_t)B * N * E); Bf.hn = A.get((size_t)B * N * E); Bf.on = A.get((size_t)B * N * net.Cn);
+    Bf.pe_img = Bf.pe_dimg = Bf.ro_img = Bf.ro_dimg = Bf.ro_bias = nullptr;
+    if (net.P > 1) {
+        const size_t PP = (size_t)net.P * net.P;
+        Bf.pe_img = A.get((size_t)E * net.Kp); Bf.pe_dimg = A.get((size_t)E * net.Kp);
+        Bf.ro_img = A.get(PP * E * E); Bf.ro_dimg = A.get(PP * E * E); Bf.ro_bias = A.get(PP * E);
+    }
 }
 
 // Validates, binds every parameter (and, with `weight_grads`, every gradient buffer of names / grad_params) once, and carves the
@@ -4092,7 +4110,9 @@ static int train_net_build(dsg_handle h, TrainNet &net, int32_t B, const float *
     if (h->cfg.self_condition && ((sc_adj == nullptr) != (sc_node == nullptr))) return fail(h, DSG_ERR_INVALID, "self-conditioning needs both tensors or none");
     const int L = h->L;
     net.B = B; net.N = h->N; net.E = h->E; net.L = L; net.Ca = h->Ca; net.Cn = h->Cn; net.Cin = h->Cin;
-    net.self_condition = h->cfg.self_condition; net.M0 = (size_t)B * h->N * h->N;
+    net.self_condition = h->cfg.self_condition; net.P = h->P; net.R0 = h->R0;
+    net.Kp = h->P > 1 ? t_pe_image_width(h->Cin, h->P) : h->Cin;
+    net.M0 = (size_t)B * h->R0 * h->R0; net.Mp = (size_t)B * h->N * h->N;
     if (!h->train_const) {
         const int zo[2] = {0, 1};
         if (int rc = owned_alloc(h, h->allocs, (void **)&h->train_const, sizeof(zo), AC_STATE)) return rc;
@@ -4135,7 +4155,9 @@ static int train_net_build(dsg_handle h, TrainNet &net, int32_t B, const float *
     if (!missing.empty()) return fail(h, DSG_ERR_INVALID, "missing tensor '%s'", missing.c_str());
     // the saved-activation arena and the backward scratch belong to the handle and are kept between calls.  Scratch: three of the
     // widest tensors, level 0's [M0, 4E] (every level has M C constant up to the 2x of merging), and four of [M0, 2E]
-    const size_t wide = net.M0 * (size_t)(4 * net.E), two = net.M0 * (size_t)net.E * 2;
+    // (patch_size > 1: the read-out chain's [Mp, E] and [Mp, Ca] gradients pass through the same regions)
+    const size_t wide = std::max(net.M0 * (size_t)(4 * net.E), net.P > 1 ? net.Mp * (size_t)std::max(net.E, net.Ca) : (size_t)0);
+    const size_t two = std::max(net.M0 * (size_t)net.E * 2, net.P > 1 ? net.Mp * (size_t)net.E : (size_t)0);
     if (!train_carve(h, h->train_arena, s, [&](TArena &A) { train_net_carve(net, A); A.get(16); }) ||
         !train_carve(h, h->train_scr, s, [&](TArena &A) {
             net.t_mh = A.get(wide); net.t_m3c = A.get(wide); net.t_w = A.get(wide); net.t_mc = A.get(two); net.t_mc2 = A.get(two);
@@ -4171,7 +4193,7 @@ static bool train_lp_begin(dsg_handle h, TrainNet &net, TrainLp &lp, hipStream_t
         const size_t M = (size_t)a.B * a.res * a.res;
         add(a.W.qkv_w, M, a.C, 3 * a.C); add(a.W.proj_w, M, a.C, a.C); add(a.W.fc1_w, M, a.C, a.hidden); add(a.W.fc2_w, M, a.hidden, a.C);
     }
-    int res = net.N, C = net.E;
+    int res = net.R0, C = net.E;
     for (int l = 0; l < net.L - 1; l++) {   // merging after encoder level l: [M / 4, 4C] -> 2C
         res /= 2;
         add(net.mrg_red[l].w, (size_t)net.B * res * res, 4 * C, 2 * C);
@@ -4205,16 +4227,22 @@ static void train_lp_end(dsg_handle h, const TrainLp &lp) { h->train_counts = lp
 // F = network(in) in training form, every activation the backward needs left in the arena; false: a block refused to launch
 static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F, hipStream_t s) {
     const TrainBufs &Bf = net.Bf;
-    const int B = net.B, N = net.N, E = net.E, L = net.L, Ca = net.Ca, Cn = net.Cn, Cin = net.Cin, T0 = N * N;
-    const size_t M0 = net.M0;
+    const int B = net.B, N = net.N, E = net.E, L = net.L, Ca = net.Ca, Cn = net.Cn, Cin = net.Cin, P = net.P, PP = P * P, T0 = net.R0 * net.R0;
+    const size_t M0 = net.M0, Mp = net.Mp;
     bool ok = true;
     launch_noise_pe(in.c_noise, Bf.pe, B, E, s);
     lin_fwd(Bf.pe, net.map0.w, net.map0.b, Bf.m0, B, E, NOISE_EMB, s);
     t_silu(Bf.m0, nullptr, Bf.s0, (size_t)B * NOISE_EMB, false, s);
     lin_fwd(Bf.s0, net.map1.w, net.map1.b, Bf.m1, B, NOISE_EMB, NOISE_EMB, s);
     t_silu(Bf.m1, nullptr, Bf.emb, (size_t)B * NOISE_EMB, false, s);
-    launch_assemble(in.adj, in.node, in.sc_adj, in.sc_node, net.has_sc, in.flags, Bf.tok, B, N, Ca, Cn, net.self_condition, Cin, s);
-    lin_fwd(Bf.tok, net.pe.w, net.pe.b, Bf.pe_lin, M0, Cin, E, s);
+    if (P > 1) {   // the p^2 sub-pixels' channels side by side against the weight image of this call's raw weight: the strided convolution
+        ok = launch_assemble_patch(in.adj, in.node, in.sc_adj, in.sc_node, net.has_sc, in.flags, Bf.tok, B, N, P, Ca, Cn, net.self_condition, net.Kp, s) &&
+             t_pe_pack(net.pe.w, Bf.pe_img, E, Cin, P, net.Kp, s);
+        lin_fwd(Bf.tok, Bf.pe_img, net.pe.b, Bf.pe_lin, M0, net.Kp, E, s);
+    } else {
+        launch_assemble(in.adj, in.node, in.sc_adj, in.sc_node, net.has_sc, in.flags, Bf.tok, B, N, Ca, Cn, net.self_condition, Cin, s);
+        lin_fwd(Bf.tok, net.pe.w, net.pe.b, Bf.pe_lin, M0, Cin, E, s);
+    }
     t_ln_fwd(Bf.pe_lin, net.pe_norm.w, net.pe_norm.b, Bf.pe_ln, Bf.pe_stats, (int)M0, E, s);
     if (net.grouped) {
         // every `affine` linear of the network (PatchEmbed + all blocks) hangs off emb: one grouped launch
@@ -4228,7 +4256,7 @@ static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F,
     }
     t_modulate(Bf.pe_ln, Bf.pe_aff, nullptr, Bf.x0, nullptr, B, T0, E, false, s);
     const float *x = Bf.x0, *skip[8] = {};
-    int res = N, C = E;
+    int res = net.R0, C = E;
     auto run_blocks = [&](int g) {
         for (int k = net.first[g]; k < net.first[g + 1]; k++) {
             TrainStage &st = net.stages[k];
@@ -4263,14 +4291,22 @@ static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F,
     }
     net.xL = x;
     t_ln_fwd(x, net.norm.w, net.norm.b, Bf.fy, Bf.fstats, (int)M0, E, s);
-    t_gemm(false, false, Bf.fy, E, net.ro0.w, E, net.ro0.b, Bf.z1, E, (int)M0, E, E, false, s);   // ConvTranspose2d: [in, out]
-    lin_fwd(Bf.z1, net.ro1.w, net.ro1.b, Bf.z2, M0, E, E, s);
-    lin_fwd(Bf.z2, net.ro2.w, net.ro2.b, Bf.rep, M0, E, E, s);
-    lin_fwd(Bf.rep, net.adj1.w, net.adj1.b, Bf.ha_pre, M0, E, E, s);
-    t_gelu(Bf.ha_pre, nullptr, Bf.ha, M0 * E, false, s);
-    lin_fwd(Bf.ha, net.adj2.w, net.adj2.b, Bf.oa, M0, E, Ca, s);
-    t_adj_out(Bf.oa, in.flags, out_F.adj, nullptr, nullptr, B, N, Ca, false, s);
-    launch_pool(Bf.rep, in.flags, Bf.pool, B, N, E, s);
+    if (P > 1) {   // [M0, p^2 E] = fy img: read as [Mp, E] it is z1 with rows in (token, a, b) order
+        ok = ok && t_ro0_pack(net.ro0.w, net.ro0.b, Bf.ro_img, Bf.ro_bias, E, E, P, s);
+        t_gemm(false, false, Bf.fy, E, Bf.ro_img, PP * E, Bf.ro_bias, Bf.z1, PP * E, (int)M0, PP * E, E, false, s);
+    } else t_gemm(false, false, Bf.fy, E, net.ro0.w, E, net.ro0.b, Bf.z1, E, (int)M0, E, E, false, s);   // ConvTranspose2d: [in, out]
+    lin_fwd(Bf.z1, net.ro1.w, net.ro1.b, Bf.z2, Mp, E, E, s);
+    lin_fwd(Bf.z2, net.ro2.w, net.ro2.b, Bf.rep, Mp, E, E, s);
+    lin_fwd(Bf.rep, net.adj1.w, net.adj1.b, Bf.ha_pre, Mp, E, E, s);
+    t_gelu(Bf.ha_pre, nullptr, Bf.ha, Mp * E, false, s);
+    lin_fwd(Bf.ha, net.adj2.w, net.adj2.b, Bf.oa, Mp, E, Ca, s);
+    if (P > 1) {
+        ok = ok && t_adj_out_patch(Bf.oa, in.flags, out_F.adj, nullptr, nullptr, B, N, P, Ca, false, s) &&
+             launch_pool_patch(Bf.rep, in.flags, Bf.pool, B, N, P, E, s);
+    } else {
+        t_adj_out(Bf.oa, in.flags, out_F.adj, nullptr, nullptr, B, N, Ca, false, s);
+        launch_pool(Bf.rep, in.flags, Bf.pool, B, N, E, s);
+    }
     lin_fwd(Bf.pool, net.node1.w, net.node1.b, Bf.hn_pre, (size_t)B * N, E, E, s);
     t_gelu(Bf.hn_pre, nullptr, Bf.hn, (size_t)B * N * E, false, s);
     lin_fwd(Bf.hn, net.node2.w, net.node2.b, Bf.on, (size_t)B * N, E, Cn, s);
@@ -4283,8 +4319,8 @@ static bool train_forward(TrainNet &net, const TrainInputs &in, StatePtrs out_F,
 static bool train_backward(TrainNet &net, TrainBackward mode, const uint8_t *flags, CStatePtrs dF, const TrainInputGrad *ig, hipStream_t s) {
     const bool wg = mode == TRAIN_WEIGHT_GRADS;
     const TrainBufs &Bf = net.Bf;
-    const int B = net.B, N = net.N, E = net.E, L = net.L, Ca = net.Ca, Cn = net.Cn, Cin = net.Cin, T0 = N * N;
-    const size_t M0 = net.M0;
+    const int B = net.B, N = net.N, E = net.E, L = net.L, Ca = net.Ca, Cn = net.Cn, Cin = net.Cin, P = net.P, PP = P * P, T0 = net.R0 * net.R0;
+    const size_t M0 = net.M0, Mp = net.Mp;
     float *const t_mh = net.t_mh, *const t_m3c = net.t_m3c, *const t_w = net.t_w, *const t_mc = net.t_mc, *const t_mc2 = net.t_mc2;
     auto skip_size = [&](int l) { return (size_t)B * net.skip_res[l] * net.skip_res[l] * net.skip_C[l]; };
     hipError_t e0 = (net.grouped || !wg) ? hipSuccess : hipMemsetAsync(Bf.d_emb, 0, sizeof(float) * (size_t)B * NOISE_EMB, s);
@@ -4297,20 +4333,31 @@ static bool train_backward(TrainNet &net, TrainBackward mode, const uint8_t *fla
     t_gelu(Bf.hn_pre, d_hn, d_hn, (size_t)B * N * E, true, s);
     lin_bwd(wg, Bf.pool, net.node1.w, d_hn, d_pool, net.node1.dw, net.node1.db, (size_t)B * N, E, E, s);
     float *d_oa = t_m3c, *d_ha = t_mh;
-    t_adj_out(nullptr, flags, nullptr, dF.adj, d_oa, B, N, Ca, true, s);
-    lin_bwd(wg, Bf.ha, net.adj2.w, d_oa, d_ha, net.adj2.dw, net.adj2.db, M0, E, Ca, s);
-    t_gelu(Bf.ha_pre, d_ha, d_ha, M0 * E, true, s);
-    lin_bwd(wg, Bf.rep, net.adj1.w, d_ha, d_rep, net.adj1.dw, net.adj1.db, M0, E, E, s);
-    t_pool_bwd(d_pool, flags, d_rep, B, N, E, s);
+    if (P > 1) ok = ok && t_adj_out_patch(nullptr, flags, nullptr, dF.adj, d_oa, B, N, P, Ca, true, s);
+    else t_adj_out(nullptr, flags, nullptr, dF.adj, d_oa, B, N, Ca, true, s);
+    lin_bwd(wg, Bf.ha, net.adj2.w, d_oa, d_ha, net.adj2.dw, net.adj2.db, Mp, E, Ca, s);
+    t_gelu(Bf.ha_pre, d_ha, d_ha, Mp * E, true, s);
+    lin_bwd(wg, Bf.rep, net.adj1.w, d_ha, d_rep, net.adj1.dw, net.adj1.db, Mp, E, E, s);
+    if (P > 1) ok = ok && t_pool_bwd_patch(d_pool, flags, d_rep, B, N, P, E, s);
+    else t_pool_bwd(d_pool, flags, d_rep, B, N, E, s);
     // read_out.2, .1 (Conv2d [out,in]) and .0 (ConvTranspose2d [in,out]), final norm
     float *d_z2 = t_mh, *d_z1 = t_m3c, *d_fy = t_w;
-    lin_bwd(wg, Bf.z2, net.ro2.w, d_rep, d_z2, net.ro2.dw, net.ro2.db, M0, E, E, s);
-    lin_bwd(wg, Bf.z1, net.ro1.w, d_z2, d_z1, net.ro1.dw, net.ro1.db, M0, E, E, s);
-    if (wg) {
-        t_gemm(true, false, Bf.fy, E, d_z1, E, nullptr, net.ro0.dw, E, E, E, (int)M0, false, s);    // dW [in,out] = y^T dz
-        t_colsum(d_z1, E, net.ro0.db, (int)M0, E, s);
+    lin_bwd(wg, Bf.z2, net.ro2.w, d_rep, d_z2, net.ro2.dw, net.ro2.db, Mp, E, E, s);
+    lin_bwd(wg, Bf.z1, net.ro1.w, d_z2, d_z1, net.ro1.dw, net.ro1.db, Mp, E, E, s);
+    if (P > 1) {   // d_z1 viewed [M0, p^2 E] against the weight image of the forward; the bias sees every pixel row
+        if (wg) {
+            t_gemm(true, false, Bf.fy, E, d_z1, PP * E, nullptr, Bf.ro_dimg, PP * E, E, PP * E, (int)M0, false, s);
+            ok = ok && t_ro0_unpack(Bf.ro_dimg, net.ro0.dw, E, E, P, s);
+            t_colsum(d_z1, E, net.ro0.db, (int)Mp, E, s);
+        }
+        t_gemm(false, true, d_z1, PP * E, Bf.ro_img, PP * E, nullptr, d_fy, E, (int)M0, E, PP * E, false, s);
+    } else {
+        if (wg) {
+            t_gemm(true, false, Bf.fy, E, d_z1, E, nullptr, net.ro0.dw, E, E, E, (int)M0, false, s);    // dW [in,out] = y^T dz
+            t_colsum(d_z1, E, net.ro0.db, (int)M0, E, s);
+        }
+        t_gemm(false, true, d_z1, E, net.ro0.w, E, nullptr, d_fy, E, (int)M0, E, E, false, s);        // dy = dz W^T
     }
-    t_gemm(false, true, d_z1, E, net.ro0.w, E, nullptr, d_fy, E, (int)M0, E, E, false, s);        // dy = dz W^T
     // blocks / up / down in reverse; dcur: the running gradient wrt the current activation (size up to M0*E*2), ping-pong with dnext
     float *dcur = net.d_x, *dnext = net.d_y;
     t_ln_bwd(net.xL, net.norm.w, Bf.fstats, d_fy, nullptr, dcur, net.norm.dw, net.norm.db, (int)M0, E, s);
@@ -4326,7 +4373,7 @@ static bool train_backward(TrainNet &net, TrainBackward mode, const uint8_t *fla
             std::swap(dcur, dnext);
         }
     };
-    int res = N, C = E;
+    int res = net.R0, C = E;
     for (int i = L - 1; i >= 0; i--) {
         run_blocks(L + i);
         if (i > 0) {
@@ -4387,10 +4434,14 @@ static bool train_backward(TrainNet &net, TrainBackward mode, const uint8_t *fla
     if (!wg) {
         // d_tok = d_pe_lin W_img: only the columns of the current adjacency / node values, the weight image zero-padded to x32 columns
         // (sigma is not differentiated: no noise-embedding backward)
-        t_live_cols(net.pe.w, Cin, ig->img, E, Ca, Cn, net.self_condition != 0, s);
+        if (P > 1) ok = ok && t_live_cols_patch(net.pe.w, Cin, P, ig->img, E, Ca, Cn, net.self_condition != 0, s);
+        else t_live_cols(net.pe.w, Cin, ig->img, E, Ca, Cn, net.self_condition != 0, s);
         t_gemm(false, false, d_pe_lin, E, ig->img, ig->ld, nullptr, ig->d_tok, ig->ld, (int)M0, ig->ld, E, false, s);
     } else {
-        lin_bwd(wg, Bf.tok, net.pe.w, d_pe_lin, nullptr, net.pe.dw, net.pe.db, M0, Cin, E, s);
+        if (P > 1) {   // the gradient of the weight image, then back to [E, Cin, p, p]
+            lin_bwd(wg, Bf.tok, Bf.pe_img, d_pe_lin, nullptr, Bf.pe_dimg, net.pe.db, M0, net.Kp, E, s);
+            ok = ok && t_pe_unpack(Bf.pe_dimg, net.pe.dw, E, Cin, P, net.Kp, s);
+        } else lin_bwd(wg, Bf.tok, net.pe.w, d_pe_lin, nullptr, net.pe.dw, net.pe.db, M0, Cin, E, s);
         // noise embedding: emb = silu(map1(silu(map0(pe))))
         float *d_m1 = t_mc, *d_s0 = t_mc2;
         t_silu(Bf.m1, Bf.d_emb, d_m1, (size_t)B * NOISE_EMB, true, s);
@@ -4418,7 +4469,7 @@ int dsg_train_grads(dsg_handle h, int32_t B, const float *in_adj, const float *i
     // the training form reads the raw weights only, so weights re-uploaded after an optimiser step need no re-packing here
     // (dsg_finalize_weights must have run once: block plans); the sampling-path entries still insist on `finalized`
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
-    if (h->P != 1) return patch_no_training(h, "dsg_train_grads");
+    if (int rc = patch_training_gate(h, "dsg_train_grads")) return rc;
     if (B < 1 || !in_adj || !in_node || !flags || !c_noise || !out_F_adj || !out_F_node) return fail(h, DSG_ERR_INVALID, "null argument");
     const bool bwd = grad_F_adj != nullptr;
     if (bwd && (!grad_F_node || !names || !grad_params)) return fail(h, DSG_ERR_INVALID, "backward needs both output gradients and the parameter gradient buffers");
@@ -4452,7 +4503,7 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
                          int32_t iou_loss_type, float *out_D_adj, float *out_D_node, float *out_loss_adj, float *out_loss_node,
                          int32_t n_params, const char *const *names, float *const *grad_params, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
-    if (h->P != 1) return patch_no_training(h, "dsg_train_step_grads");
+    if (int rc = patch_training_gate(h, "dsg_train_step_grads")) return rc;
     if (iou_loss_type < DSG_IOU_IOU || iou_loss_type > DSG_IOU_CIOU) return fail(h, DSG_ERR_INVALID, "iou_loss_type %d", iou_loss_type);
     if (B < 1 || !noisy_adj || !noisy_node || !flags || !sigmas || !target_adj || !target_node || !out_D_adj || !out_D_node || !out_loss_adj ||
         !out_loss_node)
@@ -4488,7 +4539,7 @@ int dsg_train_step_grads(dsg_handle h, int32_t B, const float *noisy_adj, const 
 int dsg_train_self_cond(dsg_handle h, int32_t B, const float *noisy_adj, const float *noisy_node, const uint8_t *flags, const float *sigmas,
                         float *out_sc_adj, float *out_sc_node, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
-    if (h->P != 1) return patch_no_training(h, "dsg_train_self_cond");
+    if (int rc = patch_training_gate(h, "dsg_train_self_cond")) return rc;
     if (B < 1 || !noisy_adj || !noisy_node || !flags || !sigmas || !out_sc_adj || !out_sc_node) return fail(h, DSG_ERR_INVALID, "null argument");
     hipStream_t s = (hipStream_t)stream;
     const Dims d = dims_of(h, B);
@@ -4512,19 +4563,19 @@ int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node
                     const float *sc_adj, const float *sc_node, const float *grad_D_adj, const float *grad_D_node, dsg_grad_fn fn, void *user,
                     float *out_D_adj, float *out_D_node, float *out_grad_adj, float *out_grad_node, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
-    if (h->P != 1) return patch_no_training(h, "dsg_precond_vjp");
+    if (int rc = patch_training_gate(h, "dsg_precond_vjp")) return rc;
     if (B < 1 || !adj || !node || !flags || !sigmas || !out_D_adj || !out_D_node || !out_grad_adj || !out_grad_node)
         return fail(h, DSG_ERR_INVALID, "null argument");
     if ((grad_D_adj == nullptr) != (grad_D_node == nullptr)) return fail(h, DSG_ERR_INVALID, "grad_D_adj and grad_D_node go together");
     if ((fn != nullptr) == (grad_D_adj != nullptr)) return fail(h, DSG_ERR_INVALID, "give either the callback or grad_D_adj / grad_D_node, not %s", fn ? "both" : "neither");
     hipStream_t s = (hipStream_t)stream;
     const Dims d = dims_of(h, B);
-    const int N = h->N, Ca = h->Ca, Cn = h->Cn, E = h->E;
-    const size_t M0 = (size_t)B * N * N;
+    const int N = h->N, Ca = h->Ca, Cn = h->Cn, E = h->E, P = h->P;
+    const size_t M0 = (size_t)B * h->R0 * h->R0;
     // refused before anything is enqueued: what the last kernel (t_assemble_bwd) cannot take
-    if (!t_assemble_bwd_ok(Cn) || (size_t)B * N > 0x7fffffffu)
+    if (!(P > 1 ? t_assemble_bwd_patch_ok(Cn) : t_assemble_bwd_ok(Cn)) || (size_t)B * N > 0x7fffffffu)
         return fail(h, DSG_ERR_INVALID, "input gradients are not built for C_node %d (partial sums beyond LDS) or B * N = %zu", Cn, (size_t)B * N);
-    const int Np = t_live_cols_width(Ca, Cn);
+    const int Np = P > 1 ? t_live_cols_patch_width(Ca, Cn, P) : t_live_cols_width(Ca, Cn);
     TrainIo io;
     TrainInputGrad ig{nullptr, nullptr, Np};
     float *coef = nullptr;   // c_skip [B] | c_in [B], left by t_precond_bwd for t_assemble_bwd
@@ -4552,7 +4603,8 @@ int dsg_precond_vjp(dsg_handle h, int32_t B, const float *adj, const float *node
     }
     if (ok) ok = train_backward(net, TRAIN_INPUT_GRADS, flags, CStatePtrs{io.dF_a, io.dF_n}, &ig, s);
     if ((rc = train_finish(h, ok, s)) != DSG_OK) return rc;
-    if (!t_assemble_bwd(ig.d_tok, Np, flags, coef, coef + B, g_a, g_n, out_grad_adj, out_grad_node, B, N, Ca, Cn, false, s))
+    if (!(P > 1 ? t_assemble_bwd_patch(ig.d_tok, Np, flags, coef, coef + B, g_a, g_n, out_grad_adj, out_grad_node, B, N, P, Ca, Cn, s)
+                : t_assemble_bwd(ig.d_tok, Np, flags, coef, coef + B, g_a, g_n, out_grad_adj, out_grad_node, B, N, Ca, Cn, false, s)))
         return fail(h, DSG_ERR_INVALID, "the assemble backward refused B %d, N %d, C_adj %d, C_node %d, pitch %d", B, N, Ca, Cn, Np);
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
@@ -4600,7 +4652,7 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
                 const float *x_node, const uint64_t *graph_seeds, const float *probe_adj, const float *probe_node, float *out_adj,
                 float *out_node, float *out_probe_adj, float *out_probe_node, double *out_net_trace, void *stream) {
     if (!h || !h->ever_finalized) return fail(h, DSG_ERR_STATE, "weights not finalized");
-    if (h->P != 1) return patch_no_training(h, "dsg_ode_run");
+    if (int rc = patch_training_gate(h, "dsg_ode_run")) return rc;
     if (!cfg || !ode || B < 1 || !flags || !x_adj || !x_node || !out_adj || !out_node) return fail(h, DSG_ERR_INVALID, "null argument");
     if (cfg->num_steps < 2) return fail(h, DSG_ERR_INVALID, "dsg_ode_run needs num_steps >= 2 (it steps between the schedule's levels; num_steps is %d)", cfg->num_steps);
     if (solver_2m(cfg)) return fail(h, DSG_ERR_INVALID, "dsg_ode_run has no multistep solver (heun = %d): use DSG_SOLVER_EULER or DSG_SOLVER_HEUN", DSG_SOLVER_DPMPP_2M);
@@ -4617,9 +4669,9 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
     if (probing && !out_net_trace) return fail(h, DSG_ERR_INVALID, "a probe needs out_net_trace (device, [n_evals = %d, B] doubles)", n_evals);
     hipStream_t s = (hipStream_t)stream;
     const Dims d = dims_of(h, B);
-    const int N = h->N, Ca = h->Ca, Cn = h->Cn, E = h->E;
-    const size_t M0 = (size_t)B * N * N, na = (size_t)B * Ca * N * N, nn = (size_t)B * N * Cn;
-    if (!t_assemble_bwd_ok(Cn) || (size_t)B * N > 0x7fffffffu)
+    const int N = h->N, Ca = h->Ca, Cn = h->Cn, E = h->E, P = h->P;
+    const size_t M0 = (size_t)B * h->R0 * h->R0, na = (size_t)B * Ca * N * N, nn = (size_t)B * N * Cn;
+    if (!(P > 1 ? t_assemble_bwd_patch_ok(Cn) : t_assemble_bwd_ok(Cn)) || (size_t)B * N > 0x7fffffffu)
         return fail(h, DSG_ERR_INVALID, "input gradients are not built for C_node %d (partial sums beyond LDS) or B * N = %zu", Cn, (size_t)B * N);
     const bool heun = solver_heun(cfg);
     const int n_steps = cfg->num_steps - 1;
@@ -4637,7 +4689,7 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
         rows[j] = StepRow{0.f, a, 1.0f / a, 1.0f / b, hs, k, 0.f, 0};
     }
     // buffers: the training entries' io and vjp regions, and this entry's own
-    const int Np = t_live_cols_width(Ca, Cn);
+    const int Np = P > 1 ? t_live_cols_patch_width(Ca, Cn, P) : t_live_cols_width(Ca, Cn);
     TrainIo io;
     TrainInputGrad ig{nullptr, nullptr, Np};
     float *coef = nullptr, *zero = nullptr, *sig_d = nullptr, *tab_f = nullptr, *ctl_f = nullptr, *seeds_f = nullptr;
@@ -4688,7 +4740,8 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
         if (!probing) return;
         t_precond_bwd(ceps.adj, ceps.node, sg, flags, io.dF_a, io.dF_n, coef, B, N, Ca, Cn, s);
         ok = ok && train_backward(net, TRAIN_INPUT_GRADS, flags, CStatePtrs{io.dF_a, io.dF_n}, &ig, s);
-        ok = ok && t_assemble_bwd(ig.d_tok, Np, flags, zero, coef + B, ceps.adj, ceps.node, g.adj, g.node, B, N, Ca, Cn, false, s);
+        ok = ok && (P > 1 ? t_assemble_bwd_patch(ig.d_tok, Np, flags, zero, coef + B, ceps.adj, ceps.node, g.adj, g.node, B, N, P, Ca, Cn, s)
+                          : t_assemble_bwd(ig.d_tok, Np, flags, zero, coef + B, ceps.adj, ceps.node, g.adj, g.node, B, N, Ca, Cn, false, s));
         ok = ok && t_graph_dot(ceps.adj, ceps.node, g.adj, g.node, flags, out_net_trace + (size_t)e * B, B, N, Ca, Cn, s);
     };
     const CStatePtrs cx{x.adj, x.node}, cxp{xp.adj, xp.node}, cD1{D1.adj, D1.node}, cD2{D2.adj, D2.node};
@@ -4710,6 +4763,14 @@ int dsg_ode_run(dsg_handle h, const dsg_sampler_cfg *cfg, const dsg_ode_cfg *ode
     HIP_TRY(h, hipGetLastError());
     return DSG_OK;
 }
+
+int dsg_train_enable_patch(dsg_handle h, int32_t on) {
+    if (!h) return DSG_ERR_INVALID;
+    h->train_patch = on != 0;
+    return DSG_OK;
+}
+
+int32_t dsg_train_patch_enabled(dsg_handle h) { return h ? h->train_patch : 0; }
 
 int dsg_train_set_precision(dsg_handle h, int32_t mode) {
     if (!h) return DSG_ERR_INVALID;

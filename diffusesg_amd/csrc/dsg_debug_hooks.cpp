@@ -484,6 +484,46 @@ int dsg_debug_t_assemble_bwd(int32_t B, int32_t N, int32_t c_adj, int32_t c_node
     return debug_t_finish(t_assemble_bwd(d_tok, ld, flags, c_skip, c_in, g_adj, g_node, out_adj, out_node, B, N, c_adj, c_node, self_cond != 0, s), s);
 }
 
+// ---- the edges of the training form at patch_size > 1 (train_kernels_patch.hip; tests/test_patch_train_kernels.py) ----
+
+int dsg_debug_t_patch_pack(int32_t kind, int32_t unpack, int32_t E, int32_t c_in, int32_t p, int32_t ld, float *W, float *img, const float *bias,
+                           float *bias_rep, void *stream) {
+    if ((kind != DSG_TPACK_PE && kind != DSG_TPACK_RO0) || !W || !img) return DSG_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    bool ok;
+    if (kind == DSG_TPACK_PE) ok = unpack ? t_pe_unpack(img, W, E, c_in, p, ld, s) : t_pe_pack(W, img, E, c_in, p, ld, s);
+    else ok = unpack ? t_ro0_unpack(img, W, E, c_in, p, s) : t_ro0_pack(W, bias, img, bias && bias_rep ? bias_rep : nullptr, E, c_in, p, s);
+    return debug_t_finish(ok, s);
+}
+
+int dsg_debug_t_adj_out_patch(int32_t bwd, int32_t B, int32_t N, int32_t p, int32_t c_adj, const float *oa, const uint8_t *flags, float *F,
+                              const float *dF, float *d_oa, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    return debug_t_finish(t_adj_out_patch(oa, flags, F, dF, d_oa, B, N, p, c_adj, bwd != 0, s), s);
+}
+
+int dsg_debug_t_pool_bwd_patch(int32_t B, int32_t N, int32_t p, int32_t E, const float *d_pool, const uint8_t *flags, float *d_rep_acc,
+                               void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    return debug_t_finish(t_pool_bwd_patch(d_pool, flags, d_rep_acc, B, N, p, E, s), s);
+}
+
+int dsg_debug_t_live_cols_patch(int32_t E, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t p, const float *W, float *img,
+                                int32_t *ld_out, void *stream) {
+    if (c_adj < 1 || c_node < 1 || (p != 1 && p != 2 && p != 4)) return DSG_ERR_INVALID;
+    if (ld_out) *ld_out = t_live_cols_patch_width(c_adj, c_node, p);
+    if (!img) return DSG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    return debug_t_finish(t_live_cols_patch(W, (self_cond ? 2 : 1) * (c_adj + 2 * c_node), p, img, E, c_adj, c_node, self_cond != 0, s), s);
+}
+
+int dsg_debug_t_assemble_bwd_patch(int32_t B, int32_t N, int32_t p, int32_t c_adj, int32_t c_node, const float *d_tok, int32_t ld,
+                                   const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj, const float *g_node,
+                                   float *out_adj, float *out_node, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    return debug_t_finish(t_assemble_bwd_patch(d_tok, ld, flags, c_skip, c_in, g_adj, g_node, out_adj, out_node, B, N, p, c_adj, c_node, s), s);
+}
+
 int dsg_debug_t_grouped(int32_t kind, int32_t n, const dsg_t_prob *probs, float *out, int32_t n_out, void *stream) {
     if (n < 1 || n > T_GROUP_MAX || !probs || kind < DSG_TGROUP_NT || kind > DSG_TGROUP_TT) return DSG_ERR_INVALID;
     TGemmGroup g;

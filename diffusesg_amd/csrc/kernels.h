@@ -622,6 +622,24 @@ void t_live_cols(const float *W, int Cin, float *img, int E, int Ca, int Cn, boo
 bool t_assemble_bwd_ok(int Cn);
 bool t_assemble_bwd(const float *d_tok, int ld, const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj,
                     const float *g_node, float *out_adj, float *out_node, int B, int N, int Ca, int Cn, bool self_cond, hipStream_t s);
+// the edges of the training form at patch_size p in {2, 4} (train_kernels_patch.hip; p = 1 is accepted and gives the p = 1 layouts).
+// Rows of the read-out chain are in (token, a, b) order.  Every launcher returns false on refused arguments, before anything is enqueued.
+// patch_embed.proj.weight [E, Cin, p, p] <-> image [E, Kp], column (a p + b) Cin + c, zero-padded (unpack reads the live columns only)
+int t_pe_image_width(int Cin, int p);
+bool t_pe_pack(const float *W, float *img, int E, int Cin, int p, int Kp, hipStream_t s);
+bool t_pe_unpack(const float *img, float *dW, int E, int Cin, int p, int Kp, hipStream_t s);
+// read_out.0.weight [in, out, p, p] <-> image [in, p^2 out], column (a p + b) out + o; bias_rep [p^2 out] (may be null)
+bool t_ro0_pack(const float *W, const float *bias, float *img, float *bias_rep, int Ei, int Eo, int p, hipStream_t s);
+bool t_ro0_unpack(const float *img, float *dW, int Ei, int Eo, int p, hipStream_t s);
+bool t_adj_out_patch(const float *oa, const uint8_t *flags, float *F, const float *dF, float *d_oa, int B, int N, int p, int Ca, bool bwd,
+                     hipStream_t s);
+bool t_pool_bwd_patch(const float *d_pool, const uint8_t *flags, float *d_rep_acc, int B, int N, int p, int E, hipStream_t s);
+// img [E][t_live_cols_patch_width]: per sub-pixel group (a p + b) the (adj | row node | column node) slots of the current values
+int t_live_cols_patch_width(int Ca, int Cn, int p);
+bool t_live_cols_patch(const float *W, int Cin, int p, float *img, int E, int Ca, int Cn, bool self_cond, hipStream_t s);
+bool t_assemble_bwd_patch_ok(int Cn);
+bool t_assemble_bwd_patch(const float *d_tok, int ld, const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj,
+                          const float *g_node, float *out_adj, float *out_node, int B, int N, int p, int Ca, int Cn, hipStream_t s);
 // out[b] = sum over the live entries of graph b of a_j b_j (adjacency entries whose two nodes are valid, node entries of valid nodes; the
 // flags select, so whatever sits at a padded entry -- t_assemble_bwd leaves anything there -- never reaches the sum), accumulated in
 // float64 in one fixed order by one block per graph: no atomics, and a graph's result depends neither on B nor on its position.

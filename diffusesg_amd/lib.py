@@ -21,7 +21,7 @@ EXPORTS = [
     "dsg_sgstat_f1_rowstats", "dsg_sample_known", "dsg_encode", "dsg_sample_walk", "dsg_walk_steps", "dsg_multistep_coef",
     "dsg_sample_seeded", "dsg_gen_noise_seeded", "dsg_precond_vjp", "dsg_ode_run", "dsg_ode_evals", "dsg_guide_coef", "dsg_sample_guided",
     "dsg_sample_guided_rel", "dsg_sample_guided_content", "dsg_option_info", "dsg_create_patch", "dsg_train_set_precision", "dsg_train_get_precision",
-    "dsg_attach_guide", "dsg_detach_guide", "dsg_guide_info", "dsg_guide_forwards",
+    "dsg_attach_guide", "dsg_detach_guide", "dsg_guide_info", "dsg_guide_forwards", "dsg_train_enable_patch", "dsg_train_patch_enabled",
 ]
 
 TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}   # DSG_TRAIN_F32 / DSG_TRAIN_BF16 of include/dsg.h
@@ -111,6 +111,8 @@ DEBUG_EXPORTS = [
     "dsg_debug_gemm_lp", "dsg_debug_convert", "dsg_debug_row_lp", "dsg_debug_window_attn_lp", "dsg_debug_patch_forms",
     "dsg_debug_assemble_patch_f32", "dsg_debug_head_patch_f32", "dsg_debug_patch_embed_patch_f32", "dsg_debug_readout_patch_f32",
     "dsg_debug_t_gemm_lp", "dsg_debug_t_cast_lp", "dsg_debug_train_routes", "dsg_debug_gemm_bx_args", "dsg_debug_mlp_bx_args",
+    "dsg_debug_t_patch_pack", "dsg_debug_t_adj_out_patch", "dsg_debug_t_pool_bwd_patch", "dsg_debug_t_live_cols_patch",
+    "dsg_debug_t_assemble_bwd_patch",
 ]
 
 
@@ -226,6 +228,11 @@ def _declare_debug(L: C.CDLL) -> None:
     L.dsg_debug_gemm_bx_args.argtypes = [C.POINTER(DsgBxGemmArgs), vp]
     L.dsg_debug_mlp_bx_args.argtypes = [C.POINTER(DsgBxMlpArgs), vp]
     L.dsg_debug_t_assemble_bwd.argtypes = [i32] * 5 + [vp, i32] + [vp] * 8
+    L.dsg_debug_t_patch_pack.argtypes = [i32] * 6 + [vp] * 5
+    L.dsg_debug_t_adj_out_patch.argtypes = [i32] * 5 + [vp] * 6
+    L.dsg_debug_t_pool_bwd_patch.argtypes = [i32] * 4 + [vp] * 4
+    L.dsg_debug_t_live_cols_patch.argtypes = [i32] * 5 + [vp, vp, C.POINTER(i32), vp]
+    L.dsg_debug_t_assemble_bwd_patch.argtypes = [i32] * 5 + [vp, i32] + [vp] * 8
     L.dsg_debug_graph_dot.argtypes = [i32] * 4 + [vp] * 7
     L.dsg_debug_poison.argtypes = [vp, i32, i32, C.c_uint64, vp]
     L.dsg_profile_forward.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
@@ -321,6 +328,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
     L.dsg_train_bind_params.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
     L.dsg_train_set_precision.argtypes = [vp, i32]
     L.dsg_train_get_precision.argtypes = [vp, C.POINTER(i32)]
+    L.dsg_train_enable_patch.argtypes = [vp, i32]
+    L.dsg_train_patch_enabled.argtypes = [vp]
+    L.dsg_train_patch_enabled.restype = i32
     L.dsg_attach_guide.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float]
     L.dsg_detach_guide.argtypes = [vp]
     L.dsg_guide_info.argtypes = [vp, C.POINTER(vp)] + [C.POINTER(C.c_float)] * 3
@@ -447,6 +457,14 @@ class Handle:
         v = C.c_int32(0)
         self.check(self.L.dsg_train_get_precision(self._h, C.byref(v)), "dsg_train_get_precision")
         return {m: name for name, m in TRAIN_PRECISIONS.items()}[int(v.value)]
+
+    def enable_patch_training(self, on: bool = True):
+        """The training form at patch_size > 1 (dsg_train_enable_patch): off by default, a no-op at patch_size 1.  The Python training,
+        input-gradient and ODE entry points call it themselves: calling them is the opt-in."""
+        self.check(self.L.dsg_train_enable_patch(self._h, 1 if on else 0), "dsg_train_enable_patch")
+
+    def patch_training_enabled(self) -> bool:
+        return bool(self.L.dsg_train_patch_enabled(self._h))
 
     def attach_guide(self, guide: "Handle", scale: float, sigma_lo: float, sigma_hi: float):
         """Autoguidance (dsg_attach_guide): `guide` becomes this handle's weaker network, D~ = D + (scale - 1)(D - D_guide) at the noise

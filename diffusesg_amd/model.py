@@ -242,6 +242,8 @@ class NodeAdjPrecondHip(nn.Module):
             raise ValueError("value_and_input_grad: give exactly one of loss_fn and grad_outputs")
         m = self.model
         h = m._ensure_handle()
+        if int(getattr(h.cfg, "patch_size", 1)) > 1:
+            h.enable_patch_training()   # calling this is the opt-in to the training form at patch_size > 1
         B, a, x, fl, sa, sx = m._canon(adjs, nodes, node_flags, self_cond_adjs, self_cond_nodes)
         if (sa is None) != (sx is None):
             raise ValueError("value_and_input_grad: self_cond_adjs and self_cond_nodes go together")

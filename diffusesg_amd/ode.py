@@ -68,6 +68,8 @@ def run(net, sampler, adjs, nodes, node_flags, direction: str, probe: str = "non
     pre = _net(net)
     m = pre.model
     h = m._ensure_handle()
+    if int(getattr(h.cfg, "patch_size", 1)) > 1:
+        h.enable_patch_training()   # calling this is the opt-in to the training form at patch_size > 1
     scfg, ocfg, t_eval, _w, _, _ = _plan(sampler, direction, probe)
     B, a, x, fl, pa, px = m._canon(adjs, nodes, node_flags, None if probes is None else probes[0], None if probes is None else probes[1])
     gs = None if graph_seeds is None else check_graph_seeds(graph_seeds, B)

@@ -462,3 +462,83 @@ def autoguide_precond_case(si: int):
     """inputs of the fixture's composite calls at PRECOND_SIGMAS[si]: sigma, flags, adj, node, sc_adj, sc_node"""
     sigma = PRECOND_SIGMAS[si]
     return (sigma,) + case_inputs(S.tiny_config(), 3, AUTOGUIDE_VALID, 6, f"autoguide/pre/{si}", sigma_scale=float(np.sqrt(sigma ** 2 + 0.25)))
+
+
+# ---- the training form at patch_size > 1 (tests/golden/train_patch.npz, tools/gen_patch_train_golden.py; DESIGN.md §15) -----------
+# training cases: case -> (PATCH_CONFIGS name, valid nodes per graph (B = 4), the self-conditioning coin: 0.9 does not fire, 0.3 fires so
+# that the detached self-conditioning pass feeds the differentiated one).  Odd valid counts put a token with a single valid pixel row
+# in every case.
+PATCH_TRAIN_CASES = {
+    "tiny_p2": ("tiny_p2", [8, 5, 3, 6], 0.9),
+    "tiny_p2_sc": ("tiny_p2", [8, 5, 3, 6], 0.3),
+    "small_p4_sc": ("small_p4", [16, 9, 3, 11], 0.3),
+    "nosc_p2": ("nosc_p2", [8, 5, 3, 6], 0.9),
+}
+PATCH_TRAIN_MAX_SAMPLE = 256     # stored gradient elements per tensor (every stride-th, train_backward.npz's format)
+PATCH_TRAIN_ADAM_CASE = "tiny_p2"   # the case whose parameters after the reference's Adam step are stored
+# the tensors whose gradients the fixture also stores whole for PATCH_TRAIN_ADAM_CASE, with the activations around them (CPU test)
+PATCH_TRAIN_EDGE_PARAMS = ("patch_embed.proj.weight", "patch_embed.proj.bias", "read_out.0.weight", "read_out.0.bias")
+
+
+def patch_train_case(case: str, seed: int = 7):
+    """train_case's tuple for a case of PATCH_TRAIN_CASES (with one node channel, `nosc_p2`, that channel holds the box values)"""
+    cfg_name, valid, coin = PATCH_TRAIN_CASES[case]
+    cfg = PATCH_CONFIGS[cfg_name]()
+    B, n = len(valid), cfg.max_node_num
+    flags = W.synth_flags(B, n, valid)
+    tag = f"trnp/{cfg_name}"
+    clean_adj = W.mask_adj(np.sign(W.normal(seed, f"{tag}/adj", (B, cfg.c_adj, n, n))).astype(np.float32), flags)
+    node = np.sign(W.normal(seed, f"{tag}/node", (B, n, cfg.c_node))).astype(np.float32)
+    nb = min(4, cfg.c_node)
+    node[..., -nb:] = (2.0 * W.uniform01(seed, f"{tag}/bbox", B * n * nb) - 1.0).astype(np.float32).reshape(B, n, nb) * 0.8
+    clean_node = W.mask_node(node, flags)
+    rnd = W.normal(seed, f"{tag}/rnd", (B,))
+    eps_adj = W.normal(seed, f"{tag}/eps_adj", (B, cfg.c_adj, n, n))
+    eps_node = W.normal(seed, f"{tag}/eps_node", (B, n, cfg.c_node))
+    return cfg, flags, clean_adj, clean_node, rnd, eps_adj, eps_node, coin
+
+
+# input-gradient cases, INPUT_GRAD_CASES' recipe: tag -> (PATCH_CONFIGS name, valid nodes, sigmas, self-conditioning given, cotangent)
+PATCH_INPUT_GRAD_CASES = {
+    "tiny_p2_sc": ("tiny_p2", [8, 5, 3], [80.0, 1.5, 0.002], True, "gen"),
+    "small_p4": ("small_p4", [16, 9], [1.5, 0.3], True, "gen"),
+    "tiny_p2_overlap": ("tiny_p2", [8, 5, 3], [1.5, 0.6, 0.2], True, "overlap"),
+}
+PATCH_INPUT_GRAD_EDGE_CASE = "tiny_p2_sc"   # the case whose gradient at PatchEmbed's output is stored (CPU test of the assembly backward)
+
+
+def patch_input_grad_case(tag: str, seed: int = 29):
+    """input_grad_case's tuple (without the stride) for a case of PATCH_INPUT_GRAD_CASES"""
+    name, valid, sigmas, with_sc, cot = PATCH_INPUT_GRAD_CASES[tag]
+    cfg = PATCH_CONFIGS[name]()
+    B, n = len(valid), cfg.max_node_num
+    sig = np.asarray(sigmas, np.float32)
+    flags, adj, node, sc_adj, sc_node = case_inputs(cfg, B, valid, seed, f"igradp/{tag}")
+    scale = np.sqrt(sig.astype(np.float64) ** 2 + 0.25).astype(np.float32)
+    adj = (adj * scale[:, None, None, None]).astype(np.float32)
+    node = (node * scale[:, None, None]).astype(np.float32)
+    if not with_sc:
+        sc_adj = sc_node = None
+    g_adj = g_node = None
+    if cot == "gen":
+        g_adj = W.normal(seed, f"igradp/{tag}/g_adj", (B, cfg.c_adj, n, n))
+        g_node = W.normal(seed, f"igradp/{tag}/g_node", (B, n, cfg.c_node))
+    return cfg, flags, adj, node, sig, sc_adj, sc_node, g_adj, g_node
+
+
+# the ODE case, ode_case's recipe: tiny_p2 with no self-conditioning input, a recorded probe, Heun at the fixture's smallest step count
+PATCH_ODE_NET, PATCH_ODE_VALID, PATCH_ODE_RUN = "tiny_p2", [8, 5, 3], (8, "heun")
+
+
+def patch_ode_case(seed: int = 37):
+    """cfg, flags, adj, node (+-1 at live entries, 0 at padded ones), probe_adj, probe_node (the same)"""
+    cfg = PATCH_CONFIGS[PATCH_ODE_NET]()
+    B, n = len(PATCH_ODE_VALID), cfg.max_node_num
+    flags = W.synth_flags(B, n, PATCH_ODE_VALID)
+    sign = lambda x: np.where(x >= 0, np.float32(1), np.float32(-1)).astype(np.float32)
+    tag = f"odep/{PATCH_ODE_NET}"
+    adj = W.mask_adj(sign(W.normal(seed, f"{tag}/adj", (B, cfg.c_adj, n, n))), flags)
+    node = W.mask_node(sign(W.normal(seed, f"{tag}/node", (B, n, cfg.c_node))), flags)
+    p_adj = W.mask_adj(sign(W.normal(seed, f"{tag}/probe_adj", (B, cfg.c_adj, n, n))), flags)
+    p_node = W.mask_node(sign(W.normal(seed, f"{tag}/probe_node", (B, n, cfg.c_node))), flags)
+    return cfg, flags, adj, node, p_adj, p_node

@@ -262,10 +262,13 @@ def _flat_layout(m):
 
 def _train_handle(m):
     """The handle for the training-form entries: the parameters are read IN PLACE (dsg_train_bind_params) when they live on the
-    device -- no upload per iteration; only the very first call pays for dsg_finalize_weights (block plans)."""
+    device -- no upload per iteration; only the very first call pays for dsg_finalize_weights (block plans).  On a patch_size > 1
+    handle the training form is switched on (lib.Handle.enable_patch_training): calling a training entry point is the opt-in."""
     if m._handle is None:
         m._ensure_handle()
     h = m._handle
+    if int(getattr(h.cfg, "patch_size", 1)) > 1:
+        h.enable_patch_training()
     params = [(k, p_) for k, p_ in m.named_parameters()]
     if all(p_.is_cuda and p_.dtype == torch.float32 and p_.is_contiguous() for _, p_ in params):
         sig = tuple(p_.data_ptr() for _, p_ in params)

@@ -109,8 +109,8 @@ int dsg_create(const dsg_config *cfg, dsg_handle *out);   /* == dsg_create_patch
  * "gemm_split", "gemm_bf16" and "batch_invariant" are refused (dsg_set_option keeps the old value; a handle created under such an
  * environment default is refused by its first forward until the option is set to 0); "fused_patch_embed" / "fused_readout" select the
  * fused E = 96 kernels at p = 2 (in_chans <= 64, C_adj <= 32; default) or the chain of kernels, p = 4 always runs the chain; and
- * dsg_train_grads,
- * dsg_train_step_grads, dsg_train_self_cond, dsg_precond_vjp and dsg_ode_run return DSG_ERR_INVALID (messages name patch_size). */
+ * dsg_train_grads, dsg_train_step_grads, dsg_train_self_cond, dsg_precond_vjp and dsg_ode_run return DSG_ERR_INVALID (messages name
+ * patch_size) until dsg_train_enable_patch switches the training form on for the handle. */
 int dsg_create_patch(const dsg_config *cfg, int32_t patch_size, dsg_handle *out);
 void dsg_destroy(dsg_handle h);
 /* h == NULL: the reason the last dsg_create on the calling thread failed (there is no handle to ask then) */
@@ -776,12 +776,26 @@ int dsg_train_bind_params(dsg_handle h, int32_t n_params, const char *const *nam
  *   The parameters are read in place and may change between calls, so every entry call in this mode re-rounds the covered weights into
  *   handle-owned bf16 planes (both orientations) before its first product; nothing is cached across calls.
  * dsg_train_set_precision: DSG_ERR_INVALID for any other value, the old mode kept.  Handles with patch_size > 1 accept the setter and
- *   keep refusing the training entries.  No trained weights exist for this model offline: nothing is claimed about the convergence or
+ *   keep refusing the training entries (with dsg_train_enable_patch on as well: the bf16 products are not built at patch_size > 1).  No trained weights exist for this model offline: nothing is claimed about the convergence or
  *   the quality of models trained in this mode. */
 #define DSG_TRAIN_F32  0   /* default */
 #define DSG_TRAIN_BF16 1
 int dsg_train_set_precision(dsg_handle h, int32_t mode);
 int dsg_train_get_precision(dsg_handle h, int32_t *mode);
+
+/* The training form at patch_size > 1 (dsg_create_patch with p in {2, 4}): handle state, OFF by default -- a fresh handle refuses
+ * dsg_train_grads, dsg_train_step_grads, dsg_train_self_cond, dsg_precond_vjp and dsg_ode_run as the first check of each entry, with a
+ * message naming the entry, patch_size and this function.  on != 0 switches it on, 0 off again; accepted at any patch size and without
+ * effect at patch_size 1 (the same bits either way).  Setting it enqueues nothing and touches neither the options nor the packed weights.
+ * Once on, the five entries compute at p > 1 what they compute at p = 1, on R x R tokens (R = N / p): the raw weights are read in place
+ * in the reference's layouts -- patch_embed.proj.weight [E, Cin, p, p], read_out.0.weight [E, E, p, p] ([in, out, a, b]) -- and packed
+ * per call into weight images; their gradients arrive in those layouts; every mask is per pixel (flag_I && flag_J), the node mean is
+ * over the N pixels of a row, exact zeros at masked entries of the outputs, of dL/dF and of the node gradient.
+ * fp32 only: with dsg_train_set_precision(h, DSG_TRAIN_BF16) the five entries return DSG_ERR_INVALID with a message naming both
+ * settings.  Still refused at p > 1 whatever this is: "gemm_split", "gemm_bf16", "batch_invariant"; pruning and deduplication stay off.
+ * dsg_train_patch_enabled: the stored value (0 for a NULL handle). */
+int dsg_train_enable_patch(dsg_handle h, int32_t on);
+int32_t dsg_train_patch_enabled(dsg_handle h);
 
 /* ---- Autoguidance (Karras et al. 2024, "Guiding a diffusion model with a bad version of itself") ----
  * A main handle h can have a second, weaker network -- the guide handle -- attached, with a scale s and a noise-level interval

@@ -457,6 +457,36 @@ int dsg_debug_t_colsum(const float *X, int32_t ld, float *out, int32_t M, int32_
 int dsg_debug_t_assemble_bwd(int32_t B, int32_t N, int32_t c_adj, int32_t c_node, int32_t self_cond, const float *d_tok, int32_t ld,
                              const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj, const float *g_node,
                              float *out_adj, float *out_node, void *stream);
+/* ---- the edges of the training form at patch_size p in {2, 4} on their own (csrc/train_kernels_patch.hip; p = 1 is accepted).  Token
+ * t = ti R + tj, R = N / p, covers the pixels (I, J) = (p ti + a, p tj + b); rows "in (token, a, b) order": m = (graph R^2 + t) p^2 + a p + b.
+ * Every hook returns DSG_ERR_INVALID for a refused shape before anything is enqueued. */
+/* kind DSG_TPACK_PE: W [E, c_in, p, p] (patch_embed.proj.weight) <-> img [E, ld], column (a p + b) c_in + c, ld >= p^2 c_in; pack writes
+ * zeros from p^2 c_in up to ld, unpack never reads there.  kind DSG_TPACK_RO0: W [E, c_in, p, p] (read_out.0.weight, [in, out, p, p] with
+ * out = c_in) <-> img [E, p^2 c_in], column (a p + b) c_in + o (ld is ignored); pack also writes bias_rep [p^2 c_in] from bias [c_in] when
+ * both are given.  unpack != 0: img -> W. */
+enum { DSG_TPACK_PE = 0, DSG_TPACK_RO0 = 1 };
+int dsg_debug_t_patch_pack(int32_t kind, int32_t unpack, int32_t E, int32_t c_in, int32_t p, int32_t ld, float *W, float *img,
+                           const float *bias, float *bias_rep, void *stream);
+/* bwd == 0: F[b, c, I, J] = flag_I && flag_J ? oa[m][c] : 0 from oa [B N N, c_adj] in (token, a, b) order; bwd != 0 the transpose:
+ * d_oa[m][c] = flag_I && flag_J ? dF[b, c, I, J] : 0.  Exact copies and exact zeros. */
+int dsg_debug_t_adj_out_patch(int32_t bwd, int32_t B, int32_t N, int32_t p, int32_t c_adj, const float *oa, const uint8_t *flags, float *F,
+                              const float *dF, float *d_oa, void *stream);
+/* d_rep[m][e] += flag_I && flag_J ? d_pool[(b, I)][e] / N : 0, d_rep [B N N, E] in (token, a, b) order, d_pool [B N, E] */
+int dsg_debug_t_pool_bwd_patch(int32_t B, int32_t N, int32_t p, int32_t E, const float *d_pool, const uint8_t *flags, float *d_rep_acc,
+                               void *stream);
+/* img [E, ld], ld = (p^2 G rounded up to 32), G = c_adj + 2 c_node: column (a p + b) G + slot holds W[e, src(slot), a, b], src the
+ * current-value channel of the slot in the assembly's order (adj | node of the row | node of the column), zeros behind p^2 G.
+ * W [E, c_in, p, p] with c_in = (self_cond ? 2 : 1) G.  *ld_out (host, may be NULL) receives ld; img == NULL only reports it. */
+int dsg_debug_t_live_cols_patch(int32_t E, int32_t c_adj, int32_t c_node, int32_t self_cond, int32_t p, const float *W, float *img,
+                                int32_t *ld_out, void *stream);
+/* dsg_debug_t_assemble_bwd at patch_size p: d_tok [B R^2, ld] holds per token the p^2 groups of dsg_debug_t_live_cols_patch (columns
+ * behind p^2 G are never read); pixel (I, J) reads group (I mod p) p + J mod p of token (I / p, J / p):
+ *   out_adj[b,c,I,J] = c_skip_b m_I m_J g_adj[b,c,I,J] + c_in_b d_tok[pixel (I, J)][c]
+ *   out_node[b,I,c]  = m_I (c_skip_b g_node[b,I,c] + c_in_b (sum_J m_J d_tok[pixel (I, J)][c_adj + c] + sum_J m_J d_tok[pixel (J, I)][c_adj + c_node + c]))
+ * No atomics, one summation order; out_* may alias g_*; node values of padded nodes are never read. */
+int dsg_debug_t_assemble_bwd_patch(int32_t B, int32_t N, int32_t p, int32_t c_adj, int32_t c_node, const float *d_tok, int32_t ld,
+                                   const uint8_t *flags, const float *c_skip, const float *c_in, const float *g_adj, const float *g_node,
+                                   float *out_adj, float *out_node, void *stream);
 /* up to 32 small problems in one launch.  kind: DSG_TGROUP_NT / TN / NN: C_z = op(A_z) op(B_z) (+ bias_z); NN_SUM: ONE C = sum_z A_z B_z
  * (shared M, N, C; bias of problem 0); SUM: out[i] = sum_z C_z[i], i < n_out; COLSUM: C_z[n] = sum_m A_z[m lda + n]; TT is not built
  * and is refused. */
